@@ -42,6 +42,16 @@ labelled with the file and build it came from.
 cpu_baseline: the reference's own compute_flux_edge (oracle/_ref, built from the reference sources) — or the C oracle
 port when that build is absent — timed on one host core on the same mesh for a bounded number of passes; beside it the
 all-cores figure (the reference's race-free way to use threads: one private mesh copy per thread, its -m).
+
+Plain run and --full: a plain run does only what `value` needs — set-up, an untimed ramp of the flux kernel (it leaves the
+state alone), the untimed preheat sweeps, the W warm-up and K timed steps — and prints the line with `metric`, `value`,
+`unit`, `higher_is_better`, `dtype` and `ms_per_step`.  `metric` names BASELINE's two-part metric as it always has; its V-cycle
+half (`vcycle`) and every other figure that takes runs of its own — `roofline` (with `two_launches_in_flight` and
+`mixed_mesh`), `cpu_baseline`, and at N > 1 the `rank_graphs` and `in_process_group` legs — are measured only with --full.
+--dump-outputs DIR: after the timed steps, the arrays the timed step leaves for its caller are written as DIR/<name>.npy in
+float64 — `variables`, `residuals`, `step_factors` of the swept level (a level-per-gpu step: `variables_level<l>` of every
+level this rank holds; at N > 1 rank 0's arrays, its owned nodes); beyond 64 MB in all, the same seeded sample of rows of
+each.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -67,6 +77,7 @@ HIERARCHY_8X = (134, 110, 96, 86)   # the same hierarchy tiled 8x (connected): 2
 TRAFFIC_PROFILE = os.path.join("profiles", "r4_traffic.json")
 ROOFLINE_LAUNCHES = 1000     # back-to-back launches of the standalone flux kernel / of its data-movement probe per measurement
 PREHEAT_SWEEPS = 1000           # untimed sweeps in front of a short timed region (see main)
+DUMP_BYTES_MAX = 64 << 20       # --dump-outputs writes at most this much
 
 
 def build_workload(lattice: int, seed: int = 0, mesh: str = "lattice"):
@@ -147,6 +158,20 @@ def perturbed_state(nel, ff_var, seed=1234, amplitude=0.01):
     rng = np.random.default_rng(seed)
     base = np.tile(np.asarray(ff_var, dtype=np.float64), (nel, 1))
     return base * (1.0 + amplitude * rng.uniform(-1.0, 1.0, base.shape))
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: every array as <directory>/<name>.npy in float64.  Arrays larger together than DUMP_BYTES_MAX are cut
+    to the same seeded sample of rows (in row order; arrays of equal length keep the same rows)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES_MAX - 1024 * len(arrays)               # (room for the .npy headers)
+    for name, a in arrays.items():
+        if total > budget:
+            keep = max(1, len(a) * budget // total)
+            a = a[np.sort(np.random.default_rng(seed).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def cpu_model():
@@ -709,6 +734,11 @@ def main():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="start the ranks, rendezvous, build the host-side partition and print the line without touching a GPU "
                          "(value null): what the CPU-side test of the N > 1 launcher runs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, every other figure of the line: roofline, V-cycle, CPU baseline and, at N > 1, the "
+                         "rank_graphs and in-process group legs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed step leaves for its caller as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -1142,30 +1172,31 @@ def main():
         # driver's default of 5 warm-up steps is 0.3 ms.  The line says so in "preheat".
         # (first of all — it builds and frees a second solver, half a second of idle device — what the kernel does with two
         #  independent launches in flight: roofline.two_launches_in_flight)
-        if workload == "level0" and world == 1 and args.variant == -1 and not args.no_two_in_flight and os.environ.get("MGCFD_BENCH_NO_TWO_IN_FLIGHT") != "1":
+        if args.full and workload == "level0" and world == 1 and args.variant == -1 and not args.no_two_in_flight and os.environ.get("MGCFD_BENCH_NO_TWO_IN_FLIGHT") != "1":
             two_in_flight = two_launches_in_flight(solver, levels, mg.mesh_variant, local_rank, args.fast)
-        solver.bench_flux(0, 2 * ROOFLINE_LAUNCHES)             # (untimed: the ramp itself)
-        flux_only = solver.bench_flux(0, ROOFLINE_LAUNCHES)
+        solver.bench_flux(0, 2 * ROOFLINE_LAUNCHES)             # (untimed: the ramp itself; in a plain run the only flux launches here)
         flux_contracted = flux_free = None
-        if not args.fast:
-            # the same launch with FMA contraction allowed (MGCFD_OPT_EXACT = 0: results within 1e-12 relative of the reference's,
-            # tests/test_gpu_parity.py REL_FAST; north_star's bound is 1e-10) — reported beside the bit-identical figure, never as it
-            solver.set_option("exact", 0)
-            if args.variant == -1:
-                solver.set_option("flux_variant", 1)                # (the node gather: auto would take the order-free kernel in this mode)
-            solver.bench_flux(0, ROOFLINE_LAUNCHES)                 # (untimed: the first batch after the switch reads 1 % slower)
-            flux_contracted = solver.bench_flux(0, ROOFLINE_LAUNCHES)
-            # ... and with ORDER-FREE accumulation on top (k_flux_free, variant bit 6, the contracted namespace only: every edge of a
-            # tile evaluated once, the other end's share added to its LDS sum with ds_add_f64; tests/test_gpu_order_free.py)
-            if args.variant == -1 and solver.has_order_free(0):
-                solver.set_option("flux_variant", 65)
-                solver.bench_flux(0, ROOFLINE_LAUNCHES)
-                flux_free = solver.bench_flux(0, ROOFLINE_LAUNCHES)
-                solver.set_option("flux_variant", args.variant)
-            solver.set_option("exact", 1)
-        probe = solver.bench_indirect_rw(0, ROOFLINE_LAUNCHES) if hasattr(solver, "bench_indirect_rw") else None
-        # ... and a tile-shaped STREAM of exactly the algorithmic bytes (one workgroup per tile, nothing dependent, nothing computed)
-        stream_ceiling = solver.bench_stream_ceiling(0, ROOFLINE_LAUNCHES)
+        if args.full:                                           # (the roofline figures: a plain run has only the ramp above)
+            flux_only = solver.bench_flux(0, ROOFLINE_LAUNCHES)
+            if not args.fast:
+                # the same launch with FMA contraction allowed (MGCFD_OPT_EXACT = 0: results within 1e-12 relative of the reference's,
+                # tests/test_gpu_parity.py REL_FAST; north_star's bound is 1e-10) — reported beside the bit-identical figure, never as it
+                solver.set_option("exact", 0)
+                if args.variant == -1:
+                    solver.set_option("flux_variant", 1)                # (the node gather: auto would take the order-free kernel in this mode)
+                solver.bench_flux(0, ROOFLINE_LAUNCHES)                 # (untimed: the first batch after the switch reads 1 % slower)
+                flux_contracted = solver.bench_flux(0, ROOFLINE_LAUNCHES)
+                # ... and with ORDER-FREE accumulation on top (k_flux_free, variant bit 6, the contracted namespace only: every edge of a
+                # tile evaluated once, the other end's share added to its LDS sum with ds_add_f64; tests/test_gpu_order_free.py)
+                if args.variant == -1 and solver.has_order_free(0):
+                    solver.set_option("flux_variant", 65)
+                    solver.bench_flux(0, ROOFLINE_LAUNCHES)
+                    flux_free = solver.bench_flux(0, ROOFLINE_LAUNCHES)
+                    solver.set_option("flux_variant", args.variant)
+                solver.set_option("exact", 1)
+            probe = solver.bench_indirect_rw(0, ROOFLINE_LAUNCHES) if hasattr(solver, "bench_indirect_rw") else None
+            # ... and a tile-shaped STREAM of exactly the algorithmic bytes (one workgroup per tile, nothing dependent, nothing computed)
+            stream_ceiling = solver.bench_stream_ceiling(0, ROOFLINE_LAUNCHES)
         solver.zero_fluxes(0)                                   # (the sweeps start from zero fluxes, as after any time_step)
         # A short timed region (the driver's 20 steps are 1.1 ms) would otherwise run before the device has settled under THIS
         # kernel: after the flux launches above the first few hundred sweeps still take 57.6-60 us against 55.2 in the steady state
@@ -1239,6 +1270,13 @@ def main():
     rc, bad = solver.check_for_invalid_variables(0)
     if rc != 0:
         raise SystemExit(f"state became invalid during the bench (code {rc}, cell {bad})")
+    if args.dump_outputs and rank == 0:
+        if workload == "level-per-gpu":
+            dumped = {f"variables_level{l}": solver.get(l, "variables") for l in range(solver.num_levels) if l % world == rank}
+        else:
+            n_rows = P.n_owned if workload == "partitioned" else solver.nel(0)
+            dumped = {name: solver.get(0, name)[:n_rows] for name in ("variables", "residuals", "step_factors")}
+        dump_outputs(args.dump_outputs, dumped)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -1248,7 +1286,9 @@ def main():
     out = None
     if rank == 0:
         out = {
-            "metric": "Medges/s (compute_flux_edge)" + (" + MG V-cycle wall-s" if workload == "level0" and not args.no_vcycle else ""),
+            # (BASELINE's two-part metric, named as before whether or not this run measures the V-cycle half: that takes --full)
+            "metric": "Medges/s (compute_flux_edge)" + (" + MG V-cycle wall-s" if (workload == "level0" or (world > 1 and workload == "partitioned"))
+                                                        and not args.no_vcycle else ""),
             "value": round(edges_per_step_all_ranks * args.steps / elapsed / 1e6, 3),
             "unit": "Medges/s",
             "n_gpus": world,
@@ -1264,7 +1304,7 @@ def main():
         }
         if workload == "level-per-gpu":
             out["vcycle"] = {"wall_s_per_cycle": round(elapsed / args.steps, 9), "flux_edge_iterations_per_cycle": edges_per_step_all_ranks}
-    if workload in ("level0", "copies"):
+    if args.full and workload in ("level0", "copies"):
         if rank == 0:
             bytes_flux = 40 * n_int + 80 * nel                  # compute_flux_edge
             bytes_ts = 168 * nel                                # time_step
@@ -1345,19 +1385,19 @@ def main():
                                        "traffic": stage_traffic,
                                        "traffic_over_bytes_a_fused_stage_must_move": round(stage_traffic / (40 * n_int + 128 * nel), 3) if stage_traffic else None}
             out["roofline"] = roof
-    if workload == "partitioned" and world > 1 and not args.no_rank_graphs and not args.rank_graphs and (library_passed[0] or (rehearsal and injected("rank-graphs-rehearsal"))):
+    if args.full and workload == "partitioned" and world > 1 and not args.no_rank_graphs and not args.rank_graphs and (library_passed[0] or (rehearsal and injected("rank-graphs-rehearsal"))):
         with leg_guard(float(os.environ.get("MGCFD_BENCH_LEG_S", "420")), rank, out, "rank_graphs", "the RCCL ranks' sweeps replayed from hipGraphs"):
             graphs_rec = rank_graphs_leg()
         if rank == 0:
             out["rank_graphs"] = graphs_rec
     solver.close()
-    if rank == 0 and world == 1 and workload == "level0" and args.mesh == "lattice" and lattice == LATTICE and not args.no_vcycle and "roofline" in out:
+    if args.full and rank == 0 and world == 1 and workload == "level0" and args.mesh == "lattice" and lattice == LATTICE and not args.no_vcycle and "roofline" in out:
         out["roofline"]["mixed_mesh"] = mixed_mesh_roofline(make_solver, args.fast)
     if world > 1:
         dist.barrier()
     vc_sizes = {"8x": HIERARCHY_8X, "base": HIERARCHY, "tiny": (20, 12, 8, 6)}[args.vcycle_hierarchy]
     kept = [] if (rank == 0 and not args.no_group) else None
-    if world > 1 and workload in ("partitioned", "partitioned-mg") and not args.no_vcycle:
+    if args.full and world > 1 and workload in ("partitioned", "partitioned-mg") and not args.no_vcycle:
         # the second half of BASELINE's metric on N GPUs: every level of the hierarchy partitioned, the cycle inside the library.
         # (guarded: nothing of it has run on several GPUs yet, and the sweeps' figure must survive whatever it does)
         with leg_guard(float(os.environ.get("MGCFD_BENCH_LEG_S", "420")), rank, out, "vcycle", "the V-cycle leg on the partitioned hierarchy"):
@@ -1365,7 +1405,7 @@ def main():
         if rank == 0:
             out["vcycle"] = vc
             out["metric"] = "Medges/s (compute_flux_edge) + MG V-cycle wall-s"
-    if world > 1 and workload in ("partitioned", "partitioned-mg") and not args.no_group:
+    if args.full and world > 1 and workload in ("partitioned", "partitioned-mg") and not args.no_group:
         # beside the RCCL ranks' figure, never as it: the SAME level and hierarchy swept by ONE process over all N devices (the
         # in-process group the drop-in binary runs).  Rank 0 runs it while the other ranks — their solvers closed — wait on the
         # rendezvous store, not in a collective (a barrier kernel would spin on the devices being measured).
@@ -1386,9 +1426,9 @@ def main():
                 import datetime
                 store.wait(["mgcfd_group_leg_done"], datetime.timedelta(seconds=float(os.environ.get("MGCFD_BENCH_LEG_S", "420")) + 120.0))
     if rank == 0:
-        if world == 1 and workload == "level0" and not args.no_vcycle:
+        if args.full and world == 1 and workload == "level0" and not args.no_vcycle:
             out["vcycle"] = vcycle_wall(args.fast, device=local_rank)
-        if args.cpu_seconds > 0 and world == 1 and workload == "level0":
+        if args.full and args.cpu_seconds > 0 and world == 1 and workload == "level0":
             out["cpu_baseline"] = cpu_baseline(levels, args.cpu_seconds)
         print(json.dumps(out))
         sys.stdout.flush()

@@ -344,7 +344,7 @@ def test_cfg4_one_level_per_solver_at_full_size(oracle):
 
 
 def test_bench_line_at_the_drivers_arguments():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` — what the driver runs — prints ONE JSON line with the contract's
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` — the driver's arguments with every figure — prints ONE JSON line with the contract's
     fields: BASELINE's metric and unit, whole-job value, steps / warmup echoed, the roofline object of the flux kernel
     (HBM bound, achieved / peak / frac consistent, traffic named with the profile it came from), the V-cycle leg and the
     CPU baseline of the same level (bounded sample)."""
@@ -357,7 +357,7 @@ def test_bench_line_at_the_drivers_arguments():
     #  halves the figure.  The figure's lower bound below is there to catch a sweep that silently left the fused path, so a
     #  run below it is repeated once before it counts.)
     for attempt in range(2):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2"],
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--full"],
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -400,6 +400,48 @@ def test_bench_line_at_the_drivers_arguments():
     assert 1 <= mt["threads"] <= mt["cores_usable_by_this_process"] and mt["value"] > cpu["value"]
 
 
+def test_bench_plain_line_and_its_outputs(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps 20 --warmup 5` times the steps and nothing else: the contract's fields, no
+    figure that takes runs of its own.  With --dump-outputs it writes the swept level's arrays, the same bits from run to
+    run, and they are the state the same sweeps leave when run directly from the bench's start state (1,000 preheat sweeps,
+    as the line's steps are fewer than 1,000, + W + K)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    import mgcfd
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["metric"] == "Medges/s (compute_flux_edge) + MG V-cycle wall-s" and line["unit"] == "Medges/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f64" and line["steps"] == 20 and line["warmup"] == 5 and line["n_gpus"] == 1
+        assert line["value"] > 0 and abs(line["value"] - 3 * 888822 / (line["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * line["value"]
+        assert not {"roofline", "vcycle", "cpu_baseline"} & set(line)
+        files = sorted(os.listdir(d))
+        assert files == ["residuals.npy", "step_factors.npy", "variables.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float64 and np.isfinite(a).all()
+        _bits_equal(dumps[1][name], a, f"{name}: second run")
+    mg, levels = bench.build_workload(bench.LATTICE)
+    s = mgcfd.Solver.from_arrays(levels, mg.mesh_variant)
+    s.set(0, "variables", bench.perturbed_state(s.nel(0), s.far_field()[:5]))
+    s.smooth(0, bench.PREHEAT_SWEEPS + 5 + 20)
+    assert dumps[0]["variables"].shape == (300763, 5) and dumps[0]["step_factors"].shape == (300763,)
+    for name, a in dumps[0].items():
+        _bits_equal(a, s.get(0, name), f"{name}: against the same sweeps run directly")
+    s.close()
+
+
 def test_bench_rehearsal_two_ranks_on_this_gpu():
     """`python bench.py --gpus 2` from a plain invocation starts two ranks itself (here both on device 0 with gloo
     collectives: MGCFD_BENCH_REHEARSAL=1, a functional rehearsal of the N > 1 path, not a measurement) and reports
@@ -412,7 +454,7 @@ def test_bench_rehearsal_two_ranks_on_this_gpu():
     env = dict(os.environ, MGCFD_BENCH_REHEARSAL="1")
     for extra, kind, scaling in ((["--lattice", "30", "--vcycle-hierarchy", "tiny"], "partitioned", "strong"), (["--workload", "copies", "--lattice", "24"], "copies", "weak"),
                                  (["--lattice", "30", "--exchange", "ipc", "--no-vcycle"], "partitioned", "strong")):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"] + extra,
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"] + extra,
                            capture_output=True, text=True, env=env, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -450,7 +492,7 @@ def test_bench_form_ladder_survives_injected_failures(fail, expect):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MGCFD_BENCH_REHEARSAL="1", MGCFD_BENCH_FAIL=fail, MGCFD_BENCH_WATCHDOG_S="240", MGCFD_BENCH_LEG_S="200")
     legs = ["--vcycle-hierarchy", "tiny", "--no-group"] if fail.startswith("vcycle") else (["--no-vcycle"] if fail.startswith("group") else ["--no-vcycle", "--no-group"])
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--lattice", "30"] + legs,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--lattice", "30", "--full"] + legs,
                        capture_output=True, text=True, env=env, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -513,7 +555,7 @@ def test_bench_in_process_group_leg_on_this_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MGCFD_BENCH_REHEARSAL="1", MGCFD_BENCH_WATCHDOG_S="300")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--lattice", "30", "--vcycle-hierarchy", "tiny"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--lattice", "30", "--vcycle-hierarchy", "tiny", "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

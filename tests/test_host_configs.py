@@ -1,10 +1,11 @@
 """CPU-side tests of BASELINE.json's configurations and of bench.py's launcher.
 
 * configs[0] at size: the ORACLE against the REFERENCE BINARY on the fvcorr-like 97,335-node input, 1,000 iterations
-  (needs oracle/_ref, i.e. the build container; the GPU test test_cfg1_* then compares the HIP path with the oracle
-  on the same input).
+  (the binary's run is pinned in tests/golden/fvcorr_97k_1000, made by tests/golden/make_golden.py; the GPU test
+  test_cfg1_* then compares the HIP path with the oracle on the same input).
 * bench.py --gpus N from a plain invocation starts N ranks itself; N must equal WORLD_SIZE under a launcher.
 """
+import hashlib
 import json
 import os
 import subprocess
@@ -14,13 +15,12 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_BIN = os.path.join(ROOT, "oracle", "_ref", "euler3d_cpu_double_ref.b")
+GOLDEN_CFG1 = os.path.join(ROOT, "tests", "golden", "fvcorr_97k_1000")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref not built (needs the reference sources)")
 def test_cfg1_oracle_equals_reference_binary_at_97k_nodes_1000_iterations(oracle, tmp_path):
-    """The reference binary (oracle/_ref, -g 1000 --output-variables) and the oracle read the same files: the dumped
-    variables bit for bit, the RMS lines, the loop counters."""
+    """The reference binary (-g 1000 --output-variables, its run pinned in tests/golden/fvcorr_97k_1000) and the oracle read
+    the same files: the dumped variables bit for bit (SHA-256 of their bits), the RMS lines, the loop counters."""
     from mgcfd import meshgen
     from test_oracle_golden import read_loop_iters
     d = str(tmp_path)
@@ -28,18 +28,15 @@ def test_cfg1_oracle_equals_reference_binary_at_97k_nodes_1000_iterations(oracle
     assert mg.levels[0].nel == 97335
     meshgen.write_input(mg, d)
     iters = 1000
-    r = subprocess.run([REF_BIN, "-i", "input.dat", "-d", d, "-o", d + "/", "-g", str(iters), "--output-variables"],
-                       capture_output=True, text=True, env=dict(os.environ, OMP_NUM_THREADS="1"), cwd=d, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:]
-    want = np.loadtxt(os.path.join(d, f"variables.size=1x.cycles={iters}.level=0")).reshape(-1, 5)
     oc = oracle.OracleCase.from_input_dat(os.path.join(d, "input.dat"), coords_as_reference=True)
     rc, rms, it = oc.solve(iters, run_indirect_rw=True)
     assert rc == 0
-    got = np.ascontiguousarray(oc.array(0, "variables").reshape(-1, 5))
-    assert np.array_equal(got.view(np.int64), want.view(np.int64)), f"max abs diff {np.abs(got - want).max():.3e}"
-    lines = [ln for ln in r.stdout.splitlines() if "RMS" in ln]
+    got = np.ascontiguousarray(oc.array(0, "variables").reshape(-1, 5), dtype="<f8")
+    assert got.shape == (97335, 5)
+    assert hashlib.sha256(got.tobytes()).hexdigest() == open(os.path.join(GOLDEN_CFG1, "variables.level0.sha256")).read().strip()
+    lines = [ln for ln in open(os.path.join(GOLDEN_CFG1, "stdout.txt")) if "RMS" in ln]
     assert len(lines) == iters and all(f"(RMS = {rms[c]:.3e})" in lines[c] for c in range(iters))
-    want_it = read_loop_iters(os.path.join(d, "LoopNumIters.csv"), 1)[0]
+    want_it = read_loop_iters(os.path.join(GOLDEN_CFG1, "LoopNumIters.csv"), 1)[0]
     assert want_it["flux"] == it[0].flux and want_it["time_step"] == it[0].time_step and want_it["indirect_rw"] == it[0].indirect_rw
     assert rms[-1] < 0.2 * rms[0]                                   # a developed, converging flow
     oc.close()

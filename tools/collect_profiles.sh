@@ -10,17 +10,17 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 cd /tmp && cd "$OLDPWD"
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_bench -- python3 bench.py --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/bench_default_under_rocprof.json 2> $out/kt_bench.log
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_bench -- python3 bench.py --full --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/bench_default_under_rocprof.json 2> $out/kt_bench.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_vcycle -- python3 tools/vcycle_bench.py --cycles 50 --repeats 2 > $out/vcycle_under_rocprof.json 2> $out/kt_vcycle.log
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_$c -- python3 bench.py --steps 40 --warmup 5 --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/pmc_$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_$c -- python3 bench.py --full --steps 40 --warmup 5 --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/pmc_$c.log 2>&1
 done
 # the fast mode (MGCFD_OPT_EXACT = 0: order-free stages): its line, its kernel summary, its traffic
-python3 bench.py --fast --steps 2000 --warmup 200 --cpu-seconds 0 > $out/bench_fast.json 2> $out/bench_fast.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_bench_fast -- python3 bench.py --fast --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/bench_fast_under_rocprof.json 2> $out/kt_bench_fast.log
+python3 bench.py --full --fast --steps 2000 --warmup 200 --cpu-seconds 0 > $out/bench_fast.json 2> $out/bench_fast.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_bench_fast -- python3 bench.py --full --fast --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/bench_fast_under_rocprof.json 2> $out/kt_bench_fast.log
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmcfast_$c -- python3 bench.py --fast --steps 40 --warmup 5 --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/pmcfast_$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmcfast_$c -- python3 bench.py --full --fast --steps 40 --warmup 5 --no-vcycle --cpu-seconds 0 --no-two-in-flight > $out/pmcfast_$c.log 2>&1
 done
 python3 - "$out" <<'PY'
 import csv, glob, json, os, sys, collections
@@ -45,7 +45,7 @@ def mean(sub, counter):
 def pack(sub):
     f, w = mean(sub, "FETCH_SIZE"), mean(sub, "WRITE_SIZE")
     return None if f is None or w is None else {"fetch_kb": round(f), "write_kb": round(w), "bytes": int(2 * f * 1024 + w * 1024)}
-traffic = {"_comment": "HBM-side bytes per launch from rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE passes over `python3 bench.py --steps 40 --warmup 5 --no-vcycle --cpu-seconds 0`), corrected as MI355X_MICROARCH.md prescribes for gfx950: bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024.  fused_stage = mean over the three role-specialised instantiations of the stage kernel.",
+traffic = {"_comment": "HBM-side bytes per launch from rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE passes over `python3 bench.py --full --steps 40 --warmup 5 --no-vcycle --cpu-seconds 0`), corrected for gfx950, whose FETCH_SIZE counts half the bytes of a wide streaming read: bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024.  fused_stage = mean over the three role-specialised instantiations of the stage kernel.",
            "build": os.environ.get("MGCFD_BUILD_TAG", "unknown"),
            "flux_only": pack(lambda k: "exact::k_flux_tile<" in k and ", false, false," in k),
            "fused_stage": pack(lambda k: "exact::k_flux_tile<" in k and ", true, false," in k),
