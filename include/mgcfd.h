@@ -110,12 +110,16 @@ enum {
                                   ROCm 7.2 / MI355X the graph costs ~1.7 us per kernel node more than direct launches
                                   (sweep 75 us replayed, 70 us launched), so it only pays when the host cannot keep
                                   the queue full */
-    MGCFD_OPT_RANK_SPLIT = 7   /* ranks in different processes, direct stores (mgcfd_rank_ipc_*): 1 (default) a stage runs its
+    MGCFD_OPT_RANK_SPLIT = 7,  /* ranks in different processes, direct stores (mgcfd_rank_ipc_*): 1 (default) a stage runs its
                                   boundary tiles first, sends, then the interior tiles (the message's flight is hidden);
                                   0: all tiles in ONE launch, then the message (two launches less per stage, the flight
                                   exposed); 2: ONE launch that sends its own message — the boundary tiles come first, their
                                   epilogue stores into the neighbours, the last of them raises the flags while the interior
                                   tiles still run.  Which is fastest depends on the flight time: bench.py times all three. */
+    MGCFD_OPT_STAGE_WG4 = 8    /* 1 (default): the bit-identical fused stages (MGCFD_OPT_EXACT = 1, roles without a message or an
+                                  absorbed stage, levels without long rows) of a level whose every tile halo fits 254 LDS slots and
+                                  whose tiles outnumber three per CU run the instantiation with 80-byte node records, four
+                                  workgroups per CU instead of three; same bits.  0: always the 96-byte-record instantiation (A/B) */
 };
 
 /* Same 40-byte layout as the reference's edge_neighbour (src/Base/definitions.h:83). */
@@ -213,6 +217,10 @@ int mgcfd_level_has_half_rows(const mgcfd_solver *s, int level, int *yes);
 /* *yes = 1 when level `level` can run the order-free flux kernel (MGCFD_OPT_FLUX_VARIANT bit 6 with MGCFD_OPT_EXACT = 0): no halo
  * node left outside LDS; any number of edges per node (what a lane's five requested rows do not hold is walked in a loop). */
 int mgcfd_level_has_order_free(const mgcfd_solver *s, int level, int *yes);
+/* *yes = 1 when the bit-identical fused stages of level `level` run the four-workgroups-per-CU instantiation (MGCFD_OPT_STAGE_WG4
+ * set, MGCFD_OPT_EXACT = 1, no long rows, every tile halo within 254 LDS slots, more tiles than three per CU; the split sweep's
+ * absorbed first stage and a stage that sends its own message keep the other one). */
+int mgcfd_level_stage_wg4(const mgcfd_solver *s, int level, int *yes);
 /* What the tiling of level `level` looks like (the figures MGCFD_VERBOSE=1 prints at creation):
  * out[0] tiles of 256 nodes, out[1] halo nodes of all tiles together, out[2] the largest halo, out[3] halo nodes a
  * tile can stage in LDS, out[4] incidence-row entries that refer to a halo node beyond that (each a gather from

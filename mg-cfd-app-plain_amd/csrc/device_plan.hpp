@@ -15,6 +15,10 @@ constexpr int kNumStateFields = 5;
 static_assert(sizeof(EdgeW) == 32, "EdgeW must be 32 bytes");
 static_assert(sizeof(ProlongW) == 24, "ProlongW must be 24 bytes");
 
+// launch_flux's variant bit for the bit-identical fused stages (never part of a user's MGCFD_OPT_FLUX_VARIANT: solver.cpp adds
+// it with MGCFD_OPT_STAGE_WG4): the four-workgroups-per-CU instantiation where the level's tile halos fit kTileCap4 - kTile slots
+constexpr int kVariantStageWg4 = 1 << 7;
+
 // ff_variable + ff_flux_contribution_* (src/Base/globals.h:11-15), passed by value.
 struct FarField {
     double var[5];
@@ -168,5 +172,9 @@ struct DevicePlan {
     int32_t *pro_parent = nullptr;
     double *pro_wsum = nullptr;
 };
+
+// The level can run the stages of kVariantStageWg4: no long rows, every tile's halo within the 80-byte records' slots (so no
+// overflow table and no second halo id per thread either)
+inline bool stage_wg4_fits(const DevicePlan &p) { return !p.has_tail && p.halo_max <= kTileCap4 - kTile; }
 
 } // namespace mgcfd

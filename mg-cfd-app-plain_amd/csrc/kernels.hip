@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <stdint.h>
+#include <type_traits>
 
 #include "device_plan.hpp"
 
@@ -155,6 +156,45 @@ __device__ __forceinline__ NodeQ lds_load_record(const double2 *tile, uint32_t s
     r.rho = a.x; r.mx = a.y; r.my = bq.x; r.mz = bq.y; r.en = c.x; r.vx = c.y;
     r.vy = d.x; r.vz = d.y; r.p = e.x; r.speed = e.y; r.c = f;
     return r;
+}
+
+// The records of the four-workgroups-per-CU stages (FluxTileLds4): 10 doubles (80 B), the pressure left out and recomputed
+// where a record is read, by derive's expression on the same stored doubles (the same bits under -ffp-contract=off).  The
+// stride of 5 quads is odd, so 16 consecutive slots already cover all 16 quad positions of the 256-B bank row: no swizzle.
+constexpr int kLdsRec80D2 = 5;
+
+__device__ __forceinline__ void lds_put_record80(double2 *tile, uint32_t slot, const NodeQ &n)
+{
+    double2 *rec = tile + slot * kLdsRec80D2;
+    rec[0] = make_double2(n.rho, n.mx);
+    rec[1] = make_double2(n.my, n.mz);
+    rec[2] = make_double2(n.en, n.vx);
+    rec[3] = make_double2(n.vy, n.vz);
+    rec[4] = make_double2(n.speed, n.c);
+}
+
+__device__ __forceinline__ NodeQ lds_get_record80(const double2 *tile, uint32_t slot)
+{
+    const double2 *rec = tile + slot * kLdsRec80D2;
+    const double2 a = rec[0], b = rec[1], c = rec[2], d = rec[3], e = rec[4];
+    NodeQ r;
+    r.rho = a.x; r.mx = a.y; r.my = b.x; r.mz = b.y; r.en = c.x; r.vx = c.y;
+    r.vy = d.x; r.vz = d.y; r.speed = e.x; r.c = e.y;
+    r.p = (kGamma - 1.0) * (r.en - 0.5 * r.rho * (r.vx * r.vx + r.vy * r.vy + r.vz * r.vz));      // derive(), cfd_loops.h:121-148
+    return r;
+}
+
+template <bool SLIM>
+__device__ __forceinline__ void lds_put_rec(double2 *tile, uint32_t slot, const NodeQ &n)
+{
+    if (SLIM) lds_put_record80(tile, slot, n);
+    else lds_store_record(tile, slot, n);
+}
+
+template <bool SLIM>
+__device__ __forceinline__ NodeQ lds_get_rec(const double2 *tile, uint32_t slot)
+{
+    return SLIM ? lds_get_record80(tile, slot) : lds_load_record(tile, slot);
 }
 
 // The nine distinct flux-contribution components (cfd_loops.h:57-83); the momentum tensor is
@@ -596,12 +636,22 @@ struct FluxTileLds {
     double s_pm[kBlock / 64];
     double s_next[2][kBlock / 64];
 };
+// SLIM: the 80-byte records (lds_put_record80) of at most kTileCap4 staged nodes, 40,896 B: four workgroups per CU.  Levels
+// whose every tile halo fits kTileCap4 - kTile slots (the launcher checks halo_max; no overflow table, no second halo id).
+struct FluxTileLds4 {
+    double2 tile[kTileCap4 * kLdsRec80D2];
+    double s_pm[kBlock / 64];
+    double s_next[2][kBlock / 64];
+};
+static_assert(sizeof(FluxTileLds4) <= 160 * 1024 / 4, "four workgroups per CU");
+static_assert(kTileCap4 - kTile < kBlock, "one halo id per thread");
 
 // The kernel's body as a function of the workgroup's position in the launch (`block`): k_flux_tile calls it with blockIdx.x
 // (tools/exp/sweep_flow.patch: a dataflow sweep calls it with the tile a workgroup has claimed).
-template <int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH>
+// SLIM (with FluxTileLds4): 80-byte records and the rows walked one at a time, for four workgroups per CU.
+template <int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH, bool SLIM = false, typename Lds = FluxTileLds>
 __device__ __forceinline__ void
-flux_tile_body(FluxTileLds &lds, const unsigned block,
+flux_tile_body(Lds &lds, const unsigned block,
                const double *__restrict__ q, const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int32_t pad_row,
                int64_t stride, int64_t nel, const int32_t *__restrict__ slice_row0,
                const int32_t *__restrict__ rows_int, const int32_t *__restrict__ rows_bnd,
@@ -617,6 +667,7 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
     PH_BEGIN();
     constexpr bool IDXW = WMODE == 2;
     static_assert(!(IDXW && TAIL), "indexed weights: levels without long rows only");
+    static_assert(!SLIM || (!TAIL && !IDXW && !PUSH && ROLE != 5), "80-byte records: the stages without long rows, indexed weights, message or absorbed stage");
     double2 *const tile = lds.tile;
 
     // FUSE: this launch is a whole Runge-Kutta stage — the node's complete flux never leaves
@@ -650,7 +701,7 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
     // — then the own node's state, the first two rows' ids and weights, and the halo state by id.
     const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
     const int32_t hid = hrow[tid];                                     // -1: no halo node for this thread
-    const int32_t hid2 = (ROLE != 5 && tid < kHaloStride - kBlock) ? hrow[kBlock + tid] : -1;   // halo larger than the workgroup (rare)
+    const int32_t hid2 = (!SLIM && ROLE != 5 && tid < kHaloStride - kBlock) ? hrow[kBlock + tid] : -1;   // halo larger than the workgroup (rare)
     const int32_t row0 = slice_row0[slice];
     const int32_t n_int = (classes & 1) ? (TAIL ? tp.rows_main : rows_int)[slice] : 0;
     const int32_t n_bnd = rows_bnd[slice];
@@ -720,7 +771,7 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
         if (IDXW) { e0 = gather_weights(tw, i0); e1 = gather_weights(tw, i1); }
         else {
             e0 = load_row<LOADK>(nbr16, w, n_int > 0 ? row0 : pad_row, lane);
-            e1 = load_row<LOADK>(nbr16, w, n_int > 1 ? row0 + 1 : pad_row, lane);
+            if (!SLIM) e1 = load_row<LOADK>(nbr16, w, n_int > 1 ? row0 + 1 : pad_row, lane);
         }
     }
     // (the step-factor partials: wanted only at the staging barrier, so requested after everything on the critical chain)
@@ -732,11 +783,13 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
         }
     }
     const NodeQ me = make_nodeq(o0, o1, o2, o3, o4);
-    lds_store_record(tile, uint32_t(tid), me);
+    lds_put_rec<SLIM>(tile, uint32_t(tid), me);
     // Unconditional: a thread without a halo node re-reads its own node and parks the copy in its
     // (unused) halo slot.  A branch here lets the compiler sink the gather loads below the own
-    // record's derivation and serialise the two.
-    lds_store_record(tile, uint32_t(kTile + tid), make_nodeq(g0, g1, g2, g3, g4));
+    // record's derivation and serialise the two.  (SLIM: the last threads have no halo slot — their halo
+    // id is -1 on the levels that run it — and write the copy over their own record, the same bits.)
+    const uint32_t hslot = (SLIM && tid >= kTileCap4 - kTile) ? uint32_t(tid) : uint32_t(kTile + tid);
+    lds_put_rec<SLIM>(tile, hslot, make_nodeq(g0, g1, g2, g3, g4));
     if (hid2 >= 0) lds_store_record(tile, uint32_t(kTile + kBlock + tid), load_and_derive(q, stride, hid2));
 
     const FluxC fm_pre = flux_contribution(me);
@@ -805,6 +858,41 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
         if (e_first < tl_e) { tl_r0 = tp.rec[3 * int64_t(e_first)]; tl_r1 = tp.rec[3 * int64_t(e_first) + 1]; tl_r2 = tp.rec[3 * int64_t(e_first) + 2]; }
     }
     double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, r4 = 0.0, sfv = 0.0;       // fused stages: the time_step operands
+    // SLIM: one row at a time, the next row's ids and weights fetched one row ahead (two rows of records and
+    // weights in registers do not fit the 128 registers of four waves per SIMD).  Same rows in the same order, the same
+    // adds; no overflow table (every halo node has its slot).
+#define MGCFD_ROW_ONE()                                                                                      \
+    do {                                                                                                     \
+            const uint32_t s0 = e0.code & kT16SlotMask;                                                      \
+            const bool v0 = s0 != kT16Pad;                                                                   \
+            const NodeQ n0 = lds_get_record80(tile, v0 ? s0 : uint32_t(tid));                              \
+            const Flux5 f0 = edge_flux<LOADK>(me, fm_pre, n0, e0);                                           \
+            if (ACC) {                                                                                       \
+                a0 = v0 ? a0 + f0.d : a0;   a1 = v0 ? a1 + f0.mx : a1;   a2 = v0 ? a2 + f0.my : a2;          \
+                a3 = v0 ? a3 + f0.mz : a3;  a4 = v0 ? a4 + f0.en : a4;                                       \
+            } else {                                                                                         \
+                a0 += f0.d; a1 += f0.mx; a2 += f0.my; a3 += f0.mz; a4 += f0.en;                              \
+            }                                                                                                \
+    } while (0)
+    if (SLIM) {
+        int32_t r = 0;
+        for (; r + 1 < n_int; r++) {
+            const EdgeRow e1n = load_row<LOADK>(nbr16, w, row0 + r + 1, lane);
+            MGCFD_ROW_ONE();
+            e0 = e1n;
+        }
+        // the last row: the time_step operands arrive while it is summed (as after the last pair below)
+        if (FUSE) {
+            if (ROLE == 0) {
+                r0 = me.rho; r1 = me.mx; r2 = me.my; r3 = me.mz; r4 = me.en;
+            } else {
+                r0 = fs.old_variables[i]; r1 = fs.old_variables[stride + i]; r2 = fs.old_variables[2 * stride + i];
+                r3 = fs.old_variables[3 * stride + i]; r4 = fs.old_variables[4 * stride + i];
+            }
+            sfv = (ROLE == 0 ? fs.volumes : fs.step_factors)[i];
+        }
+        if (r < n_int) MGCFD_ROW_ONE();
+    } else
     {
         // every pair but the last, each prefetching the pair after it
         int32_t r = 0;
@@ -840,6 +928,7 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
         if (r < n_int) MGCFD_ROW_PAIR();
     }
 #undef MGCFD_ROW_PAIR
+#undef MGCFD_ROW_ONE
     PH_MARK(2);
 
     if (TAIL && (classes & 1) && tl_e > tl_b) {                            // (uniform)
@@ -1036,7 +1125,7 @@ flux_tile_body(FluxTileLds &lds, const unsigned block,
     PH_MARK(3);
 }
 
-template <int MINW, int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false>
+template <int MINW, int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false, bool SLIM = false>
 __global__ void __launch_bounds__(kBlock, MINW)
 k_flux_tile(// the first 16 dwords of the arguments are preloaded into SGPRs at wave launch (Makefile:
             // -amdgpu-kernarg-preload-count): what the first loads of the prologue need comes first
@@ -1049,8 +1138,8 @@ k_flux_tile(// the first 16 dwords of the arguments are preloaded into SGPRs at 
             const uint16_t *__restrict__ gat16, const int32_t *__restrict__ te_chunk_ptr, const double *__restrict__ te_w3,
             StagePush push)
 {
-    __shared__ FluxTileLds lds;
-    flux_tile_body<WMODE, FUSE, ACC, ROLE, TAIL, PUSH>(lds, blockIdx.x, q, tile_halo, n_tiles, pad_row, stride, nel, slice_row0, rows_int, rows_bnd, nbr16, w,
+    __shared__ std::conditional_t<SLIM, FluxTileLds4, FluxTileLds> lds;
+    flux_tile_body<WMODE, FUSE, ACC, ROLE, TAIL, PUSH, SLIM>(lds, blockIdx.x, q, tile_halo, n_tiles, pad_row, stride, nel, slice_row0, rows_int, rows_bnd, nbr16, w,
                                                        tile_ovf_ptr, tile_ovf, ff, fluxes, classes, fs, tp, gat16, te_chunk_ptr, te_w3, push);
 }
 
@@ -2731,6 +2820,29 @@ void launch_flux(hipStream_t st, const DevicePlan &p, const double *q, const Far
 #undef MGCFD_EO_LAUNCH
         return;
     }
+#ifndef MGCFD_ORDER_FREE
+    // kVariantStageWg4 (the bit-identical stages, solver.cpp): four workgroups per CU with 80-byte records where every tile
+    // halo fits kTileCap4 - kTile slots — roles 0-4 of levels without long rows, k recomputed or streamed
+    if (fused && (variant & kVariantStageWg4) && stage_wg4_fits(p) && !indexed && role != 5) {
+#define MGCFD_SLIM_LAUNCH_T(WMODE, ROLE)                                                                        \
+    hipLaunchKernelGGL((k_flux_tile<4, WMODE, true, false, ROLE, false, false, true>), grid, block, 0, st, q, p.tile_halo, \
+                       uint32_t(grid.x), p.pad_row, p.stride, nel_arg, p.slice_row0, p.rows_int, p.rows_bnd, \
+                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, classes, fs, p.tail, p.gat16,     \
+                       p.te_chunk_ptr, p.te_w3, StagePush{})
+#define MGCFD_SLIM_LAUNCH_R(WMODE)                                                                              \
+    do {                                                                                                       \
+        if (role == 0) MGCFD_SLIM_LAUNCH_T(WMODE, 0);                                                          \
+        else if (role == 2) MGCFD_SLIM_LAUNCH_T(WMODE, 2);                                                     \
+        else if (role == 3) MGCFD_SLIM_LAUNCH_T(WMODE, 3);                                                     \
+        else if (role == 4) MGCFD_SLIM_LAUNCH_T(WMODE, 4);                                                     \
+        else MGCFD_SLIM_LAUNCH_T(WMODE, 1);                                                                    \
+    } while (0)
+        if (loadk) MGCFD_SLIM_LAUNCH_R(1); else MGCFD_SLIM_LAUNCH_R(0);
+#undef MGCFD_SLIM_LAUNCH_R
+#undef MGCFD_SLIM_LAUNCH_T
+        return;
+    }
+#endif
     if (fused) {
         if (loadk) MGCFD_TILE_LAUNCH(true, true, false); else MGCFD_TILE_LAUNCH(false, true, false);
     } else if (accumulate) {

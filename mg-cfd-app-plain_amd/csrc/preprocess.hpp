@@ -26,6 +26,9 @@ constexpr int kTile = 256;   // nodes per tile = one 256-thread workgroup = 4 sl
 // the records (per-wave minima and sums): 559 * 96 B = 53,664 B leaves them 96 B inside the 42nd granule.  With 560 records the
 // first and the last stage of every sweep ran at two workgroups per CU: 20.6 / 21.1 us against 18.3 / 19.1 (profiles/README.md).
 constexpr int kTileCap = 559;
+// ... and what the four-workgroups-per-CU form of the bit-identical stages stages (80-byte records, kernels.hip: FluxTileLds4):
+// 510 * 80 B + 96 B = 40,896 B = 32 granules = a quarter of the CU.  Levels whose every tile halo fits 254 slots run it.
+constexpr int kTileCap4 = 510;
 // edge-once tiles: a tile's internal edges are evaluated in chunks of one edge per thread; the
 // fluxes of up to kMaxEdgeChunks chunks wait in registers, then replace the node records in LDS
 // (kMaxEdgeChunks * 256 * 40 B must fit kTileCap * 96 B)

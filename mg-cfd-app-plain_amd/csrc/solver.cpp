@@ -213,7 +213,7 @@ struct mgcfd_solver {
     FarField ff{};
     double ff17[17] = {0};
     unsigned long long *err = nullptr;       // device: packed (cell << 8 | code), ~0 = clean
-    int opt_exact = 1, opt_timing = 0, opt_indirect_rw = 0, opt_check = 1, opt_variant = -1, opt_fuse = 1, opt_graph = 0;
+    int opt_exact = 1, opt_timing = 0, opt_indirect_rw = 0, opt_check = 1, opt_variant = -1, opt_fuse = 1, opt_graph = 0, opt_stage_wg4 = 1;
     // (MGCFD_LAZY_RESIDUAL=0: every sweep's last stage writes residuals[] — for A/B measurements)
     int opt_rank_split = 1;
     bool opt_lazy_residual = !(std::getenv("MGCFD_LAZY_RESIDUAL") && std::atoi(std::getenv("MGCFD_LAZY_RESIDUAL")) == 0);
@@ -419,6 +419,20 @@ struct mgcfd_solver {
         if (!opt_exact && lv.dp.free_rows && (!fused || lv.dp.free_wide || lv.dp.has_tail || free_fast_path)) return 1 | 64;
         return 1;
     }
+    // MGCFD_OPT_STAGE_WG4: the bit-identical stages of a level at four workgroups per CU (80-byte records, rows one at a time)
+    // where its halos fit the records' slots AND its tiles outnumber what three per CU hold at once.  The bench level (1,175
+    // tiles) then runs in 1.15 rounds instead of 1.53: stages 18.3 / 17.4 / 18.9 -> 17.1 / 16.2 / 17.8 us, sweep 53.0 -> 50.5 us;
+    // a level of one round either way only pays the single-row loop (the V-cycle's 48^3 level, 432 tiles: +1.7 % per cycle).
+    mutable int n_cus = 0;
+    bool stage_wg4_for(const DeviceLevel &lv) const
+    {
+        if (!opt_exact || !opt_stage_wg4 || !stage_wg4_fits(lv.dp)) return false;
+        if (n_cus == 0) {
+            use_device();
+            HIP_CHECK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+        }
+        return lv.dp.n_tiles > 3 * n_cus;
+    }
     // classes: bit0 internal, bit1 solid wall (-1), bit2 far field (-2)
     void op_flux(int l, int classes)
     {
@@ -449,7 +463,7 @@ struct mgcfd_solver {
         DeviceLevel &lv = level(l);
         const FusedStep fs = fused_step(l, j, out, apply_min, with_residual, old, look_ahead, sumsq, vin_flux, tile_list, n_list, min_list, n_min, lazy_residual);
         Timed t(this, l, MGCFD_LOOP_FLUX, true);
-        if (opt_exact) exact::launch_flux(stream, lv.dp, in, ff, lv.fluxes, 7, 0, variant_for(lv, true), &fs, push);
+        if (opt_exact) exact::launch_flux(stream, lv.dp, in, ff, lv.fluxes, 7, 0, variant_for(lv, true) | (stage_wg4_for(lv) ? kVariantStageWg4 : 0), &fs, push);
         else fast::launch_flux(stream, lv.dp, in, ff, lv.fluxes, 7, 0, variant_for(lv, true), &fs, push);
         if (count_iters) {                          // (a stage launched in two parts counts once)
             lv.iters[MGCFD_LOOP_FLUX] += lv.info.n_internal;
@@ -1165,6 +1179,7 @@ int mgcfd_set_option(mgcfd_solver *s, int option, int value)
             case MGCFD_OPT_FUSE_UPDATE: s->opt_fuse = value != 0; break;
             case MGCFD_OPT_GRAPH: s->opt_graph = value != 0; break;
             case MGCFD_OPT_RANK_SPLIT: s->opt_rank_split = value < 0 ? 0 : (value > 2 ? 2 : value); break;
+            case MGCFD_OPT_STAGE_WG4: s->opt_stage_wg4 = value != 0; break;
             default: throw std::invalid_argument("unknown option");
         }
     });
@@ -1181,6 +1196,13 @@ int mgcfd_level_has_order_free(const mgcfd_solver *s, int level, int *yes)
     REQUIRE(s); REQUIRE(yes);
     if (level < 0 || level >= static_cast<int>(s->L.size())) { g_last_error = "level out of range"; return MGCFD_ERR_ARG; }
     *yes = s->L[static_cast<size_t>(level)].dp.free_rows;
+    return MGCFD_OK;
+}
+int mgcfd_level_stage_wg4(const mgcfd_solver *s, int level, int *yes)
+{
+    REQUIRE(s); REQUIRE(yes);
+    if (level < 0 || level >= static_cast<int>(s->L.size())) { g_last_error = "level out of range"; return MGCFD_ERR_ARG; }
+    *yes = s->stage_wg4_for(s->L[static_cast<size_t>(level)]) ? 1 : 0;
     return MGCFD_OK;
 }
 int mgcfd_level_has_edge_once(const mgcfd_solver *s, int level, int *yes)
@@ -1220,6 +1242,7 @@ int mgcfd_get_option(const mgcfd_solver *s, int option, int *value)
         case MGCFD_OPT_FUSE_UPDATE: *value = s->opt_fuse; break;
         case MGCFD_OPT_GRAPH: *value = s->opt_graph; break;
         case MGCFD_OPT_RANK_SPLIT: *value = s->opt_rank_split; break;
+        case MGCFD_OPT_STAGE_WG4: *value = s->opt_stage_wg4; break;
         default: g_last_error = "unknown option"; return MGCFD_ERR_ARG;
     }
     return MGCFD_OK;
@@ -1430,7 +1453,7 @@ static void run_sweep(mgcfd_solver *s, int level)
         s->opt_timing = keep;
         return;
     }
-    const uint64_t key = (uint64_t(level) << 32) | (uint64_t(lv.want_sumsq) << 28) | (uint64_t(lv.sf_par) << 27) | (uint64_t(lv.rot) << 25) | (uint64_t(lv.min_ahead) << 24) | (uint64_t(s->opt_exact) << 16) | (uint64_t(s->opt_check) << 8) | uint64_t(s->opt_variant & 0xFF);
+    const uint64_t key = (uint64_t(level) << 32) | (uint64_t(lv.want_sumsq) << 28) | (uint64_t(lv.sf_par) << 27) | (uint64_t(lv.rot) << 25) | (uint64_t(lv.min_ahead) << 24) | (uint64_t(s->opt_exact) << 16) | (uint64_t(s->opt_stage_wg4) << 17) | (uint64_t(s->opt_check) << 8) | uint64_t(s->opt_variant & 0xFF);
     auto it = s->sweep_graphs.find(key);
     if (it == s->sweep_graphs.end()) {
         mgcfd_solver::SweepGraph g;
@@ -1662,7 +1685,7 @@ int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out)
                 // The launch sequence depends on which levels enter with their step-factor minima
                 // already computed (min_ahead), so that is part of the key and looked up per cycle.
                 for (int c = 0; c < chunk; c++) {
-                    uint64_t key = (uint64_t(s->opt_exact) << 16) | (uint64_t(s->opt_check) << 8) | uint64_t(s->opt_variant & 0xFF);
+                    uint64_t key = (uint64_t(s->opt_exact) << 16) | (uint64_t(s->opt_stage_wg4) << 17) | (uint64_t(s->opt_check) << 8) | uint64_t(s->opt_variant & 0xFF);
                     for (size_t l = 0; l < nl && l < 8; l++) key |= (uint64_t(s->L[l].min_ahead) << (24 + l)) | (uint64_t(s->L[l].rot) << (32 + 2 * l)) | (uint64_t(s->L[l].sf_par) << (48 + l));
                     auto it = s->cycle_graphs.find(key);
                     if (it == s->cycle_graphs.end()) {

@@ -24,7 +24,7 @@ NVAR = 5
 RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6}
-OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7}
+OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
 
@@ -72,6 +72,7 @@ _SIGNATURES = [
     ("mgcfd_level_has_half_rows", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     ("mgcfd_pending_invalid_state", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("mgcfd_level_has_order_free", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
+    ("mgcfd_level_stage_wg4", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     ("mgcfd_level_tiling", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64)]),
     ("mgcfd_invalid_state_location", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     ("mgcfd_get_option", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
@@ -380,6 +381,12 @@ class Solver:
     def has_order_free(self, l: int) -> bool:
         yes = C.c_int(0)
         self._c(self.lib.mgcfd_level_has_order_free(self.handle, l, C.byref(yes)))
+        return bool(yes.value)
+
+    def stage_wg4(self, l: int) -> bool:
+        """The fused stages of level l run the four-workgroups-per-CU instantiation (MGCFD_OPT_STAGE_WG4)."""
+        yes = C.c_int(0)
+        self._c(self.lib.mgcfd_level_stage_wg4(self.handle, l, C.byref(yes)))
         return bool(yes.value)
 
     def has_edge_once(self, l: int) -> bool:
