@@ -296,6 +296,26 @@ int mgcfd_smooth(mgcfd_solver *s, int level, int sweeps);
  * cell id are what is reported (the reference stops at exactly that cell).  The cycles of the current batch (up to
  * 4096) still run to the end; rms_out entries from the failing cycle on are NaN. */
 int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out);
+/* ---------------------------------------------------------------------------------
+ * Surface loads — no reference counterpart: the pressure force and moment on the solid walls (neighbour code -1,
+ * src/Base/io.cpp:92-104), the sum over those edges of the momentum term compute_boundary_flux_edge adds
+ * (flux_boundary_kernel.elemfunc.c) with the far-field pressure taken off.  For edge (node b, weights w):
+ * f = (p_b - p_inf) w, m = (coords[b] - ref_point) x f; summed in a fixed order (chunks of 256 edges, stride-halving
+ * tree, then the same over the partial sums), never contracted to FMA: a bitwise function of the state.  INTEGRATION.md
+ * gives the whole definition.  Solvers of a partitioned level or attached as ranks: MGCFD_ERR_ARG.
+ * --------------------------------------------------------------------------------- */
+/* Loads of level `level`'s current `variables`: out6 = Fx Fy Fz Mx My Mz.  ref_point NULL = the origin.  Synchronises.
+ * A level without solid-wall edges gives exact zeros. */
+int mgcfd_surface_loads(mgcfd_solver *s, int level, const double ref_point[3], double out6[6]);
+/* mgcfd_run_cycles (same RMS, same final state, same errors), and loads_out[c*6 .. c*6+5] = the level-0 loads of the
+ * state at the end of cycle c (after its last prolongation), recorded on the device inside the cycle and read back with
+ * the RMS.  Rows of cycles that did not complete are NaN, as rms_out's. */
+int mgcfd_run_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out);
+/* Host only: coefficients of a loads vector against the far field ff17 (mgcfd_get_far_field): q = 0.5 rho |V|^2,
+ * alpha = atan2(Vy, Vx); out6 = CD = F.(cos a, sin a, 0)/(q S), CL = F.(-sin a, cos a, 0)/(q S), CS = Fz/(q S),
+ * CMx CMy CMz = M/(q S c).  ref_area S and ref_length c must be positive. */
+int mgcfd_load_coefficients(const double ff17[17], const double loads6[6], double ref_area, double ref_length,
+                            double out6[6]);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

@@ -112,6 +112,29 @@ struct SumTask {
     int cap = 0;
 };
 
+// One solid-wall edge (neighbour code -1) as the surface-loads kernel reads it: the edge's weights after adjust/dampen,
+// the coordinates of its node and the node's index in the solver's numbering.
+struct WallRecord {
+    double x, y, z;                       // edge weights
+    double cx, cy, cz;                    // coordinates of node b (zeros where the level has none)
+    int32_t node;                         // node b, renumbered
+    int32_t pad;
+};
+
+// The pressure loads of one level's solid walls (k_surface_loads): six sums Fx Fy Fz Mx My Mz over `n` records.
+struct LoadsTask {
+    const WallRecord *rec = nullptr;      // [n]
+    int64_t n = 0;
+    double p_inf = 0.0;                   // far-field pressure
+    const double *ref = nullptr;          // device [3]: moment reference point
+    double *partial = nullptr;            // [6][ceil(n / 256)] per-workgroup sums (stage A), reduced in place (stage B)
+    unsigned *ticket = nullptr;           // arrival counter of the workgroups; the last one resets it to 0
+    double *out = nullptr;                // nullptr, or: the 6 sums
+    double *ring = nullptr;               // nullptr, or: the 6 sums into row (*count - 1) of this [cap][6] history
+    const int *count = nullptr;
+    int cap = 0;
+};
+
 // Long rows (preprocess.hpp: LevelPlan::tail_*): device arrays of the entries the per-node loop leaves to the workgroup.
 struct TailPlan {
     const int32_t *rows_main = nullptr;   // [n_slices] internal rows the per-node loop walks

@@ -2396,6 +2396,120 @@ __global__ void k_append_scalar(const double *__restrict__ src, double *__restri
 }
 
 // ------------------------------------------------------------------------------------------
+// Surface loads: the pressure force and moment on the solid walls, sum over the solid-wall edges (neighbour code -1) of
+// the term compute_boundary_flux_edge adds to the momentum residual (flux_boundary_kernel.elemfunc.c), with the far-field
+// pressure taken off: f = (p_b - p_inf) * (x, y, z), m = (c_b - ref) x f.  Summation order fixed: chunks
+// of 256 edges reduced by the stride-halving tree v[t] += v[t + s], s = 128 .. 1 (stage A, one workgroup per chunk), then
+// the same over the list of partial sums until one value is left (stage B, the workgroup that arrives last).  Never
+// contracted to FMA, whichever flavour is compiled, so the loads are a bitwise function of the state.
+// ------------------------------------------------------------------------------------------
+// The tree over the 256 lanes' six values; lane 0 holds the sums.  s = 128, 64 through LDS, s < 64 by shuffles within
+// wave 0 (lane t adds lane t + s: the same operand pairs).
+__device__ __forceinline__ void loads_tree(double v[6], double (*sh)[kBlock])
+{
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < 6; c++) sh[c][t] = v[c];
+    __syncthreads();
+    if (t < 128) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) v[c] += sh[c][t + 128];
+    }
+    __syncthreads();
+    if (t < 128) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) sh[c][t] = v[c];
+    }
+    __syncthreads();
+    if (t < 64) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) v[c] += sh[c][t + 64];
+        for (int s = 32; s > 0; s >>= 1) {
+#pragma unroll
+            for (int c = 0; c < 6; c++) v[c] += __shfl_down(v[c], s, 64);
+        }
+    }
+    __syncthreads();                                                   // (sh is free again)
+}
+
+__device__ __forceinline__ void loads_store(const LoadsTask &task, const double v[6])
+{
+    if (task.out) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) task.out[c] = v[c];
+    }
+    if (task.ring) {
+        const int k = *task.count - 1;                                 // the row of the cycle whose RMS was appended last
+        if (k >= 0 && k < task.cap) {
+#pragma unroll
+            for (int c = 0; c < 6; c++) task.ring[int64_t(k) * 6 + c] = v[c];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_surface_loads(int64_t stride, const double *__restrict__ q, LoadsTask task)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[6][kBlock];
+    __shared__ int last;
+    const int t = threadIdx.x;
+    const int64_t e = int64_t(blockIdx.x) * kBlock + t;
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (e < task.n) {
+        const WallRecord r = task.rec[e];
+        const int64_t b = r.node;
+        const double rho = q[b], mx = q[stride + b], my = q[2 * stride + b], mz = q[3 * stride + b], en = q[4 * stride + b];
+        // derive()'s pressure, written out here so that the pragma above covers it (cfd_loops.h:121-148)
+        const double vx = mx / rho, vy = my / rho, vz = mz / rho;
+        const double speed_sqd = vx * vx + vy * vy + vz * vz;
+        const double p = (kGamma - 1.0) * (en - 0.5 * rho * speed_sqd);
+        const double dp = p - task.p_inf;
+        const double fx = dp * r.x, fy = dp * r.y, fz = dp * r.z;
+        const double rx = r.cx - task.ref[0], ry = r.cy - task.ref[1], rz = r.cz - task.ref[2];
+        v[0] = fx; v[1] = fy; v[2] = fz;
+        v[3] = ry * fz - rz * fy;
+        v[4] = rz * fx - rx * fz;
+        v[5] = rx * fy - ry * fx;
+    }
+    loads_tree(v, sh);                                                 // stage A
+    const int nb = int(gridDim.x);
+    if (nb == 1) {
+        if (t == 0) loads_store(task, v);
+        return;
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) task.partial[int64_t(c) * nb + blockIdx.x] = v[c];
+        const unsigned done = __hip_atomic_fetch_add(task.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        last = done == unsigned(nb - 1);
+        if (last) __hip_atomic_store(task.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a graph replay starts from zero)
+    }
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                  // every lane sees the other workgroups' partials
+    // stage B: the list of partials reduced by the same tree, chunk by chunk, in place (chunk k's sum lands in slot k,
+    // which chunk k has already read or an earlier chunk has), until one value is left
+    for (int n = nb; n > 1;) {
+        const int m = (n + kBlock - 1) / kBlock;
+        for (int k = 0; k < m; k++) {
+            const int i = k * kBlock + t;
+#pragma unroll
+            for (int c = 0; c < 6; c++) v[c] = i < n ? task.partial[int64_t(c) * nb + i] : 0.0;
+            loads_tree(v, sh);
+            if (t == 0) {
+#pragma unroll
+                for (int c = 0; c < 6; c++) task.partial[int64_t(c) * nb + k] = v[c];
+            }
+            __syncthreads();
+        }
+        n = m;
+    }
+    if (t == 0) loads_store(task, v);
+}
+
+// ------------------------------------------------------------------------------------------
 // mg_restrict (mg_loops.cpp:30-202) as a coarse-centred gather: coarse = (sum of children in
 // ascending fine id) * (1/count); coarse nodes without children keep their value.
 // ------------------------------------------------------------------------------------------
@@ -2964,6 +3078,12 @@ void launch_sum_partials_append(hipStream_t st, int n, const double *partial, do
 
 void launch_append_scalar(hipStream_t st, const double *src, double *ring, int *count, int cap)
 { hipLaunchKernelGGL(k_append_scalar, dim3(1), dim3(64), 0, st, src, ring, count, cap); }
+
+void launch_surface_loads(hipStream_t st, int64_t stride, const double *q, const LoadsTask &task)
+{
+    if (task.n <= 0) return;                                           // (the caller writes the zeros)
+    hipLaunchKernelGGL(k_surface_loads, dim3(unsigned((task.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, stride, q, task);
+}
 
 void launch_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine,
                      const int32_t *child_ptr, const int32_t *child, const int32_t *child4, const double *fine_q,

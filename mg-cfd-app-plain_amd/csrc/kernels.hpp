@@ -50,6 +50,7 @@
                          const int32_t *child_ptr, const int32_t *child, const int32_t *child4, const double *fine_q, \
                          double *coarse_q,                                                                        \
                          const double *cbrt_vol, double *partial_min, const SumTask &rms);                          \
+    void launch_surface_loads(hipStream_t, int64_t stride, const double *q, const LoadsTask &task);                  \
     void launch_prolong(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_residuals,      \
                         const double *fine_residuals, double *fine_q, const double *cbrt_vol,                       \
                         double *partial_min);                                                                        \

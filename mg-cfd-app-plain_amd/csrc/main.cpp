@@ -8,7 +8,9 @@
 #include <sched.h>
 #include <unistd.h>
 
+#include <cctype>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,7 +45,28 @@ struct Config {                       // the reference's `config` (src/Base/conf
     int gpus = 1;                     // --gpus N: a single-level input partitioned over N GPUs, a multigrid input one level per GPU
     bool gpus_share_device = false;   // --gpus-share-device: all N ranks on --device (rehearsal on a one-GPU box)
     bool gpus_partition = false;      // --gpus-partition: split every level of a multigrid input over the N GPUs (the default when N > levels)
+    bool output_loads = false;        // --output-loads: the level-0 surface loads of every cycle into surface_loads.* (one GPU only)
+    double loads_ref[5] = {1.0, 1.0, 0.0, 0.0, 0.0};   // --loads-reference=S,c,x,y,z: reference area, length and moment point
 };
+
+// "S,c,x,y,z": five finite numbers, S and c positive; false on anything else
+bool parse_loads_reference(const char *text, double out[5])
+{
+    const char *p = text;
+    for (int k = 0; k < 5; k++) {
+        if (k > 0) {
+            if (*p != ',') return false;
+            p++;
+        }
+        if (*p == '\0' || *p == ',' || std::isspace(static_cast<unsigned char>(*p))) return false;
+        char *end = nullptr;
+        const double v = std::strtod(p, &end);
+        if (end == p || !std::isfinite(v)) return false;
+        out[k] = v;
+        p = end;
+    }
+    return *p == '\0' && out[0] > 0.0 && out[1] > 0.0;
+}
 
 std::string trim(const std::string &s)
 {
@@ -130,7 +153,10 @@ void print_help()
         "  --no-indirect-rw                 Skip the indirect_rw bandwidth probe each RK stage\n"
         "  --fast                           Fast mode: FMA contraction and order-free flux accumulation (results within\n"
         "                                   1e-12 relative of the reference's per sweep, not reproducible bit for bit from run to run)\n"
-        "  --legacy-ordering                Sort edges by (a,b,x,y,z) like the reference built with -DLEGACY_ORDERING\n");
+        "  --legacy-ordering                Sort edges by (a,b,x,y,z) like the reference built with -DLEGACY_ORDERING\n"
+        "  --output-loads                   Write the pressure force and moment on the solid walls and their coefficients\n"
+        "                                   after every cycle to surface_loads.* (CSV; one GPU only)\n"
+        "  --loads-reference=S,c,x,y,z      Reference area, length and moment point of --output-loads (default 1,1,0,0,0)\n");
 }
 
 bool parse_arguments(int argc, char **argv, Config &c)
@@ -160,6 +186,8 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"gpus-share-device", no_argument, nullptr, 1010},
         {"loop-timers", no_argument, nullptr, 1011},
         {"gpus-partition", no_argument, nullptr, 1012},
+        {"output-loads", no_argument, nullptr, 1013},
+        {"loads-reference", required_argument, nullptr, 1014},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -185,6 +213,13 @@ bool parse_arguments(int argc, char **argv, Config &c)
             case 1010: c.gpus_share_device = true; break;
             case 1011: c.loop_timers = true; break;
             case 1012: c.gpus_partition = true; break;
+            case 1013: c.output_loads = true; break;
+            case 1014:
+                if (!parse_loads_reference(optarg, c.loads_ref)) {
+                    std::fprintf(stderr, "ERROR: --loads-reference=%s: expected S,c,x,y,z (five numbers, S and c positive)\n", optarg);
+                    return false;
+                }
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
@@ -338,6 +373,31 @@ int validate_and_dump(const Config &conf, int levels, int mesh_variant, int64_t 
     return 0;
 }
 
+// --output-loads: one row per cycle, the loads and their coefficients (nothing on stdout: it stays the reference's)
+int write_loads_csv(const Config &conf, mgcfd_solver *solver, const std::vector<double> &loads)
+{
+    double ff17[17];
+    if (mgcfd_get_far_field(solver, ff17) != MGCFD_OK) return fail("reading the far field");
+    const std::string path = output_filepath(conf, "surface_loads", 0);
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail(("opening " + path).c_str());
+    std::fprintf(f, "cycle,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz\n");
+    for (int c = 0; c < conf.num_cycles; c++) {
+        const double *row = loads.data() + static_cast<size_t>(c) * 6;
+        double coef[6];
+        if (mgcfd_load_coefficients(ff17, row, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) {
+            std::fclose(f);
+            return fail("computing the load coefficients");
+        }
+        std::fprintf(f, "%d", c + 1);
+        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", row[k]);
+        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
+    return 0;
+}
+
 // --gpus N (multi_gpu.cpp): the same outputs as the one-GPU run from N ranks of this process
 int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int mesh_variant, int problem_size)
 {
@@ -401,6 +461,10 @@ int main(int argc, char **argv)
     const double epoch_at_main = std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count();
     Config conf;
     if (!parse_arguments(argc, argv, conf)) return 1;
+    if (conf.output_loads && conf.gpus > 1) {
+        std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only (loads summed over ranks are not supported)\n");
+        return 1;
+    }
     if (conf.input_file.empty()) {
         std::printf("ERROR: input_file not set\n");
         return 1;
@@ -439,7 +503,9 @@ int main(int argc, char **argv)
     // ---- compute (src/euler3d_cpu_double.cpp:368-698) ----
     std::vector<double> rms(static_cast<size_t>(conf.num_cycles > 0 ? conf.num_cycles : 0));
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = mgcfd_run_cycles(solver, conf.num_cycles, rms.data());
+    std::vector<double> loads(conf.output_loads ? rms.size() * 6 : 0);
+    const int rc = conf.output_loads ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms.data(), loads.data())
+                                     : mgcfd_run_cycles(solver, conf.num_cycles, rms.data());
     const double total_compute_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const bool invalid = rc == MGCFD_ERR_NAN || rc == MGCFD_ERR_NEG_DENSITY || rc == MGCFD_ERR_NEG_ENERGY;
     int64_t bad_cell = -1;
@@ -469,6 +535,7 @@ int main(int argc, char **argv)
                           [&](int which, int ncols, double *out) { (void)ncols; return mgcfd_get_array(solver, 0, which, out); },
                           [&](int level, int64_t *bad) { return mgcfd_check_for_invalid_variables(solver, level, bad); }))
         return EXIT_FAILURE;
+    if (conf.output_loads && write_loads_csv(conf, solver, loads)) return EXIT_FAILURE;
 
     // ---- performance data (src/euler3d_cpu_double.cpp:778-785) ----
     std::string ih, il;

@@ -187,6 +187,11 @@ struct DeviceLevel {
     std::vector<std::pair<int32_t *, int64_t>> halo_plans;   // device id lists of the halo messages
     std::unique_ptr<HaloExchange> hx;    // the C++-side exchange of a partitioned level (mgcfd_rank_set_halo)
     bool has_transfer = false;           // plan to the next-coarser level present
+    // surface loads (mgcfd_surface_loads): one record per solid-wall edge, the per-workgroup sums, the arrival ticket
+    WallRecord *wall_rec = nullptr;
+    int64_t n_wall_rec = 0;
+    double *loads_partial = nullptr;
+    unsigned *loads_ticket = nullptr;
     void *block = nullptr;               // the one allocation behind every array listed at creation (LevelStaging)
     size_t block_bytes = 0;
     bool in_block(const void *p) const { return block && p >= block && p < static_cast<const char *>(block) + block_bytes; }
@@ -235,6 +240,13 @@ struct mgcfd_solver {
     static constexpr int kRmsRing = 4096;
     double *rms_ring = nullptr;                    // level-0 sum of squares of the cycles run since the last read-back
     int *rms_count = nullptr;
+    // surface loads: a [kRmsRing][6] history filled beside rms_ring (row = the cycle's RMS slot), the reference point and
+    // a synchronous call's result on the device; the cycle appends to the history while loads_in_cycle is set
+    double *loads_ring = nullptr, *loads_dev = nullptr;                       // loads_dev: ref [3] | out [6]
+    double loads_ref_host[3] = {0.0, 0.0, 0.0};
+    bool loads_in_cycle = false;
+    bool partitioned = false;                      // made by mgcfd_create_partitioned* (no loads: they would need a sum over ranks)
+    double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
     std::vector<EventPair> pending;
     std::vector<hipEvent_t> free_events;
 
@@ -639,6 +651,8 @@ mgcfd_solver::~mgcfd_solver()
     for (auto &g : cycle_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
     if (rms_ring) (void)hipFree(rms_ring);
     if (rms_count) (void)hipFree(rms_count);
+    if (loads_ring) (void)hipFree(loads_ring);
+    if (loads_dev) (void)hipFree(loads_dev);
     for (auto &p : pending) { (void)hipEventDestroy(p.start); (void)hipEventDestroy(p.stop); }
     for (auto e : free_events) (void)hipEventDestroy(e);
     for (auto &lv : L) {
@@ -722,6 +736,14 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
     std::memcpy(s->ff.fc_my, s->ff17 + 8, sizeof(double) * 3);
     std::memcpy(s->ff.fc_mz, s->ff17 + 11, sizeof(double) * 3);
     std::memcpy(s->ff.fc_de, s->ff17 + 14, sizeof(double) * 3);
+    s->partitioned = n_owned != nullptr;
+    {
+        // derive() (cfd_loops.h:121-148) on the far field, as k_surface_loads evaluates it per node
+        const double *f = s->ff17;
+        const double vx = f[1] / f[0], vy = f[2] / f[0], vz = f[3] / f[0];
+        const double speed_sqd = vx * vx + vy * vy + vz * vz;
+        s->p_inf = (1.4 - 1.0) * (f[4] - 0.5 * f[0] * speed_sqd);
+    }
 
     s->L.resize(static_cast<size_t>(nlevels));
     const bool timing = std::getenv("MGCFD_PLAN_TIMING") != nullptr;      // where the host time of a solver's creation goes (stderr)
@@ -963,6 +985,25 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
             lv.plan.pro.clear(); lv.plan.pro.shrink_to_fit();
         }
         lv.plan.w.clear(); lv.plan.w.shrink_to_fit();
+        // the solid-wall edges (neighbour code -1) as compact records for the surface loads; no host copy is kept
+        lv.n_wall_rec = d.n_boundary;
+        if (d.n_boundary > 0) {
+            std::vector<WallRecord> rec(static_cast<size_t>(d.n_boundary));
+            for (int64_t k = 0; k < d.n_boundary; k++) {
+                const mgcfd_edge &e = lv.edges[static_cast<size_t>(d.boundary_start + k)];
+                if (e.b < 0 || e.b >= nel) throw std::invalid_argument("solid-wall edge with a node out of range");
+                WallRecord &r = rec[static_cast<size_t>(k)];
+                r.x = e.x; r.y = e.y; r.z = e.z;
+                r.cx = d.coords ? d.coords[e.b * 3 + 0] : 0.0;
+                r.cy = d.coords ? d.coords[e.b * 3 + 1] : 0.0;
+                r.cz = d.coords ? d.coords[e.b * 3 + 2] : 0.0;
+                r.node = P.new_of_old[static_cast<size_t>(e.b)];
+                r.pad = 0;
+            }
+            st.upload(lv.wall_rec, std::move(rec));
+            st.alloc(lv.loads_partial, sizeof(double) * 6 * static_cast<size_t>((d.n_boundary + 255) / 256));
+            st.upload(lv.loads_ticket, std::vector<unsigned>(1, 0u));
+        }
     });
     lap("device layouts repacked (a thread per level)");
     if (device_later) device_ready();
@@ -1606,6 +1647,30 @@ int mgcfd_smooth(mgcfd_solver *s, int level, int sweeps)
     });
 }
 
+// ---- surface loads (no reference counterpart: the sum of compute_boundary_flux_edge's momentum term) ----
+// Level `lv`'s loads of its current `variables`, into the synchronous result (loads_dev + 3) or into the history row of
+// the cycle whose RMS was appended last.  Always the non-contracting kernel, whatever MGCFD_OPT_EXACT says.
+static void launch_loads(mgcfd_solver *s, DeviceLevel &lv, bool to_ring)
+{
+    LoadsTask t;
+    t.rec = lv.wall_rec; t.n = lv.n_wall_rec; t.p_inf = s->p_inf; t.ref = s->loads_dev;
+    t.partial = lv.loads_partial; t.ticket = lv.loads_ticket;
+    if (to_ring) { t.ring = s->loads_ring; t.count = s->rms_count; t.cap = mgcfd_solver::kRmsRing; }
+    else t.out = s->loads_dev + 3;
+    exact::launch_surface_loads(s->stream, lv.dp.stride, lv.q, t);
+}
+
+// Loads need the whole level on one solver: refuse a partitioned solver or a rank.
+static void loads_require_whole(const mgcfd_solver *s);
+
+static void loads_prepare(mgcfd_solver *s, const double *ref_point)
+{
+    loads_require_whole(s);
+    if (!s->loads_dev) s->loads_dev = dev_alloc<double>(9);
+    for (int k = 0; k < 3; k++) s->loads_ref_host[k] = ref_point ? ref_point[k] : 0.0;
+    HIP_CHECK(hipMemcpyAsync(s->loads_dev, s->loads_ref_host, sizeof(double) * 3, hipMemcpyHostToDevice, s->stream));
+}
+
 // ---- cycle driver: src/euler3d_cpu_double.cpp:371-694 ----
 // One multigrid cycle of the reference's state machine, unrolled: sweeps on levels
 // 0,1,..,n-1,n-2,..,1 with restrictions on the way up and prolongations on the way down
@@ -1656,17 +1721,27 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
         transfer(false, l, nullptr);                                       // :560-688
         if (l > 0) sweep(l);
     }
+    if (s->loads_in_cycle) launch_loads(s, s->L[0], true);                // (the state the cycle leaves: after the last prolongation)
 }
 
-int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out)
+// loads_out != nullptr (mgcfd_run_cycles_loads): also the level-0 surface loads at the end of every cycle, [cycles][6]
+static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out)
 {
     REQUIRE(s);
     int code = MGCFD_OK, failed_cycle = -1, seq_before = 0, seq_per_cycle = 0;
+    std::vector<double> loads;
     int rc = guarded([&] {
         s->use_device();
         if (!s->rms_ring) {
             s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing);
             s->rms_count = dev_alloc<int>(1);
+        }
+        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = false; } } loads_off{s};
+        if (loads_out) {
+            loads_prepare(s, ref_point);
+            if (!s->loads_ring) s->loads_ring = dev_alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+            s->loads_in_cycle = s->L[0].n_wall_rec > 0;        // (no solid wall: zeros, nothing launched)
+            loads.reserve(static_cast<size_t>(cycles > 0 ? cycles : 0) * 6);
         }
         const size_t nl = s->L.size();
         std::vector<double> sums;
@@ -1686,6 +1761,7 @@ int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out)
                 // already computed (min_ahead), so that is part of the key and looked up per cycle.
                 for (int c = 0; c < chunk; c++) {
                     uint64_t key = (uint64_t(s->opt_exact) << 16) | (uint64_t(s->opt_stage_wg4) << 17) | (uint64_t(s->opt_check) << 8) | uint64_t(s->opt_variant & 0xFF);
+                    key |= uint64_t(s->loads_in_cycle) << 18;      // (the cycle that appends its surface loads)
                     for (size_t l = 0; l < nl && l < 8; l++) key |= (uint64_t(s->L[l].min_ahead) << (24 + l)) | (uint64_t(s->L[l].rot) << (32 + 2 * l)) | (uint64_t(s->L[l].sf_par) << (48 + l));
                     auto it = s->cycle_graphs.find(key);
                     if (it == s->cycle_graphs.end()) {
@@ -1752,6 +1828,11 @@ int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out)
             const size_t at = sums.size();
             sums.resize(at + static_cast<size_t>(chunk));
             HIP_CHECK(hipMemcpyAsync(sums.data() + at, s->rms_ring, sizeof(double) * chunk, hipMemcpyDeviceToHost, s->stream));
+            if (loads_out) {
+                loads.resize((at + static_cast<size_t>(chunk)) * 6, 0.0);
+                if (s->loads_in_cycle)
+                    HIP_CHECK(hipMemcpyAsync(loads.data() + at * 6, s->loads_ring, sizeof(double) * 6 * chunk, hipMemcpyDeviceToHost, s->stream));
+            }
             int seq = 0;
             code = s->read_error(nullptr, &seq);                           // synchronises
             if (att1) {
@@ -1777,6 +1858,13 @@ int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out)
                 rms_out[c] = (c < static_cast<int>(sums.size()) && (failed_cycle < 0 || c < failed_cycle))
                                  ? std::sqrt(sums[static_cast<size_t>(c)] / double(s->L[0].n_owned)) : nan;
         }
+        if (loads_out) {
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            for (int c = 0; c < cycles; c++) {
+                const bool ok = c < static_cast<int>(sums.size()) && (failed_cycle < 0 || c < failed_cycle);
+                for (int k = 0; k < 6; k++) loads_out[c * 6 + k] = ok ? loads[static_cast<size_t>(c) * 6 + static_cast<size_t>(k)] : nan;
+            }
+        }
         HIP_CHECK(hipGetLastError());
     });
     if (rc != MGCFD_OK) return rc;
@@ -1789,6 +1877,8 @@ int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out)
     }
     return code;
 }
+
+int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out) { return run_cycles_impl(s, cycles, rms_out, nullptr, nullptr); }
 
 // ---- state access ----
 static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
@@ -3721,6 +3811,70 @@ int mgcfd_rank_halo_info(const mgcfd_solver *s, int level, int64_t out[4])
     if (level < 0 || level >= static_cast<int>(s->L.size()) || !s->L[static_cast<size_t>(level)].hx) { g_last_error = "the level has no halo lists"; return MGCFD_ERR_ARG; }
     const HaloExchange &hx = *s->L[static_cast<size_t>(level)].hx;
     out[0] = hx.n_boundary; out[1] = hx.n_interior; out[2] = hx.total_send(); out[3] = hx.total_recv();
+    return MGCFD_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Surface loads on the solid walls ("Surface loads")
+// ------------------------------------------------------------------------------------------
+static void loads_require_whole(const mgcfd_solver *s)
+{
+    if (s->partitioned)
+        throw std::invalid_argument("surface loads: the solver holds a partitioned level (mgcfd_create_partitioned*); loads summed "
+                                    "over ranks are not supported");
+    if (g_comms.count(const_cast<mgcfd_solver *>(s)))
+        throw std::invalid_argument("surface loads: the solver is attached as a rank; loads summed over ranks are not supported");
+}
+
+extern "C" {
+
+int mgcfd_surface_loads(mgcfd_solver *s, int level, const double ref_point[3], double out6[6])
+{
+    REQUIRE(s); REQUIRE(out6);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        loads_prepare(s, ref_point);
+        double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (lv.n_wall_rec > 0) {                          // (no solid wall: exact zeros, nothing launched)
+            launch_loads(s, lv, false);
+            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            HIP_CHECK(hipGetLastError());
+        }
+        std::memcpy(out6, got, sizeof(got));
+    });
+}
+
+int mgcfd_run_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
+{
+    REQUIRE(s); REQUIRE(loads_out);
+    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out);
+}
+
+int mgcfd_load_coefficients(const double ff17[17], const double loads6[6], double ref_area, double ref_length, double out6[6])
+{
+    REQUIRE(ff17); REQUIRE(loads6); REQUIRE(out6);
+    if (!(ref_area > 0.0) || !(ref_length > 0.0) || !std::isfinite(ref_area) || !std::isfinite(ref_length)) {
+        g_last_error = "mgcfd_load_coefficients: the reference area and length must be positive and finite";
+        return MGCFD_ERR_ARG;
+    }
+    const double rho = ff17[0];
+    const double vx = ff17[1] / rho, vy = ff17[2] / rho, vz = ff17[3] / rho;
+    const double q = 0.5 * rho * (vx * vx + vy * vy + vz * vz);
+    if (!(q > 0.0) || !std::isfinite(q)) {
+        g_last_error = "mgcfd_load_coefficients: the far field has no positive dynamic pressure";
+        return MGCFD_ERR_ARG;
+    }
+    const double alpha = std::atan2(vy, vx);              // the angle of attack lies in the x-y plane (cfd_loops.h:85-104)
+    const double ca = std::cos(alpha), sa = std::sin(alpha);
+    const double qs = q * ref_area, qsc = qs * ref_length;
+    out6[0] = (loads6[0] * ca + loads6[1] * sa) / qs;     // CD
+    out6[1] = (-loads6[0] * sa + loads6[1] * ca) / qs;    // CL
+    out6[2] = loads6[2] / qs;                             // CS
+    for (int k = 0; k < 3; k++) out6[3 + k] = loads6[3 + k] / qsc;
     return MGCFD_OK;
 }
 

@@ -148,6 +148,9 @@ _SIGNATURES = [
     ("mgcfd_group_sweeps_rms", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_group_rms", C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_group_synchronize", C.c_int, [_vp]),
+    ("mgcfd_surface_loads", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_run_cycles_loads", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_load_coefficients", C.c_int, [_vp, _vp, C.c_double, C.c_double, _vp]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -283,6 +286,22 @@ def plan_audit(levels: Sequence[dict], mesh_variant: int, n_owned=None, order_ke
     if rc not in (0, 1):
         _check(lib, rc)
     return buf.value.decode()
+
+
+def load_coefficients(ff17, loads, ref_area: float = 1.0, ref_length: float = 1.0) -> np.ndarray:
+    """Host only (mgcfd_load_coefficients): CD CL CS CMx CMy CMz of a loads vector ``[6]`` or history ``[n, 6]`` against the
+    far field ``ff17`` (Solver.far_field())."""
+    lib = load_library()
+    ff = np.ascontiguousarray(ff17, dtype=np.float64).reshape(17)
+    rows = np.ascontiguousarray(loads, dtype=np.float64)
+    flat = rows.reshape(-1, 6)
+    out = np.zeros_like(flat)
+    for k in range(len(flat)):
+        row = np.ascontiguousarray(flat[k])
+        res = np.zeros(6)
+        _check(lib, lib.mgcfd_load_coefficients(_ptr(ff), _ptr(row), float(ref_area), float(ref_length), _ptr(res)))
+        out[k] = res
+    return out.reshape(rows.shape)
 
 
 class Solver:
@@ -461,10 +480,28 @@ class Solver:
     def smooth(self, l: int, sweeps: int = 1):
         self._c(self.lib.mgcfd_smooth(self.handle, l, sweeps))
 
-    def run_cycles(self, cycles: int) -> np.ndarray:
+    def run_cycles(self, cycles: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
+        """The RMS of every cycle; with ``loads=True`` also the level-0 surface loads at the end of every cycle:
+        ``(rms, loads[cycles, 6])`` (Fx Fy Fz Mx My Mz about ``ref_point``; mgcfd_run_cycles_loads)."""
         rms = np.zeros(max(cycles, 1))
-        self._c(self.lib.mgcfd_run_cycles(self.handle, cycles, _ptr(rms)))
-        return rms[:cycles]
+        if not loads:
+            self._c(self.lib.mgcfd_run_cycles(self.handle, cycles, _ptr(rms)))
+            return rms[:cycles]
+        hist = np.zeros((max(cycles, 1), 6))
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        self._c(self.lib.mgcfd_run_cycles_loads(self.handle, cycles, _ptr(ref), _ptr(rms), _ptr(hist)))
+        return rms[:cycles], hist[:cycles]
+
+    def surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """Fx Fy Fz Mx My Mz: the pressure loads on level ``level``'s solid walls in its current state (mgcfd_surface_loads)."""
+        out = np.zeros(6)
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        self._c(self.lib.mgcfd_surface_loads(self.handle, level, _ptr(ref), _ptr(out)))
+        return out
+
+    def load_coefficients(self, loads, ref_area: float = 1.0, ref_length: float = 1.0) -> np.ndarray:
+        """CD CL CS CMx CMy CMz of one loads vector, or of every row of a ``[n, 6]`` history, against this solver's far field."""
+        return load_coefficients(self.far_field(), loads, ref_area, ref_length)
 
     # ---- state ----
     def get(self, l: int, name: str) -> np.ndarray:
