@@ -626,6 +626,9 @@ __device__ __forceinline__ void boundary_rows(const NodeQ &me, const FluxC &fm, 
 
 // ROLE (fused stages only): 0 = may finish compute_step_factor (first stage), 2 = may write the residual, its
 // squares and the look-ahead (last stage), 1 = neither: the paths a stage cannot take are compiled out.
+// 3 = a last stage that also leaves the next sweep's partial minima, 4 = ... fvcorr's next step factors instead,
+// 5 = a middle stage that applies the first stage's time_step while it stages its input (FusedStep::vin_flux); stage_role()
+// beside launch_flux reads the role off a stage's arguments.
 // TAIL: the level has long rows (TailPlan): the per-node loop stops at the tile's row limit and the workgroup
 // evaluates the remaining entries together (see below).
 // WMODE: 0 = the length factor k recomputed from the row's weights, 1 = k streamed with them, 2 = indexed weights (above).
@@ -2776,83 +2779,107 @@ void launch_step_factor_legacy(hipStream_t st, int64_t nel, int64_t stride, cons
                                double *old_variables)
 { hipLaunchKernelGGL(k_step_factor_legacy, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, q, volumes, sf, old_variables); }
 
+// ---- the flux launch: which kernel, which instantiation ------------------------------------------------------------------
+// A run-time value as a compile-time constant: f(std::integral_constant<int, V>) for the V of the list that equals v.
+template <int... Vs, typename F>
+static void with_constant(int v, F &&f)
+{ if (!((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...)) throw std::logic_error("no kernel is built for this value"); }
+template <typename F>
+static void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// The three kinds of flux launch as f(FUSE, ACC): a fused stage, '+=' into fluxes[], '='.
+template <typename F>
+static void with_kind(bool fused, bool accumulate, F &&f)
+{
+    if (fused) f(std::true_type{}, std::false_type{});
+    else if (accumulate) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+
+// What every flux kernel is launched with.
+struct FluxLaunch {
+    hipStream_t st; const DevicePlan &p; const double *q; const FarField &ff; double *fluxes; int classes; const FusedStep &fs;
+    dim3 grid; int64_t nel_arg;         // the launch's workgroups; the nodes it treats as present (FusedStep::nel_active)
+};
+
+template <int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false, bool SLIM = false>
+static void launch_tile(const FluxLaunch &a, const StagePush &push = StagePush{})
+{
+    const DevicePlan &p = a.p;
+    // 3 tiles of 52.4 KiB LDS fit a CU (preprocess.hpp: kTileCap) => at least 3 waves per SIMD wanted (168 registers).  The two long-row instantiations that
+    // do not fit them — the kernel-granular '+=' launch and the split sweep's absorbed first stage, both off the sweep path —
+    // are built for 2 waves per SIMD instead of spilling 20-36 bytes per lane.  (SLIM: four workgroups of 40,896 B per CU.)
+    constexpr int MINW = SLIM ? 4 : ((TAIL && (ACC || ROLE == 5)) ? 2 : 3);
+    hipLaunchKernelGGL((k_flux_tile<MINW, WMODE, FUSE, ACC, ROLE, TAIL, PUSH, SLIM>), a.grid, dim3(kBlock), 0, a.st, a.q, p.tile_halo,
+                       uint32_t(a.grid.x), p.pad_row, p.stride, a.nel_arg, p.slice_row0, p.rows_int, p.rows_bnd,
+                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, a.ff, a.fluxes, a.classes, a.fs, p.tail, p.gat16,
+                       p.te_chunk_ptr, p.te_w3, push);
+}
+
+#ifdef MGCFD_ORDER_FREE
+// (WIDE: a level with halos beyond the shared table: the kernel's own table of kFreeHaloStride ids per tile, 768 LDS images)
+template <bool FUSE, bool ACC, int CAP, bool LONG, bool WIDE = false, int ROLE = -1>
+static void launch_free(const FluxLaunch &a)
+{
+    const DevicePlan &p = a.p;
+    hipLaunchKernelGGL((k_flux_free<FUSE, ACC, CAP, LONG, WIDE, ROLE>), a.grid, dim3(kBlock), 0, a.st, a.q, WIDE ? p.free_halo : p.tile_halo, uint32_t(p.n_tiles),
+                       p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.slice_row0,
+                       p.rows_int, p.rows_bnd, p.nbr16, p.w, a.ff, a.fluxes, a.classes, a.fs);
+}
+
+// The order-free kernel's role-specialised instantiations know roles 0-3 only; everything else runs its generic epilogue (-1).
+static int free_stage_role(const FusedStep &fs, int role)
+{
+    if (fs.next_legacy_sf) return -1;                   // fvcorr's look-ahead, whatever else the stage does: the generic epilogue
+    if (role == 1 && fs.sumsq_partial) return 2;        // sums of squares without residuals[] (a lazy residual): a last stage all the same
+    return role;
+}
+#endif
+
+// The role of a fused stage (k_flux_tile's ROLE), read off its arguments; a launch that is no stage runs as role 1.
+static inline int stage_role(const FusedStep &fs)
+{
+    if (fs.vin_flux) return 5;
+    if (fs.partial_min) return 0;
+    if (fs.next_partial_min) return 3;
+    if (fs.next_legacy_sf) return 4;
+    return fs.residuals ? 2 : 1;
+}
+
+// (role 0 takes the sweep's start state from its own record instead of loading old_variables)
+static void check_first_stage_input(int role, const double *q, const FusedStep &fs)
+{ if (role == 0 && q != fs.old_variables) throw std::logic_error("a first stage whose input is not the sweep's start state"); }
+
 void launch_flux(hipStream_t st, const DevicePlan &p, const double *q, const FarField &ff, double *fluxes,
                  int classes, int accumulate, int variant, const FusedStep *fused, const StagePush *push)
 {
-    const dim3 block(kBlock);
     FusedStep fs{};
     if (fused) fs = *fused;
     const bool part = fused && fs.tile_list;                        // part of the level's tiles (node gather only)
-    const int64_t nel_arg = (fused && fs.nel_active > 0) ? fs.nel_active : p.nel;
-    const dim3 grid(part ? fs.n_list : p.n_tiles);
     if (part && fs.n_list <= 0) return;
-
-    // 3 tiles of 52.4 KiB LDS fit a CU (preprocess.hpp: kTileCap) => at least 3 waves per SIMD wanted (168 registers).  The two long-row instantiations that
-    // do not fit them — the kernel-granular '+=' launch and the split sweep's absorbed first stage, both off the sweep path —
-    // are built for 2 waves per SIMD instead of spilling 20-36 bytes per lane.
-#define MGCFD_TILE_LAUNCH_T(WMODE, FUSE, ACC, ROLE, TAIL)                                                      \
-    hipLaunchKernelGGL((k_flux_tile<((TAIL) && ((ACC) || (ROLE) == 5)) ? 2 : 3, WMODE, FUSE, ACC, ROLE, TAIL>), grid, block, 0, st, q, p.tile_halo,     \
-                       uint32_t(grid.x), p.pad_row, p.stride, nel_arg, p.slice_row0, p.rows_int, p.rows_bnd, \
-                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, classes, fs, p.tail, p.gat16,     \
-                       p.te_chunk_ptr, p.te_w3, StagePush{})
+    const FluxLaunch a{st, p, q, ff, fluxes, classes, fs, dim3(part ? fs.n_list : p.n_tiles), (fused && fs.nel_active > 0) ? fs.nel_active : p.nel};
+    // fused stages: the role decides which optional paths exist in the launched kernel
+    const int role = fused ? stage_role(fs) : 1;
     // levels with long rows (tetrahedral meshes, hubs) run the instantiation that hands them to the workgroup
     const bool tail = p.has_tail && (classes & 1);
+    const bool loadk = (variant & 1) == 0;      // odd variants recompute k = -|e|*s*0.5 from the weights
     // a stage that sends its own message (StagePush): fused stages over a tile list, roles 0-4, k streamed or recomputed
     if (push && fused && part && !fs.vin_flux) {
-        const int role_p = fs.partial_min ? 0 : (fs.next_partial_min ? 3 : (fs.next_legacy_sf ? 4 : (fs.residuals ? 2 : 1)));
-#define MGCFD_PUSH_LAUNCH_T(WMODE, ROLE, TAIL)                                                                  \
-    hipLaunchKernelGGL((k_flux_tile<3, WMODE, true, false, ROLE, TAIL, true>), grid, block, 0, st, q, p.tile_halo,     \
-                       uint32_t(grid.x), p.pad_row, p.stride, nel_arg, p.slice_row0, p.rows_int, p.rows_bnd, \
-                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, classes, fs, p.tail, p.gat16,     \
-                       p.te_chunk_ptr, p.te_w3, *push)
-#define MGCFD_PUSH_LAUNCH_R(WMODE, TAIL)                                                                        \
-    do {                                                                                                       \
-        if (role_p == 0) MGCFD_PUSH_LAUNCH_T(WMODE, 0, TAIL);                                                  \
-        else if (role_p == 2) MGCFD_PUSH_LAUNCH_T(WMODE, 2, TAIL);                                             \
-        else if (role_p == 3) MGCFD_PUSH_LAUNCH_T(WMODE, 3, TAIL);                                             \
-        else if (role_p == 4) MGCFD_PUSH_LAUNCH_T(WMODE, 4, TAIL);                                             \
-        else MGCFD_PUSH_LAUNCH_T(WMODE, 1, TAIL);                                                              \
-    } while (0)
-        if (role_p == 0 && q != fs.old_variables) throw std::logic_error("a first stage whose input is not the sweep's start state");
-        const bool k_streamed = (variant & 1) == 0;
-        if (tail) { if (k_streamed) MGCFD_PUSH_LAUNCH_R(1, true); else MGCFD_PUSH_LAUNCH_R(0, true); }
-        else { if (k_streamed) MGCFD_PUSH_LAUNCH_R(1, false); else MGCFD_PUSH_LAUNCH_R(0, false); }
-#undef MGCFD_PUSH_LAUNCH_R
-#undef MGCFD_PUSH_LAUNCH_T
+        check_first_stage_input(role, q, fs);
+        with_bool(loadk, [&](auto K) { with_bool(tail, [&](auto T) { with_constant<0, 1, 2, 3, 4>(role, [&](auto R) {
+            launch_tile<decltype(K)::value ? 1 : 0, true, false, decltype(R)::value, decltype(T)::value, true>(a, *push);
+        }); }); });
         return;
     }
-    // variant bit 4 (16): indexed weights — every edge's weights once per tile (needs the tile edge lists: p.edge_once)
-    const bool indexed = (variant & 16) && p.edge_once && p.te_w3 && !tail;
-#define MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, ROLE)                                                            \
-    do {                                                                                                       \
-        if (tail) MGCFD_TILE_LAUNCH_T(LOADK ? 1 : 0, FUSE, ACC, ROLE, true);                                   \
-        else if (indexed) MGCFD_TILE_LAUNCH_T(2, FUSE, ACC, ROLE, false);                                      \
-        else MGCFD_TILE_LAUNCH_T(LOADK ? 1 : 0, FUSE, ACC, ROLE, false);                                       \
-    } while (0)
-    // fused stages: the role decides which optional paths exist in the launched kernel
-    const int role = !fused ? 1 : (fs.vin_flux ? 5 : fs.partial_min ? 0 : (fs.next_partial_min ? 3 : (fs.next_legacy_sf ? 4 : (fs.residuals ? 2 : 1))));
-    // (role 0 takes the sweep's start state from its own record instead of loading old_variables)
-    if (role == 0 && q != fs.old_variables) throw std::logic_error("a first stage whose input is not the sweep's start state");
-#define MGCFD_TILE_LAUNCH(LOADK, FUSE, ACC)                                                                    \
-    do {                                                                                                       \
-        if (role == 0) MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, 0);                                               \
-        else if (role == 2) MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, 2);                                          \
-        else if (role == 3) MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, 3);                                          \
-        else if (role == 4) MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, 4);                                          \
-        else if (role == 5) MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, 5);                                          \
-        else MGCFD_TILE_LAUNCH_R(LOADK, FUSE, ACC, 1);                                                         \
-    } while (0)
+    check_first_stage_input(role, q, fs);
     // variant bit 2: the two-phase design point (never for the fused stages: they keep the flux in registers)
     if ((variant & 4) && !fused && p.edge_flux) {
         if (classes & 1)
-            hipLaunchKernelGGL(k_fission_edge_flux, dim3(grid_for(p.n_edges)), block, 0, st, p.n_edges, p.n_edges_pad, p.stride, q,
+            hipLaunchKernelGGL(k_fission_edge_flux, dim3(grid_for(p.n_edges)), dim3(kBlock), 0, st, p.n_edges, p.n_edges_pad, p.stride, q,
                                p.fe_ab, p.fe_w, p.edge_flux);
-        if (accumulate)
-            hipLaunchKernelGGL(k_fission_node_sum<true>, grid, block, 0, st, p.nel, p.stride, p.n_edges_pad, q, p.slice_row0,
+        with_bool(accumulate != 0, [&](auto A) {
+            hipLaunchKernelGGL(k_fission_node_sum<decltype(A)::value>, a.grid, dim3(kBlock), 0, st, p.nel, p.stride, p.n_edges_pad, q, p.slice_row0,
                                p.rows_int, p.rows_bnd, p.row_edge, p.nbr16, p.w, p.edge_flux, ff, fluxes, classes);
-        else
-            hipLaunchKernelGGL(k_fission_node_sum<false>, grid, block, 0, st, p.nel, p.stride, p.n_edges_pad, q, p.slice_row0,
-                               p.rows_int, p.rows_bnd, p.row_edge, p.nbr16, p.w, p.edge_flux, ff, fluxes, classes);
+        });
         return;
     }
 #ifdef MGCFD_ORDER_FREE
@@ -2860,113 +2887,71 @@ void launch_flux(hipStream_t st, const DevicePlan &p, const double *q, const Far
     // (not for a launch that must leave the ghost slots alone — fs.nel_active, a partitioned level in direct mode: this kernel
     //  writes every node of the level)
     if ((variant & 64) && p.free_rows && (classes & 1) && !(fused && fs.vin_flux) && !part && !(fused && fs.nel_active > 0)) {
-#define MGCFD_FREE_LAUNCH_L(FUSE, ACC, CAP, LONG)                                                               \
-    hipLaunchKernelGGL((k_flux_free<FUSE, ACC, CAP, LONG>), grid, block, 0, st, q, p.tile_halo, uint32_t(p.n_tiles), \
-                       p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.slice_row0,               \
-                       p.rows_int, p.rows_bnd, p.nbr16, p.w, ff, fluxes, classes, fs)
-#define MGCFD_FREE_LAUNCH_C(FUSE, ACC, CAP)                                                                     \
-    do { if (p.hr_max_rows > kHalfMaxRows) MGCFD_FREE_LAUNCH_L(FUSE, ACC, CAP, true); else MGCFD_FREE_LAUNCH_L(FUSE, ACC, CAP, false); } while (0)
-        // (a level with halos beyond the shared table: the kernel's own table of kFreeHaloStride ids per tile, 768 LDS images)
-#define MGCFD_FREE_LAUNCH_W(FUSE, ACC)                                                                          \
-    hipLaunchKernelGGL((k_flux_free<FUSE, ACC, kTile + kFreeHaloStride, true, true>), grid, block, 0, st, q, p.free_halo, uint32_t(p.n_tiles), \
-                       p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.slice_row0,               \
-                       p.rows_int, p.rows_bnd, p.nbr16, p.w, ff, fluxes, classes, fs)
         // (four workgroups per CU where every tile's halo fits the smaller LDS image, three otherwise; MGCFD_FREE_WG3=1: always three, for A/B)
         static const bool wg3 = std::getenv("MGCFD_FREE_WG3") && std::atoi(std::getenv("MGCFD_FREE_WG3")) != 0;
-#define MGCFD_FREE_LAUNCH(FUSE, ACC)                                                                            \
-    do { if (p.free_wide) MGCFD_FREE_LAUNCH_W(FUSE, ACC);                                                       \
-         else if (p.halo_max <= kFreeCap4 - kTile && !wg3) MGCFD_FREE_LAUNCH_C(FUSE, ACC, kFreeCap4); else MGCFD_FREE_LAUNCH_C(FUSE, ACC, kTileCap); } while (0)
+        static const bool no_roles = std::getenv("MGCFD_FREE_NO_ROLES") && std::atoi(std::getenv("MGCFD_FREE_NO_ROLES")) != 0;   // (A/B)
+        const bool cap4 = p.halo_max <= kFreeCap4 - kTile && !wg3;
         // fused stages of levels on the fast path (halos within the smaller LDS image, at most five half rows per lane): the
         // role-specialised instantiations; fvcorr's look-ahead and every other configuration: the generic epilogue
-        const int role_f = !fused ? -1 : (fs.next_legacy_sf ? -1 : (fs.partial_min ? 0 : (fs.next_partial_min ? 3 : ((fs.residuals || fs.sumsq_partial) ? 2 : 1))));
-        static const bool no_roles = std::getenv("MGCFD_FREE_NO_ROLES") && std::atoi(std::getenv("MGCFD_FREE_NO_ROLES")) != 0;   // (A/B)
-        const bool fast_path = !p.free_wide && p.halo_max <= kFreeCap4 - kTile && !wg3 && p.hr_max_rows <= kHalfMaxRows;
-#define MGCFD_FREE_LAUNCH_ROLE(ROLE)                                                                            \
-    hipLaunchKernelGGL((k_flux_free<true, false, kFreeCap4, false, false, ROLE>), grid, block, 0, st, q, p.tile_halo, uint32_t(p.n_tiles), \
-                       p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.slice_row0,               \
-                       p.rows_int, p.rows_bnd, p.nbr16, p.w, ff, fluxes, classes, fs)
-        if (fused && role_f >= 0 && fast_path && !no_roles && !(role_f == 0 && q != fs.old_variables)) {
-            if (role_f == 0) MGCFD_FREE_LAUNCH_ROLE(0);
-            else if (role_f == 2) MGCFD_FREE_LAUNCH_ROLE(2);
-            else if (role_f == 3) MGCFD_FREE_LAUNCH_ROLE(3);
-            else MGCFD_FREE_LAUNCH_ROLE(1);
+        // (a first stage with another input than the sweep's start state has been refused above)
+        const int role_f = fused ? free_stage_role(fs, role) : -1;
+        if (role_f >= 0 && !p.free_wide && cap4 && p.hr_max_rows <= kHalfMaxRows && !no_roles) {
+            with_constant<0, 1, 2, 3>(role_f, [&](auto R) { launch_free<true, false, kFreeCap4, false, false, decltype(R)::value>(a); });
+            return;
         }
-        else if (fused) MGCFD_FREE_LAUNCH(true, false);
-        else if (accumulate) MGCFD_FREE_LAUNCH(false, true);
-        else MGCFD_FREE_LAUNCH(false, false);
-#undef MGCFD_FREE_LAUNCH_ROLE
-#undef MGCFD_FREE_LAUNCH_C
-#undef MGCFD_FREE_LAUNCH_L
-#undef MGCFD_FREE_LAUNCH_W
-#undef MGCFD_FREE_LAUNCH
+        with_kind(fused, accumulate, [&](auto F, auto A) {
+            constexpr bool FUSE = decltype(F)::value, ACC = decltype(A)::value;
+            if (p.free_wide) launch_free<FUSE, ACC, kTile + kFreeHaloStride, true, true>(a);
+            else with_bool(p.hr_max_rows > kHalfMaxRows, [&](auto L) {
+                if (cap4) launch_free<FUSE, ACC, kFreeCap4, decltype(L)::value>(a); else launch_free<FUSE, ACC, kTileCap, decltype(L)::value>(a);
+            });
+        });
         return;
     }
 #endif
     // variant bit 5 (32): half rows — every edge evaluated once per tile by one of its end points (k_flux_half); the
     // split sweep's absorbed first stage (role 5) stays with the node gather
     if ((variant & 32) && p.half && (classes & 1) && !(fused && fs.vin_flux) && !part) {
-#define MGCFD_HALF_LAUNCH(FUSE, ACC)                                                                            \
-    hipLaunchKernelGGL((k_flux_half<FUSE, ACC>), grid, block, 0, st, q, p.tile_halo, uint32_t(p.n_tiles),       \
-                       p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.hg16, p.slice_row0,       \
-                       p.rows_int, p.rows_bnd, p.pad_row, p.nbr16, p.w, ff, fluxes, classes, fs)
-        if (fused) MGCFD_HALF_LAUNCH(true, false);
-        else if (accumulate) MGCFD_HALF_LAUNCH(false, true);
-        else MGCFD_HALF_LAUNCH(false, false);
-#undef MGCFD_HALF_LAUNCH
+        with_kind(fused, accumulate, [&](auto F, auto A) {
+            hipLaunchKernelGGL((k_flux_half<decltype(F)::value, decltype(A)::value>), a.grid, dim3(kBlock), 0, st, q, p.tile_halo, uint32_t(p.n_tiles),
+                               p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.hg16, p.slice_row0,
+                               p.rows_int, p.rows_bnd, p.pad_row, p.nbr16, p.w, ff, fluxes, classes, fs);
+        });
         return;
     }
-    const bool loadk = (variant & 1) == 0;      // odd variants recompute k = -|e|*s*0.5 from the weights
     // variants 2, 3: every edge evaluated once per tile (needs the internal class and a level whose
     // tiles fit the edge-once limits; otherwise the node gather below)
     if ((variant & 2) && p.edge_once && (classes & 1) && !part) {
-#define MGCFD_EO_LAUNCH(LOADK, FUSE, ACC)                                                                      \
-    hipLaunchKernelGGL((k_flux_edge_once<LOADK, FUSE, ACC>), grid, block, 0, st, q, p.tile_halo,               \
-                       uint32_t(p.n_tiles), p.pad_row, p.stride, p.nel, p.te_chunk_ptr, p.te_count,            \
-                       p.pad_chunk, classes, p.slice_row0, p.rows_int, p.rows_bnd, p.nbr16, p.w, p.gat16,      \
-                       p.te_slots, p.te_w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, fs)
-        if (fused) {
-            if (loadk) MGCFD_EO_LAUNCH(true, true, false); else MGCFD_EO_LAUNCH(false, true, false);
-        } else if (accumulate) {
-            if (loadk) MGCFD_EO_LAUNCH(true, false, true); else MGCFD_EO_LAUNCH(false, false, true);
-        } else {
-            if (loadk) MGCFD_EO_LAUNCH(true, false, false); else MGCFD_EO_LAUNCH(false, false, false);
-        }
-#undef MGCFD_EO_LAUNCH
+        with_bool(loadk, [&](auto K) { with_kind(fused, accumulate, [&](auto F, auto A) {
+            hipLaunchKernelGGL((k_flux_edge_once<decltype(K)::value, decltype(F)::value, decltype(A)::value>), a.grid, dim3(kBlock), 0, st, q, p.tile_halo,
+                               uint32_t(p.n_tiles), p.pad_row, p.stride, p.nel, p.te_chunk_ptr, p.te_count,
+                               p.pad_chunk, classes, p.slice_row0, p.rows_int, p.rows_bnd, p.nbr16, p.w, p.gat16,
+                               p.te_slots, p.te_w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, fs);
+        }); });
         return;
     }
+    // variant bit 4 (16): indexed weights — every edge's weights once per tile (needs the tile edge lists: p.edge_once)
+    const bool indexed = (variant & 16) && p.edge_once && p.te_w3 && !tail;
 #ifndef MGCFD_ORDER_FREE
     // kVariantStageWg4 (the bit-identical stages, solver.cpp): four workgroups per CU with 80-byte records where every tile
     // halo fits kTileCap4 - kTile slots — roles 0-4 of levels without long rows, k recomputed or streamed
     if (fused && (variant & kVariantStageWg4) && stage_wg4_fits(p) && !indexed && role != 5) {
-#define MGCFD_SLIM_LAUNCH_T(WMODE, ROLE)                                                                        \
-    hipLaunchKernelGGL((k_flux_tile<4, WMODE, true, false, ROLE, false, false, true>), grid, block, 0, st, q, p.tile_halo, \
-                       uint32_t(grid.x), p.pad_row, p.stride, nel_arg, p.slice_row0, p.rows_int, p.rows_bnd, \
-                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, classes, fs, p.tail, p.gat16,     \
-                       p.te_chunk_ptr, p.te_w3, StagePush{})
-#define MGCFD_SLIM_LAUNCH_R(WMODE)                                                                              \
-    do {                                                                                                       \
-        if (role == 0) MGCFD_SLIM_LAUNCH_T(WMODE, 0);                                                          \
-        else if (role == 2) MGCFD_SLIM_LAUNCH_T(WMODE, 2);                                                     \
-        else if (role == 3) MGCFD_SLIM_LAUNCH_T(WMODE, 3);                                                     \
-        else if (role == 4) MGCFD_SLIM_LAUNCH_T(WMODE, 4);                                                     \
-        else MGCFD_SLIM_LAUNCH_T(WMODE, 1);                                                                    \
-    } while (0)
-        if (loadk) MGCFD_SLIM_LAUNCH_R(1); else MGCFD_SLIM_LAUNCH_R(0);
-#undef MGCFD_SLIM_LAUNCH_R
-#undef MGCFD_SLIM_LAUNCH_T
+        with_bool(loadk, [&](auto K) { with_constant<0, 1, 2, 3, 4>(role, [&](auto R) {
+            launch_tile<decltype(K)::value ? 1 : 0, true, false, decltype(R)::value, false, false, true>(a);
+        }); });
         return;
     }
 #endif
-    if (fused) {
-        if (loadk) MGCFD_TILE_LAUNCH(true, true, false); else MGCFD_TILE_LAUNCH(false, true, false);
-    } else if (accumulate) {
-        if (loadk) MGCFD_TILE_LAUNCH(true, false, true); else MGCFD_TILE_LAUNCH(false, false, true);
-    } else {
-        if (loadk) MGCFD_TILE_LAUNCH(true, false, false); else MGCFD_TILE_LAUNCH(false, false, false);
-    }
-#undef MGCFD_TILE_LAUNCH
-#undef MGCFD_TILE_LAUNCH_R
-#undef MGCFD_TILE_LAUNCH_T
+    // the node gather: WMODE 2 on levels without long rows only; a launch that is no stage has no role (1)
+    with_constant<0, 1, 2>(indexed ? 2 : (loadk ? 1 : 0), [&](auto W) { with_bool(tail, [&](auto T) {
+        constexpr int WMODE = decltype(W)::value;
+        constexpr bool TAIL = decltype(T)::value;
+        if constexpr (!(WMODE == 2 && TAIL)) {
+            if (fused) with_constant<0, 1, 2, 3, 4, 5>(role, [&](auto R) { launch_tile<WMODE, true, false, decltype(R)::value, TAIL>(a); });
+            else if (accumulate) launch_tile<WMODE, false, true, 1, TAIL>(a);
+            else launch_tile<WMODE, false, false, 1, TAIL>(a);
+        }
+    }); });
 }
 
 // The practical ceiling of the flux launch's data movement (bench.py: roofline.practical_ceiling_us): a tile-shaped STREAM of
@@ -3011,12 +2996,10 @@ void launch_indirect_rw(hipStream_t st, const DevicePlan &p, const double *q, do
     // through the flux kernel's LDS tiles where the level allows it (no halo node left outside LDS, no long rows);
     // variant bit 3 (8) forces the plain L1 gather
     if (p.lds_complete && !p.has_tail && !(variant & 8)) {
-        if ((variant & 1) == 0)
-            hipLaunchKernelGGL((k_indirect_rw_tile<true>), dim3(p.n_tiles), dim3(kBlock), 0, st, q, p.tile_halo, uint32_t(p.n_tiles),
+        with_bool((variant & 1) == 0, [&](auto K) {
+            hipLaunchKernelGGL((k_indirect_rw_tile<decltype(K)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st, q, p.tile_halo, uint32_t(p.n_tiles),
                                p.pad_row, p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, fluxes);
-        else
-            hipLaunchKernelGGL((k_indirect_rw_tile<false>), dim3(p.n_tiles), dim3(kBlock), 0, st, q, p.tile_halo, uint32_t(p.n_tiles),
-                               p.pad_row, p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, fluxes);
+        });
         return;
     }
     hipLaunchKernelGGL(k_indirect_rw, dim3(p.n_tiles), dim3(kBlock), 0, st, p.nel, p.stride, q,

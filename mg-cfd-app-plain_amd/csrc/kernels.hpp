@@ -14,8 +14,7 @@
     void launch_step_factor_legacy(hipStream_t, int64_t nel, int64_t stride, const double *q, const double *volumes, \
                                    double *sf, double *old_variables);                                               \
     void launch_flux(hipStream_t, const DevicePlan &, const double *q, const FarField &, double *fluxes,             \
-                     int classes, int accumulate, int variant, const FusedStep *fused,                               \
-                     const StagePush *push = nullptr);                                                               \
+                     int classes, int accumulate, int variant, const FusedStep *fused, const StagePush *push);       \
     void launch_indirect_rw(hipStream_t, const DevicePlan &, const double *q, double *fluxes, int variant);                       \
     void launch_stream_tiles(hipStream_t, int n_tiles, const double *src, double *dst, int64_t rd_total, int64_t wr_total);      \
     void launch_time_step(hipStream_t, int64_t nel, int64_t stride, int j, double *sf, double *fluxes,               \
@@ -58,3 +57,15 @@
 
 MGCFD_DECLARE_LAUNCHERS(exact)
 MGCFD_DECLARE_LAUNCHERS(fast)
+
+// The launchers whose numeric flavour follows MGCFD_OPT_EXACT (solver.cpp: mgcfd_solver::k() holds one table per flavour).
+// Everything else is called as exact:: — those kernels do no arithmetic that contraction could change.
+namespace mgcfd {
+struct Launchers {
+    decltype(exact::launch_step_factor_local) *step_factor_local;    decltype(exact::launch_step_factor_apply) *step_factor_apply;
+    decltype(exact::launch_step_factor_legacy) *step_factor_legacy;  decltype(exact::launch_flux) *flux;
+    decltype(exact::launch_indirect_rw) *indirect_rw;                decltype(exact::launch_time_step) *time_step;
+    decltype(exact::launch_residual) *residual;                      decltype(exact::launch_sumsq) *sumsq;
+    decltype(exact::launch_restrict) *restrict_;                     decltype(exact::launch_prolong) *prolong;
+};
+}

@@ -160,6 +160,9 @@ struct DeviceLevel {
     double *state[3] = {nullptr, nullptr, nullptr};
     int rot = 0;
     void apply_rot() { q = state[rot % 3]; q_alt = state[(rot + 1) % 3]; old_variables = state[(rot + 2) % 3]; }
+    // The end of a fused sweep: variables = b1 (the last stage's result: stage_out, where a sweep keeps it, needs no update),
+    // q_alt = b2, old_variables = start.  ahead: the last stage looked ahead (min_ahead).
+    void finish_sweep(bool ahead) { rot = (rot + 1) % 3; apply_rot(); min_ahead = ahead; }
     double *tile_sumsq = nullptr;        // [n_tiles] per-tile sums of squares of the residuals, written by a last stage on request
     bool want_sumsq = false;             // the next fused sweep's last stage also fills tile_sumsq (cycle driver, level 0)
     bool have_sumsq = false;             // ... and did
@@ -203,6 +206,34 @@ struct DeviceLevel {
     int64_t att_sweeps = 0, att_sweeps_sampled = 0;      // smoothing sweeps (flux, compute_step, time_step, indirect_rw run together)
     int64_t att_calls[MGCFD_NUM_LOOPS] = {0}, att_calls_sampled[MGCFD_NUM_LOOPS] = {0};   // restrict (booked on the coarse level) and prolong
 };
+
+// Where a sweep's first stage (or time_step) takes the global time step's minimum from.
+// None: the step factors are final (local time step, or not a first stage); Partials: the workgroups' partial minima (partial_min);
+// Scalar: the reduced — on a rank: all-reduced — scalar (min_dt); List: a list of rank minima (StageArgs::min_list)
+enum class ApplyMin { None, Partials, Scalar, List };
+// What one fused Runge-Kutta stage does beside flux + time_step (mgcfd_solver::op_fused_stage); a caller names what it means.
+struct StageArgs {
+    ApplyMin apply_min = ApplyMin::None;
+    const double *min_list = nullptr; int n_min = 0;        // ApplyMin::List
+    bool with_residual = false;              // last stage: residuals = variables - old ...
+    bool lazy_residual = false;              // ... left unwritten (settle_residuals writes it on demand)
+    bool sumsq = false;                      // ... and its squares per tile into tile_sumsq
+    const double *old = nullptr;             // where the sweep's start state is read from (default: old_variables)
+    bool look_ahead = false;                 // the stage leaves the next sweep's step-factor work behind (partial minima in partial_min, or fvcorr's factors in sf_alt)
+    const double *vin_flux = nullptr;        // the stage applies the first stage's time_step on these fluxes to its input (role 5)
+    const int32_t *tile_list = nullptr; int32_t n_list = 0; // a launch over part of the level's tiles (a partitioned level)
+    bool count_iters = true;                 // (a stage launched in two parts counts once)
+    const StagePush *push = nullptr;         // the stage sends its own halo message
+};
+
+// The state buffers of stage j of a fused sweep: the stages run variables -> q_alt -> (the former old_variables buffer) -> q_alt
+// from the sweep's start state, which stays in `variables` until finish_sweep rotates the three.
+struct StageBuffers { double *start, *in, *out; };
+static StageBuffers stage_buffers(const DeviceLevel &lv, int j)
+{
+    double *const start = lv.q, *const b1 = lv.q_alt, *const b2 = lv.old_variables;
+    return {start, j == 0 ? start : (j == 1 ? b1 : b2), j == 1 ? b2 : b1};
+}
 
 } // namespace mgcfd
 
@@ -252,6 +283,14 @@ struct mgcfd_solver {
 
     ~mgcfd_solver();
     void use_device() const { HIP_CHECK(hipSetDevice(device)); }
+    const Launchers &k() const                                  // the kernels of this solver's numeric flavour
+    {
+#define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
+                                NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong}
+        static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
+#undef MGCFD_LAUNCHERS_OF
+        return opt_exact ? kExact : kFast;
+    }
     DeviceLevel &level(int l)
     {
         if (l < 0 || l >= static_cast<int>(L.size())) throw std::invalid_argument("level out of range");
@@ -319,15 +358,13 @@ struct mgcfd_solver {
         lv.min_ahead = false;                       // partial_min is rewritten (same values if it was ahead)
         if (fuse_copy_old) settle_residuals(lv);
         double *old = fuse_copy_old ? lv.old_variables : nullptr;
-        if (opt_exact) exact::launch_step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.step_factors, lv.partial_min, old);
-        else fast::launch_step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.step_factors, lv.partial_min, old);
+        k().step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.step_factors, lv.partial_min, old);
         if (reduce_to_scalar) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
     }
     void op_step_factor_apply(int l)
     {
         DeviceLevel &lv = level(l);
-        if (opt_exact) exact::launch_step_factor_apply(stream, lv.info.nel, lv.min_dt, lv.volumes, lv.step_factors);
-        else fast::launch_step_factor_apply(stream, lv.info.nel, lv.min_dt, lv.volumes, lv.step_factors);
+        k().step_factor_apply(stream, lv.info.nel, lv.min_dt, lv.volumes, lv.step_factors);
     }
     // Write the residual of the last sweep if its last stage left it out (single-level runs: the next sweep would only
     // overwrite it).  Both operands are still in place — `variables` and the sweep's start state, which the buffer rotation
@@ -337,8 +374,7 @@ struct mgcfd_solver {
     {
         if (!lv.residuals_stale) return;
         lv.residuals_stale = false;
-        if (opt_exact) exact::launch_residual(stream, lv.dp.stride, lv.old_variables, lv.q, lv.residuals);
-        else fast::launch_residual(stream, lv.dp.stride, lv.old_variables, lv.q, lv.residuals);
+        k().residual(stream, lv.dp.stride, lv.old_variables, lv.q, lv.residuals);
     }
     // materialise a logically-zero flux array before anything reads its memory
     void settle_fluxes(DeviceLevel &lv)
@@ -357,8 +393,7 @@ struct mgcfd_solver {
         if (mesh_variant == MGCFD_MESH_FVCORR) {
             double *old = (fused && copy_old) ? lv.old_variables : nullptr;
             if (old) settle_residuals(lv);
-            if (opt_exact) exact::launch_step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, lv.step_factors, old);
-            else fast::launch_step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, lv.step_factors, old);
+            k().step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, lv.step_factors, old);
         } else {
             op_step_factor_local(l, fused && copy_old, !fused);
             if (fused) apply_pending = true;
@@ -455,62 +490,53 @@ struct mgcfd_solver {
         const int variant = variant_for(lv);
         if ((variant & 4) && !lv.dp.edge_flux)              // two-phase design point: edge-flux scratch on first use
             lv.dp.edge_flux = dev_alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
-        if (opt_exact) exact::launch_flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr);
-        else fast::launch_flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr);
+        k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr, nullptr);
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
         if (classes & 1) lv.iters[MGCFD_LOOP_FLUX] += lv.info.n_internal;
     }
     // One whole Runge-Kutta stage in one launch: fluxes of all edge classes from `in`, then
     // time_step into `out` (in != out).  fluxes[] stays logically zero, as after time_step.
-    // apply_min: 0 no, 1 from the workgroups' partial minima, 2 from the (all-reduced) scalar
-    // old: where the sweep's start state is read from (default: old_variables); look_ahead: the stage leaves
-    // the next sweep's step-factor work behind (partial minima in partial_min, or fvcorr's factors in sf_alt)
-    void op_fused_stage(int l, int j, const double *in, double *out, int apply_min, bool with_residual,
-                        const double *old = nullptr, bool look_ahead = false, bool sumsq = false,
-                        const double *vin_flux = nullptr, const int32_t *tile_list = nullptr, int32_t n_list = 0,
-                        bool count_iters = true, const double *min_list = nullptr, int n_min = 0, bool lazy_residual = false,
-                        const StagePush *push = nullptr)
+    void op_fused_stage(int l, int j, const double *in, double *out, const StageArgs &a = StageArgs{})
     {
         DeviceLevel &lv = level(l);
-        const FusedStep fs = fused_step(l, j, out, apply_min, with_residual, old, look_ahead, sumsq, vin_flux, tile_list, n_list, min_list, n_min, lazy_residual);
+        const FusedStep fs = fused_step(l, j, out, a);
         Timed t(this, l, MGCFD_LOOP_FLUX, true);
-        if (opt_exact) exact::launch_flux(stream, lv.dp, in, ff, lv.fluxes, 7, 0, variant_for(lv, true) | (stage_wg4_for(lv) ? kVariantStageWg4 : 0), &fs, push);
-        else fast::launch_flux(stream, lv.dp, in, ff, lv.fluxes, 7, 0, variant_for(lv, true), &fs, push);
-        if (count_iters) {                          // (a stage launched in two parts counts once)
+        // (kVariantStageWg4 is never set with MGCFD_OPT_EXACT = 0: stage_wg4_for)
+        k().flux(stream, lv.dp, in, ff, lv.fluxes, 7, 0, variant_for(lv, true) | (stage_wg4_for(lv) ? kVariantStageWg4 : 0), &fs, a.push);
+        if (a.count_iters) {
             lv.iters[MGCFD_LOOP_FLUX] += lv.info.n_internal;
             lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
         }
     }
-    // the arguments of one fused stage (what op_fused_stage launches; tools/exp/sweep_flow.patch takes three of them for one launch)
-    FusedStep fused_step(int l, int j, double *out, int apply_min, bool with_residual, const double *old, bool look_ahead, bool sumsq,
-                         const double *vin_flux, const int32_t *tile_list, int32_t n_list, const double *min_list, int n_min, bool lazy_residual)
+    // the kernel's arguments of one fused stage (what op_fused_stage launches; tools/exp/sweep_flow.patch takes three of them for one launch)
+    FusedStep fused_step(int l, int j, double *out, const StageArgs &a)
     {
         DeviceLevel &lv = level(l);
         settle_residuals(lv);                       // (a sweep that supersedes the residual has dropped the flag: smooth_once)
         FusedStep fs;
-        fs.tile_list = tile_list;
-        fs.n_list = n_list;
+        fs.tile_list = a.tile_list;
+        fs.n_list = a.n_list;
         // the C++ partitioned sweeps (tile lists): ghosts numbered last are left to the halo messages
-        if (tile_list && lv.plan.ghosts_last && lv.n_owned < lv.info.nel) fs.nel_active = lv.n_owned;
+        if (a.tile_list && lv.plan.ghosts_last && lv.n_owned < lv.info.nel) fs.nel_active = lv.n_owned;
         fs.rk_div = double(MGCFD_RK + 1 - j);
         fs.step_factors = lv.step_factors;
-        fs.old_variables = old ? old : lv.old_variables;
+        fs.old_variables = a.old ? a.old : lv.old_variables;
         fs.q_out = out;
-        fs.next_partial_min = (look_ahead && mesh_variant != MGCFD_MESH_FVCORR) ? lv.partial_min : nullptr;
-        fs.next_legacy_sf = (look_ahead && mesh_variant == MGCFD_MESH_FVCORR) ? lv.sf_alt : nullptr;
+        fs.next_partial_min = (a.look_ahead && mesh_variant != MGCFD_MESH_FVCORR) ? lv.partial_min : nullptr;
+        fs.next_legacy_sf = (a.look_ahead && mesh_variant == MGCFD_MESH_FVCORR) ? lv.sf_alt : nullptr;
         fs.cbrt_vol = lv.cbrt_vol;
         if (out == lv.q) lv.min_ahead = false;      // (a caller that looks ahead sets it after its last stage)
-        fs.partial_min = apply_min == 1 ? lv.partial_min : (apply_min == 2 ? lv.min_dt : (apply_min == 3 ? min_list : nullptr));
-        fs.n_partial = apply_min == 2 ? 1 : (apply_min == 3 ? n_min : static_cast<int>((lv.info.nel + 255) / 256));
+        fs.partial_min = a.apply_min == ApplyMin::Partials ? lv.partial_min : (a.apply_min == ApplyMin::Scalar ? lv.min_dt : (a.apply_min == ApplyMin::List ? a.min_list : nullptr));
+        fs.n_partial = a.apply_min == ApplyMin::Scalar ? 1 : (a.apply_min == ApplyMin::List ? a.n_min : static_cast<int>((lv.info.nel + 255) / 256));
         fs.volumes = lv.volumes;
-        fs.residuals = (with_residual && !lazy_residual) ? lv.residuals : nullptr;
-        fs.sumsq_partial = (with_residual && sumsq) ? lv.tile_sumsq : nullptr;
-        fs.vin_flux = vin_flux;                     // role 5: the input is the first stage's time_step of (old, vin_flux)
+        fs.residuals = (a.with_residual && !a.lazy_residual) ? lv.residuals : nullptr;
+        fs.sumsq_partial = (a.with_residual && a.sumsq) ? lv.tile_sumsq : nullptr;
+        fs.vin_flux = a.vin_flux;                   // role 5: the input is the first stage's time_step of (old, vin_flux)
         fs.vin_div = double(MGCFD_RK + 1);
         fs.old_of_new = lv.dp.old_of_new;
         fs.err = err;
-        if (vin_flux) fs.check_vin = next_check();       // the absorbed first stage's check_for_invalid_variables comes first
+        if (a.vin_flux) fs.check_vin = next_check();     // the absorbed first stage's check_for_invalid_variables comes first
         fs.check = force_check >= 0 ? force_check : next_check();
         return fs;
     }
@@ -519,8 +545,7 @@ struct mgcfd_solver {
         DeviceLevel &lv = level(l);
         settle_fluxes(lv);
         Timed t(this, l, MGCFD_LOOP_INDIRECT_RW);
-        if (opt_exact) exact::launch_indirect_rw(stream, lv.dp, lv.q, lv.fluxes, variant_for(lv));
-        else fast::launch_indirect_rw(stream, lv.dp, lv.q, lv.fluxes, variant_for(lv));
+        k().indirect_rw(stream, lv.dp, lv.q, lv.fluxes, variant_for(lv));
         lv.fluxes_zero = false;
         lv.iters[MGCFD_LOOP_INDIRECT_RW] += lv.info.n_internal;
     }
@@ -531,10 +556,9 @@ struct mgcfd_solver {
         lv.fluxes_zero = true;
         lv.fluxes_stale = false;
     }
-    // apply_min: 0 no, 1 from the workgroups' partial minima, 2 from the (all-reduced) scalar
     // old / out: default old_variables / variables (in place, as the reference); a sweep that keeps its
     // start state in `variables` passes both
-    void op_time_step(int l, int j, int apply_min = 0, bool with_residual = false, bool lazy_zero = false,
+    void op_time_step(int l, int j, ApplyMin apply_min = ApplyMin::None, bool with_residual = false, bool lazy_zero = false,
                       const double *old = nullptr, double *out = nullptr)
     {
         if (j < 0 || j >= MGCFD_RK) throw std::invalid_argument("RK stage out of range");
@@ -545,12 +569,11 @@ struct mgcfd_solver {
         if (!out) out = lv.q;
         if (out == lv.q) lv.min_ahead = false;
         Timed t(this, l, MGCFD_LOOP_TIME_STEP);
-        const double *pm = apply_min == 1 ? lv.partial_min : (apply_min == 2 ? lv.min_dt : nullptr);
-        const int n_pm = apply_min == 2 ? 1 : static_cast<int>((lv.info.nel + 255) / 256);
+        const double *pm = apply_min == ApplyMin::Partials ? lv.partial_min : (apply_min == ApplyMin::Scalar ? lv.min_dt : nullptr);
+        const int n_pm = apply_min == ApplyMin::Scalar ? 1 : static_cast<int>((lv.info.nel + 255) / 256);
         double *res = with_residual ? lv.residuals : nullptr;
         const int check = next_check();
-        if (opt_exact) exact::launch_time_step(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, check, pm, n_pm, lv.volumes, res, lazy_zero ? 0 : 1);
-        else fast::launch_time_step(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, check, pm, n_pm, lv.volumes, res, lazy_zero ? 0 : 1);
+        k().time_step(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, check, pm, n_pm, lv.volumes, res, lazy_zero ? 0 : 1);
         lv.fluxes_stale = lazy_zero;
         lv.fluxes_zero = true;
         lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
@@ -559,15 +582,13 @@ struct mgcfd_solver {
     {
         DeviceLevel &lv = level(l);
         lv.residuals_stale = false;
-        if (opt_exact) exact::launch_residual(stream, lv.dp.stride, lv.old_variables, lv.q, lv.residuals);
-        else fast::launch_residual(stream, lv.dp.stride, lv.old_variables, lv.q, lv.residuals);
+        k().residual(stream, lv.dp.stride, lv.old_variables, lv.q, lv.residuals);
     }
     void op_sumsq(int l)
     {
         DeviceLevel &lv = level(l);
         settle_residuals(lv);
-        if (opt_exact) exact::launch_sumsq(stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
-        else fast::launch_sumsq(stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
+        k().sumsq(stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
     }
     // rms (may be null): per-tile sums of squares of the fine level that the launch adds up on the side (cycle_once)
     void op_restrict(int fine, const SumTask *rms = nullptr)
@@ -585,8 +606,7 @@ struct mgcfd_solver {
         double *pm = ahead ? C.partial_min : nullptr;
         Timed t(this, fine + 1, MGCFD_LOOP_RESTRICT);
         const SumTask task = rms ? *rms : SumTask{};
-        if (opt_exact) exact::launch_restrict(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, pm, task);
-        else fast::launch_restrict(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, pm, task);
+        k().restrict_(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, pm, task);
         C.min_ahead = ahead;
         C.iters[MGCFD_LOOP_RESTRICT] += 2 * F.info.mgc + C.info.nel;   // mg_loops.cpp:61,117,172
     }
@@ -600,8 +620,7 @@ struct mgcfd_solver {
         const bool ahead = mesh_variant != MGCFD_MESH_FVCORR && F.n_owned == F.info.nel;   // as in op_restrict
         double *pm = ahead ? F.partial_min : nullptr;
         Timed t(this, fine, MGCFD_LOOP_PROLONG);
-        if (opt_exact) exact::launch_prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, pm);
-        else fast::launch_prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, pm);
+        k().prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, pm);
         F.min_ahead = ahead;
         F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;  // mg_loops.cpp:728,842
     }
@@ -1388,6 +1407,15 @@ int mgcfd_pending_invalid_state(mgcfd_solver *s, int64_t *bad_cell)
     return code;
 }
 
+// Every workgroup of a sweep's first stage takes the minimum over ALL per-workgroup partial minima: fine for a
+// thousand tiles (11 MB of L2 reads at the M6 size), quadratic beyond — large levels reduce them once.
+static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
+{
+    if (lv.plan.n_tiles <= 2048) return ApplyMin::Partials;
+    exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
+    return ApplyMin::Scalar;
+}
+
 // One smoothing sweep = the per-level body of the reference's cycle loop
 // (src/euler3d_cpu_double.cpp:383-508): copy, step factor, RK x (fluxes, time_step), residual.
 // Same operations, fewer passes over memory: the copy rides on the step-factor kernel, the
@@ -1414,40 +1442,31 @@ static void smooth_once(mgcfd_solver *s, int level)
         }
         // single level: the next sweep starts from this sweep's result, let the last stage look ahead
         const bool look_ahead = s->L.size() == 1 && lv.n_owned == lv.info.nel;   // (a partitioned level's ghosts are stale)
-        double *const start = lv.q, *const b1 = lv.q_alt, *const b2 = lv.old_variables;
-        // Every workgroup of the first stage takes the minimum over ALL per-workgroup partial minima: fine for a
-        // thousand tiles (11 MB of L2 reads at the M6 size), quadratic beyond — large levels reduce them once.
-        int apply = apply_pending ? 1 : 0;
-        if (apply_pending && lv.plan.n_tiles > 2048) {
-            exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
-            apply = 2;
-        }
         const bool sumsq = lv.want_sumsq && lv.n_owned == lv.info.nel;
-        mgcfd_solver::Timed group(s, level, MGCFD_LOOP_FLUX, true, s->opt_timing == 2 ? MGCFD_RK : 1);
-        s->op_fused_stage(level, 0, start, b1, apply, false, start);
-        s->op_fused_stage(level, 1, b1, b2, 0, false, start);
-        // residual (:508) = this stage's result - the sweep's start state.  On a single-level run nothing reads it before
+        // residual (:508) = the last stage's result - the sweep's start state.  On a single-level run nothing reads it before
         // the next sweep overwrites it, so the stage leaves the 40 B per node unwritten (its squares still go into the
         // RMS partials) and settle_residuals writes it if anybody asks: both operands stay where they are.
         const bool lazy_res = s->L.size() == 1 && s->opt_lazy_residual;
-        s->op_fused_stage(level, 2, b2, b1, 0, true, start, look_ahead, sumsq, nullptr, nullptr, 0, true, nullptr, 0, lazy_res);
+        const ApplyMin apply = apply_pending ? first_stage_min(s, lv) : ApplyMin::None;
+        mgcfd_solver::Timed group(s, level, MGCFD_LOOP_FLUX, true, s->opt_timing == 2 ? MGCFD_RK : 1);
+        for (int j = 0; j < MGCFD_RK; j++) {
+            const StageBuffers b = stage_buffers(lv, j);
+            StageArgs a;
+            a.old = b.start;
+            if (j == 0) a.apply_min = apply;
+            if (j == MGCFD_RK - 1) { a.with_residual = true; a.lazy_residual = lazy_res; a.sumsq = sumsq; a.look_ahead = look_ahead; }
+            s->op_fused_stage(level, j, b.in, b.out, a);
+        }
         lv.have_sumsq = sumsq;
-        lv.rot = (lv.rot + 1) % 3;                 // variables = b1, q_alt = b2, old_variables = start
-        lv.apply_rot();
-        lv.min_ahead = look_ahead;
+        lv.finish_sweep(look_ahead);
         lv.residuals_stale = lazy_res;
         return;
     }
-    const bool apply_pending = s->op_step_factor(level, true);     // :383 + :388-395
-    int apply0 = apply_pending ? 1 : 0;
-    if (apply_pending && lv.plan.n_tiles > 2048) {                 // large level: reduce the partial minima once (see above)
-        exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
-        apply0 = 2;
-    }
+    const ApplyMin apply0 = s->op_step_factor(level, true) ? first_stage_min(s, lv) : ApplyMin::None;   // :383 + :388-395
     for (int j = 0; j < MGCFD_RK; j++) {                           // :397-506
         s->op_flux(level, 7);
         // the indirect_rw probe reads fluxes[] right after, so zero for real when it is on
-        s->op_time_step(level, j, j == 0 ? apply0 : 0, j == MGCFD_RK - 1, !s->opt_indirect_rw);   // + :508 on the last stage
+        s->op_time_step(level, j, j == 0 ? apply0 : ApplyMin::None, j == MGCFD_RK - 1, !s->opt_indirect_rw);   // + :508 on the last stage
         if (s->opt_indirect_rw && (j == 0 || !s->probe_first_stage_only)) { s->op_indirect_rw(level); s->op_zero_fluxes(level); }
     }
 }
@@ -1569,33 +1588,39 @@ static int sweep_end_impl(mgcfd_solver *s, int level, bool scalar)
     OP({
         DeviceLevel &lv = s->level(level);
         const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
-        const int apply = global_dt ? (scalar ? 2 : 1) : 0;
+        const ApplyMin apply = global_dt ? (scalar ? ApplyMin::Scalar : ApplyMin::Partials) : ApplyMin::None;
         const bool look_ahead = s->L.size() == 1 && lv.n_owned == lv.info.nel;
-        double *const start = lv.q;
-        double *const b1 = lv.q_alt;
-        double *const b2 = lv.old_variables;
+        auto stage = [&](int j, StageArgs a) {
+            const StageBuffers b = stage_buffers(lv, j);
+            a.old = b.start;
+            s->op_fused_stage(level, j, a.vin_flux ? b.start : b.in, b.out, a);
+        };
+        StageArgs first;
+        first.apply_min = apply;
         if (lv.sweep_flux0_done && global_dt && lv.dp.vin_ok && !((s->variant_for(lv) & 2) && lv.dp.edge_once)) {
             // the second stage applies the first stage's time_step (on the fluxes of sweep_flux0) to its own
             // input while it stages it: no separate time_step launch, the first stage's result never touches memory
-            s->op_fused_stage(level, 1, start, b2, apply, false, start, false, false, lv.fluxes);
+            first.vin_flux = lv.fluxes;
+            stage(1, first);
             lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;      // the first stage's time_step
             lv.fluxes_zero = true;                               // ... which leaves fluxes[] logically zero
             lv.fluxes_stale = true;
             lv.sweep_flux0_done = false;
         } else {
             if (lv.sweep_flux0_done) {
-                s->op_time_step(level, 0, apply, false, true, start, b1);   // time_step on the fluxes of sweep_flux0
+                s->op_time_step(level, 0, apply, false, true, lv.q, lv.q_alt);   // time_step on the fluxes of sweep_flux0
                 lv.sweep_flux0_done = false;
             } else {
                 s->settle_fluxes(lv);
-                s->op_fused_stage(level, 0, start, b1, apply, false, start);
+                stage(0, first);
             }
-            s->op_fused_stage(level, 1, b1, b2, 0, false, start);
+            stage(1, StageArgs{});
         }
-        s->op_fused_stage(level, 2, b2, b1, 0, true, start, look_ahead);
-        lv.rot = (lv.rot + 1) % 3;                 // variables = b1, q_alt = b2, old_variables = start
-        lv.apply_rot();
-        lv.min_ahead = look_ahead;
+        StageArgs last;
+        last.with_residual = true;
+        last.look_ahead = look_ahead;
+        stage(2, last);
+        lv.finish_sweep(look_ahead);
     });
 }
 
@@ -1605,28 +1630,20 @@ int mgcfd_sweep_stage(mgcfd_solver *s, int level, int j, int partials)
         DeviceLevel &lv = s->level(level);
         if (j != lv.stage_next) throw std::invalid_argument("mgcfd_sweep_stage: stages must run in order 0, 1, 2 after mgcfd_sweep_begin");
         const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
-        double *const start = lv.q;
-        double *const b1 = lv.q_alt;
-        double *const b2 = lv.old_variables;
+        const StageBuffers b = stage_buffers(lv, j);
+        StageArgs a;
+        a.old = b.start;
         if (j == 0) {
             if (!lv.fluxes_zero) throw std::invalid_argument("mgcfd_sweep_stage needs zero fluxes (as after time_step)");
             s->settle_fluxes(lv);
-            s->op_fused_stage(level, 0, start, b1, global_dt ? (partials ? 1 : 2) : 0, false, start);
-            lv.stage_out = b1;
-            lv.stage_next = 1;
-        } else if (j == 1) {
-            s->op_fused_stage(level, 1, b1, b2, 0, false, start);
-            lv.stage_out = b2;
-            lv.stage_next = 2;
-        } else {
-            // (no look-ahead: on a partitioned level the ghosts of the new state are stale until the exchange)
-            s->op_fused_stage(level, 2, b2, b1, 0, true, start, false);
-            lv.rot = (lv.rot + 1) % 3;             // variables = b1, q_alt = b2, old_variables = start
-            lv.apply_rot();
-            lv.stage_out = lv.q;                   // == b1
-            lv.stage_next = 0;
-            lv.min_ahead = false;
+            if (global_dt) a.apply_min = partials ? ApplyMin::Partials : ApplyMin::Scalar;
         }
+        // (no look-ahead: on a partitioned level the ghosts of the new state are stale until the exchange)
+        a.with_residual = j == MGCFD_RK - 1;
+        s->op_fused_stage(level, j, b.in, b.out, a);
+        lv.stage_out = b.out;
+        lv.stage_next = (j + 1) % MGCFD_RK;
+        if (j == MGCFD_RK - 1) lv.finish_sweep(false);
     });
 }
 int mgcfd_sweep_begin(mgcfd_solver *s, int level) { return sweep_begin_impl(s, level, true); }
@@ -2106,8 +2123,7 @@ int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_secon
         if ((variant & 4) && !lv.dp.edge_flux)
             lv.dp.edge_flux = dev_alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
         auto go = [&] {
-            if (s->opt_exact) exact::launch_flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, variant, nullptr);
-            else fast::launch_flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, variant, nullptr);
+            s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, variant, nullptr, nullptr);
         };
         go();
         HIP_CHECK(hipEventRecord(a, s->stream));
@@ -2135,8 +2151,7 @@ int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *av
         hipEvent_t a = s->get_event(), b = s->get_event();
         const int variant = s->variant_for(lv);
         auto go = [&] {
-            if (s->opt_exact) exact::launch_indirect_rw(s->stream, lv.dp, lv.q, lv.fluxes, variant);
-            else fast::launch_indirect_rw(s->stream, lv.dp, lv.q, lv.fluxes, variant);
+            s->k().indirect_rw(s->stream, lv.dp, lv.q, lv.fluxes, variant);
         };
         go();
         HIP_CHECK(hipEventRecord(a, s->stream));
@@ -2405,43 +2420,60 @@ static bool part_look_ahead()
     return on;
 }
 
+// Does the last stage of a partitioned sweep look ahead?  Under a global time step only — which is what `apply_min` says:
+// every caller passes None exactly when mesh_name = fvcorr (rank_sweep_once and the group sweeps pass global_dt ? Scalar or
+// List : None; rank_sweep_once_ipc sets it under `if (global_dt)`).
+static bool part_looks_ahead(ApplyMin apply_min) { return apply_min != ApplyMin::None && part_look_ahead(); }
+// How a partitioned sweep's first stage gets the global time step (None: local time step).
+struct PartMin { ApplyMin apply = ApplyMin::None; const double *list = nullptr; int n = 0; };
+// The arguments of stage j of a partitioned sweep, launched over `tiles`: the time step on the first stage, the residual
+// and the look-ahead on the last — there every tile leaves its own minimum over its OWNED nodes (cbrt_vol is +inf on ghosts).
+static StageArgs part_stage_args(const DeviceLevel &lv, int j, const PartMin &pm, const int32_t *tiles, int32_t n_tiles)
+{
+    StageArgs a;
+    a.old = lv.q;
+    a.tile_list = tiles; a.n_list = n_tiles;
+    if (j == 0) { a.apply_min = pm.apply; a.min_list = pm.list; a.n_min = pm.n; }
+    if (j == MGCFD_RK - 1) { a.with_residual = true; a.look_ahead = part_looks_ahead(pm.apply); }
+    return a;
+}
+// Before the first launch of a partitioned stage (its input's ghosts are there, or being waited for on the stream)
+static void part_stage_begin(mgcfd_solver *s, DeviceLevel &lv, int j)
+{
+    if (j == 0 && !lv.fluxes_zero) throw std::invalid_argument("a partitioned sweep needs zero fluxes (as after time_step)");
+    if (j == 0) s->settle_fluxes(lv);
+    s->force_check = s->next_check();                       // all launches of the stage are one time_step for check_for_invalid_variables
+}
+// ... and behind its last
+static void part_stage_end(mgcfd_solver *s, DeviceLevel &lv, int j, const PartMin &pm)
+{
+    s->force_check = -1;
+    if (j == MGCFD_RK - 1) lv.finish_sweep(part_looks_ahead(pm.apply));
+}
+
 // One stage of a partitioned sweep on one rank, part 1: the ghosts of the stage's input arrive (the previous stage's
 // message), the boundary tiles run, their results are packed and sent.  Part 2 (stage_interior) runs the other tiles
 // while the message travels.
-static void stage_boundary(mgcfd_solver *s, int level, int j, int apply_min, const double *min_list, int n_min)
+static void stage_boundary(mgcfd_solver *s, int level, int j, const PartMin &pm)
 {
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
-    double *const start = lv.q, *const b1 = lv.q_alt, *const b2 = lv.old_variables;
-    double *in = j == 0 ? start : (j == 1 ? b1 : b2);
-    double *out = j == 0 ? b1 : (j == 1 ? b2 : b1);
-    if (j > 0) halo_finish(s, level, in, j - 1);
-    if (j == 0) {
-        if (!lv.fluxes_zero) throw std::invalid_argument("a partitioned sweep needs zero fluxes (as after time_step)");
-        s->settle_fluxes(lv);
-    }
-    s->force_check = s->next_check();                       // both parts of the stage are one time_step for check_for_invalid_variables
-    s->op_fused_stage(level, j, in, out, j == 0 ? apply_min : 0, j == 2, start, j == 2 && apply_min != 0 && part_look_ahead(), false, nullptr, hx.tiles_boundary, hx.n_boundary, true, min_list, n_min);
-    lv.stage_out = out;
-    halo_start(s, level, out, j);
+    const StageBuffers b = stage_buffers(lv, j);
+    if (j > 0) halo_finish(s, level, b.in, j - 1);
+    part_stage_begin(s, lv, j);
+    s->op_fused_stage(level, j, b.in, b.out, part_stage_args(lv, j, pm, hx.tiles_boundary, hx.n_boundary));
+    lv.stage_out = b.out;
+    halo_start(s, level, b.out, j);
 }
-static void stage_interior(mgcfd_solver *s, int level, int j, int apply_min, const double *min_list, int n_min)
+static void stage_interior(mgcfd_solver *s, int level, int j, const PartMin &pm)
 {
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
-    double *const start = lv.q, *const b1 = lv.q_alt, *const b2 = lv.old_variables;
-    double *in = j == 0 ? start : (j == 1 ? b1 : b2);
-    double *out = j == 0 ? b1 : (j == 1 ? b2 : b1);
-    s->op_fused_stage(level, j, in, out, j == 0 ? apply_min : 0, j == 2, start, j == 2 && apply_min != 0 && part_look_ahead(), false, nullptr, hx.tiles_interior, hx.n_interior, false, min_list, n_min);
-    s->force_check = -1;
-    if (j == 2) {
-        lv.rot = (lv.rot + 1) % 3;                          // variables = b1, q_alt = b2, old_variables = start
-        lv.apply_rot();
-        lv.stage_out = lv.q;
-        // global time step: both launches of the last stage left the first half of the NEXT sweep's compute_step_factor
-        // in partial_min, every tile its own minimum over its OWNED nodes (cbrt_vol is +inf on ghosts)
-        lv.min_ahead = apply_min != 0 && part_look_ahead();
-    }
+    const StageBuffers b = stage_buffers(lv, j);
+    StageArgs a = part_stage_args(lv, j, pm, hx.tiles_interior, hx.n_interior);
+    a.count_iters = false;                                  // (stage_boundary has counted the stage)
+    s->op_fused_stage(level, j, b.in, b.out, a);
+    part_stage_end(s, lv, j, pm);
 }
 
 static void sweep_first_half(mgcfd_solver *s, int level, double *min_out = nullptr)
@@ -2463,9 +2495,11 @@ static void rank_sweep_once(mgcfd_solver *s, int level)
     const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
     sweep_first_half(s, level);
     if (global_dt) RCCL_CHECK(g_rccl.AllReduce(lv.min_dt, lv.min_dt, 1, Rccl::kDouble, Rccl::kMin, c.rccl, s->stream));
+    PartMin pm;
+    if (global_dt) pm.apply = ApplyMin::Scalar;
     for (int j = 0; j < MGCFD_RK; j++) {
-        stage_boundary(s, level, j, global_dt ? 2 : 0, nullptr, 0);
-        stage_interior(s, level, j, global_dt ? 2 : 0, nullptr, 0);
+        stage_boundary(s, level, j, pm);
+        stage_interior(s, level, j, pm);
     }
     halo_finish(s, level, lv.q, MGCFD_RK - 1);              // the ghosts of `variables` are current when the sweep ends
 }
@@ -2523,9 +2557,6 @@ static void group_prepare_direct(mgcfd_group *g, int level)
     for (mgcfd_solver *s : g->ranks) s->level(level).hx->direct = true;
 }
 
-// which of a rank's three state buffers a stage writes (as stage_boundary / stage_interior name them)
-static double *stage_out_buffer(DeviceLevel &lv, int j) { return j == 1 ? lv.old_variables : lv.q_alt; }
-
 // where a rank's push goes: the buffer `peer_field(peer's level)` of every peer, the peers' segments of the message
 template <typename PeerField>
 static PushPeers make_push_peers(mgcfd_group *g, mgcfd_solver *s, int level, PeerField &&peer_field)
@@ -2558,25 +2589,21 @@ static void wait_for_peers(mgcfd_group *g, mgcfd_solver *s, int level, int ev)
     for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->bdone[ev], 0));
 }
 
+// the time step of an in-process group's sweep: the first stage takes the minimum over the group's minima (hx.gmin)
+static PartMin group_min(bool global_dt, const HaloExchange &hx) { return {global_dt ? ApplyMin::List : ApplyMin::None, hx.gmin, 1}; }
+
 // part 1 of a stage in direct mode (part 2 is stage_interior as it is); `to` = where the push goes (nullptr: the peers'
 // buffers as they are named now — one host thread drives the group, nobody has rotated since the stage began)
-static void stage_boundary_direct(mgcfd_group *g, mgcfd_solver *s, int level, int j, int apply_min, const double *min_list, int n_min,
-                                  const PushPeers *to = nullptr)
+static void stage_boundary_direct(mgcfd_group *g, mgcfd_solver *s, int level, int j, const PartMin &pm, const PushPeers *to = nullptr)
 {
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
-    double *const start = lv.q, *const b1 = lv.q_alt, *const b2 = lv.old_variables;
-    double *in = j == 0 ? start : (j == 1 ? b1 : b2);
-    double *out = j == 0 ? b1 : (j == 1 ? b2 : b1);
+    const StageBuffers b = stage_buffers(lv, j);
     wait_for_peers(g, s, level, (j + 2) % 3);               // the ghosts of `in`: the peers' pushes of the stage before (stage 0: of the last sweep, or of the exchange)
-    if (j == 0) {
-        if (!lv.fluxes_zero) throw std::invalid_argument("a partitioned sweep needs zero fluxes (as after time_step)");
-        s->settle_fluxes(lv);
-    }
-    s->force_check = s->next_check();
-    s->op_fused_stage(level, j, in, out, j == 0 ? apply_min : 0, j == 2, start, j == 2 && apply_min != 0 && part_look_ahead(), false, nullptr, hx.tiles_boundary, hx.n_boundary, true, min_list, n_min);
-    lv.stage_out = out;
-    push_and_record(s, level, out, to ? *to : make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_out_buffer(pl, j); }), j);
+    part_stage_begin(s, lv, j);
+    s->op_fused_stage(level, j, b.in, b.out, part_stage_args(lv, j, pm, hx.tiles_boundary, hx.n_boundary));
+    lv.stage_out = b.out;
+    push_and_record(s, level, b.out, to ? *to : make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_buffers(pl, j).out; }), j);
 }
 
 // ---- a host thread per rank ---------------------------------------------------------------------------------------------
@@ -2642,12 +2669,12 @@ static void group_sweeps_threaded(mgcfd_group *g, int level, int sweeps, bool wi
                 }
                 // the peers' buffers of this sweep's three stages, read while nobody rotates (a rank rotates in its last stage's
                 // second part, two barriers from here; its previous rotation lies before the barrier just passed)
-                for (int j = 0; j < MGCFD_RK; j++) to[j] = make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_out_buffer(pl, j); });
+                for (int j = 0; j < MGCFD_RK; j++) to[j] = make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_buffers(pl, j).out; });
             });
             for (int j = 0; j < MGCFD_RK; j++) {
                 step([&] {
-                    stage_boundary_direct(g, s, level, j, global_dt ? 3 : 0, hx.gmin, 1, &to[j]);
-                    stage_interior(s, level, j, global_dt ? 3 : 0, hx.gmin, 1);
+                    stage_boundary_direct(g, s, level, j, group_min(global_dt, hx), &to[j]);
+                    stage_interior(s, level, j, group_min(global_dt, hx));
                 });
                 bar.wait();
             }
@@ -2688,14 +2715,14 @@ static void group_sweep_once(mgcfd_group *g, int level)
     for (int j = 0; j < MGCFD_RK; j++) {
         for (mgcfd_solver *s : g->ranks) {
             s->use_device();
-            if (direct) stage_boundary_direct(g, s, level, j, global_dt ? 3 : 0, s->level(level).hx->gmin, 1);
-            else stage_boundary(s, level, j, global_dt ? 3 : 0, s->level(level).hx->gmin, 1);
+            if (direct) stage_boundary_direct(g, s, level, j, group_min(global_dt, *s->level(level).hx));
+            else stage_boundary(s, level, j, group_min(global_dt, *s->level(level).hx));
         }
         // (set 0 is also the set of the transfers' exchanges, outside the sweeps' rotation: a destination's copies of stage 0 wait
         //  for its OWN pack of this stage, which lies behind its unpack of such an exchange — with the local time step nothing
         //  else orders a peer's stage-0 message behind that unpack; round 3's advisor finding)
         if (!direct) group_deliver(g, level, j, j == 0);
-        for (mgcfd_solver *s : g->ranks) { s->use_device(); stage_interior(s, level, j, global_dt ? 3 : 0, s->level(level).hx->gmin, 1); }
+        for (mgcfd_solver *s : g->ranks) { s->use_device(); stage_interior(s, level, j, group_min(global_dt, *s->level(level).hx)); }
     }
     // (direct mode: the last stage's pushes went into the buffer that is `variables` now; whoever reads ghosts next waits for bdone[2])
     if (!direct) for (mgcfd_solver *s : g->ranks) { s->use_device(); halo_finish(s, level, s->level(level).q, MGCFD_RK - 1); }
@@ -2803,30 +2830,23 @@ static void rank_sweep_once_ipc(mgcfd_solver *s, int level)
     sweep_first_half(s, level);
     // the time step: over the flags when every rank is attached (the ranks' minima side by side, the first stage takes their
     // minimum), else RCCL's all-reduce into the scalar
-    const double *min_list = nullptr;
-    int n_min = 0, apply = 0;
+    PartMin pm;
     if (global_dt) {
-        if (hx.ipc_all) { min_list = ipc_allreduce_min(s, lv); n_min = c.world; apply = 3; }
-        else { RCCL_CHECK(g_rccl.AllReduce(lv.min_dt, lv.min_dt, 1, Rccl::kDouble, Rccl::kMin, c.rccl, s->stream)); apply = 2; }
+        if (hx.ipc_all) pm = PartMin{ApplyMin::List, ipc_allreduce_min(s, lv), c.world};
+        else { RCCL_CHECK(g_rccl.AllReduce(lv.min_dt, lv.min_dt, 1, Rccl::kDouble, Rccl::kMin, c.rccl, s->stream)); pm.apply = ApplyMin::Scalar; }
     }
     for (int j = 0; j < MGCFD_RK; j++) {
-        double *const start = lv.q, *const b1 = lv.q_alt, *const b2 = lv.old_variables;
-        double *in = j == 0 ? start : (j == 1 ? b1 : b2);
-        double *out = j == 0 ? b1 : (j == 1 ? b2 : b1);
+        const StageBuffers b = stage_buffers(lv, j);
+        const int which = j == 1 ? 2 : 1;                   // (before the rotation: stage 1 writes old_variables' buffer, stages 0 and 2 q_alt's)
         ipc_wait(s, hx, (j + 2) % 3);                       // the ghosts of `in`: the peers' pushes of the stage before (stage 0: of the last sweep, or of the exchange)
-        if (j == 0) {
-            if (!lv.fluxes_zero) throw std::invalid_argument("a partitioned sweep needs zero fluxes (as after time_step)");
-            s->settle_fluxes(lv);
-        }
-        s->force_check = s->next_check();
+        part_stage_begin(s, lv, j);
+        lv.stage_out = b.out;
         if (s->opt_rank_split == 2 && hx.n_boundary > 0) {
             // MGCFD_OPT_RANK_SPLIT = 2: ONE launch per stage that sends its own message — the boundary tiles first, their
             // epilogue stores into the neighbours, the last of them raises the flags, the interior tiles run on meanwhile
             StagePush sp;
             sp.send_ptr = hx.node_send_ptr; sp.send_peer = hx.node_send_peer; sp.send_target = hx.node_send_target;
-            sp.ticket = hx.ticket;
-            sp.n_boundary = hx.n_boundary;
-            const int which = j == 1 ? 2 : 1;
+            sp.ticket = hx.ticket; sp.n_boundary = hx.n_boundary;
             sp.peers.n = sp.flags.n = static_cast<int>(hx.peer.size());
             for (int k = 0; k < sp.peers.n; k++) {
                 sp.peers.base[k] = hx.peer_state[k][(lv.rot + hx.peer_rot_delta[k] + which) % 3];
@@ -2835,32 +2855,19 @@ static void rank_sweep_once_ipc(mgcfd_solver *s, int level)
             }
             hx.seq++;
             sp.flags.value = hx.seq;
-            s->op_fused_stage(level, j, in, out, j == 0 ? apply : 0, j == 2, start, j == 2 && global_dt && part_look_ahead(), false, nullptr, hx.tiles_all, hx.n_boundary + hx.n_interior, true, min_list, n_min, false, &sp);
-            s->force_check = -1;
-            lv.stage_out = out;
-            if (j == 2) {
-                lv.rot = (lv.rot + 1) % 3;
-                lv.apply_rot();
-                lv.stage_out = lv.q;
-                lv.min_ahead = apply != 0 && part_look_ahead();
-            }
+            StageArgs a = part_stage_args(lv, j, pm, hx.tiles_all, hx.n_boundary + hx.n_interior);
+            a.push = &sp;
+            s->op_fused_stage(level, j, b.in, b.out, a);
+            part_stage_end(s, lv, j, pm);
         } else if (s->opt_rank_split) {
-            s->op_fused_stage(level, j, in, out, j == 0 ? apply : 0, j == 2, start, j == 2 && global_dt && part_look_ahead(), false, nullptr, hx.tiles_boundary, hx.n_boundary, true, min_list, n_min);
-            lv.stage_out = out;
-            ipc_push(s, lv, out, j == 1 ? 2 : 1, j);        // (before the rotation: stage 1 writes old_variables' buffer, stages 0 and 2 q_alt's)
-            stage_interior(s, level, j, apply, min_list, n_min);
+            s->op_fused_stage(level, j, b.in, b.out, part_stage_args(lv, j, pm, hx.tiles_boundary, hx.n_boundary));
+            ipc_push(s, lv, b.out, which, j);
+            stage_interior(s, level, j, pm);
         } else {
             // MGCFD_OPT_RANK_SPLIT = 0: every tile of the rank in one launch, the message behind it
-            s->op_fused_stage(level, j, in, out, j == 0 ? apply : 0, j == 2, start, j == 2 && global_dt && part_look_ahead(), false, nullptr, hx.tiles_all, hx.n_boundary + hx.n_interior, true, min_list, n_min);
-            s->force_check = -1;
-            lv.stage_out = out;
-            ipc_push(s, lv, out, j == 1 ? 2 : 1, j);
-            if (j == 2) {
-                lv.rot = (lv.rot + 1) % 3;
-                lv.apply_rot();
-                lv.stage_out = lv.q;
-                lv.min_ahead = apply != 0 && part_look_ahead();
-            }
+            s->op_fused_stage(level, j, b.in, b.out, part_stage_args(lv, j, pm, hx.tiles_all, hx.n_boundary + hx.n_interior));
+            ipc_push(s, lv, b.out, which, j);
+            part_stage_end(s, lv, j, pm);
         }
     }
 }
@@ -3094,10 +3101,8 @@ int mgcfd_rank_set_halo(mgcfd_solver *s, int level, int n_peers, const int *peer
 static void after_replayed_sweep(mgcfd_solver *s, int level, const int64_t *iters_delta)
 {
     DeviceLevel &lv = s->level(level);
-    lv.rot = (lv.rot + 1) % 3;
-    lv.apply_rot();
-    lv.stage_out = lv.q;
-    lv.min_ahead = s->mesh_variant != MGCFD_MESH_FVCORR && part_look_ahead();    // (as stage_interior leaves it)
+    lv.finish_sweep(s->mesh_variant != MGCFD_MESH_FVCORR && part_look_ahead());    // (as stage_interior leaves it)
+    lv.stage_out = lv.q;                            // (the replayed stages did not name it)
     for (int k = 0; k < MGCFD_NUM_LOOPS; k++) lv.iters[k] += iters_delta[k];
 }
 
@@ -3592,12 +3597,12 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms)
                     for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced, 0));
                     exact::launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
                 }
-                for (int j = 0; j < MGCFD_RK; j++) to[j] = make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_out_buffer(pl, j); });
+                for (int j = 0; j < MGCFD_RK; j++) to[j] = make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_buffers(pl, j).out; });
             });
             for (int j = 0; j < MGCFD_RK; j++) {
                 step([&] {
-                    stage_boundary_direct(g, s, level, j, global_dt ? 3 : 0, hx.gmin, 1, &to[j]);
-                    stage_interior(s, level, j, global_dt ? 3 : 0, hx.gmin, 1);
+                    stage_boundary_direct(g, s, level, j, group_min(global_dt, hx), &to[j]);
+                    stage_interior(s, level, j, group_min(global_dt, hx));
                 });
                 bar.wait();
             }
