@@ -302,7 +302,9 @@ int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out);
  * (flux_boundary_kernel.elemfunc.c) with the far-field pressure taken off.  For edge (node b, weights w):
  * f = (p_b - p_inf) w, m = (coords[b] - ref_point) x f; summed in a fixed order (chunks of 256 edges, stride-halving
  * tree, then the same over the partial sums), never contracted to FMA: a bitwise function of the state.  INTEGRATION.md
- * gives the whole definition.  Solvers of a partitioned level or attached as ranks: MGCFD_ERR_ARG.
+ * gives the whole definition.  Solvers of a partitioned level or attached as ranks: MGCFD_ERR_ARG from the two calls below —
+ * the loads of a level split over ranks come from mgcfd_group_surface_loads / mgcfd_group_cycles_loads and
+ * mgcfd_rank_surface_loads / mgcfd_rank_cycles_loads (further down), bit for bit the same six numbers.
  * --------------------------------------------------------------------------------- */
 /* Loads of level `level`'s current `variables`: out6 = Fx Fy Fz Mx My Mz.  ref_point NULL = the origin.  Synchronises.
  * A level without solid-wall edges gives exact zeros. */
@@ -500,6 +502,30 @@ int mgcfd_group_rms(mgcfd_group *g, int level, double *rms);
 int mgcfd_group_cycles(mgcfd_group *g, int cycles, double *rms_out);
 int mgcfd_rank_cycles(mgcfd_solver *s, int cycles, double *rms_out);      /* one rank per process over RCCL (mgcfd_rank_attach_rccl) */
 int mgcfd_group_synchronize(mgcfd_group *g);
+/* Surface loads of a level split over ranks: bit for bit what mgcfd_surface_loads returns for the same state on one solver
+ * that holds the whole level.  The definition is unchanged — chunks of 256 edges of the WHOLE level's solid-wall slice in the
+ * whole level's order, the stride-halving tree, the tree over the partial sums, never contracted — so every rank says where
+ * its edges lie in that slice: slot[k] = position, in [boundary_start, boundary_start + n_boundary) of the whole level, of
+ * this rank's k-th solid-wall edge (its local boundary-class edges in local order); n_total = the whole level's n_boundary
+ * (0 is legal: a level without solid walls), n = how many slots are given.  MGCFD_ERR_ARG unless the solver was made by
+ * mgcfd_create_partitioned*, n equals the level's local n_boundary and the slots are strictly ascending in [0, n_total)
+ * (local edge lists keep the whole level's order).  Every rank stores its edges' six terms at their slots of a table on
+ * rank 0 (stores and copies only, never an arithmetic reduction), rank 0 reduces the table. */
+int mgcfd_rank_set_wall_slots(mgcfd_solver *s, int level, int64_t n_total, int64_t n, const int64_t *slot);
+/* In-process groups.  Before the first launch the group checks on the host that every rank has slots on the level, that all
+ * name the same n_total and that together they name 0 .. n_total-1 exactly once: MGCFD_ERR_ARG otherwise ("wall slots", and
+ * the rank).  mgcfd_group_surface_loads: the loads of `level`'s current state; synchronises.  mgcfd_group_cycles_loads:
+ * mgcfd_group_cycles (same RMS, same final state on every rank, same errors) and loads_out[c*6 .. c*6+5] = the level-0 loads
+ * of the state cycle c leaves (after its last prolongation and the exchange behind it), recorded on rank 0's device inside
+ * the cycles, read back once; rows stay NaN when the call fails before the read-back. */
+int mgcfd_group_surface_loads(mgcfd_group *g, int level, const double ref_point[3], double out6[6]);
+int mgcfd_group_cycles_loads(mgcfd_group *g, int cycles, const double ref_point[3], double *rms_out, double *loads_out);
+/* One rank per process over RCCL (mgcfd_rank_attach_rccl): collective, every rank receives the same numbers.  The ranks'
+ * edge counts are agreed once, outside the cycles (their sum must be n_total: MGCFD_ERR_ARG), the slots go to rank 0 once;
+ * per evaluation every other rank sends its terms to rank 0 (ncclSend / ncclRecv), which places them by slot and reduces.
+ * NOTE: exercised with ONE rank only, the most a one-GPU box offers; the messages between several ranks have never run. */
+int mgcfd_rank_surface_loads(mgcfd_solver *s, int level, const double ref_point[3], double out6[6]);
+int mgcfd_rank_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,20 @@ struct LoadsTask {
     int cap = 0;
 };
 
+// The loads of a level split over ranks: every rank stores the six terms of its own solid-wall edges at the edges' slots
+// of a terms table [6][row] (row = the whole level's edge count rounded up to 256, pad lanes zero) that lives on the
+// gathering rank (k_loads_terms), which then reduces the table exactly as k_surface_loads reduces its records
+// (k_loads_reduce: LoadsTask with rec = nullptr, n = the whole level's count).
+struct LoadsTerms {
+    const WallRecord *rec = nullptr;      // [n] this rank's records, local order
+    int64_t n = 0;
+    double p_inf = 0.0;
+    const double *ref = nullptr;          // device [3]
+    const int32_t *slot = nullptr;        // [n] position in the whole level's solid-wall slice; nullptr: lane k stores at k
+    double *table = nullptr;              // [6][row], on this device or on a peer's (peer access)
+    int64_t row = 0;
+};
+
 // Long rows (preprocess.hpp: LevelPlan::tail_*): device arrays of the entries the per-node loop leaves to the workgroup.
 struct TailPlan {
     const int32_t *rows_main = nullptr;   // [n_slices] internal rows the per-node loop walks

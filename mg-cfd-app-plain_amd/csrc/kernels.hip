@@ -2512,6 +2512,94 @@ k_surface_loads(int64_t stride, const double *__restrict__ q, LoadsTask task)
     if (t == 0) loads_store(task, v);
 }
 
+// The same loads of a level split over ranks ("Surface loads": the partitioned form), in two launches.
+// k_loads_terms, on every rank: one lane per solid-wall edge the rank holds, the six terms by the expressions of
+// k_surface_loads, stored at the edge's slot of the terms table [6][row] — the whole level's order, on the gathering
+// rank's device (plain stores over xGMI, as k_halo_push's) — or, slot == nullptr, at the lane's own index of a compact
+// buffer that travels as a message and is placed by k_loads_scatter.  Terms move by stores and copies only.
+__global__ void __launch_bounds__(kBlock)
+k_loads_terms(int64_t stride, const double *__restrict__ q, LoadsTerms task)
+{
+#pragma clang fp contract(off)
+    const int64_t e = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (e >= task.n) return;
+    const WallRecord r = task.rec[e];
+    const int64_t b = r.node;
+    const double rho = q[b], mx = q[stride + b], my = q[2 * stride + b], mz = q[3 * stride + b], en = q[4 * stride + b];
+    const double vx = mx / rho, vy = my / rho, vz = mz / rho;
+    const double speed_sqd = vx * vx + vy * vy + vz * vz;
+    const double p = (kGamma - 1.0) * (en - 0.5 * rho * speed_sqd);
+    const double dp = p - task.p_inf;
+    const double fx = dp * r.x, fy = dp * r.y, fz = dp * r.z;
+    const double rx = r.cx - task.ref[0], ry = r.cy - task.ref[1], rz = r.cz - task.ref[2];
+    const int64_t at = task.slot ? int64_t(task.slot[e]) : e;
+    double *dst = task.table + at;
+    dst[0] = fx; dst[task.row] = fy; dst[2 * task.row] = fz;
+    dst[3 * task.row] = ry * fz - rz * fy;
+    dst[4 * task.row] = rz * fx - rx * fz;
+    dst[5 * task.row] = rx * fy - ry * fx;
+}
+
+// a rank's compact terms [6][src_row] into the table, by slot (the gathering rank, behind the message's arrival)
+__global__ void __launch_bounds__(kBlock)
+k_loads_scatter(int64_t n, const double *__restrict__ src, int64_t src_row, const int32_t *__restrict__ slot,
+                double *__restrict__ table, int64_t row)
+{
+    const int64_t k = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const int64_t at = slot[k];
+#pragma unroll
+    for (int c = 0; c < 6; c++) table[c * row + at] = src[c * src_row + k];
+}
+
+// k_loads_reduce, on the gathering rank: k_surface_loads with the term evaluation replaced by a coalesced read of the
+// table — workgroup k takes lanes [256 k, 256 k + 256) of every row (pad lanes hold +0.0, what k_surface_loads gives a lane
+// past the last edge), the same trees, the same ticket.  task.n = the whole level's edge count, task.rec unused.
+__global__ void __launch_bounds__(kBlock)
+k_loads_reduce(const double *__restrict__ table, int64_t row, LoadsTask task)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[6][kBlock];
+    __shared__ int last;
+    const int t = threadIdx.x;
+    const int64_t e = int64_t(blockIdx.x) * kBlock + t;
+    double v[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[c] = table[c * row + e];
+    loads_tree(v, sh);                                                 // stage A
+    const int nb = int(gridDim.x);
+    if (nb == 1) {
+        if (t == 0) loads_store(task, v);
+        return;
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) task.partial[int64_t(c) * nb + blockIdx.x] = v[c];
+        const unsigned done = __hip_atomic_fetch_add(task.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        last = done == unsigned(nb - 1);
+        if (last) __hip_atomic_store(task.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the next call starts from zero)
+    }
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    for (int n = nb; n > 1;) {                                          // stage B, as in k_surface_loads
+        const int m = (n + kBlock - 1) / kBlock;
+        for (int k = 0; k < m; k++) {
+            const int i = k * kBlock + t;
+#pragma unroll
+            for (int c = 0; c < 6; c++) v[c] = i < n ? task.partial[int64_t(c) * nb + i] : 0.0;
+            loads_tree(v, sh);
+            if (t == 0) {
+#pragma unroll
+                for (int c = 0; c < 6; c++) task.partial[int64_t(c) * nb + k] = v[c];
+            }
+            __syncthreads();
+        }
+        n = m;
+    }
+    if (t == 0) loads_store(task, v);
+}
+
 // ------------------------------------------------------------------------------------------
 // mg_restrict (mg_loops.cpp:30-202) as a coarse-centred gather: coarse = (sum of children in
 // ascending fine id) * (1/count); coarse nodes without children keep their value.
@@ -3066,6 +3154,22 @@ void launch_surface_loads(hipStream_t st, int64_t stride, const double *q, const
 {
     if (task.n <= 0) return;                                           // (the caller writes the zeros)
     hipLaunchKernelGGL(k_surface_loads, dim3(unsigned((task.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, stride, q, task);
+}
+
+void launch_loads_terms(hipStream_t st, int64_t stride, const double *q, const LoadsTerms &task)
+{
+    if (task.n <= 0) return;                                           // (a rank without a solid-wall edge stores nothing)
+    hipLaunchKernelGGL(k_loads_terms, dim3(grid_for(task.n)), dim3(kBlock), 0, st, stride, q, task);
+}
+
+void launch_loads_scatter(hipStream_t st, int64_t n, const double *src, int64_t src_row, const int32_t *slot, double *table, int64_t row)
+{ if (n > 0) hipLaunchKernelGGL(k_loads_scatter, dim3(grid_for(n)), dim3(kBlock), 0, st, n, src, src_row, slot, table, row); }
+
+// `row` is a multiple of 256 and the table holds 6 rows of it: one workgroup per 256 lanes
+void launch_loads_reduce(hipStream_t st, const double *table, int64_t row, const LoadsTask &task)
+{
+    if (task.n <= 0) return;                                           // (the caller writes the zeros)
+    hipLaunchKernelGGL(k_loads_reduce, dim3(unsigned(row / kBlock)), dim3(kBlock), 0, st, table, row, task);
 }
 
 void launch_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine,

@@ -50,6 +50,10 @@
                          double *coarse_q,                                                                        \
                          const double *cbrt_vol, double *partial_min, const SumTask &rms);                          \
     void launch_surface_loads(hipStream_t, int64_t stride, const double *q, const LoadsTask &task);                  \
+    void launch_loads_terms(hipStream_t, int64_t stride, const double *q, const LoadsTerms &task);                   \
+    void launch_loads_scatter(hipStream_t, int64_t n, const double *src, int64_t src_row, const int32_t *slot,       \
+                              double *table, int64_t row);                                                           \
+    void launch_loads_reduce(hipStream_t, const double *table, int64_t row, const LoadsTask &task);                  \
     void launch_prolong(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_residuals,      \
                         const double *fine_residuals, double *fine_q, const double *cbrt_vol,                       \
                         double *partial_min);                                                                        \

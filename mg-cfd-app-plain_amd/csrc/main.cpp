@@ -45,7 +45,7 @@ struct Config {                       // the reference's `config` (src/Base/conf
     int gpus = 1;                     // --gpus N: a single-level input partitioned over N GPUs, a multigrid input one level per GPU
     bool gpus_share_device = false;   // --gpus-share-device: all N ranks on --device (rehearsal on a one-GPU box)
     bool gpus_partition = false;      // --gpus-partition: split every level of a multigrid input over the N GPUs (the default when N > levels)
-    bool output_loads = false;        // --output-loads: the level-0 surface loads of every cycle into surface_loads.* (one GPU only)
+    bool output_loads = false;        // --output-loads: the level-0 surface loads of every cycle into surface_loads.* (one GPU, or --gpus N --gpus-partition)
     double loads_ref[5] = {1.0, 1.0, 0.0, 0.0, 0.0};   // --loads-reference=S,c,x,y,z: reference area, length and moment point
 };
 
@@ -155,7 +155,9 @@ void print_help()
         "                                   1e-12 relative of the reference's per sweep, not reproducible bit for bit from run to run)\n"
         "  --legacy-ordering                Sort edges by (a,b,x,y,z) like the reference built with -DLEGACY_ORDERING\n"
         "  --output-loads                   Write the pressure force and moment on the solid walls and their coefficients\n"
-        "                                   after every cycle to surface_loads.* (CSV; one GPU only)\n"
+        "                                   after every cycle to surface_loads.* (CSV).  One GPU, or --gpus N together\n"
+        "                                   with --gpus-partition (every level split over the ranks; the same file, byte\n"
+        "                                   for byte); refused with --gpus N alone\n"
         "  --loads-reference=S,c,x,y,z      Reference area, length and moment point of --output-loads (default 1,1,0,0,0)\n");
 }
 
@@ -374,10 +376,8 @@ int validate_and_dump(const Config &conf, int levels, int mesh_variant, int64_t 
 }
 
 // --output-loads: one row per cycle, the loads and their coefficients (nothing on stdout: it stays the reference's)
-int write_loads_csv(const Config &conf, mgcfd_solver *solver, const std::vector<double> &loads)
+int write_loads_csv(const Config &conf, const double ff17[17], const std::vector<double> &loads)
 {
-    double ff17[17];
-    if (mgcfd_get_far_field(solver, ff17) != MGCFD_OK) return fail("reading the far field");
     const std::string path = output_filepath(conf, "surface_loads", 0);
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
@@ -413,7 +413,9 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count());
         std::vector<double> rms(static_cast<size_t>(conf.num_cycles > 0 ? conf.num_cycles : 0));
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = run.run_cycles(conf.num_cycles, rms.data());
+        std::vector<double> loads(conf.output_loads ? rms.size() * 6 : 0);
+        const int rc = conf.output_loads ? run.run_cycles_loads(conf.num_cycles, conf.loads_ref + 2, rms.data(), loads.data())
+                                         : run.run_cycles(conf.num_cycles, rms.data());
         const double total_compute_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < conf.num_cycles; i++)
             std::printf(levels <= 1 ? "\nCycle %d / %d (RMS = %.3e)" : "\nMG cycle %d / %d (RMS = %.3e)", i + 1, conf.num_cycles, rms[static_cast<size_t>(i)]);
@@ -431,6 +433,11 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
                               [&](int which, int ncols, double *out) { run.get_level0(which, ncols, out); return MGCFD_OK; },
                               [&](int level, int64_t *bad) { return run.check_invalid(level, bad); }))
             return EXIT_FAILURE;
+        if (conf.output_loads) {
+            double ff17[17];
+            run.far_field(ff17);
+            if (write_loads_csv(conf, ff17, loads)) return EXIT_FAILURE;
+        }
         std::string device_name = "unknown GPU";
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, conf.device) == hipSuccess) device_name = prop.name;
@@ -461,8 +468,8 @@ int main(int argc, char **argv)
     const double epoch_at_main = std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count();
     Config conf;
     if (!parse_arguments(argc, argv, conf)) return 1;
-    if (conf.output_loads && conf.gpus > 1) {
-        std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only (loads summed over ranks are not supported)\n");
+    if (conf.output_loads && conf.gpus > 1 && !conf.gpus_partition) {
+        std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
         return 1;
     }
     if (conf.input_file.empty()) {
@@ -535,7 +542,11 @@ int main(int argc, char **argv)
                           [&](int which, int ncols, double *out) { (void)ncols; return mgcfd_get_array(solver, 0, which, out); },
                           [&](int level, int64_t *bad) { return mgcfd_check_for_invalid_variables(solver, level, bad); }))
         return EXIT_FAILURE;
-    if (conf.output_loads && write_loads_csv(conf, solver, loads)) return EXIT_FAILURE;
+    if (conf.output_loads) {
+        double ff17[17];
+        if (mgcfd_get_far_field(solver, ff17) != MGCFD_OK) return fail("reading the far field");
+        if (write_loads_csv(conf, ff17, loads)) return EXIT_FAILURE;
+    }
 
     // ---- performance data (src/euler3d_cpu_double.cpp:778-785) ----
     std::string ih, il;

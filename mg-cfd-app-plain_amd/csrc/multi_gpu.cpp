@@ -14,6 +14,9 @@
 //                        library (mgcfd_group_cycles): the partitioned sweeps on every level, halo messages of the coarse
 //                        variables after mg_restrict, of the coarse residuals before the prolongation and of the fine
 //                        variables after it.  Every level equals the one-GPU run bit for bit on owned nodes.
+//   --output-loads       where every level is partitioned (--gpus-partition; a single-level input included): every rank is told
+//                        where its solid-wall edges lie in the whole level's order (mgcfd_rank_set_wall_slots) and the cycles
+//                        run through mgcfd_group_cycles_loads — the six loads of the one-GPU run, bit for bit.
 //
 // The reference has no multi-device path; its cycle loop (src/euler3d_cpu_double.cpp:371-694) fixes what has to move.
 #include "multi_gpu.hpp"
@@ -38,6 +41,8 @@ struct Part {
     std::vector<double> volumes, coords;
     std::vector<mgcfd_edge> edges;                    // internal | boundary | wall, the whole mesh's relative order kept
     int64_t ni = 0, nb = 0, nw = 0;
+    std::vector<int64_t> wall_slots;                  // where the nb solid-wall edges lie in the whole level's solid-wall slice ...
+    int64_t wall_total = 0;                           // ... and that slice's length (mgcfd_rank_set_wall_slots)
     std::map<int, std::vector<int64_t>> send, recv;   // peer -> local ids (ascending global id on both sides)
     std::vector<int64_t> mg_map;                      // partitioned hierarchy: LOCAL coarse id of every local node's parent
 };
@@ -79,7 +84,8 @@ std::vector<Part> partition_level(const mgcfd_level_desc &L, const std::vector<i
                 touched[static_cast<size_t>(E[e].a)] = touched[static_cast<size_t>(E[e].b)] = 1;
             }
         P.ni = static_cast<int64_t>(keep.size());
-        for (int64_t e = L.boundary_start; e < L.boundary_start + L.n_boundary; e++) if (part[static_cast<size_t>(E[e].b)] == r) { keep.push_back(e); P.nb++; }
+        P.wall_total = L.n_boundary;
+        for (int64_t e = L.boundary_start; e < L.boundary_start + L.n_boundary; e++) if (part[static_cast<size_t>(E[e].b)] == r) { keep.push_back(e); P.nb++; P.wall_slots.push_back(e - L.boundary_start); }
         for (int64_t e = L.wall_start; e < L.wall_start + L.n_wall; e++) if (part[static_cast<size_t>(E[e].b)] == r) { keep.push_back(e); P.nw++; }
         for (int64_t i = 0; i < L.nel; i++) if (touched[static_cast<size_t>(i)] && part[static_cast<size_t>(i)] != r) P.gids.push_back(i);   // ghosts, ascending
         std::fill(local.begin(), local.end(), int64_t(-1));
@@ -186,8 +192,9 @@ std::vector<std::vector<Part>> partition_hierarchy(const std::vector<mgcfd_level
                     x.a = loc[static_cast<size_t>(x.a)]; x.b = loc[static_cast<size_t>(x.b)];
                     P.edges.push_back(x); P.ni++;
                 }
+            P.wall_total = D.n_boundary;
             for (int64_t e = D.boundary_start; e < D.boundary_start + D.n_boundary; e++)
-                if (own[static_cast<size_t>(D.edges[e].b)] == r) { mgcfd_edge x = D.edges[e]; x.b = loc[static_cast<size_t>(x.b)]; P.edges.push_back(x); P.nb++; }
+                if (own[static_cast<size_t>(D.edges[e].b)] == r) { mgcfd_edge x = D.edges[e]; x.b = loc[static_cast<size_t>(x.b)]; P.edges.push_back(x); P.nb++; P.wall_slots.push_back(e - D.boundary_start); }
             for (int64_t e = D.wall_start; e < D.wall_start + D.n_wall; e++)
                 if (own[static_cast<size_t>(D.edges[e].b)] == r) { mgcfd_edge x = D.edges[e]; x.b = loc[static_cast<size_t>(x.b)]; P.edges.push_back(x); P.nw++; }
             for (size_t k = static_cast<size_t>(P.n_owned); k < P.gids.size(); k++) P.recv[own[static_cast<size_t>(P.gids[k])]].push_back(static_cast<int64_t>(k));
@@ -232,6 +239,8 @@ void set_halo(mgcfd_solver *s, int level, Part &P)
     }
     if (mgcfd_rank_set_halo(s, level, static_cast<int>(peers.size()), peers.data(), sc.data(), sp.data(), rc.data(), rp.data()) != MGCFD_OK)
         throw std::runtime_error(std::string("setting a rank's halo lists: ") + mgcfd_last_error());
+    if (mgcfd_rank_set_wall_slots(s, level, P.wall_total, static_cast<int64_t>(P.wall_slots.size()), P.wall_slots.data()) != MGCFD_OK)
+        throw std::runtime_error(std::string("setting a rank's wall slots: ") + mgcfd_last_error());
 }
 
 void check(int rc, const char *what)
@@ -404,6 +413,22 @@ static void hand_over(Run::Impl *p, int level, int which, int src, int dst, bool
         check(mgcfd_array_written(b, level, which), "marking the array written");
     }
 }
+
+int Run::run_cycles_loads(int cycles, const double ref_point[3], double *rms_out, double *loads_out)
+{
+    if (!p->partitioned && !p->partitioned_mg) throw std::runtime_error("surface loads over several GPUs need every level partitioned (--gpus-partition)");
+    // (a single partitioned level is a hierarchy of one level to mgcfd_group_cycles: the same sweeps, the same RMS)
+    std::vector<double> rms(static_cast<size_t>(std::max(cycles, 1)));
+    for (int c = 0; c < cycles; c += 4096) {
+        const int rc = mgcfd_group_cycles_loads(p->group, std::min(4096, cycles - c), ref_point, rms.data() + c, loads_out + static_cast<size_t>(c) * 6);
+        if (rc == MGCFD_ERR_NAN || rc == MGCFD_ERR_NEG_DENSITY || rc == MGCFD_ERR_NEG_ENERGY) return rc;
+        check(rc, "the partitioned V-cycles with surface loads");
+    }
+    if (rms_out) std::copy(rms.begin(), rms.begin() + cycles, rms_out);
+    return MGCFD_OK;
+}
+
+void Run::far_field(double ff17[17]) const { check(mgcfd_get_far_field(p->solvers[0], ff17), "reading the far field"); }
 
 int Run::run_cycles(int cycles, double *rms_out)
 {

@@ -25,6 +25,9 @@ public:
     bool partitioned() const;                              // true: the level(s) split over the ranks; false: one multigrid level per rank
     bool partitioned_hierarchy() const;                    // true: every level of a multigrid input split over the ranks (mgcfd_group_cycles)
     int run_cycles(int cycles, double *rms_out);           // MGCFD_OK or MGCFD_ERR_NAN / NEG_*
+    // ... and the whole level-0 surface loads of every cycle, loads_out[cycles][6] (partitioned() runs only: mgcfd_group_cycles_loads)
+    int run_cycles_loads(int cycles, const double ref_point[3], double *rms_out, double *loads_out);
+    void far_field(double ff17[17]) const;
     void get_level0(int which, int ncols, double *out) const;   // a level-0 array of the WHOLE mesh, original numbering
     int check_invalid(int level, int64_t *bad_cell) const;      // check_for_invalid_variables on `level` of the whole mesh (original cell id)
     void loop_iters(int level, int cycles, int64_t out[MGCFD_NUM_LOOPS]) const;

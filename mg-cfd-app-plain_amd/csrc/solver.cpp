@@ -147,6 +147,32 @@ struct HaloExchange {
     int64_t total_recv() const { return recv_off.empty() ? 0 : recv_off.back(); }
 };
 
+// Surface loads of a level split over ranks (mgcfd_rank_set_wall_slots; INTEGRATION.md "Surface loads", the partitioned form)
+struct RankLoads {
+    std::vector<int64_t> slot_host;      // position of this rank's k-th solid-wall edge in the whole level's solid-wall slice
+    int64_t total = 0;                   // the whole level's solid-wall edge count
+    int32_t *slot = nullptr;             // device [n_wall_rec]
+    hipEvent_t terms = nullptr;          // this rank's terms of the evaluation under way are stored up to here
+    bool checked = false;                // the host checks over all ranks have passed with these slots
+    // the gathering rank (rank 0):
+    int64_t row = 0;                     // total rounded up to 256
+    double *table = nullptr;             // device [6][row]: every rank's terms in the whole level's order, pad lanes +0.0
+    double *partial = nullptr;           // [6][row / 256]
+    unsigned *ticket = nullptr;
+    hipEvent_t read = nullptr;           // the reduce that read the table last is enqueued up to here
+    // one rank per process over RCCL: the terms travel as a message
+    std::vector<int64_t> counts;         // every rank's edge count, agreed once
+    double *compact = nullptr;           // this rank's terms [6][own count]; rank 0: the other ranks' messages, one after another
+    std::vector<int32_t *> peer_slot;    // rank 0: device copies of the other ranks' slots
+    ~RankLoads()
+    {
+        for (void *p : {static_cast<void *>(slot), static_cast<void *>(table), static_cast<void *>(partial), static_cast<void *>(ticket), static_cast<void *>(compact)})
+            if (p) (void)hipFree(p);
+        for (int32_t *p : peer_slot) if (p) (void)hipFree(p);
+        for (hipEvent_t e : {terms, read}) if (e) (void)hipEventDestroy(e);
+    }
+};
+
 struct DeviceLevel {
     mgcfd_level_desc info{};             // sizes only (pointers nulled)
     std::vector<mgcfd_edge> edges;       // final edge weights, original order
@@ -195,6 +221,7 @@ struct DeviceLevel {
     int64_t n_wall_rec = 0;
     double *loads_partial = nullptr;
     unsigned *loads_ticket = nullptr;
+    std::unique_ptr<RankLoads> rl;       // a partitioned level whose ranks add their loads up
     void *block = nullptr;               // the one allocation behind every array listed at creation (LevelStaging)
     size_t block_bytes = 0;
     bool in_block(const void *p) const { return block && p >= block && p < static_cast<const char *>(block) + block_bytes; }
@@ -276,7 +303,7 @@ struct mgcfd_solver {
     double *loads_ring = nullptr, *loads_dev = nullptr;                       // loads_dev: ref [3] | out [6]
     double loads_ref_host[3] = {0.0, 0.0, 0.0};
     bool loads_in_cycle = false;
-    bool partitioned = false;                      // made by mgcfd_create_partitioned* (no loads: they would need a sum over ranks)
+    bool partitioned = false;                      // made by mgcfd_create_partitioned* (loads: the group and rank forms, over all ranks)
     double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
     std::vector<EventPair> pending;
     std::vector<hipEvent_t> free_events;
@@ -686,6 +713,7 @@ mgcfd_solver::~mgcfd_solver()
         for (void *p : ptrs) if (p && !lv.in_block(p)) (void)hipFree(p);      // (what an option uploaded later has an allocation of its own)
         if (lv.block) (void)hipFree(lv.block);
         for (auto &hp : lv.halo_plans) if (hp.first) (void)hipFree(hp.first);
+        lv.rl.reset();
         if (lv.hx) {
             HaloExchange &hx = *lv.hx;
             for (void *m : hx.ipc_opened) (void)hipIpcCloseMemHandle(m);
@@ -1680,9 +1708,17 @@ static void launch_loads(mgcfd_solver *s, DeviceLevel &lv, bool to_ring)
 // Loads need the whole level on one solver: refuse a partitioned solver or a rank.
 static void loads_require_whole(const mgcfd_solver *s);
 
+// the reference point to the device (and the room for a synchronous call's result)
+static void loads_upload_ref(mgcfd_solver *s, const double *ref_point);
+
 static void loads_prepare(mgcfd_solver *s, const double *ref_point)
 {
     loads_require_whole(s);
+    loads_upload_ref(s, ref_point);
+}
+
+static void loads_upload_ref(mgcfd_solver *s, const double *ref_point)
+{
     if (!s->loads_dev) s->loads_dev = dev_alloc<double>(9);
     for (int k = 0; k < 3; k++) s->loads_ref_host[k] = ref_point ? ref_point[k] : 0.0;
     HIP_CHECK(hipMemcpyAsync(s->loads_dev, s->loads_ref_host, sizeof(double) * 3, hipMemcpyHostToDevice, s->stream));
@@ -2227,7 +2263,7 @@ struct Rccl {
     const char *(*GetErrorString)(int) = nullptr;
     int (*CommCount)(void *, int *) = nullptr;    // (optional: what the communicator itself says about its size and this rank)
     int (*CommUserRank)(void *, int *) = nullptr;
-    static constexpr int kDouble = 8, kMin = 3, kSum = 0;     // ncclDouble, ncclMin, ncclSum (rccl.h)
+    static constexpr int kDouble = 8, kInt32 = 2, kMin = 3, kSum = 0;     // ncclDouble, ncclInt32, ncclMin, ncclSum (rccl.h)
 };
 Rccl g_rccl;
 
@@ -3528,6 +3564,130 @@ static void group_exchange_array(mgcfd_group *g, int level, int which)
     }
 }
 
+// ---- surface loads of a partitioned level -------------------------------------------------------------------------------
+// mgcfd_surface_loads needs every solid-wall edge of the level in ONE order to be the bitwise function of the state it is.  A
+// level split over ranks keeps that order: rank r's k-th solid-wall edge is edge slot[k] of the whole level's solid-wall slice
+// (mgcfd_rank_set_wall_slots), every rank stores its edges' six terms at those slots of a table on rank 0 (k_loads_terms: in a
+// group straight into rank 0's memory, as the direct halo push stores into the peers' ghosts; over RCCL as a message that
+// rank 0 places by slot, k_loads_scatter), and rank 0 reduces the table by the trees of k_surface_loads (k_loads_reduce).
+// Terms travel by stores and copies only — an arithmetic reduction of "term + zeros" would turn -0.0 into +0.0.
+static RankLoads &rank_loads_of(mgcfd_solver *s, int level, int rank)
+{
+    DeviceLevel &lv = s->level(level);
+    if (!lv.rl)
+        throw std::invalid_argument("surface loads: rank " + std::to_string(rank) + " has no wall slots on level " + std::to_string(level) +
+                                    " (mgcfd_rank_set_wall_slots)");
+    return *lv.rl;
+}
+
+static hipEvent_t loads_event()
+{
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return e;
+}
+
+// the gathering rank's table (pad lanes zero, and they stay zero: slots lie below `total`), partial sums and ticket
+static void loads_gather_alloc(RankLoads &r0)
+{
+    if (r0.table || r0.total == 0) return;
+    r0.row = (r0.total + 255) / 256 * 256;
+    r0.table = dev_alloc<double>(static_cast<size_t>(6 * r0.row));
+    HIP_CHECK(hipMemset(r0.table, 0, sizeof(double) * static_cast<size_t>(6 * r0.row)));
+    r0.partial = dev_alloc<double>(static_cast<size_t>(6 * (r0.row / 256)));
+    r0.ticket = dev_alloc<unsigned>(1);
+    HIP_CHECK(hipMemset(r0.ticket, 0, sizeof(unsigned)));
+}
+
+static LoadsTerms loads_terms_of(mgcfd_solver *s, DeviceLevel &lv, const int32_t *slot, double *table, int64_t row)
+{
+    LoadsTerms t;
+    t.rec = lv.wall_rec; t.n = lv.n_wall_rec; t.p_inf = s->p_inf; t.ref = s->loads_dev;
+    t.slot = slot; t.table = table; t.row = row;
+    return t;
+}
+
+// rank 0's reduce of its table on its stream: into the synchronous result (loads_dev + 3) or the history row of the cycle
+static void loads_reduce(mgcfd_solver *s0, RankLoads &r0, bool to_ring)
+{
+    LoadsTask t;
+    t.n = r0.total; t.partial = r0.partial; t.ticket = r0.ticket;
+    if (to_ring) { t.ring = s0->loads_ring; t.count = s0->rms_count; t.cap = mgcfd_solver::kRmsRing; }
+    else t.out = s0->loads_dev + 3;
+    exact::launch_loads_reduce(s0->stream, r0.table, r0.row, t);
+}
+
+// In-process groups.  Before the first launch, once per set of slots: every rank of the level has slots, all name the same
+// total, and together they name every edge of the whole level exactly once.  Then the reference point to every rank, rank
+// 0's table and the events — nothing of this happens inside a cycle.
+static void group_loads_prepare(mgcfd_group *g, int level, const double *ref_point)
+{
+    const int n = static_cast<int>(g->ranks.size());
+    bool checked = true;
+    for (int r = 0; r < n; r++) checked = rank_loads_of(g->ranks[static_cast<size_t>(r)], level, r).checked && checked;
+    RankLoads &r0 = *g->ranks[0]->level(level).rl;
+    if (!checked) {
+        std::vector<int> named_by(static_cast<size_t>(r0.total), -1);
+        int64_t named = 0;
+        for (int r = 0; r < n; r++) {
+            const RankLoads &rl = *g->ranks[static_cast<size_t>(r)]->level(level).rl;
+            const std::string who = "surface loads: the wall slots of rank " + std::to_string(r) + " on level " + std::to_string(level);
+            if (rl.total != r0.total)
+                throw std::invalid_argument(who + " give the whole level " + std::to_string(rl.total) + " solid-wall edges, rank 0's " + std::to_string(r0.total));
+            for (int64_t k : rl.slot_host) {
+                int &by = named_by[static_cast<size_t>(k)];
+                if (by >= 0) throw std::invalid_argument(who + " name slot " + std::to_string(k) + ", which rank " + std::to_string(by) + " names too");
+                by = r;
+                named++;
+            }
+        }
+        if (named != r0.total)
+            throw std::invalid_argument("surface loads: the wall slots of ranks 0 .. " + std::to_string(n - 1) + " on level " + std::to_string(level) + " name " +
+                                        std::to_string(named) + " of the level's " + std::to_string(r0.total) + " solid-wall edges");
+        for (mgcfd_solver *s : g->ranks) s->level(level).rl->checked = true;
+    }
+    for (mgcfd_solver *s : g->ranks) {
+        s->use_device();
+        loads_upload_ref(s, ref_point);
+        RankLoads &rl = *s->level(level).rl;
+        if (!rl.terms) rl.terms = loads_event();
+    }
+    g->ranks[0]->use_device();
+    loads_gather_alloc(r0);
+    if (!r0.read) r0.read = loads_event();
+}
+
+// One rank's part of an evaluation (on its device): its terms into rank 0's table, behind the reduce that read the table
+// last, then its event.  A rank without a solid-wall edge launches nothing and records the event all the same.
+static void group_loads_terms(mgcfd_group *g, mgcfd_solver *s, int level)
+{
+    mgcfd_solver *s0 = g->ranks[0];
+    RankLoads &r0 = *s0->level(level).rl;
+    if (r0.total == 0) return;
+    DeviceLevel &lv = s->level(level);
+    if (s != s0) HIP_CHECK(hipStreamWaitEvent(s->stream, r0.read, 0));      // (rank 0's own stream is behind its reduce anyway)
+    exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, lv.rl->slot, r0.table, r0.row));
+    HIP_CHECK(hipEventRecord(lv.rl->terms, s->stream));
+}
+
+// ... and rank 0's (on its device, every rank's terms event of this evaluation recorded): the reduce behind all of them
+static void group_loads_reduce(mgcfd_group *g, int level, bool to_ring)
+{
+    mgcfd_solver *s0 = g->ranks[0];
+    RankLoads &r0 = *s0->level(level).rl;
+    if (r0.total == 0) return;
+    for (mgcfd_solver *s : g->ranks) if (s != s0) HIP_CHECK(hipStreamWaitEvent(s0->stream, s->level(level).rl->terms, 0));
+    loads_reduce(s0, r0, to_ring);
+    HIP_CHECK(hipEventRecord(r0.read, s0->stream));
+}
+
+static void group_loads_once(mgcfd_group *g, int level, bool to_ring)
+{
+    for (mgcfd_solver *s : g->ranks) { s->use_device(); group_loads_terms(g, s, level); }
+    g->ranks[0]->use_device();
+    group_loads_reduce(g, level, to_ring);
+}
+
 static void append_level0_sumsq(mgcfd_solver *s)
 {
     DeviceLevel &lv = s->level(0);
@@ -3536,7 +3696,8 @@ static void append_level0_sumsq(mgcfd_solver *s)
 }
 
 // one V-cycle of every rank of an in-process group (one host thread issues it)
-static void group_cycle_once(mgcfd_group *g, bool with_rms)
+// with_loads: the level-0 loads of the state the cycle leaves into the row of the cycle's RMS (rank 0's history)
+static void group_cycle_once(mgcfd_group *g, bool with_rms, bool with_loads)
 {
     const int n = static_cast<int>(g->ranks[0]->L.size());
     for (int l = 0; l < n; l++) {
@@ -3557,13 +3718,14 @@ static void group_cycle_once(mgcfd_group *g, bool with_rms)
         group_exchange_array(g, l, MGCFD_ARR_VARIABLES);
         if (l > 0) group_sweep_once(g, l);
     }
+    if (with_loads) group_loads_once(g, 0, true);
 }
 
 // The same cycle with a host thread per rank (direct mode; what mgcfd_group_cycles runs for groups of several ranks:
 // one thread issuing every rank's ~100 calls per cycle makes the host the bottleneck N times over).  As in
 // group_sweeps_threaded the threads agree on the ORDER of event records and waits through barriers: one after the first
 // half of compute_step_factor and after every stage of a sweep, two per transfer exchange (all packed | all delivered).
-static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms)
+static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms, bool with_loads)
 {
     const int n = static_cast<int>(g->ranks.size());
     const int nl = static_cast<int>(g->ranks[0]->L.size());
@@ -3642,6 +3804,12 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms)
                 exchange(l, MGCFD_ARR_VARIABLES);
                 if (l > 0) sweep(l);
             }
+            if (with_loads) {
+                step([&] { group_loads_terms(g, s, 0); });
+                bar.wait();                             // every rank's terms event is recorded
+                // (rank 0's record of `read` lies ahead of the barriers of the next cycle's first sweep, the other ranks' waits for it behind them)
+                if (r == 0) step([&] { group_loads_reduce(g, 0, true); });
+            }
         }
         step([&] { for (int l = 0; l < nl; l++) wait_for_peers(g, s, l, 2); HIP_CHECK(hipGetLastError()); });
     };
@@ -3664,15 +3832,25 @@ static int group_read_errors(mgcfd_group *g)
     return code;
 }
 
-int mgcfd_group_cycles(mgcfd_group *g, int cycles, double *rms_out)
+// loads_out != nullptr (mgcfd_group_cycles_loads): also the level-0 surface loads of the state every cycle leaves, [cycles][6]
+static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const double *ref_point, double *loads_out)
 {
     REQUIRE(g);
     int code = MGCFD_OK;
+    if (loads_out) std::fill(loads_out, loads_out + static_cast<size_t>(std::max(cycles, 0)) * 6, std::numeric_limits<double>::quiet_NaN());
+    const bool with_rms = rms_out || loads_out;                 // (a cycle's loads go into the row of its RMS)
     const int rc = guarded([&] {
         if (cycles > mgcfd_solver::kRmsRing) throw std::invalid_argument("at most 4096 cycles per call");
         const int n = static_cast<int>(g->ranks[0]->L.size());
         for (mgcfd_solver *s : g->ranks) if (static_cast<int>(s->L.size()) != n) throw std::invalid_argument("the ranks of a group hold the same number of levels");
         for (int l = 0; l < n; l++) group_prepare_level(g, l);
+        if (loads_out) {
+            group_loads_prepare(g, 0, ref_point);
+            mgcfd_solver *s0 = g->ranks[0];
+            s0->use_device();
+            if (!s0->loads_ring) s0->loads_ring = dev_alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+        }
+        const bool with_loads = loads_out != nullptr;
         for (mgcfd_solver *s : g->ranks) {
             s->use_device();
             if (!s->rms_ring) { s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing); s->rms_count = dev_alloc<int>(1); }
@@ -3691,8 +3869,8 @@ int mgcfd_group_cycles(mgcfd_group *g, int cycles, double *rms_out)
             std::sort(devs.begin(), devs.end());
             all_direct = all_direct && std::adjacent_find(devs.begin(), devs.end()) == devs.end();
         }
-        if (all_direct) group_cycles_threaded(g, cycles, rms_out != nullptr);
-        else for (int c = 0; c < cycles; c++) group_cycle_once(g, rms_out != nullptr);
+        if (all_direct) group_cycles_threaded(g, cycles, with_rms, with_loads);
+        else for (int c = 0; c < cycles; c++) group_cycle_once(g, with_rms, with_loads);
         // every rank's stream behind the last pushes into it, then the read-backs
         for (mgcfd_solver *s : g->ranks) { s->use_device(); for (int l = 0; l < n; l++) if (s->level(l).hx->direct) wait_for_peers(g, s, l, 2); }
         if (rms_out) {
@@ -3707,12 +3885,46 @@ int mgcfd_group_cycles(mgcfd_group *g, int cycles, double *rms_out)
             }
             for (int k = 0; k < cycles; k++) rms_out[k] = std::sqrt(sums[static_cast<size_t>(k)] / double(nodes));
         }
+        if (loads_out && cycles > 0) {
+            mgcfd_solver *s0 = g->ranks[0];
+            std::vector<double> rows(static_cast<size_t>(cycles) * 6, 0.0);     // (no solid wall: zeros, nothing was launched)
+            if (s0->level(0).rl->total > 0) {
+                s0->use_device();
+                HIP_CHECK(hipMemcpyAsync(rows.data(), s0->loads_ring, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, s0->stream));
+                HIP_CHECK(hipStreamSynchronize(s0->stream));
+            }
+            std::copy(rows.begin(), rows.end(), loads_out);
+        }
         code = group_read_errors(g);
         for (mgcfd_solver *s : g->ranks) { s->use_device(); HIP_CHECK(hipGetLastError()); }
     });
     if (rc != MGCFD_OK) return rc;
     if (code != MGCFD_OK) g_last_error = "check_for_invalid_variables: a rank of the group found an invalid state during the cycles";
     return code;
+}
+
+int mgcfd_group_cycles(mgcfd_group *g, int cycles, double *rms_out) { return group_cycles_impl(g, cycles, rms_out, nullptr, nullptr); }
+int mgcfd_group_cycles_loads(mgcfd_group *g, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
+{
+    REQUIRE(loads_out);
+    return group_cycles_impl(g, cycles, rms_out, ref_point, loads_out);
+}
+
+int mgcfd_group_surface_loads(mgcfd_group *g, int level, const double ref_point[3], double out6[6])
+{
+    REQUIRE(g); REQUIRE(out6);
+    return guarded([&] {
+        group_loads_prepare(g, level, ref_point);
+        mgcfd_solver *s0 = g->ranks[0];
+        double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (s0->level(level).rl->total > 0) {                 // (no solid wall: exact zeros, nothing launched)
+            group_loads_once(g, level, false);
+            HIP_CHECK(hipMemcpyAsync(got, s0->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s0->stream));
+            HIP_CHECK(hipStreamSynchronize(s0->stream));
+            HIP_CHECK(hipGetLastError());
+        }
+        std::memcpy(out6, got, sizeof(got));
+    });
 }
 
 // ---- the same for one rank per process over RCCL ----
@@ -3727,7 +3939,130 @@ static void rank_exchange_array(mgcfd_solver *s, int level, int which)
     if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
 }
 
-static void rank_cycle_once(mgcfd_solver *s, bool with_rms)
+// Surface loads, one rank per process.  NOTE: rehearsed with ONE rank only (what a one-GPU box offers): with more, the
+// agreement below and the messages are as written, never run.
+// Once per set of slots, outside the cycles: the message lengths (every rank's edge count and the total it names, by one
+// all-reduce(SUM) of a vector that is zero but for the rank's own entries — counts, not terms), the other ranks' slots to
+// rank 0, which checks them before any launch stores by them, and the verdict to everybody.
+static void rank_loads_prepare(mgcfd_solver *s, int level, const double *ref_point)
+{
+    mgcfd_comm &c = comm_of(s);
+    if (!c.rccl) throw std::invalid_argument("in-process ranks: mgcfd_group_surface_loads / mgcfd_group_cycles_loads");
+    DeviceLevel &lv = s->level(level);
+    RankLoads &rl = rank_loads_of(s, level, c.rank);
+    loads_upload_ref(s, ref_point);
+    if (rl.checked) return;
+    const size_t w = static_cast<size_t>(c.world), me = static_cast<size_t>(c.rank);
+    auto all_sum = [&](std::vector<double> &v) {
+        double *d = dev_upload(v);
+        try {
+            RCCL_CHECK(g_rccl.AllReduce(d, d, v.size(), Rccl::kDouble, Rccl::kSum, c.rccl, s->stream));
+            HIP_CHECK(hipMemcpyAsync(v.data(), d, sizeof(double) * v.size(), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+        } catch (...) { (void)hipFree(d); throw; }
+        (void)hipFree(d);
+    };
+    std::vector<double> v(2 * w, 0.0);
+    v[me] = double(lv.n_wall_rec); v[w + me] = double(rl.total);
+    all_sum(v);
+    rl.counts.assign(w, 0);
+    int64_t sum = 0;
+    for (size_t r = 0; r < w; r++) {
+        rl.counts[r] = static_cast<int64_t>(v[r]);
+        sum += rl.counts[r];
+        if (static_cast<int64_t>(v[w + r]) != rl.total)
+            throw std::invalid_argument("surface loads: the wall slots of rank " + std::to_string(r) + " on level " + std::to_string(level) + " give the whole level " +
+                                        std::to_string(static_cast<int64_t>(v[w + r])) + " solid-wall edges, rank " + std::to_string(me) + "'s " + std::to_string(rl.total));
+    }
+    if (sum != rl.total)
+        throw std::invalid_argument("surface loads: the wall slots of the ranks on level " + std::to_string(level) + " name " + std::to_string(sum) +
+                                    " of the level's " + std::to_string(rl.total) + " solid-wall edges");
+    if (w > 1 && rl.total > 0) {
+        if (me == 0) { for (int32_t *p : rl.peer_slot) if (p) (void)hipFree(p); rl.peer_slot.assign(w, nullptr); }
+        RCCL_CHECK(g_rccl.GroupStart());
+        if (me == 0) {
+            for (size_t r = 1; r < w; r++) {
+                if (rl.counts[r] == 0) continue;
+                rl.peer_slot[r] = dev_alloc<int32_t>(static_cast<size_t>(rl.counts[r]));
+                RCCL_CHECK(g_rccl.Recv(rl.peer_slot[r], static_cast<size_t>(rl.counts[r]), Rccl::kInt32, static_cast<int>(r), c.rccl, s->stream));
+            }
+        } else if (lv.n_wall_rec > 0) {
+            RCCL_CHECK(g_rccl.Send(rl.slot, static_cast<size_t>(lv.n_wall_rec), Rccl::kInt32, 0, c.rccl, s->stream));
+        }
+        RCCL_CHECK(g_rccl.GroupEnd());
+        std::vector<double> bad(1, 0.0);
+        if (me == 0) {
+            std::vector<char> seen(static_cast<size_t>(rl.total), 0);
+            for (int64_t k : rl.slot_host) seen[static_cast<size_t>(k)] = 1;
+            for (size_t r = 1; r < w; r++) {
+                std::vector<int32_t> got(static_cast<size_t>(rl.counts[r]));
+                if (!got.empty()) HIP_CHECK(hipMemcpyAsync(got.data(), rl.peer_slot[r], sizeof(int32_t) * got.size(), hipMemcpyDeviceToHost, s->stream));
+                HIP_CHECK(hipStreamSynchronize(s->stream));
+                for (int32_t k : got) {
+                    if (k < 0 || k >= rl.total || seen[static_cast<size_t>(k)]) { bad[0] = 1.0; break; }
+                    seen[static_cast<size_t>(k)] = 1;
+                }
+            }
+        }
+        all_sum(bad);
+        if (bad[0] != 0.0)
+            throw std::invalid_argument("surface loads: the wall slots of the ranks on level " + std::to_string(level) + " name a slot twice or outside the level's " +
+                                        std::to_string(rl.total) + " solid-wall edges");
+    }
+    if (me == 0) loads_gather_alloc(rl);
+    if (w > 1 && !rl.compact) {
+        const int64_t n = me == 0 ? rl.total - rl.counts[0] : lv.n_wall_rec;
+        rl.compact = dev_alloc<double>(static_cast<size_t>(6 * n));
+    }
+    rl.checked = true;
+}
+
+// one evaluation on this rank's stream: the other ranks send their compact terms, rank 0 places them by slot and reduces
+static void rank_loads_once(mgcfd_solver *s, int level, bool to_ring)
+{
+    mgcfd_comm &c = comm_of(s);
+    DeviceLevel &lv = s->level(level);
+    RankLoads &rl = *lv.rl;
+    if (rl.total == 0) return;
+    if (c.rank != 0) {
+        if (lv.n_wall_rec == 0) return;
+        exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, nullptr, rl.compact, lv.n_wall_rec));
+        RCCL_CHECK(g_rccl.GroupStart());
+        RCCL_CHECK(g_rccl.Send(rl.compact, static_cast<size_t>(6 * lv.n_wall_rec), Rccl::kDouble, 0, c.rccl, s->stream));
+        RCCL_CHECK(g_rccl.GroupEnd());
+        return;
+    }
+    exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, rl.slot, rl.table, rl.row));
+    if (c.world > 1) {
+        RCCL_CHECK(g_rccl.GroupStart());
+        int64_t off = 0;
+        for (size_t r = 1; r < rl.counts.size(); r++) {
+            if (rl.counts[r] == 0) continue;
+            RCCL_CHECK(g_rccl.Recv(rl.compact + 6 * off, static_cast<size_t>(6 * rl.counts[r]), Rccl::kDouble, static_cast<int>(r), c.rccl, s->stream));
+            off += rl.counts[r];
+        }
+        RCCL_CHECK(g_rccl.GroupEnd());
+        off = 0;
+        for (size_t r = 1; r < rl.counts.size(); r++) {
+            exact::launch_loads_scatter(s->stream, rl.counts[r], rl.compact + 6 * off, rl.counts[r], rl.peer_slot[r], rl.table, rl.row);
+            off += rl.counts[r];
+        }
+    }
+    loads_reduce(s, rl, to_ring);
+}
+
+// rank 0's `n` results at `buf` to the same place on every other rank
+static void rank_loads_share(mgcfd_solver *s, double *buf, size_t n)
+{
+    mgcfd_comm &c = comm_of(s);
+    if (c.world == 1 || n == 0) return;
+    RCCL_CHECK(g_rccl.GroupStart());
+    if (c.rank == 0) { for (int r = 1; r < c.world; r++) RCCL_CHECK(g_rccl.Send(buf, n, Rccl::kDouble, r, c.rccl, s->stream)); }
+    else RCCL_CHECK(g_rccl.Recv(buf, n, Rccl::kDouble, 0, c.rccl, s->stream));
+    RCCL_CHECK(g_rccl.GroupEnd());
+}
+
+static void rank_cycle_once(mgcfd_solver *s, bool with_rms, bool with_loads)
 {
     const int n = static_cast<int>(s->L.size());
     for (int l = 0; l < n; l++) {
@@ -3741,12 +4076,16 @@ static void rank_cycle_once(mgcfd_solver *s, bool with_rms)
         rank_exchange_array(s, l, MGCFD_ARR_VARIABLES);
         if (l > 0) rank_sweep_once(s, l);
     }
+    if (with_loads) rank_loads_once(s, 0, true);
 }
 
-int mgcfd_rank_cycles(mgcfd_solver *s, int cycles, double *rms_out)
+// loads_out != nullptr (mgcfd_rank_cycles_loads): also the level-0 surface loads of the state every cycle leaves, [cycles][6]
+static int rank_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out)
 {
     REQUIRE(s);
     int code = MGCFD_OK;
+    if (loads_out) std::fill(loads_out, loads_out + static_cast<size_t>(std::max(cycles, 0)) * 6, std::numeric_limits<double>::quiet_NaN());
+    const bool with_rms = rms_out || loads_out;                 // (a cycle's loads go into the row of its RMS)
     const int rc = guarded([&] {
         s->use_device();
         mgcfd_comm &c = comm_of(s);
@@ -3759,7 +4098,20 @@ int mgcfd_rank_cycles(mgcfd_solver *s, int cycles, double *rms_out)
         }
         if (!s->rms_ring) { s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing); s->rms_count = dev_alloc<int>(1); }
         HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
-        for (int k = 0; k < cycles; k++) rank_cycle_once(s, rms_out != nullptr);
+        if (loads_out) {
+            rank_loads_prepare(s, 0, ref_point);
+            if (!s->loads_ring) s->loads_ring = dev_alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+        }
+        for (int k = 0; k < cycles; k++) rank_cycle_once(s, with_rms, loads_out != nullptr);
+        if (loads_out && cycles > 0) {
+            std::vector<double> rows(static_cast<size_t>(cycles) * 6, 0.0);     // (no solid wall: zeros, nothing was launched)
+            if (s->level(0).rl->total > 0) {
+                rank_loads_share(s, s->loads_ring, rows.size());
+                HIP_CHECK(hipMemcpyAsync(rows.data(), s->loads_ring, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, s->stream));
+                HIP_CHECK(hipStreamSynchronize(s->stream));
+            }
+            std::copy(rows.begin(), rows.end(), loads_out);
+        }
         if (rms_out && cycles > 0) {
             // calc_rms of the whole level (validation.cpp:91-105): the ranks' sums of every cycle added by ONE all-reduce
             RCCL_CHECK(g_rccl.AllReduce(s->rms_ring, s->rms_ring, static_cast<size_t>(cycles), Rccl::kDouble, Rccl::kSum, c.rccl, s->stream));
@@ -3780,6 +4132,60 @@ int mgcfd_rank_cycles(mgcfd_solver *s, int cycles, double *rms_out)
     if (rc != MGCFD_OK) return rc;
     if (code != MGCFD_OK) g_last_error = "check_for_invalid_variables: invalid state during the cycles";
     return code;
+}
+
+int mgcfd_rank_cycles(mgcfd_solver *s, int cycles, double *rms_out) { return rank_cycles_impl(s, cycles, rms_out, nullptr, nullptr); }
+int mgcfd_rank_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
+{
+    REQUIRE(loads_out);
+    return rank_cycles_impl(s, cycles, rms_out, ref_point, loads_out);
+}
+
+int mgcfd_rank_surface_loads(mgcfd_solver *s, int level, const double ref_point[3], double out6[6])
+{
+    REQUIRE(s); REQUIRE(out6);
+    return guarded([&] {
+        s->use_device();
+        rank_loads_prepare(s, level, ref_point);
+        double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (s->level(level).rl->total > 0) {                  // (no solid wall: exact zeros, nothing launched or sent)
+            rank_loads_once(s, level, false);
+            rank_loads_share(s, s->loads_dev + 3, 6);
+            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            HIP_CHECK(hipGetLastError());
+        }
+        std::memcpy(out6, got, sizeof(got));
+    });
+}
+
+// A partitioned solver's solid-wall edges in the whole level's order: slot[k] = position of its k-th one in the whole
+// level's solid-wall slice, n_total = that slice's length, n = how many slots are given (the level's local n_boundary).
+int mgcfd_rank_set_wall_slots(mgcfd_solver *s, int level, int64_t n_total, int64_t n, const int64_t *slot)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        const std::string who = "surface loads: wall slots of level " + std::to_string(level) + ": ";
+        if (!s->partitioned) throw std::invalid_argument(who + "the solver holds whole levels (mgcfd_surface_loads needs no slots)");
+        if (n_total < 0 || n_total > int64_t(1) << 30) throw std::invalid_argument(who + "the whole level's count must lie in [0, 2^30]");
+        if (n != lv.n_wall_rec)
+            throw std::invalid_argument(who + std::to_string(n) + " slots given, the level holds " + std::to_string(lv.n_wall_rec) + " solid-wall edges here");
+        if (lv.n_wall_rec > 0 && !slot) throw std::invalid_argument(who + "null slot list");
+        auto rl = std::make_unique<RankLoads>();
+        rl->total = n_total;
+        std::vector<int32_t> slot32;
+        for (int64_t k = 0; k < lv.n_wall_rec; k++) {
+            if (slot[k] < 0 || slot[k] >= n_total || (k > 0 && slot[k] <= slot[k - 1]))
+                throw std::invalid_argument(who + "the slots must be strictly ascending in [0, n_total) (local edge lists keep the whole level's order)");
+            rl->slot_host.push_back(slot[k]);
+            slot32.push_back(static_cast<int32_t>(slot[k]));
+        }
+        if (!slot32.empty()) rl->slot = dev_upload(slot32);
+        HIP_CHECK(hipStreamSynchronize(s->stream));          // (nothing in flight still reads what the old slots' arrays held)
+        lv.rl = std::move(rl);
+    });
 }
 
 // What a solver is a rank of, AS THE LIBRARY SEES IT: out[0] this rank, out[1] the number of ranks, out[2] the transport
@@ -3827,10 +4233,10 @@ int mgcfd_rank_halo_info(const mgcfd_solver *s, int level, int64_t out[4])
 static void loads_require_whole(const mgcfd_solver *s)
 {
     if (s->partitioned)
-        throw std::invalid_argument("surface loads: the solver holds a partitioned level (mgcfd_create_partitioned*); loads summed "
-                                    "over ranks are not supported");
+        throw std::invalid_argument("surface loads: the solver holds a partitioned level (mgcfd_create_partitioned*); the loads over all "
+                                    "ranks come from mgcfd_group_surface_loads / mgcfd_group_cycles_loads or mgcfd_rank_surface_loads / mgcfd_rank_cycles_loads");
     if (g_comms.count(const_cast<mgcfd_solver *>(s)))
-        throw std::invalid_argument("surface loads: the solver is attached as a rank; loads summed over ranks are not supported");
+        throw std::invalid_argument("surface loads: the solver is attached as a rank; the loads of a partitioned level come from the group and rank calls");
 }
 
 extern "C" {

@@ -151,6 +151,11 @@ _SIGNATURES = [
     ("mgcfd_surface_loads", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_run_cycles_loads", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     ("mgcfd_load_coefficients", C.c_int, [_vp, _vp, C.c_double, C.c_double, _vp]),
+    ("mgcfd_rank_set_wall_slots", C.c_int, [_vp, C.c_int, _i64, _i64, _vp]),
+    ("mgcfd_group_surface_loads", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_group_cycles_loads", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_rank_surface_loads", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_rank_cycles_loads", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -606,6 +611,12 @@ class Solver:
         rp = (_vp * max(n, 1))(*[a.ctypes.data for a in keep[n:]])
         self._c(self.lib.mgcfd_rank_set_halo(self.handle, l, n, pa, sc, sp, rc, rp))
 
+    def rank_set_wall_slots(self, l: int, part):
+        """part: mgcfd.partition.LevelPart — where its solid-wall edges lie in the whole level's solid-wall slice
+        (``wall_slots``, ``wall_total``); what the loads over all ranks need (mgcfd_rank_set_wall_slots)."""
+        slots = np.ascontiguousarray(part.wall_slots, dtype=np.int64)
+        self._c(self.lib.mgcfd_rank_set_wall_slots(self.handle, l, int(part.wall_total), len(slots), _ptr(slots)))
+
     def rank_halo_info(self, l: int) -> dict:
         out = (_i64 * 4)()
         self._c(self.lib.mgcfd_rank_halo_info(self.handle, l, out))
@@ -654,11 +665,26 @@ class Solver:
     def rank_exchange(self, l: int): self._c(self.lib.mgcfd_rank_exchange(self.handle, l))
     def rank_sweeps(self, l: int, sweeps: int = 1): self._c(self.lib.mgcfd_rank_sweeps(self.handle, l, sweeps))
 
-    def rank_cycles(self, cycles: int, rms: bool = True) -> np.ndarray:
-        """V-cycles of this rank's share of a partitioned hierarchy over RCCL (mgcfd_rank_cycles); the level-0 RMS of each cycle."""
+    def rank_cycles(self, cycles: int, rms: bool = True, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
+        """V-cycles of this rank's share of a partitioned hierarchy over RCCL (mgcfd_rank_cycles); the level-0 RMS of each cycle.
+        With ``loads=True`` (rank_set_wall_slots on level 0 first) also the whole level's surface loads at the end of every
+        cycle: ``(rms, loads[cycles, 6])``, the same rows on every rank (mgcfd_rank_cycles_loads)."""
         out = np.zeros(max(cycles, 1), dtype=np.float64)
-        self._c(self.lib.mgcfd_rank_cycles(self.handle, cycles, out.ctypes.data_as(C.POINTER(C.c_double)) if rms else None))
-        return out[:cycles]
+        rms_ptr = out.ctypes.data_as(C.POINTER(C.c_double)) if rms else None
+        if not loads:
+            self._c(self.lib.mgcfd_rank_cycles(self.handle, cycles, rms_ptr))
+            return out[:cycles]
+        hist = np.zeros((max(cycles, 1), 6))
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        self._c(self.lib.mgcfd_rank_cycles_loads(self.handle, cycles, _ptr(ref), _ptr(out) if rms else None, _ptr(hist)))
+        return out[:cycles], hist[:cycles]
+
+    def rank_surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """Fx Fy Fz Mx My Mz of the WHOLE level ``level`` from an RCCL rank (collective; mgcfd_rank_surface_loads)."""
+        out = np.zeros(6)
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        self._c(self.lib.mgcfd_rank_surface_loads(self.handle, level, _ptr(ref), _ptr(out)))
+        return out
 
     def rank_residual_sumsq(self, l: int) -> float:
         v = C.c_double()
@@ -710,11 +736,26 @@ class Group:
         return out[:n]
     def synchronize(self): _check(self.lib, self.lib.mgcfd_group_synchronize(self.handle))
 
-    def cycles(self, n: int = 1, rms: bool = True) -> np.ndarray:
-        """n V-cycles of a partitioned hierarchy (mgcfd_group_cycles); the level-0 RMS of each cycle."""
+    def cycles(self, n: int = 1, rms: bool = True, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
+        """n V-cycles of a partitioned hierarchy (mgcfd_group_cycles); the level-0 RMS of each cycle.  With ``loads=True``
+        (Solver.rank_set_wall_slots on level 0 of every rank first) also the whole level's surface loads at the end of every
+        cycle: ``(rms, loads[n, 6])`` (mgcfd_group_cycles_loads)."""
         out = np.zeros(max(n, 1), dtype=np.float64)
-        _check(self.lib, self.lib.mgcfd_group_cycles(self.handle, n, out.ctypes.data_as(C.POINTER(C.c_double)) if rms else None))
-        return out[:n]
+        rms_ptr = out.ctypes.data_as(C.POINTER(C.c_double)) if rms else None
+        if not loads:
+            _check(self.lib, self.lib.mgcfd_group_cycles(self.handle, n, rms_ptr))
+            return out[:n]
+        hist = np.zeros((max(n, 1), 6))
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        _check(self.lib, self.lib.mgcfd_group_cycles_loads(self.handle, n, _ptr(ref), _ptr(out) if rms else None, _ptr(hist)))
+        return out[:n], hist[:n]
+
+    def surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """Fx Fy Fz Mx My Mz of the WHOLE level ``level`` in the ranks' current state (mgcfd_group_surface_loads)."""
+        out = np.zeros(6)
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        _check(self.lib, self.lib.mgcfd_group_surface_loads(self.handle, level, _ptr(ref), _ptr(out)))
+        return out
 
     def rms(self, l: int = 0) -> float:
         v = C.c_double()

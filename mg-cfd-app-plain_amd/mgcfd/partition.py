@@ -30,6 +30,10 @@ class LevelPart:
     level: dict                            # read_grid()-shaped dict of the local part (for Solver.from_arrays)
     send: Dict[int, np.ndarray] = field(default_factory=dict)   # peer -> LOCAL ids of owned nodes the peer holds as ghosts
     recv: Dict[int, np.ndarray] = field(default_factory=dict)   # peer -> LOCAL ids of ghosts owned by the peer
+    # surface loads over ranks (Solver.rank_set_wall_slots): where this part's solid-wall edges lie in the whole level's
+    # solid-wall slice [boundary_start, boundary_start + n_boundary), and that slice's length
+    wall_slots: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=np.int64))
+    wall_total: int = 0
 
     @property
     def n_local(self) -> int:
@@ -112,7 +116,8 @@ def partition_level(level: dict, part: np.ndarray) -> List[LevelPart]:
         lvl = {"nel": len(gids), "volumes": np.ascontiguousarray(level["volumes"])[gids], "coords": coords,
                "edges": le, "n_internal": len(keep_int), "n_boundary": len(keep_bnd), "n_wall": len(keep_wall),
                "mg_map": None}
-        parts.append(LevelPart(rank=r, n_owned=len(owned), global_ids=gids, level=lvl))
+        parts.append(LevelPart(rank=r, n_owned=len(owned), global_ids=gids, level=lvl,
+                               wall_slots=(keep_bnd - ni).astype(np.int64), wall_total=nb))
     # halo lists: ghosts of rank r owned by s, ascending global id on both sides
     for r, P in enumerate(parts):
         ghost_g = P.global_ids[P.n_owned:]
@@ -204,7 +209,8 @@ def partition_hierarchy(levels: List[dict], part0: np.ndarray) -> List[Hierarchy
             lvl = {"nel": len(gids), "volumes": np.ascontiguousarray(L["volumes"])[gids],
                    "coords": None if L.get("coords") is None else np.ascontiguousarray(L["coords"])[gids],
                    "edges": le, "n_internal": len(keep_int), "n_boundary": len(keep_bnd), "n_wall": len(keep_wall), "mg_map": None}
-            parts.append(LevelPart(rank=r, n_owned=len(owned[l]), global_ids=gids, level=lvl))
+            parts.append(LevelPart(rank=r, n_owned=len(owned[l]), global_ids=gids, level=lvl,
+                                   wall_slots=(keep_bnd - ni).astype(np.int64), wall_total=nb))
         for l in range(n_levels - 1):                    # local maps: parent of every local fine node, in coarse local ids
             logc = np.full(int(levels[l + 1]["nel"]), -1, dtype=np.int64)
             logc[parts[l + 1].global_ids] = np.arange(parts[l + 1].n_local)
