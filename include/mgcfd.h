@@ -243,6 +243,27 @@ int64_t mgcfd_level_nel(const mgcfd_solver *s, int level);
 int64_t mgcfd_level_num_internal_edges(const mgcfd_solver *s, int level);
 /* ff_variable[5] + the four ff_flux_contribution_* vectors (17 doubles), globals.h:11-15. */
 int mgcfd_get_far_field(const mgcfd_solver *s, double *out17);
+/* The free stream at run time.  The reference fixes it when it is compiled (ff_mach = 1.2, deg_angle_of_attack = 0,
+ * src/Base/const.h:14-15); here the caller chooses it.
+ * mgcfd_free_stream_constants — host only: the 17 doubles of mgcfd_get_far_field for a Mach number and an angle of attack in
+ * degrees, the reference's expressions (src/Kernels/cfd_loops.h:85-119 and 57-83) in their order, never contracted to FMA;
+ * gamma = 1.4, p = 1 and rho = 1.4 stay fixed, the velocity is |V| (cos a, sin a, 0).  (1.2, 0.0) gives the reference's values
+ * bit for bit.  MGCFD_ERR_ARG for a non-finite value, mach <= 0 or |alpha_deg| >= 90.
+ * mgcfd_set_free_stream — synchronises, then replaces the far field every flux, stage, init and loads kernel is given (and the
+ * far-field pressure of the surface loads).  reinitialise = 1: `variables` of every level becomes the new far field, as
+ * mgcfd_create leaves it, and a pending invalid state (mgcfd_pending_invalid_state) is forgotten; 0: the state stays (a warm
+ * start: the next cycles continue from the flow of the previous free stream).  Every captured graph of the solver
+ * (MGCFD_OPT_GRAPH: sweeps, cycles, an RCCL rank's sweeps — mgcfd_rank_graph_status out[0] goes back to 0) is dropped, since
+ * a captured launch holds the far field as an argument; the next run captures again.  Works on plain, partitioned and
+ * rank-attached solvers.  A solver it is never called on behaves as before.  MGCFD_ERR_ARG, and nothing changed, while a
+ * kernel-granular sweep is under way on any level (after mgcfd_sweep_flux0, or between mgcfd_sweep_stage 0 and the last
+ * stage): its buffers hold half a sweep of the old free stream.
+ * Ranks: the ranks of one flow must hold the same far field.  An in-process group checks it (further down); between RCCL
+ * ranks in different processes nothing can, so agreement there is the CALLER's duty: call it with the same arguments on
+ * every rank (mgcfd/distributed.py: set_free_stream_all broadcasts rank 0's). */
+int mgcfd_free_stream_constants(double mach, double alpha_deg, double out17[17]);
+int mgcfd_set_free_stream(mgcfd_solver *s, double mach, double alpha_deg, int reinitialise);
+int mgcfd_get_free_stream(const mgcfd_solver *s, double *mach, double *alpha_deg);
 
 /* ---------------------------------------------------------------------------------
  * Kernel-granular operations (asynchronous on the solver's stream)
@@ -483,6 +504,11 @@ int mgcfd_rank_ipc_status(mgcfd_solver *s, int level, int *timed_out);
 int mgcfd_rank_ipc_detach(mgcfd_solver *s, int level);       /* back to the buffered form; closes the neighbours' mappings */
 int mgcfd_group_create(int n, mgcfd_solver *const *solvers, mgcfd_group **out);   /* solvers[r] becomes rank r of n */
 void mgcfd_group_destroy(mgcfd_group *g);
+/* mgcfd_set_free_stream on every rank: one pass leaves all ranks idle and without graphs (the group's own sweep graph,
+ * MGCFD_GROUP_GRAPH=1, included), a second one sets them; a bad argument or a sweep under way changes no rank.  The group calls that run sweeps, cycles or loads (mgcfd_group_sweeps[_rms],
+ * mgcfd_group_cycles[_loads], mgcfd_group_surface_loads) return MGCFD_ERR_ARG while the ranks' far fields differ in any bit;
+ * the message names the first rank that differs from rank 0. */
+int mgcfd_group_set_free_stream(mgcfd_group *g, double mach, double alpha_deg, int reinitialise);
 int mgcfd_group_exchange(mgcfd_group *g, int level);
 int mgcfd_group_sweeps(mgcfd_group *g, int level, int sweeps);   /* asynchronous; a host thread per rank issues that rank's launches */
 /* The same with calc_rms (src/Kernels/validation.cpp:91-105) after every sweep — the reference's cycle loop prints it per

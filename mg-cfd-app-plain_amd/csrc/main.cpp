@@ -47,7 +47,43 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool gpus_partition = false;      // --gpus-partition: split every level of a multigrid input over the N GPUs (the default when N > levels)
     bool output_loads = false;        // --output-loads: the level-0 surface loads of every cycle into surface_loads.* (one GPU, or --gpus N --gpus-partition)
     double loads_ref[5] = {1.0, 1.0, 0.0, 0.0, 0.0};   // --loads-reference=S,c,x,y,z: reference area, length and moment point
+    // the free stream (the reference compiles it in: ff_mach = 1.2, deg_angle_of_attack = 0, src/Base/const.h:14-15)
+    bool free_stream_given = false;   // --mach / --alpha / ff_mach / angle_of_attack: mgcfd_set_free_stream before the first cycle
+    double ff_mach = 1.2, angle_of_attack = 0.0;
+    bool polar = false;               // --polar A0:A1:N: N angles from A0 to A1 inclusive, -g cycles each, polar.csv
+    double polar_a0 = 0.0, polar_a1 = 0.0;
+    int polar_n = 0;
+    // the k-th angle of the run (one angle without --polar)
+    int num_angles() const { return polar ? polar_n : 1; }
+    double angle(int k) const { return !polar ? angle_of_attack : (polar_n == 1 ? polar_a0 : polar_a0 + (polar_a1 - polar_a0) * double(k) / double(polar_n - 1)); }
 };
+
+// one finite number and nothing else
+bool parse_number(const char *text, double *out)
+{
+    if (!text || *text == '\0' || std::isspace(static_cast<unsigned char>(*text))) return false;
+    char *end = nullptr;
+    const double v = std::strtod(text, &end);
+    if (end == text || *end != '\0' || !std::isfinite(v)) return false;
+    *out = v;
+    return true;
+}
+
+// "A0:A1:N": two finite angles and a count of at least 1
+bool parse_polar(const char *text, Config &c)
+{
+    const std::string t(text ? text : "");
+    const size_t p1 = t.find(':'), p2 = p1 == std::string::npos ? p1 : t.find(':', p1 + 1);
+    if (p2 == std::string::npos || t.find(':', p2 + 1) != std::string::npos) return false;
+    double n = 0.0;
+    if (!parse_number(t.substr(0, p1).c_str(), &c.polar_a0) || !parse_number(t.substr(p1 + 1, p2 - p1 - 1).c_str(), &c.polar_a1) ||
+        !parse_number(t.substr(p2 + 1).c_str(), &n))
+        return false;
+    if (n < 1.0 || n > 100000.0 || n != std::floor(n)) return false;
+    c.polar_n = static_cast<int>(n);
+    c.polar = true;
+    return true;
+}
 
 // "S,c,x,y,z": five finite numbers, S and c positive; false on anything else
 bool parse_loads_reference(const char *text, double out[5])
@@ -92,6 +128,8 @@ void set_param(Config &c, const std::string &key, const std::string &value)
     else if (key == "output_edge_fluxes") { if (value == "Y") c.output_edge_fluxes = true; }
     else if (key == "output_fluxes") { if (value == "Y") c.output_fluxes = true; }
     else if (key == "output_volumes") { if (value == "Y") c.output_volumes = true; }
+    else if (key == "ff_mach") { if (parse_number(value.c_str(), &c.ff_mach)) c.free_stream_given = true; else std::printf("WARNING: ff_mach = '%s' is not a number.\n", value.c_str()); }
+    else if (key == "angle_of_attack") { if (parse_number(value.c_str(), &c.angle_of_attack)) c.free_stream_given = true; else std::printf("WARNING: angle_of_attack = '%s' is not a number.\n", value.c_str()); }
     else std::printf("WARNING: Unknown key '%s' encountered during parsing of config file.\n", key.c_str());
 }
 
@@ -158,7 +196,14 @@ void print_help()
         "                                   after every cycle to surface_loads.* (CSV).  One GPU, or --gpus N together\n"
         "                                   with --gpus-partition (every level split over the ranks; the same file, byte\n"
         "                                   for byte); refused with --gpus N alone\n"
-        "  --loads-reference=S,c,x,y,z      Reference area, length and moment point of --output-loads (default 1,1,0,0,0)\n");
+        "  --loads-reference=S,c,x,y,z      Reference area, length and moment point of --output-loads (default 1,1,0,0,0)\n"
+        "  --mach=M                         Free-stream Mach number (default 1.2, the reference's; config key ff_mach)\n"
+        "  --alpha=DEG                      Angle of attack in degrees, inside (-90, 90) (default 0; config key angle_of_attack)\n"
+        "  --polar=A0:A1:N                  N angles of attack from A0 to A1 inclusive, -g cycles each: the first starts from its\n"
+        "                                   far field, every later one from the flow of the angle before it.  Writes polar.*\n"
+        "                                   (CSV: alpha,mach,rms_last, the loads and coefficients of each angle's last cycle);\n"
+        "                                   the dumps and surface_loads.* are the last angle's.  One GPU, or --gpus N with\n"
+        "                                   --gpus-partition\n");
 }
 
 bool parse_arguments(int argc, char **argv, Config &c)
@@ -190,6 +235,9 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"gpus-partition", no_argument, nullptr, 1012},
         {"output-loads", no_argument, nullptr, 1013},
         {"loads-reference", required_argument, nullptr, 1014},
+        {"mach", required_argument, nullptr, 1015},
+        {"alpha", required_argument, nullptr, 1016},
+        {"polar", required_argument, nullptr, 1017},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -219,6 +267,20 @@ bool parse_arguments(int argc, char **argv, Config &c)
             case 1014:
                 if (!parse_loads_reference(optarg, c.loads_ref)) {
                     std::fprintf(stderr, "ERROR: --loads-reference=%s: expected S,c,x,y,z (five numbers, S and c positive)\n", optarg);
+                    return false;
+                }
+                break;
+            case 1015:
+            case 1016:
+                if (!parse_number(optarg, optc == 1015 ? &c.ff_mach : &c.angle_of_attack)) {
+                    std::fprintf(stderr, "ERROR: --%s=%s: expected a number\n", optc == 1015 ? "mach" : "alpha", optarg);
+                    return false;
+                }
+                c.free_stream_given = true;
+                break;
+            case 1017:
+                if (!parse_polar(optarg, c)) {
+                    std::fprintf(stderr, "ERROR: --polar=%s: expected A0:A1:N (two angles in degrees and a count of at least 1)\n", optarg);
                     return false;
                 }
                 break;
@@ -398,6 +460,55 @@ int write_loads_csv(const Config &conf, const double ff17[17], const std::vector
     return 0;
 }
 
+// --polar: one row per angle — the RMS, loads and coefficients of its last cycle (nothing on stdout)
+struct PolarRow { double alpha, mach, rms_last, loads[6], ff17[17]; };
+int write_polar_csv(const Config &conf, const std::vector<PolarRow> &rows)
+{
+    const std::string path = csv_filepath(conf, "polar.csv");
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail(("opening " + path).c_str());
+    std::fprintf(f, "alpha,mach,rms_last,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz\n");
+    for (const PolarRow &r : rows) {
+        double coef[6];
+        if (mgcfd_load_coefficients(r.ff17, r.loads, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) {
+            std::fclose(f);
+            return fail("computing the load coefficients");
+        }
+        std::fprintf(f, "%.17e,%.17e,%.17e", r.alpha, r.mach, r.rms_last);
+        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", r.loads[k]);
+        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
+    return 0;
+}
+
+// The cycles of the whole run: without the free-stream options one batch, as ever; with them mgcfd_set_free_stream first
+// (the first angle from its far field, a later angle of --polar from the flow before it) and one batch per angle.  rms and
+// loads end up holding the LAST angle's histories.  set(mach, alpha, reinitialise) and cycles(rms, loads-or-null) return
+// MGCFD codes.
+template <typename Set, typename Cycles>
+int run_all_cycles(const Config &conf, std::vector<double> &rms, std::vector<double> &loads, std::vector<PolarRow> &polar_rows,
+                   Set &&set, Cycles &&cycles)
+{
+    const bool want_loads = conf.output_loads || conf.polar;
+    if (!conf.free_stream_given && !conf.polar) return cycles(rms.data(), want_loads ? loads.data() : nullptr);
+    for (int k = 0; k < conf.num_angles(); k++) {
+        int rc = set(conf.ff_mach, conf.angle(k), k == 0 ? 1 : 0);
+        if (rc != MGCFD_OK) return rc;
+        rc = cycles(rms.data(), want_loads ? loads.data() : nullptr);
+        if (rc != MGCFD_OK) return rc;
+        if (conf.polar) {
+            PolarRow row{};
+            row.alpha = conf.angle(k); row.mach = conf.ff_mach;
+            row.rms_last = rms.empty() ? std::nan("") : rms.back();
+            for (int q = 0; q < 6; q++) row.loads[q] = loads.empty() ? std::nan("") : loads[loads.size() - 6 + static_cast<size_t>(q)];
+            polar_rows.push_back(row);
+        }
+    }
+    return MGCFD_OK;
+}
+
 // --gpus N (multi_gpu.cpp): the same outputs as the one-GPU run from N ranks of this process
 int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int mesh_variant, int problem_size)
 {
@@ -413,9 +524,16 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count());
         std::vector<double> rms(static_cast<size_t>(conf.num_cycles > 0 ? conf.num_cycles : 0));
         const auto t0 = std::chrono::steady_clock::now();
-        std::vector<double> loads(conf.output_loads ? rms.size() * 6 : 0);
-        const int rc = conf.output_loads ? run.run_cycles_loads(conf.num_cycles, conf.loads_ref + 2, rms.data(), loads.data())
-                                         : run.run_cycles(conf.num_cycles, rms.data());
+        std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
+        std::vector<PolarRow> polar_rows;
+        const int rc = run_all_cycles(conf, rms, loads, polar_rows,
+            [&](double mach, double alpha, int reinitialise) { return run.set_free_stream(mach, alpha, reinitialise); },
+            [&](double *rms_out, double *loads_out) {
+                return loads_out ? run.run_cycles_loads(conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out) : run.run_cycles(conf.num_cycles, rms_out);
+            });
+        for (PolarRow &row : polar_rows) {          // (the coefficients of an angle are taken against that angle's far field)
+            if (mgcfd_free_stream_constants(row.mach, row.alpha, row.ff17) != MGCFD_OK) return fail("the free stream of a polar row");
+        }
         const double total_compute_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < conf.num_cycles; i++)
             std::printf(levels <= 1 ? "\nCycle %d / %d (RMS = %.3e)" : "\nMG cycle %d / %d (RMS = %.3e)", i + 1, conf.num_cycles, rms[static_cast<size_t>(i)]);
@@ -438,6 +556,7 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
             run.far_field(ff17);
             if (write_loads_csv(conf, ff17, loads)) return EXIT_FAILURE;
         }
+        if (conf.polar && write_polar_csv(conf, polar_rows)) return EXIT_FAILURE;
         std::string device_name = "unknown GPU";
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, conf.device) == hipSuccess) device_name = prop.name;
@@ -446,7 +565,7 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
         std::vector<std::vector<std::string>> times(static_cast<size_t>(levels)), iters(static_cast<size_t>(levels));
         for (int l = 0; l < levels; l++) {
             int64_t n[MGCFD_NUM_LOOPS];
-            run.loop_iters(l, conf.num_cycles, n);
+            run.loop_iters(l, conf.num_cycles * conf.num_angles(), n);
             for (int k = 0; k < MGCFD_NUM_LOOPS; k++) { times[static_cast<size_t>(l)].push_back("0"); iters[static_cast<size_t>(l)].push_back(std::to_string(n[k])); }
         }
         const std::string tpath = csv_filepath(conf, "Times.csv"), ipath = csv_filepath(conf, "LoopNumIters.csv");
@@ -471,6 +590,19 @@ int main(int argc, char **argv)
     if (conf.output_loads && conf.gpus > 1 && !conf.gpus_partition) {
         std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
         return 1;
+    }
+    if (conf.polar && conf.gpus > 1 && !conf.gpus_partition) {
+        std::fprintf(stderr, "ERROR: --polar runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
+        return 1;
+    }
+    if (conf.free_stream_given || conf.polar) {
+        // (the arguments are checked before any file is read: the same rule as mgcfd_set_free_stream's)
+        double ff17[17];
+        for (int k = 0; k < conf.num_angles(); k += std::max(1, conf.num_angles() - 1))
+            if (mgcfd_free_stream_constants(conf.ff_mach, conf.angle(k), ff17) != MGCFD_OK) {
+                std::fprintf(stderr, "ERROR: %s\n", mgcfd_last_error());
+                return 1;
+            }
     }
     if (conf.input_file.empty()) {
         std::printf("ERROR: input_file not set\n");
@@ -510,9 +642,16 @@ int main(int argc, char **argv)
     // ---- compute (src/euler3d_cpu_double.cpp:368-698) ----
     std::vector<double> rms(static_cast<size_t>(conf.num_cycles > 0 ? conf.num_cycles : 0));
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> loads(conf.output_loads ? rms.size() * 6 : 0);
-    const int rc = conf.output_loads ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms.data(), loads.data())
-                                     : mgcfd_run_cycles(solver, conf.num_cycles, rms.data());
+    std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
+    std::vector<PolarRow> polar_rows;
+    const int rc = run_all_cycles(conf, rms, loads, polar_rows,
+        [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
+        [&](double *rms_out, double *loads_out) {
+            return loads_out ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out)
+                             : mgcfd_run_cycles(solver, conf.num_cycles, rms_out);
+        });
+    for (PolarRow &row : polar_rows)            // (the coefficients of an angle are taken against that angle's far field)
+        if (mgcfd_free_stream_constants(row.mach, row.alpha, row.ff17) != MGCFD_OK) return fail("the free stream of a polar row");
     const double total_compute_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const bool invalid = rc == MGCFD_ERR_NAN || rc == MGCFD_ERR_NEG_DENSITY || rc == MGCFD_ERR_NEG_ENERGY;
     int64_t bad_cell = -1;
@@ -547,6 +686,7 @@ int main(int argc, char **argv)
         if (mgcfd_get_far_field(solver, ff17) != MGCFD_OK) return fail("reading the far field");
         if (write_loads_csv(conf, ff17, loads)) return EXIT_FAILURE;
     }
+    if (conf.polar && write_polar_csv(conf, polar_rows)) return EXIT_FAILURE;
 
     // ---- performance data (src/euler3d_cpu_double.cpp:778-785) ----
     std::string ih, il;

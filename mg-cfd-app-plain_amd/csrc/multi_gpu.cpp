@@ -430,6 +430,17 @@ int Run::run_cycles_loads(int cycles, const double ref_point[3], double *rms_out
 
 void Run::far_field(double ff17[17]) const { check(mgcfd_get_far_field(p->solvers[0], ff17), "reading the far field"); }
 
+int Run::set_free_stream(double mach, double alpha_deg, int reinitialise)
+{
+    // (one level per GPU: every rank holds the whole hierarchy and sweeps its own levels — all of them take the far field)
+    if (p->group) return mgcfd_group_set_free_stream(p->group, mach, alpha_deg, reinitialise);
+    for (mgcfd_solver *s : p->solvers) {
+        const int rc = mgcfd_set_free_stream(s, mach, alpha_deg, reinitialise);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
 int Run::run_cycles(int cycles, double *rms_out)
 {
     const int n = p->levels, w = ranks();

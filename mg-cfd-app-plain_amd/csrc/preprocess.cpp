@@ -212,10 +212,10 @@ inline bool coincident(const double *fine, const double *coarse)
 
 } // namespace
 
-void far_field_constants(double *out)
+void free_stream_constants(double ff_mach, double deg_aoa, double *out)
 {
-    // src/Kernels/cfd_loops.h:85-119, src/Base/const.h:9-15
-    const double gamma = 1.4, ff_mach = 1.2, deg_aoa = 0.0;
+    // src/Kernels/cfd_loops.h:85-119, src/Base/const.h:9-15 with ff_mach and deg_angle_of_attack as arguments
+    const double gamma = 1.4;
     const double angle = double(3.1415926535897931 / 180.0) * double(deg_aoa);
     double var[5];
     var[0] = 1.4;
@@ -236,6 +236,9 @@ void far_field_constants(double *out)
     const double de_p = var[4] + pressure;
     de[0] = vx * de_p; de[1] = vy * de_p; de[2] = vz * de_p;
 }
+
+// the reference's compile-time free stream: Mach 1.2 at 0 degrees (src/Base/const.h:14-15)
+void far_field_constants(double *out) { free_stream_constants(kDefaultMach, kDefaultAlphaDeg, out); }
 
 void adjust_and_dampen(const mgcfd_level_desc &L, int mesh_variant, std::vector<mgcfd_edge> &edges)
 {

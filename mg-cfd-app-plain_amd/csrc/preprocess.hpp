@@ -206,5 +206,8 @@ void adjust_and_dampen(const mgcfd_level_desc &lvl, int mesh_variant, std::vecto
 
 // ff_variable + ff_flux_contribution_* (src/Kernels/cfd_loops.h:85-119); out[17].
 void far_field_constants(double *out17);
+// ... the same expressions with the Mach number and the angle of attack (degrees) as arguments (mgcfd_free_stream_constants)
+constexpr double kDefaultMach = 1.2, kDefaultAlphaDeg = 0.0;
+void free_stream_constants(double mach, double alpha_deg, double *out17);
 
 } // namespace mgcfd

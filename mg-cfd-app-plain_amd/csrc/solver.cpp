@@ -305,6 +305,36 @@ struct mgcfd_solver {
     bool loads_in_cycle = false;
     bool partitioned = false;                      // made by mgcfd_create_partitioned* (loads: the group and rank forms, over all ranks)
     double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
+    double fs_mach = kDefaultMach, fs_alpha_deg = kDefaultAlphaDeg;      // what ff17 was computed from (mgcfd_set_free_stream)
+    // ff17 -> the kernels' argument (ff) and the loads' p_inf.  Launches already captured keep the old values: drop_graphs.
+    void set_far_field(const double *in17)
+    {
+        std::memcpy(ff17, in17, sizeof(double) * 17);
+        std::memcpy(ff.var, ff17, sizeof(double) * 5);
+        std::memcpy(ff.fc_mx, ff17 + 5, sizeof(double) * 3);
+        std::memcpy(ff.fc_my, ff17 + 8, sizeof(double) * 3);
+        std::memcpy(ff.fc_mz, ff17 + 11, sizeof(double) * 3);
+        std::memcpy(ff.fc_de, ff17 + 14, sizeof(double) * 3);
+        // derive() (cfd_loops.h:121-148) on the far field, as k_surface_loads evaluates it per node
+        const double *f = ff17;
+        const double vx = f[1] / f[0], vy = f[2] / f[0], vz = f[3] / f[0];
+        const double speed_sqd = vx * vx + vy * vy + vz * vz;
+        p_inf = (1.4 - 1.0) * (f[4] - 0.5 * f[0] * speed_sqd);
+    }
+    // Every captured launch carries the far field (and p_inf) it was captured with as kernel arguments: after a change of
+    // free stream the sweep graphs, the cycle graphs and a rank's sweep graphs go, and the next run captures again.
+    // Call with the stream idle.
+    void drop_graphs()
+    {
+        for (auto &g : sweep_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
+        sweep_graphs.clear();
+        for (auto &g : cycle_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
+        cycle_graphs.clear();
+        for (DeviceLevel &lv : L) {
+            if (!lv.hx) continue;
+            for (hipGraphExec_t &ge : lv.hx->sweep_graph) if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
+        }
+    }
     std::vector<EventPair> pending;
     std::vector<hipEvent_t> free_events;
 
@@ -777,20 +807,12 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
     auto s = std::make_unique<mgcfd_solver>();
     s->device = device;
     s->mesh_variant = mesh_variant;
-    far_field_constants(s->ff17);
-    std::memcpy(s->ff.var, s->ff17, sizeof(double) * 5);
-    std::memcpy(s->ff.fc_mx, s->ff17 + 5, sizeof(double) * 3);
-    std::memcpy(s->ff.fc_my, s->ff17 + 8, sizeof(double) * 3);
-    std::memcpy(s->ff.fc_mz, s->ff17 + 11, sizeof(double) * 3);
-    std::memcpy(s->ff.fc_de, s->ff17 + 14, sizeof(double) * 3);
-    s->partitioned = n_owned != nullptr;
     {
-        // derive() (cfd_loops.h:121-148) on the far field, as k_surface_loads evaluates it per node
-        const double *f = s->ff17;
-        const double vx = f[1] / f[0], vy = f[2] / f[0], vz = f[3] / f[0];
-        const double speed_sqd = vx * vx + vy * vy + vz * vz;
-        s->p_inf = (1.4 - 1.0) * (f[4] - 0.5 * f[0] * speed_sqd);
+        double ff17[17];
+        far_field_constants(ff17);
+        s->set_far_field(ff17);
     }
+    s->partitioned = n_owned != nullptr;
 
     s->L.resize(static_cast<size_t>(nlevels));
     const bool timing = std::getenv("MGCFD_PLAN_TIMING") != nullptr;      // where the host time of a solver's creation goes (stderr)
@@ -1360,6 +1382,69 @@ int mgcfd_get_far_field(const mgcfd_solver *s, double *out17)
     REQUIRE(s); REQUIRE(out17);
     std::memcpy(out17, s->ff17, sizeof(double) * 17);
     return MGCFD_OK;
+}
+int mgcfd_free_stream_constants(double mach, double alpha_deg, double out17[17])
+{
+    REQUIRE(out17);
+    if (!std::isfinite(mach) || !std::isfinite(alpha_deg)) { g_last_error = "free stream: Mach number and angle of attack must be finite"; return MGCFD_ERR_ARG; }
+    if (!(mach > 0.0)) { g_last_error = "free stream: the Mach number must be positive"; return MGCFD_ERR_ARG; }
+    if (!(std::fabs(alpha_deg) < 90.0)) { g_last_error = "free stream: the angle of attack must lie inside (-90, 90) degrees"; return MGCFD_ERR_ARG; }
+    free_stream_constants(mach, alpha_deg, out17);
+    return MGCFD_OK;
+}
+int mgcfd_get_free_stream(const mgcfd_solver *s, double *mach, double *alpha_deg)
+{
+    REQUIRE(s);
+    if (mach) *mach = s->fs_mach;
+    if (alpha_deg) *alpha_deg = s->fs_alpha_deg;
+    return MGCFD_OK;
+}
+static void synchronize_with_group(mgcfd_solver *s);
+// A kernel-granular sweep that has begun (mgcfd_sweep_flux0, mgcfd_sweep_stage 0 or 1) holds half a sweep of the OLD free
+// stream in its buffers and flags: the setter refuses until its last stage has run.
+static void require_no_sweep_under_way(const mgcfd_solver *s)
+{
+    for (size_t l = 0; l < s->L.size(); l++)
+        if (s->L[l].stage_next != 0 || s->L[l].sweep_flux0_done)
+            throw std::invalid_argument("free stream: a sweep is under way on level " + std::to_string(l) + " (mgcfd_sweep_flux0 / mgcfd_sweep_stage): finish it first");
+}
+// The solver is idle and its graphs are gone: the new far field, and with `reinitialise` the state mgcfd_create leaves.
+static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mach, double alpha_deg, int reinitialise)
+{
+    s->use_device();
+    s->set_far_field(ff17);
+    s->fs_mach = mach;
+    s->fs_alpha_deg = alpha_deg;
+    if (!reinitialise) return;                  // warm start: the state stays
+    for (DeviceLevel &lv : s->L) {
+        s->settle_residuals(lv);                // (residuals[] keeps what the last sweep left: its operands are about to change)
+        exact::launch_init_variables(s->stream, lv.dp.stride, s->ff, lv.q);
+        exact::launch_init_variables(s->stream, lv.dp.stride, s->ff, lv.q_alt);     // valid numbers in the padded tail
+        lv.min_ahead = false;
+        lv.have_sumsq = false;
+        lv.stage_out = nullptr;                 // (MGCFD_ARR_STAGE named a stage of the state that has just gone)
+    }
+    HIP_CHECK(hipMemsetAsync(s->err, 0xFF, sizeof(unsigned long long), s->stream));
+    s->check_seq = 0;
+    s->invalid_cell = -1; s->invalid_cycle = -1;
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    HIP_CHECK(hipGetLastError());
+}
+int mgcfd_set_free_stream(mgcfd_solver *s, double mach, double alpha_deg, int reinitialise)
+{
+    REQUIRE(s);
+    double ff17[17];
+    const int rc = mgcfd_free_stream_constants(mach, alpha_deg, ff17);
+    if (rc != MGCFD_OK) return rc;
+    return guarded([&] {
+        require_no_sweep_under_way(s);
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);                  // (a rank: its message stream, and the streams a group's graph forks to)
+        s->drop_graphs();
+        apply_free_stream(s, ff17, mach, alpha_deg, reinitialise);
+    });
 }
 
 // ---- kernel-granular operations ----
@@ -2310,6 +2395,36 @@ static mgcfd_comm &comm_of(mgcfd_solver *s)
     auto it = g_comms.find(s);
     if (it == g_comms.end()) throw std::invalid_argument("the solver is not a rank of anything: call mgcfd_rank_attach_rccl or mgcfd_group_create first");
     return it->second;
+}
+
+// mgcfd_set_free_stream: whatever else may still touch this solver's memory or replay launches captured for it is idle too —
+// the rank's message stream, and in an in-process group the other ranks' streams (their pushes land in this rank's ghosts,
+// and a group's sweep graph, kept by rank 0, holds every rank's launches: it goes as well)
+static void synchronize_with_group(mgcfd_solver *s)
+{
+    for (DeviceLevel &lv : s->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+    auto it = g_comms.find(s);
+    if (it == g_comms.end() || !it->second.group) return;
+    for (mgcfd_solver *r : it->second.group->ranks) {
+        if (r == s) continue;
+        r->use_device();
+        HIP_CHECK(hipStreamSynchronize(r->stream));
+        for (DeviceLevel &lv : r->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+    }
+    mgcfd_solver *r0 = it->second.group->ranks[0];
+    if (r0 != s) { r0->use_device(); r0->drop_graphs(); }
+    s->use_device();
+}
+
+// The ranks of a group sweep ONE flow: their far fields must be the same 17 doubles, bit for bit (mgcfd_group_set_free_stream
+// sets all of them; a rank set on its own is the caller's to bring back in line).
+static void group_require_same_free_stream(const mgcfd_group *g)
+{
+    for (size_t r = 1; r < g->ranks.size(); r++)
+        if (std::memcmp(g->ranks[r]->ff17, g->ranks[0]->ff17, sizeof(double) * 17) != 0)
+            throw std::invalid_argument("the free stream of rank " + std::to_string(r) + " differs from rank 0's (Mach " + std::to_string(g->ranks[r]->fs_mach) +
+                                        ", alpha " + std::to_string(g->ranks[r]->fs_alpha_deg) + " against Mach " + std::to_string(g->ranks[0]->fs_mach) + ", alpha " +
+                                        std::to_string(g->ranks[0]->fs_alpha_deg) + "): mgcfd_group_set_free_stream sets every rank");
 }
 
 static void build_halo(mgcfd_solver *s, int level, int n_peers, const int *peers, const int64_t *send_counts, const int64_t *const *send_ids,
@@ -3282,6 +3397,26 @@ void mgcfd_group_destroy(mgcfd_group *g)
     delete g;
 }
 
+int mgcfd_group_set_free_stream(mgcfd_group *g, double mach, double alpha_deg, int reinitialise)
+{
+    REQUIRE(g);
+    double ff17[17];
+    const int rc = mgcfd_free_stream_constants(mach, alpha_deg, ff17);      // (a bad argument changes no rank)
+    if (rc != MGCFD_OK) return rc;
+    return guarded([&] {
+        for (mgcfd_solver *s : g->ranks) require_no_sweep_under_way(s);     // (... nor does a sweep under way on any of them)
+        // one pass that leaves every rank idle and without graphs (rank 0 keeps the group's sweep graph), then one that sets them
+        for (mgcfd_solver *s : g->ranks) {
+            s->use_device();
+            s->fold_events();
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            for (DeviceLevel &lv : s->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+            s->drop_graphs();
+        }
+        for (mgcfd_solver *s : g->ranks) apply_free_stream(s, ff17, mach, alpha_deg, reinitialise);
+    });
+}
+
 int mgcfd_group_exchange(mgcfd_group *g, int level)
 {
     REQUIRE(g);
@@ -3313,6 +3448,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
     REQUIRE(g);
     return guarded([&] {
         if (rms_out && sweeps > mgcfd_solver::kRmsRing) throw std::invalid_argument("at most 4096 sweeps per call with the RMS of each");
+        group_require_same_free_stream(g);
         mgcfd_solver *s0 = g->ranks[0];
         for (mgcfd_solver *s : g->ranks) {
             s->use_device();
@@ -3841,6 +3977,7 @@ static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const 
     const bool with_rms = rms_out || loads_out;                 // (a cycle's loads go into the row of its RMS)
     const int rc = guarded([&] {
         if (cycles > mgcfd_solver::kRmsRing) throw std::invalid_argument("at most 4096 cycles per call");
+        group_require_same_free_stream(g);
         const int n = static_cast<int>(g->ranks[0]->L.size());
         for (mgcfd_solver *s : g->ranks) if (static_cast<int>(s->L.size()) != n) throw std::invalid_argument("the ranks of a group hold the same number of levels");
         for (int l = 0; l < n; l++) group_prepare_level(g, l);
@@ -3914,6 +4051,7 @@ int mgcfd_group_surface_loads(mgcfd_group *g, int level, const double ref_point[
 {
     REQUIRE(g); REQUIRE(out6);
     return guarded([&] {
+        group_require_same_free_stream(g);
         group_loads_prepare(g, level, ref_point);
         mgcfd_solver *s0 = g->ranks[0];
         double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};

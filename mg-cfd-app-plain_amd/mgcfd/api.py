@@ -156,6 +156,10 @@ _SIGNATURES = [
     ("mgcfd_group_cycles_loads", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     ("mgcfd_rank_surface_loads", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_rank_cycles_loads", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_free_stream_constants", C.c_int, [C.c_double, C.c_double, _vp]),
+    ("mgcfd_set_free_stream", C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
+    ("mgcfd_get_free_stream", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("mgcfd_group_set_free_stream", C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -307,6 +311,15 @@ def load_coefficients(ff17, loads, ref_area: float = 1.0, ref_length: float = 1.
         _check(lib, lib.mgcfd_load_coefficients(_ptr(ff), _ptr(row), float(ref_area), float(ref_length), _ptr(res)))
         out[k] = res
     return out.reshape(rows.shape)
+
+
+def free_stream_constants(mach: float, alpha_deg: float) -> np.ndarray:
+    """Host only (mgcfd_free_stream_constants): the 17 far-field doubles (Solver.far_field()) of a free stream at Mach number
+    ``mach`` and angle of attack ``alpha_deg`` degrees.  (1.2, 0.0) is the reference's compile-time free stream."""
+    lib = load_library()
+    out = np.zeros(17)
+    _check(lib, lib.mgcfd_free_stream_constants(float(mach), float(alpha_deg), _ptr(out)))
+    return out
 
 
 class Solver:
@@ -507,6 +520,34 @@ class Solver:
     def load_coefficients(self, loads, ref_area: float = 1.0, ref_length: float = 1.0) -> np.ndarray:
         """CD CL CS CMx CMy CMz of one loads vector, or of every row of a ``[n, 6]`` history, against this solver's far field."""
         return load_coefficients(self.far_field(), loads, ref_area, ref_length)
+
+    # ---- free stream ----
+    def set_free_stream(self, mach: float, alpha_deg: float, reinitialise: bool = True):
+        """Replace the far field (mgcfd_set_free_stream).  ``reinitialise=True``: every level starts again from the new far
+        field; ``False``: the state stays (warm start).  Captured graphs are dropped and captured again by the next run."""
+        self._c(self.lib.mgcfd_set_free_stream(self.handle, float(mach), float(alpha_deg), 1 if reinitialise else 0))
+
+    def free_stream(self):
+        """``(mach, alpha_deg)`` of the far field in use."""
+        m, a = C.c_double(), C.c_double()
+        self._c(self.lib.mgcfd_get_free_stream(self.handle, C.byref(m), C.byref(a)))
+        return m.value, a.value
+
+    def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
+              ref_area: float = 1.0, ref_length: float = 1.0) -> List[dict]:
+        """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
+        The first angle starts from its own far field; a later one continues from the flow of the angle before it
+        (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
+        dict: ``alpha``, ``mach``, ``rms`` [cycles], ``loads`` [cycles, 6] and ``coefficients`` (CD CL CS CMx CMy CMz of the
+        last cycle against that angle's far field)."""
+        m = self.free_stream()[0] if mach is None else float(mach)
+        out = []
+        for k, a in enumerate(alphas):
+            self.set_free_stream(m, float(a), reinitialise=(k == 0 or not warm_start))
+            rms, loads = self.run_cycles(cycles, loads=True, ref_point=ref_point)
+            coef = self.load_coefficients(loads[-1], ref_area, ref_length) if cycles > 0 else np.full(6, np.nan)
+            out.append({"alpha": float(a), "mach": m, "rms": rms, "loads": loads, "coefficients": coef})
+        return out
 
     # ---- state ----
     def get(self, l: int, name: str) -> np.ndarray:
@@ -735,6 +776,11 @@ class Group:
         _check(self.lib, self.lib.mgcfd_group_sweeps_rms(self.handle, l, n, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out[:n]
     def synchronize(self): _check(self.lib, self.lib.mgcfd_group_synchronize(self.handle))
+
+    def set_free_stream(self, mach: float, alpha_deg: float, reinitialise: bool = True):
+        """Solver.set_free_stream on every rank (mgcfd_group_set_free_stream).  The group's sweeps, cycles and loads raise
+        MgcfdError (MGCFD_ERR_ARG) while the ranks' far fields differ."""
+        _check(self.lib, self.lib.mgcfd_group_set_free_stream(self.handle, float(mach), float(alpha_deg), 1 if reinitialise else 0))
 
     def cycles(self, n: int = 1, rms: bool = True, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
         """n V-cycles of a partitioned hierarchy (mgcfd_group_cycles); the level-0 RMS of each cycle.  With ``loads=True``

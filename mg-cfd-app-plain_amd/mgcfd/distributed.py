@@ -451,3 +451,25 @@ class PartitionedCycle:
             self.exchange(l, "variables")
             if l > 0:
                 self.sweep(l)
+
+
+def set_free_stream_all(solver, mach=None, alpha_deg=None, reinitialise=True, dist=None):
+    """Set the free stream of every rank's solver from RANK 0's values (mgcfd_set_free_stream): rank 0's ``mach`` and
+    ``alpha_deg`` are broadcast — as fp64, so every rank computes the same 17 far-field doubles — and every rank, rank 0
+    included, applies what it received; the other ranks' own arguments are ignored and may be None.  Between ranks in
+    different processes the library cannot compare far fields, so this is how a job keeps them equal.  Collective; returns
+    ``(mach, alpha_deg)`` as applied.  Without an initialised ``dist`` it only sets ``solver``.
+    Backend "nccl" (RCCL) broadcasts a tensor on the process's current device, any other backend a host tensor."""
+    active = dist is not None and dist.is_initialized()
+    if active:
+        import torch
+        rank0 = dist.get_rank() == 0
+        # (backend "nccl" — RCCL — takes device tensors only, on the process's current device; gloo takes this host tensor)
+        on_device = "nccl" in str(dist.get_backend()) and "gloo" not in str(dist.get_backend())
+        t = torch.tensor([float(mach) if rank0 else 0.0, float(alpha_deg) if rank0 else 0.0, 1.0 if reinitialise else 0.0],
+                         dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()) if on_device else "cpu")
+        dist.broadcast(t, src=0)
+        mach, alpha_deg, reinitialise = (float(v) for v in t.tolist())      # (.tolist() waits for a device tensor's broadcast)
+        reinitialise = reinitialise != 0.0
+    solver.set_free_stream(float(mach), float(alpha_deg), reinitialise)
+    return float(mach), float(alpha_deg)
