@@ -264,6 +264,27 @@ int mgcfd_get_far_field(const mgcfd_solver *s, double *out17);
 int mgcfd_free_stream_constants(double mach, double alpha_deg, double out17[17]);
 int mgcfd_set_free_stream(mgcfd_solver *s, double mach, double alpha_deg, int reinitialise);
 int mgcfd_get_free_stream(const mgcfd_solver *s, double *mach, double *alpha_deg);
+/* The time step at run time: which step-factor formula every smoothing sweep starts with, and its CFL number.  The reference
+ * ties both to the mesh NAME and the literal 0.5 (src/euler3d_cpu_double.cpp:388-395, src/Kernels/cfd_loops.cpp:13-157).
+ * With derive()'s speed and c of node i (cfd_loops.h:121-148) and dt_i = cbrt(vol_i) / (speed_i + c_i) — cbrt from the host's
+ * libm, as the reference calls it — the step factors of a sweep are, associated as written and never contracted to FMA:
+ *   MGCFD_DT_REFERENCE     what the mesh name selects: GLOBAL, or LOCAL_LEGACY for mesh_name = fvcorr (the default)
+ *   MGCFD_DT_GLOBAL        sf_i = min_j(cfl * dt_j) / vol_i          compute_step_factor, cfd_loops.cpp:76-157
+ *   MGCFD_DT_LOCAL         sf_i = (cfl * dt_i) / vol_i               every node marches at its own step; no reference counterpart
+ *   MGCFD_DT_LOCAL_LEGACY  sf_i = cfl / (sqrt(vol_i) * (speed_i + c_i))   compute_step_factor_legacy, cfd_loops.cpp:13-73
+ * (MGCFD_DT_REFERENCE, 0.5) is what a solver starts with and launches what it launched before this call existed.  Under a
+ * local mode nothing is reduced: a level split over ranks needs no all-reduce of the time step (no RCCL call, no flag round,
+ * no event fan-in per sweep) and mgcfd_step_factor_local returns MGCFD_ERR_ARG.  The ghosts of a partitioned level get the
+ * factor 0 under MGCFD_DT_LOCAL (their owners compute theirs).
+ * mgcfd_set_time_step — synchronises, drops every captured graph of the solver (a captured launch holds the CFL number) and
+ * discards step-factor work done ahead under the old policy; the state stays.  MGCFD_ERR_ARG, and nothing changed, for an
+ * unknown mode, a non-finite cfl or cfl <= 0, and while a kernel-granular sweep is under way (as mgcfd_set_free_stream).
+ * Ranks: the ranks of one flow must hold the same mode and CFL number.  An in-process group checks it
+ * (mgcfd_group_set_time_step, further down); between RCCL ranks in different processes agreement is the CALLER's duty
+ * (mgcfd/distributed.py: set_time_step_all broadcasts rank 0's). */
+enum { MGCFD_DT_REFERENCE = 0, MGCFD_DT_GLOBAL = 1, MGCFD_DT_LOCAL = 2, MGCFD_DT_LOCAL_LEGACY = 3 };
+int mgcfd_set_time_step(mgcfd_solver *s, int mode, double cfl);
+int mgcfd_get_time_step(const mgcfd_solver *s, int *mode, double *cfl);
 
 /* ---------------------------------------------------------------------------------
  * Kernel-granular operations (asynchronous on the solver's stream)
@@ -271,7 +292,7 @@ int mgcfd_get_free_stream(const mgcfd_solver *s, double *mach, double *alpha_deg
 /* copy<double>(old_variables, variables)                    src/Base/common.h:100-112 */
 int mgcfd_copy_old_variables(mgcfd_solver *s, int level);
 /* compute_step_factor / compute_step_factor_legacy (chosen by mesh variant exactly as
- * euler3d_cpu_double.cpp:388-395 does)                       src/Kernels/cfd_loops.cpp:13-157 */
+ * euler3d_cpu_double.cpp:388-395 does, unless mgcfd_set_time_step chose)   src/Kernels/cfd_loops.cpp:13-157 */
 int mgcfd_compute_step_factor(mgcfd_solver *s, int level);
 /* compute_flux_edge over the level's internal edges: fluxes += …   flux_loops.cpp:78-153 */
 int mgcfd_compute_flux_edge(mgcfd_solver *s, int level);
@@ -393,7 +414,8 @@ int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double 
  * host through RCCL — see INTEGRATION.md).  compute_step_factor's global min
  * (cfd_loops.cpp:137-150) is split so an all-reduce(min) can run between the halves.
  * --------------------------------------------------------------------------------- */
-/* First half: per-node 0.5*dt and the rank-local minimum, left in a device scalar. */
+/* First half: per-node cfl*dt (cfl = 0.5 unless mgcfd_set_time_step chose) and the rank-local minimum, left in a device
+ * scalar.  MGCFD_ERR_ARG under a local time step. */
 int mgcfd_step_factor_local(mgcfd_solver *s, int level);
 /* Device address of that fp64 scalar (for an in-place RCCL all-reduce MIN). */
 int mgcfd_step_factor_min_devptr(mgcfd_solver *s, int level, void **devptr);
@@ -509,6 +531,10 @@ void mgcfd_group_destroy(mgcfd_group *g);
  * mgcfd_group_cycles[_loads], mgcfd_group_surface_loads) return MGCFD_ERR_ARG while the ranks' far fields differ in any bit;
  * the message names the first rank that differs from rank 0. */
 int mgcfd_group_set_free_stream(mgcfd_group *g, double mach, double alpha_deg, int reinitialise);
+/* mgcfd_set_time_step on every rank, in the same two passes; a bad argument or a sweep under way changes no rank.  The group
+ * calls that run sweeps, cycles or loads return MGCFD_ERR_ARG while the ranks' mode or CFL number differ; the message names the
+ * first rank that differs from rank 0. */
+int mgcfd_group_set_time_step(mgcfd_group *g, int mode, double cfl);
 int mgcfd_group_exchange(mgcfd_group *g, int level);
 int mgcfd_group_sweeps(mgcfd_group *g, int level, int sweeps);   /* asynchronous; a host thread per rank issues that rank's launches */
 /* The same with calc_rms (src/Kernels/validation.cpp:91-105) after every sweep — the reference's cycle loop prints it per

@@ -92,7 +92,9 @@ struct FusedStep {
     // look-ahead for the NEXT sweep on this level, from the state this launch produces:
     double *next_partial_min = nullptr;       // first half of compute_step_factor: per-tile minima of 0.5*cbrt(vol)/(|v|+c)
     const double *cbrt_vol = nullptr;
-    double *next_legacy_sf = nullptr;         // mesh_name = fvcorr: next sweep's step factors 0.5/(sqrt(vol)*(|v|+c)) (cfd_loops.cpp:37-61) go here
+    double *next_legacy_sf = nullptr;         // a local time step: next sweep's step factors go here — cfl/(sqrt(vol)*(|v|+c)) (cfd_loops.cpp:37-61) ...
+    int next_nodal = 0;                       // ... or, when set, (cfl*cbrt(vol)/(|v|+c))/vol (MGCFD_DT_LOCAL)
+    double cfl = 0.5;                         // the CFL number of whichever look-ahead runs (the reference's literal 0.5)
     // a launch over PART of the level's tiles (a partitioned level: the tiles next to ghost nodes first, so that their
     // results can travel while the others are computed): tile_list[k] = tile of workgroup k; nullptr = all tiles
     const int32_t *tile_list = nullptr;

@@ -287,13 +287,14 @@ k_init_variables(int64_t stride, FarField ff, double *__restrict__ q)
 }
 
 // ------------------------------------------------------------------------------------------
-// compute_step_factor, first half (cfd_loops.cpp:98-125): sf = 0.5 * cbrt(vol) / (|v| + c) and
-// the minimum over the level.  cbrt(vol) is static and precomputed on the host with the same
-// libm the reference would call.
+// compute_step_factor, first half (cfd_loops.cpp:98-125): sf = cfl * (cbrt(vol) / (|v| + c)) and
+// the minimum over the level (cfl: the reference's literal 0.5, an argument here — the same IEEE
+// multiplication).  cbrt(vol) is static and precomputed on the host with the same libm the
+// reference would call.
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock)
 k_step_factor_local(int64_t nel, int64_t stride, const double *__restrict__ q, const double *__restrict__ cbrt_vol,
-                    double *__restrict__ step_factors, double *__restrict__ partial_min,
+                    double cfl, double *__restrict__ step_factors, double *__restrict__ partial_min,
                     double *__restrict__ old_variables /* nullptr, or: fused copy<double>(old, variables) */)
 {
     __shared__ double s_min[kBlock / 64];
@@ -307,7 +308,7 @@ k_step_factor_local(int64_t nel, int64_t stride, const double *__restrict__ q, c
         }
         const Derived d = derive(rho, mx, my, mz, en);
         const double dt = cbrt_vol[i] / (d.speed + d.c);
-        sf = 0.5 * dt;
+        sf = cfl * dt;
         step_factors[i] = sf;
     }
     // One partial minimum per workgroup; the consumer reduces them (min is order independent,
@@ -351,11 +352,20 @@ __device__ __forceinline__ void block_min_to(double v, double *__restrict__ out)
 }
 
 // first half of compute_step_factor for one node, as k_step_factor_local computes it
-__device__ __forceinline__ double local_step_factor(double rho, double mx, double my, double mz, double en, double cbrt_vol)
+__device__ __forceinline__ double local_step_factor(double rho, double mx, double my, double mz, double en, double cbrt_vol, double cfl)
 {
     const Derived d = derive(rho, mx, my, mz, en);
     const double dt = cbrt_vol / (d.speed + d.c);
-    return 0.5 * dt;
+    return cfl * dt;
+}
+
+// MGCFD_DT_LOCAL: a node's own step, sf = (cfl * dt) / vol with the dt of compute_step_factor (cfd_loops.cpp:116).
+// A ghost of a partitioned level (cbrt_vol = +inf: its owner computes its step) gets 0: it holds no rows, so its sum of
+// fluxes is zero and time_step leaves it where it is, which inf * 0 would not.
+__device__ __forceinline__ double nodal_step_factor(const Derived &d, double cbrt_vol, double vol, double cfl)
+{
+    const double dt = cbrt_vol / (d.speed + d.c);
+    return cbrt_vol < __longlong_as_double(0x7FF0000000000000LL) ? (cfl * dt) / vol : 0.0;
 }
 
 // partial minima -> one scalar (only needed where the scalar itself is the interface: the
@@ -377,10 +387,11 @@ k_step_factor_apply(int64_t nel, const double *__restrict__ min_dt_scalar,
     step_factors[i] = min_dt_scalar[0] / volumes[i];
 }
 
-// compute_step_factor_legacy (cfd_loops.cpp:37-61), mesh_name = fvcorr only
+// compute_step_factor_legacy (cfd_loops.cpp:37-61): what mesh_name = fvcorr runs, MGCFD_DT_LOCAL_LEGACY on any mesh
+// (cfl: the reference's literal 0.5)
 __global__ void __launch_bounds__(kBlock)
 k_step_factor_legacy(int64_t nel, int64_t stride, const double *__restrict__ q, const double *__restrict__ volumes,
-                     double *__restrict__ step_factors, double *__restrict__ old_variables /* nullptr or fused copy */)
+                     double cfl, double *__restrict__ step_factors, double *__restrict__ old_variables /* nullptr or fused copy */)
 {
     const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
     if (i >= nel) return;
@@ -390,7 +401,24 @@ k_step_factor_legacy(int64_t nel, int64_t stride, const double *__restrict__ q, 
         old_variables[3 * stride + i] = mz; old_variables[4 * stride + i] = en;
     }
     const Derived d = derive(rho, mx, my, mz, en);
-    step_factors[i] = 0.5 / (sqrt(volumes[i]) * (d.speed + d.c));
+    step_factors[i] = cfl / (sqrt(volumes[i]) * (d.speed + d.c));
+}
+
+// MGCFD_DT_LOCAL: step_factors[i] = (cfl * cbrt(vol_i) / (|v_i| + c_i)) / vol_i, no minimum over the level
+__global__ void __launch_bounds__(kBlock)
+k_step_factor_nodal(int64_t nel, int64_t stride, const double *__restrict__ q, const double *__restrict__ cbrt_vol,
+                    const double *__restrict__ volumes, double cfl, double *__restrict__ step_factors,
+                    double *__restrict__ old_variables /* nullptr or fused copy */)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double rho = q[i], mx = q[stride + i], my = q[2 * stride + i], mz = q[3 * stride + i], en = q[4 * stride + i];
+    if (old_variables) {
+        old_variables[i] = rho; old_variables[stride + i] = mx; old_variables[2 * stride + i] = my;
+        old_variables[3 * stride + i] = mz; old_variables[4 * stride + i] = en;
+    }
+    const Derived d = derive(rho, mx, my, mz, en);
+    step_factors[i] = nodal_step_factor(d, cbrt_vol[i], volumes[i], cfl);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -576,10 +604,11 @@ __device__ __forceinline__ void finish_node(int64_t i, int64_t nel, int64_t stri
         if (fs.next_partial_min) {
             const Derived d = derive(rho, mx, my, mz, en);
             const double dt = fs.cbrt_vol[i] / (d.speed + d.c);          // k_step_factor_local
-            sf_next = 0.5 * dt;
+            sf_next = fs.cfl * dt;
         } else if (fs.next_legacy_sf) {
             const Derived d = derive(rho, mx, my, mz, en);
-            fs.next_legacy_sf[i] = 0.5 / (sqrt(fs.volumes[i]) * (d.speed + d.c));   // k_step_factor_legacy
+            if (fs.next_nodal) fs.next_legacy_sf[i] = nodal_step_factor(d, fs.cbrt_vol[i], fs.volumes[i], fs.cfl);   // k_step_factor_nodal
+            else fs.next_legacy_sf[i] = fs.cfl / (sqrt(fs.volumes[i]) * (d.speed + d.c));   // k_step_factor_legacy
         }
     }
     if (fs.next_partial_min || fs.sumsq_partial) {  // uniform: every thread of the workgroup takes part
@@ -1078,10 +1107,11 @@ flux_tile_body(Lds &lds, const unsigned block,
         if (ROLE == 3) {
             const Derived d = derive(rho, mx, my, mz, en);
             const double dt = fs.cbrt_vol[i] / (d.speed + d.c);          // k_step_factor_local
-            sf_next = 0.5 * dt;
+            sf_next = fs.cfl * dt;
         } else if (ROLE == 4) {
             const Derived d = derive(rho, mx, my, mz, en);
-            fs.next_legacy_sf[i] = 0.5 / (sqrt(fs.volumes[i]) * (d.speed + d.c));   // k_step_factor_legacy
+            if (fs.next_nodal) fs.next_legacy_sf[i] = nodal_step_factor(d, fs.cbrt_vol[i], fs.volumes[i], fs.cfl);   // k_step_factor_nodal
+            else fs.next_legacy_sf[i] = fs.cfl / (sqrt(fs.volumes[i]) * (d.speed + d.c));   // k_step_factor_legacy
         }
         if (PUSH && block < unsigned(push.n_boundary)) {
             // this node into the ghost slots of the neighbours that hold it
@@ -1907,7 +1937,7 @@ k_flux_free(// (the first 16 dwords are preloaded into SGPRs: what the prologue'
         if (ROLE == 3) {                            // look-ahead: the next sweep's compute_step_factor starts from the state just produced
             const Derived d = derive(rho, mx, my, mz, en);
             const double dt = fs.cbrt_vol[i] / (d.speed + d.c);          // k_step_factor_local
-            sf_next = 0.5 * dt;
+            sf_next = fs.cfl * dt;
         }
     }
     if (ROLE == 3 || (ROLE == 2 && fs.sumsq_partial)) {                // uniform: every thread of the workgroup takes part
@@ -2607,7 +2637,7 @@ k_loads_reduce(const double *__restrict__ table, int64_t row, LoadsTask task)
 __global__ void __launch_bounds__(kBlock)
 k_restrict(int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, const int32_t *__restrict__ child_ptr,
            const int32_t *__restrict__ child, const int4 *__restrict__ child4, const double *__restrict__ fine_q,
-           double *__restrict__ coarse_q, const double *__restrict__ cbrt_vol,
+           double *__restrict__ coarse_q, const double *__restrict__ cbrt_vol, double cfl,
            double *__restrict__ partial_min /* nullptr, or: look ahead, see below */,
            SumTask rms /* .partial != nullptr: the last workgroup also adds up the fine level's per-tile sums of squares
                           (calc_rms of the sweep just finished) — the launch that would do only that is saved */)
@@ -2652,7 +2682,7 @@ k_restrict(int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, const
         }
         // The sweep that follows on the coarse level starts with compute_step_factor on exactly these
         // values: leave its first half (the per-workgroup minima) behind.
-        if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[c]);
+        if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[c], cfl);
     }
     if (partial_min) block_min_to(sf, partial_min);
     // (the workgroup dispatched FIRST adds them up: its extra microsecond ends long before the launch's last workgroups do)
@@ -2670,7 +2700,7 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
           const int32_t *__restrict__ rows_int, const double *__restrict__ pro_w, const int32_t *__restrict__ pro_p,
           const int32_t *__restrict__ pro_parent, const double *__restrict__ pro_wsum,
           const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals,
-          double *__restrict__ fine_q, const double *__restrict__ cbrt_vol,
+          double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl,
           double *__restrict__ partial_min /* nullptr, or: look ahead as in k_restrict */)
 {
     const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
@@ -2727,7 +2757,7 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
         const double n3 = q3 + (f3 - r3 / ws);
         const double n4 = q4 + (f4 - r4 / ws);
         store_conserved(fine_q, stride, i, n0, n1, n2, n3, n4);
-        if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[i]);
+        if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[i], cfl);
     }
     if (partial_min) block_min_to(sf, partial_min);
 }
@@ -2745,7 +2775,7 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
                const int32_t *__restrict__ pro_tile_n, const int32_t *__restrict__ pro_tile_ids,
                const int32_t *__restrict__ pro_parent, const double *__restrict__ pro_wsum,
                const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals,
-               double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double *__restrict__ partial_min)
+               double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl, double *__restrict__ partial_min)
 {
     __shared__ double cr[kProCap * 5];
     const unsigned t = xcd_contiguous_block(blockIdx.x, gridDim.x);   // neighbouring tiles (they share coarse parents) on one XCD's L2
@@ -2838,7 +2868,7 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
         const double n3 = q3 + (f3 - r3 / ws);
         const double n4 = q4 + (f4 - r4 / ws);
         store_conserved(fine_q, stride, i, n0, n1, n2, n3, n4);
-        if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[i]);
+        if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[i], cfl);
     }
     if (partial_min) block_min_to(sf, partial_min);
 }
@@ -2853,8 +2883,8 @@ void launch_init_variables(hipStream_t st, int64_t stride, const FarField &ff, d
 
 // partial_min must hold grid_for(nel) doubles
 void launch_step_factor_local(hipStream_t st, int64_t nel, int64_t stride, const double *q, const double *cbrt_vol,
-                              double *sf, double *partial_min, double *old_variables)
-{ hipLaunchKernelGGL(k_step_factor_local, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, q, cbrt_vol, sf, partial_min, old_variables); }
+                              double cfl, double *sf, double *partial_min, double *old_variables)
+{ hipLaunchKernelGGL(k_step_factor_local, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, q, cbrt_vol, cfl, sf, partial_min, old_variables); }
 
 void launch_min_reduce(hipStream_t st, int64_t nel, const double *partial_min, double *out)
 { hipLaunchKernelGGL(k_min_reduce, dim3(1), dim3(kBlock), 0, st, partial_min, int(grid_for(nel)), out); }
@@ -2863,9 +2893,13 @@ void launch_step_factor_apply(hipStream_t st, int64_t nel, const double *min_dt_
                               const double *volumes, double *sf)
 { hipLaunchKernelGGL(k_step_factor_apply, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, min_dt_scalar, volumes, sf); }
 
-void launch_step_factor_legacy(hipStream_t st, int64_t nel, int64_t stride, const double *q, const double *volumes, double *sf,
-                               double *old_variables)
-{ hipLaunchKernelGGL(k_step_factor_legacy, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, q, volumes, sf, old_variables); }
+void launch_step_factor_legacy(hipStream_t st, int64_t nel, int64_t stride, const double *q, const double *volumes, double cfl,
+                               double *sf, double *old_variables)
+{ hipLaunchKernelGGL(k_step_factor_legacy, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, q, volumes, cfl, sf, old_variables); }
+
+void launch_step_factor_nodal(hipStream_t st, int64_t nel, int64_t stride, const double *q, const double *cbrt_vol,
+                              const double *volumes, double cfl, double *sf, double *old_variables)
+{ hipLaunchKernelGGL(k_step_factor_nodal, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, q, cbrt_vol, volumes, cfl, sf, old_variables); }
 
 // ---- the flux launch: which kernel, which instantiation ------------------------------------------------------------------
 // A run-time value as a compile-time constant: f(std::integral_constant<int, V>) for the V of the list that equals v.
@@ -3174,26 +3208,26 @@ void launch_loads_reduce(hipStream_t st, const double *table, int64_t row, const
 
 void launch_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine,
                      const int32_t *child_ptr, const int32_t *child, const int32_t *child4, const double *fine_q,
-                     double *coarse_q, const double *cbrt_vol, double *partial_min, const SumTask &rms)
+                     double *coarse_q, const double *cbrt_vol, double cfl, double *partial_min, const SumTask &rms)
 {
     hipLaunchKernelGGL(k_restrict, dim3(grid_for(nel_coarse)), dim3(kBlock), 0, st, nel_coarse, stride_coarse,
                        stride_fine, child_ptr, child, reinterpret_cast<const int4 *>(child4), fine_q, coarse_q, cbrt_vol,
-                       partial_min, rms);
+                       cfl, partial_min, rms);
 }
 
 void launch_prolong(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_residuals,
-                    const double *fine_residuals, double *fine_q, const double *cbrt_vol, double *partial_min)
+                    const double *fine_residuals, double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
 {
     // grid_for(nel) workgroups: the same partition k_step_factor_local's partial minima use
     if (p.pro_tiled) {
         hipLaunchKernelGGL(k_prolong_tile, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
                            p.slice_row0, p.rows_int, p.pro_w, p.pro_s16, p.pro_own16, p.pro_tile_n, p.pro_tile_ids,
-                           p.pro_parent, p.pro_wsum, coarse_residuals, fine_residuals, fine_q, cbrt_vol, partial_min);
+                           p.pro_parent, p.pro_wsum, coarse_residuals, fine_residuals, fine_q, cbrt_vol, cfl, partial_min);
         return;
     }
     hipLaunchKernelGGL(k_prolong, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
                        p.slice_row0, p.rows_int, p.pro_w, p.pro_p, p.pro_parent, p.pro_wsum, coarse_residuals, fine_residuals, fine_q,
-                       cbrt_vol, partial_min);
+                       cbrt_vol, cfl, partial_min);
 }
 
 } // namespace MGCFD_KERNEL_NS

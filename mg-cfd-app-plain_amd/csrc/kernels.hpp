@@ -7,12 +7,14 @@
     namespace mgcfd { namespace NS {                                                                                 \
     void launch_init_variables(hipStream_t, int64_t stride, const FarField &, double *q);                            \
     void launch_step_factor_local(hipStream_t, int64_t nel, int64_t stride, const double *q, const double *cbrt_vol, \
-                                  double *sf, double *partial_min, double *old_variables);                           \
+                                  double cfl, double *sf, double *partial_min, double *old_variables);               \
     void launch_min_reduce(hipStream_t, int64_t nel, const double *partial_min, double *out);                        \
     void launch_step_factor_apply(hipStream_t, int64_t nel, const double *min_dt_scalar,                             \
                                   const double *volumes, double *sf);                                                \
     void launch_step_factor_legacy(hipStream_t, int64_t nel, int64_t stride, const double *q, const double *volumes, \
-                                   double *sf, double *old_variables);                                               \
+                                   double cfl, double *sf, double *old_variables);                                   \
+    void launch_step_factor_nodal(hipStream_t, int64_t nel, int64_t stride, const double *q, const double *cbrt_vol, \
+                                  const double *volumes, double cfl, double *sf, double *old_variables);             \
     void launch_flux(hipStream_t, const DevicePlan &, const double *q, const FarField &, double *fluxes,             \
                      int classes, int accumulate, int variant, const FusedStep *fused, const StagePush *push);       \
     void launch_indirect_rw(hipStream_t, const DevicePlan &, const double *q, double *fluxes, int variant);                       \
@@ -48,7 +50,7 @@
     void launch_restrict(hipStream_t, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine,                \
                          const int32_t *child_ptr, const int32_t *child, const int32_t *child4, const double *fine_q, \
                          double *coarse_q,                                                                        \
-                         const double *cbrt_vol, double *partial_min, const SumTask &rms);                          \
+                         const double *cbrt_vol, double cfl, double *partial_min, const SumTask &rms);              \
     void launch_surface_loads(hipStream_t, int64_t stride, const double *q, const LoadsTask &task);                  \
     void launch_loads_terms(hipStream_t, int64_t stride, const double *q, const LoadsTerms &task);                   \
     void launch_loads_scatter(hipStream_t, int64_t n, const double *src, int64_t src_row, const int32_t *slot,       \
@@ -56,7 +58,7 @@
     void launch_loads_reduce(hipStream_t, const double *table, int64_t row, const LoadsTask &task);                  \
     void launch_prolong(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_residuals,      \
                         const double *fine_residuals, double *fine_q, const double *cbrt_vol,                       \
-                        double *partial_min);                                                                        \
+                        double cfl, double *partial_min);                                                            \
     } }
 
 MGCFD_DECLARE_LAUNCHERS(exact)
@@ -71,5 +73,6 @@ struct Launchers {
     decltype(exact::launch_indirect_rw) *indirect_rw;                decltype(exact::launch_time_step) *time_step;
     decltype(exact::launch_residual) *residual;                      decltype(exact::launch_sumsq) *sumsq;
     decltype(exact::launch_restrict) *restrict_;                     decltype(exact::launch_prolong) *prolong;
+    decltype(exact::launch_step_factor_nodal) *step_factor_nodal;
 };
 }

@@ -53,6 +53,11 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool polar = false;               // --polar A0:A1:N: N angles from A0 to A1 inclusive, -g cycles each, polar.csv
     double polar_a0 = 0.0, polar_a1 = 0.0;
     int polar_n = 0;
+    // the time step (the reference ties it to the mesh name and the literal 0.5, src/euler3d_cpu_double.cpp:388-395)
+    bool time_step_given = false;     // --time-step / --cfl / time_step / cfl: mgcfd_set_time_step before the first cycle
+    int time_step_mode = MGCFD_DT_REFERENCE;
+    double cfl = 0.5;
+    bool time_step_bad = false;       // a config file's value was refused: the run ends right after parsing
     // the k-th angle of the run (one angle without --polar)
     int num_angles() const { return polar ? polar_n : 1; }
     double angle(int k) const { return !polar ? angle_of_attack : (polar_n == 1 ? polar_a0 : polar_a0 + (polar_a1 - polar_a0) * double(k) / double(polar_n - 1)); }
@@ -65,6 +70,26 @@ bool parse_number(const char *text, double *out)
     char *end = nullptr;
     const double v = std::strtod(text, &end);
     if (end == text || *end != '\0' || !std::isfinite(v)) return false;
+    *out = v;
+    return true;
+}
+
+// reference | global | local | local-legacy (or local_legacy)
+bool parse_time_step_mode(const char *text, int *out)
+{
+    const std::string t(text ? text : "");
+    if (t == "reference") *out = MGCFD_DT_REFERENCE;
+    else if (t == "global") *out = MGCFD_DT_GLOBAL;
+    else if (t == "local") *out = MGCFD_DT_LOCAL;
+    else if (t == "local-legacy" || t == "local_legacy") *out = MGCFD_DT_LOCAL_LEGACY;
+    else return false;
+    return true;
+}
+// a finite CFL number above zero
+bool parse_cfl(const char *text, double *out)
+{
+    double v = 0.0;
+    if (!parse_number(text, &v) || !(v > 0.0)) return false;
     *out = v;
     return true;
 }
@@ -130,6 +155,14 @@ void set_param(Config &c, const std::string &key, const std::string &value)
     else if (key == "output_volumes") { if (value == "Y") c.output_volumes = true; }
     else if (key == "ff_mach") { if (parse_number(value.c_str(), &c.ff_mach)) c.free_stream_given = true; else std::printf("WARNING: ff_mach = '%s' is not a number.\n", value.c_str()); }
     else if (key == "angle_of_attack") { if (parse_number(value.c_str(), &c.angle_of_attack)) c.free_stream_given = true; else std::printf("WARNING: angle_of_attack = '%s' is not a number.\n", value.c_str()); }
+    else if (key == "time_step") {
+        if (parse_time_step_mode(value.c_str(), &c.time_step_mode)) c.time_step_given = true;
+        else { std::fprintf(stderr, "ERROR: time_step = '%s': expected reference, global, local or local-legacy\n", value.c_str()); c.time_step_bad = true; }
+    }
+    else if (key == "cfl") {
+        if (parse_cfl(value.c_str(), &c.cfl)) c.time_step_given = true;
+        else { std::fprintf(stderr, "ERROR: cfl = '%s': expected a finite number above zero\n", value.c_str()); c.time_step_bad = true; }
+    }
     else std::printf("WARNING: Unknown key '%s' encountered during parsing of config file.\n", key.c_str());
 }
 
@@ -203,7 +236,11 @@ void print_help()
         "                                   far field, every later one from the flow of the angle before it.  Writes polar.*\n"
         "                                   (CSV: alpha,mach,rms_last, the loads and coefficients of each angle's last cycle);\n"
         "                                   the dumps and surface_loads.* are the last angle's.  One GPU, or --gpus N with\n"
-        "                                   --gpus-partition\n");
+        "                                   --gpus-partition\n"
+        "  --time-step=MODE                 reference (default: what the mesh name selects), global, local or local-legacy\n"
+        "                                   (config key time_step); with --gpus N, --polar and --output-loads alike\n"
+        "  --cfl=X                          CFL number of the time step, finite and above zero (default 0.5, the reference's;\n"
+        "                                   config key cfl)\n");
 }
 
 bool parse_arguments(int argc, char **argv, Config &c)
@@ -238,6 +275,8 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"mach", required_argument, nullptr, 1015},
         {"alpha", required_argument, nullptr, 1016},
         {"polar", required_argument, nullptr, 1017},
+        {"time-step", required_argument, nullptr, 1018},
+        {"cfl", required_argument, nullptr, 1019},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -284,10 +323,24 @@ bool parse_arguments(int argc, char **argv, Config &c)
                     return false;
                 }
                 break;
+            case 1018:
+                if (!parse_time_step_mode(optarg, &c.time_step_mode)) {
+                    std::fprintf(stderr, "ERROR: --time-step=%s: expected reference, global, local or local-legacy\n", optarg);
+                    return false;
+                }
+                c.time_step_given = true;
+                break;
+            case 1019:
+                if (!parse_cfl(optarg, &c.cfl)) {
+                    std::fprintf(stderr, "ERROR: --cfl=%s: expected a finite number above zero\n", optarg);
+                    return false;
+                }
+                c.time_step_given = true;
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
-    return true;
+    return !c.time_step_bad;
 }
 
 // src/Base/io_enhanced.cpp:26-74
@@ -526,6 +579,7 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
         std::vector<PolarRow> polar_rows;
+        if (conf.time_step_given && run.set_time_step(conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
         const int rc = run_all_cycles(conf, rms, loads, polar_rows,
             [&](double mach, double alpha, int reinitialise) { return run.set_free_stream(mach, alpha, reinitialise); },
             [&](double *rms_out, double *loads_out) {
@@ -644,6 +698,7 @@ int main(int argc, char **argv)
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
     std::vector<PolarRow> polar_rows;
+    if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
         [&](double *rms_out, double *loads_out) {

@@ -441,6 +441,16 @@ int Run::set_free_stream(double mach, double alpha_deg, int reinitialise)
     return MGCFD_OK;
 }
 
+int Run::set_time_step(int mode, double cfl)
+{
+    if (p->group) return mgcfd_group_set_time_step(p->group, mode, cfl);
+    for (mgcfd_solver *s : p->solvers) {
+        const int rc = mgcfd_set_time_step(s, mode, cfl);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
 int Run::run_cycles(int cycles, double *rms_out)
 {
     const int n = p->levels, w = ranks();

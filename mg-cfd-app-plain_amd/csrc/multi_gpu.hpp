@@ -30,6 +30,8 @@ public:
     void far_field(double ff17[17]) const;
     // mgcfd_set_free_stream on every rank (the group's call where the ranks form one); MGCFD_OK or MGCFD_ERR_ARG
     int set_free_stream(double mach, double alpha_deg, int reinitialise);
+    // mgcfd_set_time_step on every rank, likewise
+    int set_time_step(int mode, double cfl);
     void get_level0(int which, int ncols, double *out) const;   // a level-0 array of the WHOLE mesh, original numbering
     int check_invalid(int level, int64_t *bad_cell) const;      // check_for_invalid_variables on `level` of the whole mesh (original cell id)
     void loop_iters(int level, int cycles, int64_t out[MGCFD_NUM_LOOPS]) const;

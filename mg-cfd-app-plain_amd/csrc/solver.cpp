@@ -195,8 +195,8 @@ struct DeviceLevel {
     int64_t row_bytes = 0;               // bytes of the incidence rows (ids + weights)
     bool min_ahead = false;              // the launch that produced the CURRENT variables looked ahead: partial_min holds the
                                          // first half of compute_step_factor for them (global time step), or sf_alt holds
-                                         // their step factors (mesh_name = fvcorr, local time step)
-    double *sf_alt = nullptr;            // [stride] fvcorr look-ahead target; swapped with step_factors when consumed
+                                         // their step factors (a local time step: mesh_name = fvcorr, or mgcfd_set_time_step)
+    double *sf_alt = nullptr;            // [stride] a local time step's look-ahead target; swapped with step_factors when consumed
     int sf_par = 0;                      // parity of those swaps (part of the graph keys)
     double *sfb[2] = {nullptr, nullptr};
     void apply_sf() { step_factors = sfb[sf_par & 1]; sf_alt = sfb[(sf_par & 1) ^ 1]; }
@@ -306,6 +306,12 @@ struct mgcfd_solver {
     bool partitioned = false;                      // made by mgcfd_create_partitioned* (loads: the group and rank forms, over all ranks)
     double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
     double fs_mach = kDefaultMach, fs_alpha_deg = kDefaultAlphaDeg;      // what ff17 was computed from (mgcfd_set_free_stream)
+    // The time step (mgcfd_set_time_step): which formula compute_step_factor runs and its CFL number.  REFERENCE is what the
+    // reference's main() picks by mesh name (src/euler3d_cpu_double.cpp:388-395); every caller asks the two predicates.
+    int dt_mode = MGCFD_DT_REFERENCE;
+    double cfl = 0.5;                                                    // the reference's literal (cfd_loops.cpp:56,118)
+    bool global_dt() const { return dt_mode == MGCFD_DT_GLOBAL || (dt_mode == MGCFD_DT_REFERENCE && mesh_variant != MGCFD_MESH_FVCORR); }   // one step for the level: a minimum to reduce
+    bool legacy_dt() const { return dt_mode == MGCFD_DT_LOCAL_LEGACY || (dt_mode == MGCFD_DT_REFERENCE && mesh_variant == MGCFD_MESH_FVCORR); }   // compute_step_factor_legacy's formula
     // ff17 -> the kernels' argument (ff) and the loads' p_inf.  Launches already captured keep the old values: drop_graphs.
     void set_far_field(const double *in17)
     {
@@ -343,7 +349,8 @@ struct mgcfd_solver {
     const Launchers &k() const                                  // the kernels of this solver's numeric flavour
     {
 #define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
-                                NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong}
+                                NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
+                                NS::launch_step_factor_nodal}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -415,7 +422,7 @@ struct mgcfd_solver {
         lv.min_ahead = false;                       // partial_min is rewritten (same values if it was ahead)
         if (fuse_copy_old) settle_residuals(lv);
         double *old = fuse_copy_old ? lv.old_variables : nullptr;
-        k().step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.step_factors, lv.partial_min, old);
+        k().step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, cfl, lv.step_factors, lv.partial_min, old);
         if (reduce_to_scalar) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
     }
     void op_step_factor_apply(int l)
@@ -447,10 +454,11 @@ struct mgcfd_solver {
         DeviceLevel &lv = level(l);
         Timed t(this, l, MGCFD_LOOP_COMPUTE_STEP);
         bool apply_pending = false;
-        if (mesh_variant == MGCFD_MESH_FVCORR) {
+        if (!global_dt()) {
             double *old = (fused && copy_old) ? lv.old_variables : nullptr;
             if (old) settle_residuals(lv);
-            k().step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, lv.step_factors, old);
+            if (legacy_dt()) k().step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, cfl, lv.step_factors, old);
+            else k().step_factor_nodal(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.volumes, cfl, lv.step_factors, old);
         } else {
             op_step_factor_local(l, fused && copy_old, !fused);
             if (fused) apply_pending = true;
@@ -580,8 +588,10 @@ struct mgcfd_solver {
         fs.step_factors = lv.step_factors;
         fs.old_variables = a.old ? a.old : lv.old_variables;
         fs.q_out = out;
-        fs.next_partial_min = (a.look_ahead && mesh_variant != MGCFD_MESH_FVCORR) ? lv.partial_min : nullptr;
-        fs.next_legacy_sf = (a.look_ahead && mesh_variant == MGCFD_MESH_FVCORR) ? lv.sf_alt : nullptr;
+        fs.next_partial_min = (a.look_ahead && global_dt()) ? lv.partial_min : nullptr;
+        fs.next_legacy_sf = (a.look_ahead && !global_dt()) ? lv.sf_alt : nullptr;
+        fs.next_nodal = legacy_dt() ? 0 : 1;
+        fs.cfl = cfl;
         fs.cbrt_vol = lv.cbrt_vol;
         if (out == lv.q) lv.min_ahead = false;      // (a caller that looks ahead sets it after its last stage)
         fs.partial_min = a.apply_min == ApplyMin::Partials ? lv.partial_min : (a.apply_min == ApplyMin::Scalar ? lv.min_dt : (a.apply_min == ApplyMin::List ? a.min_list : nullptr));
@@ -659,11 +669,11 @@ struct mgcfd_solver {
         // the coarse sweep that follows starts with compute_step_factor on the restricted state: the
         // kernel leaves its first half (per-workgroup minima) in partial_min (global time step only)
         // (not on a partitioned level: its ghosts are stale until the halo exchange that follows)
-        const bool ahead = mesh_variant != MGCFD_MESH_FVCORR && C.n_owned == C.info.nel;
+        const bool ahead = global_dt() && C.n_owned == C.info.nel;
         double *pm = ahead ? C.partial_min : nullptr;
         Timed t(this, fine + 1, MGCFD_LOOP_RESTRICT);
         const SumTask task = rms ? *rms : SumTask{};
-        k().restrict_(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, pm, task);
+        k().restrict_(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, cfl, pm, task);
         C.min_ahead = ahead;
         C.iters[MGCFD_LOOP_RESTRICT] += 2 * F.info.mgc + C.info.nel;   // mg_loops.cpp:61,117,172
     }
@@ -674,10 +684,10 @@ struct mgcfd_solver {
         if (!F.has_transfer) throw std::invalid_argument("level has no multigrid map");
         settle_residuals(C);
         settle_residuals(F);
-        const bool ahead = mesh_variant != MGCFD_MESH_FVCORR && F.n_owned == F.info.nel;   // as in op_restrict
+        const bool ahead = global_dt() && F.n_owned == F.info.nel;   // as in op_restrict
         double *pm = ahead ? F.partial_min : nullptr;
         Timed t(this, fine, MGCFD_LOOP_PROLONG);
-        k().prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, pm);
+        k().prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, cfl, pm);
         F.min_ahead = ahead;
         F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;  // mg_loops.cpp:728,842
     }
@@ -1402,11 +1412,11 @@ int mgcfd_get_free_stream(const mgcfd_solver *s, double *mach, double *alpha_deg
 static void synchronize_with_group(mgcfd_solver *s);
 // A kernel-granular sweep that has begun (mgcfd_sweep_flux0, mgcfd_sweep_stage 0 or 1) holds half a sweep of the OLD free
 // stream in its buffers and flags: the setter refuses until its last stage has run.
-static void require_no_sweep_under_way(const mgcfd_solver *s)
+static void require_no_sweep_under_way(const mgcfd_solver *s, const char *what = "free stream")
 {
     for (size_t l = 0; l < s->L.size(); l++)
         if (s->L[l].stage_next != 0 || s->L[l].sweep_flux0_done)
-            throw std::invalid_argument("free stream: a sweep is under way on level " + std::to_string(l) + " (mgcfd_sweep_flux0 / mgcfd_sweep_stage): finish it first");
+            throw std::invalid_argument(std::string(what) + ": a sweep is under way on level " + std::to_string(l) + " (mgcfd_sweep_flux0 / mgcfd_sweep_stage): finish it first");
 }
 // The solver is idle and its graphs are gone: the new far field, and with `reinitialise` the state mgcfd_create leaves.
 static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mach, double alpha_deg, int reinitialise)
@@ -1447,6 +1457,43 @@ int mgcfd_set_free_stream(mgcfd_solver *s, double mach, double alpha_deg, int re
     });
 }
 
+// ---- the time step: mode and CFL number ----
+static void check_time_step(int mode, double cfl)
+{
+    if (mode != MGCFD_DT_REFERENCE && mode != MGCFD_DT_GLOBAL && mode != MGCFD_DT_LOCAL && mode != MGCFD_DT_LOCAL_LEGACY)
+        throw std::invalid_argument("time step: unknown mode " + std::to_string(mode));
+    if (!std::isfinite(cfl) || !(cfl > 0.0)) throw std::invalid_argument("time step: the CFL number must be finite and positive");
+}
+// The solver is idle and its graphs are gone (captured launches carry the CFL number and the look-ahead they were captured
+// with): the new policy, and nothing computed ahead under the old one survives.
+static void apply_time_step(mgcfd_solver *s, int mode, double cfl)
+{
+    s->dt_mode = mode;
+    s->cfl = cfl;
+    for (DeviceLevel &lv : s->L) lv.min_ahead = false;          // partial_min / sf_alt hold the old policy's work
+}
+int mgcfd_set_time_step(mgcfd_solver *s, int mode, double cfl)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        check_time_step(mode, cfl);
+        require_no_sweep_under_way(s, "time step");
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);
+        s->drop_graphs();
+        apply_time_step(s, mode, cfl);
+    });
+}
+int mgcfd_get_time_step(const mgcfd_solver *s, int *mode, double *cfl)
+{
+    REQUIRE(s);
+    if (mode) *mode = s->dt_mode;
+    if (cfl) *cfl = s->cfl;
+    return MGCFD_OK;
+}
+
 // ---- kernel-granular operations ----
 #define OP(body) REQUIRE(s); return guarded([&] { s->use_device(); body; HIP_CHECK(hipGetLastError()); })   /* (a launch that failed must not come back as MGCFD_OK) */
 int mgcfd_copy_old_variables(mgcfd_solver *s, int level) { OP(s->op_copy_old(level)); }
@@ -1464,7 +1511,7 @@ int mgcfd_prolong(mgcfd_solver *s, int fine_level) { OP(s->op_prolong(fine_level
 int mgcfd_step_factor_local(mgcfd_solver *s, int level)
 {
     OP({
-        if (s->mesh_variant == MGCFD_MESH_FVCORR) throw std::invalid_argument("fvcorr uses a local time step: nothing to reduce");
+        if (!s->global_dt()) throw std::invalid_argument("a local time step (mesh_name = fvcorr, or a local mode of mgcfd_set_time_step): nothing to reduce");
         s->op_step_factor_local(level, false, true);
         s->level(level).iters[MGCFD_LOOP_COMPUTE_STEP] += s->level(level).info.nel;
     });
@@ -1542,7 +1589,7 @@ static void smooth_once(mgcfd_solver *s, int level)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
         // change roles at the end (DeviceLevel::rot).
-        const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+        const bool global_dt = s->global_dt();
         bool apply_pending = global_dt;
         lv.residuals_stale = false;                // (an unwritten residual of the previous sweep: this sweep's replaces it)
         if (lv.min_ahead) {
@@ -1677,7 +1724,7 @@ static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
         // As in smooth_once: no copy (the start state stays in `variables` and becomes old_variables
         // when sweep_end rotates the buffers), and no step-factor kernel when the launch that produced
         // `variables` already left the minima behind.
-        const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+        const bool global_dt = s->global_dt();
         if (lv.min_ahead) {
             if (!global_dt) { lv.sf_par ^= 1; lv.apply_sf(); }
             lv.iters[MGCFD_LOOP_COMPUTE_STEP] += lv.info.nel;
@@ -1700,7 +1747,7 @@ static int sweep_end_impl(mgcfd_solver *s, int level, bool scalar)
 {
     OP({
         DeviceLevel &lv = s->level(level);
-        const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+        const bool global_dt = s->global_dt();
         const ApplyMin apply = global_dt ? (scalar ? ApplyMin::Scalar : ApplyMin::Partials) : ApplyMin::None;
         const bool look_ahead = s->L.size() == 1 && lv.n_owned == lv.info.nel;
         auto stage = [&](int j, StageArgs a) {
@@ -1742,7 +1789,7 @@ int mgcfd_sweep_stage(mgcfd_solver *s, int level, int j, int partials)
     OP({
         DeviceLevel &lv = s->level(level);
         if (j != lv.stage_next) throw std::invalid_argument("mgcfd_sweep_stage: stages must run in order 0, 1, 2 after mgcfd_sweep_begin");
-        const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+        const bool global_dt = s->global_dt();
         const StageBuffers b = stage_buffers(lv, j);
         StageArgs a;
         a.old = b.start;
@@ -2427,6 +2474,17 @@ static void group_require_same_free_stream(const mgcfd_group *g)
                                         std::to_string(g->ranks[0]->fs_alpha_deg) + "): mgcfd_group_set_free_stream sets every rank");
 }
 
+// ... and one time-step policy: the same mode and the same CFL number, bit for bit (mgcfd_group_set_time_step).
+static void group_require_same_time_step(const mgcfd_group *g)
+{
+    const mgcfd_solver *r0 = g->ranks[0];
+    for (size_t r = 1; r < g->ranks.size(); r++)
+        if (g->ranks[r]->dt_mode != r0->dt_mode || std::memcmp(&g->ranks[r]->cfl, &r0->cfl, sizeof(double)) != 0)
+            throw std::invalid_argument("the time step of rank " + std::to_string(r) + " differs from rank 0's (mode " + std::to_string(g->ranks[r]->dt_mode) +
+                                        ", CFL " + std::to_string(g->ranks[r]->cfl) + " against mode " + std::to_string(r0->dt_mode) + ", CFL " +
+                                        std::to_string(r0->cfl) + "): mgcfd_group_set_time_step sets every rank");
+}
+
 static void build_halo(mgcfd_solver *s, int level, int n_peers, const int *peers, const int64_t *send_counts, const int64_t *const *send_ids,
                        const int64_t *recv_counts, const int64_t *const *recv_ids, int world)
 {
@@ -2572,7 +2630,7 @@ static bool part_look_ahead()
 }
 
 // Does the last stage of a partitioned sweep look ahead?  Under a global time step only — which is what `apply_min` says:
-// every caller passes None exactly when mesh_name = fvcorr (rank_sweep_once and the group sweeps pass global_dt ? Scalar or
+// every caller passes None exactly under a local time step (rank_sweep_once and the group sweeps pass global_dt ? Scalar or
 // List : None; rank_sweep_once_ipc sets it under `if (global_dt)`).
 static bool part_looks_ahead(ApplyMin apply_min) { return apply_min != ApplyMin::None && part_look_ahead(); }
 // How a partitioned sweep's first stage gets the global time step (None: local time step).
@@ -2632,7 +2690,7 @@ static void sweep_first_half(mgcfd_solver *s, int level, double *min_out = nullp
     DeviceLevel &lv = s->level(level);
     if (!lv.hx) throw std::invalid_argument("the level has no halo lists: call mgcfd_rank_set_halo first");
     if (lv.stage_next != 0) throw std::invalid_argument("a sweep is under way (mgcfd_sweep_stage)");
-    const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+    const bool global_dt = s->global_dt();
     if (global_dt && lv.min_ahead) lv.iters[MGCFD_LOOP_COMPUTE_STEP] += lv.info.nel;      // the previous sweep's last stage looked ahead
     else s->op_step_factor(level, true, false);             // first half of compute_step_factor (a ghost's factor is its owner's business)
     if (global_dt) exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, min_out ? min_out : lv.min_dt);
@@ -2643,7 +2701,7 @@ static void rank_sweep_once(mgcfd_solver *s, int level)
 {
     mgcfd_comm &c = comm_of(s);
     DeviceLevel &lv = s->level(level);
-    const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+    const bool global_dt = s->global_dt();
     sweep_first_half(s, level);
     if (global_dt) RCCL_CHECK(g_rccl.AllReduce(lv.min_dt, lv.min_dt, 1, Rccl::kDouble, Rccl::kMin, c.rccl, s->stream));
     PartMin pm;
@@ -2792,7 +2850,7 @@ static void group_sweeps_threaded(mgcfd_group *g, int level, int sweeps, bool wi
     std::atomic<bool> failed{false};
     std::mutex mu;
     std::exception_ptr first_error;
-    const bool global_dt = g->ranks[0]->mesh_variant != MGCFD_MESH_FVCORR;
+    const bool global_dt = g->ranks[0]->global_dt();
     auto run = [&](int r) {
         mgcfd_solver *s = g->ranks[static_cast<size_t>(r)];
         // (a rank that failed keeps arriving at the barriers, doing nothing, so that the others are not left waiting)
@@ -2848,7 +2906,7 @@ static void group_sweeps_threaded(mgcfd_group *g, int level, int sweeps, bool wi
 static void group_sweep_once(mgcfd_group *g, int level)
 {
     const int n = static_cast<int>(g->ranks.size());
-    const bool global_dt = g->ranks[0]->mesh_variant != MGCFD_MESH_FVCORR;
+    const bool global_dt = g->ranks[0]->global_dt();
     const int par = g->ranks[0]->level(level).hx->min_parity;       // (the ranks of a group sweep in step)
     for (mgcfd_solver *s : g->ranks) { s->use_device(); HaloExchange &hx = *s->level(level).hx; sweep_first_half(s, level, hx.min_par + par); hx.min_parity = par ^ 1; }
     if (global_dt) {
@@ -2976,7 +3034,7 @@ static void rank_sweep_once_ipc(mgcfd_solver *s, int level)
     mgcfd_comm &c = comm_of(s);
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
-    const bool global_dt = s->mesh_variant != MGCFD_MESH_FVCORR;
+    const bool global_dt = s->global_dt();
     if (global_dt && !c.rccl && !hx.ipc_all) throw std::invalid_argument("a global time step needs the all-reduce: attach every rank (mgcfd_rank_ipc_attach with all exports) or RCCL");
     sweep_first_half(s, level);
     // the time step: over the flags when every rank is attached (the ranks' minima side by side, the first stage takes their
@@ -3252,7 +3310,7 @@ int mgcfd_rank_set_halo(mgcfd_solver *s, int level, int n_peers, const int *peer
 static void after_replayed_sweep(mgcfd_solver *s, int level, const int64_t *iters_delta)
 {
     DeviceLevel &lv = s->level(level);
-    lv.finish_sweep(s->mesh_variant != MGCFD_MESH_FVCORR && part_look_ahead());    // (as stage_interior leaves it)
+    lv.finish_sweep(s->global_dt() && part_look_ahead());    // (as stage_interior leaves it)
     lv.stage_out = lv.q;                            // (the replayed stages did not name it)
     for (int k = 0; k < MGCFD_NUM_LOOPS; k++) lv.iters[k] += iters_delta[k];
 }
@@ -3310,7 +3368,7 @@ int mgcfd_rank_sweeps(mgcfd_solver *s, int level, int sweeps)
             // there, hence opt-in)
             // (global time step: a sweep is captured / replayed only from a looked-ahead state — the steady state; the first
             //  sweep after an exchange, which still runs k_step_factor_local, goes out eagerly)
-            const bool steady = s->mesh_variant == MGCFD_MESH_FVCORR || lv.min_ahead || !part_look_ahead();
+            const bool steady = !s->global_dt() || lv.min_ahead || !part_look_ahead();
             if (s->opt_graph && sweep_graphs_enabled() && !hx.graph_failed && s->opt_timing == 0 && steady) {
                 if (!hx.sweep_graph[rot]) {
                     const bool ahead_before = lv.min_ahead;
@@ -3417,6 +3475,23 @@ int mgcfd_group_set_free_stream(mgcfd_group *g, double mach, double alpha_deg, i
     });
 }
 
+int mgcfd_group_set_time_step(mgcfd_group *g, int mode, double cfl)
+{
+    REQUIRE(g);
+    return guarded([&] {
+        check_time_step(mode, cfl);                                         // (a bad argument changes no rank)
+        for (mgcfd_solver *s : g->ranks) require_no_sweep_under_way(s, "time step");
+        for (mgcfd_solver *s : g->ranks) {                                  // as mgcfd_group_set_free_stream: all idle and without graphs, then set
+            s->use_device();
+            s->fold_events();
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            for (DeviceLevel &lv : s->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+            s->drop_graphs();
+        }
+        for (mgcfd_solver *s : g->ranks) apply_time_step(s, mode, cfl);
+    });
+}
+
 int mgcfd_group_exchange(mgcfd_group *g, int level)
 {
     REQUIRE(g);
@@ -3449,6 +3524,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
     return guarded([&] {
         if (rms_out && sweeps > mgcfd_solver::kRmsRing) throw std::invalid_argument("at most 4096 sweeps per call with the RMS of each");
         group_require_same_free_stream(g);
+        group_require_same_time_step(g);
         mgcfd_solver *s0 = g->ranks[0];
         for (mgcfd_solver *s : g->ranks) {
             s->use_device();
@@ -3553,7 +3629,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
         bool replayed = false;
         for (int k = 0; k < sweeps; k++) {
             const int rot = s0->level(level).rot % 3 + 3 * h0.min_parity;     // (the captured launches name the minima's word of this parity)
-            const bool steady = s0->mesh_variant == MGCFD_MESH_FVCORR || s0->level(level).min_ahead || !part_look_ahead();   // (as in mgcfd_rank_sweeps)
+            const bool steady = !s0->global_dt() || s0->level(level).min_ahead || !part_look_ahead();   // (as in mgcfd_rank_sweeps)
             if (graphs && !h0.graph_failed && steady) {
                 if (!h0.sweep_graph[rot]) {
                     const bool ahead_before = s0->level(level).min_ahead;
@@ -3869,7 +3945,7 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms, boo
     std::atomic<bool> failed{false};
     std::mutex mu;
     std::exception_ptr first_error;
-    const bool global_dt = g->ranks[0]->mesh_variant != MGCFD_MESH_FVCORR;
+    const bool global_dt = g->ranks[0]->global_dt();
     auto run = [&](int r) {
         mgcfd_solver *s = g->ranks[static_cast<size_t>(r)];
         // (a rank that failed keeps arriving at the barriers, doing nothing, so that the others are not left waiting)
@@ -3978,6 +4054,7 @@ static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const 
     const int rc = guarded([&] {
         if (cycles > mgcfd_solver::kRmsRing) throw std::invalid_argument("at most 4096 cycles per call");
         group_require_same_free_stream(g);
+        group_require_same_time_step(g);
         const int n = static_cast<int>(g->ranks[0]->L.size());
         for (mgcfd_solver *s : g->ranks) if (static_cast<int>(s->L.size()) != n) throw std::invalid_argument("the ranks of a group hold the same number of levels");
         for (int l = 0; l < n; l++) group_prepare_level(g, l);
@@ -4052,6 +4129,7 @@ int mgcfd_group_surface_loads(mgcfd_group *g, int level, const double ref_point[
     REQUIRE(g); REQUIRE(out6);
     return guarded([&] {
         group_require_same_free_stream(g);
+        group_require_same_time_step(g);
         group_loads_prepare(g, level, ref_point);
         mgcfd_solver *s0 = g->ranks[0];
         double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};

@@ -45,6 +45,19 @@ class MgcfdError(RuntimeError):
 
 
 # Every symbol include/mgcfd.h declares: (name, restype, argtypes)
+# time-step modes (mgcfd_set_time_step): MGCFD_DT_*
+DT_MODE = {"reference": 0, "global": 1, "local": 2, "local_legacy": 3}
+
+
+def _dt_mode(mode) -> int:
+    if isinstance(mode, str):
+        key = mode.replace("-", "_")
+        if key not in DT_MODE:
+            raise ValueError(f"time step: unknown mode {mode!r} (one of {', '.join(DT_MODE)})")
+        return DT_MODE[key]
+    return int(mode)
+
+
 _SIGNATURES = [
     ("mgcfd_last_error", C.c_char_p, []),
     ("mgcfd_abi_version", C.c_int, []),
@@ -160,6 +173,9 @@ _SIGNATURES = [
     ("mgcfd_set_free_stream", C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
     ("mgcfd_get_free_stream", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("mgcfd_group_set_free_stream", C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
+    ("mgcfd_set_time_step", C.c_int, [_vp, C.c_int, C.c_double]),
+    ("mgcfd_get_time_step", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("mgcfd_group_set_time_step", C.c_int, [_vp, C.c_int, C.c_double]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -533,13 +549,29 @@ class Solver:
         self._c(self.lib.mgcfd_get_free_stream(self.handle, C.byref(m), C.byref(a)))
         return m.value, a.value
 
+    # ---- time step ----
+    def set_time_step(self, mode="reference", cfl: float = 0.5):
+        """Which step-factor formula the sweeps run and its CFL number (mgcfd_set_time_step): ``"reference"`` (what the mesh
+        name selects), ``"global"``, ``"local"`` or ``"local_legacy"``.  The state stays; captured graphs are dropped."""
+        self._c(self.lib.mgcfd_set_time_step(self.handle, _dt_mode(mode), float(cfl)))
+
+    def time_step_control(self):
+        """``(mode, cfl)`` in use, the mode by name."""
+        m, c = C.c_int(), C.c_double()
+        self._c(self.lib.mgcfd_get_time_step(self.handle, C.byref(m), C.byref(c)))
+        return {v: k for k, v in DT_MODE.items()}[m.value], c.value
+
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
-              ref_area: float = 1.0, ref_length: float = 1.0) -> List[dict]:
+              ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
         dict: ``alpha``, ``mach``, ``rms`` [cycles], ``loads`` [cycles, 6] and ``coefficients`` (CD CL CS CMx CMy CMz of the
-        last cycle against that angle's far field)."""
+        last cycle against that angle's far field).  ``time_step`` / ``cfl`` (None: as the solver has them) are set once,
+        before the first angle, and stay (``set_time_step``)."""
+        if time_step is not None or cfl is not None:
+            mode0, cfl0 = self.time_step_control()
+            self.set_time_step(mode0 if time_step is None else time_step, cfl0 if cfl is None else cfl)
         m = self.free_stream()[0] if mach is None else float(mach)
         out = []
         for k, a in enumerate(alphas):
@@ -781,6 +813,11 @@ class Group:
         """Solver.set_free_stream on every rank (mgcfd_group_set_free_stream).  The group's sweeps, cycles and loads raise
         MgcfdError (MGCFD_ERR_ARG) while the ranks' far fields differ."""
         _check(self.lib, self.lib.mgcfd_group_set_free_stream(self.handle, float(mach), float(alpha_deg), 1 if reinitialise else 0))
+
+    def set_time_step(self, mode="reference", cfl: float = 0.5):
+        """Solver.set_time_step on every rank (mgcfd_group_set_time_step).  The group's sweeps, cycles and loads raise
+        MgcfdError (MGCFD_ERR_ARG) while the ranks' mode or CFL number differ."""
+        _check(self.lib, self.lib.mgcfd_group_set_time_step(self.handle, _dt_mode(mode), float(cfl)))
 
     def cycles(self, n: int = 1, rms: bool = True, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
         """n V-cycles of a partitioned hierarchy (mgcfd_group_cycles); the level-0 RMS of each cycle.  With ``loads=True``

@@ -350,6 +350,12 @@ def _all_reduce_min(dist, t):
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
 
 
+def _local_time_step(solver) -> bool:
+    """The solver runs a local time-step mode (Solver.set_time_step "local" / "local_legacy"): nothing to all-reduce."""
+    ctl = getattr(solver, "time_step_control", None)
+    return ctl is not None and ctl()[0] in ("local", "local_legacy")
+
+
 def _fused_partitioned_sweep(s, level, global_time_step, allreduce_min_fn, dist, exchange_stage, owner):
     """A sweep of a partitioned level with one fused launch per Runge-Kutta stage: the first half of
     compute_step_factor reduced to the rank's scalar minimum (the ranks' levels differ in size, so their per-workgroup
@@ -372,7 +378,7 @@ class PartitionedCycle:
     `variables` after every time_step, after mgcfd_restrict (the coarse level's ghosts) and after mgcfd_prolong (the
     fine level's), coarse `residuals` before mgcfd_prolong — as packed point-to-point messages (mgcfd_halo_pack /
     _unpack around torch.distributed.batch_isend_irecv, or the injected `exchange`).  One all-reduce(MIN) of the time
-    step per sweep as in PartitionedSweep."""
+    step per sweep as in PartitionedSweep — none under a local time-step mode (Solver.set_time_step), asked per sweep."""
 
     def __init__(self, solver, hpart, dist=None, make_buffer=None, exchange=None, allreduce_min=None, fused=False):
         self.s, self.h = solver, hpart
@@ -420,17 +426,21 @@ class PartitionedCycle:
 
     def sweep(self, level):
         s = self.s
+        local = _local_time_step(s)
         if self.fused:
-            _fused_partitioned_sweep(s, level, True, self.allreduce_min_fn, self.dist,
+            _fused_partitioned_sweep(s, level, not local, self.allreduce_min_fn, self.dist,
                                      lambda: self.exchange(level, "stage"), self)
             return
         s.copy_old_variables(level)
-        s.step_factor_local(level)
-        if self.allreduce_min_fn:
-            self.allreduce_min_fn(self, level)
-        elif self.dist:
-            self.dist.all_reduce(s.min_tensor(level), op=self.dist.ReduceOp.MIN)
-        s.step_factor_apply(level)
+        if local:
+            s.compute_step_factor(level)
+        else:
+            s.step_factor_local(level)
+            if self.allreduce_min_fn:
+                self.allreduce_min_fn(self, level)
+            elif self.dist:
+                self.dist.all_reduce(s.min_tensor(level), op=self.dist.ReduceOp.MIN)
+            s.step_factor_apply(level)
         for j in range(RK):
             s.compute_fluxes(level)
             s.time_step(level, j)
@@ -473,3 +483,25 @@ def set_free_stream_all(solver, mach=None, alpha_deg=None, reinitialise=True, di
         reinitialise = reinitialise != 0.0
     solver.set_free_stream(float(mach), float(alpha_deg), reinitialise)
     return float(mach), float(alpha_deg)
+
+
+def set_time_step_all(solver, mode=None, cfl=None, dist=None):
+    """Set the time-step mode and CFL number of every rank's solver from RANK 0's values (mgcfd_set_time_step): rank 0's
+    ``mode`` and ``cfl`` are broadcast — the CFL number as fp64, so every rank holds the same bits — and every rank, rank 0
+    included, applies what it received; the other ranks' own arguments are ignored and may be None.  Between ranks in
+    different processes the library cannot compare them, so this is how a job keeps them equal.  Collective; returns
+    ``(mode, cfl)`` as applied, the mode by name.  Without an initialised ``dist`` it only sets ``solver``."""
+    from .api import DT_MODE, _dt_mode
+    active = dist is not None and dist.is_initialized()
+    if active:
+        import torch
+        rank0 = dist.get_rank() == 0
+        on_device = "nccl" in str(dist.get_backend()) and "gloo" not in str(dist.get_backend())
+        t = torch.tensor([float(_dt_mode(mode)) if rank0 else 0.0, float(cfl) if rank0 else 0.0],
+                         dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()) if on_device else "cpu")
+        dist.broadcast(t, src=0)
+        mode, cfl = t.tolist()
+        mode = int(mode)
+    name = {v: k for k, v in DT_MODE.items()}[_dt_mode(mode)]
+    solver.set_time_step(name, float(cfl))
+    return name, float(cfl)

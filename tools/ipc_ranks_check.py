@@ -39,15 +39,23 @@ def rank_main(a):
     else:                                                   # global time step: every rank's minimum to every rank, through the flags
         mg = meshgen.make_multigrid((a.lattice,), "m6wing", seed=4, cavity_radius=0.15, jitter=0.2, area_noise=0.05, volume_noise=0.05)
     L = mgcfd.generated_to_levels(mg)[0]
-    parts = partition_level(L, rcb_partition(np.asarray(L["coords"]), a.ranks))
+    if a.strips:                                            # slabs along x: rank r touches r - 1 and r + 1 only
+        x = np.asarray(L["coords"]).reshape(-1, 3)[:, 0]
+        part = np.empty(L["nel"], dtype=np.int64)
+        part[np.argsort(x, kind="stable")] = (np.arange(L["nel"]) * a.ranks) // L["nel"]
+    else:
+        part = rcb_partition(np.asarray(L["coords"]), a.ranks)
+    parts = partition_level(L, part)
     P = parts[a.rank]
     whole = mgcfd.Solver.from_arrays([L], mg.mesh_variant)
     q0 = perturbed_state(L["nel"], whole.far_field()[:5], seed=21)
+    whole.set_time_step(a.time_step, a.cfl)
     whole.set(0, "variables", q0)
     whole.smooth(0, a.sweeps)
     want = whole.get(0, "variables")
     whole.close()
     s = mgcfd.Solver.from_arrays([P.level], mg.mesh_variant, n_owned=[P.n_owned])
+    s.set_time_step(a.time_step, a.cfl)
     s.set(0, "variables", q0[P.global_ids])
     s.rank_attach_plain(a.rank, a.ranks)
     if a.unsplit:
@@ -57,7 +65,9 @@ def rank_main(a):
     s.rank_set_halo(0, P)
     publish(os.path.join(a.dir, f"export.{a.rank}"), s.rank_ipc_export(0))
     peers = sorted(set(P.send) | set(P.recv))
-    s.rank_ipc_attach(0, [wait_for(os.path.join(a.dir, f"export.{p}")) for p in range(a.ranks) if p != a.rank])
+    # (--neighbours-only: no rank holds every rank's export, so the all-reduce of a global time step has nowhere to go —
+    #  a local time step needs none)
+    s.rank_ipc_attach(0, [wait_for(os.path.join(a.dir, f"export.{p}")) for p in (peers if a.neighbours_only else range(a.ranks)) if p != a.rank])
     # nobody pushes before everybody has opened everybody's buffers
     publish(os.path.join(a.dir, f"attached.{a.rank}"), b"1")
     for p in range(a.ranks):
@@ -74,6 +84,8 @@ def rank_main(a):
     ok_own = bool(np.array_equal(got[:P.n_owned].view(np.int64), want[own].view(np.int64)))
     ok_gh = bool(np.array_equal(got[P.n_owned:].view(np.int64), want[gh].view(np.int64)))
     info = s.rank_halo_info(0)
+    if a.neighbours_only:
+        print(f"rank {a.rank}: attached {len(peers)} of {a.ranks - 1} other ranks", flush=True)
     print(f"rank {a.rank}: {P.n_owned} owned + {len(gh)} ghost nodes, peers {peers}, {info['nodes_sent']} nodes per message, owned {'equal' if ok_own else 'DIFFER'}, "
           f"ghosts {'equal' if ok_gh else 'DIFFER'}, waits that gave up: {late}", flush=True)
     if a.time:
@@ -103,6 +115,10 @@ def main():
     ap.add_argument("--one-by-one", action="store_true", help="one mgcfd_rank_sweeps call per sweep")
     ap.add_argument("--unsplit", action="store_true", help="MGCFD_OPT_RANK_SPLIT = 0")
     ap.add_argument("--fused", action="store_true", help="MGCFD_OPT_RANK_SPLIT = 2")
+    ap.add_argument("--time-step", default="reference", choices=["reference", "global", "local", "local_legacy"], help="mgcfd_set_time_step's mode")
+    ap.add_argument("--cfl", type=float, default=0.5)
+    ap.add_argument("--strips", action="store_true", help="partition into slabs along x instead of recursive bisection")
+    ap.add_argument("--neighbours-only", action="store_true", help="every rank attaches its neighbours' exports only")
     ap.add_argument("--rank", type=int, default=-1)
     ap.add_argument("--dir", default="")
     a = ap.parse_args()
@@ -110,7 +126,7 @@ def main():
         sys.exit(rank_main(a))
     with tempfile.TemporaryDirectory(prefix="mgcfd_ipc_") as d:
         procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--ranks", str(a.ranks), "--lattice", str(a.lattice), "--sweeps", str(a.sweeps), "--mesh", a.mesh,
-                                   "--time", str(a.time), "--rank", str(r), "--dir", d] + (["--one-by-one"] if a.one_by_one else []) + (["--unsplit"] if a.unsplit else []) + (["--fused"] if a.fused else [])) for r in range(a.ranks)]
+                                   "--time", str(a.time), "--time-step", a.time_step, "--cfl", repr(a.cfl), "--rank", str(r), "--dir", d] + (["--strips"] if a.strips else []) + (["--neighbours-only"] if a.neighbours_only else []) + (["--one-by-one"] if a.one_by_one else []) + (["--unsplit"] if a.unsplit else []) + (["--fused"] if a.fused else [])) for r in range(a.ranks)]
         rcs = [p.wait(timeout=600) for p in procs]
     print("ranks returned", rcs)
     sys.exit(0 if all(rc == 0 for rc in rcs) else 1)
