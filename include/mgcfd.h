@@ -149,6 +149,11 @@ int mgcfd_abi_version(void);
  * that it happens WHILE the caller reads its input files (0.1 s of a drop-in run's start-up); mgcfd_create* waits for it.
  * No reference counterpart (a CPU code has no device to wake).  Errors surface in mgcfd_create*, not here. */
 int mgcfd_device_warm_up(int device);
+/* What the library holds on the devices in this process right now: out[0] device allocations, out[1] their bytes, out[2]
+ * handles (streams, events, graph executables, opened HIP IPC mappings) — of every solver, whatever its device.  Counted by
+ * the library itself, so the figures do not move with what else runs on a card; after every solver and group has been
+ * destroyed they are back where they were before the first was created.  Touches no device. */
+int mgcfd_live_device_resources(int64_t out[3]);
 
 /* ---------------------------------------------------------------------------------
  * File boundary (host only, no GPU needed)
@@ -486,7 +491,11 @@ int mgcfd_rank_attach_rccl(mgcfd_solver *s, int rank, int world, const void *id1
 int mgcfd_rank_detach(mgcfd_solver *s);
 /* The level's neighbours: peers[k] ascending; send_ids[k] = the OWNED local nodes peer k holds as ghosts, recv_ids[k] =
  * the local GHOSTS peer k owns, both in an order the two ranks agree on (ascending global id).  Also splits the level's
- * tiles into boundary / interior for the overlapped exchange. */
+ * tiles into boundary / interior for the overlapped exchange.
+ * A level that already has an exchange gets a new one: the call synchronises the solver's stream and the old exchange's
+ * message stream and frees the old one.  It is refused (MGCFD_ERR_ARG, nothing changed) while other ranks hold device
+ * addresses into the old exchange: while it is attached through HIP IPC (mgcfd_rank_ipc_detach on every rank first), and
+ * once a group has run mgcfd_group_exchange, sweeps or cycles on the level (create the solvers and the group anew). */
 int mgcfd_rank_set_halo(mgcfd_solver *s, int level, int n_peers, const int *peers, const int64_t *send_counts,
                         const int64_t *const *send_ids, const int64_t *recv_counts, const int64_t *const *recv_ids);
 int mgcfd_rank_halo_info(const mgcfd_solver *s, int level, int64_t out[4]);   /* boundary tiles, interior tiles, nodes sent, nodes received */
@@ -525,7 +534,7 @@ int mgcfd_rank_ipc_attach(mgcfd_solver *s, int level, int n_exports, const void 
 int mgcfd_rank_ipc_status(mgcfd_solver *s, int level, int *timed_out);
 int mgcfd_rank_ipc_detach(mgcfd_solver *s, int level);       /* back to the buffered form; closes the neighbours' mappings */
 int mgcfd_group_create(int n, mgcfd_solver *const *solvers, mgcfd_group **out);   /* solvers[r] becomes rank r of n */
-void mgcfd_group_destroy(mgcfd_group *g);
+void mgcfd_group_destroy(mgcfd_group *g);       /* its solvers are ranks of nothing afterwards; they and the group may be destroyed in either order */
 /* mgcfd_set_free_stream on every rank: one pass leaves all ranks idle and without graphs (the group's own sweep graph,
  * MGCFD_GROUP_GRAPH=1, included), a second one sets them; a bad argument or a sweep under way changes no rank.  The group calls that run sweeps, cycles or loads (mgcfd_group_sweeps[_rms],
  * mgcfd_group_cycles[_loads], mgcfd_group_surface_loads) return MGCFD_ERR_ARG while the ranks' far fields differ in any bit;

@@ -21,11 +21,13 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "device_owner.hpp"
 #include "kernels.hpp"
 #include "mesh.hpp"
 #include "mgcfd.h"
@@ -35,32 +37,7 @@ namespace mgcfd {
 
 static thread_local std::string g_last_error;
 
-struct HipError : std::runtime_error {
-    explicit HipError(const std::string &m) : std::runtime_error(m) {}
-};
-
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            throw HipError(std::string(#expr) + " failed: " + hipGetErrorString(_e));                \
-    } while (0)
-
-template <typename T> static T *dev_alloc(size_t n)
-{
-    void *p = nullptr;
-    HIP_CHECK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-    return static_cast<T *>(p);
-}
-
-template <typename T> static T *dev_upload(const std::vector<T> &v)
-{
-    T *p = dev_alloc<T>(v.size());
-    if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return p;
-}
-
-// A level's device arrays live in ONE block (a creation is one hipMalloc and a destruction one hipFree per level instead
+// A level's device arrays live in ONE block (a creation is one allocation and a destruction one free per level instead
 // of 55 of each).  build_solver first lists them — which member points where, from which host array it is filled — with
 // no call into the runtime (so that the listing and the repacking into device layouts can run while the device is still
 // waking up), then allocates the block, sets the members and copies.
@@ -86,7 +63,7 @@ struct LevelStaging {
     }
 };
 
-struct EventPair { hipEvent_t start, stop; int level, loop; bool is_flux_internal; int launches; };
+struct EventPair { Event start, stop; int level, loop; bool is_flux_internal; int launches; };
 
 // The halo exchange of one partitioned level as the C++ host runs it (mgcfd_rank_* / mgcfd_group_*): ONE packed message
 // per exchange holding every peer's segment (one pack and one unpack launch whatever the number of peers), one buffer
@@ -95,15 +72,16 @@ struct EventPair { hipEvent_t start, stop; int level, loop; bool is_flux_interna
 // which run while the message travels.
 struct HaloExchange {
     static constexpr int kSets = 3;
+    DeviceOwner mem;                                     // every device array named below (not the opened mappings)
     std::vector<int> peer;                               // neighbouring ranks, ascending
     std::vector<int64_t> send_off, recv_off;             // [n_peers+1] node offsets of the peers' segments
     int32_t *send_idx = nullptr, *recv_idx = nullptr;    // device: library node ids, all peers concatenated
     double *send_buf[kSets] = {nullptr, nullptr, nullptr}, *recv_buf[kSets] = {nullptr, nullptr, nullptr};   // device: [nodes][5]
     int32_t *tiles_boundary = nullptr, *tiles_interior = nullptr, *tiles_all = nullptr;   // (all = boundary then interior: one launch per stage)
     int32_t n_boundary = 0, n_interior = 0;
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t packed[kSets] = {nullptr, nullptr, nullptr}, arrived[kSets] = {nullptr, nullptr, nullptr};
-    hipEvent_t reduced = nullptr, gathered = nullptr, joined = nullptr;   // the in-process all-reduce of the time step; graph capture joins
+    Stream comm_stream;
+    Event packed[kSets], arrived[kSets];
+    Event reduced, gathered, joined;   // the in-process all-reduce of the time step; graph capture joins
     double *gmin = nullptr;                              // device [world]: [0] = the group's minimum time step (in-process groups)
     // in-process groups: every rank reads the others' minima IN PLACE (k_min_over_peers), so a rank's minimum of sweep k must not
     // be overwritten by its reduction of sweep k + 1 while a rank that is no halo neighbour — nothing on the device orders the two —
@@ -113,7 +91,7 @@ struct HaloExchange {
     int min_parity = 0;                                  // ... and which of them the NEXT sweep writes
     const double **peer_scalars[2] = {nullptr, nullptr}; // device [world] per parity: where every rank of the group keeps that minimum
     // the sweep as a captured graph per buffer rotation (one host call per sweep instead of ~25): RCCL ranks
-    hipGraphExec_t sweep_graph[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [rotation (+ 3 x parity of the minima: in-process groups)]
+    GraphExec sweep_graph[6];   // [rotation (+ 3 x parity of the minima: in-process groups)]
     int64_t graph_iters[6][MGCFD_NUM_LOOPS] = {{0}};
     bool graph_failed = false;
     int64_t sweeps_replayed = 0;          // ... launched from one of them so far (mgcfd_rank_graph_status)
@@ -122,7 +100,7 @@ struct HaloExchange {
     // previous-stage events instead
     std::vector<int32_t> recv_idx_host;                  // recv_idx on the host (a peer builds its push targets from it)
     int32_t *push_target = nullptr;                      // device [total_send]: slot k's node in the numbering of the peer it goes to
-    hipEvent_t bdone[3] = {nullptr, nullptr, nullptr};   // [stage] this rank's boundary tiles and push of that stage are enqueued up to here
+    Event bdone[3];                                      // [stage] this rank's boundary tiles and push of that stage are enqueued up to here
     bool direct = false;
     // ranks in different PROCESSES, direct mode (mgcfd_rank_ipc_*): the peers' state buffers and flag words opened through HIP IPC
     bool ipc = false;
@@ -140,9 +118,10 @@ struct HaloExchange {
     int64_t peer_stride[kMaxPushPeers] = {};
     int peer_rot_delta[kMaxPushPeers] = {};              // (peer's rotation - ours) mod 3 when the buffers were exchanged
     unsigned long long *peer_flag[kMaxPushPeers] = {};   // opened: the words of peer k's flag array this rank raises
-    std::vector<void *> ipc_opened;                      // every mapping opened (closed again in mgcfd_rank_detach / the destructor)
+    std::vector<IpcMapping> ipc_opened;                  // every mapping opened (closed again in mgcfd_rank_ipc_detach, or with the exchange)
     int32_t *node_send_ptr = nullptr, *node_send_target = nullptr;   // device: the message per NODE (StagePush: a stage that sends it itself)
     int8_t *node_send_peer = nullptr;
+    bool group_prepared() const { return min_par || peer_scalars[0] || direct; }   // the other ranks of a group hold addresses into this exchange
     int64_t total_send() const { return send_off.empty() ? 0 : send_off.back(); }
     int64_t total_recv() const { return recv_off.empty() ? 0 : recv_off.back(); }
 };
@@ -151,26 +130,20 @@ struct HaloExchange {
 struct RankLoads {
     std::vector<int64_t> slot_host;      // position of this rank's k-th solid-wall edge in the whole level's solid-wall slice
     int64_t total = 0;                   // the whole level's solid-wall edge count
+    DeviceOwner mem;                     // every device array named below
     int32_t *slot = nullptr;             // device [n_wall_rec]
-    hipEvent_t terms = nullptr;          // this rank's terms of the evaluation under way are stored up to here
+    Event terms;                         // this rank's terms of the evaluation under way are stored up to here
     bool checked = false;                // the host checks over all ranks have passed with these slots
     // the gathering rank (rank 0):
     int64_t row = 0;                     // total rounded up to 256
     double *table = nullptr;             // device [6][row]: every rank's terms in the whole level's order, pad lanes +0.0
     double *partial = nullptr;           // [6][row / 256]
     unsigned *ticket = nullptr;
-    hipEvent_t read = nullptr;           // the reduce that read the table last is enqueued up to here
+    Event read;                          // the reduce that read the table last is enqueued up to here
     // one rank per process over RCCL: the terms travel as a message
     std::vector<int64_t> counts;         // every rank's edge count, agreed once
     double *compact = nullptr;           // this rank's terms [6][own count]; rank 0: the other ranks' messages, one after another
     std::vector<int32_t *> peer_slot;    // rank 0: device copies of the other ranks' slots
-    ~RankLoads()
-    {
-        for (void *p : {static_cast<void *>(slot), static_cast<void *>(table), static_cast<void *>(partial), static_cast<void *>(ticket), static_cast<void *>(compact)})
-            if (p) (void)hipFree(p);
-        for (int32_t *p : peer_slot) if (p) (void)hipFree(p);
-        for (hipEvent_t e : {terms, read}) if (e) (void)hipEventDestroy(e);
-    }
 };
 
 struct DeviceLevel {
@@ -222,9 +195,8 @@ struct DeviceLevel {
     double *loads_partial = nullptr;
     unsigned *loads_ticket = nullptr;
     std::unique_ptr<RankLoads> rl;       // a partitioned level whose ranks add their loads up
-    void *block = nullptr;               // the one allocation behind every array listed at creation (LevelStaging)
-    size_t block_bytes = 0;
-    bool in_block(const void *p) const { return block && p >= block && p < static_cast<const char *>(block) + block_bytes; }
+    DeviceOwner mem;                     // the one block behind every array listed at creation (LevelStaging), the three state
+                                         // buffers, and what an option or a halo plan uploaded later
     int64_t iters[MGCFD_NUM_LOOPS] = {0};
     double times[MGCFD_NUM_LOOPS] = {0};
     double flux_time = 0.0;
@@ -268,11 +240,27 @@ using namespace mgcfd;
 
 struct mgcfd_mesh { HostMesh mesh; };
 
+// what a solver knows about the ranks around it
+struct mgcfd_comm {
+    int rank = 0, world = 1;
+    void *rccl = nullptr;                         // ncclComm_t (one rank per process)
+    struct mgcfd_group *group = nullptr;          // or: the in-process group this solver is rank `rank` of
+};
+struct mgcfd_group {
+    std::vector<struct mgcfd_solver *> ranks;     // (a rank destroyed before its group leaves a null entry)
+    bool peer_ok = true;                          // every device of the group can address every other one's memory (direct mode stores into it)
+};
+
 struct mgcfd_solver {
     int device = 0;
     int mesh_variant = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    // Members that own device resources free them after ~mgcfd_solver's body has synchronised, in reverse order of
+    // declaration: the stream is declared first, so everything that ran on it goes before it does.
+    Stream own_stream;
+    hipStream_t stream = nullptr;
+    DeviceOwner mem;                         // err, the RMS and loads rings, loads_dev
     std::vector<DeviceLevel> L;
+    std::optional<mgcfd_comm> comm;          // set while the solver is a rank of something (mgcfd_rank_attach_*, mgcfd_group_create)
     FarField ff{};
     double ff17[17] = {0};
     unsigned long long *err = nullptr;       // device: packed (cell << 8 | code), ~0 = clean
@@ -291,9 +279,9 @@ struct mgcfd_solver {
     bool probe_first_stage_only = false;    // (a sampled sweep of OPT_TIMING == 4 runs the indirect_rw probe behind its first stage only)
     int64_t sweep_counter = 0;
     bool in_timed_group = false;
-    struct SweepGraph { hipGraphExec_t exec = nullptr; int64_t iters[MGCFD_NUM_LOOPS] = {0}; bool ahead_after = false; int rot_after = 0; int sf_par_after = 0; bool sumsq_after = false, res_stale_after = false; };
+    struct SweepGraph { GraphExec exec; int64_t iters[MGCFD_NUM_LOOPS] = {0}; bool ahead_after = false; int rot_after = 0; int sf_par_after = 0; bool sumsq_after = false, res_stale_after = false; };
     std::map<uint64_t, SweepGraph> sweep_graphs;   // captured smoothing sweeps, keyed by (level, options)
-    struct CycleGraph { hipGraphExec_t exec = nullptr; std::vector<std::vector<int64_t>> iters; std::vector<bool> ahead_after, res_stale_after; std::vector<int> rot_after, sf_par_after; };
+    struct CycleGraph { GraphExec exec; std::vector<std::vector<int64_t>> iters; std::vector<bool> ahead_after, res_stale_after; std::vector<int> rot_after, sf_par_after; };
     std::map<uint64_t, CycleGraph> cycle_graphs;   // captured whole multigrid cycles, keyed by options
     static constexpr int kRmsRing = 4096;
     double *rms_ring = nullptr;                    // level-0 sum of squares of the cycles run since the last read-back
@@ -332,17 +320,13 @@ struct mgcfd_solver {
     // Call with the stream idle.
     void drop_graphs()
     {
-        for (auto &g : sweep_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
         sweep_graphs.clear();
-        for (auto &g : cycle_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
         cycle_graphs.clear();
-        for (DeviceLevel &lv : L) {
-            if (!lv.hx) continue;
-            for (hipGraphExec_t &ge : lv.hx->sweep_graph) if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
-        }
+        for (DeviceLevel &lv : L)
+            if (lv.hx) for (GraphExec &ge : lv.hx->sweep_graph) ge.reset();
     }
     std::vector<EventPair> pending;
-    std::vector<hipEvent_t> free_events;
+    std::vector<Event> free_events;
 
     ~mgcfd_solver();
     void use_device() const { HIP_CHECK(hipSetDevice(device)); }
@@ -362,12 +346,12 @@ struct mgcfd_solver {
     }
 
     // ---- timing --------------------------------------------------------------------------
-    hipEvent_t get_event()
+    Event get_event()
     {
         if (pending.size() >= 8192) fold_events();
-        if (!free_events.empty()) { hipEvent_t e = free_events.back(); free_events.pop_back(); return e; }
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreate(&e));
+        if (free_events.empty()) return make_event();
+        Event e = std::move(free_events.back());
+        free_events.pop_back();
         return e;
     }
     void fold_events()
@@ -376,12 +360,12 @@ struct mgcfd_solver {
         HIP_CHECK(hipStreamSynchronize(stream));
         for (auto &p : pending) {
             float ms = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&ms, p.start, p.stop));
+            HIP_CHECK(hipEventElapsedTime(&ms, p.start.get(), p.stop.get()));
             DeviceLevel &lv = L[static_cast<size_t>(p.level)];
             lv.times[p.loop] += double(ms) * 1e-3;
             if (p.is_flux_internal) { lv.flux_time += double(ms) * 1e-3; lv.flux_launches += p.launches; }
-            free_events.push_back(p.start);
-            free_events.push_back(p.stop);
+            free_events.push_back(std::move(p.start));
+            free_events.push_back(std::move(p.stop));
         }
         pending.clear();
     }
@@ -396,14 +380,14 @@ struct mgcfd_solver {
             if (!on) return;
             p = EventPair{s->get_event(), s->get_event(), level, loop, flux_internal, launches};
             if (launches > 1) s->in_timed_group = true;
-            HIP_CHECK(hipEventRecord(p.start, s->stream));
+            HIP_CHECK(hipEventRecord(p.start.get(), s->stream));
         }
         ~Timed()
         {
             if (!on) return;
-            (void)hipEventRecord(p.stop, s->stream);
-            s->pending.push_back(p);
+            (void)hipEventRecord(p.stop.get(), s->stream);
             if (p.launches > 1) s->in_timed_group = false;
+            s->pending.push_back(std::move(p));
         }
     };
 
@@ -474,10 +458,10 @@ struct mgcfd_solver {
     {
         LevelPlan &P = lv.plan;
         const int v = opt_variant;
-        auto take = [](auto &vec) { auto *p = dev_upload(vec); vec.clear(); vec.shrink_to_fit(); return p; };
+        auto take = [&lv](auto &vec) { auto *p = lv.mem.upload(vec); vec.clear(); vec.shrink_to_fit(); return p; };
         // order-free / half rows: MGCFD_OPT_EXACT = 0 (the automatic variant takes the order-free kernel), or bits 5 / 6
         if (lv.dp.free_rows && !lv.dp.hr_code && (!opt_exact || (v >= 0 && (v & (32 | 64))))) {
-            lv.dp.hr_row0 = dev_upload(P.hr_row0);
+            lv.dp.hr_row0 = lv.mem.upload(P.hr_row0);
             lv.dp.hr_code = take(P.hr_code);
             lv.dp.hr_w = take(P.hr_w);
             if (lv.dp.free_wide) lv.dp.free_halo = take(P.free_halo);
@@ -485,8 +469,8 @@ struct mgcfd_solver {
         if (lv.dp.free_rows && !lv.dp.hg16 && v >= 0 && (v & 32)) lv.dp.hg16 = take(P.hg16);
         // edge-once tiles (bit 1) and indexed weights (bit 4)
         if (lv.dp.edge_once && !lv.dp.gat16 && v >= 0 && (v & (2 | 16))) {
-            lv.dp.te_chunk_ptr = dev_upload(P.te_chunk_ptr);
-            lv.dp.te_count = dev_upload(P.te_count);
+            lv.dp.te_chunk_ptr = lv.mem.upload(P.te_chunk_ptr);
+            lv.dp.te_count = lv.mem.upload(P.te_count);
             lv.dp.gat16 = take(P.gat16);
             {   // the a-side weights as 24-byte records, one per listed edge (k_flux_tile WMODE 2: indexed weights)
                 const size_t n_chunks = P.te_w.size() / (4 * kEdgeChunk);
@@ -494,7 +478,7 @@ struct mgcfd_solver {
                 for (size_t c = 0; c < n_chunks; c++)
                     for (size_t ln = 0; ln < size_t(kEdgeChunk); ln++)
                         for (size_t k = 0; k < 3; k++) w3[(c * kEdgeChunk + ln) * 3 + k] = P.te_w[(c * 4 + k) * kEdgeChunk + ln];
-                lv.dp.te_w3 = dev_upload(w3);
+                lv.dp.te_w3 = lv.mem.upload(w3);
             }
             lv.dp.te_slots = take(P.te_slots);
             lv.dp.te_w = take(P.te_w);
@@ -554,7 +538,7 @@ struct mgcfd_solver {
         const int accumulate = lv.fluxes_zero ? 0 : 1;     // 0.0 + x: same bits either way
         const int variant = variant_for(lv);
         if ((variant & 4) && !lv.dp.edge_flux)              // two-phase design point: edge-flux scratch on first use
-            lv.dp.edge_flux = dev_alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
+            lv.dp.edge_flux = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
         k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr, nullptr);
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
@@ -729,50 +713,13 @@ static void fail_on_ipc_timeouts(mgcfd_solver *s)
     }
 }
 
+// (does not call into RCCL: a communicator goes with mgcfd_rank_detach)
 mgcfd_solver::~mgcfd_solver()
 {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
-    for (auto &g : sweep_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    for (auto &g : cycle_graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    if (rms_ring) (void)hipFree(rms_ring);
-    if (rms_count) (void)hipFree(rms_count);
-    if (loads_ring) (void)hipFree(loads_ring);
-    if (loads_dev) (void)hipFree(loads_dev);
-    for (auto &p : pending) { (void)hipEventDestroy(p.start); (void)hipEventDestroy(p.stop); }
-    for (auto e : free_events) (void)hipEventDestroy(e);
-    for (auto &lv : L) {
-        void *ptrs[] = {lv.q_alt, lv.sf_alt, lv.tile_sumsq, lv.dp.nbr16, lv.dp.tile_halo, lv.dp.tile_ovf_ptr, lv.dp.tile_ovf, lv.q, lv.old_variables, lv.fluxes, lv.residuals, lv.step_factors, lv.volumes,
-                        lv.cbrt_vol, lv.min_dt, lv.partial_min, lv.sumsq, lv.partials, lv.dp.slice_row0, lv.dp.rows_int,
-                        lv.dp.rows_bnd, lv.dp.nbr, lv.dp.w, lv.dp.old_of_new, lv.dp.child_ptr, lv.dp.child, lv.dp.child4, lv.dp.pro_w, lv.dp.pro_p, lv.dp.pro_tile_n, lv.dp.pro_tile_ids, lv.dp.pro_s16, lv.dp.pro_own16,
-                        lv.dp.pro_parent, lv.dp.pro_wsum, lv.dp.te_chunk_ptr, lv.dp.te_count, lv.dp.te_slots, lv.dp.te_w, lv.dp.te_w3, lv.dp.hr_row0, lv.dp.hr_code, lv.dp.hr_w, lv.dp.hg16, lv.dp.free_halo,
-                        lv.dp.gat16, lv.dp.fe_ab, lv.dp.fe_w, lv.dp.row_edge, lv.dp.edge_flux,
-                        const_cast<int32_t *>(lv.dp.tail.rows_main), const_cast<int32_t *>(lv.dp.tail.tile_ptr),
-                        const_cast<double2 *>(lv.dp.tail.rec), const_cast<int32_t *>(lv.dp.tail.begin),
-                        const_cast<int32_t *>(lv.dp.tail.count), lv.dp.tail.flux};
-        for (void *p : ptrs) if (p && !lv.in_block(p)) (void)hipFree(p);      // (what an option uploaded later has an allocation of its own)
-        if (lv.block) (void)hipFree(lv.block);
-        for (auto &hp : lv.halo_plans) if (hp.first) (void)hipFree(hp.first);
-        lv.rl.reset();
-        if (lv.hx) {
-            HaloExchange &hx = *lv.hx;
-            for (void *m : hx.ipc_opened) (void)hipIpcCloseMemHandle(m);
-            void *hp[] = {hx.node_send_ptr, hx.node_send_target, hx.node_send_peer, hx.send_idx, hx.recv_idx, hx.tiles_boundary, hx.tiles_interior, hx.tiles_all, hx.gmin, hx.peer_scalars[0], hx.peer_scalars[1], hx.min_par, hx.push_target, hx.flags, hx.ticket, hx.ipc_timeouts, hx.gmins};
-            for (hipEvent_t e : hx.bdone) if (e) (void)hipEventDestroy(e);
-            for (void *p : hp) if (p) (void)hipFree(p);
-            for (int b = 0; b < HaloExchange::kSets; b++) {
-                if (hx.send_buf[b]) (void)hipFree(hx.send_buf[b]);
-                if (hx.recv_buf[b]) (void)hipFree(hx.recv_buf[b]);
-                if (hx.packed[b]) (void)hipEventDestroy(hx.packed[b]);
-                if (hx.arrived[b]) (void)hipEventDestroy(hx.arrived[b]);
-            }
-            for (hipGraphExec_t ge : hx.sweep_graph) if (ge) (void)hipGraphExecDestroy(ge);
-            for (hipEvent_t e : {hx.reduced, hx.gathered, hx.joined}) if (e) (void)hipEventDestroy(e);
-            if (hx.comm_stream) (void)hipStreamDestroy(hx.comm_stream);
-        }
-    }
-    if (err) (void)hipFree(err);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
+    for (DeviceLevel &lv : L) if (lv.hx) (void)hipStreamSynchronize(lv.hx->comm_stream.get());
+    if (comm && comm->group) comm->group->ranks[static_cast<size_t>(comm->rank)] = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1087,9 +1034,9 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
     lap("device layouts repacked (a thread per level)");
     if (device_later) device_ready();
     s->use_device();
-    HIP_CHECK(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    s->stream = s->own_stream;
-    s->err = dev_alloc<unsigned long long>(1);
+    s->own_stream = make_stream();
+    s->stream = s->own_stream.get();
+    s->err = s->mem.alloc<unsigned long long>(1);
     HIP_CHECK(hipMemset(s->err, 0xFF, sizeof(unsigned long long)));
     lap("device (behind its warm-up), stream");
     // the copies out of pageable memory are host work too: a thread per level again, every thread selects the device
@@ -1099,18 +1046,17 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
         DeviceLevel &lv = s->L[static_cast<size_t>(l)];
         LevelStaging &st = staging[static_cast<size_t>(l)];
         const int64_t stride = lv.dp.stride;
-        HIP_CHECK(hipMalloc(&lv.block, st.total));
-        lv.block_bytes = st.total;
+        char *const block = static_cast<char *>(lv.mem.alloc_bytes(st.total));
         for (const LevelStaging::Item &it : st.items) {
-            it.place(static_cast<char *>(lv.block));
-            if (it.bytes) HIP_CHECK(hipMemcpy(static_cast<char *>(lv.block) + it.offset, it.src, it.bytes, hipMemcpyHostToDevice));
+            it.place(block);
+            if (it.bytes) HIP_CHECK(hipMemcpy(block + it.offset, it.src, it.bytes, hipMemcpyHostToDevice));
         }
         st = LevelStaging();
         // (the three state buffers keep allocations of their own: a partitioned level exports them to its peers'
         // processes, and an inter-process handle names a whole allocation)
-        lv.q = dev_alloc<double>(static_cast<size_t>(stride) * kNumStateFields);
-        lv.q_alt = dev_alloc<double>(static_cast<size_t>(stride) * 5);
-        lv.old_variables = dev_alloc<double>(static_cast<size_t>(stride) * 5);
+        lv.q = lv.mem.alloc<double>(static_cast<size_t>(stride) * kNumStateFields);
+        lv.q_alt = lv.mem.alloc<double>(static_cast<size_t>(stride) * 5);
+        lv.old_variables = lv.mem.alloc<double>(static_cast<size_t>(stride) * 5);
         lv.state[0] = lv.q; lv.state[1] = lv.q_alt; lv.state[2] = lv.old_variables;
         lv.sfb[0] = lv.step_factors; lv.sfb[1] = lv.sf_alt;
         lv.plan.nbr16.clear(); lv.plan.nbr16.shrink_to_fit();
@@ -1157,6 +1103,12 @@ extern "C" {
 
 const char *mgcfd_last_error(void) { return g_last_error.c_str(); }
 int mgcfd_abi_version(void) { return 1; }
+int mgcfd_live_device_resources(int64_t out[3])
+{
+    REQUIRE(out);
+    out[0] = g_live.allocations; out[1] = g_live.bytes; out[2] = g_live.handles;
+    return MGCFD_OK;
+}
 int mgcfd_device_warm_up(int device)
 {
     std::lock_guard<std::mutex> lk(g_warm_mutex);
@@ -1374,7 +1326,7 @@ int mgcfd_set_stream(mgcfd_solver *s, void *hip_stream)
         s->use_device();
         s->fold_events();
         HIP_CHECK(hipStreamSynchronize(s->stream));
-        s->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->own_stream;
+        s->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->own_stream.get();
     });
 }
 int mgcfd_synchronize(mgcfd_solver *s)
@@ -1693,17 +1645,16 @@ static void run_sweep(mgcfd_solver *s, int level)
         }
         s->opt_timing = keep;
         HIP_CHECK(hipStreamEndCapture(s->stream, &graph));
-        HIP_CHECK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-        HIP_CHECK(hipGraphDestroy(graph));
+        g.exec = instantiate(graph);
         for (int k = 0; k < MGCFD_NUM_LOOPS; k++) { g.iters[k] = lv.iters[k] - before[k]; lv.iters[k] = before[k]; }
         g.ahead_after = lv.min_ahead;
         g.rot_after = lv.rot;
         g.sf_par_after = lv.sf_par;
         g.sumsq_after = lv.have_sumsq;
         g.res_stale_after = lv.residuals_stale;
-        it = s->sweep_graphs.emplace(key, g).first;
+        it = s->sweep_graphs.emplace(key, std::move(g)).first;
     }
-    HIP_CHECK(hipGraphLaunch(it->second.exec, s->stream));
+    HIP_CHECK(hipGraphLaunch(it->second.exec.get(), s->stream));
     lv.min_ahead = it->second.ahead_after;
     lv.rot = it->second.rot_after;
     lv.apply_rot();
@@ -1843,6 +1794,19 @@ static void loads_require_whole(const mgcfd_solver *s);
 // the reference point to the device (and the room for a synchronous call's result)
 static void loads_upload_ref(mgcfd_solver *s, const double *ref_point);
 
+// The rings a run of cycles or sweeps appends to, made by whoever first asks for them — with the solver's device selected,
+// and never inside a capture.
+static void ensure_rms_ring(mgcfd_solver *s)
+{
+    if (s->rms_ring) return;
+    s->rms_ring = s->mem.alloc<double>(mgcfd_solver::kRmsRing);
+    s->rms_count = s->mem.alloc<int>(1);
+}
+static void ensure_loads_ring(mgcfd_solver *s)
+{
+    if (!s->loads_ring) s->loads_ring = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+}
+
 static void loads_prepare(mgcfd_solver *s, const double *ref_point)
 {
     loads_require_whole(s);
@@ -1851,7 +1815,7 @@ static void loads_prepare(mgcfd_solver *s, const double *ref_point)
 
 static void loads_upload_ref(mgcfd_solver *s, const double *ref_point)
 {
-    if (!s->loads_dev) s->loads_dev = dev_alloc<double>(9);
+    if (!s->loads_dev) s->loads_dev = s->mem.alloc<double>(9);
     for (int k = 0; k < 3; k++) s->loads_ref_host[k] = ref_point ? ref_point[k] : 0.0;
     HIP_CHECK(hipMemcpyAsync(s->loads_dev, s->loads_ref_host, sizeof(double) * 3, hipMemcpyHostToDevice, s->stream));
 }
@@ -1917,14 +1881,11 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
     std::vector<double> loads;
     int rc = guarded([&] {
         s->use_device();
-        if (!s->rms_ring) {
-            s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing);
-            s->rms_count = dev_alloc<int>(1);
-        }
+        ensure_rms_ring(s);
         struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = false; } } loads_off{s};
         if (loads_out) {
             loads_prepare(s, ref_point);
-            if (!s->loads_ring) s->loads_ring = dev_alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+            ensure_loads_ring(s);
             s->loads_in_cycle = s->L[0].n_wall_rec > 0;        // (no solid wall: zeros, nothing launched)
             loads.reserve(static_cast<size_t>(cycles > 0 ? cycles : 0) * 6);
         }
@@ -1935,8 +1896,8 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
         for (int done = 0; done < cycles;) {
             const int chunk = std::min(cycles - done, mgcfd_solver::kRmsRing);
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
-            hipEvent_t att0 = nullptr, att1 = nullptr;
-            if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0, s->stream)); }
+            Event att0, att1;
+            if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
             bool graphable = s->opt_graph && s->opt_fuse && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
@@ -1971,8 +1932,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
                             throw;
                         }
                         HIP_CHECK(hipStreamEndCapture(s->stream, &graph));
-                        HIP_CHECK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-                        HIP_CHECK(hipGraphDestroy(graph));
+                        g.exec = instantiate(graph);
                         g.iters.resize(nl);
                         for (size_t l = 0; l < nl; l++) {
                             for (int k = 0; k < MGCFD_NUM_LOOPS; k++) {
@@ -1992,7 +1952,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
                         }
                         it = s->cycle_graphs.emplace(key, std::move(g)).first;
                     }
-                    HIP_CHECK(hipGraphLaunch(it->second.exec, s->stream));
+                    HIP_CHECK(hipGraphLaunch(it->second.exec.get(), s->stream));
                     for (size_t l = 0; l < nl; l++) {
                         for (int k = 0; k < MGCFD_NUM_LOOPS; k++) s->L[l].iters[k] += it->second.iters[l][static_cast<size_t>(k)];
                         s->L[l].min_ahead = it->second.ahead_after[l];
@@ -2009,7 +1969,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
                     if (c == 0) seq_per_cycle = s->check_seq - seq_before;
                 }
             }
-            if (att1) HIP_CHECK(hipEventRecord(att1, s->stream));
+            if (att1) HIP_CHECK(hipEventRecord(att1.get(), s->stream));
             const size_t at = sums.size();
             sums.resize(at + static_cast<size_t>(chunk));
             HIP_CHECK(hipMemcpyAsync(sums.data() + at, s->rms_ring, sizeof(double) * chunk, hipMemcpyDeviceToHost, s->stream));
@@ -2022,9 +1982,9 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             code = s->read_error(nullptr, &seq);                           // synchronises
             if (att1) {
                 float ms = 0.f;
-                HIP_CHECK(hipEventElapsedTime(&ms, att0, att1));
+                HIP_CHECK(hipEventElapsedTime(&ms, att0.get(), att1.get()));
                 s->att_total += double(ms) * 1e-3;
-                s->free_events.push_back(att0); s->free_events.push_back(att1);
+                s->free_events.push_back(std::move(att0)); s->free_events.push_back(std::move(att1));
             }
             if (code != MGCFD_OK) {
                 // the reference exits inside the failing time_step: stop here, and say in which cycle it was when
@@ -2187,7 +2147,7 @@ int mgcfd_halo_plan(mgcfd_solver *s, int level, int64_t n, const int64_t *node_i
             if (node_ids[k] < 0 || node_ids[k] >= lv.info.nel) throw std::invalid_argument("halo node id out of range");
             ids[static_cast<size_t>(k)] = lv.plan.new_of_old[static_cast<size_t>(node_ids[k])];
         }
-        lv.halo_plans.emplace_back(dev_upload(ids), n);
+        lv.halo_plans.emplace_back(lv.mem.upload(ids), n);
         *plan = static_cast<int>(lv.halo_plans.size()) - 1;
     });
 }
@@ -2286,22 +2246,22 @@ int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_secon
     return guarded([&] {
         s->use_device();
         DeviceLevel &lv = s->level(level);
-        hipEvent_t a = s->get_event(), b = s->get_event();
+        Event a = s->get_event(), b = s->get_event();
         const int variant = s->variant_for(lv);
         if ((variant & 4) && !lv.dp.edge_flux)
-            lv.dp.edge_flux = dev_alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
+            lv.dp.edge_flux = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
         auto go = [&] {
             s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, variant, nullptr, nullptr);
         };
         go();
-        HIP_CHECK(hipEventRecord(a, s->stream));
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
         for (int k = 0; k < launches; k++) go();
-        HIP_CHECK(hipEventRecord(b, s->stream));
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
         float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        s->free_events.push_back(a);
-        s->free_events.push_back(b);
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
         lv.fluxes_zero = false;
         *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
@@ -2316,20 +2276,20 @@ int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *av
         s->use_device();
         DeviceLevel &lv = s->level(level);
         s->settle_fluxes(lv);
-        hipEvent_t a = s->get_event(), b = s->get_event();
+        Event a = s->get_event(), b = s->get_event();
         const int variant = s->variant_for(lv);
         auto go = [&] {
             s->k().indirect_rw(s->stream, lv.dp, lv.q, lv.fluxes, variant);
         };
         go();
-        HIP_CHECK(hipEventRecord(a, s->stream));
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
         for (int k = 0; k < launches; k++) go();
-        HIP_CHECK(hipEventRecord(b, s->stream));
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
         float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        s->free_events.push_back(a);
-        s->free_events.push_back(b);
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
         lv.fluxes_zero = false;
         *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
@@ -2346,20 +2306,20 @@ int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double 
         DeviceLevel &lv = s->level(level);
         s->settle_fluxes(lv);
         const int64_t rd_total = (5 * int64_t(lv.info.n_internal) + 5 * lv.dp.nel + 1) & ~int64_t(1), wr_total = 5 * lv.dp.nel;
-        double *src = dev_alloc<double>(static_cast<size_t>(rd_total) + 512);
+        DeviceOwner scratch;
+        double *src = scratch.alloc<double>(static_cast<size_t>(rd_total) + 512);
         HIP_CHECK(hipMemsetAsync(src, 0, (static_cast<size_t>(rd_total) + 512) * sizeof(double), s->stream));
-        hipEvent_t a = s->get_event(), b = s->get_event();
+        Event a = s->get_event(), b = s->get_event();
         auto go = [&] { exact::launch_stream_tiles(s->stream, lv.dp.n_tiles, src, lv.fluxes, rd_total, wr_total); };
         go();
-        HIP_CHECK(hipEventRecord(a, s->stream));
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
         for (int k = 0; k < launches; k++) go();
-        HIP_CHECK(hipEventRecord(b, s->stream));
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
         float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        s->free_events.push_back(a);
-        s->free_events.push_back(b);
-        HIP_CHECK(hipFree(src));
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
         lv.fluxes_zero = false;
         *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
@@ -2424,24 +2384,11 @@ void rccl_load()
 
 } // namespace
 
-// what a solver knows about the ranks around it
-struct mgcfd_comm {
-    int rank = 0, world = 1;
-    void *rccl = nullptr;                         // ncclComm_t (one rank per process)
-    struct mgcfd_group *group = nullptr;          // or: the in-process group this solver is rank `rank` of
-};
-struct mgcfd_group {
-    std::vector<mgcfd_solver *> ranks;
-    bool peer_ok = true;                          // every device of the group can address every other one's memory (direct mode stores into it)
-};
-
-static std::map<mgcfd_solver *, mgcfd_comm> g_comms;     // (one host thread per solver; groups are driven by one thread)
 
 static mgcfd_comm &comm_of(mgcfd_solver *s)
 {
-    auto it = g_comms.find(s);
-    if (it == g_comms.end()) throw std::invalid_argument("the solver is not a rank of anything: call mgcfd_rank_attach_rccl or mgcfd_group_create first");
-    return it->second;
+    if (!s->comm) throw std::invalid_argument("the solver is not a rank of anything: call mgcfd_rank_attach_rccl or mgcfd_group_create first");
+    return *s->comm;
 }
 
 // mgcfd_set_free_stream: whatever else may still touch this solver's memory or replay launches captured for it is idle too —
@@ -2449,16 +2396,16 @@ static mgcfd_comm &comm_of(mgcfd_solver *s)
 // and a group's sweep graph, kept by rank 0, holds every rank's launches: it goes as well)
 static void synchronize_with_group(mgcfd_solver *s)
 {
-    for (DeviceLevel &lv : s->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
-    auto it = g_comms.find(s);
-    if (it == g_comms.end() || !it->second.group) return;
-    for (mgcfd_solver *r : it->second.group->ranks) {
+    for (DeviceLevel &lv : s->L) if (lv.hx) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream.get()));
+    if (!s->comm || !s->comm->group) return;
+    mgcfd_group *const g = s->comm->group;
+    for (mgcfd_solver *r : g->ranks) {
         if (r == s) continue;
         r->use_device();
         HIP_CHECK(hipStreamSynchronize(r->stream));
-        for (DeviceLevel &lv : r->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+        for (DeviceLevel &lv : r->L) if (lv.hx) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream.get()));
     }
-    mgcfd_solver *r0 = it->second.group->ranks[0];
+    mgcfd_solver *r0 = g->ranks[0];
     if (r0 != s) { r0->use_device(); r0->drop_graphs(); }
     s->use_device();
 }
@@ -2490,6 +2437,11 @@ static void build_halo(mgcfd_solver *s, int level, int n_peers, const int *peers
 {
     s->use_device();
     DeviceLevel &lv = s->level(level);
+    // other ranks hold device addresses into an exchange they have attached to or a group has prepared
+    if (lv.hx && lv.hx->ipc)
+        throw std::invalid_argument("the level's halo exchange is attached to other processes: mgcfd_rank_ipc_detach on every rank before mgcfd_rank_set_halo replaces it");
+    if (lv.hx && lv.hx->group_prepared())
+        throw std::invalid_argument("the level's halo exchange is in use by its group, whose ranks hold addresses into it: it cannot be replaced (create the solvers and the group anew)");
     auto hx = std::make_unique<HaloExchange>();
     std::vector<int32_t> sidx, ridx;
     hx->send_off.push_back(0); hx->recv_off.push_back(0);
@@ -2509,21 +2461,21 @@ static void build_halo(mgcfd_solver *s, int level, int n_peers, const int *peers
         hx->send_off.push_back(static_cast<int64_t>(sidx.size()));
         hx->recv_off.push_back(static_cast<int64_t>(ridx.size()));
     }
-    hx->send_idx = dev_upload(sidx);
-    hx->recv_idx = dev_upload(ridx);
+    hx->send_idx = hx->mem.upload(sidx);
+    hx->recv_idx = hx->mem.upload(ridx);
     hx->recv_idx_host = ridx;
-    for (int j = 0; j < 3; j++) HIP_CHECK(hipEventCreateWithFlags(&hx->bdone[j], hipEventDisableTiming));
+    for (int j = 0; j < 3; j++) hx->bdone[j] = make_event(hipEventDisableTiming);
     for (int b = 0; b < HaloExchange::kSets; b++) {
-        hx->send_buf[b] = dev_alloc<double>(sidx.size() * 5);
-        hx->recv_buf[b] = dev_alloc<double>(ridx.size() * 5);
-        HIP_CHECK(hipEventCreateWithFlags(&hx->packed[b], hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&hx->arrived[b], hipEventDisableTiming));
+        hx->send_buf[b] = hx->mem.alloc<double>(sidx.size() * 5);
+        hx->recv_buf[b] = hx->mem.alloc<double>(ridx.size() * 5);
+        hx->packed[b] = make_event(hipEventDisableTiming);
+        hx->arrived[b] = make_event(hipEventDisableTiming);
     }
-    HIP_CHECK(hipEventCreateWithFlags(&hx->reduced, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&hx->gathered, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&hx->joined, hipEventDisableTiming));
-    HIP_CHECK(hipStreamCreateWithFlags(&hx->comm_stream, hipStreamNonBlocking));
-    hx->gmin = dev_alloc<double>(static_cast<size_t>(std::max(world, 1)));
+    hx->reduced = make_event(hipEventDisableTiming);
+    hx->gathered = make_event(hipEventDisableTiming);
+    hx->joined = make_event(hipEventDisableTiming);
+    hx->comm_stream = make_stream();
+    hx->gmin = hx->mem.alloc<double>(static_cast<size_t>(std::max(world, 1)));
     // tiles next to ghosts: a tile that holds a ghost node, or an owned node with an edge to one
     std::vector<char> boundary(static_cast<size_t>(lv.plan.n_tiles), 0);
     auto tile_of = [&](int64_t original) { return lv.plan.new_of_old[static_cast<size_t>(original)] / kTile; };
@@ -2539,12 +2491,17 @@ static void build_halo(mgcfd_solver *s, int level, int n_peers, const int *peers
     }
     hx->n_boundary = static_cast<int32_t>(tb.size());
     hx->n_interior = static_cast<int32_t>(ti.size());
-    hx->tiles_boundary = dev_upload(tb);
-    hx->tiles_interior = dev_upload(ti);
+    hx->tiles_boundary = hx->mem.upload(tb);
+    hx->tiles_interior = hx->mem.upload(ti);
     {
         std::vector<int32_t> all(tb);
         all.insert(all.end(), ti.begin(), ti.end());
-        hx->tiles_all = dev_upload(all);
+        hx->tiles_all = hx->mem.upload(all);
+    }
+    if (lv.hx) {
+        // the old exchange goes: nothing of this rank may still run on it
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream.get()));
     }
     lv.hx = std::move(hx);
 }
@@ -2557,17 +2514,17 @@ static void halo_start(mgcfd_solver *s, int level, const double *field, int b)
     mgcfd_comm &c = comm_of(s);
     if (hx.total_send() > 0)
         exact::launch_halo_pack(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, field, hx.send_buf[b]);
-    HIP_CHECK(hipEventRecord(hx.packed[b], s->stream));
+    HIP_CHECK(hipEventRecord(hx.packed[b].get(), s->stream));
     if (c.rccl) {
-        HIP_CHECK(hipStreamWaitEvent(hx.comm_stream, hx.packed[b], 0));
+        HIP_CHECK(hipStreamWaitEvent(hx.comm_stream.get(), hx.packed[b].get(), 0));
         RCCL_CHECK(g_rccl.GroupStart());
         for (size_t k = 0; k < hx.peer.size(); k++) {
             const int64_t ns = hx.send_off[k + 1] - hx.send_off[k], nr = hx.recv_off[k + 1] - hx.recv_off[k];
-            if (ns > 0) RCCL_CHECK(g_rccl.Send(hx.send_buf[b] + hx.send_off[k] * 5, static_cast<size_t>(ns) * 5, Rccl::kDouble, hx.peer[k], c.rccl, hx.comm_stream));
-            if (nr > 0) RCCL_CHECK(g_rccl.Recv(hx.recv_buf[b] + hx.recv_off[k] * 5, static_cast<size_t>(nr) * 5, Rccl::kDouble, hx.peer[k], c.rccl, hx.comm_stream));
+            if (ns > 0) RCCL_CHECK(g_rccl.Send(hx.send_buf[b] + hx.send_off[k] * 5, static_cast<size_t>(ns) * 5, Rccl::kDouble, hx.peer[k], c.rccl, hx.comm_stream.get()));
+            if (nr > 0) RCCL_CHECK(g_rccl.Recv(hx.recv_buf[b] + hx.recv_off[k] * 5, static_cast<size_t>(nr) * 5, Rccl::kDouble, hx.peer[k], c.rccl, hx.comm_stream.get()));
         }
         RCCL_CHECK(g_rccl.GroupEnd());
-        HIP_CHECK(hipEventRecord(hx.arrived[b], hx.comm_stream));
+        HIP_CHECK(hipEventRecord(hx.arrived[b].get(), hx.comm_stream.get()));
     }
     // (in-process group: the copies are issued by group_deliver once every rank has packed)
 }
@@ -2590,7 +2547,7 @@ static void deliver_to(mgcfd_group *g, mgcfd_solver *dst, int level, int b, bool
         bool any = false;
         // (an exchange outside the sweeps' three-set rotation: the destination's receive buffer is free only behind its own
         //  stream's last unpack, which lies before its pack of this exchange)
-        if (behind_own_pack) HIP_CHECK(hipStreamWaitEvent(hd.comm_stream, hd.packed[b], 0));
+        if (behind_own_pack) HIP_CHECK(hipStreamWaitEvent(hd.comm_stream.get(), hd.packed[b].get(), 0));
         for (size_t k = 0; k < hd.peer.size(); k++) {
             mgcfd_solver *src = g->ranks[static_cast<size_t>(hd.peer[k])];
             HaloExchange &hs = *src->level(level).hx;
@@ -2600,14 +2557,14 @@ static void deliver_to(mgcfd_group *g, mgcfd_solver *dst, int level, int b, bool
             const int64_t n = hd.recv_off[k + 1] - hd.recv_off[k];
             if (n != hs.send_off[ks + 1] - hs.send_off[ks]) throw std::logic_error("halo message lengths of two ranks do not match");
             if (n == 0) continue;
-            HIP_CHECK(hipStreamWaitEvent(hd.comm_stream, hs.packed[b], 0));
+            HIP_CHECK(hipStreamWaitEvent(hd.comm_stream.get(), hs.packed[b].get(), 0));
             // (unified addressing + peer access: a plain device-to-device copy crosses xGMI; unlike hipMemcpyPeerAsync it can be captured)
             HIP_CHECK(hipMemcpyAsync(hd.recv_buf[b] + hd.recv_off[k] * 5, hs.send_buf[b] + hs.send_off[ks] * 5,
-                                     sizeof(double) * 5 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, hd.comm_stream));
+                                     sizeof(double) * 5 * static_cast<size_t>(n), hipMemcpyDeviceToDevice, hd.comm_stream.get()));
             any = true;
         }
-        if (!any) HIP_CHECK(hipStreamWaitEvent(hd.comm_stream, hd.packed[b], 0));     // (keeps the comm stream behind the rank's own stream)
-        HIP_CHECK(hipEventRecord(hd.arrived[b], hd.comm_stream));
+        if (!any) HIP_CHECK(hipStreamWaitEvent(hd.comm_stream.get(), hd.packed[b].get(), 0));     // (keeps the comm stream behind the rank's own stream)
+        HIP_CHECK(hipEventRecord(hd.arrived[b].get(), hd.comm_stream.get()));
     }
 }
 
@@ -2616,7 +2573,7 @@ static void halo_finish(mgcfd_solver *s, int level, double *field, int b)
 {
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
-    HIP_CHECK(hipStreamWaitEvent(s->stream, hx.arrived[b], 0));
+    HIP_CHECK(hipStreamWaitEvent(s->stream, hx.arrived[b].get(), 0));
     if (hx.total_recv() > 0)
         exact::launch_halo_unpack(s->stream, hx.total_recv(), lv.dp.stride, hx.recv_idx, hx.recv_buf[b], field);
 }
@@ -2733,6 +2690,28 @@ static bool group_direct_wanted()
     return on;
 }
 
+// every rank's two words for its time-step minimum (HaloExchange::min_par) and, on every rank, where all of them lie
+static void group_ensure_min_words(mgcfd_group *g, int level)
+{
+    for (mgcfd_solver *s : g->ranks) {
+        HaloExchange &hx = *s->level(level).hx;
+        if (hx.min_par) continue;
+        s->use_device();
+        hx.min_par = hx.mem.alloc<double>(2);
+    }
+    for (mgcfd_solver *s : g->ranks) {
+        HaloExchange &hx = *s->level(level).hx;
+        if (hx.peer_scalars[1]) continue;
+        s->use_device();
+        for (int par = 0; par < 2; par++) {
+            std::vector<const double *> ptrs;
+            for (mgcfd_solver *src : g->ranks) ptrs.push_back(src->level(level).hx->min_par + par);
+            hx.mem.release(hx.peer_scalars[par]);           // (of an earlier call that threw before the second list)
+            hx.peer_scalars[par] = hx.mem.upload(ptrs);
+        }
+    }
+}
+
 // build the push targets of every rank (once; allocations and uploads never happen inside a sweep)
 static void group_prepare_direct(mgcfd_group *g, int level)
 {
@@ -2761,7 +2740,8 @@ static void group_prepare_direct(mgcfd_group *g, int level)
             for (int64_t i = 0; i < n; i++)
                 target[static_cast<size_t>(hs.send_off[k] + i)] = hd.recv_idx_host[static_cast<size_t>(hd.recv_off[kd] + i)];
         }
-        hs.push_target = dev_upload(target);
+        hs.mem.release(hs.push_target);                     // (of an earlier call that threw at a later rank)
+        hs.push_target = hs.mem.upload(target);
     }
     for (mgcfd_solver *s : g->ranks) s->level(level).hx->direct = true;
 }
@@ -2789,13 +2769,13 @@ static void push_and_record(mgcfd_solver *s, int level, const double *field, con
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
     if (hx.total_send() > 0) exact::launch_halo_push(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, hx.push_target, field, pp);
-    HIP_CHECK(hipEventRecord(hx.bdone[ev], s->stream));
+    HIP_CHECK(hipEventRecord(hx.bdone[ev].get(), s->stream));
 }
 
 static void wait_for_peers(mgcfd_group *g, mgcfd_solver *s, int level, int ev)
 {
     HaloExchange &hx = *s->level(level).hx;
-    for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->bdone[ev], 0));
+    for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->bdone[ev].get(), 0));
 }
 
 // the time step of an in-process group's sweep: the first stage takes the minimum over the group's minima (hx.gmin)
@@ -2866,14 +2846,14 @@ static void group_sweeps_threaded(mgcfd_group *g, int level, int sweeps, bool wi
             const int par = hx.min_parity;
             step([&] {
                 sweep_first_half(s, level, hx.min_par + par);
-                if (global_dt) HIP_CHECK(hipEventRecord(hx.reduced, s->stream));
+                if (global_dt) HIP_CHECK(hipEventRecord(hx.reduced.get(), s->stream));
             });
             hx.min_parity = par ^ 1;
             bar.wait();
             PushPeers to[MGCFD_RK];
             step([&] {
                 if (global_dt) {
-                    for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced, 0));
+                    for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced.get(), 0));
                     exact::launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
                 }
                 // the peers' buffers of this sweep's three stages, read while nobody rotates (a rank rotates in its last stage's
@@ -2912,11 +2892,11 @@ static void group_sweep_once(mgcfd_group *g, int level)
     if (global_dt) {
         // all-reduce(MIN) of one fp64 over the group: behind every rank's reduction event each rank reads the others'
         // scalars itself (k_min_over_peers: 8-byte loads over xGMI) — no message, no second stream
-        for (mgcfd_solver *src : g->ranks) { src->use_device(); HIP_CHECK(hipEventRecord(src->level(level).hx->reduced, src->stream)); }
+        for (mgcfd_solver *src : g->ranks) { src->use_device(); HIP_CHECK(hipEventRecord(src->level(level).hx->reduced.get(), src->stream)); }
         for (mgcfd_solver *dst : g->ranks) {
             dst->use_device();
             HaloExchange &hd = *dst->level(level).hx;
-            for (mgcfd_solver *src : g->ranks) if (src != dst) HIP_CHECK(hipStreamWaitEvent(dst->stream, src->level(level).hx->reduced, 0));
+            for (mgcfd_solver *src : g->ranks) if (src != dst) HIP_CHECK(hipStreamWaitEvent(dst->stream, src->level(level).hx->reduced.get(), 0));
             exact::launch_min_over_peers(dst->stream, hd.peer_scalars[par], n, hd.gmin);
         }
     }
@@ -2943,7 +2923,7 @@ static void group_sweep_once(mgcfd_group *g, int level)
 // from and joined to the capturing stream.  Returns false (and leaves everything eager) when capture is not possible.
 template <typename Body>
 static bool capture_sweep(hipStream_t origin, const std::vector<std::pair<hipStream_t, hipEvent_t>> &others, hipEvent_t fork, Body &&body,
-                          hipGraphExec_t *exec)
+                          GraphExec &exec)
 {
     hipGraph_t graph = nullptr;
     if (hipStreamBeginCapture(origin, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -2957,8 +2937,10 @@ static bool capture_sweep(hipStream_t origin, const std::vector<std::pair<hipStr
         ok = false;
     }
     if (hipStreamEndCapture(origin, &graph) != hipSuccess || !graph) { (void)hipGetLastError(); ok = false; }
-    if (ok && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); *exec = nullptr; ok = false; }
+    hipGraphExec_t made = nullptr;
+    if (ok && hipGraphInstantiate(&made, graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); made = nullptr; ok = false; }
     if (graph) (void)hipGraphDestroy(graph);
+    exec = adopt_graph_exec(made);
     return ok;
 }
 
@@ -3101,7 +3083,7 @@ int mgcfd_rank_attach_rccl(mgcfd_solver *s, int rank, int world, const void *id1
         mgcfd_comm c;
         c.rank = rank; c.world = world;
         RCCL_CHECK(g_rccl.CommInitRank(&c.rccl, world, id, rank));
-        g_comms[s] = c;
+        s->comm = c;
     });
 }
 
@@ -3114,7 +3096,7 @@ int mgcfd_rank_attach_plain(mgcfd_solver *s, int rank, int world)
         if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
         mgcfd_comm c;
         c.rank = rank; c.world = world;
-        g_comms[s] = c;
+        s->comm = c;
     });
 }
 
@@ -3139,22 +3121,20 @@ int mgcfd_rank_ipc_export(mgcfd_solver *s, int level, void *out)
         if (static_cast<int>(hx.peer.size()) > kMaxPushPeers) throw std::invalid_argument("more neighbouring ranks than a push addresses (8)");
         if (lv.n_owned < lv.info.nel && !lv.plan.ghosts_last) throw std::invalid_argument("the level's plan mixes ghosts into the tiles");
         if (!hx.flags) {
-            // the words other devices write and this one polls: fine-grained device memory (not cached across the writes of
-            // another agent) where the runtime grants it, ordinary device memory otherwise
-            auto fine = [](size_t bytes) {
-                void *m = nullptr;
-                if (hipExtMallocWithFlags(&m, bytes, hipDeviceMallocFinegrained) != hipSuccess || !m) { (void)hipGetLastError(); HIP_CHECK(hipMalloc(&m, bytes)); }
-                return m;
-            };
-            hx.flags = static_cast<unsigned long long *>(fine(sizeof(unsigned long long) * kMaxIpcRanks * 4));
-            HIP_CHECK(hipMemset(hx.flags, 0, sizeof(unsigned long long) * kMaxIpcRanks * 4));
-            hx.gmins = static_cast<double *>(fine(sizeof(double) * 2 * kMaxIpcRanks));
+            // the words other devices write and this one polls; made under an owner of their own, so that a failure leaves
+            // the exchange without any of them
+            DeviceOwner made;
+            auto *flags = static_cast<unsigned long long *>(made.alloc_fine_grained(sizeof(unsigned long long) * kMaxIpcRanks * 4));
+            HIP_CHECK(hipMemset(flags, 0, sizeof(unsigned long long) * kMaxIpcRanks * 4));
+            auto *gmins = static_cast<double *>(made.alloc_fine_grained(sizeof(double) * 2 * kMaxIpcRanks));
             const std::vector<double> inf(2 * kMaxIpcRanks, std::numeric_limits<double>::infinity());
-            HIP_CHECK(hipMemcpy(hx.gmins, inf.data(), sizeof(double) * inf.size(), hipMemcpyHostToDevice));
-            hx.ticket = dev_alloc<unsigned>(1);
-            HIP_CHECK(hipMemset(hx.ticket, 0, sizeof(unsigned)));
-            hx.ipc_timeouts = dev_alloc<int>(1);
-            HIP_CHECK(hipMemset(hx.ipc_timeouts, 0, sizeof(int)));
+            HIP_CHECK(hipMemcpy(gmins, inf.data(), sizeof(double) * inf.size(), hipMemcpyHostToDevice));
+            auto *ticket = made.alloc<unsigned>(1);
+            HIP_CHECK(hipMemset(ticket, 0, sizeof(unsigned)));
+            auto *timeouts = made.alloc<int>(1);
+            HIP_CHECK(hipMemset(timeouts, 0, sizeof(int)));
+            hx.mem.absorb(std::move(made));
+            hx.flags = flags; hx.gmins = gmins; hx.ticket = ticket; hx.ipc_timeouts = timeouts;
         }
         IpcExportHeader h{};
         for (int k = 0; k < 3; k++) HIP_CHECK(hipIpcGetMemHandle(&h.state[k], lv.state[k]));
@@ -3189,10 +3169,8 @@ int mgcfd_rank_ipc_attach(mgcfd_solver *s, int level, int n_exports, const void 
         std::vector<int32_t> target(static_cast<size_t>(hx.total_send()), 0);
         std::vector<char> peer_seen(hx.peer.size(), 0), rank_seen(static_cast<size_t>(c.world), 0);
         auto open = [&](const hipIpcMemHandle_t &h) {
-            void *m = nullptr;
-            HIP_CHECK(hipIpcOpenMemHandle(&m, h, hipIpcMemLazyEnablePeerAccess));
-            hx.ipc_opened.push_back(m);
-            return m;
+            hx.ipc_opened.push_back(open_ipc_mapping(h));
+            return hx.ipc_opened.back().get();
         };
         for (int e = 0; e < n_exports; e++) {
             IpcExportHeader h;
@@ -3225,8 +3203,8 @@ int mgcfd_rank_ipc_attach(mgcfd_solver *s, int level, int n_exports, const void 
         int others = 0;
         for (char seen : rank_seen) others += seen;
         hx.ipc_all = others == c.world - 1;
-        if (hx.push_target) { HIP_CHECK(hipFree(hx.push_target)); hx.push_target = nullptr; }
-        hx.push_target = dev_upload(target);
+        hx.mem.release(hx.push_target);
+        hx.push_target = hx.mem.upload(target);
         {   // the same message per node (library numbering): what a stage that sends its own message walks (StagePush)
             std::vector<int32_t> sidx(static_cast<size_t>(hx.total_send()));
             HIP_CHECK(hipMemcpy(sidx.data(), hx.send_idx, sizeof(int32_t) * sidx.size(), hipMemcpyDeviceToHost));
@@ -3241,11 +3219,13 @@ int mgcfd_rank_ipc_attach(mgcfd_solver *s, int level, int n_exports, const void 
                     peer[static_cast<size_t>(at)] = static_cast<int8_t>(k);
                     tgt[static_cast<size_t>(at)] = target[static_cast<size_t>(m)];
                 }
-            for (void *old : {static_cast<void *>(hx.node_send_ptr), static_cast<void *>(hx.node_send_target), static_cast<void *>(hx.node_send_peer)}) if (old) HIP_CHECK(hipFree(old));
-            hx.node_send_ptr = dev_upload(ptr);
+            hx.mem.release(hx.node_send_ptr);
+            hx.mem.release(hx.node_send_target);
+            hx.mem.release(hx.node_send_peer);
+            hx.node_send_ptr = hx.mem.upload(ptr);
             if (tgt.empty()) { tgt.push_back(0); peer.push_back(0); }
-            hx.node_send_target = dev_upload(tgt);
-            hx.node_send_peer = dev_upload(peer);
+            hx.node_send_target = hx.mem.upload(tgt);
+            hx.node_send_peer = hx.mem.upload(peer);
         }
         hx.ipc = true;
     });
@@ -3261,7 +3241,6 @@ int mgcfd_rank_ipc_detach(mgcfd_solver *s, int level)
         if (!lv.hx || !lv.hx->ipc) return;
         HaloExchange &hx = *lv.hx;
         HIP_CHECK(hipStreamSynchronize(s->stream));
-        for (void *m : hx.ipc_opened) (void)hipIpcCloseMemHandle(m);
         hx.ipc_opened.clear();
         hx.ipc = false;
         hx.ipc_all = false;
@@ -3290,10 +3269,9 @@ int mgcfd_rank_detach(mgcfd_solver *s)
 {
     REQUIRE(s);
     return guarded([&] {
-        auto it = g_comms.find(s);
-        if (it == g_comms.end()) return;
-        if (it->second.rccl) { s->use_device(); (void)hipStreamSynchronize(s->stream); (void)g_rccl.CommDestroy(it->second.rccl); }
-        g_comms.erase(it);
+        if (!s->comm) return;
+        if (s->comm->rccl) { s->use_device(); (void)hipStreamSynchronize(s->stream); (void)g_rccl.CommDestroy(s->comm->rccl); }
+        s->comm.reset();
     });
 }
 
@@ -3375,7 +3353,7 @@ int mgcfd_rank_sweeps(mgcfd_solver *s, int level, int sweeps)
                     int64_t before[MGCFD_NUM_LOOPS];
                     std::memcpy(before, lv.iters, sizeof(before));
                     const int rot_before = lv.rot;
-                    const bool ok = capture_sweep(s->stream, {}, hx.joined, [&] { rank_sweep_once(s, level); }, &hx.sweep_graph[rot]);
+                    const bool ok = capture_sweep(s->stream, {}, hx.joined.get(), [&] { rank_sweep_once(s, level); }, hx.sweep_graph[rot]);
                     s->force_check = -1;
                     if (!ok) {                              // nothing ran: put the host state back and go on eagerly
                         hx.graph_failed = true;
@@ -3389,7 +3367,7 @@ int mgcfd_rank_sweeps(mgcfd_solver *s, int level, int sweeps)
                     lv.rot = rot_before; lv.apply_rot();    // (the capture advanced the host state without running anything)
                     lv.min_ahead = ahead_before;
                 }
-                HIP_CHECK(hipGraphLaunch(hx.sweep_graph[rot], s->stream));
+                HIP_CHECK(hipGraphLaunch(hx.sweep_graph[rot].get(), s->stream));
                 hx.sweeps_replayed++;
                 after_replayed_sweep(s, level, hx.graph_iters[rot]);
             } else {
@@ -3442,7 +3420,7 @@ int mgcfd_group_create(int n, mgcfd_solver *const *solvers, mgcfd_group **out)
         for (int r = 0; r < n; r++) {
             mgcfd_comm c;
             c.rank = r; c.world = n; c.group = g.get();
-            g_comms[solvers[r]] = c;
+            solvers[r]->comm = c;
         }
         *out = g.release();
     });
@@ -3451,7 +3429,7 @@ int mgcfd_group_create(int n, mgcfd_solver *const *solvers, mgcfd_group **out)
 void mgcfd_group_destroy(mgcfd_group *g)
 {
     if (!g) return;
-    for (mgcfd_solver *s : g->ranks) g_comms.erase(s);
+    for (mgcfd_solver *s : g->ranks) if (s && s->comm && s->comm->group == g) s->comm.reset();
     delete g;
 }
 
@@ -3468,7 +3446,7 @@ int mgcfd_group_set_free_stream(mgcfd_group *g, double mach, double alpha_deg, i
             s->use_device();
             s->fold_events();
             HIP_CHECK(hipStreamSynchronize(s->stream));
-            for (DeviceLevel &lv : s->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+            for (DeviceLevel &lv : s->L) if (lv.hx) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream.get()));
             s->drop_graphs();
         }
         for (mgcfd_solver *s : g->ranks) apply_free_stream(s, ff17, mach, alpha_deg, reinitialise);
@@ -3485,7 +3463,7 @@ int mgcfd_group_set_time_step(mgcfd_group *g, int mode, double cfl)
             s->use_device();
             s->fold_events();
             HIP_CHECK(hipStreamSynchronize(s->stream));
-            for (DeviceLevel &lv : s->L) if (lv.hx && lv.hx->comm_stream) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream));
+            for (DeviceLevel &lv : s->L) if (lv.hx) HIP_CHECK(hipStreamSynchronize(lv.hx->comm_stream.get()));
             s->drop_graphs();
         }
         for (mgcfd_solver *s : g->ranks) apply_time_step(s, mode, cfl);
@@ -3532,22 +3510,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
             if (!lv.hx) throw std::invalid_argument("a rank has no halo lists: call mgcfd_rank_set_halo first");
             s->settle_fluxes(lv);
         }
-        for (mgcfd_solver *s : g->ranks) {                  // (allocations and uploads: never inside a capture)
-            HaloExchange &hx = *s->level(level).hx;
-            if (hx.min_par) continue;
-            s->use_device();
-            hx.min_par = dev_alloc<double>(2);
-        }
-        for (mgcfd_solver *s : g->ranks) {
-            HaloExchange &hx = *s->level(level).hx;
-            if (hx.peer_scalars[0]) continue;
-            s->use_device();
-            for (int par = 0; par < 2; par++) {
-                std::vector<const double *> ptrs;
-                for (mgcfd_solver *src : g->ranks) ptrs.push_back(src->level(level).hx->min_par + par);
-                hx.peer_scalars[par] = dev_upload(ptrs);
-            }
-        }
+        group_ensure_min_words(g, level);               // (allocations and uploads: never inside a capture)
         group_prepare_direct(g, level);
         HaloExchange &h0 = *s0->level(level).hx;
         bool timing = false;
@@ -3580,7 +3543,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
             if (rms_out)
                 for (mgcfd_solver *s : g->ranks) {
                     s->use_device();
-                    if (!s->rms_ring) { s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing); s->rms_count = dev_alloc<int>(1); }
+                    ensure_rms_ring(s);
                     HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
                 }
             if (threaded) group_sweeps_threaded(g, level, sweeps, rms_out != nullptr);
@@ -3622,8 +3585,8 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
             for (mgcfd_solver *s : g->ranks) {
                 if (s == s0) continue;
                 s->use_device();
-                HIP_CHECK(hipEventRecord(s->level(level).hx->joined, s->stream));
-                HIP_CHECK(hipStreamWaitEvent(s0->stream, s->level(level).hx->joined, 0));
+                HIP_CHECK(hipEventRecord(s->level(level).hx->joined.get(), s->stream));
+                HIP_CHECK(hipStreamWaitEvent(s0->stream, s->level(level).hx->joined.get(), 0));
             }
         }
         bool replayed = false;
@@ -3641,10 +3604,10 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
                         DeviceLevel &lv = s->level(level);
                         before.emplace_back(lv.iters, lv.iters + MGCFD_NUM_LOOPS);
                         rot_before.push_back(lv.rot);
-                        if (s != s0) others.emplace_back(s->stream, lv.hx->joined);
+                        if (s != s0) others.emplace_back(s->stream, lv.hx->joined.get());
                     }
                     s0->use_device();
-                    const bool ok = capture_sweep(s0->stream, others, h0.joined, [&] { group_sweep_once(g, level); }, &h0.sweep_graph[rot]);
+                    const bool ok = capture_sweep(s0->stream, others, h0.joined.get(), [&] { group_sweep_once(g, level); }, h0.sweep_graph[rot]);
                     for (size_t r = 0; r < g->ranks.size(); r++) {
                         mgcfd_solver *s = g->ranks[r];
                         DeviceLevel &lv = s->level(level);
@@ -3657,7 +3620,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
                     if (!ok) { h0.graph_failed = true; group_sweep_once(g, level); continue; }
                 }
                 s0->use_device();
-                HIP_CHECK(hipGraphLaunch(h0.sweep_graph[rot], s0->stream));
+                HIP_CHECK(hipGraphLaunch(h0.sweep_graph[rot].get(), s0->stream));
                 replayed = true;
                 for (mgcfd_solver *s : g->ranks) { after_replayed_sweep(s, level, s->level(level).hx->graph_iters[rot]); s->level(level).hx->min_parity ^= 1; }
             } else {
@@ -3669,8 +3632,8 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
         if (replayed) {
             // ... and what the other ranks' streams are given next must wait for the graphs
             s0->use_device();
-            HIP_CHECK(hipEventRecord(h0.joined, s0->stream));
-            for (mgcfd_solver *s : g->ranks) if (s != s0) { s->use_device(); HIP_CHECK(hipStreamWaitEvent(s->stream, h0.joined, 0)); }
+            HIP_CHECK(hipEventRecord(h0.joined.get(), s0->stream));
+            for (mgcfd_solver *s : g->ranks) if (s != s0) { s->use_device(); HIP_CHECK(hipStreamWaitEvent(s->stream, h0.joined.get(), 0)); }
         }
     });
 }
@@ -3729,22 +3692,7 @@ static void group_prepare_level(mgcfd_group *g, int level)
         if (!lv.hx) throw std::invalid_argument("a rank has no halo lists on level " + std::to_string(level) + ": call mgcfd_rank_set_halo for every level");
         s->settle_fluxes(lv);
     }
-    for (mgcfd_solver *s : g->ranks) {                      // (allocations and uploads: never inside a sweep)
-        HaloExchange &hx = *s->level(level).hx;
-        if (hx.min_par) continue;
-        s->use_device();
-        hx.min_par = dev_alloc<double>(2);
-    }
-    for (mgcfd_solver *s : g->ranks) {
-        HaloExchange &hx = *s->level(level).hx;
-        if (hx.peer_scalars[0]) continue;
-        s->use_device();
-        for (int par = 0; par < 2; par++) {
-            std::vector<const double *> ptrs;
-            for (mgcfd_solver *src : g->ranks) ptrs.push_back(src->level(level).hx->min_par + par);
-            hx.peer_scalars[par] = dev_upload(ptrs);
-        }
-    }
+    group_ensure_min_words(g, level);                       // (allocations and uploads: never inside a sweep)
     group_prepare_direct(g, level);
 }
 
@@ -3761,7 +3709,7 @@ static void group_exchange_array(mgcfd_group *g, int level, int which)
         s->settle_residuals(lv);
         // this rank's send buffer is free behind the copies the peers made out of it (their `arrived` of the last use of the
         // set); and in direct mode nobody's last push into this rank's ghosts may still be on its way when the unpack writes them
-        for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->arrived[b], 0));
+        for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->arrived[b].get(), 0));
         if (hx.direct) wait_for_peers(g, s, level, 2);
         int nc = 0;
         halo_start(s, level, array_ptr(lv, which, &nc), b);
@@ -3792,23 +3740,19 @@ static RankLoads &rank_loads_of(mgcfd_solver *s, int level, int rank)
     return *lv.rl;
 }
 
-static hipEvent_t loads_event()
-{
-    hipEvent_t e = nullptr;
-    HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return e;
-}
-
 // the gathering rank's table (pad lanes zero, and they stay zero: slots lie below `total`), partial sums and ticket
 static void loads_gather_alloc(RankLoads &r0)
 {
     if (r0.table || r0.total == 0) return;
     r0.row = (r0.total + 255) / 256 * 256;
-    r0.table = dev_alloc<double>(static_cast<size_t>(6 * r0.row));
-    HIP_CHECK(hipMemset(r0.table, 0, sizeof(double) * static_cast<size_t>(6 * r0.row)));
-    r0.partial = dev_alloc<double>(static_cast<size_t>(6 * (r0.row / 256)));
-    r0.ticket = dev_alloc<unsigned>(1);
-    HIP_CHECK(hipMemset(r0.ticket, 0, sizeof(unsigned)));
+    DeviceOwner made;                                   // (all three or none: r0.table says whether this has been done)
+    double *table = made.alloc<double>(static_cast<size_t>(6 * r0.row));
+    HIP_CHECK(hipMemset(table, 0, sizeof(double) * static_cast<size_t>(6 * r0.row)));
+    double *partial = made.alloc<double>(static_cast<size_t>(6 * (r0.row / 256)));
+    unsigned *ticket = made.alloc<unsigned>(1);
+    HIP_CHECK(hipMemset(ticket, 0, sizeof(unsigned)));
+    r0.mem.absorb(std::move(made));
+    r0.table = table; r0.partial = partial; r0.ticket = ticket;
 }
 
 static LoadsTerms loads_terms_of(mgcfd_solver *s, DeviceLevel &lv, const int32_t *slot, double *table, int64_t row)
@@ -3862,11 +3806,11 @@ static void group_loads_prepare(mgcfd_group *g, int level, const double *ref_poi
         s->use_device();
         loads_upload_ref(s, ref_point);
         RankLoads &rl = *s->level(level).rl;
-        if (!rl.terms) rl.terms = loads_event();
+        if (!rl.terms) rl.terms = make_event(hipEventDisableTiming);
     }
     g->ranks[0]->use_device();
     loads_gather_alloc(r0);
-    if (!r0.read) r0.read = loads_event();
+    if (!r0.read) r0.read = make_event(hipEventDisableTiming);
 }
 
 // One rank's part of an evaluation (on its device): its terms into rank 0's table, behind the reduce that read the table
@@ -3877,9 +3821,9 @@ static void group_loads_terms(mgcfd_group *g, mgcfd_solver *s, int level)
     RankLoads &r0 = *s0->level(level).rl;
     if (r0.total == 0) return;
     DeviceLevel &lv = s->level(level);
-    if (s != s0) HIP_CHECK(hipStreamWaitEvent(s->stream, r0.read, 0));      // (rank 0's own stream is behind its reduce anyway)
+    if (s != s0) HIP_CHECK(hipStreamWaitEvent(s->stream, r0.read.get(), 0));      // (rank 0's own stream is behind its reduce anyway)
     exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, lv.rl->slot, r0.table, r0.row));
-    HIP_CHECK(hipEventRecord(lv.rl->terms, s->stream));
+    HIP_CHECK(hipEventRecord(lv.rl->terms.get(), s->stream));
 }
 
 // ... and rank 0's (on its device, every rank's terms event of this evaluation recorded): the reduce behind all of them
@@ -3888,9 +3832,9 @@ static void group_loads_reduce(mgcfd_group *g, int level, bool to_ring)
     mgcfd_solver *s0 = g->ranks[0];
     RankLoads &r0 = *s0->level(level).rl;
     if (r0.total == 0) return;
-    for (mgcfd_solver *s : g->ranks) if (s != s0) HIP_CHECK(hipStreamWaitEvent(s0->stream, s->level(level).rl->terms, 0));
+    for (mgcfd_solver *s : g->ranks) if (s != s0) HIP_CHECK(hipStreamWaitEvent(s0->stream, s->level(level).rl->terms.get(), 0));
     loads_reduce(s0, r0, to_ring);
-    HIP_CHECK(hipEventRecord(r0.read, s0->stream));
+    HIP_CHECK(hipEventRecord(r0.read.get(), s0->stream));
 }
 
 static void group_loads_once(mgcfd_group *g, int level, bool to_ring)
@@ -3961,14 +3905,14 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms, boo
             const int par = hx.min_parity;
             step([&] {
                 sweep_first_half(s, level, hx.min_par + par);
-                if (global_dt) HIP_CHECK(hipEventRecord(hx.reduced, s->stream));
+                if (global_dt) HIP_CHECK(hipEventRecord(hx.reduced.get(), s->stream));
             });
             hx.min_parity = par ^ 1;
             bar.wait();
             PushPeers to[MGCFD_RK];
             step([&] {
                 if (global_dt) {
-                    for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced, 0));
+                    for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced.get(), 0));
                     exact::launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
                 }
                 for (int j = 0; j < MGCFD_RK; j++) to[j] = make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_buffers(pl, j).out; });
@@ -3987,7 +3931,7 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms, boo
             HaloExchange &hx = *lv.hx;
             step([&] {
                 s->settle_residuals(lv);
-                for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->arrived[b], 0));
+                for (int p : hx.peer) HIP_CHECK(hipStreamWaitEvent(s->stream, g->ranks[static_cast<size_t>(p)]->level(level).hx->arrived[b].get(), 0));
                 wait_for_peers(g, s, level, 2);
                 int nc = 0;
                 halo_start(s, level, array_ptr(lv, which, &nc), b);
@@ -4062,12 +4006,12 @@ static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const 
             group_loads_prepare(g, 0, ref_point);
             mgcfd_solver *s0 = g->ranks[0];
             s0->use_device();
-            if (!s0->loads_ring) s0->loads_ring = dev_alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+            ensure_loads_ring(s0);
         }
         const bool with_loads = loads_out != nullptr;
         for (mgcfd_solver *s : g->ranks) {
             s->use_device();
-            if (!s->rms_ring) { s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing); s->rms_count = dev_alloc<int>(1); }
+            ensure_rms_ring(s);
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
         }
         // A host thread per rank where every level runs the direct form and every rank has a device of its own: one thread
@@ -4170,13 +4114,11 @@ static void rank_loads_prepare(mgcfd_solver *s, int level, const double *ref_poi
     if (rl.checked) return;
     const size_t w = static_cast<size_t>(c.world), me = static_cast<size_t>(c.rank);
     auto all_sum = [&](std::vector<double> &v) {
-        double *d = dev_upload(v);
-        try {
-            RCCL_CHECK(g_rccl.AllReduce(d, d, v.size(), Rccl::kDouble, Rccl::kSum, c.rccl, s->stream));
-            HIP_CHECK(hipMemcpyAsync(v.data(), d, sizeof(double) * v.size(), hipMemcpyDeviceToHost, s->stream));
-            HIP_CHECK(hipStreamSynchronize(s->stream));
-        } catch (...) { (void)hipFree(d); throw; }
-        (void)hipFree(d);
+        DeviceOwner scratch;
+        double *d = scratch.upload(v);
+        RCCL_CHECK(g_rccl.AllReduce(d, d, v.size(), Rccl::kDouble, Rccl::kSum, c.rccl, s->stream));
+        HIP_CHECK(hipMemcpyAsync(v.data(), d, sizeof(double) * v.size(), hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
     };
     std::vector<double> v(2 * w, 0.0);
     v[me] = double(lv.n_wall_rec); v[w + me] = double(rl.total);
@@ -4194,12 +4136,12 @@ static void rank_loads_prepare(mgcfd_solver *s, int level, const double *ref_poi
         throw std::invalid_argument("surface loads: the wall slots of the ranks on level " + std::to_string(level) + " name " + std::to_string(sum) +
                                     " of the level's " + std::to_string(rl.total) + " solid-wall edges");
     if (w > 1 && rl.total > 0) {
-        if (me == 0) { for (int32_t *p : rl.peer_slot) if (p) (void)hipFree(p); rl.peer_slot.assign(w, nullptr); }
+        if (me == 0) { for (int32_t *&p : rl.peer_slot) rl.mem.release(p); rl.peer_slot.assign(w, nullptr); }
         RCCL_CHECK(g_rccl.GroupStart());
         if (me == 0) {
             for (size_t r = 1; r < w; r++) {
                 if (rl.counts[r] == 0) continue;
-                rl.peer_slot[r] = dev_alloc<int32_t>(static_cast<size_t>(rl.counts[r]));
+                rl.peer_slot[r] = rl.mem.alloc<int32_t>(static_cast<size_t>(rl.counts[r]));
                 RCCL_CHECK(g_rccl.Recv(rl.peer_slot[r], static_cast<size_t>(rl.counts[r]), Rccl::kInt32, static_cast<int>(r), c.rccl, s->stream));
             }
         } else if (lv.n_wall_rec > 0) {
@@ -4228,7 +4170,7 @@ static void rank_loads_prepare(mgcfd_solver *s, int level, const double *ref_poi
     if (me == 0) loads_gather_alloc(rl);
     if (w > 1 && !rl.compact) {
         const int64_t n = me == 0 ? rl.total - rl.counts[0] : lv.n_wall_rec;
-        rl.compact = dev_alloc<double>(static_cast<size_t>(6 * n));
+        rl.compact = rl.mem.alloc<double>(static_cast<size_t>(6 * n));
     }
     rl.checked = true;
 }
@@ -4312,11 +4254,11 @@ static int rank_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const 
             if (lv.hx->ipc) throw std::invalid_argument("mgcfd_rank_cycles runs the buffered exchange: mgcfd_rank_ipc_detach first");
             s->settle_fluxes(lv);
         }
-        if (!s->rms_ring) { s->rms_ring = dev_alloc<double>(mgcfd_solver::kRmsRing); s->rms_count = dev_alloc<int>(1); }
+        ensure_rms_ring(s);
         HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
         if (loads_out) {
             rank_loads_prepare(s, 0, ref_point);
-            if (!s->loads_ring) s->loads_ring = dev_alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
+            ensure_loads_ring(s);
         }
         for (int k = 0; k < cycles; k++) rank_cycle_once(s, with_rms, loads_out != nullptr);
         if (loads_out && cycles > 0) {
@@ -4398,7 +4340,7 @@ int mgcfd_rank_set_wall_slots(mgcfd_solver *s, int level, int64_t n_total, int64
             rl->slot_host.push_back(slot[k]);
             slot32.push_back(static_cast<int32_t>(slot[k]));
         }
-        if (!slot32.empty()) rl->slot = dev_upload(slot32);
+        if (!slot32.empty()) rl->slot = rl->mem.upload(slot32);
         HIP_CHECK(hipStreamSynchronize(s->stream));          // (nothing in flight still reads what the old slots' arrays held)
         lv.rl = std::move(rl);
     });
@@ -4411,9 +4353,8 @@ int mgcfd_rank_info(const mgcfd_solver *s, int out[4])
 {
     REQUIRE(s); REQUIRE(out);
     out[0] = 0; out[1] = 1; out[2] = 0; out[3] = -1;
-    const auto it = g_comms.find(const_cast<mgcfd_solver *>(s));
-    if (it == g_comms.end()) return MGCFD_OK;
-    const mgcfd_comm &c = it->second;
+    if (!s->comm) return MGCFD_OK;
+    const mgcfd_comm &c = *s->comm;
     out[0] = c.rank; out[1] = c.world; out[2] = c.rccl ? 1 : (c.group ? 2 : 3);
     if (c.rccl && g_rccl.CommCount) { int n = -1; if (g_rccl.CommCount(c.rccl, &n) == 0) out[3] = n; }
     return MGCFD_OK;
@@ -4425,7 +4366,7 @@ int mgcfd_rank_graph_status(const mgcfd_solver *s, int level, int64_t out[3])
     if (level < 0 || level >= static_cast<int>(s->L.size()) || !s->L[static_cast<size_t>(level)].hx) { g_last_error = "the level has no halo lists"; return MGCFD_ERR_ARG; }
     const HaloExchange &hx = *s->L[static_cast<size_t>(level)].hx;
     out[0] = 0;
-    for (hipGraphExec_t ge : hx.sweep_graph) if (ge) out[0]++;
+    for (const GraphExec &ge : hx.sweep_graph) if (ge) out[0]++;
     out[1] = hx.graph_failed ? 1 : 0;
     out[2] = hx.sweeps_replayed;
     return MGCFD_OK;
@@ -4451,7 +4392,7 @@ static void loads_require_whole(const mgcfd_solver *s)
     if (s->partitioned)
         throw std::invalid_argument("surface loads: the solver holds a partitioned level (mgcfd_create_partitioned*); the loads over all "
                                     "ranks come from mgcfd_group_surface_loads / mgcfd_group_cycles_loads or mgcfd_rank_surface_loads / mgcfd_rank_cycles_loads");
-    if (g_comms.count(const_cast<mgcfd_solver *>(s)))
+    if (s->comm)
         throw std::invalid_argument("surface loads: the solver is attached as a rank; the loads of a partitioned level come from the group and rank calls");
 }
 

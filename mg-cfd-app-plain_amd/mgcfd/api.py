@@ -80,6 +80,7 @@ _SIGNATURES = [
     ("mgcfd_halo_pack", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     ("mgcfd_halo_unpack", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     ("mgcfd_destroy", None, [_vp]),
+    ("mgcfd_live_device_resources", C.c_int, [C.POINTER(_i64)]),
     ("mgcfd_set_option", C.c_int, [_vp, C.c_int, C.c_int]),
     ("mgcfd_level_has_edge_once", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     ("mgcfd_level_has_half_rows", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
@@ -778,6 +779,15 @@ def generated_to_levels(mg: MultigridMesh) -> List[dict]:
         out.append({"nel": lvl.nel, "volumes": lvl.volumes, "coords": lvl.coords, "edges": edges,
                     "n_internal": ni, "n_boundary": nb, "n_wall": nw, "mg_map": lvl.mg_map})
     return out
+
+
+def live_device_resources() -> dict:
+    """What the library holds on the devices in this process: allocations, their bytes, handles (streams, events, graph
+    executables, opened IPC mappings), as the library counts them itself (mgcfd_live_device_resources)."""
+    lib = load_library()
+    out = (_i64 * 3)()
+    _check(lib, lib.mgcfd_live_device_resources(out))
+    return {"allocations": int(out[0]), "bytes": int(out[1]), "handles": int(out[2])}
 
 
 def rccl_unique_id() -> bytes:
