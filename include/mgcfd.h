@@ -290,6 +290,33 @@ int mgcfd_get_free_stream(const mgcfd_solver *s, double *mach, double *alpha_deg
 enum { MGCFD_DT_REFERENCE = 0, MGCFD_DT_GLOBAL = 1, MGCFD_DT_LOCAL = 2, MGCFD_DT_LOCAL_LEGACY = 3 };
 int mgcfd_set_time_step(mgcfd_solver *s, int mode, double cfl);
 int mgcfd_get_time_step(const mgcfd_solver *s, int *mode, double *cfl);
+/* Implicit residual smoothing (Jameson): every time_step's update D_i = step_factor_i * fluxes_i is replaced by `iterations`
+ * Jacobi iterations on (1 + eps * n_i) Db_i - eps * sum_j Db_j = D_i over the level's internal edges, which raises the
+ * usable CFL number of the three-stage scheme by a factor of two or more.  No reference counterpart.  With iterations = M >= 1,
+ * stage j of every sweep of every level computes its fluxes as before (internal, solid wall, far field) and then, in place
+ * of time_step(j), with every operation one IEEE-754 double operation, never contracted to FMA under MGCFD_OPT_EXACT = 1:
+ *   D[i][v]   = sf[i] * F[i][v]                       sf: the sweep's step factors under the mgcfd_set_time_step policy
+ *   den[i]    = 1.0 + eps * (double)n_i               n_i: internal edges with i as an end point (boundary faces do not count)
+ *   Db0 = D;  for m = 1 .. M:   S[i][v] = the sum, started at +0.0, of Db(m-1)[other end][v] over the internal edges at i
+ *                               in the level's original edge order, one addition per edge;
+ *                               Db(m)[i][v] = (D[i][v] + eps * S[i][v]) / den[i]
+ *   variables[i][v] = old_variables[i][v] + Db(M)[i][v] / (double)(MGCFD_RK + 1 - j)
+ * fluxes are zero afterwards and check_for_invalid_variables runs inside the last launch, as time_step carries it; residual,
+ * RMS and everything behind the sweep are unchanged.  A stage is one standalone flux launch + M smoothing launches (the
+ * fused flux + time_step stages and captured graphs are not used while it is on; MGCFD_OPT_GRAPH is accepted and runs the
+ * same launches directly); mgcfd_time_step(s, level, j) performs the steps above; LoopNumIters counts are unchanged and the
+ * launches are timed as MGCFD_LOOP_TIME_STEP.  iterations = 0 switches it off (eps is then ignored and reported as 0): the
+ * solver launches exactly what it launched before this call existed.  The first call with iterations > 0 allocates two
+ * [5][stride] arrays per level; a solver it is never called on holds what it held before.
+ * mgcfd_set_residual_smoothing synchronises and drops every captured graph; the state stays.  MGCFD_ERR_ARG, and nothing
+ * changed: iterations < 0 or > MGCFD_MAX_SMOOTHING_ITERATIONS; with iterations > 0 a non-finite eps or eps <= 0; while a
+ * kernel-granular sweep is under way (as mgcfd_set_free_stream); with iterations > 0 on a solver made by
+ * mgcfd_create_partitioned* or attached to a group or as a rank — a level split over ranks would need a ghost exchange per
+ * Jacobi iteration, which is deliberately out of scope.  While it is on, mgcfd_sweep_begin*, mgcfd_sweep_flux0,
+ * mgcfd_sweep_stage and mgcfd_sweep_end* return MGCFD_ERR_ARG, and mgcfd_group_create and mgcfd_rank_attach_* refuse the solver. */
+#define MGCFD_MAX_SMOOTHING_ITERATIONS 8
+int mgcfd_set_residual_smoothing(mgcfd_solver *s, double eps, int iterations);
+int mgcfd_get_residual_smoothing(const mgcfd_solver *s, double *eps, int *iterations);
 
 /* ---------------------------------------------------------------------------------
  * Kernel-granular operations (asynchronous on the solver's stream)
@@ -406,6 +433,10 @@ int mgcfd_get_flux_kernel_time(mgcfd_solver *s, int level, double *avg_seconds, 
 /* Diagnostic: mean GPU time of `launches` back-to-back flux launches (internal + boundary +
  * far field, starting from zero fluxes), hipEvents around the batch on the solver's stream. */
 int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_seconds);
+/* Diagnostic: the same for `launches` back-to-back launches of one kind of residual-smoothing iteration (kind 0: the first,
+ * which forms D on load; 1: a middle one; 2: the last, which applies the update — here into the second state buffer, without
+ * check or residual, so the state stays), behind one flux launch.  MGCFD_ERR_ARG while the smoothing is off. */
+int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* The same for the indirect_rw probe (src/Kernels/indirect_rw_loop.cpp:8-78; fluxes += ..., accumulating over the
  * launches): the empirical data-movement ceiling of the flux kernel on this level's tiles. */
 int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *avg_seconds);

@@ -104,6 +104,22 @@ struct FusedStep {
     int64_t nel_active = 0;
 };
 
+// One Jacobi iteration of the implicit residual smoothing (kernels.hip: k_smooth_tile; mgcfd_set_residual_smoothing).
+struct SmoothStep {
+    const double *fluxes = nullptr;           // the stage's fluxes F [5][stride] and ...
+    const double *step_factors = nullptr;     // ... the sweep's step factors: D = step_factors * F
+    const double *prev = nullptr;             // the previous iteration's result [5][stride]; nullptr: the first iteration (starts from D)
+    double *next = nullptr;                   // this iteration's result; nullptr: the last iteration, which applies the update instead:
+    double eps = 0.0;
+    double rk_div = 1.0;                      // double(RK+1-j)
+    const double *old_variables = nullptr;
+    double *q_out = nullptr;                  // variables = old_variables + result / rk_div
+    double *residuals = nullptr;              // != nullptr: residuals = variables - old_variables
+    const int32_t *old_of_new = nullptr;
+    unsigned long long *err = nullptr;
+    int check = 0;
+};
+
 // "Add up these partial sums" as an argument: k_sum_partials does only that; k_restrict can take it along.
 struct SumTask {
     const double *partial = nullptr;      // [n]

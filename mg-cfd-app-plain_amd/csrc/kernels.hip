@@ -2213,6 +2213,124 @@ k_time_step(int64_t nel, int64_t stride, double rk_div, double *__restrict__ ste
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Implicit residual smoothing (no reference counterpart; INTEGRATION.md "Implicit residual smoothing"): one Jacobi
+// iteration of (1 + eps*n_i) Db_i - eps * sum_j Db_j = D_i over the internal edges, D_i = step_factor_i * fluxes_i.
+//   Db^m_i = (D_i + eps * S_i) / (1 + eps * n_i),   S_i = the sum of Db^(m-1) at the other ends of node i's internal edges,
+// started at +0.0 and added one edge at a time in the level's original edge order — the incidence rows' order, so the
+// per-node walk is the one k_flux_tile does: a workgroup stages the Db^(m-1) records of its 256 nodes and of their halo in
+// LDS, every lane walks its internal rows through nbr16 (a halo node beyond the table: from the overflow list in memory),
+// then — long rows — its entries of the workgroup's list, which follow the loop rows in row order (preprocess.cpp).
+//   FIRST: Db^0 = D is formed from fluxes and step_factors while it is staged (own and halo nodes alike).
+//   LAST:  time_step with Db^M in place of step_factor * fluxes: variables = old + Db^M / (RK+1-j), the residual on
+//          request and check_for_invalid_variables, as k_time_step carries them.  fluxes[] is left as it is (the
+//          solver treats it as logically zero, as after a lazy time_step): with FIRST && LAST other tiles still read it.
+// LDS: five fields of 560 doubles (22,400 B; one field per instruction, a slot's doubles 8 B apart: lanes that read
+// consecutive slots hit consecutive bank pairs — the 40-byte record of the state arrays would put two lanes in five on
+// the same pair).  44-56 registers, no scratch; seven workgroups per CU by LDS (the launch bound asks for six at least):
+// nothing here waits on arithmetic, so the loads in flight are what matters.
+// ------------------------------------------------------------------------------------------
+constexpr int kSmoothRow = 560;
+static_assert(kSmoothRow >= kTileCap, "every staged slot has a place");
+
+template <bool FIRST, bool LAST, bool TAIL>
+__global__ void __launch_bounds__(kBlock, 6)
+k_smooth_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
+              const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
+              const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf, TailPlan tp, SmoothStep a)
+{
+    __shared__ double rec[5][kSmoothRow];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
+    const int64_t i = int64_t(t) * kTile + tid;
+    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
+    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
+    const int32_t hid = hrow[tid];
+    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;
+    const int32_t row0 = slice_row0[slice];
+    const int32_t n_int = (TAIL ? tp.rows_main : rows_int)[slice];
+    const int32_t ovf0 = tile_ovf_ptr[t];
+    const int64_t hnode = hid >= 0 ? int64_t(hid) : i;                 // (no halo node: a copy of the own one in the unused slot)
+    // Db^(m-1) of node n: the previous iteration's record, or (FIRST) D = step_factor * fluxes, one multiplication
+    auto previous = [&](int64_t n, double &v0, double &v1, double &v2, double &v3, double &v4) {
+        if (FIRST) {
+            const double sf = a.step_factors[n];
+            v0 = sf * a.fluxes[n]; v1 = sf * a.fluxes[stride + n]; v2 = sf * a.fluxes[2 * stride + n];
+            v3 = sf * a.fluxes[3 * stride + n]; v4 = sf * a.fluxes[4 * stride + n];
+        } else {
+            v0 = a.prev[n]; v1 = a.prev[stride + n]; v2 = a.prev[2 * stride + n]; v3 = a.prev[3 * stride + n]; v4 = a.prev[4 * stride + n];
+        }
+    };
+    auto stage = [&](uint32_t slot, int64_t n) {
+        double v0, v1, v2, v3, v4;
+        previous(n, v0, v1, v2, v3, v4);
+        rec[0][slot] = v0; rec[1][slot] = v1; rec[2][slot] = v2; rec[3][slot] = v3; rec[4][slot] = v4;
+    };
+    uint32_t c = nbr16[(int64_t(n_int > 0 ? row0 : 0) << 6) + lane];   // (row 0 exists on every level; unused when n_int == 0)
+    stage(uint32_t(tid), i);
+    stage(uint32_t(kTile + tid), hnode);
+    if (hid2 >= 0) stage(uint32_t(kTile + kBlock + tid), hid2);
+    // the right-hand side D of the own node (FIRST: what was just staged)
+    const double sfi = a.step_factors[i];
+    const double d0 = sfi * a.fluxes[i], d1 = sfi * a.fluxes[stride + i], d2 = sfi * a.fluxes[2 * stride + i],
+                 d3 = sfi * a.fluxes[3 * stride + i], d4 = sfi * a.fluxes[4 * stride + i];
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, r4 = 0.0;
+    if (LAST) {
+        r0 = a.old_variables[i]; r1 = a.old_variables[stride + i]; r2 = a.old_variables[2 * stride + i];
+        r3 = a.old_variables[3 * stride + i]; r4 = a.old_variables[4 * stride + i];
+    }
+    int32_t tl_b = 0, tl_n = 0;
+    if (TAIL) { tl_b = tp.begin[i]; tl_n = tp.count[i]; }
+    __syncthreads();
+
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+    int32_t n_edges = 0;                                               // n_i: internal edges with this node as an end point
+    auto add = [&](uint32_t code) {
+        const uint32_t s = code & kT16SlotMask;
+        if (s == kT16Pad) return;
+        double v0, v1, v2, v3, v4;
+        if (s >= uint32_t(kTileCap)) previous(tile_ovf[ovf0 + int32_t(s) - kTileCap], v0, v1, v2, v3, v4);
+        else { v0 = rec[0][s]; v1 = rec[1][s]; v2 = rec[2][s]; v3 = rec[3][s]; v4 = rec[4][s]; }
+        s0 += v0; s1 += v1; s2 += v2; s3 += v3; s4 += v4;
+        n_edges++;
+    };
+    for (int32_t r = 0; r < n_int; r++) {                             // the codes one row ahead of the sums
+        const uint32_t cn = r + 1 < n_int ? nbr16[(int64_t(row0 + r + 1) << 6) + lane] : kT16Pad;
+        add(c);
+        c = cn;
+    }
+    if (TAIL) {
+        for (int32_t k = 0; k < tl_n; k++) {
+            const unsigned long long word = static_cast<unsigned long long>(__double_as_longlong(tp.rec[3 * int64_t(tl_b + k) + 2].x));
+            add(static_cast<uint32_t>(word >> 16) & 0xFFFFu);
+        }
+    }
+    if (i >= nel) return;
+    const double den = 1.0 + a.eps * double(n_edges);
+    const double b0 = (d0 + a.eps * s0) / den, b1 = (d1 + a.eps * s1) / den, b2 = (d2 + a.eps * s2) / den,
+                 b3 = (d3 + a.eps * s3) / den, b4 = (d4 + a.eps * s4) / den;
+    if (!LAST) {
+        a.next[i] = b0; a.next[stride + i] = b1; a.next[2 * stride + i] = b2; a.next[3 * stride + i] = b3; a.next[4 * stride + i] = b4;
+        return;
+    }
+    const double rho = r0 + b0 / a.rk_div, mx = r1 + b1 / a.rk_div, my = r2 + b2 / a.rk_div, mz = r3 + b3 / a.rk_div,
+                 en = r4 + b4 / a.rk_div;
+    store_conserved(a.q_out, stride, i, rho, mx, my, mz, en);
+    if (a.residuals) {
+        a.residuals[i] = rho - r0; a.residuals[stride + i] = mx - r1; a.residuals[2 * stride + i] = my - r2;
+        a.residuals[3 * stride + i] = mz - r3; a.residuals[4 * stride + i] = en - r4;
+    }
+    if (a.check) {
+        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
+        int code = 0;
+        if (!finite) code = 1;
+        else if (rho < 0.0) code = 2;
+        else if (en < 0.0) code = 3;
+        if (code) atomicMin(a.err, err_key(a.check, a.old_of_new[i], code));
+    }
+}
+
 // check_for_invalid_variables as a standalone sweep
 __global__ void __launch_bounds__(kBlock)
 k_check_invalid(int64_t nel, int64_t stride, const double *__restrict__ q, const int32_t *__restrict__ old_of_new,
@@ -3136,6 +3254,19 @@ void launch_time_step(hipStream_t st, int64_t nel, int64_t stride, int j, double
     hipLaunchKernelGGL(k_time_step, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, rk_div, sf, fluxes,
                        old_variables, q, old_of_new, err, check, partial_min, n_partial, volumes, residuals,
                        zero_fluxes);
+}
+
+// one iteration of the residual smoothing: the first forms D on load (a.prev == nullptr), the last applies the update (a.next == nullptr)
+void launch_smooth(hipStream_t st, const DevicePlan &p, const SmoothStep &a)
+{
+    with_bool(a.prev == nullptr, [&](auto first) {
+        with_bool(a.next == nullptr, [&](auto last) {
+            with_bool(p.has_tail != 0, [&](auto tail) {
+                hipLaunchKernelGGL((k_smooth_tile<decltype(first)::value, decltype(last)::value, decltype(tail)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                                   p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
+            });
+        });
+    });
 }
 
 void launch_check_invalid(hipStream_t st, int64_t nel, int64_t stride, const double *q, const int32_t *old_of_new,

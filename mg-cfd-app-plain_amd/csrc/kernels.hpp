@@ -23,6 +23,7 @@
                           const double *old_variables, double *q, const int32_t *old_of_new,                         \
                           unsigned long long *err, int check, const double *partial_min, int n_partial,              \
                           const double *volumes, double *residuals, int zero_fluxes);                                \
+    void launch_smooth(hipStream_t, const DevicePlan &, const SmoothStep &);                                          \
     void launch_check_invalid(hipStream_t, int64_t nel, int64_t stride, const double *q,                             \
                               const int32_t *old_of_new, unsigned long long *err);                                   \
     void launch_residual(hipStream_t, int64_t stride, const double *old_variables, const double *q,                  \
@@ -73,6 +74,6 @@ struct Launchers {
     decltype(exact::launch_indirect_rw) *indirect_rw;                decltype(exact::launch_time_step) *time_step;
     decltype(exact::launch_residual) *residual;                      decltype(exact::launch_sumsq) *sumsq;
     decltype(exact::launch_restrict) *restrict_;                     decltype(exact::launch_prolong) *prolong;
-    decltype(exact::launch_step_factor_nodal) *step_factor_nodal;
+    decltype(exact::launch_step_factor_nodal) *step_factor_nodal;    decltype(exact::launch_smooth) *smooth;
 };
 }

@@ -57,7 +57,12 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool time_step_given = false;     // --time-step / --cfl / time_step / cfl: mgcfd_set_time_step before the first cycle
     int time_step_mode = MGCFD_DT_REFERENCE;
     double cfl = 0.5;
-    bool time_step_bad = false;       // a config file's value was refused: the run ends right after parsing
+    bool config_bad = false;          // a config file's value (time step, residual smoothing) was refused: the run ends right after parsing
+    // implicit residual smoothing: --residual-smoothing EPS / --smoothing-iterations N / residual_smoothing / smoothing_iterations
+    bool smoothing_given = false;     // an EPS was given: mgcfd_set_residual_smoothing before the first cycle
+    bool smoothing_iterations_given = false;
+    double smoothing_eps = 0.0;
+    int smoothing_iterations = 2;     // (the default when only EPS is given)
     // the k-th angle of the run (one angle without --polar)
     int num_angles() const { return polar ? polar_n : 1; }
     double angle(int k) const { return !polar ? angle_of_attack : (polar_n == 1 ? polar_a0 : polar_a0 + (polar_a1 - polar_a0) * double(k) / double(polar_n - 1)); }
@@ -85,12 +90,21 @@ bool parse_time_step_mode(const char *text, int *out)
     else return false;
     return true;
 }
-// a finite CFL number above zero
-bool parse_cfl(const char *text, double *out)
+// a finite number above zero (the CFL number, the residual smoothing's coefficient)
+bool parse_positive(const char *text, double *out)
 {
     double v = 0.0;
     if (!parse_number(text, &v) || !(v > 0.0)) return false;
     *out = v;
+    return true;
+}
+
+// the smoothing's Jacobi iterations: a whole number 0 ... MGCFD_MAX_SMOOTHING_ITERATIONS
+bool parse_smoothing_iterations(const char *text, int *out)
+{
+    double v = 0.0;
+    if (!parse_number(text, &v) || v < 0.0 || v > double(MGCFD_MAX_SMOOTHING_ITERATIONS) || v != double(int(v))) return false;
+    *out = int(v);
     return true;
 }
 
@@ -157,11 +171,19 @@ void set_param(Config &c, const std::string &key, const std::string &value)
     else if (key == "angle_of_attack") { if (parse_number(value.c_str(), &c.angle_of_attack)) c.free_stream_given = true; else std::printf("WARNING: angle_of_attack = '%s' is not a number.\n", value.c_str()); }
     else if (key == "time_step") {
         if (parse_time_step_mode(value.c_str(), &c.time_step_mode)) c.time_step_given = true;
-        else { std::fprintf(stderr, "ERROR: time_step = '%s': expected reference, global, local or local-legacy\n", value.c_str()); c.time_step_bad = true; }
+        else { std::fprintf(stderr, "ERROR: time_step = '%s': expected reference, global, local or local-legacy\n", value.c_str()); c.config_bad = true; }
     }
     else if (key == "cfl") {
-        if (parse_cfl(value.c_str(), &c.cfl)) c.time_step_given = true;
-        else { std::fprintf(stderr, "ERROR: cfl = '%s': expected a finite number above zero\n", value.c_str()); c.time_step_bad = true; }
+        if (parse_positive(value.c_str(), &c.cfl)) c.time_step_given = true;
+        else { std::fprintf(stderr, "ERROR: cfl = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "residual_smoothing") {
+        if (parse_positive(value.c_str(), &c.smoothing_eps)) c.smoothing_given = true;
+        else { std::fprintf(stderr, "ERROR: residual_smoothing = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "smoothing_iterations") {
+        if (parse_smoothing_iterations(value.c_str(), &c.smoothing_iterations)) c.smoothing_iterations_given = true;
+        else { std::fprintf(stderr, "ERROR: smoothing_iterations = '%s': expected a whole number 0 ... %d\n", value.c_str(), MGCFD_MAX_SMOOTHING_ITERATIONS); c.config_bad = true; }
     }
     else std::printf("WARNING: Unknown key '%s' encountered during parsing of config file.\n", key.c_str());
 }
@@ -240,7 +262,12 @@ void print_help()
         "  --time-step=MODE                 reference (default: what the mesh name selects), global, local or local-legacy\n"
         "                                   (config key time_step); with --gpus N, --polar and --output-loads alike\n"
         "  --cfl=X                          CFL number of the time step, finite and above zero (default 0.5, the reference's;\n"
-        "                                   config key cfl)\n");
+        "                                   config key cfl)\n"
+        "  --residual-smoothing=EPS         implicit residual smoothing with coefficient EPS, finite and above zero (config key\n"
+        "                                   residual_smoothing): every stage's update goes through Jacobi iterations over the edge\n"
+        "                                   graph, which lets --cfl be two or more times as large.  One GPU, or --gpus N with one\n"
+        "                                   multigrid level per GPU; not with --gpus-partition or a level split over GPUs\n"
+        "  --smoothing-iterations=N         its Jacobi iterations, 0 ... 8 (default 2; 0 = off; config key smoothing_iterations)\n");
 }
 
 bool parse_arguments(int argc, char **argv, Config &c)
@@ -277,6 +304,8 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"polar", required_argument, nullptr, 1017},
         {"time-step", required_argument, nullptr, 1018},
         {"cfl", required_argument, nullptr, 1019},
+        {"residual-smoothing", required_argument, nullptr, 1020},
+        {"smoothing-iterations", required_argument, nullptr, 1021},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -331,16 +360,34 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 c.time_step_given = true;
                 break;
             case 1019:
-                if (!parse_cfl(optarg, &c.cfl)) {
+                if (!parse_positive(optarg, &c.cfl)) {
                     std::fprintf(stderr, "ERROR: --cfl=%s: expected a finite number above zero\n", optarg);
                     return false;
                 }
                 c.time_step_given = true;
                 break;
+            case 1020:
+                if (!parse_positive(optarg, &c.smoothing_eps)) {
+                    std::fprintf(stderr, "ERROR: --residual-smoothing=%s: expected a finite number above zero\n", optarg);
+                    return false;
+                }
+                c.smoothing_given = true;
+                break;
+            case 1021:
+                if (!parse_smoothing_iterations(optarg, &c.smoothing_iterations)) {
+                    std::fprintf(stderr, "ERROR: --smoothing-iterations=%s: expected a whole number 0 ... %d\n", optarg, MGCFD_MAX_SMOOTHING_ITERATIONS);
+                    return false;
+                }
+                c.smoothing_iterations_given = true;
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
-    return !c.time_step_bad;
+    if (c.smoothing_iterations_given && !c.smoothing_given && c.smoothing_iterations > 0) {
+        std::fprintf(stderr, "ERROR: --smoothing-iterations needs --residual-smoothing EPS (the residual smoothing's coefficient)\n");
+        return false;
+    }
+    return !c.config_bad;
 }
 
 // src/Base/io_enhanced.cpp:26-74
@@ -580,6 +627,7 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
         std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
         std::vector<PolarRow> polar_rows;
         if (conf.time_step_given && run.set_time_step(conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
+        if (conf.smoothing_given && run.set_residual_smoothing(conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
         const int rc = run_all_cycles(conf, rms, loads, polar_rows,
             [&](double mach, double alpha, int reinitialise) { return run.set_free_stream(mach, alpha, reinitialise); },
             [&](double *rms_out, double *loads_out) {
@@ -645,6 +693,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
         return 1;
     }
+    if (conf.smoothing_given && conf.smoothing_iterations > 0 && conf.gpus > 1 && conf.gpus_partition) {
+        std::fprintf(stderr, "ERROR: residual smoothing (--residual-smoothing) does not run with --gpus-partition: a level split over GPUs would need a halo exchange per Jacobi iteration\n");
+        return 1;
+    }
     if (conf.polar && conf.gpus > 1 && !conf.gpus_partition) {
         std::fprintf(stderr, "ERROR: --polar runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
         return 1;
@@ -699,6 +751,7 @@ int main(int argc, char **argv)
     std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
     std::vector<PolarRow> polar_rows;
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
+    if (conf.smoothing_given && mgcfd_set_residual_smoothing(solver, conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
         [&](double *rms_out, double *loads_out) {

@@ -451,6 +451,16 @@ int Run::set_time_step(int mode, double cfl)
     return MGCFD_OK;
 }
 
+int Run::set_residual_smoothing(double eps, int iterations)
+{
+    // (a group's ranks hold parts of a level: the library refuses them, mgcfd.h)
+    for (mgcfd_solver *s : p->solvers) {
+        const int rc = mgcfd_set_residual_smoothing(s, eps, iterations);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
 int Run::run_cycles(int cycles, double *rms_out)
 {
     const int n = p->levels, w = ranks();

@@ -32,6 +32,8 @@ public:
     int set_free_stream(double mach, double alpha_deg, int reinitialise);
     // mgcfd_set_time_step on every rank, likewise
     int set_time_step(int mode, double cfl);
+    // mgcfd_set_residual_smoothing on every rank (one multigrid level per rank only: MGCFD_ERR_ARG where a level is split)
+    int set_residual_smoothing(double eps, int iterations);
     void get_level0(int which, int ncols, double *out) const;   // a level-0 array of the WHOLE mesh, original numbering
     int check_invalid(int level, int64_t *bad_cell) const;      // check_for_invalid_variables on `level` of the whole mesh (original cell id)
     void loop_iters(int level, int cycles, int64_t out[MGCFD_NUM_LOOPS]) const;

@@ -173,6 +173,7 @@ struct DeviceLevel {
     int sf_par = 0;                      // parity of those swaps (part of the graph keys)
     double *sfb[2] = {nullptr, nullptr};
     void apply_sf() { step_factors = sfb[sf_par & 1]; sf_alt = sfb[(sf_par & 1) ^ 1]; }
+    double *smooth_buf[2] = {nullptr, nullptr};   // [5][stride] each: the residual smoothing's iterates, alternating (allocated when it is first switched on)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
     double *min_dt = nullptr;            // global-min time step scalar (after the reduction)
     double *partial_min = nullptr;       // one partial minimum per step-factor workgroup
@@ -300,6 +301,12 @@ struct mgcfd_solver {
     double cfl = 0.5;                                                    // the reference's literal (cfd_loops.cpp:56,118)
     bool global_dt() const { return dt_mode == MGCFD_DT_GLOBAL || (dt_mode == MGCFD_DT_REFERENCE && mesh_variant != MGCFD_MESH_FVCORR); }   // one step for the level: a minimum to reduce
     bool legacy_dt() const { return dt_mode == MGCFD_DT_LOCAL_LEGACY || (dt_mode == MGCFD_DT_REFERENCE && mesh_variant == MGCFD_MESH_FVCORR); }   // compute_step_factor_legacy's formula
+    // Implicit residual smoothing (mgcfd_set_residual_smoothing): irs_iters Jacobi iterations with coefficient irs_eps stand in
+    // for every time_step; 0 = off.  While it is on a stage is one standalone flux launch + irs_iters smoothing launches: no
+    // fused stage, no look-ahead, no graph (the launches leave fluxes[] to be zeroed lazily, a host-side flag).
+    double irs_eps = 0.0;
+    int irs_iters = 0;
+    bool smoothing() const { return irs_iters > 0; }
     // ff17 -> the kernels' argument (ff) and the loads' p_inf.  Launches already captured keep the old values: drop_graphs.
     void set_far_field(const double *in17)
     {
@@ -334,7 +341,7 @@ struct mgcfd_solver {
     {
 #define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
-                                NS::launch_step_factor_nodal}
+                                NS::launch_step_factor_nodal, NS::launch_smooth}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -619,6 +626,29 @@ struct mgcfd_solver {
         if (!old) old = lv.old_variables;
         if (!out) out = lv.q;
         if (out == lv.q) lv.min_ahead = false;
+        if (smoothing()) {
+            // the smoothing works on final step factors: finish compute_step_factor first (the same division k_time_step would do)
+            // (booked where k_time_step's own division is booked: under time_step)
+            Timed t(this, l, MGCFD_LOOP_TIME_STEP);
+            if (apply_min == ApplyMin::Partials) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
+            if (apply_min != ApplyMin::None) op_step_factor_apply(l);
+            SmoothStep a;
+            a.fluxes = lv.fluxes; a.step_factors = lv.step_factors; a.eps = irs_eps;
+            for (int m = 0; m < irs_iters; m++) {
+                a.prev = m == 0 ? nullptr : lv.smooth_buf[(m - 1) & 1];
+                a.next = m == irs_iters - 1 ? nullptr : lv.smooth_buf[m & 1];
+                if (!a.next) {
+                    a.rk_div = double(MGCFD_RK + 1 - j); a.old_variables = old; a.q_out = out;
+                    a.residuals = with_residual ? lv.residuals : nullptr;
+                    a.old_of_new = lv.dp.old_of_new; a.err = err; a.check = next_check();
+                }
+                k().smooth(stream, lv.dp, a);
+            }
+            lv.fluxes_stale = true;                 // (never zeroed by these launches: with one iteration other tiles still read them)
+            lv.fluxes_zero = true;
+            lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
+            return;
+        }
         Timed t(this, l, MGCFD_LOOP_TIME_STEP);
         const double *pm = apply_min == ApplyMin::Partials ? lv.partial_min : (apply_min == ApplyMin::Scalar ? lv.min_dt : nullptr);
         const int n_pm = apply_min == ApplyMin::Scalar ? 1 : static_cast<int>((lv.info.nel + 255) / 256);
@@ -1446,6 +1476,38 @@ int mgcfd_get_time_step(const mgcfd_solver *s, int *mode, double *cfl)
     return MGCFD_OK;
 }
 
+// ---- implicit residual smoothing: coefficient and Jacobi iterations ----
+int mgcfd_set_residual_smoothing(mgcfd_solver *s, double eps, int iterations)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (iterations < 0 || iterations > MGCFD_MAX_SMOOTHING_ITERATIONS)
+            throw std::invalid_argument("residual smoothing: iterations must be 0 ... " + std::to_string(MGCFD_MAX_SMOOTHING_ITERATIONS));
+        if (iterations > 0 && (!std::isfinite(eps) || !(eps > 0.0))) throw std::invalid_argument("residual smoothing: eps must be finite and positive");
+        if (iterations > 0 && (s->partitioned || s->comm))
+            throw std::invalid_argument("residual smoothing: not on a partitioned solver or a rank (a level split over ranks would need a ghost exchange per iteration)");
+        require_no_sweep_under_way(s, "residual smoothing");
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);
+        s->drop_graphs();
+        if (iterations > 0)
+            for (DeviceLevel &lv : s->L)
+                for (double *&b : lv.smooth_buf)
+                    if (!b) b = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
+        s->irs_iters = iterations;
+        s->irs_eps = iterations > 0 ? eps : 0.0;
+    });
+}
+int mgcfd_get_residual_smoothing(const mgcfd_solver *s, double *eps, int *iterations)
+{
+    REQUIRE(s);
+    if (eps) *eps = s->irs_eps;
+    if (iterations) *iterations = s->irs_iters;
+    return MGCFD_OK;
+}
+
 // ---- kernel-granular operations ----
 #define OP(body) REQUIRE(s); return guarded([&] { s->use_device(); body; HIP_CHECK(hipGetLastError()); })   /* (a launch that failed must not come back as MGCFD_OK) */
 int mgcfd_copy_old_variables(mgcfd_solver *s, int level) { OP(s->op_copy_old(level)); }
@@ -1536,7 +1598,7 @@ static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 static void smooth_once(mgcfd_solver *s, int level)
 {
     DeviceLevel &lv = s->level(level);
-    if (s->opt_fuse && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
+    if (s->opt_fuse && !s->smoothing() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
         // Fused stages: flux + time_step in one launch each.  No copy<double>(old_variables, variables)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
@@ -1617,7 +1679,7 @@ static void run_sweep(mgcfd_solver *s, int level)
     }
     // (only the fused launches are replayed: the unfused ones — the two-phase flux variant — leave host-side flags
     //  behind, fluxes_stale, that a replay would not set)
-    const bool graphable = s->opt_graph && s->opt_fuse && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
+    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
     if (!graphable) {
         const int keep = s->opt_timing;
         if (!timed) s->opt_timing = 0;
@@ -1665,10 +1727,16 @@ static void run_sweep(mgcfd_solver *s, int level)
     for (int k = 0; k < MGCFD_NUM_LOOPS; k++) lv.iters[k] += it->second.iters[k];
 }
 
+// The split sweep is made of fused stages, which residual smoothing replaces: refused while it is on.
+static void require_no_smoothing(const mgcfd_solver *s, const char *who)
+{
+    if (s->smoothing()) throw std::invalid_argument(std::string(who) + ": not while residual smoothing is on (mgcfd_set_residual_smoothing; use mgcfd_smooth or the kernel-granular calls)");
+}
 // The same sweep split around the one collective a multi-GPU run needs (see mgcfd.h).
 static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
 {
     OP({
+        require_no_smoothing(s, "mgcfd_sweep_begin");
         DeviceLevel &lv = s->level(level);
         if (!lv.fluxes_zero) throw std::invalid_argument("sweep_begin needs zero fluxes (as after time_step)");
         lv.sweep_flux0_done = false;
@@ -1688,6 +1756,7 @@ static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
 int mgcfd_sweep_flux0(mgcfd_solver *s, int level)
 {
     OP({
+        require_no_smoothing(s, "mgcfd_sweep_flux0");
         DeviceLevel &lv = s->level(level);
         if (!lv.fluxes_zero) throw std::invalid_argument("sweep_flux0 must follow sweep_begin");
         s->op_flux(level, 7);                      // stage-0 fluxes: independent of the time step
@@ -1697,6 +1766,7 @@ int mgcfd_sweep_flux0(mgcfd_solver *s, int level)
 static int sweep_end_impl(mgcfd_solver *s, int level, bool scalar)
 {
     OP({
+        require_no_smoothing(s, "mgcfd_sweep_end");
         DeviceLevel &lv = s->level(level);
         const bool global_dt = s->global_dt();
         const ApplyMin apply = global_dt ? (scalar ? ApplyMin::Scalar : ApplyMin::Partials) : ApplyMin::None;
@@ -1738,6 +1808,7 @@ static int sweep_end_impl(mgcfd_solver *s, int level, bool scalar)
 int mgcfd_sweep_stage(mgcfd_solver *s, int level, int j, int partials)
 {
     OP({
+        require_no_smoothing(s, "mgcfd_sweep_stage");
         DeviceLevel &lv = s->level(level);
         if (j != lv.stage_next) throw std::invalid_argument("mgcfd_sweep_stage: stages must run in order 0, 1, 2 after mgcfd_sweep_begin");
         const bool global_dt = s->global_dt();
@@ -1898,7 +1969,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && s->opt_fuse && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2263,6 +2334,40 @@ int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_secon
         s->free_events.push_back(std::move(a));
         s->free_events.push_back(std::move(b));
         lv.fluxes_zero = false;
+        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+    });
+}
+
+// ... and for one kind of residual-smoothing launch: 0 the first iteration (D formed on load), 1 a middle one, 2 the last
+// (the update, written to the second state buffer: the state stays; no check, no residual).  After one flux launch, so
+// that fluxes[] holds a stage's numbers.
+int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->smoothing()) throw std::invalid_argument("residual smoothing is off: switch it on first (mgcfd_set_residual_smoothing)");
+        if (kind < 0 || kind > 2) throw std::invalid_argument("residual smoothing launch kind: 0 first, 1 middle, 2 last");
+        Event a = s->get_event(), b = s->get_event();
+        s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
+        SmoothStep st;
+        st.fluxes = lv.fluxes; st.step_factors = lv.step_factors; st.eps = s->irs_eps;
+        st.next = lv.smooth_buf[0];
+        s->k().smooth(s->stream, lv.dp, st);                       // smooth_buf[0] holds an iterate
+        if (kind >= 1) st.prev = lv.smooth_buf[0];
+        st.next = kind == 1 ? lv.smooth_buf[1] : (kind == 0 ? lv.smooth_buf[0] : nullptr);
+        if (kind == 2) { st.rk_div = double(MGCFD_RK + 1); st.old_variables = lv.q; st.q_out = lv.q_alt; st.old_of_new = lv.dp.old_of_new; st.err = s->err; }
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
+        for (int k = 0; k < launches; k++) s->k().smooth(s->stream, lv.dp, st);
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
+        lv.fluxes_zero = false;
+        lv.fluxes_stale = false;
         *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
@@ -3076,6 +3181,7 @@ int mgcfd_rank_attach_rccl(mgcfd_solver *s, int rank, int world, const void *id1
     REQUIRE(s); REQUIRE(id128);
     return guarded([&] {
         if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
+        require_no_smoothing(s, "mgcfd_rank_attach_rccl");
         s->use_device();
         rccl_load();
         Rccl::Id id;
@@ -3094,6 +3200,7 @@ int mgcfd_rank_attach_plain(mgcfd_solver *s, int rank, int world)
     REQUIRE(s);
     return guarded([&] {
         if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
+        require_no_smoothing(s, "mgcfd_rank_attach_plain");
         mgcfd_comm c;
         c.rank = rank; c.world = world;
         s->comm = c;
@@ -3403,6 +3510,7 @@ int mgcfd_group_create(int n, mgcfd_solver *const *solvers, mgcfd_group **out)
         auto g = std::make_unique<mgcfd_group>();
         for (int r = 0; r < n; r++) {
             if (!solvers[r]) throw std::invalid_argument("null solver");
+            require_no_smoothing(solvers[r], "mgcfd_group_create");
             g->ranks.push_back(solvers[r]);
         }
         // peer access between the devices of the group (xGMI): a copy between two devices then goes direct

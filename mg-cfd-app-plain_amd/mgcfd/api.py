@@ -177,6 +177,9 @@ _SIGNATURES = [
     ("mgcfd_set_time_step", C.c_int, [_vp, C.c_int, C.c_double]),
     ("mgcfd_get_time_step", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("mgcfd_group_set_time_step", C.c_int, [_vp, C.c_int, C.c_double]),
+    ("mgcfd_set_residual_smoothing", C.c_int, [_vp, C.c_double, C.c_int]),
+    ("mgcfd_get_residual_smoothing", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("mgcfd_bench_residual_smoothing", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -562,14 +565,31 @@ class Solver:
         self._c(self.lib.mgcfd_get_time_step(self.handle, C.byref(m), C.byref(c)))
         return {v: k for k, v in DT_MODE.items()}[m.value], c.value
 
+    # ---- implicit residual smoothing ----
+    def set_residual_smoothing(self, eps: float, iterations: int = 2):
+        """Every stage's update goes through ``iterations`` Jacobi iterations of implicit residual smoothing with coefficient
+        ``eps`` (mgcfd_set_residual_smoothing), which lets the sweeps run at a CFL number two or more times as large;
+        ``iterations=0`` switches it off.  The state stays; captured graphs are dropped.  Not on partitioned solvers or ranks."""
+        self._c(self.lib.mgcfd_set_residual_smoothing(self.handle, float(eps), int(iterations)))
+
+    def residual_smoothing(self):
+        """``(eps, iterations)`` in use; ``(0.0, 0)`` when off."""
+        e, m = C.c_double(), C.c_int()
+        self._c(self.lib.mgcfd_get_residual_smoothing(self.handle, C.byref(e), C.byref(m)))
+        return e.value, m.value
+
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
-              ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None) -> List[dict]:
+              ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
+              residual_smoothing=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
         dict: ``alpha``, ``mach``, ``rms`` [cycles], ``loads`` [cycles, 6] and ``coefficients`` (CD CL CS CMx CMy CMz of the
         last cycle against that angle's far field).  ``time_step`` / ``cfl`` (None: as the solver has them) are set once,
-        before the first angle, and stay (``set_time_step``)."""
+        before the first angle, and stay (``set_time_step``); likewise ``residual_smoothing=(eps, iterations)``
+        (``set_residual_smoothing``)."""
+        if residual_smoothing is not None:
+            self.set_residual_smoothing(*residual_smoothing)
         if time_step is not None or cfl is not None:
             mode0, cfl0 = self.time_step_control()
             self.set_time_step(mode0 if time_step is None else time_step, cfl0 if cfl is None else cfl)
@@ -623,6 +643,13 @@ class Solver:
     def bench_flux(self, l: int, launches: int) -> float:
         t = C.c_double()
         self._c(self.lib.mgcfd_bench_flux(self.handle, l, launches, C.byref(t)))
+        return t.value
+
+    def bench_residual_smoothing(self, l: int, kind: int, launches: int) -> float:
+        """Mean GPU seconds of one residual-smoothing launch of ``kind`` (0 first, 1 middle, 2 last iteration) over ``launches``
+        back-to-back launches under one event pair (mgcfd_bench_residual_smoothing); the smoothing must be on."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_residual_smoothing(self.handle, l, kind, launches, C.byref(t)))
         return t.value
 
     def bench_stream_ceiling(self, l: int, launches: int) -> float:
