@@ -52,7 +52,8 @@ enum { MGCFD_LOOP_FLUX = 0, MGCFD_LOOP_UPDATE, MGCFD_LOOP_COMPUTE_STEP, MGCFD_LO
  * src/euler3d_cpu_double.cpp:138-162). */
 enum { MGCFD_ARR_VARIABLES = 0, MGCFD_ARR_OLD_VARIABLES, MGCFD_ARR_FLUXES, MGCFD_ARR_RESIDUALS,
        MGCFD_ARR_STEP_FACTORS, MGCFD_ARR_VOLUMES,
-       MGCFD_ARR_STAGE /* the state the last mgcfd_sweep_stage wrote (halo messages between the stages of a split sweep) */ };
+       MGCFD_ARR_STAGE /* the state the last mgcfd_sweep_stage wrote (halo messages between the stages of a split sweep) */,
+       MGCFD_ARR_TIME_N, MGCFD_ARR_TIME_N1 /* dual time stepping's time levels Wn and Wn1 (while mgcfd_set_dual_time has it on) */ };
 
 /* Solver options (mgcfd_set_option) */
 enum {
@@ -317,6 +318,71 @@ int mgcfd_get_time_step(const mgcfd_solver *s, int *mode, double *cfl);
 #define MGCFD_MAX_SMOOTHING_ITERATIONS 8
 int mgcfd_set_residual_smoothing(mgcfd_solver *s, double eps, int iterations);
 int mgcfd_get_residual_smoothing(const mgcfd_solver *s, double *eps, int *iterations);
+/* Dual time stepping (Jameson 1991): time-accurate flows.  Physical time is discretised by the second-order backward
+ * difference formula (BDF2, BDF1 on the first step) and every physical step is solved as a steady problem in pseudo-time
+ * by the machinery above: V-cycles, local or global pseudo steps (mgcfd_set_time_step), residual smoothing.  No reference
+ * counterpart.  With dual time on and physical step dt every level l holds two more [5][stride] arrays: Wn, the state at the
+ * last physical time level, and Wn1, the one before it.  Stage j of every sweep of every level computes its fluxes F as
+ * before (internal, solid wall, far field) and then forms for every node i and variable v, with W the stage's input state
+ * (the state the fluxes were computed from), every operation one IEEE-754 double operation, never contracted to FMA under
+ * MGCFD_OPT_EXACT = 1:
+ *   a = W[i][v] - Wn[i][v]
+ *   b = Wn[i][v] - Wn1[i][v]
+ *   second order (BDF2):   src = vol[i] * ((3.0 * a - b) / (2.0 * dt))
+ *   first order  (BDF1):   src = vol[i] * (a / dt)
+ *   F'[i][v] = F[i][v] - src
+ * (the differences first: a uniform state gives src = +0.0 exactly).  The update proceeds with F' in place of F and nothing
+ * else changes: time_step(j) without residual smoothing, D = sf * F' into the Jacobi iterations with it.  The source is
+ * explicit in pseudo-time, so after a sweep's step factors are final under the mgcfd_set_time_step policy and before
+ * stage 0:   sf[i] = min(sf[i], (clamp * dt) / vol[i])   (clamp: a run-time number, finite and above zero; the callers' default
+ * is 2.0/3.0, MGCFD_DUAL_TIME_CLAMP; vol: the volumes the step factor uses; a node whose factor is NaN keeps it).
+ * The RMS of a cycle while dual time is on (mgcfd_run_cycles[_loads], mgcfd_advance) is sqrt(S / nel) with S, the sum of the
+ * squares of level 0's residuals, added up in an order fixed by the ORIGINAL node numbering, every operation one IEEE-754
+ * double operation, never contracted: node o gives q[o] = ((((+0.0 + r0*r0) + r1*r1) + r2*r2) + r3*r3) + r4*r4; nodes
+ * 256 g .. 256 g + 255 (missing ones count +0.0) form group g of four blocks of 64; a block of 64 values is halved five times
+ * (v[i] + v[i + 32] for i < 32, then + 16, 8, 4, 2) and its last two values added; the group's sum is ((+0.0 + block 0) +
+ * block 1) + block 2) + block 3; the group sums p[g] are added up the same way: t[i] = p[i] + p[i + 256] + ... one after
+ * another from +0.0 for i < 256, then t as one group.  (With dual time off the sum keeps the order of the library's own
+ * numbering, as before.)
+ * Time levels: mgcfd_dual_time_begin_step does Wn1 <- Wn and Wn <- variables[l] on EVERY level l — a coarse level takes its
+ * own current `variables` (what mg_restrict of the last cycle left, plus the sweeps and prolongations behind it): no new
+ * transfer operator is introduced.  The first step after switching on, and the first after mgcfd_dual_time_reset, sets
+ * Wn1 = Wn = variables and runs BDF1; from the second step on BDF2 runs; mgcfd_dual_time_set_order(s, 1) keeps BDF1
+ * throughout.  Switching on also sets Wn1 = Wn = variables, so sweeps before the first begin_step are defined (BDF1 against
+ * the state at switch-on).  mgcfd_set_array on MGCFD_ARR_TIME_N / _TIME_N1 (a restart) marks one / both levels as held:
+ * restore variables, Wn and Wn1 and the next begin_step shifts them and runs BDF2.
+ * mgcfd_set_dual_time(s, dt, clamp): dt > 0 and finite switches it on (the arrays are allocated at the first such call; a
+ * later one changes dt and clamp and keeps the levels), dt = 0 switches it off: the arrays are released and the solver
+ * launches what it launched, and computes the bits it computed, before the call existed.  It synchronises and drops every
+ * captured graph; the state stays.  MGCFD_ERR_ARG, and nothing changed: a negative or non-finite dt; with dt > 0 a non-finite
+ * clamp or clamp <= 0; while a kernel-granular sweep is under way (as mgcfd_set_time_step); with dt > 0 on a solver made by
+ * mgcfd_create_partitioned* or attached to a group or as a rank.  While it is on: mgcfd_smooth, mgcfd_run_cycles[_loads] and
+ * mgcfd_compute_step_factor / mgcfd_step_factor_apply / mgcfd_time_step(s, l, j) honour the clamp and the source
+ * (mgcfd_time_step with the state mgcfd_compute_fluxes last read as W); a stage is one standalone flux launch + one
+ * time_step launch that forms F' in registers (with residual smoothing: + one node-wise source launch + the M smoothing
+ * launches); the fused flux + time_step stages and captured graphs are not used (MGCFD_OPT_GRAPH is accepted and runs the
+ * launches directly); mgcfd_sweep_begin*, mgcfd_sweep_flux0, mgcfd_sweep_stage and mgcfd_sweep_end* return MGCFD_ERR_ARG, and
+ * mgcfd_group_create and mgcfd_rank_attach_* refuse the solver.  Out of scope: levels split over ranks, captured graphs
+ * with dual time on, a fused flux + dual-time stage.
+ * mgcfd_get_dual_time: any pointer may be NULL; dt = 0 when off; *order as set (2 by default); *levels = time levels held
+ * (0, 1 or 2); *invalid_step = the 0-based physical step of the last mgcfd_advance in which an invalid state was found, or -1.
+ * mgcfd_dual_time_set_order: 1 or 2.  mgcfd_dual_time_reset: the next begin_step starts again with BDF1.  Both, and
+ * mgcfd_dual_time_begin_step, return MGCFD_ERR_ARG while dual time is off.
+ * mgcfd_advance: steps x (mgcfd_dual_time_begin_step + cycles_per_step V-cycles).  rms_out (may be NULL)
+ * [step * cycles_per_step + c] receives the level-0 RMS as mgcfd_run_cycles gives it, loads_out (may be NULL) [step * 6 ..]
+ * the level-0 surface loads (mgcfd_surface_loads about ref_point) of the state each physical step ends with.  Errors and
+ * mgcfd_invalid_state_location are those of mgcfd_run_cycles (the cycle counts within the physical step, which
+ * mgcfd_get_dual_time reports); entries from the failing cycle on are NaN and later steps do not run.  At most
+ * MGCFD_MAX_ADVANCE_CYCLES cycles per call in total (steps * cycles_per_step): MGCFD_ERR_ARG beyond that, for steps < 0 or
+ * cycles_per_step < 1, and while dual time is off. */
+#define MGCFD_MAX_ADVANCE_CYCLES 4096
+#define MGCFD_DUAL_TIME_CLAMP (2.0 / 3.0)
+int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp);
+int mgcfd_get_dual_time(const mgcfd_solver *s, double *dt, double *clamp, int *order, int *levels, int *invalid_step);
+int mgcfd_dual_time_set_order(mgcfd_solver *s, int order);
+int mgcfd_dual_time_reset(mgcfd_solver *s);
+int mgcfd_dual_time_begin_step(mgcfd_solver *s);
+int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3]);
 
 /* ---------------------------------------------------------------------------------
  * Kernel-granular operations (asynchronous on the solver's stream)

@@ -120,6 +120,16 @@ struct SmoothStep {
     int check = 0;
 };
 
+// The physical-time source of dual time stepping (kernels.hip: k_time_step_dual, k_dual_source; mgcfd_set_dual_time):
+//   src = vol * ((3 (W - Wn) - (Wn - Wn1)) / (2 dt))   order 2 (BDF2);   src = vol * ((W - Wn) / dt)   order 1 (BDF1, Wn1 not read)
+struct DualSource {
+    const double *w = nullptr;                // the stage's input state W [5][stride]: what the fluxes were computed from
+    const double *wn = nullptr, *wn1 = nullptr;   // the last physical time level and the one before it
+    const double *volumes = nullptr;          // [stride]
+    double dt = 0.0;                          // the physical step
+    int order = 1;
+};
+
 // "Add up these partial sums" as an argument: k_sum_partials does only that; k_restrict can take it along.
 struct SumTask {
     const double *partial = nullptr;      // [n]

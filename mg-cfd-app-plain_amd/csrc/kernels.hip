@@ -2214,6 +2214,103 @@ k_time_step(int64_t nel, int64_t stride, double rk_div, double *__restrict__ ste
 }
 
 // ------------------------------------------------------------------------------------------
+// Dual time stepping (no reference counterpart; INTEGRATION.md "Dual time stepping"): the physical-time derivative as a
+// source in every stage's update, BDF2 (BDF1 on the first physical step) over the state W the stage's fluxes were computed
+// from and the two stored time levels Wn, Wn1.  The differences are formed first, so a state equal to both levels gives
+// src = +0.0 exactly; one IEEE operation per line of the definition (include/mgcfd.h), never contracted in the exact build.
+// ------------------------------------------------------------------------------------------
+template <bool BDF2>
+__device__ __forceinline__ double dual_source(double w, double wn, double wn1, double vol, double dt)
+{
+    const double a = w - wn;
+    if (!BDF2) return vol * (a / dt);
+    const double b = wn - wn1;
+    return vol * ((3.0 * a - b) / (2.0 * dt));
+}
+
+// time_step with F' = F - src in place of F, in the one launch: W, Wn, Wn1 (BDF2) and the volume are read beside what
+// k_time_step reads (128 B per node more; BDF1: 88), F' exists in registers only, fluxes[] is never written and stays
+// logically zero (the lazy zero of k_time_step), the residual and check_for_invalid_variables ride along as there.  The
+// step factors are final (the sweep clamped them: k_dual_clamp).  In place: W and q are the same array, every lane reads
+// its node before it writes it, so neither pointer is declared restrict.
+template <bool BDF2>
+__global__ void __launch_bounds__(kBlock)
+k_time_step_dual(int64_t nel, int64_t stride, double rk_div, const double *__restrict__ step_factors,
+                 const double *__restrict__ fluxes, const double *old_variables, double *q,
+                 const int32_t *__restrict__ old_of_new, unsigned long long *__restrict__ err, int check,
+                 double *residuals, DualSource d)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double factor = step_factors[i] / rk_div;
+    const double vol = d.volumes[i];
+    double fp[5], r[5];
+#pragma unroll
+    for (int v = 0; v < 5; v++) {
+        const int64_t at = v * stride + i;
+        const double wn1 = BDF2 ? d.wn1[at] : 0.0;
+        fp[v] = fluxes[at] - dual_source<BDF2>(d.w[at], d.wn[at], wn1, vol, d.dt);
+        r[v] = old_variables[at];
+    }
+    const double rho = r[0] + factor * fp[0];
+    const double mx = r[1] + factor * fp[1];
+    const double my = r[2] + factor * fp[2];
+    const double mz = r[3] + factor * fp[3];
+    const double en = r[4] + factor * fp[4];
+    store_conserved(q, stride, i, rho, mx, my, mz, en);
+    if (residuals) {
+        residuals[i] = rho - r[0]; residuals[stride + i] = mx - r[1]; residuals[2 * stride + i] = my - r[2];
+        residuals[3 * stride + i] = mz - r[3]; residuals[4 * stride + i] = en - r[4];
+    }
+    if (check) {
+        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
+        int code = 0;
+        if (!finite) code = 1;
+        else if (rho < 0.0) code = 2;
+        else if (en < 0.0) code = 3;
+        if (code) atomicMin(err, err_key(check, old_of_new[i], code));
+    }
+}
+
+// ... and with residual smoothing on: fluxes = F - src for every node of the level, before the Jacobi iterations, whose
+// first launch forms D = sf * F' for own and halo nodes alike from fluxes[] (k_smooth_tile stays as it is).
+template <bool BDF2>
+__global__ void __launch_bounds__(kBlock)
+k_dual_source(int64_t nel, int64_t stride, double *__restrict__ fluxes, DualSource d)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double vol = d.volumes[i];
+#pragma unroll
+    for (int v = 0; v < 5; v++) {
+        const int64_t at = v * stride + i;
+        const double wn1 = BDF2 ? d.wn1[at] : 0.0;
+        fluxes[at] = fluxes[at] - dual_source<BDF2>(d.w[at], d.wn[at], wn1, vol, d.dt);
+    }
+}
+
+// The pseudo step's clamp (the source is explicit in pseudo-time): sf = min(sf, (clamp * dt) / vol); cdt = clamp * dt.
+__global__ void __launch_bounds__(kBlock)
+k_dual_clamp(int64_t nel, double cdt, const double *__restrict__ volumes, double *__restrict__ step_factors)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double sf = step_factors[i], cap = cdt / volumes[i];
+    step_factors[i] = cap < sf ? cap : sf;              // (a NaN factor stays NaN, as the invalid-state check expects)
+}
+
+// The time levels advance: Wn1 <- Wn (first: <- variables), Wn <- variables; n = 5 * stride, padding included.
+__global__ void __launch_bounds__(kBlock)
+k_dual_shift(int64_t n, const double *__restrict__ q, double *__restrict__ wn, double *__restrict__ wn1, int first)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= n) return;
+    const double now = q[i];
+    wn1[i] = first ? now : wn[i];
+    wn[i] = now;
+}
+
+// ------------------------------------------------------------------------------------------
 // Implicit residual smoothing (no reference counterpart; INTEGRATION.md "Implicit residual smoothing"): one Jacobi
 // iteration of (1 + eps*n_i) Db_i - eps * sum_j Db_j = D_i over the internal edges, D_i = step_factor_i * fluxes_i.
 //   Db^m_i = (D_i + eps * S_i) / (1 + eps * n_i),   S_i = the sum of Db^(m-1) at the other ends of node i's internal edges,
@@ -2366,6 +2463,32 @@ k_sumsq(int64_t nel, int64_t stride, const double *__restrict__ x, double *__res
     double acc = 0.0;
     for (int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x; i < nel; i += int64_t(gridDim.x) * kBlock) {
         if (old_of_new && old_of_new[i] >= n_owned) continue;        // ghost of a partitioned level: counted by its owner
+        for (int f = 0; f < 5; f++) { const double v = x[f * stride + i]; acc += v * v; }
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < kBlock / 64; w++) t += s[w];
+        partial[blockIdx.x] = t;
+    }
+}
+
+// The level-0 sum of squares under dual time stepping, in an order that is a function of the ORIGINAL node numbering alone
+// (include/mgcfd.h states it, tests/dual_time_emulator.py repeats it in numpy): a workgroup takes 256 consecutive original
+// nodes, a lane its node's five squares added one after another from +0.0 (a lane past the last node: +0.0), a wave the
+// pairwise tree of wave_sum (lane i with lane i ^ 32, then ^ 16, ... ^ 1), lane 0 of the workgroup the four waves' sums one
+// after another.  k_sum_partials adds the workgroups' sums up.  Never contracted: always the exact build's.
+__global__ void __launch_bounds__(kBlock)
+k_sumsq_original(int64_t nel, int64_t stride, const double *__restrict__ x, const int32_t *__restrict__ new_of_old,
+                 double *__restrict__ partial)
+{
+    __shared__ double s[kBlock / 64];
+    const int64_t o = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    double acc = 0.0;
+    if (o < nel) {
+        const int64_t i = new_of_old[o];
         for (int f = 0; f < 5; f++) { const double v = x[f * stride + i]; acc += v * v; }
     }
     acc = wave_sum(acc);
@@ -3256,6 +3379,31 @@ void launch_time_step(hipStream_t st, int64_t nel, int64_t stride, int j, double
                        zero_fluxes);
 }
 
+// time_step under dual time stepping: final step factors, fluxes[] left as it is (logically zero afterwards)
+void launch_time_step_dual(hipStream_t st, int64_t nel, int64_t stride, int j, const double *sf, const double *fluxes,
+                           const double *old_variables, double *q, const int32_t *old_of_new, unsigned long long *err, int check,
+                           double *residuals, const DualSource &d)
+{
+    const double rk_div = double(3 + 1 - j);
+    with_bool(d.order == 2, [&](auto bdf2) {
+        hipLaunchKernelGGL((k_time_step_dual<decltype(bdf2)::value>), dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, rk_div, sf, fluxes,
+                           old_variables, q, old_of_new, err, check, residuals, d);
+    });
+}
+
+void launch_dual_source(hipStream_t st, int64_t nel, int64_t stride, double *fluxes, const DualSource &d)
+{
+    with_bool(d.order == 2, [&](auto bdf2) {
+        hipLaunchKernelGGL((k_dual_source<decltype(bdf2)::value>), dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, fluxes, d);
+    });
+}
+
+void launch_dual_clamp(hipStream_t st, int64_t nel, double cdt, const double *volumes, double *sf)
+{ hipLaunchKernelGGL(k_dual_clamp, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, cdt, volumes, sf); }
+
+void launch_dual_shift(hipStream_t st, int64_t n, const double *q, double *wn, double *wn1, int first)
+{ hipLaunchKernelGGL(k_dual_shift, dim3(grid_for(n)), dim3(kBlock), 0, st, n, q, wn, wn1, first); }
+
 // one iteration of the residual smoothing: the first forms D on load (a.prev == nullptr), the last applies the update (a.next == nullptr)
 void launch_smooth(hipStream_t st, const DevicePlan &p, const SmoothStep &a)
 {
@@ -3311,6 +3459,10 @@ void launch_min_over_peers(hipStream_t st, const double *const *scalars, int n, 
 
 void launch_sum_partials_append(hipStream_t st, int n, const double *partial, double *out, double *ring, int *count, int cap)
 { hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(kBlock), 0, st, SumTask{partial, n, out, ring, count, cap}); }
+
+// partial must hold grid_for(nel) doubles
+void launch_sumsq_original(hipStream_t st, int64_t nel, int64_t stride, const double *x, const int32_t *new_of_old, double *partial)
+{ hipLaunchKernelGGL(k_sumsq_original, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, x, new_of_old, partial); }
 
 void launch_append_scalar(hipStream_t st, const double *src, double *ring, int *count, int cap)
 { hipLaunchKernelGGL(k_append_scalar, dim3(1), dim3(64), 0, st, src, ring, count, cap); }

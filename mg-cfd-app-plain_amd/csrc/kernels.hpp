@@ -24,6 +24,13 @@
                           unsigned long long *err, int check, const double *partial_min, int n_partial,              \
                           const double *volumes, double *residuals, int zero_fluxes);                                \
     void launch_smooth(hipStream_t, const DevicePlan &, const SmoothStep &);                                          \
+    void launch_time_step_dual(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                   \
+                               const double *fluxes, const double *old_variables, double *q,                       \
+                               const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,    \
+                               const DualSource &);                                                                 \
+    void launch_dual_source(hipStream_t, int64_t nel, int64_t stride, double *fluxes, const DualSource &);           \
+    void launch_dual_clamp(hipStream_t, int64_t nel, double cdt, const double *volumes, double *sf);                 \
+    void launch_dual_shift(hipStream_t, int64_t n, const double *q, double *wn, double *wn1, int first);             \
     void launch_check_invalid(hipStream_t, int64_t nel, int64_t stride, const double *q,                             \
                               const int32_t *old_of_new, unsigned long long *err);                                   \
     void launch_residual(hipStream_t, int64_t stride, const double *old_variables, const double *q,                  \
@@ -43,6 +50,8 @@
                            unsigned long long value, int *timed_out);                                                \
     void launch_min_publish(hipStream_t, const double *my_min, const MinPublish &mp);                                \
     void launch_append_scalar(hipStream_t, const double *src, double *ring, int *count, int cap);                    \
+    void launch_sumsq_original(hipStream_t, int64_t nel, int64_t stride, const double *x, const int32_t *new_of_old, \
+                               double *partial);                                                                     \
     void launch_min_over_peers(hipStream_t, const double *const *scalars, int n, double *out);                       \
     void launch_accept_restricted(hipStream_t, int64_t nel_coarse, int64_t stride_coarse, const int32_t *child_ptr,  \
                                   const double *src, double *coarse_q);                                              \
@@ -75,5 +84,6 @@ struct Launchers {
     decltype(exact::launch_residual) *residual;                      decltype(exact::launch_sumsq) *sumsq;
     decltype(exact::launch_restrict) *restrict_;                     decltype(exact::launch_prolong) *prolong;
     decltype(exact::launch_step_factor_nodal) *step_factor_nodal;    decltype(exact::launch_smooth) *smooth;
+    decltype(exact::launch_time_step_dual) *time_step_dual;          decltype(exact::launch_dual_source) *dual_source;
 };
 }

@@ -63,6 +63,15 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool smoothing_iterations_given = false;
     double smoothing_eps = 0.0;
     int smoothing_iterations = 2;     // (the default when only EPS is given)
+    // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
+    // physical_time_step / time_steps / dual_time_clamp / bdf_order.  With DT given, -g is the number of cycles per physical step.
+    bool dual_given = false;          // a DT was given: mgcfd_set_dual_time before the first cycle, mgcfd_advance for the cycles
+    bool dual_extras_given = false;   // one of the three companions was given (they need DT)
+    double dual_dt = 0.0, dual_clamp = MGCFD_DUAL_TIME_CLAMP;
+    int time_steps = 1, bdf_order = 2;
+    int steps() const { return dual_given ? time_steps : 1; }
+    int total_cycles() const { return (num_cycles > 0 ? num_cycles : 0) * steps(); }      // RMS lines of the run
+    int loads_rows() const { return dual_given ? time_steps : (num_cycles > 0 ? num_cycles : 0); }   // one row per physical step
     // the k-th angle of the run (one angle without --polar)
     int num_angles() const { return polar ? polar_n : 1; }
     double angle(int k) const { return !polar ? angle_of_attack : (polar_n == 1 ? polar_a0 : polar_a0 + (polar_a1 - polar_a0) * double(k) / double(polar_n - 1)); }
@@ -107,6 +116,16 @@ bool parse_smoothing_iterations(const char *text, int *out)
     *out = int(v);
     return true;
 }
+
+// a whole number lo ... hi (the physical time steps, the BDF order)
+bool parse_whole(const char *text, int lo, int hi, int *out)
+{
+    double v = 0.0;
+    if (!parse_number(text, &v) || v < double(lo) || v > double(hi) || v != double(int(v))) return false;
+    *out = int(v);
+    return true;
+}
+constexpr int kMaxTimeSteps = 1000000;
 
 // "A0:A1:N": two finite angles and a count of at least 1
 bool parse_polar(const char *text, Config &c)
@@ -184,6 +203,22 @@ void set_param(Config &c, const std::string &key, const std::string &value)
     else if (key == "smoothing_iterations") {
         if (parse_smoothing_iterations(value.c_str(), &c.smoothing_iterations)) c.smoothing_iterations_given = true;
         else { std::fprintf(stderr, "ERROR: smoothing_iterations = '%s': expected a whole number 0 ... %d\n", value.c_str(), MGCFD_MAX_SMOOTHING_ITERATIONS); c.config_bad = true; }
+    }
+    else if (key == "physical_time_step") {
+        if (parse_positive(value.c_str(), &c.dual_dt)) c.dual_given = true;
+        else { std::fprintf(stderr, "ERROR: physical_time_step = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "time_steps") {
+        if (parse_whole(value.c_str(), 1, kMaxTimeSteps, &c.time_steps)) c.dual_extras_given = true;
+        else { std::fprintf(stderr, "ERROR: time_steps = '%s': expected a whole number 1 ... %d\n", value.c_str(), kMaxTimeSteps); c.config_bad = true; }
+    }
+    else if (key == "dual_time_clamp") {
+        if (parse_positive(value.c_str(), &c.dual_clamp)) c.dual_extras_given = true;
+        else { std::fprintf(stderr, "ERROR: dual_time_clamp = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "bdf_order") {
+        if (parse_whole(value.c_str(), 1, 2, &c.bdf_order)) c.dual_extras_given = true;
+        else { std::fprintf(stderr, "ERROR: bdf_order = '%s': expected 1 or 2\n", value.c_str()); c.config_bad = true; }
     }
     else std::printf("WARNING: Unknown key '%s' encountered during parsing of config file.\n", key.c_str());
 }
@@ -267,7 +302,17 @@ void print_help()
         "                                   residual_smoothing): every stage's update goes through Jacobi iterations over the edge\n"
         "                                   graph, which lets --cfl be two or more times as large.  One GPU, or --gpus N with one\n"
         "                                   multigrid level per GPU; not with --gpus-partition or a level split over GPUs\n"
-        "  --smoothing-iterations=N         its Jacobi iterations, 0 ... 8 (default 2; 0 = off; config key smoothing_iterations)\n");
+        "  --smoothing-iterations=N         its Jacobi iterations, 0 ... 8 (default 2; 0 = off; config key smoothing_iterations)\n"
+        "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
+        "                                   (config key physical_time_step): BDF2 in physical time, every step solved in pseudo-time\n"
+        "                                   by -g cycles (-g becomes the cycles PER PHYSICAL STEP; an RMS line per cycle as ever,\n"
+        "                                   --output-loads one row per physical step, --output-variables the final state).  One GPU,\n"
+        "                                   or --gpus N with one multigrid level per GPU; not with --gpus-partition, a level split\n"
+        "                                   over GPUs or --polar\n"
+        "  --time-steps=N                   its number of physical steps (default 1; config key time_steps)\n"
+        "  --dual-time-clamp=X              the pseudo step is clamped to X * DT / volume (default 2/3; config key dual_time_clamp)\n"
+        "  --bdf-order=1|2                  1 keeps the first-order formula throughout (default 2: BDF1 on the first step, then BDF2;\n"
+        "                                   config key bdf_order)\n");
 }
 
 bool parse_arguments(int argc, char **argv, Config &c)
@@ -306,6 +351,10 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"cfl", required_argument, nullptr, 1019},
         {"residual-smoothing", required_argument, nullptr, 1020},
         {"smoothing-iterations", required_argument, nullptr, 1021},
+        {"physical-time-step", required_argument, nullptr, 1022},
+        {"time-steps", required_argument, nullptr, 1023},
+        {"dual-time-clamp", required_argument, nullptr, 1024},
+        {"bdf-order", required_argument, nullptr, 1025},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -380,11 +429,47 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 }
                 c.smoothing_iterations_given = true;
                 break;
+            case 1022:
+                if (!parse_positive(optarg, &c.dual_dt)) {
+                    std::fprintf(stderr, "ERROR: --physical-time-step=%s: expected a finite number above zero\n", optarg);
+                    return false;
+                }
+                c.dual_given = true;
+                break;
+            case 1023:
+                if (!parse_whole(optarg, 1, kMaxTimeSteps, &c.time_steps)) {
+                    std::fprintf(stderr, "ERROR: --time-steps=%s: expected a whole number 1 ... %d\n", optarg, kMaxTimeSteps);
+                    return false;
+                }
+                c.dual_extras_given = true;
+                break;
+            case 1024:
+                if (!parse_positive(optarg, &c.dual_clamp)) {
+                    std::fprintf(stderr, "ERROR: --dual-time-clamp=%s: expected a finite number above zero\n", optarg);
+                    return false;
+                }
+                c.dual_extras_given = true;
+                break;
+            case 1025:
+                if (!parse_whole(optarg, 1, 2, &c.bdf_order)) {
+                    std::fprintf(stderr, "ERROR: --bdf-order=%s: expected 1 or 2\n", optarg);
+                    return false;
+                }
+                c.dual_extras_given = true;
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
     if (c.smoothing_iterations_given && !c.smoothing_given && c.smoothing_iterations > 0) {
         std::fprintf(stderr, "ERROR: --smoothing-iterations needs --residual-smoothing EPS (the residual smoothing's coefficient)\n");
+        return false;
+    }
+    if (c.dual_extras_given && !c.dual_given) {
+        std::fprintf(stderr, "ERROR: --time-steps, --dual-time-clamp and --bdf-order need --physical-time-step DT (dual time stepping)\n");
+        return false;
+    }
+    if (c.dual_given && (c.num_cycles < 1 || c.num_cycles > MGCFD_MAX_ADVANCE_CYCLES)) {
+        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step): -g is the cycles per physical step, 1 ... %d\n", MGCFD_MAX_ADVANCE_CYCLES);
         return false;
     }
     return !c.config_bad;
@@ -537,14 +622,14 @@ int validate_and_dump(const Config &conf, int levels, int mesh_variant, int64_t 
     return 0;
 }
 
-// --output-loads: one row per cycle, the loads and their coefficients (nothing on stdout: it stays the reference's)
+// --output-loads: one row per cycle (dual time stepping: per physical step), the loads and their coefficients (nothing on stdout: it stays the reference's)
 int write_loads_csv(const Config &conf, const double ff17[17], const std::vector<double> &loads)
 {
     const std::string path = output_filepath(conf, "surface_loads", 0);
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
     std::fprintf(f, "cycle,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz\n");
-    for (int c = 0; c < conf.num_cycles; c++) {
+    for (int c = 0; c < conf.loads_rows(); c++) {
         const double *row = loads.data() + static_cast<size_t>(c) * 6;
         double coef[6];
         if (mgcfd_load_coefficients(ff17, row, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) {
@@ -622,23 +707,28 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
                      run.partitioned_hierarchy() ? "every level partitioned, level 0 by recursive coordinate bisection; the V-cycle inside the library" :
                      run.partitioned() ? "level 0 partitioned by recursive coordinate bisection" : "one multigrid level per GPU",
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count());
-        std::vector<double> rms(static_cast<size_t>(conf.num_cycles > 0 ? conf.num_cycles : 0));
+        std::vector<double> rms(static_cast<size_t>(conf.total_cycles()));
         const auto t0 = std::chrono::steady_clock::now();
-        std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
+        std::vector<double> loads((conf.output_loads || conf.polar) ? static_cast<size_t>(conf.loads_rows()) * 6 : 0);
         std::vector<PolarRow> polar_rows;
         if (conf.time_step_given && run.set_time_step(conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
         if (conf.smoothing_given && run.set_residual_smoothing(conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
         const int rc = run_all_cycles(conf, rms, loads, polar_rows,
             [&](double mach, double alpha, int reinitialise) { return run.set_free_stream(mach, alpha, reinitialise); },
             [&](double *rms_out, double *loads_out) {
+                // dual time stepping: switched on behind the free stream, so that the time levels start as the state
+                if (conf.dual_given) {
+                    const int rc_on = run.set_dual_time(conf.dual_dt, conf.dual_clamp, conf.bdf_order);
+                    return rc_on != MGCFD_OK ? rc_on : run.advance(conf.time_steps, conf.num_cycles, rms_out);
+                }
                 return loads_out ? run.run_cycles_loads(conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out) : run.run_cycles(conf.num_cycles, rms_out);
             });
         for (PolarRow &row : polar_rows) {          // (the coefficients of an angle are taken against that angle's far field)
             if (mgcfd_free_stream_constants(row.mach, row.alpha, row.ff17) != MGCFD_OK) return fail("the free stream of a polar row");
         }
         const double total_compute_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        for (int i = 0; i < conf.num_cycles; i++)
-            std::printf(levels <= 1 ? "\nCycle %d / %d (RMS = %.3e)" : "\nMG cycle %d / %d (RMS = %.3e)", i + 1, conf.num_cycles, rms[static_cast<size_t>(i)]);
+        for (int i = 0; i < conf.total_cycles(); i++)
+            std::printf(levels <= 1 ? "\nCycle %d / %d (RMS = %.3e)" : "\nMG cycle %d / %d (RMS = %.3e)", i + 1, conf.total_cycles(), rms[static_cast<size_t>(i)]);
         std::printf("\n");
         if (rc == MGCFD_ERR_NAN || rc == MGCFD_ERR_NEG_DENSITY || rc == MGCFD_ERR_NEG_ENERGY) {
             std::printf(rc == MGCFD_ERR_NAN ? "\nERROR: NaN detected!\n" : rc == MGCFD_ERR_NEG_DENSITY ? "\nERROR: Negative density detected!\n" : "\nERROR: Negative density.energy detected!\n");
@@ -667,7 +757,7 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
         std::vector<std::vector<std::string>> times(static_cast<size_t>(levels)), iters(static_cast<size_t>(levels));
         for (int l = 0; l < levels; l++) {
             int64_t n[MGCFD_NUM_LOOPS];
-            run.loop_iters(l, conf.num_cycles * conf.num_angles(), n);
+            run.loop_iters(l, conf.total_cycles() * conf.num_angles(), n);
             for (int k = 0; k < MGCFD_NUM_LOOPS; k++) { times[static_cast<size_t>(l)].push_back("0"); iters[static_cast<size_t>(l)].push_back(std::to_string(n[k])); }
         }
         const std::string tpath = csv_filepath(conf, "Times.csv"), ipath = csv_filepath(conf, "LoopNumIters.csv");
@@ -695,6 +785,14 @@ int main(int argc, char **argv)
     }
     if (conf.smoothing_given && conf.smoothing_iterations > 0 && conf.gpus > 1 && conf.gpus_partition) {
         std::fprintf(stderr, "ERROR: residual smoothing (--residual-smoothing) does not run with --gpus-partition: a level split over GPUs would need a halo exchange per Jacobi iteration\n");
+        return 1;
+    }
+    if (conf.dual_given && conf.gpus > 1 && conf.gpus_partition) {
+        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --gpus-partition: levels split over GPUs are out of scope\n");
+        return 1;
+    }
+    if (conf.dual_given && conf.polar) {
+        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --polar\n");
         return 1;
     }
     if (conf.polar && conf.gpus > 1 && !conf.gpus_partition) {
@@ -746,15 +844,37 @@ int main(int argc, char **argv)
     }
 
     // ---- compute (src/euler3d_cpu_double.cpp:368-698) ----
-    std::vector<double> rms(static_cast<size_t>(conf.num_cycles > 0 ? conf.num_cycles : 0));
+    std::vector<double> rms(static_cast<size_t>(conf.total_cycles()));
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> loads((conf.output_loads || conf.polar) ? rms.size() * 6 : 0);
+    std::vector<double> loads((conf.output_loads || conf.polar) ? static_cast<size_t>(conf.loads_rows()) * 6 : 0);
+    int steps_done = 0;               // dual time stepping: physical steps completed (an invalid state: the step it was found in)
     std::vector<PolarRow> polar_rows;
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
     if (conf.smoothing_given && mgcfd_set_residual_smoothing(solver, conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
         [&](double *rms_out, double *loads_out) {
+            if (conf.dual_given) {
+                // switched on behind the free stream, so that the time levels start as the state; mgcfd_advance takes at most
+                // MGCFD_MAX_ADVANCE_CYCLES cycles per call: whole physical steps per call
+                int rc_on = mgcfd_set_dual_time(solver, conf.dual_dt, conf.dual_clamp);
+                if (rc_on == MGCFD_OK) rc_on = mgcfd_dual_time_set_order(solver, conf.bdf_order);
+                if (rc_on != MGCFD_OK) return rc_on;
+                const int per_call = std::max(1, MGCFD_MAX_ADVANCE_CYCLES / conf.num_cycles);
+                for (steps_done = 0; steps_done < conf.time_steps;) {
+                    const int now = std::min(per_call, conf.time_steps - steps_done);
+                    const int rc_adv = mgcfd_advance(solver, now, conf.num_cycles, rms_out + size_t(steps_done) * size_t(conf.num_cycles),
+                                                     loads_out ? loads_out + size_t(steps_done) * 6 : nullptr, conf.loads_ref + 2);
+                    if (rc_adv != MGCFD_OK) {
+                        int bad_step = -1;
+                        mgcfd_get_dual_time(solver, nullptr, nullptr, nullptr, nullptr, &bad_step);
+                        if (bad_step >= 0) steps_done += bad_step;
+                        return rc_adv;
+                    }
+                    steps_done += now;
+                }
+                return int(MGCFD_OK);
+            }
             return loads_out ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out)
                              : mgcfd_run_cycles(solver, conf.num_cycles, rms_out);
         });
@@ -766,9 +886,10 @@ int main(int argc, char **argv)
     int bad_cycle = -1;
     if (invalid) mgcfd_invalid_state_location(solver, &bad_cell, &bad_cycle);
     // (the reference prints a cycle's line when the cycle starts and exits inside the failing time_step)
-    const int printed = invalid && bad_cycle >= 0 ? bad_cycle + 1 : conf.num_cycles;
+    if (invalid && bad_cycle >= 0 && conf.dual_given) bad_cycle += steps_done * conf.num_cycles;      // (counted through the physical steps)
+    const int printed = invalid && bad_cycle >= 0 ? bad_cycle + 1 : conf.total_cycles();
     for (int i = 0; i < printed; i++) {
-        std::printf(levels <= 1 ? "\nCycle %d / %d" : "\nMG cycle %d / %d", i + 1, conf.num_cycles);
+        std::printf(levels <= 1 ? "\nCycle %d / %d" : "\nMG cycle %d / %d", i + 1, conf.total_cycles());
         if (!(invalid && i == bad_cycle)) std::printf(" (RMS = %.3e)", rms[static_cast<size_t>(i)]);
     }
     std::printf("\n");

@@ -461,6 +461,31 @@ int Run::set_residual_smoothing(double eps, int iterations)
     return MGCFD_OK;
 }
 
+int Run::set_dual_time(double dt, double clamp, int order)
+{
+    // (every rank holds the whole hierarchy and sweeps its own levels: each keeps the time levels of all, and those of the
+    //  levels it sweeps are the ones its sweeps read; a group's ranks hold parts of a level: the library refuses them)
+    for (mgcfd_solver *s : p->solvers) {
+        int rc = mgcfd_set_dual_time(s, dt, clamp);
+        if (rc == MGCFD_OK && dt > 0.0) rc = mgcfd_dual_time_set_order(s, order);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
+int Run::advance(int steps, int cycles_per_step, double *rms_out)
+{
+    for (int step = 0; step < steps; step++) {
+        for (mgcfd_solver *s : p->solvers) {
+            const int rc = mgcfd_dual_time_begin_step(s);
+            if (rc != MGCFD_OK) return rc;
+        }
+        const int rc = run_cycles(cycles_per_step, rms_out ? rms_out + size_t(step) * size_t(cycles_per_step) : nullptr);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
 int Run::run_cycles(int cycles, double *rms_out)
 {
     const int n = p->levels, w = ranks();

@@ -34,6 +34,10 @@ public:
     int set_time_step(int mode, double cfl);
     // mgcfd_set_residual_smoothing on every rank (one multigrid level per rank only: MGCFD_ERR_ARG where a level is split)
     int set_residual_smoothing(double eps, int iterations);
+    // mgcfd_set_dual_time (+ the BDF order) on every rank, likewise; advance: steps x (mgcfd_dual_time_begin_step on every rank +
+    // cycles_per_step cycles), rms_out [steps * cycles_per_step]
+    int set_dual_time(double dt, double clamp, int order);
+    int advance(int steps, int cycles_per_step, double *rms_out);
     void get_level0(int which, int ncols, double *out) const;   // a level-0 array of the WHOLE mesh, original numbering
     int check_invalid(int level, int64_t *bad_cell) const;      // check_for_invalid_variables on `level` of the whole mesh (original cell id)
     void loop_iters(int level, int cycles, int64_t out[MGCFD_NUM_LOOPS]) const;

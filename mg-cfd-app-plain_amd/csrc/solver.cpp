@@ -174,6 +174,9 @@ struct DeviceLevel {
     double *sfb[2] = {nullptr, nullptr};
     void apply_sf() { step_factors = sfb[sf_par & 1]; sf_alt = sfb[(sf_par & 1) ^ 1]; }
     double *smooth_buf[2] = {nullptr, nullptr};   // [5][stride] each: the residual smoothing's iterates, alternating (allocated when it is first switched on)
+    double *time_n = nullptr, *time_n1 = nullptr;   // [5][stride] each: dual time stepping's time levels Wn and Wn1 (held while it is on)
+    const double *flux_in = nullptr;     // the state the last flux launch read: W of the dual-time source
+    int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while dual time is on: its RMS is summed in original numbering
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
     double *min_dt = nullptr;            // global-min time step scalar (after the reduction)
     double *partial_min = nullptr;       // one partial minimum per step-factor workgroup
@@ -307,6 +310,21 @@ struct mgcfd_solver {
     double irs_eps = 0.0;
     int irs_iters = 0;
     bool smoothing() const { return irs_iters > 0; }
+    // Dual time stepping (mgcfd_set_dual_time): dual_dt > 0 = on.  Every stage's update takes F - src for F (the BDF source of
+    // the physical step over W, Wn, Wn1) and the pseudo step is clamped to dual_clamp * dual_dt / vol.  While it is on a stage is
+    // one standalone flux launch + the dual time_step (or the source launch + the smoothing launches): no fused stage, no
+    // look-ahead, no graph.  dual_levels: time levels held (0: none yet, the next mgcfd_dual_time_begin_step stores one and
+    // BDF1 runs; 2: both, BDF2 runs unless dual_order is 1).
+    double dual_dt = 0.0, dual_clamp = 0.0;
+    int dual_order = 2, dual_levels = 0, dual_invalid_step = -1;
+    bool dual_time() const { return dual_dt > 0.0; }
+    DualSource dual_source(const DeviceLevel &lv) const
+    {
+        DualSource d;
+        d.w = lv.flux_in ? lv.flux_in : lv.q; d.wn = lv.time_n; d.wn1 = lv.time_n1; d.volumes = lv.volumes;
+        d.dt = dual_dt; d.order = (dual_order == 2 && dual_levels == 2) ? 2 : 1;
+        return d;
+    }
     // ff17 -> the kernels' argument (ff) and the loads' p_inf.  Launches already captured keep the old values: drop_graphs.
     void set_far_field(const double *in17)
     {
@@ -341,7 +359,7 @@ struct mgcfd_solver {
     {
 #define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
-                                NS::launch_step_factor_nodal, NS::launch_smooth}
+                                NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_dual, NS::launch_dual_source}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -451,12 +469,21 @@ struct mgcfd_solver {
             if (legacy_dt()) k().step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, cfl, lv.step_factors, old);
             else k().step_factor_nodal(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.volumes, cfl, lv.step_factors, old);
         } else {
-            op_step_factor_local(l, fused && copy_old, !fused);
-            if (fused) apply_pending = true;
-            else op_step_factor_apply(l);
+            // (dual time stepping clamps final step factors: nothing is left to the first time_step then)
+            const bool finish = !fused || dual_time();
+            op_step_factor_local(l, fused && copy_old, finish);
+            if (finish) op_step_factor_apply(l);
+            else apply_pending = true;
         }
+        if (dual_time()) clamp_step_factors(l);
         lv.iters[MGCFD_LOOP_COMPUTE_STEP] += lv.info.nel;
         return apply_pending;
+    }
+    // dual time stepping: sf = min(sf, (clamp * dt) / vol) on final step factors, before stage 0
+    void clamp_step_factors(int l)
+    {
+        DeviceLevel &lv = level(l);
+        exact::launch_dual_clamp(stream, lv.info.nel, dual_clamp * dual_dt, lv.volumes, lv.step_factors);
     }
     // The parts of a level's plan that only a non-default option reaches are uploaded when an option first asks for them
     // (at creation: nothing but the 32-bit neighbour codes of levels whose indirect_rw probe runs the L1-gather form).  Called
@@ -547,6 +574,7 @@ struct mgcfd_solver {
         if ((variant & 4) && !lv.dp.edge_flux)              // two-phase design point: edge-flux scratch on first use
             lv.dp.edge_flux = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
         k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr, nullptr);
+        if (dual_time()) lv.flux_in = lv.q;
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
         if (classes & 1) lv.iters[MGCFD_LOOP_FLUX] += lv.info.n_internal;
@@ -632,6 +660,9 @@ struct mgcfd_solver {
             Timed t(this, l, MGCFD_LOOP_TIME_STEP);
             if (apply_min == ApplyMin::Partials) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
             if (apply_min != ApplyMin::None) op_step_factor_apply(l);
+            // dual time stepping: F' = F - src into fluxes[] first, in a node-wise launch of its own — the first iteration forms
+            // D = sf * F' for halo nodes too, which would read three more states per staged node inside k_smooth_tile
+            if (dual_time()) k().dual_source(stream, lv.info.nel, lv.dp.stride, lv.fluxes, dual_source(lv));
             SmoothStep a;
             a.fluxes = lv.fluxes; a.step_factors = lv.step_factors; a.eps = irs_eps;
             for (int m = 0; m < irs_iters; m++) {
@@ -650,6 +681,16 @@ struct mgcfd_solver {
             return;
         }
         Timed t(this, l, MGCFD_LOOP_TIME_STEP);
+        if (dual_time()) {
+            // the update with F - src for F, in the one launch; the step factors are final and clamped (op_step_factor)
+            if (apply_min != ApplyMin::None) throw std::invalid_argument("dual time: the step factors must be final before time_step");
+            k().time_step_dual(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, next_check(),
+                               with_residual ? lv.residuals : nullptr, dual_source(lv));
+            lv.fluxes_stale = true;                 // (never written: logically zero, as after a lazy time_step)
+            lv.fluxes_zero = true;
+            lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
+            return;
+        }
         const double *pm = apply_min == ApplyMin::Partials ? lv.partial_min : (apply_min == ApplyMin::Scalar ? lv.min_dt : nullptr);
         const int n_pm = apply_min == ApplyMin::Scalar ? 1 : static_cast<int>((lv.info.nel + 255) / 256);
         double *res = with_residual ? lv.residuals : nullptr;
@@ -1532,7 +1573,7 @@ int mgcfd_step_factor_local(mgcfd_solver *s, int level)
 }
 int mgcfd_step_factor_min_devptr(mgcfd_solver *s, int level, void **devptr)
 { REQUIRE(devptr); OP(*devptr = s->level(level).min_dt); }
-int mgcfd_step_factor_apply(mgcfd_solver *s, int level) { OP(s->op_step_factor_apply(level)); }
+int mgcfd_step_factor_apply(mgcfd_solver *s, int level) { OP({ s->op_step_factor_apply(level); if (s->dual_time()) s->clamp_step_factors(level); }); }
 int mgcfd_residual_sumsq(mgcfd_solver *s, int level, void **devptr)
 { REQUIRE(devptr); OP({ s->op_sumsq(level); *devptr = s->level(level).sumsq; }); }
 
@@ -1542,7 +1583,14 @@ int mgcfd_calc_rms(mgcfd_solver *s, int level, double *rms)
     return guarded([&] {
         s->use_device();
         DeviceLevel &lv = s->level(level);
-        s->op_sumsq(level);
+        if (s->dual_time() && level == 0) {
+            // the order dual time stepping fixes for the level-0 sum (mgcfd.h), as the cycle driver runs it
+            s->settle_residuals(lv);
+            exact::launch_sumsq_original(s->stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.new_of_old_dev, lv.tile_sumsq);
+            exact::launch_sum_partials_append(s->stream, static_cast<int>((lv.info.nel + 255) / 256), lv.tile_sumsq, lv.sumsq, nullptr, nullptr, 0);
+        } else {
+            s->op_sumsq(level);
+        }
         double sum = 0.0;
         HIP_CHECK(hipMemcpyAsync(&sum, lv.sumsq, sizeof(double), hipMemcpyDeviceToHost, s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -1598,7 +1646,7 @@ static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 static void smooth_once(mgcfd_solver *s, int level)
 {
     DeviceLevel &lv = s->level(level);
-    if (s->opt_fuse && !s->smoothing() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
+    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
         // Fused stages: flux + time_step in one launch each.  No copy<double>(old_variables, variables)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
@@ -1679,7 +1727,7 @@ static void run_sweep(mgcfd_solver *s, int level)
     }
     // (only the fused launches are replayed: the unfused ones — the two-phase flux variant — leave host-side flags
     //  behind, fluxes_stale, that a replay would not set)
-    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
+    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
     if (!graphable) {
         const int keep = s->opt_timing;
         if (!timed) s->opt_timing = 0;
@@ -1731,6 +1779,7 @@ static void run_sweep(mgcfd_solver *s, int level)
 static void require_no_smoothing(const mgcfd_solver *s, const char *who)
 {
     if (s->smoothing()) throw std::invalid_argument(std::string(who) + ": not while residual smoothing is on (mgcfd_set_residual_smoothing; use mgcfd_smooth or the kernel-granular calls)");
+    if (s->dual_time()) throw std::invalid_argument(std::string(who) + ": not while dual time stepping is on (mgcfd_set_dual_time; use mgcfd_smooth or the kernel-granular calls)");
 }
 // The same sweep split around the one collective a multi-GPU run needs (see mgcfd.h).
 static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
@@ -1930,6 +1979,13 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
                 // ... single level: one small launch does
                 exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
                                                   s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+            } else if (s->dual_time()) {
+                // dual time stepping defines the order of this sum on the original numbering (mgcfd.h): per-workgroup sums
+                // of 256 original nodes into tile_sumsq (no fused stage fills it while dual time is on), then their sum
+                s->settle_residuals(l0);
+                exact::launch_sumsq_original(s->stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
+                exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
+                                                  s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else {
                 s->op_sumsq(0);
                 exact::launch_append_scalar(s->stream, l0.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
@@ -1969,7 +2025,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2107,6 +2163,9 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
         case MGCFD_ARR_RESIDUALS: return lv.residuals;
         case MGCFD_ARR_STEP_FACTORS: *ncols = 1; return lv.step_factors;
         case MGCFD_ARR_VOLUMES: *ncols = 1; return lv.volumes;
+        case MGCFD_ARR_TIME_N: case MGCFD_ARR_TIME_N1:
+            if (!lv.time_n) throw std::invalid_argument("MGCFD_ARR_TIME_N / _TIME_N1: dual time stepping is off (mgcfd_set_dual_time)");
+            return which == MGCFD_ARR_TIME_N ? lv.time_n : lv.time_n1;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2155,6 +2214,9 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         HIP_CHECK(hipStreamSynchronize(s->stream));
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
+        // a restart: a time level written is a time level held
+        if (which == MGCFD_ARR_TIME_N) s->dual_levels = std::max(s->dual_levels, 1);
+        if (which == MGCFD_ARR_TIME_N1) s->dual_levels = 2;
     });
 }
 int mgcfd_array_devptr(mgcfd_solver *s, int level, int which, void **devptr, int64_t *count)
@@ -4551,6 +4613,118 @@ int mgcfd_load_coefficients(const double ff17[17], const double loads6[6], doubl
     out6[1] = (-loads6[0] * sa + loads6[1] * ca) / qs;    // CL
     out6[2] = loads6[2] / qs;                             // CS
     for (int k = 0; k < 3; k++) out6[3 + k] = loads6[3 + k] / qsc;
+    return MGCFD_OK;
+}
+
+// ---- dual time stepping: the physical step, its time levels, the driver loop ----
+static void require_dual_time(const mgcfd_solver *s, const char *who)
+{
+    if (!s->dual_time()) throw std::invalid_argument(std::string(who) + ": dual time stepping is off (mgcfd_set_dual_time)");
+}
+int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (!std::isfinite(dt) || dt < 0.0) throw std::invalid_argument("dual time: the physical step must be finite and positive (0 switches it off)");
+        const bool on = dt > 0.0;
+        if (on && (!std::isfinite(clamp) || !(clamp > 0.0))) throw std::invalid_argument("dual time: the clamp must be finite and positive");
+        if (on && (s->partitioned || s->comm))
+            throw std::invalid_argument("dual time: not on a partitioned solver or a rank (levels split over ranks are out of scope)");
+        require_no_sweep_under_way(s, "dual time");
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);
+        s->drop_graphs();
+        if (on && !s->dual_time()) {
+            // switched on: both levels start as the current state (sweeps before the first begin_step see BDF1 against it)
+            for (DeviceLevel &lv : s->L) {
+                lv.flux_in = nullptr;               // (no flux launch has run under dual time yet: W is `variables`)
+                if (!lv.time_n) lv.time_n = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
+                if (!lv.time_n1) lv.time_n1 = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
+            }
+            if (!s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
+            for (DeviceLevel &lv : s->L) exact::launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, 1);
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            HIP_CHECK(hipGetLastError());
+            s->dual_levels = 0;
+            s->dual_invalid_step = -1;
+        }
+        if (!on) {
+            for (DeviceLevel &lv : s->L) { lv.mem.release(lv.time_n); lv.mem.release(lv.time_n1); lv.mem.release(lv.new_of_old_dev); lv.flux_in = nullptr; }
+            s->dual_levels = 0;
+        }
+        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
+        s->dual_dt = dt;
+        s->dual_clamp = on ? clamp : 0.0;
+    });
+}
+int mgcfd_get_dual_time(const mgcfd_solver *s, double *dt, double *clamp, int *order, int *levels, int *invalid_step)
+{
+    REQUIRE(s);
+    if (dt) *dt = s->dual_dt;
+    if (clamp) *clamp = s->dual_clamp;
+    if (order) *order = s->dual_order;
+    if (levels) *levels = s->dual_levels;
+    if (invalid_step) *invalid_step = s->dual_invalid_step;
+    return MGCFD_OK;
+}
+int mgcfd_dual_time_set_order(mgcfd_solver *s, int order)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        require_dual_time(s, "mgcfd_dual_time_set_order");
+        if (order != 1 && order != 2) throw std::invalid_argument("dual time: the order is 1 (BDF1) or 2 (BDF2)");
+        require_no_sweep_under_way(s, "dual time");
+        s->dual_order = order;
+    });
+}
+int mgcfd_dual_time_reset(mgcfd_solver *s)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        require_dual_time(s, "mgcfd_dual_time_reset");
+        require_no_sweep_under_way(s, "dual time");
+        s->dual_levels = 0;
+    });
+}
+// Wn1 <- Wn, Wn <- variables on every level (the first step: both <- variables); asynchronous on the solver's stream
+static void dual_begin_step(mgcfd_solver *s)
+{
+    require_dual_time(s, "mgcfd_dual_time_begin_step");
+    require_no_sweep_under_way(s, "dual time");
+    for (DeviceLevel &lv : s->L)
+        exact::launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, s->dual_levels == 0 ? 1 : 0);
+    s->dual_levels = s->dual_levels == 0 ? 1 : 2;
+}
+int mgcfd_dual_time_begin_step(mgcfd_solver *s) { OP(dual_begin_step(s)); }
+int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
+{
+    REQUIRE(s);
+    int rc = guarded([&] {
+        require_dual_time(s, "mgcfd_advance");
+        if (steps < 0 || cycles_per_step < 1) throw std::invalid_argument("mgcfd_advance (dual time): steps >= 0 and cycles_per_step >= 1");
+        if (int64_t(steps) * cycles_per_step > MGCFD_MAX_ADVANCE_CYCLES)
+            throw std::invalid_argument("mgcfd_advance (dual time): at most " + std::to_string(MGCFD_MAX_ADVANCE_CYCLES) + " cycles per call (steps * cycles_per_step)");
+        if (loads_out) loads_require_whole(s);
+        s->dual_invalid_step = -1;
+    });
+    if (rc != MGCFD_OK) return rc;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int step = 0; step < steps; step++) {
+        double *rms = rms_out ? rms_out + size_t(step) * size_t(cycles_per_step) : nullptr;
+        rc = mgcfd_dual_time_begin_step(s);
+        if (rc == MGCFD_OK) rc = run_cycles_impl(s, cycles_per_step, rms, nullptr, nullptr);
+        if (rc == MGCFD_OK && loads_out) rc = mgcfd_surface_loads(s, 0, ref_point, loads_out + size_t(step) * 6);
+        if (rc == MGCFD_OK) continue;
+        // as mgcfd_run_cycles: what did not complete is NaN (the failing step's RMS entries are already), later steps do not run
+        if (rc >= MGCFD_ERR_NAN && rc <= MGCFD_ERR_NEG_ENERGY) s->dual_invalid_step = step;
+        for (int k = step + 1; rms_out && k < steps; k++)
+            for (int c = 0; c < cycles_per_step; c++) rms_out[size_t(k) * size_t(cycles_per_step) + size_t(c)] = nan;
+        for (int k = step; loads_out && k < steps; k++)
+            for (int c = 0; c < 6; c++) loads_out[size_t(k) * 6 + size_t(c)] = nan;
+        return rc;
+    }
     return MGCFD_OK;
 }
 

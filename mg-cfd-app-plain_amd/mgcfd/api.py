@@ -23,7 +23,8 @@ LIB_PATH = os.environ.get("MGCFD_LIB") or os.path.join(CSRC_DIR, "libmgcfd_hip.s
 NVAR = 5
 RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
-ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6}
+ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
+       "time_n": 7, "time_n1": 8}
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -180,6 +181,13 @@ _SIGNATURES = [
     ("mgcfd_set_residual_smoothing", C.c_int, [_vp, C.c_double, C.c_int]),
     ("mgcfd_get_residual_smoothing", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("mgcfd_bench_residual_smoothing", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_dual_time", C.c_int, [_vp, C.c_double, C.c_double]),
+    ("mgcfd_get_dual_time", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int)]),
+    ("mgcfd_dual_time_set_order", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_dual_time_reset", C.c_int, [_vp]),
+    ("mgcfd_dual_time_begin_step", C.c_int, [_vp]),
+    ("mgcfd_advance", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -577,6 +585,54 @@ class Solver:
         e, m = C.c_double(), C.c_int()
         self._c(self.lib.mgcfd_get_residual_smoothing(self.handle, C.byref(e), C.byref(m)))
         return e.value, m.value
+
+    # ---- dual time stepping ----
+    def set_dual_time(self, dt: float, clamp: float = 2.0 / 3.0):
+        """Time-accurate runs (mgcfd_set_dual_time): every stage's update carries the BDF source of the physical step ``dt`` and
+        the pseudo step is clamped to ``clamp * dt / vol``; ``dt=0`` switches it off and releases the time levels.  The state
+        stays; captured graphs are dropped.  Not on partitioned solvers or ranks."""
+        self._c(self.lib.mgcfd_set_dual_time(self.handle, float(dt), float(clamp)))
+
+    def dual_time(self) -> dict:
+        """``dt`` (0.0 when off), ``clamp``, ``order`` (1 or 2), ``levels`` (time levels held: 0, 1 or 2) and ``invalid_step``
+        (the physical step of the last ``advance`` that found an invalid state, or -1)."""
+        dt, cl, o, n, bad = C.c_double(), C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        self._c(self.lib.mgcfd_get_dual_time(self.handle, C.byref(dt), C.byref(cl), C.byref(o), C.byref(n), C.byref(bad)))
+        return {"dt": dt.value, "clamp": cl.value, "order": o.value, "levels": n.value, "invalid_step": bad.value}
+
+    def dual_time_order(self, n: int):
+        """1 keeps BDF1 throughout; 2 (the default) runs BDF2 from the second physical step on."""
+        self._c(self.lib.mgcfd_dual_time_set_order(self.handle, int(n)))
+
+    def dual_time_reset(self):
+        """The next ``begin_step`` starts again: both time levels become the state and BDF1 runs."""
+        self._c(self.lib.mgcfd_dual_time_reset(self.handle))
+
+    def begin_step(self):
+        """A physical step begins: Wn1 <- Wn, Wn <- variables on every level (mgcfd_dual_time_begin_step)."""
+        self._c(self.lib.mgcfd_dual_time_begin_step(self.handle))
+
+    def advance(self, steps: int, cycles_per_step: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
+        """``steps`` physical steps of ``begin_step`` + ``cycles_per_step`` V-cycles (mgcfd_advance): the RMS of every cycle
+        ``[steps, cycles_per_step]``; with ``loads=True`` also the level-0 surface loads at the end of every physical step:
+        ``(rms, loads[steps, 6])``.  An invalid state raises MgcfdError with ``.rms``, ``.loads`` (NaN from the failing cycle on)
+        and ``.step`` (the physical step it was found in)."""
+        rms = np.zeros(max(steps * cycles_per_step, 1))
+        out = np.zeros((max(steps, 1), 6))
+        ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
+        rc = self.lib.mgcfd_advance(self.handle, int(steps), int(cycles_per_step), _ptr(rms), _ptr(out) if loads else None, _ptr(ref))
+        if rc in (4, 5, 6):
+            # an invalid state: the error carries what the call filled (NaN from the failing cycle on) and the physical step
+            try:
+                self._c(rc)
+            except MgcfdError as e:
+                e.rms = rms[:steps * cycles_per_step].reshape(steps, cycles_per_step)
+                e.loads = out[:steps] if loads else None
+                e.step = self.dual_time()["invalid_step"]
+                raise
+        self._c(rc)
+        rms = rms[:steps * cycles_per_step].reshape(steps, cycles_per_step) if cycles_per_step > 0 else rms[:0]
+        return (rms, out[:steps]) if loads else rms
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
