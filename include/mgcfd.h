@@ -53,7 +53,9 @@ enum { MGCFD_LOOP_FLUX = 0, MGCFD_LOOP_UPDATE, MGCFD_LOOP_COMPUTE_STEP, MGCFD_LO
 enum { MGCFD_ARR_VARIABLES = 0, MGCFD_ARR_OLD_VARIABLES, MGCFD_ARR_FLUXES, MGCFD_ARR_RESIDUALS,
        MGCFD_ARR_STEP_FACTORS, MGCFD_ARR_VOLUMES,
        MGCFD_ARR_STAGE /* the state the last mgcfd_sweep_stage wrote (halo messages between the stages of a split sweep) */,
-       MGCFD_ARR_TIME_N, MGCFD_ARR_TIME_N1 /* dual time stepping's time levels Wn and Wn1 (while mgcfd_set_dual_time has it on) */ };
+       MGCFD_ARR_TIME_N, MGCFD_ARR_TIME_N1 /* dual time stepping's time levels Wn and Wn1 (while mgcfd_set_dual_time has it on) */,
+       MGCFD_ARR_JST_LAPLACIAN, MGCFD_ARR_JST_SENSOR, MGCFD_ARR_JST_RADIUS /* read-only: L [nel][5], nu [nel] and r [nel] of the last
+                                 flux launch of a level the JST dissipation is on for (mgcfd_set_jst) */ };
 
 /* Solver options (mgcfd_set_option) */
 enum {
@@ -383,6 +385,45 @@ int mgcfd_dual_time_set_order(mgcfd_solver *s, int order);
 int mgcfd_dual_time_reset(mgcfd_solver *s);
 int mgcfd_dual_time_begin_step(mgcfd_solver *s);
 int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3]);
+/* JST dissipation (Jameson, Schmidt, Turkel 1981): the reference's scalar first-difference dissipation, 0.2 * spectral radius *
+ * (W_i - W_j) on every internal edge, is kept only where a pressure sensor sees a shock; elsewhere a small fourth difference
+ * takes over.  No reference counterpart.  Per solver: kappa2 >= 0, kappa4 >= 0 (finite, in units of the reference's own
+ * dissipation: the textbook pair k2 = 1/2, k4 = 1/32 is MGCFD_JST_KAPPA2 = 2.5, MGCFD_JST_KAPPA4 = 0.15625) and levels >= 0: it
+ * runs on levels 0 .. levels-1 (capped at the number of levels; 0 = off).  On such a level stage j of every sweep computes its
+ * fluxes F from the stage's input state W as before (internal, solid wall, far field) and then, over the level's internal
+ * edges only, in the level's original edge order, every operation one IEEE-754 double operation, never contracted to FMA
+ * under MGCFD_OPT_EXACT = 1:
+ *   pass 1, node i:   p_i = the reference's pressure (velocities by division, speed_sqd left to right,
+ *                     (GAMMA-1)*(en - 0.5*rho*speed_sqd));  r_i = sqrt(speed_sqd_i) + sqrt(GAMMA * p_i / rho_i);
+ *                     sums from +0.0, one addition per internal edge (i, j) at i:  L_i[v] += W_j[v] - W_i[v];
+ *                     Pm_i += p_j - p_i;  Pp_i += p_j + p_i;   nu_i = fabs(Pm_i) / Pp_i  (no internal edge: 0.0)
+ *   pass 2, node i:   C_i[v] from +0.0, over the same edges in the same order, k_e = -|e| * (double)0.2f * 0.5:
+ *                     fac = k_e * (r_i + r_j);  nu = nu_i > nu_j ? nu_i : nu_j;
+ *                     e2 = kappa2 * nu;  e2 = e2 < 1.0 ? e2 : 1.0;   e4 = kappa4 - e2;  e4 = e4 > 0.0 ? e4 : 0.0;
+ *                     C_i[v] += fac * ((e2 - 1.0) * (W_i[v] - W_j[v]) - e4 * (L_i[v] - L_j[v]))
+ *                     F[i][v] = F[i][v] + C_i[v]
+ * With the first-difference term already inside F the edge's dissipation is fac * (e2 * (W_i - W_j) - e4 * (L_i - L_j)):
+ * never more than the reference's, and the reference's where e2 = 1.  Everything behind F sees F + C: time_step, the
+ * dual-time source and clamp, the residual smoothing, residual, RMS, loads.  Step factors are unchanged.
+ * While it is on for level 0 the RMS of a cycle is summed in the order dual time stepping fixes on the original numbering
+ * (above), so a history is reproducible bit for bit.
+ * Launches: on a JST level a stage is one standalone flux launch, the sensor launch, the dissipation launch, then the update
+ * the other settings select; fused flux + time_step stages, the step-factor look-ahead and captured graphs are not used on
+ * that level (MGCFD_OPT_GRAPH is accepted and the launches run directly); other levels launch and compute what they did.
+ * mgcfd_compute_fluxes and mgcfd_compute_flux_edge include both passes on a JST level (the boundary and far-field calls do
+ * not: call them first, or use mgcfd_compute_fluxes, for F + C as defined).  MGCFD_OPT_EXACT = 0 may contract and may take the
+ * order-free kernel for F; the two passes keep edge order.  Timed as MGCFD_LOOP_FLUX; LoopNumIters counts are unchanged.
+ * mgcfd_set_jst synchronises and drops every captured graph; the state stays.  The first enabling call allocates seven [stride]
+ * arrays (L [5], nu, r) per JST level; a solver it is never called on holds what it held.  MGCFD_ERR_ARG, and nothing
+ * changed: a negative or non-finite coefficient; levels < 0; levels > 0 with both coefficients zero; while a kernel-granular
+ * sweep is under way; levels > 0 on a solver made by mgcfd_create_partitioned* or attached to a group or as a rank (a split
+ * level would need L, nu and r exchanged per stage: out of scope).  While it is on, mgcfd_sweep_begin*, mgcfd_sweep_flux0,
+ * mgcfd_sweep_stage and mgcfd_sweep_end* return MGCFD_ERR_ARG, and mgcfd_group_create and mgcfd_rank_attach_* refuse the solver.
+ * mgcfd_get_jst: any pointer may be NULL; *levels is the capped number, 0 when off (the coefficients are then reported as 0). */
+#define MGCFD_JST_KAPPA2 2.5
+#define MGCFD_JST_KAPPA4 0.15625
+int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels);
+int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *levels);
 
 /* ---------------------------------------------------------------------------------
  * Kernel-granular operations (asynchronous on the solver's stream)
@@ -503,6 +544,9 @@ int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_secon
  * which forms D on load; 1: a middle one; 2: the last, which applies the update — here into the second state buffer, without
  * check or residual, so the state stays), behind one flux launch.  MGCFD_ERR_ARG while the smoothing is off. */
 int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* Diagnostic: the same for one of the JST dissipation's launches (kind 0: the sensor, 1: the dissipation, which adds into
+ * fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where it is off. */
+int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* The same for the indirect_rw probe (src/Kernels/indirect_rw_loop.cpp:8-78; fluxes += ..., accumulating over the
  * launches): the empirical data-movement ceiling of the flux kernel on this level's tiles. */
 int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *avg_seconds);

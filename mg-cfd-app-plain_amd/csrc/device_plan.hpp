@@ -120,6 +120,17 @@ struct SmoothStep {
     int check = 0;
 };
 
+// The two launches of the JST dissipation (kernels.hip: k_jst_sensor_tile, k_jst_dissipation_tile; mgcfd_set_jst): the sensor
+// writes lap, nu and r from w; the dissipation reads all four and adds the correction C into fluxes.
+struct JstStep {
+    const double *w = nullptr;                // the stage's input state W [5][stride]: what the fluxes were computed from
+    double *lap = nullptr;                    // L [5][stride]: the undivided Laplacian of W over the internal edges
+    double *nu = nullptr;                     // [stride] the pressure sensor
+    double *r = nullptr;                      // [stride] the spectral radius |v| + c
+    double *fluxes = nullptr;                 // the stage's fluxes F [5][stride] (dissipation only): F = F + C
+    double kappa2 = 0.0, kappa4 = 0.0;
+};
+
 // The physical-time source of dual time stepping (kernels.hip: k_time_step_dual, k_dual_source; mgcfd_set_dual_time):
 //   src = vol * ((3 (W - Wn) - (Wn - Wn1)) / (2 dt))   order 2 (BDF2);   src = vol * ((W - Wn) / dt)   order 1 (BDF1, Wn1 not read)
 struct DualSource {

@@ -2428,6 +2428,173 @@ k_smooth_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t s
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// JST dissipation (no reference counterpart; INTEGRATION.md "JST dissipation"): the pressure-switched blend of second and
+// fourth differences as a CORRECTION C added to the stage's fluxes F, which already hold the reference's first-difference term
+// k_e (r_i + r_j) (W_i - W_j) on every internal edge.  Two node-centred gathers over the internal incidence rows in row order,
+// the walk k_smooth_tile does (halo table, nbr16, overflow list, long-row lists), sums started at +0.0, one addition per edge:
+//   k_jst_sensor_tile       L_i = sum (W_j - W_i),  nu_i = |sum (p_j - p_i)| / sum (p_j + p_i)  (no internal edge: 0.0),
+//                           r_i = |v_i| + c_i;  p and r are derive()'s expressions.
+//   k_jst_dissipation_tile  C_i = sum fac ((e2 - 1) (W_i - W_j) - e4 (L_i - L_j)),  fac = k_e (r_i + r_j),
+//                           e2 = min(kappa2 max(nu_i, nu_j), 1),  e4 = max(kappa4 - e2, 0);  fluxes_i = fluxes_i + C_i.
+// LDS, one field per array as in k_smooth_tile (a slot's doubles 8 B apart): the sensor stages W and the pressure derived
+// once per slot (six fields of 560 doubles, 26,880 B); the dissipation stages W, L, nu and r (twelve fields, 53,760 B, under
+// the 64 KB of static LDS; two workgroups per CU by LDS).  A halo node beyond the table is read — and for the sensor derived —
+// from memory.  Pad lanes of the last tile write zeros to L, nu and r so that whoever stages them reads numbers.
+// ------------------------------------------------------------------------------------------
+template <bool TAIL>
+__global__ void __launch_bounds__(kBlock, 4)
+k_jst_sensor_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
+                  const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
+                  const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf, TailPlan tp, JstStep a)
+{
+    __shared__ double rec[6][kSmoothRow];                              // W [5] and p
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
+    const int64_t i = int64_t(t) * kTile + tid;
+    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
+    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
+    const int32_t hid = hrow[tid];
+    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;
+    const int32_t row0 = slice_row0[slice];
+    const int32_t n_int = (TAIL ? tp.rows_main : rows_int)[slice];
+    const int32_t ovf0 = tile_ovf_ptr[t];
+    const int64_t hnode = hid >= 0 ? int64_t(hid) : i;                 // (no halo node: a copy of the own one in the unused slot)
+    auto stage = [&](uint32_t slot, int64_t n) {
+        const double rho = a.w[n], mx = a.w[stride + n], my = a.w[2 * stride + n], mz = a.w[3 * stride + n], en = a.w[4 * stride + n];
+        const Derived d = derive(rho, mx, my, mz, en);
+        rec[0][slot] = rho; rec[1][slot] = mx; rec[2][slot] = my; rec[3][slot] = mz; rec[4][slot] = en; rec[5][slot] = d.p;
+    };
+    uint32_t c = nbr16[(int64_t(n_int > 0 ? row0 : 0) << 6) + lane];   // (row 0 exists on every level; unused when n_int == 0)
+    const double w0 = a.w[i], w1 = a.w[stride + i], w2 = a.w[2 * stride + i], w3 = a.w[3 * stride + i], w4 = a.w[4 * stride + i];
+    const Derived me = derive(w0, w1, w2, w3, w4);
+    rec[0][tid] = w0; rec[1][tid] = w1; rec[2][tid] = w2; rec[3][tid] = w3; rec[4][tid] = w4; rec[5][tid] = me.p;
+    stage(uint32_t(kTile + tid), hnode);
+    if (hid2 >= 0) stage(uint32_t(kTile + kBlock + tid), hid2);
+    int32_t tl_b = 0, tl_n = 0;
+    if (TAIL) { tl_b = tp.begin[i]; tl_n = tp.count[i]; }
+    __syncthreads();
+
+    double l0 = 0.0, l1 = 0.0, l2 = 0.0, l3 = 0.0, l4 = 0.0, pm = 0.0, pp = 0.0;
+    int32_t n_edges = 0;
+    auto add = [&](uint32_t code) {
+        const uint32_t s = code & kT16SlotMask;
+        if (s == kT16Pad) return;
+        double v0, v1, v2, v3, v4, p;
+        if (s >= uint32_t(kTileCap)) {
+            const int64_t n = tile_ovf[ovf0 + int32_t(s) - kTileCap];
+            v0 = a.w[n]; v1 = a.w[stride + n]; v2 = a.w[2 * stride + n]; v3 = a.w[3 * stride + n]; v4 = a.w[4 * stride + n];
+            p = derive(v0, v1, v2, v3, v4).p;
+        } else { v0 = rec[0][s]; v1 = rec[1][s]; v2 = rec[2][s]; v3 = rec[3][s]; v4 = rec[4][s]; p = rec[5][s]; }
+        l0 += v0 - w0; l1 += v1 - w1; l2 += v2 - w2; l3 += v3 - w3; l4 += v4 - w4;
+        pm += p - me.p;
+        pp += p + me.p;
+        n_edges++;
+    };
+    for (int32_t r = 0; r < n_int; r++) {                             // the codes one row ahead of the sums
+        const uint32_t cn = r + 1 < n_int ? nbr16[(int64_t(row0 + r + 1) << 6) + lane] : kT16Pad;
+        add(c);
+        c = cn;
+    }
+    if (TAIL) {
+        for (int32_t k = 0; k < tl_n; k++) {
+            const unsigned long long word = static_cast<unsigned long long>(__double_as_longlong(tp.rec[3 * int64_t(tl_b + k) + 2].x));
+            add(static_cast<uint32_t>(word >> 16) & 0xFFFFu);
+        }
+    }
+    const bool present = i < nel;
+    a.lap[i] = present ? l0 : 0.0; a.lap[stride + i] = present ? l1 : 0.0; a.lap[2 * stride + i] = present ? l2 : 0.0;
+    a.lap[3 * stride + i] = present ? l3 : 0.0; a.lap[4 * stride + i] = present ? l4 : 0.0;
+    a.nu[i] = (present && n_edges > 0) ? fabs(pm) / pp : 0.0;
+    a.r[i] = present ? me.speed + me.c : 0.0;
+}
+
+template <bool TAIL>
+__global__ void __launch_bounds__(kBlock, 2)
+k_jst_dissipation_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
+                       const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
+                       const double *__restrict__ w, const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf,
+                       TailPlan tp, JstStep a)
+{
+    __shared__ double rec[12][kSmoothRow];                             // W [5], L [5], nu, r
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
+    const int64_t i = int64_t(t) * kTile + tid;
+    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
+    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
+    const int32_t hid = hrow[tid];
+    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;
+    const int32_t row0 = slice_row0[slice];
+    const int32_t n_int = (TAIL ? tp.rows_main : rows_int)[slice];
+    const int32_t ovf0 = tile_ovf_ptr[t];
+    const int64_t hnode = hid >= 0 ? int64_t(hid) : i;                 // (no halo node: a copy of the own one in the unused slot)
+    struct Node { double w[5], l[5], nu, r; };
+    auto load = [&](int64_t n) {
+        Node q;
+        for (int v = 0; v < 5; v++) { q.w[v] = a.w[v * stride + n]; q.l[v] = a.lap[v * stride + n]; }
+        q.nu = a.nu[n]; q.r = a.r[n];
+        return q;
+    };
+    auto stage = [&](uint32_t slot, const Node &q) {
+        for (int v = 0; v < 5; v++) { rec[v][slot] = q.w[v]; rec[5 + v][slot] = q.l[v]; }
+        rec[10][slot] = q.nu; rec[11][slot] = q.r;
+    };
+    const int64_t first_row = n_int > 0 ? row0 : 0;                    // (row 0 exists on every level; unused when n_int == 0)
+    uint32_t c = nbr16[(first_row << 6) + lane];
+    double ke = w[(first_row << 8) + 192 + lane];
+    const Node me = load(i);
+    stage(uint32_t(tid), me);
+    stage(uint32_t(kTile + tid), load(hnode));
+    if (hid2 >= 0) stage(uint32_t(kTile + kBlock + tid), load(hid2));
+    int32_t tl_b = 0, tl_n = 0;
+    if (TAIL) { tl_b = tp.begin[i]; tl_n = tp.count[i]; }
+    __syncthreads();
+
+    double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0, c4 = 0.0;
+    auto add = [&](uint32_t code, double k_e) {
+        const uint32_t s = code & kT16SlotMask;
+        if (s == kT16Pad) return;
+        Node ot;
+        if (s >= uint32_t(kTileCap)) ot = load(tile_ovf[ovf0 + int32_t(s) - kTileCap]);
+        else {
+            for (int v = 0; v < 5; v++) { ot.w[v] = rec[v][s]; ot.l[v] = rec[5 + v][s]; }
+            ot.nu = rec[10][s]; ot.r = rec[11][s];
+        }
+        const double fac = k_e * (me.r + ot.r);
+        const double nu = me.nu > ot.nu ? me.nu : ot.nu;
+        double e2 = a.kappa2 * nu;
+        e2 = e2 < 1.0 ? e2 : 1.0;
+        double e4 = a.kappa4 - e2;
+        e4 = e4 > 0.0 ? e4 : 0.0;
+        const double e2m = e2 - 1.0;
+        c0 += fac * (e2m * (me.w[0] - ot.w[0]) - e4 * (me.l[0] - ot.l[0]));
+        c1 += fac * (e2m * (me.w[1] - ot.w[1]) - e4 * (me.l[1] - ot.l[1]));
+        c2 += fac * (e2m * (me.w[2] - ot.w[2]) - e4 * (me.l[2] - ot.l[2]));
+        c3 += fac * (e2m * (me.w[3] - ot.w[3]) - e4 * (me.l[3] - ot.l[3]));
+        c4 += fac * (e2m * (me.w[4] - ot.w[4]) - e4 * (me.l[4] - ot.l[4]));
+    };
+    for (int32_t r = 0; r < n_int; r++) {                             // code and weight one row ahead of the sums
+        const bool more = r + 1 < n_int;
+        const uint32_t cn = more ? nbr16[(int64_t(row0 + r + 1) << 6) + lane] : kT16Pad;
+        const double kn = more ? w[(int64_t(row0 + r + 1) << 8) + 192 + lane] : 0.0;
+        add(c, ke);
+        c = cn;
+        ke = kn;
+    }
+    if (TAIL) {
+        for (int32_t k = 0; k < tl_n; k++) {
+            const double2 fzk = tp.rec[3 * int64_t(tl_b + k) + 1];
+            const unsigned long long word = static_cast<unsigned long long>(__double_as_longlong(tp.rec[3 * int64_t(tl_b + k) + 2].x));
+            add(static_cast<uint32_t>(word >> 16) & 0xFFFFu, fzk.y);
+        }
+    }
+    if (i >= nel) return;
+    a.fluxes[i] = a.fluxes[i] + c0; a.fluxes[stride + i] = a.fluxes[stride + i] + c1; a.fluxes[2 * stride + i] = a.fluxes[2 * stride + i] + c2;
+    a.fluxes[3 * stride + i] = a.fluxes[3 * stride + i] + c3; a.fluxes[4 * stride + i] = a.fluxes[4 * stride + i] + c4;
+}
+
 // check_for_invalid_variables as a standalone sweep
 __global__ void __launch_bounds__(kBlock)
 k_check_invalid(int64_t nel, int64_t stride, const double *__restrict__ q, const int32_t *__restrict__ old_of_new,
@@ -3414,6 +3581,22 @@ void launch_smooth(hipStream_t st, const DevicePlan &p, const SmoothStep &a)
                                    p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
             });
         });
+    });
+}
+
+// the two launches of the JST dissipation: L, nu, r from W; then fluxes += C
+void launch_jst_sensor(hipStream_t st, const DevicePlan &p, const JstStep &a)
+{
+    with_bool(p.has_tail != 0, [&](auto tail) {
+        hipLaunchKernelGGL((k_jst_sensor_tile<decltype(tail)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
+    });
+}
+void launch_jst_dissipation(hipStream_t st, const DevicePlan &p, const JstStep &a)
+{
+    with_bool(p.has_tail != 0, [&](auto tail) {
+        hipLaunchKernelGGL((k_jst_dissipation_tile<decltype(tail)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
     });
 }
 

@@ -24,6 +24,8 @@
                           unsigned long long *err, int check, const double *partial_min, int n_partial,              \
                           const double *volumes, double *residuals, int zero_fluxes);                                \
     void launch_smooth(hipStream_t, const DevicePlan &, const SmoothStep &);                                          \
+    void launch_jst_sensor(hipStream_t, const DevicePlan &, const JstStep &);                                        \
+    void launch_jst_dissipation(hipStream_t, const DevicePlan &, const JstStep &);                                   \
     void launch_time_step_dual(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                   \
                                const double *fluxes, const double *old_variables, double *q,                       \
                                const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,    \
@@ -85,5 +87,6 @@ struct Launchers {
     decltype(exact::launch_restrict) *restrict_;                     decltype(exact::launch_prolong) *prolong;
     decltype(exact::launch_step_factor_nodal) *step_factor_nodal;    decltype(exact::launch_smooth) *smooth;
     decltype(exact::launch_time_step_dual) *time_step_dual;          decltype(exact::launch_dual_source) *dual_source;
+    decltype(exact::launch_jst_sensor) *jst_sensor;                  decltype(exact::launch_jst_dissipation) *jst_dissipation;
 };
 }

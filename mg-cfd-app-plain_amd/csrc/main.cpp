@@ -63,6 +63,11 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool smoothing_iterations_given = false;
     double smoothing_eps = 0.0;
     int smoothing_iterations = 2;     // (the default when only EPS is given)
+    // JST dissipation: --jst / --jst-kappa2 X / --jst-kappa4 X / --jst-levels N and the config keys jst (Y) / jst_kappa2 / jst_kappa4 /
+    // jst_levels; each of the three values implies --jst
+    bool jst_given = false;           // mgcfd_set_jst before the first cycle
+    double jst_kappa2 = MGCFD_JST_KAPPA2, jst_kappa4 = MGCFD_JST_KAPPA4;
+    int jst_levels = 1;
     // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
     // physical_time_step / time_steps / dual_time_clamp / bdf_order.  With DT given, -g is the number of cycles per physical step.
     bool dual_given = false;          // a DT was given: mgcfd_set_dual_time before the first cycle, mgcfd_advance for the cycles
@@ -117,7 +122,16 @@ bool parse_smoothing_iterations(const char *text, int *out)
     return true;
 }
 
-// a whole number lo ... hi (the physical time steps, the BDF order)
+// a finite number not below zero (the JST coefficients)
+bool parse_not_negative(const char *text, double *out)
+{
+    double v = 0.0;
+    if (!parse_number(text, &v) || !(v >= 0.0)) return false;
+    *out = v;
+    return true;
+}
+
+// a whole number lo ... hi (the physical time steps, the BDF order, the JST levels)
 bool parse_whole(const char *text, int lo, int hi, int *out)
 {
     double v = 0.0;
@@ -126,6 +140,7 @@ bool parse_whole(const char *text, int lo, int hi, int *out)
     return true;
 }
 constexpr int kMaxTimeSteps = 1000000;
+constexpr int kMaxJstLevels = 64;
 
 // "A0:A1:N": two finite angles and a count of at least 1
 bool parse_polar(const char *text, Config &c)
@@ -203,6 +218,15 @@ void set_param(Config &c, const std::string &key, const std::string &value)
     else if (key == "smoothing_iterations") {
         if (parse_smoothing_iterations(value.c_str(), &c.smoothing_iterations)) c.smoothing_iterations_given = true;
         else { std::fprintf(stderr, "ERROR: smoothing_iterations = '%s': expected a whole number 0 ... %d\n", value.c_str(), MGCFD_MAX_SMOOTHING_ITERATIONS); c.config_bad = true; }
+    }
+    else if (key == "jst") { if (value == "Y") c.jst_given = true; }
+    else if (key == "jst_kappa2" || key == "jst_kappa4") {
+        if (parse_not_negative(value.c_str(), key == "jst_kappa2" ? &c.jst_kappa2 : &c.jst_kappa4)) c.jst_given = true;
+        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number, zero or above\n", key.c_str(), value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "jst_levels") {
+        if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.jst_levels)) c.jst_given = true;
+        else { std::fprintf(stderr, "ERROR: jst_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
     }
     else if (key == "physical_time_step") {
         if (parse_positive(value.c_str(), &c.dual_dt)) c.dual_given = true;
@@ -303,6 +327,15 @@ void print_help()
         "                                   graph, which lets --cfl be two or more times as large.  One GPU, or --gpus N with one\n"
         "                                   multigrid level per GPU; not with --gpus-partition or a level split over GPUs\n"
         "  --smoothing-iterations=N         its Jacobi iterations, 0 ... 8 (default 2; 0 = off; config key smoothing_iterations)\n"
+        "  --jst                            JST dissipation (config key jst = Y): the first-difference dissipation is kept only where a\n"
+        "                                   pressure sensor sees a shock, a small fourth difference takes over elsewhere; with\n"
+        "                                   kappa2 = 2.5, kappa4 = 0.15625 on level 0 unless said otherwise.  One GPU, or --gpus N with\n"
+        "                                   one multigrid level per GPU; not with --gpus-partition or a level split over GPUs\n"
+        "  --jst-kappa2=X                   its second-difference coefficient, finite, zero or above, in units of the reference's\n"
+        "                                   dissipation (config key jst_kappa2; implies --jst)\n"
+        "  --jst-kappa4=X                   its fourth-difference coefficient, likewise (config key jst_kappa4; implies --jst)\n"
+        "  --jst-levels=N                   the multigrid levels 0 ... N-1 it runs on (default 1; 0 = off; config key jst_levels;\n"
+        "                                   implies --jst)\n"
         "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
         "                                   (config key physical_time_step): BDF2 in physical time, every step solved in pseudo-time\n"
         "                                   by -g cycles (-g becomes the cycles PER PHYSICAL STEP; an RMS line per cycle as ever,\n"
@@ -355,6 +388,10 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"time-steps", required_argument, nullptr, 1023},
         {"dual-time-clamp", required_argument, nullptr, 1024},
         {"bdf-order", required_argument, nullptr, 1025},
+        {"jst", no_argument, nullptr, 1026},
+        {"jst-kappa2", required_argument, nullptr, 1027},
+        {"jst-kappa4", required_argument, nullptr, 1028},
+        {"jst-levels", required_argument, nullptr, 1029},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -456,6 +493,22 @@ bool parse_arguments(int argc, char **argv, Config &c)
                     return false;
                 }
                 c.dual_extras_given = true;
+                break;
+            case 1026: c.jst_given = true; break;
+            case 1027:
+            case 1028:
+                if (!parse_not_negative(optarg, optc == 1027 ? &c.jst_kappa2 : &c.jst_kappa4)) {
+                    std::fprintf(stderr, "ERROR: --jst-kappa%d=%s: expected a finite number, zero or above\n", optc == 1027 ? 2 : 4, optarg);
+                    return false;
+                }
+                c.jst_given = true;
+                break;
+            case 1029:
+                if (!parse_whole(optarg, 0, kMaxJstLevels, &c.jst_levels)) {
+                    std::fprintf(stderr, "ERROR: --jst-levels=%s: expected a whole number 0 ... %d\n", optarg, kMaxJstLevels);
+                    return false;
+                }
+                c.jst_given = true;
                 break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
@@ -713,6 +766,7 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
         std::vector<PolarRow> polar_rows;
         if (conf.time_step_given && run.set_time_step(conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
         if (conf.smoothing_given && run.set_residual_smoothing(conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
+        if (conf.jst_given && run.set_jst(conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
         const int rc = run_all_cycles(conf, rms, loads, polar_rows,
             [&](double mach, double alpha, int reinitialise) { return run.set_free_stream(mach, alpha, reinitialise); },
             [&](double *rms_out, double *loads_out) {
@@ -787,6 +841,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "ERROR: residual smoothing (--residual-smoothing) does not run with --gpus-partition: a level split over GPUs would need a halo exchange per Jacobi iteration\n");
         return 1;
     }
+    if (conf.jst_given && conf.jst_levels > 0 && conf.gpus > 1 && conf.gpus_partition) {
+        std::fprintf(stderr, "ERROR: the JST dissipation (--jst) does not run with --gpus-partition: a level split over GPUs would need its sensor and Laplacian exchanged per stage\n");
+        return 1;
+    }
     if (conf.dual_given && conf.gpus > 1 && conf.gpus_partition) {
         std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --gpus-partition: levels split over GPUs are out of scope\n");
         return 1;
@@ -851,6 +909,7 @@ int main(int argc, char **argv)
     std::vector<PolarRow> polar_rows;
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
     if (conf.smoothing_given && mgcfd_set_residual_smoothing(solver, conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
+    if (conf.jst_given && mgcfd_set_jst(solver, conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
         [&](double *rms_out, double *loads_out) {

@@ -461,6 +461,16 @@ int Run::set_residual_smoothing(double eps, int iterations)
     return MGCFD_OK;
 }
 
+int Run::set_jst(double kappa2, double kappa4, int levels)
+{
+    // (every rank holds the whole hierarchy and sweeps its own levels; a group's ranks hold parts of a level: the library refuses them)
+    for (mgcfd_solver *s : p->solvers) {
+        const int rc = mgcfd_set_jst(s, kappa2, kappa4, levels);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
 int Run::set_dual_time(double dt, double clamp, int order)
 {
     // (every rank holds the whole hierarchy and sweeps its own levels: each keeps the time levels of all, and those of the

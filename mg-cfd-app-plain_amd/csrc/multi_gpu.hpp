@@ -34,6 +34,8 @@ public:
     int set_time_step(int mode, double cfl);
     // mgcfd_set_residual_smoothing on every rank (one multigrid level per rank only: MGCFD_ERR_ARG where a level is split)
     int set_residual_smoothing(double eps, int iterations);
+    // mgcfd_set_jst on every rank, likewise
+    int set_jst(double kappa2, double kappa4, int levels);
     // mgcfd_set_dual_time (+ the BDF order) on every rank, likewise; advance: steps x (mgcfd_dual_time_begin_step on every rank +
     // cycles_per_step cycles), rms_out [steps * cycles_per_step]
     int set_dual_time(double dt, double clamp, int order);

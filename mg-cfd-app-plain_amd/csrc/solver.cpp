@@ -174,6 +174,7 @@ struct DeviceLevel {
     double *sfb[2] = {nullptr, nullptr};
     void apply_sf() { step_factors = sfb[sf_par & 1]; sf_alt = sfb[(sf_par & 1) ^ 1]; }
     double *smooth_buf[2] = {nullptr, nullptr};   // [5][stride] each: the residual smoothing's iterates, alternating (allocated when it is first switched on)
+    double *jst_buf = nullptr;           // [7][stride]: the JST dissipation's L [5], nu and r (allocated when it is first switched on for this level)
     double *time_n = nullptr, *time_n1 = nullptr;   // [5][stride] each: dual time stepping's time levels Wn and Wn1 (held while it is on)
     const double *flux_in = nullptr;     // the state the last flux launch read: W of the dual-time source
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while dual time is on: its RMS is summed in original numbering
@@ -325,6 +326,21 @@ struct mgcfd_solver {
         d.dt = dual_dt; d.order = (dual_order == 2 && dual_levels == 2) ? 2 : 1;
         return d;
     }
+    // JST dissipation (mgcfd_set_jst): on levels 0 .. jst_levels-1 every flux launch is followed by the sensor and the
+    // dissipation launch, which add the correction C into fluxes[].  Such a level runs a stage as standalone flux launch + the
+    // two + the update the other settings select: no fused stage, no look-ahead, no graph.  Other levels run as ever.
+    double jst_kappa2 = 0.0, jst_kappa4 = 0.0;
+    int jst_levels = 0;
+    bool jst_on(int l) const { return l < jst_levels; }
+    // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while either is on
+    bool ordered_rms() const { return dual_time() || jst_on(0); }
+    JstStep jst_step(DeviceLevel &lv) const
+    {
+        JstStep a;
+        a.w = lv.q; a.lap = lv.jst_buf; a.nu = lv.jst_buf + 5 * lv.dp.stride; a.r = lv.jst_buf + 6 * lv.dp.stride;
+        a.fluxes = lv.fluxes; a.kappa2 = jst_kappa2; a.kappa4 = jst_kappa4;
+        return a;
+    }
     // ff17 -> the kernels' argument (ff) and the loads' p_inf.  Launches already captured keep the old values: drop_graphs.
     void set_far_field(const double *in17)
     {
@@ -359,7 +375,8 @@ struct mgcfd_solver {
     {
 #define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
-                                NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_dual, NS::launch_dual_source}
+                                NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_dual, NS::launch_dual_source, \
+                                NS::launch_jst_sensor, NS::launch_jst_dissipation}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -574,6 +591,12 @@ struct mgcfd_solver {
         if ((variant & 4) && !lv.dp.edge_flux)              // two-phase design point: edge-flux scratch on first use
             lv.dp.edge_flux = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
         k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr, nullptr);
+        if ((classes & 1) && jst_on(l)) {
+            // JST: L, nu, r of the state the fluxes were computed from, then fluxes += C (both passes keep row order in either flavour)
+            const JstStep a = jst_step(lv);
+            k().jst_sensor(stream, lv.dp, a);
+            k().jst_dissipation(stream, lv.dp, a);
+        }
         if (dual_time()) lv.flux_in = lv.q;
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
@@ -1549,6 +1572,45 @@ int mgcfd_get_residual_smoothing(const mgcfd_solver *s, double *eps, int *iterat
     return MGCFD_OK;
 }
 
+// ---- JST dissipation: the two coefficients and the levels it runs on ----
+int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (levels < 0) throw std::invalid_argument("JST dissipation: levels must be 0 (off) or more");
+        if (!std::isfinite(kappa2) || kappa2 < 0.0 || !std::isfinite(kappa4) || kappa4 < 0.0)
+            throw std::invalid_argument("JST dissipation: kappa2 and kappa4 must be finite and not negative");
+        if (levels > 0 && !(kappa2 > 0.0) && !(kappa4 > 0.0)) throw std::invalid_argument("JST dissipation: one of kappa2 and kappa4 must be positive");
+        if (levels > 0 && (s->partitioned || s->comm))
+            throw std::invalid_argument("JST dissipation: not on a partitioned solver or a rank (a level split over ranks would need L, nu and r exchanged per stage)");
+        require_no_sweep_under_way(s, "JST dissipation");
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);
+        s->drop_graphs();
+        const int n = std::min(levels, static_cast<int>(s->L.size()));
+        for (int l = 0; l < n; l++) {
+            DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+            if (!lv.jst_buf) lv.jst_buf = lv.mem.alloc<double>(static_cast<size_t>(7 * lv.dp.stride));
+        }
+        if (n > 0 && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
+        if (n == 0 && !s->dual_time()) s->L[0].mem.release(s->L[0].new_of_old_dev);
+        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
+        s->jst_levels = n;
+        s->jst_kappa2 = n > 0 ? kappa2 : 0.0;
+        s->jst_kappa4 = n > 0 ? kappa4 : 0.0;
+    });
+}
+int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *levels)
+{
+    REQUIRE(s);
+    if (kappa2) *kappa2 = s->jst_kappa2;
+    if (kappa4) *kappa4 = s->jst_kappa4;
+    if (levels) *levels = s->jst_levels;
+    return MGCFD_OK;
+}
+
 // ---- kernel-granular operations ----
 #define OP(body) REQUIRE(s); return guarded([&] { s->use_device(); body; HIP_CHECK(hipGetLastError()); })   /* (a launch that failed must not come back as MGCFD_OK) */
 int mgcfd_copy_old_variables(mgcfd_solver *s, int level) { OP(s->op_copy_old(level)); }
@@ -1583,8 +1645,8 @@ int mgcfd_calc_rms(mgcfd_solver *s, int level, double *rms)
     return guarded([&] {
         s->use_device();
         DeviceLevel &lv = s->level(level);
-        if (s->dual_time() && level == 0) {
-            // the order dual time stepping fixes for the level-0 sum (mgcfd.h), as the cycle driver runs it
+        if (s->ordered_rms() && level == 0) {
+            // the order dual time stepping and the JST dissipation fix for the level-0 sum (mgcfd.h), as the cycle driver runs it
             s->settle_residuals(lv);
             exact::launch_sumsq_original(s->stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.new_of_old_dev, lv.tile_sumsq);
             exact::launch_sum_partials_append(s->stream, static_cast<int>((lv.info.nel + 255) / 256), lv.tile_sumsq, lv.sumsq, nullptr, nullptr, 0);
@@ -1646,7 +1708,7 @@ static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 static void smooth_once(mgcfd_solver *s, int level)
 {
     DeviceLevel &lv = s->level(level);
-    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
+    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
         // Fused stages: flux + time_step in one launch each.  No copy<double>(old_variables, variables)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
@@ -1727,7 +1789,7 @@ static void run_sweep(mgcfd_solver *s, int level)
     }
     // (only the fused launches are replayed: the unfused ones — the two-phase flux variant — leave host-side flags
     //  behind, fluxes_stale, that a replay would not set)
-    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
+    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
     if (!graphable) {
         const int keep = s->opt_timing;
         if (!timed) s->opt_timing = 0;
@@ -1780,6 +1842,7 @@ static void require_no_smoothing(const mgcfd_solver *s, const char *who)
 {
     if (s->smoothing()) throw std::invalid_argument(std::string(who) + ": not while residual smoothing is on (mgcfd_set_residual_smoothing; use mgcfd_smooth or the kernel-granular calls)");
     if (s->dual_time()) throw std::invalid_argument(std::string(who) + ": not while dual time stepping is on (mgcfd_set_dual_time; use mgcfd_smooth or the kernel-granular calls)");
+    if (s->jst_on(0)) throw std::invalid_argument(std::string(who) + ": not while the JST dissipation is on (mgcfd_set_jst; use mgcfd_smooth or the kernel-granular calls)");
 }
 // The same sweep split around the one collective a multi-GPU run needs (see mgcfd.h).
 static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
@@ -1979,9 +2042,9 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
                 // ... single level: one small launch does
                 exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
                                                   s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
-            } else if (s->dual_time()) {
-                // dual time stepping defines the order of this sum on the original numbering (mgcfd.h): per-workgroup sums
-                // of 256 original nodes into tile_sumsq (no fused stage fills it while dual time is on), then their sum
+            } else if (s->ordered_rms()) {
+                // dual time stepping and the JST dissipation define the order of this sum on the original numbering (mgcfd.h):
+                // per-workgroup sums of 256 original nodes into tile_sumsq (no fused stage fills it while either is on), then their sum
                 s->settle_residuals(l0);
                 exact::launch_sumsq_original(s->stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
                 exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
@@ -2025,7 +2088,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2166,6 +2229,11 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
         case MGCFD_ARR_TIME_N: case MGCFD_ARR_TIME_N1:
             if (!lv.time_n) throw std::invalid_argument("MGCFD_ARR_TIME_N / _TIME_N1: dual time stepping is off (mgcfd_set_dual_time)");
             return which == MGCFD_ARR_TIME_N ? lv.time_n : lv.time_n1;
+        case MGCFD_ARR_JST_LAPLACIAN: case MGCFD_ARR_JST_SENSOR: case MGCFD_ARR_JST_RADIUS:
+            if (!lv.jst_buf) throw std::invalid_argument("MGCFD_ARR_JST_*: the JST dissipation has not been on for this level (mgcfd_set_jst)");
+            if (which == MGCFD_ARR_JST_LAPLACIAN) return lv.jst_buf;
+            *ncols = 1;
+            return lv.jst_buf + (which == MGCFD_ARR_JST_SENSOR ? 5 : 6) * lv.dp.stride;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2201,6 +2269,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         int nc = 0;
         double *dst = (s->settle_residuals(lv), array_ptr(lv, which, &nc));
         if (which == MGCFD_ARR_VOLUMES) throw std::invalid_argument("volumes are fixed at creation");
+        if (which == MGCFD_ARR_JST_LAPLACIAN || which == MGCFD_ARR_JST_SENSOR || which == MGCFD_ARR_JST_RADIUS)
+            throw std::invalid_argument("MGCFD_ARR_JST_*: read-only (every flux launch of a JST level overwrites them)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -2422,6 +2492,38 @@ int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int lau
         if (kind == 2) { st.rk_div = double(MGCFD_RK + 1); st.old_variables = lv.q; st.q_out = lv.q_alt; st.old_of_new = lv.dp.old_of_new; st.err = s->err; }
         HIP_CHECK(hipEventRecord(a.get(), s->stream));
         for (int k = 0; k < launches; k++) s->k().smooth(s->stream, lv.dp, st);
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
+        lv.fluxes_zero = false;
+        lv.fluxes_stale = false;
+        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+    });
+}
+
+// ... and for one of the JST dissipation's launches: 0 the sensor, 1 the dissipation (which adds into fluxes[], accumulating
+// over the launches: the state stays).  After one flux launch with both passes, so that every array holds a stage's numbers.
+int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->jst_on(level)) throw std::invalid_argument("the JST dissipation is off on this level: switch it on first (mgcfd_set_jst)");
+        if (kind < 0 || kind > 1) throw std::invalid_argument("JST launch kind: 0 sensor, 1 dissipation");
+        Event a = s->get_event(), b = s->get_event();
+        s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
+        const JstStep st = s->jst_step(lv);
+        s->k().jst_sensor(s->stream, lv.dp, st);
+        s->k().jst_dissipation(s->stream, lv.dp, st);
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
+        for (int k = 0; k < launches; k++) {
+            if (kind == 0) s->k().jst_sensor(s->stream, lv.dp, st);
+            else s->k().jst_dissipation(s->stream, lv.dp, st);
+        }
         HIP_CHECK(hipEventRecord(b.get(), s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
         float ms = 0.f;
@@ -4651,7 +4753,8 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
             s->dual_invalid_step = -1;
         }
         if (!on) {
-            for (DeviceLevel &lv : s->L) { lv.mem.release(lv.time_n); lv.mem.release(lv.time_n1); lv.mem.release(lv.new_of_old_dev); lv.flux_in = nullptr; }
+            for (DeviceLevel &lv : s->L) { lv.mem.release(lv.time_n); lv.mem.release(lv.time_n1); lv.flux_in = nullptr; }
+            if (!s->jst_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);        // (the JST dissipation orders the RMS the same way)
             s->dual_levels = 0;
         }
         for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)

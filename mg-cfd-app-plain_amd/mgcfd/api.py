@@ -24,7 +24,7 @@ NVAR = 5
 RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
-       "time_n": 7, "time_n1": 8}
+       "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11}
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -188,6 +188,9 @@ _SIGNATURES = [
     ("mgcfd_dual_time_reset", C.c_int, [_vp]),
     ("mgcfd_dual_time_begin_step", C.c_int, [_vp]),
     ("mgcfd_advance", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_set_jst", C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
+    ("mgcfd_get_jst", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("mgcfd_bench_jst", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -587,6 +590,20 @@ class Solver:
         return e.value, m.value
 
     # ---- dual time stepping ----
+    # ---- JST dissipation ----
+    def set_jst(self, kappa2: float = 2.5, kappa4: float = 0.15625, levels: int = 1):
+        """JST dissipation on levels ``0 .. levels-1`` (mgcfd_set_jst): the first-difference dissipation stays only where the
+        pressure sensor sees a shock, a fourth difference scaled by ``kappa4`` takes over elsewhere; both coefficients are in
+        units of the reference's dissipation (the defaults are the textbook 1/2 and 1/32).  ``levels=0`` switches it off.  The
+        state stays; captured graphs are dropped.  Not on partitioned solvers or ranks."""
+        self._c(self.lib.mgcfd_set_jst(self.handle, float(kappa2), float(kappa4), int(levels)))
+
+    def jst(self):
+        """``(kappa2, kappa4, levels)`` in use, ``levels`` capped at the solver's; ``(0.0, 0.0, 0)`` when off."""
+        k2, k4, n = C.c_double(), C.c_double(), C.c_int()
+        self._c(self.lib.mgcfd_get_jst(self.handle, C.byref(k2), C.byref(k4), C.byref(n)))
+        return k2.value, k4.value, n.value
+
     def set_dual_time(self, dt: float, clamp: float = 2.0 / 3.0):
         """Time-accurate runs (mgcfd_set_dual_time): every stage's update carries the BDF source of the physical step ``dt`` and
         the pseudo step is clamped to ``clamp * dt / vol``; ``dt=0`` switches it off and releases the time levels.  The state
@@ -636,14 +653,16 @@ class Solver:
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
-              residual_smoothing=None) -> List[dict]:
+              residual_smoothing=None, jst=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
         dict: ``alpha``, ``mach``, ``rms`` [cycles], ``loads`` [cycles, 6] and ``coefficients`` (CD CL CS CMx CMy CMz of the
         last cycle against that angle's far field).  ``time_step`` / ``cfl`` (None: as the solver has them) are set once,
         before the first angle, and stay (``set_time_step``); likewise ``residual_smoothing=(eps, iterations)``
-        (``set_residual_smoothing``)."""
+        (``set_residual_smoothing``) and ``jst=(kappa2, kappa4, levels)`` (``set_jst``)."""
+        if jst is not None:
+            self.set_jst(*jst)
         if residual_smoothing is not None:
             self.set_residual_smoothing(*residual_smoothing)
         if time_step is not None or cfl is not None:
@@ -660,14 +679,14 @@ class Solver:
 
     # ---- state ----
     def get(self, l: int, name: str) -> np.ndarray:
-        ncols = 1 if name in ("step_factors", "volumes") else NVAR
+        ncols = 1 if name in ("step_factors", "volumes", "jst_sensor", "jst_radius") else NVAR
         out = np.zeros(self.nel(l) * ncols)
         self._c(self.lib.mgcfd_get_array(self.handle, l, ARR[name], _ptr(out)))
         return out.reshape(-1, ncols) if ncols > 1 else out
 
     def set(self, l: int, name: str, values: np.ndarray):
         a = np.ascontiguousarray(values, dtype=np.float64).ravel()
-        ncols = 1 if name in ("step_factors", "volumes") else NVAR
+        ncols = 1 if name in ("step_factors", "volumes", "jst_sensor", "jst_radius") else NVAR
         assert a.size == self.nel(l) * ncols
         self._c(self.lib.mgcfd_set_array(self.handle, l, ARR[name], _ptr(a)))
 
@@ -706,6 +725,13 @@ class Solver:
         back-to-back launches under one event pair (mgcfd_bench_residual_smoothing); the smoothing must be on."""
         t = C.c_double()
         self._c(self.lib.mgcfd_bench_residual_smoothing(self.handle, l, kind, launches, C.byref(t)))
+        return t.value
+
+    def bench_jst(self, l: int, kind: int, launches: int) -> float:
+        """Mean GPU seconds of one JST launch of ``kind`` (0 sensor, 1 dissipation) over ``launches`` back-to-back launches under
+        one event pair (mgcfd_bench_jst); the JST dissipation must be on for level ``l``."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_jst(self.handle, l, kind, launches, C.byref(t)))
         return t.value
 
     def bench_stream_ceiling(self, l: int, launches: int) -> float:
