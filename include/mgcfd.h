@@ -554,6 +554,11 @@ int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *av
  * node read, 40 B per node written; one workgroup per tile, nothing dependent, nothing computed): the practical ceiling of its
  * data movement on this chip, launch included.  Overwrites `fluxes`. */
 int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double *avg_seconds);
+/* Diagnostic: out[i] = f(in[i]) for the n host doubles of `in`, with f one of the approximations the MGCFD_OPT_EXACT = 0 build's
+ * order-free flux kernel uses in place of division and square root, run on the device from that build (whatever MGCFD_OPT_EXACT
+ * is set to): kind 0 its 1/x, kind 1 its sqrt(x) with the special cases (+0 -> +0, +inf -> +inf, negative or NaN -> NaN), kind 2
+ * its sqrt(x) for x > 0 without them.  What tests/test_gpu_fast_accuracy.py measures against long double. */
+int mgcfd_diag_fast_math(mgcfd_solver *s, int kind, int64_t n, const double *in, double *out);
 
 /* ---------------------------------------------------------------------------------
  * Multi-GPU hooks (one process per GPU; the collectives themselves are issued by the

@@ -1955,6 +1955,17 @@ k_flux_free(// (the first 16 dwords are preloaded into SGPRs: what the prologue'
     }
     PH_MARK(4);
 }
+
+// Diagnostic (mgcfd_diag_fast_math): one of the approximations above per element, as this build compiles it for the flux kernel.
+// kind 0: fast_rcp, 1: fast_sqrt, 2: fast_sqrt_pos.
+__global__ void __launch_bounds__(kBlock)
+k_diag_fast_math(int kind, int64_t n, const double *__restrict__ in, double *__restrict__ out)
+{
+    const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double x = in[i];
+    out[i] = kind == 0 ? fast_rcp(x) : (kind == 1 ? fast_sqrt(x) : fast_sqrt_pos(x));
+}
 #endif // MGCFD_ORDER_FREE
 
 // ------------------------------------------------------------------------------------------
@@ -3363,6 +3374,9 @@ static int free_stage_role(const FusedStep &fs, int role)
     if (role == 1 && fs.sumsq_partial) return 2;        // sums of squares without residuals[] (a lazy residual): a last stage all the same
     return role;
 }
+
+void launch_diag_fast_math(hipStream_t st, int kind, int64_t n, const double *in, double *out)
+{ if (n > 0) hipLaunchKernelGGL(k_diag_fast_math, dim3(grid_for(n)), dim3(kBlock), 0, st, kind, n, in, out); }
 #endif
 
 // The role of a fused stage (k_flux_tile's ROLE), read off its arguments; a launch that is no stage runs as role 1.

@@ -76,6 +76,11 @@
 MGCFD_DECLARE_LAUNCHERS(exact)
 MGCFD_DECLARE_LAUNCHERS(fast)
 
+// The `fast` build only: 1/x and sqrt(x) as the order-free flux kernel computes them (mgcfd_diag_fast_math).
+namespace mgcfd { namespace fast {
+void launch_diag_fast_math(hipStream_t, int kind, int64_t n, const double *in, double *out);
+} }
+
 // The launchers whose numeric flavour follows MGCFD_OPT_EXACT (solver.cpp: mgcfd_solver::k() holds one table per flavour).
 // Everything else is called as exact:: — those kernels do no arithmetic that contraction could change.
 namespace mgcfd {

@@ -2594,6 +2594,25 @@ int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double 
     });
 }
 
+// 1/x and sqrt(x) as the `fast` build's order-free flux kernel computes them (kernels.hip: fast_rcp, fast_sqrt, fast_sqrt_pos),
+// element by element; whatever MGCFD_OPT_EXACT says, the `fast` build's code runs.
+int mgcfd_diag_fast_math(mgcfd_solver *s, int kind, int64_t n, const double *in, double *out)
+{
+    REQUIRE(s);
+    if (kind < 0 || kind > 2 || n < 0 || (n > 0 && (!in || !out))) { g_last_error = "mgcfd_diag_fast_math: kind 0, 1 or 2, n >= 0 and both arrays"; return MGCFD_ERR_ARG; }
+    return guarded([&] {
+        if (n == 0) return;
+        s->use_device();
+        DeviceOwner scratch;
+        double *d_in = scratch.alloc<double>(static_cast<size_t>(n)), *d_out = scratch.alloc<double>(static_cast<size_t>(n));
+        HIP_CHECK(hipMemcpyAsync(d_in, in, static_cast<size_t>(n) * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        fast::launch_diag_fast_math(s->stream, kind, n, d_in, d_out);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out, d_out, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+    });
+}
+
 } // extern "C"
 
 // ==========================================================================================================

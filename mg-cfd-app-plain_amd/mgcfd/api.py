@@ -126,6 +126,7 @@ _SIGNATURES = [
     ("mgcfd_bench_flux", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_bench_indirect_rw", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_bench_stream_ceiling", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_diag_fast_math", C.c_int, [_vp, C.c_int, _i64, _vp, _vp]),
     ("mgcfd_device_warm_up", C.c_int, [C.c_int]),
     ("mgcfd_step_factor_local", C.c_int, [_vp, C.c_int]),
     ("mgcfd_step_factor_min_devptr", C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
@@ -739,6 +740,16 @@ class Solver:
         t = C.c_double(0.0)
         self._c(self.lib.mgcfd_bench_stream_ceiling(self.handle, l, launches, C.byref(t)))
         return t.value
+
+    FAST_MATH = {"rcp": 0, "sqrt": 1, "sqrt_pos": 2}
+
+    def diag_fast_math(self, kind: str, x) -> np.ndarray:
+        """The fast mode's own ``1/x`` (``"rcp"``), ``sqrt(x)`` (``"sqrt"``) or ``sqrt(x)`` for ``x > 0`` (``"sqrt_pos"``) of
+        every element of ``x``, computed on the device by the code the order-free flux kernel uses (mgcfd_diag_fast_math)."""
+        a = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        out = np.zeros_like(a)
+        self._c(self.lib.mgcfd_diag_fast_math(self.handle, self.FAST_MATH[kind], a.size, _ptr(a), _ptr(out)))
+        return out.reshape(np.shape(x))
 
     def bench_indirect_rw(self, l: int, launches: int) -> float:
         t = C.c_double()
