@@ -55,7 +55,9 @@ enum { MGCFD_ARR_VARIABLES = 0, MGCFD_ARR_OLD_VARIABLES, MGCFD_ARR_FLUXES, MGCFD
        MGCFD_ARR_STAGE /* the state the last mgcfd_sweep_stage wrote (halo messages between the stages of a split sweep) */,
        MGCFD_ARR_TIME_N, MGCFD_ARR_TIME_N1 /* dual time stepping's time levels Wn and Wn1 (while mgcfd_set_dual_time has it on) */,
        MGCFD_ARR_JST_LAPLACIAN, MGCFD_ARR_JST_SENSOR, MGCFD_ARR_JST_RADIUS /* read-only: L [nel][5], nu [nel] and r [nel] of the last
-                                 flux launch of a level the JST dissipation is on for (mgcfd_set_jst) */ };
+                                 flux launch of a level the JST dissipation is on for (mgcfd_set_jst) */,
+       MGCFD_ARR_FAS_FORCING, MGCFD_ARR_FAS_START /* read-only, levels >= 1 while FAS multigrid is on (mgcfd_set_fas): the forcing P and
+                                 the start state W0 [nel][5] of the last mgcfd_fas_restrict onto the level */ };
 
 /* Solver options (mgcfd_set_option) */
 enum {
@@ -424,6 +426,56 @@ int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_o
 #define MGCFD_JST_KAPPA4 0.15625
 int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels);
 int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *levels);
+/* FAS multigrid (Brandt's full approximation storage, as Jameson's multigrid uses it): the coarse equations carry a forcing
+ * term and what comes back up is a correction, so the cycle's fixed point is the fine grid's steady state.  The reference's
+ * cycle (mgcfd_restrict, unforced coarse sweeps, mgcfd_prolong of one sweep's change of state) has another fixed point; it
+ * stays the default.  Per solver, off by default: with it off the solver launches what it launches and computes the bits it
+ * computes without this call.  Every operation below is one IEEE-754 double operation, never contracted to FMA under
+ * MGCFD_OPT_EXACT = 1; n is the number of levels.
+ *   Total residual R_l(W) of level l, formed from zero fluxes in this order, each part only where its feature is on for l:
+ *     1. F, the internal, solid-wall and far-field fluxes, as mgcfd_compute_fluxes;
+ *     2. + C, the two JST passes, where mgcfd_set_jst covers l;
+ *     3. - src, the dual-time source with W as the state, while dual time is on.
+ *   Forced stage: on a level l >= 1 every stage of every sweep takes F' = R_l(W) + P_l wherever it took R_l(W) — the forcing is
+ *     the last addition; D = sf * F' goes into the Jacobi iterations with residual smoothing on.  Step factors, the dual-time
+ *     clamp, the invalid-state check and `residuals` are unchanged.  Level 0 has no forcing: its sweeps are the sweeps of a
+ *     solver with FAS off, fused stages included.
+ *   Down leg, l = 0 .. n-2, after sweep(l):
+ *     1. T_l = R_l(variables[l]); for l >= 1 then T_l[i][v] = R_l[i][v] + P_l[i][v].
+ *     2. mg_restrict of the state exactly as mgcfd_restrict(l); W0_{l+1} = a copy of all of variables[l+1], nodes without
+ *        children included.
+ *     3. Q[c][v], from +0.0, receives one addition per child, T_l[child][v], over the children of c in ascending original fine
+ *        id (mg_restrict's order): summed, not averaged.
+ *     4. P_{l+1}[c][v] = Q[c][v] - R_{l+1}(W0_{l+1})[c][v] for a coarse node with children, +0.0 for one without.  fluxes[l+1]
+ *        is logically zero afterwards.
+ *     Then sweep(l+1), forced.
+ *   Up leg, l = n-2 .. 0:
+ *     1. D[c][v] = W0_{l+1}[c][v] - variables[l+1][c][v].
+ *     2. variables[l][i][v] = variables[l][i][v] + (0.0 - wavg_i(D)[v]), wavg_i what mgcfd_prolong applies to the coarse
+ *        residuals — the same entries, order and weights, the division by the weight sum, the coincident-node rule and the
+ *        reference's b-end quirk (mg_loops.cpp:730-851): prolong_residuals_interpolate_proper with residuals1 = D and
+ *        residuals2 = +0.0.
+ *     3. The `residuals` arrays of both levels are not touched.
+ *     4. For l > 0, sweep(l), forced with the same P_l.
+ *   The level-0 RMS of a cycle keeps its definition and, while FAS is on, is summed in the fixed original-numbering order of
+ *   dual time stepping and the JST dissipation (above).
+ * mgcfd_set_fas(s, on): switching on allocates P and W0, [5][stride] each, on the levels >= 1, both zeroed; every enabling call
+ * and mgcfd_set_free_stream(.., reinitialise = 1) zero P again; switching off releases them.  It synchronises and drops every
+ * captured graph; the state stays.  MGCFD_ERR_ARG, and nothing changed: a one-level solver; while a kernel-granular sweep is
+ * under way; a solver made by mgcfd_create_partitioned* or attached to a group or as a rank (a split level would need T, P and D
+ * exchanged: out of scope).  While it is on: mgcfd_group_create and mgcfd_rank_attach_* refuse the solver; mgcfd_sweep_begin*,
+ * mgcfd_sweep_flux0, mgcfd_sweep_stage and mgcfd_sweep_end* return MGCFD_ERR_ARG; MGCFD_OPT_GRAPH is accepted and the launches run
+ * directly; mgcfd_time_step(s, l, j) and mgcfd_smooth(s, l, k) honour P_l on l >= 1 (a stage there is one standalone flux
+ * launch + the forced update); mgcfd_restrict and mgcfd_prolong stay the reference's; mgcfd_run_cycles[_loads] and mgcfd_advance
+ * run the cycle above.  mgcfd_fas_restrict(s, fine) does down-leg steps 1-4 (both levels' fluxes must be zero, as after
+ * time_step), mgcfd_fas_prolong(s, fine) up-leg steps 1-2; MGCFD_ERR_ARG while FAS is off.  LoopNumIters: the extra residual
+ * evaluations count, and are timed, as MGCFD_LOOP_FLUX; restrict and prolong count as before.
+ * Out of scope: levels split over ranks or GPUs; captured graphs with FAS on; a fused flux + forced-update stage; W-cycles and
+ * sweep counts per level; a volume-weighted state restriction. */
+int mgcfd_set_fas(mgcfd_solver *s, int on);
+int mgcfd_get_fas(const mgcfd_solver *s, int *on);
+int mgcfd_fas_restrict(mgcfd_solver *s, int fine_level);
+int mgcfd_fas_prolong(mgcfd_solver *s, int fine_level);
 
 /* ---------------------------------------------------------------------------------
  * Kernel-granular operations (asynchronous on the solver's stream)
@@ -547,6 +599,11 @@ int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int lau
 /* Diagnostic: the same for one of the JST dissipation's launches (kind 0: the sensor, 1: the dissipation, which adds into
  * fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where it is off. */
 int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* Diagnostic: the same for one of FAS multigrid's launches between `fine_level` and the level above it, behind one
+ * mgcfd_fas_restrict (kind 0: k_restrict_fas, 1: the forcing launch, 2: k_time_step_fas on the coarse level, 3: the FAS
+ * prolongation) and for the launches they stand beside (4: k_restrict, 5: k_time_step on the coarse level, 6: the reference's
+ * prolongation, which moves the fine state: re-initialise afterwards).  MGCFD_ERR_ARG while FAS is off. */
+int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, double *avg_seconds);
 /* The same for the indirect_rw probe (src/Kernels/indirect_rw_loop.cpp:8-78; fluxes += ..., accumulating over the
  * launches): the empirical data-movement ceiling of the flux kernel on this level's tiles. */
 int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *avg_seconds);

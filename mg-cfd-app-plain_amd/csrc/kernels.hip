@@ -2300,6 +2300,80 @@ k_dual_source(int64_t nel, int64_t stride, double *__restrict__ fluxes, DualSour
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// FAS multigrid (no reference counterpart; INTEGRATION.md "FAS multigrid"): on a level >= 1 every stage's update takes
+// F' = R + P for R, the level's total residual (fluxes, + the JST correction, - the dual-time source), P the forcing of the
+// cycle's down leg.  The forcing is the last addition; one IEEE operation per line of the definition (include/mgcfd.h).
+// ------------------------------------------------------------------------------------------
+// time_step with F' = F + P, or (F - src) + P beside the dual-time source (SRC: 0 none, 1 BDF1, 2 BDF2), in the one launch:
+// F' exists in registers only, fluxes[] is never written and stays logically zero, the residual and
+// check_for_invalid_variables ride along as in k_time_step_dual.  The step factors are final.  In place, as there.
+template <int SRC>
+__global__ void __launch_bounds__(kBlock)
+k_time_step_fas(int64_t nel, int64_t stride, double rk_div, const double *__restrict__ step_factors,
+                const double *__restrict__ fluxes, const double *__restrict__ forcing, const double *old_variables, double *q,
+                const int32_t *__restrict__ old_of_new, unsigned long long *__restrict__ err, int check,
+                double *residuals, DualSource d)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double factor = step_factors[i] / rk_div;
+    const double vol = SRC ? d.volumes[i] : 0.0;
+    double fp[5], r[5];
+#pragma unroll
+    for (int v = 0; v < 5; v++) {
+        const int64_t at = v * stride + i;
+        double f = fluxes[at];
+        if (SRC) f = f - dual_source<SRC == 2>(d.w[at], d.wn[at], SRC == 2 ? d.wn1[at] : 0.0, vol, d.dt);
+        fp[v] = f + forcing[at];
+        r[v] = old_variables[at];
+    }
+    const double rho = r[0] + factor * fp[0];
+    const double mx = r[1] + factor * fp[1];
+    const double my = r[2] + factor * fp[2];
+    const double mz = r[3] + factor * fp[3];
+    const double en = r[4] + factor * fp[4];
+    store_conserved(q, stride, i, rho, mx, my, mz, en);
+    if (residuals) {
+        residuals[i] = rho - r[0]; residuals[stride + i] = mx - r[1]; residuals[2 * stride + i] = my - r[2];
+        residuals[3 * stride + i] = mz - r[3]; residuals[4 * stride + i] = en - r[4];
+    }
+    if (check) {
+        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
+        int code = 0;
+        if (!finite) code = 1;
+        else if (rho < 0.0) code = 2;
+        else if (en < 0.0) code = 3;
+        if (code) atomicMin(err, err_key(check, old_of_new[i], code));
+    }
+}
+
+// ... and with residual smoothing on: fluxes = F' for every node of the level before the Jacobi iterations, as k_dual_source
+// (which runs first where dual time is on); n = 5 * stride, padding included (P's padding is zero).
+__global__ void __launch_bounds__(kBlock)
+k_fas_add_forcing(int64_t n, double *__restrict__ fluxes, const double *__restrict__ forcing)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= n) return;
+    fluxes[i] = fluxes[i] + forcing[i];
+}
+
+// The forcing of the coarse level: P = Q - R(W0) where the coarse node has children (Q, the children's summed residuals, is
+// what k_restrict_fas left in P), +0.0 where it has none.
+__global__ void __launch_bounds__(kBlock)
+k_fas_forcing(int64_t nel_coarse, int64_t stride_coarse, const int32_t *__restrict__ child_ptr,
+              const double *__restrict__ fluxes, double *__restrict__ forcing)
+{
+    const int64_t c = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (c >= nel_coarse) return;
+    const bool has_children = child_ptr[c + 1] > child_ptr[c];
+#pragma unroll
+    for (int v = 0; v < 5; v++) {
+        const int64_t at = v * stride_coarse + c;
+        forcing[at] = has_children ? forcing[at] - fluxes[at] : 0.0;
+    }
+}
+
 // The pseudo step's clamp (the source is explicit in pseudo-time): sf = min(sf, (clamp * dt) / vol); cdt = clamp * dt.
 __global__ void __launch_bounds__(kBlock)
 k_dual_clamp(int64_t nel, double cdt, const double *__restrict__ volumes, double *__restrict__ step_factors)
@@ -3109,18 +3183,89 @@ k_restrict(int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, const
 }
 
 // ------------------------------------------------------------------------------------------
+// The FAS restriction: k_restrict's gather carrying ten values per child — the state, averaged exactly as there (same
+// operations in the same order: same bits), and the fine level's total residual T = R (+ P on a fine level >= 1), summed
+// from +0.0 in the same child order and not averaged.  One launch writes the coarse state, its copy W0 (all nodes: a node
+// without children keeps its value there too) and the residual sum Q (+0.0 without children).
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock)
+k_restrict_fas(int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, const int32_t *__restrict__ child_ptr,
+               const int32_t *__restrict__ child, const int4 *__restrict__ child4, const double *__restrict__ fine_q,
+               const double *__restrict__ fine_r, const double *__restrict__ fine_p /* nullptr on level 0: no forcing there */,
+               double *__restrict__ coarse_q, double *__restrict__ w0, double *__restrict__ qsum)
+{
+    const int64_t c = xcd_contiguous_block(blockIdx.x, gridDim.x) * int64_t(kBlock) + threadIdx.x;
+    if (c >= nel_coarse) return;
+    const int4 k4 = child4[c];
+    const int32_t b = child_ptr[c], e = child_ptr[c + 1];
+    const int32_t n = e - b;
+    const int64_t sfn = stride_fine, sc = stride_coarse;
+    // the first four children unconditionally (-1 padded table: a missing one reads node 0 and is not added)
+    const int64_t j4[4] = {k4.x < 0 ? 0 : k4.x, k4.y < 0 ? 0 : k4.y, k4.z < 0 ? 0 : k4.z, k4.w < 0 ? 0 : k4.w};
+    double a[4][5], t[4][5];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+#pragma unroll
+        for (int v = 0; v < 5; v++) {
+            a[k][v] = fine_q[v * sfn + j4[k]];
+            t[k][v] = fine_r[v * sfn + j4[k]];
+            if (fine_p) t[k][v] = t[k][v] + fine_p[v * sfn + j4[k]];
+        }
+    }
+    if (n == 0) {
+#pragma unroll
+        for (int v = 0; v < 5; v++) { w0[v * sc + c] = coarse_q[v * sc + c]; qsum[v * sc + c] = 0.0; }
+        return;
+    }
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, g[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (n > k) {
+#pragma unroll
+            for (int v = 0; v < 5; v++) { s[v] += a[k][v]; g[v] += t[k][v]; }
+        }
+    }
+    for (int32_t k = b + 4; k < e; k++) {                             // fifth child onwards
+        const int64_t j = child[k];
+#pragma unroll
+        for (int v = 0; v < 5; v++) {
+            double tv = fine_r[v * sfn + j];
+            if (fine_p) tv = tv + fine_p[v * sfn + j];
+            s[v] += fine_q[v * sfn + j];
+            g[v] += tv;
+        }
+    }
+    const double average = 1.0 / double(n);
+    const double n0 = s[0] * average, n1 = s[1] * average, n2 = s[2] * average, n3 = s[3] * average, n4 = s[4] * average;
+    store_conserved(coarse_q, sc, c, n0, n1, n2, n3, n4);
+    store_conserved(w0, sc, c, n0, n1, n2, n3, n4);
+#pragma unroll
+    for (int v = 0; v < 5; v++) qsum[v * sc + c] = g[v];
+}
+
+// ------------------------------------------------------------------------------------------
 // prolong_residuals_interpolate_proper (mg_loops.cpp:678-864) as a fine-node gather over the
 // same sliced-ELL rows as the flux (one entry per incident internal edge, reference order):
 //   wavg = sum_e (w_own*R[p_own] + w_other*R[p_other]) / w_sum   (or R[parent] if coincident)
 //   variables += residuals - wavg
 // ------------------------------------------------------------------------------------------
+// FAS (the up leg of a FAS cycle): what is interpolated is D = W0 - W, the coarse level's start state minus its current one,
+// formed as the coarse value is loaded (`coarse_residuals` is W0, `coarse_q` is W), and the fine residual's place is taken by
+// +0.0: variables += 0.0 - wavg(D).  Same entries, order, weights and quirks.
+template <bool FAS>
+__device__ __forceinline__ double pro_coarse(const double *__restrict__ coarse_residuals, const double *__restrict__ coarse_q, int64_t at)
+{
+    return FAS ? coarse_residuals[at] - coarse_q[at] : coarse_residuals[at];
+}
+
+template <bool FAS>
 __global__ void __launch_bounds__(kBlock)
 k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__restrict__ slice_row0,
           const int32_t *__restrict__ rows_int, const double *__restrict__ pro_w, const int32_t *__restrict__ pro_p,
           const int32_t *__restrict__ pro_parent, const double *__restrict__ pro_wsum,
-          const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals,
+          const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals /* not FAS */,
           double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl,
-          double *__restrict__ partial_min /* nullptr, or: look ahead as in k_restrict */)
+          double *__restrict__ partial_min /* nullptr, or: look ahead as in k_restrict */, const double *__restrict__ coarse_q /* FAS only */)
 {
     const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -3138,14 +3283,14 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
     // this node's own state and residual: needed at the end, requested now
     const double q0 = fine_q[ii], q1 = fine_q[stride + ii], q2 = fine_q[2 * stride + ii], q3 = fine_q[3 * stride + ii],
                  q4 = fine_q[4 * stride + ii];
-    const double f0 = fine_residuals[ii], f1 = fine_residuals[stride + ii], f2 = fine_residuals[2 * stride + ii],
-                 f3 = fine_residuals[3 * stride + ii], f4 = fine_residuals[4 * stride + ii];
+    const double f0 = FAS ? 0.0 : fine_residuals[ii], f1 = FAS ? 0.0 : fine_residuals[stride + ii], f2 = FAS ? 0.0 : fine_residuals[2 * stride + ii],
+                 f3 = FAS ? 0.0 : fine_residuals[3 * stride + ii], f4 = FAS ? 0.0 : fine_residuals[4 * stride + ii];
     const double ws = pro_wsum[ii];
     // The node's own parent appears in every entry (and, through the reference's b1-for-a1 quirk,
     // as BOTH terms of every entry in which this node is the edge's 'b' end): fetch it once.
     const int64_t own = parent < 0 ? int64_t(~parent) : int64_t(parent);
-    const double o0 = coarse_residuals[own], o1 = coarse_residuals[sc + own], o2 = coarse_residuals[2 * sc + own],
-                 o3 = coarse_residuals[3 * sc + own], o4 = coarse_residuals[4 * sc + own];
+    const double o0 = pro_coarse<FAS>(coarse_residuals, coarse_q, own), o1 = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + own), o2 = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + own),
+                 o3 = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + own), o4 = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + own);
     double r0, r1, r2, r3, r4;
     if (parent < 0) {
         r0 = o0; r1 = o1; r2 = o2; r3 = o3; r4 = o4;
@@ -3162,8 +3307,8 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
             double x0 = o0, x1 = o1, x2 = o2, x3 = o3, x4 = o4;
             if (p_other != parent) {                                   // the other end's parent: gather
                 const int64_t px = p_other;
-                x0 = coarse_residuals[px]; x1 = coarse_residuals[sc + px]; x2 = coarse_residuals[2 * sc + px];
-                x3 = coarse_residuals[3 * sc + px]; x4 = coarse_residuals[4 * sc + px];
+                x0 = pro_coarse<FAS>(coarse_residuals, coarse_q, px); x1 = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + px); x2 = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + px);
+                x3 = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + px); x4 = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + px);
             }
             r0 += w_other * x0; r1 += w_other * x1; r2 += w_other * x2; r3 += w_other * x3; r4 += w_other * x4;
         }
@@ -3187,14 +3332,16 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
 // hundred) are read from HBM once, 40 bytes each, and every entry then finds them in LDS instead
 // of gathering five scattered doubles through L1.  Same entries, same order, same arithmetic.
 // ------------------------------------------------------------------------------------------
+template <bool FAS>
 __global__ void __launch_bounds__(kBlock)
 k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__restrict__ slice_row0,
                const int32_t *__restrict__ rows_int, const double *__restrict__ pro_w,
                const uint16_t *__restrict__ pro_s16, const uint16_t *__restrict__ pro_own16,
                const int32_t *__restrict__ pro_tile_n, const int32_t *__restrict__ pro_tile_ids,
                const int32_t *__restrict__ pro_parent, const double *__restrict__ pro_wsum,
-               const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals,
-               double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl, double *__restrict__ partial_min)
+               const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals /* not FAS */,
+               double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl, double *__restrict__ partial_min,
+               const double *__restrict__ coarse_q /* FAS only */)
 {
     __shared__ double cr[kProCap * 5];
     const unsigned t = xcd_contiguous_block(blockIdx.x, gridDim.x);   // neighbouring tiles (they share coarse parents) on one XCD's L2
@@ -3220,8 +3367,8 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
     const uint32_t own_slot = pro_own16[ii];
     const double q0 = fine_q[ii], q1 = fine_q[stride + ii], q2 = fine_q[2 * stride + ii], q3 = fine_q[3 * stride + ii],
                  q4 = fine_q[4 * stride + ii];
-    const double f0 = fine_residuals[ii], f1 = fine_residuals[stride + ii], f2 = fine_residuals[2 * stride + ii],
-                 f3 = fine_residuals[3 * stride + ii], f4 = fine_residuals[4 * stride + ii];
+    const double f0 = FAS ? 0.0 : fine_residuals[ii], f1 = FAS ? 0.0 : fine_residuals[stride + ii], f2 = FAS ? 0.0 : fine_residuals[2 * stride + ii],
+                 f3 = FAS ? 0.0 : fine_residuals[3 * stride + ii], f4 = FAS ? 0.0 : fine_residuals[4 * stride + ii];
     const double ws = pro_wsum[ii];
     // the first row pair's entries go out before the staging barrier too (they do not depend on the staged residuals)
     const double *wr = pro_w + (int64_t(row0) << 7) + lane;
@@ -3231,14 +3378,14 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
     {
         // (a thread without a staged node of its own gathers node 0 and stores nothing: the load is never conditional)
         const int64_t c = c_first >= 0 ? c_first : 0;
-        const double d0 = coarse_residuals[c], d1 = coarse_residuals[sc + c], d2 = coarse_residuals[2 * sc + c],
-                     d3 = coarse_residuals[3 * sc + c], d4 = coarse_residuals[4 * sc + c];
+        const double d0 = pro_coarse<FAS>(coarse_residuals, coarse_q, c), d1 = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + c), d2 = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + c),
+                     d3 = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + c), d4 = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + c);
         if (tid < n_ids) { double *d = cr + tid * 5; d[0] = d0; d[1] = d1; d[2] = d2; d[3] = d3; d[4] = d4; }
         for (int32_t k = tid + kBlock; k < n_ids; k += kBlock) {        // (a tile that refers to more than 256 coarse nodes: rare)
             const int64_t c2 = ids[k];
             double *d = cr + k * 5;
-            d[0] = coarse_residuals[c2]; d[1] = coarse_residuals[sc + c2]; d[2] = coarse_residuals[2 * sc + c2];
-            d[3] = coarse_residuals[3 * sc + c2]; d[4] = coarse_residuals[4 * sc + c2];
+            d[0] = pro_coarse<FAS>(coarse_residuals, coarse_q, c2); d[1] = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + c2); d[2] = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + c2);
+            d[3] = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + c2); d[4] = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + c2);
         }
     }
     __syncthreads();
@@ -3695,19 +3842,56 @@ void launch_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, 
                        cfl, partial_min, rms);
 }
 
-void launch_prolong(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_residuals,
-                    const double *fine_residuals, double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
+// FAS = false: coarse_a = the coarse residuals, fine_residuals given; FAS = true: coarse_a = W0, coarse_q = W, no fine residuals
+template <bool FAS>
+static void launch_prolong_kind(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_a, const double *coarse_q,
+                                const double *fine_residuals, double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
 {
     // grid_for(nel) workgroups: the same partition k_step_factor_local's partial minima use
     if (p.pro_tiled) {
-        hipLaunchKernelGGL(k_prolong_tile, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
+        hipLaunchKernelGGL(k_prolong_tile<FAS>, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
                            p.slice_row0, p.rows_int, p.pro_w, p.pro_s16, p.pro_own16, p.pro_tile_n, p.pro_tile_ids,
-                           p.pro_parent, p.pro_wsum, coarse_residuals, fine_residuals, fine_q, cbrt_vol, cfl, partial_min);
+                           p.pro_parent, p.pro_wsum, coarse_a, fine_residuals, fine_q, cbrt_vol, cfl, partial_min, coarse_q);
         return;
     }
-    hipLaunchKernelGGL(k_prolong, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
-                       p.slice_row0, p.rows_int, p.pro_w, p.pro_p, p.pro_parent, p.pro_wsum, coarse_residuals, fine_residuals, fine_q,
-                       cbrt_vol, cfl, partial_min);
+    hipLaunchKernelGGL(k_prolong<FAS>, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
+                       p.slice_row0, p.rows_int, p.pro_w, p.pro_p, p.pro_parent, p.pro_wsum, coarse_a, fine_residuals, fine_q,
+                       cbrt_vol, cfl, partial_min, coarse_q);
+}
+void launch_prolong(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_residuals,
+                    const double *fine_residuals, double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
+{ launch_prolong_kind<false>(st, p, stride_coarse, coarse_residuals, nullptr, fine_residuals, fine_q, cbrt_vol, cfl, partial_min); }
+
+// the up leg of a FAS cycle: variables[fine] += 0.0 - wavg(W0 - W) of the coarse level
+void launch_prolong_fas(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_w0, const double *coarse_q,
+                        double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
+{ launch_prolong_kind<true>(st, p, stride_coarse, coarse_w0, coarse_q, nullptr, fine_q, cbrt_vol, cfl, partial_min); }
+
+void launch_restrict_fas(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, const int32_t *child_ptr,
+                         const int32_t *child, const int32_t *child4, const double *fine_q, const double *fine_r, const double *fine_p,
+                         double *coarse_q, double *w0, double *qsum)
+{
+    hipLaunchKernelGGL(k_restrict_fas, dim3(grid_for(nel_coarse)), dim3(kBlock), 0, st, nel_coarse, stride_coarse, stride_fine,
+                       child_ptr, child, reinterpret_cast<const int4 *>(child4), fine_q, fine_r, fine_p, coarse_q, w0, qsum);
+}
+
+void launch_fas_forcing(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, const int32_t *child_ptr, const double *fluxes,
+                        double *forcing)
+{ hipLaunchKernelGGL(k_fas_forcing, dim3(grid_for(nel_coarse)), dim3(kBlock), 0, st, nel_coarse, stride_coarse, child_ptr, fluxes, forcing); }
+
+void launch_fas_add_forcing(hipStream_t st, int64_t stride, double *fluxes, const double *forcing)
+{ hipLaunchKernelGGL(k_fas_add_forcing, dim3(grid_for(stride * 5)), dim3(kBlock), 0, st, stride * 5, fluxes, forcing); }
+
+// time_step on a FAS-forced level: F + P, or (F - src) + P where d.order is 1 or 2 (0: dual time off, d otherwise unused)
+void launch_time_step_fas(hipStream_t st, int64_t nel, int64_t stride, int j, const double *sf, const double *fluxes,
+                          const double *forcing, const double *old_variables, double *q, const int32_t *old_of_new,
+                          unsigned long long *err, int check, double *residuals, const DualSource &d)
+{
+    const double rk_div = double(3 + 1 - j);
+    with_constant<0, 1, 2>(d.order, [&](auto src) {
+        hipLaunchKernelGGL((k_time_step_fas<decltype(src)::value>), dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, rk_div, sf, fluxes,
+                           forcing, old_variables, q, old_of_new, err, check, residuals, d);
+    });
 }
 
 } // namespace MGCFD_KERNEL_NS

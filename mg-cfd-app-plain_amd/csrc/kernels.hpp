@@ -71,6 +71,20 @@
     void launch_prolong(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_residuals,      \
                         const double *fine_residuals, double *fine_q, const double *cbrt_vol,                       \
                         double cfl, double *partial_min);                                                            \
+    void launch_restrict_fas(hipStream_t, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine,            \
+                             const int32_t *child_ptr, const int32_t *child, const int32_t *child4,                  \
+                             const double *fine_q, const double *fine_r, const double *fine_p, double *coarse_q,     \
+                             double *w0, double *qsum);                                                              \
+    void launch_fas_forcing(hipStream_t, int64_t nel_coarse, int64_t stride_coarse, const int32_t *child_ptr,        \
+                            const double *fluxes, double *forcing);                                                  \
+    void launch_fas_add_forcing(hipStream_t, int64_t stride, double *fluxes, const double *forcing);                 \
+    void launch_time_step_fas(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                     \
+                              const double *fluxes, const double *forcing, const double *old_variables, double *q,  \
+                              const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,     \
+                              const DualSource &);                                                                   \
+    void launch_prolong_fas(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_w0,         \
+                            const double *coarse_q, double *fine_q, const double *cbrt_vol, double cfl,              \
+                            double *partial_min);                                                                    \
     } }
 
 MGCFD_DECLARE_LAUNCHERS(exact)
@@ -93,5 +107,7 @@ struct Launchers {
     decltype(exact::launch_step_factor_nodal) *step_factor_nodal;    decltype(exact::launch_smooth) *smooth;
     decltype(exact::launch_time_step_dual) *time_step_dual;          decltype(exact::launch_dual_source) *dual_source;
     decltype(exact::launch_jst_sensor) *jst_sensor;                  decltype(exact::launch_jst_dissipation) *jst_dissipation;
+    decltype(exact::launch_restrict_fas) *restrict_fas;              decltype(exact::launch_prolong_fas) *prolong_fas;
+    decltype(exact::launch_time_step_fas) *time_step_fas;
 };
 }

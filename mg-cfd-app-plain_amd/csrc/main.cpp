@@ -68,6 +68,8 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool jst_given = false;           // mgcfd_set_jst before the first cycle
     double jst_kappa2 = MGCFD_JST_KAPPA2, jst_kappa4 = MGCFD_JST_KAPPA4;
     int jst_levels = 1;
+    // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
+    bool fas = false;
     // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
     // physical_time_step / time_steps / dual_time_clamp / bdf_order.  With DT given, -g is the number of cycles per physical step.
     bool dual_given = false;          // a DT was given: mgcfd_set_dual_time before the first cycle, mgcfd_advance for the cycles
@@ -220,6 +222,7 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         else { std::fprintf(stderr, "ERROR: smoothing_iterations = '%s': expected a whole number 0 ... %d\n", value.c_str(), MGCFD_MAX_SMOOTHING_ITERATIONS); c.config_bad = true; }
     }
     else if (key == "jst") { if (value == "Y") c.jst_given = true; }
+    else if (key == "fas") { if (value == "Y") c.fas = true; }
     else if (key == "jst_kappa2" || key == "jst_kappa4") {
         if (parse_not_negative(value.c_str(), key == "jst_kappa2" ? &c.jst_kappa2 : &c.jst_kappa4)) c.jst_given = true;
         else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number, zero or above\n", key.c_str(), value.c_str()); c.config_bad = true; }
@@ -331,6 +334,9 @@ void print_help()
         "                                   pressure sensor sees a shock, a small fourth difference takes over elsewhere; with\n"
         "                                   kappa2 = 2.5, kappa4 = 0.15625 on level 0 unless said otherwise.  One GPU, or --gpus N with\n"
         "                                   one multigrid level per GPU; not with --gpus-partition or a level split over GPUs\n"
+        "  --fas                            FAS multigrid (config key fas = Y): the coarse levels carry the fine level's residual as a\n"
+        "                                   forcing term and return a correction, so the V-cycles converge to the fine grid's steady\n"
+        "                                   state; one GPU, an input of two levels or more\n"
         "  --jst-kappa2=X                   its second-difference coefficient, finite, zero or above, in units of the reference's\n"
         "                                   dissipation (config key jst_kappa2; implies --jst)\n"
         "  --jst-kappa4=X                   its fourth-difference coefficient, likewise (config key jst_kappa4; implies --jst)\n"
@@ -389,6 +395,7 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"dual-time-clamp", required_argument, nullptr, 1024},
         {"bdf-order", required_argument, nullptr, 1025},
         {"jst", no_argument, nullptr, 1026},
+        {"fas", no_argument, nullptr, 1030},
         {"jst-kappa2", required_argument, nullptr, 1027},
         {"jst-kappa4", required_argument, nullptr, 1028},
         {"jst-levels", required_argument, nullptr, 1029},
@@ -495,6 +502,7 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 c.dual_extras_given = true;
                 break;
             case 1026: c.jst_given = true; break;
+            case 1030: c.fas = true; break;
             case 1027:
             case 1028:
                 if (!parse_not_negative(optarg, optc == 1027 ? &c.jst_kappa2 : &c.jst_kappa4)) {
@@ -849,6 +857,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --gpus-partition: levels split over GPUs are out of scope\n");
         return 1;
     }
+    if (conf.fas && conf.gpus > 1) {
+        std::fprintf(stderr, "ERROR: FAS multigrid (--fas) runs on one GPU only: levels split over GPUs, or one level per GPU, would need the residuals, the forcing and the corrections exchanged\n");
+        return 1;
+    }
     if (conf.dual_given && conf.polar) {
         std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --polar\n");
         return 1;
@@ -882,6 +894,10 @@ int main(int argc, char **argv)
     const int problem_size = mgcfd_mesh_size(mesh);
 
     const double t_read = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    if (conf.fas && levels < 2) {
+        std::fprintf(stderr, "ERROR: FAS multigrid (--fas) needs an input of two levels or more: with one level there is no coarse level to force and no correction to bring back\n");
+        return 1;
+    }
     if (conf.gpus > 1) return run_on_several_gpus(conf, mesh, levels, mesh_variant, problem_size);
 
     mgcfd_solver *solver = nullptr;
@@ -910,6 +926,7 @@ int main(int argc, char **argv)
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
     if (conf.smoothing_given && mgcfd_set_residual_smoothing(solver, conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
     if (conf.jst_given && mgcfd_set_jst(solver, conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
+    if (conf.fas && mgcfd_set_fas(solver, 1) != MGCFD_OK) return fail("switching FAS multigrid on");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
         [&](double *rms_out, double *loads_out) {

@@ -177,6 +177,7 @@ struct DeviceLevel {
     double *jst_buf = nullptr;           // [7][stride]: the JST dissipation's L [5], nu and r (allocated when it is first switched on for this level)
     double *time_n = nullptr, *time_n1 = nullptr;   // [5][stride] each: dual time stepping's time levels Wn and Wn1 (held while it is on)
     const double *flux_in = nullptr;     // the state the last flux launch read: W of the dual-time source
+    double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while dual time is on: its RMS is summed in original numbering
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
     double *min_dt = nullptr;            // global-min time step scalar (after the reduction)
@@ -332,8 +333,13 @@ struct mgcfd_solver {
     double jst_kappa2 = 0.0, jst_kappa4 = 0.0;
     int jst_levels = 0;
     bool jst_on(int l) const { return l < jst_levels; }
-    // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while either is on
-    bool ordered_rms() const { return dual_time() || jst_on(0); }
+    // FAS multigrid (mgcfd_set_fas): the V-cycle's transfers become the FAS legs (op_fas_restrict, op_fas_prolong) and every stage
+    // of a level >= 1 takes R + P for its total residual R.  Such a level runs unfused stages (standalone flux launch + the
+    // forced update): no fused stage, no look-ahead; no graph on any level.  Level 0 sweeps as ever.
+    bool fas = false;
+    bool fas_forced(int l) const { return fas && l >= 1; }
+    // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while any of them is on
+    bool ordered_rms() const { return dual_time() || jst_on(0) || fas; }
     JstStep jst_step(DeviceLevel &lv) const
     {
         JstStep a;
@@ -376,7 +382,8 @@ struct mgcfd_solver {
 #define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
                                 NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_dual, NS::launch_dual_source, \
-                                NS::launch_jst_sensor, NS::launch_jst_dissipation}
+                                NS::launch_jst_sensor, NS::launch_jst_dissipation, NS::launch_restrict_fas, NS::launch_prolong_fas, \
+                                NS::launch_time_step_fas}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -487,7 +494,8 @@ struct mgcfd_solver {
             else k().step_factor_nodal(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.volumes, cfl, lv.step_factors, old);
         } else {
             // (dual time stepping clamps final step factors: nothing is left to the first time_step then)
-            const bool finish = !fused || dual_time();
+            // (... nor on a FAS-forced level, whose time_step takes final factors)
+            const bool finish = !fused || dual_time() || fas_forced(l);
             op_step_factor_local(l, fused && copy_old, finish);
             if (finish) op_step_factor_apply(l);
             else apply_pending = true;
@@ -686,6 +694,8 @@ struct mgcfd_solver {
             // dual time stepping: F' = F - src into fluxes[] first, in a node-wise launch of its own — the first iteration forms
             // D = sf * F' for halo nodes too, which would read three more states per staged node inside k_smooth_tile
             if (dual_time()) k().dual_source(stream, lv.info.nel, lv.dp.stride, lv.fluxes, dual_source(lv));
+            // FAS: the forcing is the last addition, F' = (F - src) + P, node-wise as the source
+            if (fas_forced(l)) exact::launch_fas_add_forcing(stream, lv.dp.stride, lv.fluxes, lv.fas_p);
             SmoothStep a;
             a.fluxes = lv.fluxes; a.step_factors = lv.step_factors; a.eps = irs_eps;
             for (int m = 0; m < irs_iters; m++) {
@@ -704,6 +714,18 @@ struct mgcfd_solver {
             return;
         }
         Timed t(this, l, MGCFD_LOOP_TIME_STEP);
+        if (fas_forced(l)) {
+            // the update with F + P, or (F - src) + P, for F, in the one launch; the step factors are final (op_step_factor)
+            if (apply_min != ApplyMin::None) throw std::invalid_argument("FAS multigrid: the step factors must be final before time_step");
+            DualSource d;
+            if (dual_time()) d = dual_source(lv); else d.order = 0;
+            k().time_step_fas(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, lv.fas_p, old, out, lv.dp.old_of_new, err, next_check(),
+                              with_residual ? lv.residuals : nullptr, d);
+            lv.fluxes_stale = true;                 // (never written: logically zero, as after a lazy time_step)
+            lv.fluxes_zero = true;
+            lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
+            return;
+        }
         if (dual_time()) {
             // the update with F - src for F, in the one launch; the step factors are final and clamped (op_step_factor)
             if (apply_min != ApplyMin::None) throw std::invalid_argument("dual time: the step factors must be final before time_step");
@@ -768,6 +790,61 @@ struct mgcfd_solver {
         k().prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, cfl, pm);
         F.min_ahead = ahead;
         F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;  // mg_loops.cpp:728,842
+    }
+    // ---- FAS multigrid: the two legs of the cycle (mgcfd.h) ----
+    // R_l(variables[l]) into fluxes[l], from zero fluxes: the fluxes of all three classes (+ C on a JST level: op_flux), then
+    // - src while dual time is on.  Serves step 1 and step 4 of the down leg; counted and timed as flux launches.
+    void op_total_residual(int l)
+    {
+        DeviceLevel &lv = level(l);
+        if (!lv.fluxes_zero) throw std::invalid_argument("FAS multigrid: the total residual needs zero fluxes (as after time_step)");
+        op_flux(l, 7);
+        if (dual_time()) {
+            Timed t(this, l, MGCFD_LOOP_FLUX);
+            k().dual_source(stream, lv.info.nel, lv.dp.stride, lv.fluxes, dual_source(lv));
+        }
+    }
+    // down-leg steps 1-4: T = R (+ P) of the fine level; the state restricted as mg_restrict does it, W0 its copy, Q the
+    // children's summed T, in one launch; then P = Q - R(W0) on the coarse level.  Both levels' fluxes are logically zero after.
+    void op_fas_restrict(int fine)
+    {
+        if (!fas) throw std::invalid_argument("FAS multigrid is off: switch it on first (mgcfd_set_fas)");
+        DeviceLevel &F = level(fine);
+        DeviceLevel &C = level(fine + 1);
+        if (!F.has_transfer) throw std::invalid_argument("level has no multigrid map");
+        if (!C.fluxes_zero) throw std::invalid_argument("FAS multigrid: the coarse level needs zero fluxes (as after time_step)");
+        op_total_residual(fine);
+        settle_residuals(C);
+        {
+            Timed t(this, fine + 1, MGCFD_LOOP_RESTRICT);       // (booked on the coarse level, as op_restrict)
+            k().restrict_fas(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
+                             fine >= 1 ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p);
+        }
+        F.fluxes_zero = true; F.fluxes_stale = true;            // (T is used up)
+        C.min_ahead = false;
+        C.iters[MGCFD_LOOP_RESTRICT] += 2 * F.info.mgc + C.info.nel;
+        op_total_residual(fine + 1);                            // R(W0): variables[fine + 1] is W0 now
+        {
+            Timed t(this, fine + 1, MGCFD_LOOP_FLUX);
+            exact::launch_fas_forcing(stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p);
+        }
+        C.fluxes_zero = true; C.fluxes_stale = true;
+    }
+    // up-leg steps 1-2: variables[fine] += 0.0 - wavg(W0 - variables[fine + 1]); no residuals array is touched
+    void op_fas_prolong(int fine)
+    {
+        if (!fas) throw std::invalid_argument("FAS multigrid is off: switch it on first (mgcfd_set_fas)");
+        DeviceLevel &F = level(fine);
+        DeviceLevel &C = level(fine + 1);
+        if (!F.has_transfer) throw std::invalid_argument("level has no multigrid map");
+        settle_residuals(F);                                    // (an unwritten residual's operand is about to change)
+        // (the look-ahead only where the sweep that follows takes it: level 0's fused stages under a global time step)
+        const bool ahead = global_dt() && !fas_forced(fine) && F.n_owned == F.info.nel;
+        double *pm = ahead ? F.partial_min : nullptr;
+        Timed t(this, fine, MGCFD_LOOP_PROLONG);
+        k().prolong_fas(stream, F.dp, C.dp.stride, C.fas_w0, C.q, F.q, F.cbrt_vol, cfl, pm);
+        F.min_ahead = ahead;
+        F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;
     }
     // Synchronises.  seq (may be null): the sequence number of the checked launch that found it.
     int read_error(int64_t *bad_cell, int *seq = nullptr)
@@ -1479,6 +1556,7 @@ static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mac
         lv.min_ahead = false;
         lv.have_sumsq = false;
         lv.stage_out = nullptr;                 // (MGCFD_ARR_STAGE named a stage of the state that has just gone)
+        if (lv.fas_p) HIP_CHECK(hipMemsetAsync(lv.fas_p, 0, sizeof(double) * 5 * lv.dp.stride, s->stream));   // (the forcing belonged to the old state)
     }
     HIP_CHECK(hipMemsetAsync(s->err, 0xFF, sizeof(unsigned long long), s->stream));
     s->check_seq = 0;
@@ -1595,7 +1673,7 @@ int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels)
             if (!lv.jst_buf) lv.jst_buf = lv.mem.alloc<double>(static_cast<size_t>(7 * lv.dp.stride));
         }
         if (n > 0 && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
-        if (n == 0 && !s->dual_time()) s->L[0].mem.release(s->L[0].new_of_old_dev);
+        if (n == 0 && !s->dual_time() && !s->fas) s->L[0].mem.release(s->L[0].new_of_old_dev);
         for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->jst_levels = n;
         s->jst_kappa2 = n > 0 ? kappa2 : 0.0;
@@ -1608,6 +1686,46 @@ int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *le
     if (kappa2) *kappa2 = s->jst_kappa2;
     if (kappa4) *kappa4 = s->jst_kappa4;
     if (levels) *levels = s->jst_levels;
+    return MGCFD_OK;
+}
+
+// ---- FAS multigrid: the switch ----
+int mgcfd_set_fas(mgcfd_solver *s, int on)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (on && s->L.size() < 2) throw std::invalid_argument("FAS multigrid: a one-level solver has no coarse level to force");
+        if (on && (s->partitioned || s->comm))
+            throw std::invalid_argument("FAS multigrid: not on a partitioned solver or a rank (a level split over ranks would need T, P and D exchanged)");
+        require_no_sweep_under_way(s, "FAS multigrid");
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);
+        s->drop_graphs();
+        for (size_t l = 1; l < s->L.size(); l++) {
+            DeviceLevel &lv = s->L[l];
+            const size_t n = static_cast<size_t>(5 * lv.dp.stride);
+            if (on) {
+                if (!lv.fas_p) lv.fas_p = lv.mem.alloc<double>(n);
+                HIP_CHECK(hipMemsetAsync(lv.fas_p, 0, sizeof(double) * n, s->stream));
+                if (!lv.fas_w0) { lv.fas_w0 = lv.mem.alloc<double>(n); HIP_CHECK(hipMemsetAsync(lv.fas_w0, 0, sizeof(double) * n, s->stream)); }
+            } else {
+                lv.mem.release(lv.fas_p);
+                lv.mem.release(lv.fas_w0);
+            }
+        }
+        if (on && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
+        if (!on && !s->dual_time() && !s->jst_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
+        s->fas = on != 0;
+    });
+}
+int mgcfd_get_fas(const mgcfd_solver *s, int *on)
+{
+    REQUIRE(s);
+    if (on) *on = s->fas ? 1 : 0;
     return MGCFD_OK;
 }
 
@@ -1625,6 +1743,8 @@ int mgcfd_indirect_rw(mgcfd_solver *s, int level) { OP(s->op_indirect_rw(level))
 int mgcfd_residual(mgcfd_solver *s, int level) { OP(s->op_residual(level)); }
 int mgcfd_restrict(mgcfd_solver *s, int fine_level) { OP(s->op_restrict(fine_level)); }
 int mgcfd_prolong(mgcfd_solver *s, int fine_level) { OP(s->op_prolong(fine_level)); }
+int mgcfd_fas_restrict(mgcfd_solver *s, int fine_level) { OP(s->op_fas_restrict(fine_level)); }
+int mgcfd_fas_prolong(mgcfd_solver *s, int fine_level) { OP(s->op_fas_prolong(fine_level)); }
 int mgcfd_step_factor_local(mgcfd_solver *s, int level)
 {
     OP({
@@ -1708,7 +1828,7 @@ static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 static void smooth_once(mgcfd_solver *s, int level)
 {
     DeviceLevel &lv = s->level(level);
-    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
+    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->fas_forced(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
         // Fused stages: flux + time_step in one launch each.  No copy<double>(old_variables, variables)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
@@ -1789,7 +1909,7 @@ static void run_sweep(mgcfd_solver *s, int level)
     }
     // (only the fused launches are replayed: the unfused ones — the two-phase flux variant — leave host-side flags
     //  behind, fluxes_stale, that a replay would not set)
-    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
+    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->fas && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
     if (!graphable) {
         const int keep = s->opt_timing;
         if (!timed) s->opt_timing = 0;
@@ -1843,6 +1963,7 @@ static void require_no_smoothing(const mgcfd_solver *s, const char *who)
     if (s->smoothing()) throw std::invalid_argument(std::string(who) + ": not while residual smoothing is on (mgcfd_set_residual_smoothing; use mgcfd_smooth or the kernel-granular calls)");
     if (s->dual_time()) throw std::invalid_argument(std::string(who) + ": not while dual time stepping is on (mgcfd_set_dual_time; use mgcfd_smooth or the kernel-granular calls)");
     if (s->jst_on(0)) throw std::invalid_argument(std::string(who) + ": not while the JST dissipation is on (mgcfd_set_jst; use mgcfd_smooth or the kernel-granular calls)");
+    if (s->fas) throw std::invalid_argument(std::string(who) + ": not while FAS multigrid is on (mgcfd_set_fas; use mgcfd_smooth or the kernel-granular calls)");
 }
 // The same sweep split around the one collective a multi-GPU run needs (see mgcfd.h).
 static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
@@ -2024,11 +2145,15 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
             if (sampled) book.att_calls_sampled[loop]++;
             s->opt_timing = sampled ? 1 : 0;
         }
-        try { if (restriction) s->op_restrict(fine, task); else s->op_prolong(fine); } catch (...) { s->opt_timing = keep; throw; }
+        try {
+            if (s->fas) { if (restriction) s->op_fas_restrict(fine); else s->op_fas_prolong(fine); }      // the FAS legs (mgcfd.h)
+            else if (restriction) s->op_restrict(fine, task); else s->op_prolong(fine);
+        } catch (...) { s->opt_timing = keep; throw; }
         s->opt_timing = keep;
     };
     for (int l = 0; l < n; l++) {
-        if (l == 0) { s->L[0].want_sumsq = true; s->L[0].have_sumsq = false; }
+        // (FAS keeps level 0's fused stages but fixes the order of the RMS sum: their per-tile sums are not asked for)
+        if (l == 0) { s->L[0].want_sumsq = !s->ordered_rms(); s->L[0].have_sumsq = false; }
         sweep(l);                                                          // :383-508
         if (l == 0) {                                                      // :509-512
             DeviceLevel &l0 = s->L[0];
@@ -2088,7 +2213,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->fas && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2234,6 +2359,9 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (which == MGCFD_ARR_JST_LAPLACIAN) return lv.jst_buf;
             *ncols = 1;
             return lv.jst_buf + (which == MGCFD_ARR_JST_SENSOR ? 5 : 6) * lv.dp.stride;
+        case MGCFD_ARR_FAS_FORCING: case MGCFD_ARR_FAS_START:
+            if (!lv.fas_p) throw std::invalid_argument("MGCFD_ARR_FAS_*: levels >= 1 while FAS multigrid is on (mgcfd_set_fas)");
+            return which == MGCFD_ARR_FAS_FORCING ? lv.fas_p : lv.fas_w0;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2271,6 +2399,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         if (which == MGCFD_ARR_VOLUMES) throw std::invalid_argument("volumes are fixed at creation");
         if (which == MGCFD_ARR_JST_LAPLACIAN || which == MGCFD_ARR_JST_SENSOR || which == MGCFD_ARR_JST_RADIUS)
             throw std::invalid_argument("MGCFD_ARR_JST_*: read-only (every flux launch of a JST level overwrites them)");
+        if (which == MGCFD_ARR_FAS_FORCING || which == MGCFD_ARR_FAS_START)
+            throw std::invalid_argument("MGCFD_ARR_FAS_*: read-only (every FAS restriction overwrites them)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -2532,6 +2662,52 @@ int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *
         s->free_events.push_back(std::move(b));
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
+        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+    });
+}
+
+// ... and for one of FAS multigrid's launches between levels `fine_level` and `fine_level + 1`, behind one mgcfd_fas_restrict
+// (so that W0 equals the coarse state and the correction the prolongation interpolates is zero): kind 0 k_restrict_fas, 1 the
+// forcing launch, 2 k_time_step_fas on the coarse level (into the second state buffer, unchecked: the state stays), 3 the FAS
+// prolongation; and the launches they stand beside: 4 k_restrict, 5 k_time_step on the coarse level (likewise), 6 the
+// reference's prolongation (which moves the fine state launch after launch: re-initialise afterwards).
+int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        if (kind < 0 || kind > 6) throw std::invalid_argument("FAS launch kind: 0 ... 6");
+        s->op_fas_restrict(fine_level);             // (throws while FAS is off)
+        DeviceLevel &F = s->level(fine_level);
+        DeviceLevel &C = s->level(fine_level + 1);
+        s->settle_residuals(F);
+        DualSource none;
+        none.order = 0;
+        Event a = s->get_event(), b = s->get_event();
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
+        for (int k = 0; k < launches; k++) {
+            switch (kind) {
+                case 0: s->k().restrict_fas(s->stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
+                                            fine_level >= 1 ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p); break;
+                case 1: exact::launch_fas_forcing(s->stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p); break;
+                case 2: s->k().time_step_fas(s->stream, C.info.nel, C.dp.stride, 0, C.step_factors, C.fluxes, C.fas_p, C.q, C.q_alt, C.dp.old_of_new,
+                                             s->err, 0, nullptr, none); break;
+                case 3: s->k().prolong_fas(s->stream, F.dp, C.dp.stride, C.fas_w0, C.q, F.q, F.cbrt_vol, s->cfl, nullptr); break;
+                case 4: s->k().restrict_(s->stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol,
+                                         s->cfl, nullptr, SumTask{}); break;
+                case 5: s->k().time_step(s->stream, C.info.nel, C.dp.stride, 0, C.step_factors, C.fluxes, C.q, C.q_alt, C.dp.old_of_new, s->err, 0,
+                                         nullptr, 0, C.volumes, nullptr, 0); break;
+                default: s->k().prolong(s->stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, s->cfl, nullptr); break;
+            }
+        }
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
+        F.min_ahead = false;
+        C.min_ahead = false;
         *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
@@ -4773,7 +4949,7 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         }
         if (!on) {
             for (DeviceLevel &lv : s->L) { lv.mem.release(lv.time_n); lv.mem.release(lv.time_n1); lv.flux_in = nullptr; }
-            if (!s->jst_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);        // (the JST dissipation orders the RMS the same way)
+            if (!s->jst_on(0) && !s->fas) s->L[0].mem.release(s->L[0].new_of_old_dev);        // (the JST dissipation and FAS order the RMS the same way)
             s->dual_levels = 0;
         }
         for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)

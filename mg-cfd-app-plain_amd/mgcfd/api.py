@@ -24,7 +24,8 @@ NVAR = 5
 RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
-       "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11}
+       "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
+       "fas_forcing": 12, "fas_start": 13}
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -192,6 +193,11 @@ _SIGNATURES = [
     ("mgcfd_set_jst", C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
     ("mgcfd_get_jst", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("mgcfd_bench_jst", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_fas", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_get_fas", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("mgcfd_fas_restrict", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_fas_prolong", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_bench_fas", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -605,6 +611,28 @@ class Solver:
         self._c(self.lib.mgcfd_get_jst(self.handle, C.byref(k2), C.byref(k4), C.byref(n)))
         return k2.value, k4.value, n.value
 
+    # ---- FAS multigrid ----
+    def set_fas(self, on: bool = True):
+        """FAS multigrid (mgcfd_set_fas): the V-cycle restricts the fine level's residual beside its state, the coarse sweeps
+        carry the forcing ``P`` and what is prolonged is the coarse level's correction, so the cycle converges to the fine
+        grid's steady state.  Off by default.  The state stays; captured graphs are dropped.  Needs two levels or more; not on
+        partitioned solvers or ranks."""
+        self._c(self.lib.mgcfd_set_fas(self.handle, 1 if on else 0))
+
+    def fas(self) -> bool:
+        on = C.c_int()
+        self._c(self.lib.mgcfd_get_fas(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    def fas_restrict(self, fine):
+        """The down leg from level ``fine``: its total residual, the restricted state, ``fas_start`` and ``fas_forcing`` of
+        level ``fine + 1`` (mgcfd_fas_restrict)."""
+        self._c(self.lib.mgcfd_fas_restrict(self.handle, fine))
+
+    def fas_prolong(self, fine):
+        """The up leg onto level ``fine``: the coarse level's correction, interpolated as ``prolong`` does (mgcfd_fas_prolong)."""
+        self._c(self.lib.mgcfd_fas_prolong(self.handle, fine))
+
     def set_dual_time(self, dt: float, clamp: float = 2.0 / 3.0):
         """Time-accurate runs (mgcfd_set_dual_time): every stage's update carries the BDF source of the physical step ``dt`` and
         the pseudo step is clamped to ``clamp * dt / vol``; ``dt=0`` switches it off and releases the time levels.  The state
@@ -654,14 +682,16 @@ class Solver:
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
-              residual_smoothing=None, jst=None) -> List[dict]:
+              residual_smoothing=None, jst=None, fas: Optional[bool] = None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
         dict: ``alpha``, ``mach``, ``rms`` [cycles], ``loads`` [cycles, 6] and ``coefficients`` (CD CL CS CMx CMy CMz of the
         last cycle against that angle's far field).  ``time_step`` / ``cfl`` (None: as the solver has them) are set once,
         before the first angle, and stay (``set_time_step``); likewise ``residual_smoothing=(eps, iterations)``
-        (``set_residual_smoothing``) and ``jst=(kappa2, kappa4, levels)`` (``set_jst``)."""
+        (``set_residual_smoothing``), ``jst=(kappa2, kappa4, levels)`` (``set_jst``) and ``fas=True / False`` (``set_fas``)."""
+        if fas is not None:
+            self.set_fas(fas)
         if jst is not None:
             self.set_jst(*jst)
         if residual_smoothing is not None:
@@ -733,6 +763,15 @@ class Solver:
         one event pair (mgcfd_bench_jst); the JST dissipation must be on for level ``l``."""
         t = C.c_double()
         self._c(self.lib.mgcfd_bench_jst(self.handle, l, kind, launches, C.byref(t)))
+        return t.value
+
+    FAS_LAUNCHES = {"restrict_fas": 0, "forcing": 1, "time_step_fas": 2, "prolong_fas": 3, "restrict": 4, "time_step": 5, "prolong": 6}
+
+    def bench_fas(self, fine: int, kind: str, launches: int) -> float:
+        """Mean GPU seconds of one launch of ``kind`` (a key of ``FAS_LAUNCHES``) between levels ``fine`` and ``fine + 1`` over
+        ``launches`` back-to-back launches under one event pair (mgcfd_bench_fas); FAS multigrid must be on."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_fas(self.handle, fine, self.FAS_LAUNCHES[kind], launches, C.byref(t)))
         return t.value
 
     def bench_stream_ceiling(self, l: int, launches: int) -> float:
