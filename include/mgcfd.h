@@ -57,7 +57,9 @@ enum { MGCFD_ARR_VARIABLES = 0, MGCFD_ARR_OLD_VARIABLES, MGCFD_ARR_FLUXES, MGCFD
        MGCFD_ARR_JST_LAPLACIAN, MGCFD_ARR_JST_SENSOR, MGCFD_ARR_JST_RADIUS /* read-only: L [nel][5], nu [nel] and r [nel] of the last
                                  flux launch of a level the JST dissipation is on for (mgcfd_set_jst) */,
        MGCFD_ARR_FAS_FORCING, MGCFD_ARR_FAS_START /* read-only, levels >= 1 while FAS multigrid is on (mgcfd_set_fas): the forcing P and
-                                 the start state W0 [nel][5] of the last mgcfd_fas_restrict onto the level */ };
+                                 the start state W0 [nel][5] of the last mgcfd_fas_restrict onto the level */,
+       MGCFD_ARR_VISCOUS_STRESS /* read-only: the node stresses S [nel][12] of the last flux launch of a level the viscous terms are on
+                                 for (mgcfd_set_viscous): u v w | txx tyy tzz txy txz tyz | qx qy qz */ };
 
 /* Solver options (mgcfd_set_option) */
 enum {
@@ -474,6 +476,74 @@ int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *le
  * sweep counts per level; a volume-weighted state restriction. */
 int mgcfd_set_fas(mgcfd_solver *s, int on);
 int mgcfd_get_fas(const mgcfd_solver *s, int *on);
+/* Laminar viscous terms: the Navier-Stokes stresses, heat conduction and a no-slip wall.  No reference counterpart.  Per solver:
+ * mu > 0 (dynamic viscosity in the solver's units, constant: no Sutherland law), prandtl > 0, wall (0 = slip, as without the
+ * feature; 1 = no-slip, adiabatic), cfl_v > 0 (the viscous step limit, (c)) and levels >= 0: it runs on levels 0 .. levels-1
+ * (capped at the number of levels; 0 = off, the other arguments are then ignored), exactly mgcfd_set_jst's levels.  Off by
+ * default; with it off the solver launches what it launched and computes the bits it computed.
+ * Every operation below is one IEEE-754 double operation, never contracted to FMA under MGCFD_OPT_EXACT = 1.  Both passes run over
+ * the level's internal edges only, in the level's original edge order, one addition per edge at each end.  For an edge record
+ * (a, b, e) the normal seen from end a is n = (e.x, e.y, e.z) and the other node is b; seen from end b it is n = (-e.x, -e.y, -e.z)
+ * (the negation is exact) and the other node is a.  W is the state the stage's fluxes were computed from.
+ *   (a) pass 1, node i: the node stresses S_i, twelve doubles.  u = mx / rho, v = my / rho, w = mz / rho; p the reference's
+ *       pressure ((GAMMA-1)*(en - 0.5*rho*speed_sqd), speed_sqd = u*u + v*v + w*w left to right); T = p / rho.
+ *       For phi in (u, v, w, T) and d in (x, y, z): A[phi][d] from +0.0, A[phi][d] += (phi_j - phi_i) * n_d per edge at i;
+ *       G[phi][d] = (0.5 * A[phi][d]) / vol_i with the volumes the step factor uses (Green-Gauss in difference form: wherever a
+ *       node's dual surface closes it equals the face-value form with the boundary faces included, it needs no boundary edge
+ *       and is exactly zero for a uniform field).
+ *       div = (G[u][x] + G[v][y]) + G[w][z];  t = (2.0/3.0) * div;
+ *       txx = mu * (2.0 * G[u][x] - t), tyy and tzz likewise;  txy = mu * (G[u][y] + G[v][x]);  txz = mu * (G[u][z] + G[w][x]);
+ *       tyz = mu * (G[v][z] + G[w][y]);  q_d = kappa * G[T][d], kappa = (mu * GAMMA) / ((GAMMA - 1.0) * prandtl) formed once on
+ *       the host.  S_i = (u, v, w, txx, tyy, tzz, txy, txz, tyz, qx, qy, qz).  A node without internal edges has zero
+ *       stresses, heat flux and viscous flux.
+ *   (b) pass 2, node i: V_i[1..4] from +0.0 over the same edges in the same order with the same n; barred values are
+ *       0.5 * (x_i + x_j) of the twelve components of S:
+ *       fx = (txx*nx + txy*ny) + txz*nz;  fy = (txy*nx + tyy*ny) + tyz*nz;  fz = (txz*nx + tyz*ny) + tzz*nz;
+ *       ex = ((u*txx + v*txy) + w*txz) + qx, ey and ez likewise with the matching rows of the tensor;
+ *       fe = (ex*nx + ey*ny) + ez*nz;   V_i[1] += fx; V_i[2] += fy; V_i[3] += fz; V_i[4] += fe.
+ *       Then F[i][v] = F[i][v] + V_i[v] for v = 1..4; F[i][0] is not touched.  The two ends of an edge receive exactly opposite
+ *       terms: the viscous flux is conservative.  Faces of the boundary classes carry no viscous flux: a wall (no-slip
+ *       adiabatic, or slip) has none by definition, the far field's is neglected.  Where the JST dissipation is on too, V is
+ *       added after C; everything behind F sees F + C + V: time_step, the dual-time source, the residual smoothing, FAS's total
+ *       residual R_l (step "2b. + V where mgcfd_set_viscous covers l"), residual, RMS, loads.  mgcfd_compute_fluxes and
+ *       mgcfd_compute_flux_edge include both passes on a viscous level, as they include JST's.
+ *   (c) the viscous step limit: at enable the host forms g_i = (cbrt(vol_i) * cbrt(vol_i)) / vol_i with libm's cbrt,
+ *       kv = max(4.0/3.0, GAMMA / prandtl) and k0 = cfl_v / (kv * mu).  After a sweep's step factors are final under the
+ *       mgcfd_set_time_step policy and before dual time stepping's clamp: sf[i] = min(sf[i], (k0 * rho_i) * g_i); a NaN factor
+ *       stays NaN.
+ *   (d) the no-slip wall (wall = 1): the wall nodes of a level are the distinct b ends of its solid-wall (class -1) edges.  A
+ *       small launch sets variables[i][1..3] = +0.0 there; density and energy stay.  It runs after every launch that writes a
+ *       viscous level's variables: every stage's update on every path, mgcfd_prolong / mgcfd_fas_prolong onto the level,
+ *       mgcfd_restrict / mgcfd_fas_restrict into it (W0 too), once at enable, and after mgcfd_set_free_stream(.., reinitialise
+ *       = 1).  Where the update wrote residuals the same launch stores residuals[i][v] = +0.0 - old_variables[i][v], v = 1..3:
+ *       the residual of the clamped state.  The invalid-state check looks at the update's result, as before.
+ * While it is on for level 0 the RMS of a cycle is summed in the order dual time stepping fixes on the original numbering.
+ * Launches: on a viscous level a stage is one standalone flux launch, JST's two launches where on, the stress launch and the
+ * viscous-flux launch, the update the other settings select and, with wall = 1, the wall launch; fused flux + time_step stages,
+ * the step-factor look-ahead and captured graphs are not used on that level (MGCFD_OPT_GRAPH is accepted and the launches run
+ * directly); other levels launch and compute what they did.  Timed as MGCFD_LOOP_FLUX; LoopNumIters counts are unchanged.
+ * MGCFD_OPT_EXACT = 0 may contract and may take the order-free kernel for F; the two passes keep edge order.
+ * mgcfd_set_viscous synchronises and drops every captured graph; the state stays but for the wall nodes' momentum.  The first
+ * enabling call allocates per viscous level S [12][stride], g [stride] and the wall-node list; switching off releases them.
+ * MGCFD_ERR_ARG, and nothing changed: levels < 0; with levels > 0 a mu, prandtl or cfl_v that is not finite and positive or a
+ * wall other than 0 and 1; while a kernel-granular sweep is under way; levels > 0 on a solver made by mgcfd_create_partitioned*
+ * or attached to a group or as a rank.  While it is on, mgcfd_sweep_begin*, mgcfd_sweep_flux0, mgcfd_sweep_stage and
+ * mgcfd_sweep_end* return MGCFD_ERR_ARG, and mgcfd_group_create and mgcfd_rank_attach_* refuse the solver.
+ * Out of scope: friction in the surface loads (mgcfd_surface_loads stays the pressure loads); an edge-direction correction of
+ * the face gradient (it needs node coordinates on the device); variable viscosity and turbulence models; viscous flux through
+ * far-field faces; levels split over ranks; graphs and fused stages with viscosity on.
+ * The weights are used as the solver holds them: on meshes whose variant makes the reference rescale them at load (every
+ * variant but fvcorr) the viscous terms inherit that rescaling as the inviscid ones do; physical statements are made on
+ * fvcorr-variant meshes.
+ * mgcfd_get_viscous: any pointer may be NULL; *levels is the capped number, 0 when off (the other values are then 0).
+ * mgcfd_viscosity_from_reynolds (host only): mu = rho_inf * |V_inf| * ref_length / reynolds from a far field as
+ * mgcfd_free_stream_constants / mgcfd_get_far_field give it; MGCFD_ERR_ARG unless reynolds, ref_length and the result are finite
+ * and positive. */
+#define MGCFD_VISCOUS_PRANDTL 0.72
+#define MGCFD_VISCOUS_CFL 0.25
+int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, double cfl_v, int levels);
+int mgcfd_get_viscous(const mgcfd_solver *s, double *mu, double *prandtl, int *wall, double *cfl_v, int *levels);
+int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double ref_length, double *mu);
 int mgcfd_fas_restrict(mgcfd_solver *s, int fine_level);
 int mgcfd_fas_prolong(mgcfd_solver *s, int fine_level);
 
@@ -599,6 +669,9 @@ int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int lau
 /* Diagnostic: the same for one of the JST dissipation's launches (kind 0: the sensor, 1: the dissipation, which adds into
  * fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where it is off. */
 int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* Diagnostic: the same for one of the viscous terms' launches (kind 0: the stress launch, 1: the viscous-flux launch, which adds
+ * into fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where they are off. */
+int mgcfd_bench_viscous(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Diagnostic: the same for one of FAS multigrid's launches between `fine_level` and the level above it, behind one
  * mgcfd_fas_restrict (kind 0: k_restrict_fas, 1: the forcing launch, 2: k_time_step_fas on the coarse level, 3: the FAS
  * prolongation) and for the launches they stand beside (4: k_restrict, 5: k_time_step on the coarse level, 6: the reference's

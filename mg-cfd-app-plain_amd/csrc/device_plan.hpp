@@ -131,6 +131,16 @@ struct JstStep {
     double kappa2 = 0.0, kappa4 = 0.0;
 };
 
+// The two launches of the viscous terms (kernels.hip: k_viscous_stress_tile, k_viscous_flux_tile; mgcfd_set_viscous): the stress
+// launch writes s from w; the flux launch reads s and adds the viscous flux V into components 1..4 of fluxes.
+struct ViscousStep {
+    const double *w = nullptr;                // the stage's input state W [5][stride]: what the fluxes were computed from
+    double *s = nullptr;                      // S [12][stride]: u v w | txx tyy tzz txy txz tyz | qx qy qz per node
+    const double *volumes = nullptr;          // [stride]
+    double *fluxes = nullptr;                 // the stage's fluxes F (+ C) [5][stride] (flux launch only): F = F + V
+    double mu = 0.0, kappa = 0.0;             // kappa = (mu * GAMMA) / ((GAMMA - 1) * prandtl), formed on the host
+};
+
 // The physical-time source of dual time stepping (kernels.hip: k_time_step_dual, k_dual_source; mgcfd_set_dual_time):
 //   src = vol * ((3 (W - Wn) - (Wn - Wn1)) / (2 dt))   order 2 (BDF2);   src = vol * ((W - Wn) / dt)   order 1 (BDF1, Wn1 not read)
 struct DualSource {

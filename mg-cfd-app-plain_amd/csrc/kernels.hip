@@ -2680,6 +2680,224 @@ k_jst_dissipation_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, 
     a.fluxes[3 * stride + i] = a.fluxes[3 * stride + i] + c3; a.fluxes[4 * stride + i] = a.fluxes[4 * stride + i] + c4;
 }
 
+// ------------------------------------------------------------------------------------------
+// Laminar viscous terms (no reference counterpart; INTEGRATION.md "Laminar viscous terms"): the Navier-Stokes stresses and
+// the heat flux as a CORRECTION V added to the stage's fluxes F (+ C), components 1..4.  Two node-centred gathers over the
+// internal incidence rows in row order, the walk k_jst_dissipation_tile does (halo table, nbr16, overflow list, long-row
+// lists; code and weights one row ahead of the sums), sums started at +0.0, one addition per edge.  The rows hold the edge
+// weights as the flux kernel wants them, f = -0.5 e at the a end and +0.5 e at the b end: the normal seen from this node
+// is n = -2.0 * f, exactly.
+//   k_viscous_stress_tile   A[phi][d] = sum (phi_j - phi_i) n_d for phi in (u, v, w, T = p / rho);  G = (0.5 A) / vol;
+//                           S_i = (u, v, w, txx, tyy, tzz, txy, txz, tyz, qx, qy, qz): Stokes' stresses at constant mu and
+//                           q = kappa grad T, finished per node so that pass 2 stages twelve doubles and not seventeen.
+//   k_viscous_flux_tile     V_i[1..3] = sum tau_bar . n,  V_i[4] = sum (tau_bar . v_bar + q_bar) . n,  bars = 0.5 (S_i + S_j);
+//                           fluxes_i[1..4] = fluxes_i[1..4] + V_i[1..4].
+// LDS, one field per array as in k_smooth_tile (a slot's doubles 8 B apart): the stress launch stages u, v, w, T derived
+// once per slot (four fields of 560 doubles, 17,920 B); the flux launch stages S (twelve fields, 53,760 B, the JST
+// dissipation launch's footprint; two workgroups per CU by LDS).  A halo node beyond the table is read — and for the stress
+// launch derived — from memory.  Pad lanes of the last tile write zeros to S so that whoever stages them reads numbers.
+// ------------------------------------------------------------------------------------------
+struct Primitive { double u, v, w, T; };
+
+__device__ __forceinline__ Primitive primitive_of(const double *__restrict__ q, int64_t stride, int64_t n)
+{
+    const double rho = q[n];
+    const Derived d = derive(rho, q[stride + n], q[2 * stride + n], q[3 * stride + n], q[4 * stride + n]);
+    Primitive r;
+    r.u = d.vx; r.v = d.vy; r.w = d.vz; r.T = d.p / rho;
+    return r;
+}
+
+template <bool TAIL>
+__global__ void __launch_bounds__(kBlock, 4)
+k_viscous_stress_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
+                      const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
+                      const double *__restrict__ w, const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf,
+                      TailPlan tp, ViscousStep a)
+{
+    __shared__ double rec[4][kSmoothRow];                              // u, v, w, T
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
+    const int64_t i = int64_t(t) * kTile + tid;
+    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
+    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
+    const int32_t hid = hrow[tid];
+    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;
+    const int32_t row0 = slice_row0[slice];
+    const int32_t n_int = (TAIL ? tp.rows_main : rows_int)[slice];
+    const int32_t ovf0 = tile_ovf_ptr[t];
+    const int64_t hnode = hid >= 0 ? int64_t(hid) : i;                 // (no halo node: a copy of the own one in the unused slot)
+    auto stage = [&](uint32_t slot, const Primitive &q) { rec[0][slot] = q.u; rec[1][slot] = q.v; rec[2][slot] = q.w; rec[3][slot] = q.T; };
+    const int64_t first_row = n_int > 0 ? row0 : 0;                    // (row 0 exists on every level; unused when n_int == 0)
+    uint32_t c = nbr16[(first_row << 6) + lane];
+    double fx = w[(first_row << 8) + lane], fy = w[(first_row << 8) + 64 + lane], fz = w[(first_row << 8) + 128 + lane];
+    const Primitive me = primitive_of(a.w, stride, i);
+    stage(uint32_t(tid), me);
+    stage(uint32_t(kTile + tid), primitive_of(a.w, stride, hnode));
+    if (hid2 >= 0) stage(uint32_t(kTile + kBlock + tid), primitive_of(a.w, stride, hid2));
+    int32_t tl_b = 0, tl_n = 0;
+    if (TAIL) { tl_b = tp.begin[i]; tl_n = tp.count[i]; }
+    const double vol = a.volumes[i];
+    __syncthreads();
+
+    double ux = 0.0, uy = 0.0, uz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0, wx = 0.0, wy = 0.0, wz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
+    auto add = [&](uint32_t code, double hx, double hy, double hz) {
+        const uint32_t s = code & kT16SlotMask;
+        if (s == kT16Pad) return;
+        Primitive ot;
+        if (s >= uint32_t(kTileCap)) ot = primitive_of(a.w, stride, tile_ovf[ovf0 + int32_t(s) - kTileCap]);
+        else { ot.u = rec[0][s]; ot.v = rec[1][s]; ot.w = rec[2][s]; ot.T = rec[3][s]; }
+        const double nx = -2.0 * hx, ny = -2.0 * hy, nz = -2.0 * hz;   // the rows hold -+0.5 e
+        const double du = ot.u - me.u, dv = ot.v - me.v, dw = ot.w - me.w, dT = ot.T - me.T;
+        ux += du * nx; uy += du * ny; uz += du * nz;
+        vx += dv * nx; vy += dv * ny; vz += dv * nz;
+        wx += dw * nx; wy += dw * ny; wz += dw * nz;
+        tx += dT * nx; ty += dT * ny; tz += dT * nz;
+    };
+    for (int32_t r = 0; r < n_int; r++) {                             // code and weights one row ahead of the sums
+        const bool more = r + 1 < n_int;
+        const int64_t nr = int64_t(row0 + r + 1);
+        const uint32_t cn = more ? nbr16[(nr << 6) + lane] : kT16Pad;
+        const double fxn = more ? w[(nr << 8) + lane] : 0.0, fyn = more ? w[(nr << 8) + 64 + lane] : 0.0, fzn = more ? w[(nr << 8) + 128 + lane] : 0.0;
+        add(c, fx, fy, fz);
+        c = cn; fx = fxn; fy = fyn; fz = fzn;
+    }
+    if (TAIL) {
+        for (int32_t k = 0; k < tl_n; k++) {
+            const double2 fxy = tp.rec[3 * int64_t(tl_b + k)], fzk = tp.rec[3 * int64_t(tl_b + k) + 1];
+            const unsigned long long word = static_cast<unsigned long long>(__double_as_longlong(tp.rec[3 * int64_t(tl_b + k) + 2].x));
+            add(static_cast<uint32_t>(word >> 16) & 0xFFFFu, fxy.x, fxy.y, fzk.x);
+        }
+    }
+    const double gux = (0.5 * ux) / vol, guy = (0.5 * uy) / vol, guz = (0.5 * uz) / vol;
+    const double gvx = (0.5 * vx) / vol, gvy = (0.5 * vy) / vol, gvz = (0.5 * vz) / vol;
+    const double gwx = (0.5 * wx) / vol, gwy = (0.5 * wy) / vol, gwz = (0.5 * wz) / vol;
+    const double gtx = (0.5 * tx) / vol, gty = (0.5 * ty) / vol, gtz = (0.5 * tz) / vol;
+    const double div = (gux + gvy) + gwz;
+    const double tt = (2.0 / 3.0) * div;
+    const bool present = i < nel;
+    double out[12];
+    out[0] = me.u; out[1] = me.v; out[2] = me.w;
+    out[3] = a.mu * (2.0 * gux - tt); out[4] = a.mu * (2.0 * gvy - tt); out[5] = a.mu * (2.0 * gwz - tt);
+    out[6] = a.mu * (guy + gvx); out[7] = a.mu * (guz + gwx); out[8] = a.mu * (gvz + gwy);
+    out[9] = a.kappa * gtx; out[10] = a.kappa * gty; out[11] = a.kappa * gtz;
+#pragma unroll
+    for (int f = 0; f < 12; f++) a.s[f * stride + i] = present ? out[f] : 0.0;
+}
+
+template <bool TAIL>
+__global__ void __launch_bounds__(kBlock, 2)
+k_viscous_flux_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
+                    const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
+                    const double *__restrict__ w, const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf,
+                    TailPlan tp, ViscousStep a)
+{
+    __shared__ double rec[12][kSmoothRow];                             // S
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
+    const int64_t i = int64_t(t) * kTile + tid;
+    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
+    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
+    const int32_t hid = hrow[tid];
+    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;
+    const int32_t row0 = slice_row0[slice];
+    const int32_t n_int = (TAIL ? tp.rows_main : rows_int)[slice];
+    const int32_t ovf0 = tile_ovf_ptr[t];
+    const int64_t hnode = hid >= 0 ? int64_t(hid) : i;                 // (no halo node: a copy of the own one in the unused slot)
+    struct Node { double s[12]; };
+    auto load = [&](int64_t n) {
+        Node q;
+#pragma unroll
+        for (int f = 0; f < 12; f++) q.s[f] = a.s[f * stride + n];
+        return q;
+    };
+    auto stage = [&](uint32_t slot, const Node &q) {
+#pragma unroll
+        for (int f = 0; f < 12; f++) rec[f][slot] = q.s[f];
+    };
+    const int64_t first_row = n_int > 0 ? row0 : 0;                    // (row 0 exists on every level; unused when n_int == 0)
+    uint32_t c = nbr16[(first_row << 6) + lane];
+    double fx = w[(first_row << 8) + lane], fy = w[(first_row << 8) + 64 + lane], fz = w[(first_row << 8) + 128 + lane];
+    const Node me = load(i);
+    stage(uint32_t(tid), me);
+    stage(uint32_t(kTile + tid), load(hnode));
+    if (hid2 >= 0) stage(uint32_t(kTile + kBlock + tid), load(hid2));
+    int32_t tl_b = 0, tl_n = 0;
+    if (TAIL) { tl_b = tp.begin[i]; tl_n = tp.count[i]; }
+    __syncthreads();
+
+    double v1 = 0.0, v2 = 0.0, v3 = 0.0, v4 = 0.0;
+    auto add = [&](uint32_t code, double hx, double hy, double hz) {
+        const uint32_t s = code & kT16SlotMask;
+        if (s == kT16Pad) return;
+        Node ot;
+        if (s >= uint32_t(kTileCap)) ot = load(tile_ovf[ovf0 + int32_t(s) - kTileCap]);
+        else {
+#pragma unroll
+            for (int f = 0; f < 12; f++) ot.s[f] = rec[f][s];
+        }
+        const double nx = -2.0 * hx, ny = -2.0 * hy, nz = -2.0 * hz;   // the rows hold -+0.5 e
+        double b[12];
+#pragma unroll
+        for (int f = 0; f < 12; f++) b[f] = 0.5 * (me.s[f] + ot.s[f]);
+        const double u = b[0], v = b[1], ww = b[2], txx = b[3], tyy = b[4], tzz = b[5], txy = b[6], txz = b[7], tyz = b[8];
+        const double ex = ((u * txx + v * txy) + ww * txz) + b[9];
+        const double ey = ((u * txy + v * tyy) + ww * tyz) + b[10];
+        const double ez = ((u * txz + v * tyz) + ww * tzz) + b[11];
+        v1 += (txx * nx + txy * ny) + txz * nz;
+        v2 += (txy * nx + tyy * ny) + tyz * nz;
+        v3 += (txz * nx + tyz * ny) + tzz * nz;
+        v4 += (ex * nx + ey * ny) + ez * nz;
+    };
+    for (int32_t r = 0; r < n_int; r++) {                             // code and weights one row ahead of the sums
+        const bool more = r + 1 < n_int;
+        const int64_t nr = int64_t(row0 + r + 1);
+        const uint32_t cn = more ? nbr16[(nr << 6) + lane] : kT16Pad;
+        const double fxn = more ? w[(nr << 8) + lane] : 0.0, fyn = more ? w[(nr << 8) + 64 + lane] : 0.0, fzn = more ? w[(nr << 8) + 128 + lane] : 0.0;
+        add(c, fx, fy, fz);
+        c = cn; fx = fxn; fy = fyn; fz = fzn;
+    }
+    if (TAIL) {
+        for (int32_t k = 0; k < tl_n; k++) {
+            const double2 fxy = tp.rec[3 * int64_t(tl_b + k)], fzk = tp.rec[3 * int64_t(tl_b + k) + 1];
+            const unsigned long long word = static_cast<unsigned long long>(__double_as_longlong(tp.rec[3 * int64_t(tl_b + k) + 2].x));
+            add(static_cast<uint32_t>(word >> 16) & 0xFFFFu, fxy.x, fxy.y, fzk.x);
+        }
+    }
+    if (i >= nel) return;
+    a.fluxes[stride + i] = a.fluxes[stride + i] + v1; a.fluxes[2 * stride + i] = a.fluxes[2 * stride + i] + v2;
+    a.fluxes[3 * stride + i] = a.fluxes[3 * stride + i] + v3; a.fluxes[4 * stride + i] = a.fluxes[4 * stride + i] + v4;
+}
+
+// The viscous limit on final step factors: sf = min(sf, (k0 * rho) * g), k0 = cfl_v / (kv * mu), g = cbrt(vol)^2 / vol from the host.
+__global__ void __launch_bounds__(kBlock)
+k_viscous_clamp(int64_t nel, double k0, const double *__restrict__ rho, const double *__restrict__ g, double *__restrict__ step_factors)
+{
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double sf = step_factors[i], cap = (k0 * rho[i]) * g[i];
+    step_factors[i] = cap < sf ? cap : sf;              // (a NaN factor stays NaN, as the invalid-state check expects)
+}
+
+// The no-slip wall: momentum +0.0 at the n listed nodes of q (and of q2, where given: FAS's copy of a restricted state);
+// where the launch before wrote residuals, the residual of the clamped state, +0.0 - old.
+__global__ void __launch_bounds__(kBlock)
+k_viscous_wall(int64_t n, int64_t stride, const int32_t *__restrict__ nodes, double *__restrict__ q, double *__restrict__ q2,
+               const double *__restrict__ old_variables, double *__restrict__ residuals)
+{
+    const int64_t k = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (k >= n) return;
+    const int64_t i = nodes[k];
+#pragma unroll
+    for (int v = 1; v <= 3; v++) {
+        q[v * stride + i] = 0.0;
+        if (q2) q2[v * stride + i] = 0.0;
+        if (residuals) residuals[v * stride + i] = 0.0 - old_variables[v * stride + i];
+    }
+}
+
 // check_for_invalid_variables as a standalone sweep
 __global__ void __launch_bounds__(kBlock)
 k_check_invalid(int64_t nel, int64_t stride, const double *__restrict__ q, const int32_t *__restrict__ old_of_new,
@@ -3760,6 +3978,27 @@ void launch_jst_dissipation(hipStream_t st, const DevicePlan &p, const JstStep &
                            p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
     });
 }
+
+// the two launches of the viscous terms: S from W; then fluxes[1..4] += V; the step-factor limit and the no-slip wall
+void launch_viscous_stress(hipStream_t st, const DevicePlan &p, const ViscousStep &a)
+{
+    with_bool(p.has_tail != 0, [&](auto tail) {
+        hipLaunchKernelGGL((k_viscous_stress_tile<decltype(tail)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
+    });
+}
+void launch_viscous_flux(hipStream_t st, const DevicePlan &p, const ViscousStep &a)
+{
+    with_bool(p.has_tail != 0, [&](auto tail) {
+        hipLaunchKernelGGL((k_viscous_flux_tile<decltype(tail)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
+    });
+}
+void launch_viscous_clamp(hipStream_t st, int64_t nel, double k0, const double *rho, const double *g, double *sf)
+{ hipLaunchKernelGGL(k_viscous_clamp, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, k0, rho, g, sf); }
+void launch_viscous_wall(hipStream_t st, int64_t n, int64_t stride, const int32_t *nodes, double *q, double *q2,
+                         const double *old_variables, double *residuals)
+{ if (n > 0) hipLaunchKernelGGL(k_viscous_wall, dim3(grid_for(n)), dim3(kBlock), 0, st, n, stride, nodes, q, q2, old_variables, residuals); }
 
 void launch_check_invalid(hipStream_t st, int64_t nel, int64_t stride, const double *q, const int32_t *old_of_new,
                           unsigned long long *err)

@@ -26,6 +26,11 @@
     void launch_smooth(hipStream_t, const DevicePlan &, const SmoothStep &);                                          \
     void launch_jst_sensor(hipStream_t, const DevicePlan &, const JstStep &);                                        \
     void launch_jst_dissipation(hipStream_t, const DevicePlan &, const JstStep &);                                   \
+    void launch_viscous_stress(hipStream_t, const DevicePlan &, const ViscousStep &);                                \
+    void launch_viscous_flux(hipStream_t, const DevicePlan &, const ViscousStep &);                                  \
+    void launch_viscous_clamp(hipStream_t, int64_t nel, double k0, const double *rho, const double *g, double *sf);  \
+    void launch_viscous_wall(hipStream_t, int64_t n, int64_t stride, const int32_t *nodes, double *q, double *q2,    \
+                             const double *old_variables, double *residuals);                                        \
     void launch_time_step_dual(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                   \
                                const double *fluxes, const double *old_variables, double *q,                       \
                                const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,    \
@@ -109,5 +114,6 @@ struct Launchers {
     decltype(exact::launch_jst_sensor) *jst_sensor;                  decltype(exact::launch_jst_dissipation) *jst_dissipation;
     decltype(exact::launch_restrict_fas) *restrict_fas;              decltype(exact::launch_prolong_fas) *prolong_fas;
     decltype(exact::launch_time_step_fas) *time_step_fas;
+    decltype(exact::launch_viscous_stress) *viscous_stress;          decltype(exact::launch_viscous_flux) *viscous_flux;
 };
 }

@@ -68,6 +68,14 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool jst_given = false;           // mgcfd_set_jst before the first cycle
     double jst_kappa2 = MGCFD_JST_KAPPA2, jst_kappa4 = MGCFD_JST_KAPPA4;
     int jst_levels = 1;
+    // laminar viscous terms: --viscosity MU or --reynolds RE (with --ref-length L), --prandtl X, --no-slip, --viscous-cfl X,
+    // --viscous-levels N and the config keys viscosity / reynolds / ref_length / prandtl / no_slip (Y) / viscous_cfl / viscous_levels
+    bool viscosity_given = false, reynolds_given = false;   // one of the two switches the terms on: mgcfd_set_viscous before the first cycle
+    bool viscous_extras_given = false;                      // one of the companions was given (they need MU or RE)
+    double viscosity = 0.0, reynolds = 0.0, ref_length = 1.0, prandtl = MGCFD_VISCOUS_PRANDTL, viscous_cfl = MGCFD_VISCOUS_CFL;
+    bool no_slip = false;
+    int viscous_levels = 1;
+    bool viscous() const { return viscosity_given || reynolds_given; }
     // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
     bool fas = false;
     // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
@@ -231,6 +239,18 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.jst_levels)) c.jst_given = true;
         else { std::fprintf(stderr, "ERROR: jst_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
     }
+    else if (key == "viscosity" || key == "reynolds" || key == "ref_length" || key == "prandtl" || key == "viscous_cfl") {
+        double *dst = key == "viscosity" ? &c.viscosity : key == "reynolds" ? &c.reynolds : key == "ref_length" ? &c.ref_length : key == "prandtl" ? &c.prandtl : &c.viscous_cfl;
+        if (parse_positive(value.c_str(), dst)) {
+            if (key == "viscosity") c.viscosity_given = true; else if (key == "reynolds") c.reynolds_given = true; else c.viscous_extras_given = true;
+        }
+        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "no_slip") { if (value == "Y") { c.no_slip = true; c.viscous_extras_given = true; } }
+    else if (key == "viscous_levels") {
+        if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.viscous_levels)) c.viscous_extras_given = true;
+        else { std::fprintf(stderr, "ERROR: viscous_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
+    }
     else if (key == "physical_time_step") {
         if (parse_positive(value.c_str(), &c.dual_dt)) c.dual_given = true;
         else { std::fprintf(stderr, "ERROR: physical_time_step = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
@@ -342,6 +362,20 @@ void print_help()
         "  --jst-kappa4=X                   its fourth-difference coefficient, likewise (config key jst_kappa4; implies --jst)\n"
         "  --jst-levels=N                   the multigrid levels 0 ... N-1 it runs on (default 1; 0 = off; config key jst_levels;\n"
         "                                   implies --jst)\n"
+        "  --viscosity=MU                   laminar viscous terms with dynamic viscosity MU, finite and above zero, in the solver's units\n"
+        "                                   (config key viscosity): Navier-Stokes stresses and heat conduction added to every stage's\n"
+        "                                   fluxes on level 0 unless said otherwise, and a viscous limit on the step.  One GPU, or --gpus N\n"
+        "                                   with one multigrid level per GPU; not with --gpus-partition or a level split over GPUs\n"
+        "  --reynolds=RE                    the same with MU = rho_inf * |V_inf| * L / RE of the free stream in use (after --mach / --alpha;\n"
+        "                                   config key reynolds); not together with --viscosity\n"
+        "  --ref-length=L                   the length L of --reynolds (default 1; config key ref_length)\n"
+        "  --prandtl=X                      the Prandtl number (default 0.72; config key prandtl)\n"
+        "  --no-slip                        solid walls are no-slip and adiabatic: momentum zero at their nodes (config key no_slip = Y;\n"
+        "                                   default: slip walls, as without viscosity)\n"
+        "  --viscous-cfl=X                  the step factors are limited to X * rho * h^2 / (max(4/3, gamma / Pr) * MU) (default 0.25;\n"
+        "                                   config key viscous_cfl)\n"
+        "  --viscous-levels=N               the multigrid levels 0 ... N-1 the viscous terms run on (default 1; 0 = off; config key\n"
+        "                                   viscous_levels)\n"
         "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
         "                                   (config key physical_time_step): BDF2 in physical time, every step solved in pseudo-time\n"
         "                                   by -g cycles (-g becomes the cycles PER PHYSICAL STEP; an RMS line per cycle as ever,\n"
@@ -399,6 +433,13 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"jst-kappa2", required_argument, nullptr, 1027},
         {"jst-kappa4", required_argument, nullptr, 1028},
         {"jst-levels", required_argument, nullptr, 1029},
+        {"viscosity", required_argument, nullptr, 1031},
+        {"reynolds", required_argument, nullptr, 1032},
+        {"ref-length", required_argument, nullptr, 1033},
+        {"prandtl", required_argument, nullptr, 1034},
+        {"viscous-cfl", required_argument, nullptr, 1035},
+        {"no-slip", no_argument, nullptr, 1036},
+        {"viscous-levels", required_argument, nullptr, 1037},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -518,11 +559,37 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 }
                 c.jst_given = true;
                 break;
+            case 1031: case 1032: case 1033: case 1034: case 1035: {
+                static const char *const names[] = {"viscosity", "reynolds", "ref-length", "prandtl", "viscous-cfl"};
+                double *const dst[] = {&c.viscosity, &c.reynolds, &c.ref_length, &c.prandtl, &c.viscous_cfl};
+                if (!parse_positive(optarg, dst[optc - 1031])) {
+                    std::fprintf(stderr, "ERROR: --%s=%s: expected a finite number above zero\n", names[optc - 1031], optarg);
+                    return false;
+                }
+                if (optc == 1031) c.viscosity_given = true; else if (optc == 1032) c.reynolds_given = true; else c.viscous_extras_given = true;
+                break;
+            }
+            case 1036: c.no_slip = true; c.viscous_extras_given = true; break;
+            case 1037:
+                if (!parse_whole(optarg, 0, kMaxJstLevels, &c.viscous_levels)) {
+                    std::fprintf(stderr, "ERROR: --viscous-levels=%s: expected a whole number 0 ... %d\n", optarg, kMaxJstLevels);
+                    return false;
+                }
+                c.viscous_extras_given = true;
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
     if (c.smoothing_iterations_given && !c.smoothing_given && c.smoothing_iterations > 0) {
         std::fprintf(stderr, "ERROR: --smoothing-iterations needs --residual-smoothing EPS (the residual smoothing's coefficient)\n");
+        return false;
+    }
+    if (c.viscosity_given && c.reynolds_given) {
+        std::fprintf(stderr, "ERROR: --viscosity and --reynolds both set the viscosity: give one of them\n");
+        return false;
+    }
+    if (c.viscous_extras_given && !c.viscous()) {
+        std::fprintf(stderr, "ERROR: --ref-length, --prandtl, --no-slip, --viscous-cfl and --viscous-levels need --viscosity MU or --reynolds RE (the viscous terms)\n");
         return false;
     }
     if (c.dual_extras_given && !c.dual_given) {
@@ -755,6 +822,16 @@ int run_all_cycles(const Config &conf, std::vector<double> &rms, std::vector<dou
     return MGCFD_OK;
 }
 
+// The viscosity of the run: --viscosity as given, or --reynolds against the free stream in use (the Mach number sets |V_inf|; the
+// angle of attack does not change it, so a polar has one viscosity).
+int viscosity_of(const Config &conf, double *mu)
+{
+    if (conf.viscosity_given) { *mu = conf.viscosity; return MGCFD_OK; }
+    double ff17[17];
+    const int rc = mgcfd_free_stream_constants(conf.ff_mach, conf.angle(0), ff17);
+    return rc != MGCFD_OK ? rc : mgcfd_viscosity_from_reynolds(ff17, conf.reynolds, conf.ref_length, mu);
+}
+
 // --gpus N (multi_gpu.cpp): the same outputs as the one-GPU run from N ranks of this process
 int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int mesh_variant, int problem_size)
 {
@@ -775,6 +852,11 @@ int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int me
         if (conf.time_step_given && run.set_time_step(conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
         if (conf.smoothing_given && run.set_residual_smoothing(conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
         if (conf.jst_given && run.set_jst(conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
+        if (conf.viscous()) {
+            double mu = 0.0;
+            if (viscosity_of(conf, &mu) != MGCFD_OK || run.set_viscous(mu, conf.prandtl, conf.no_slip ? 1 : 0, conf.viscous_cfl, conf.viscous_levels) != MGCFD_OK)
+                return fail("setting the viscous terms");
+        }
         const int rc = run_all_cycles(conf, rms, loads, polar_rows,
             [&](double mach, double alpha, int reinitialise) { return run.set_free_stream(mach, alpha, reinitialise); },
             [&](double *rms_out, double *loads_out) {
@@ -853,6 +935,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "ERROR: the JST dissipation (--jst) does not run with --gpus-partition: a level split over GPUs would need its sensor and Laplacian exchanged per stage\n");
         return 1;
     }
+    if (conf.viscous() && conf.viscous_levels > 0 && conf.gpus > 1 && conf.gpus_partition) {
+        std::fprintf(stderr, "ERROR: the viscous terms (--viscosity, --reynolds) do not run with --gpus-partition: a level split over GPUs would need its node stresses exchanged per stage\n");
+        return 1;
+    }
     if (conf.dual_given && conf.gpus > 1 && conf.gpus_partition) {
         std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --gpus-partition: levels split over GPUs are out of scope\n");
         return 1;
@@ -926,6 +1012,11 @@ int main(int argc, char **argv)
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
     if (conf.smoothing_given && mgcfd_set_residual_smoothing(solver, conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
     if (conf.jst_given && mgcfd_set_jst(solver, conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
+    if (conf.viscous()) {
+        double mu = 0.0;
+        if (viscosity_of(conf, &mu) != MGCFD_OK || mgcfd_set_viscous(solver, mu, conf.prandtl, conf.no_slip ? 1 : 0, conf.viscous_cfl, conf.viscous_levels) != MGCFD_OK)
+            return fail("setting the viscous terms");
+    }
     if (conf.fas && mgcfd_set_fas(solver, 1) != MGCFD_OK) return fail("switching FAS multigrid on");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },

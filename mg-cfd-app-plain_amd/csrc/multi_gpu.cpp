@@ -471,6 +471,16 @@ int Run::set_jst(double kappa2, double kappa4, int levels)
     return MGCFD_OK;
 }
 
+int Run::set_viscous(double mu, double prandtl, int wall, double cfl_v, int levels)
+{
+    // (as set_jst: every rank holds the whole hierarchy; the library refuses a rank that holds part of a level)
+    for (mgcfd_solver *s : p->solvers) {
+        const int rc = mgcfd_set_viscous(s, mu, prandtl, wall, cfl_v, levels);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
+
 int Run::set_dual_time(double dt, double clamp, int order)
 {
     // (every rank holds the whole hierarchy and sweeps its own levels: each keeps the time levels of all, and those of the

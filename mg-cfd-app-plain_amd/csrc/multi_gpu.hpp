@@ -36,6 +36,8 @@ public:
     int set_residual_smoothing(double eps, int iterations);
     // mgcfd_set_jst on every rank, likewise
     int set_jst(double kappa2, double kappa4, int levels);
+    // mgcfd_set_viscous on every rank, likewise
+    int set_viscous(double mu, double prandtl, int wall, double cfl_v, int levels);
     // mgcfd_set_dual_time (+ the BDF order) on every rank, likewise; advance: steps x (mgcfd_dual_time_begin_step on every rank +
     // cycles_per_step cycles), rms_out [steps * cycles_per_step]
     int set_dual_time(double dt, double clamp, int order);

@@ -177,6 +177,11 @@ struct DeviceLevel {
     double *jst_buf = nullptr;           // [7][stride]: the JST dissipation's L [5], nu and r (allocated when it is first switched on for this level)
     double *time_n = nullptr, *time_n1 = nullptr;   // [5][stride] each: dual time stepping's time levels Wn and Wn1 (held while it is on)
     const double *flux_in = nullptr;     // the state the last flux launch read: W of the dual-time source
+    // the viscous terms (mgcfd_set_viscous), held while they are on for this level: the node stresses S [12][stride], the step
+    // limit's g = cbrt(vol)^2 / vol [stride] and the no-slip wall's nodes (the distinct b ends of the solid-wall edges, renumbered)
+    double *visc_s = nullptr, *visc_g = nullptr;
+    int32_t *visc_wall = nullptr;
+    int64_t n_visc_wall = 0;
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while dual time is on: its RMS is summed in original numbering
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
@@ -333,13 +338,41 @@ struct mgcfd_solver {
     double jst_kappa2 = 0.0, jst_kappa4 = 0.0;
     int jst_levels = 0;
     bool jst_on(int l) const { return l < jst_levels; }
+    // Laminar viscous terms (mgcfd_set_viscous): on levels 0 .. visc_levels-1 every flux launch (behind the JST pair, where on)
+    // is followed by the stress and the viscous-flux launch, which add V into fluxes[], the final step factors take the
+    // viscous limit, and with visc_wall every launch that writes such a level's variables is followed by the no-slip launch.
+    // Such a level runs unfused stages outside graphs, as a JST level does.
+    double visc_mu = 0.0, visc_prandtl = 0.0, visc_cfl = 0.0;
+    int visc_wall = 0, visc_levels = 0;
+    bool viscous_on(int l) const { return l < visc_levels; }
+    ViscousStep viscous_step(DeviceLevel &lv) const
+    {
+        ViscousStep a;
+        a.w = lv.q; a.s = lv.visc_s; a.volumes = lv.volumes; a.fluxes = lv.fluxes;
+        a.mu = visc_mu; a.kappa = (visc_mu * 1.4) / ((1.4 - 1.0) * visc_prandtl);
+        return a;
+    }
+    // sf = min(sf, (k0 * rho) * g) on final step factors, before dual time stepping's clamp
+    void viscous_clamp(int l)
+    {
+        DeviceLevel &lv = level(l);
+        const double kv = std::max(4.0 / 3.0, 1.4 / visc_prandtl);
+        exact::launch_viscous_clamp(stream, lv.info.nel, visc_cfl / (kv * visc_mu), lv.q, lv.visc_g, lv.step_factors);
+    }
+    // the no-slip wall behind a launch that wrote q (and q2: FAS's copy of it); residuals where that launch wrote them
+    void viscous_wall(int l, double *q, double *q2 = nullptr, const double *old = nullptr, double *residuals = nullptr)
+    {
+        if (!viscous_on(l) || !visc_wall) return;
+        DeviceLevel &lv = level(l);
+        exact::launch_viscous_wall(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, q, q2, old, residuals);
+    }
     // FAS multigrid (mgcfd_set_fas): the V-cycle's transfers become the FAS legs (op_fas_restrict, op_fas_prolong) and every stage
     // of a level >= 1 takes R + P for its total residual R.  Such a level runs unfused stages (standalone flux launch + the
     // forced update): no fused stage, no look-ahead; no graph on any level.  Level 0 sweeps as ever.
     bool fas = false;
     bool fas_forced(int l) const { return fas && l >= 1; }
     // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while any of them is on
-    bool ordered_rms() const { return dual_time() || jst_on(0) || fas; }
+    bool ordered_rms() const { return dual_time() || jst_on(0) || fas || viscous_on(0); }
     JstStep jst_step(DeviceLevel &lv) const
     {
         JstStep a;
@@ -383,7 +416,7 @@ struct mgcfd_solver {
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
                                 NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_dual, NS::launch_dual_source, \
                                 NS::launch_jst_sensor, NS::launch_jst_dissipation, NS::launch_restrict_fas, NS::launch_prolong_fas, \
-                                NS::launch_time_step_fas}
+                                NS::launch_time_step_fas, NS::launch_viscous_stress, NS::launch_viscous_flux}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -495,11 +528,13 @@ struct mgcfd_solver {
         } else {
             // (dual time stepping clamps final step factors: nothing is left to the first time_step then)
             // (... nor on a FAS-forced level, whose time_step takes final factors)
-            const bool finish = !fused || dual_time() || fas_forced(l);
+            // (... nor on a viscous level, whose limit works on final factors)
+            const bool finish = !fused || dual_time() || fas_forced(l) || viscous_on(l);
             op_step_factor_local(l, fused && copy_old, finish);
             if (finish) op_step_factor_apply(l);
             else apply_pending = true;
         }
+        if (viscous_on(l)) viscous_clamp(l);
         if (dual_time()) clamp_step_factors(l);
         lv.iters[MGCFD_LOOP_COMPUTE_STEP] += lv.info.nel;
         return apply_pending;
@@ -605,6 +640,12 @@ struct mgcfd_solver {
             k().jst_sensor(stream, lv.dp, a);
             k().jst_dissipation(stream, lv.dp, a);
         }
+        if ((classes & 1) && viscous_on(l)) {
+            // viscous terms: S of the same state, then fluxes[1..4] += V, behind C (both passes keep row order in either flavour)
+            const ViscousStep a = viscous_step(lv);
+            k().viscous_stress(stream, lv.dp, a);
+            k().viscous_flux(stream, lv.dp, a);
+        }
         if (dual_time()) lv.flux_in = lv.q;
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
@@ -708,6 +749,7 @@ struct mgcfd_solver {
                 }
                 k().smooth(stream, lv.dp, a);
             }
+            viscous_wall(l, out, nullptr, old, with_residual ? lv.residuals : nullptr);
             lv.fluxes_stale = true;                 // (never zeroed by these launches: with one iteration other tiles still read them)
             lv.fluxes_zero = true;
             lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
@@ -721,6 +763,7 @@ struct mgcfd_solver {
             if (dual_time()) d = dual_source(lv); else d.order = 0;
             k().time_step_fas(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, lv.fas_p, old, out, lv.dp.old_of_new, err, next_check(),
                               with_residual ? lv.residuals : nullptr, d);
+            viscous_wall(l, out, nullptr, old, with_residual ? lv.residuals : nullptr);
             lv.fluxes_stale = true;                 // (never written: logically zero, as after a lazy time_step)
             lv.fluxes_zero = true;
             lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
@@ -731,6 +774,7 @@ struct mgcfd_solver {
             if (apply_min != ApplyMin::None) throw std::invalid_argument("dual time: the step factors must be final before time_step");
             k().time_step_dual(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, next_check(),
                                with_residual ? lv.residuals : nullptr, dual_source(lv));
+            viscous_wall(l, out, nullptr, old, with_residual ? lv.residuals : nullptr);
             lv.fluxes_stale = true;                 // (never written: logically zero, as after a lazy time_step)
             lv.fluxes_zero = true;
             lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
@@ -741,6 +785,7 @@ struct mgcfd_solver {
         double *res = with_residual ? lv.residuals : nullptr;
         const int check = next_check();
         k().time_step(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, check, pm, n_pm, lv.volumes, res, lazy_zero ? 0 : 1);
+        viscous_wall(l, out, nullptr, old, res);
         lv.fluxes_stale = lazy_zero;
         lv.fluxes_zero = true;
         lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
@@ -769,11 +814,13 @@ struct mgcfd_solver {
         // the coarse sweep that follows starts with compute_step_factor on the restricted state: the
         // kernel leaves its first half (per-workgroup minima) in partial_min (global time step only)
         // (not on a partitioned level: its ghosts are stale until the halo exchange that follows)
-        const bool ahead = global_dt() && C.n_owned == C.info.nel;
+        // (nor onto a viscous level: its sweeps are unfused and the no-slip launch below changes the state)
+        const bool ahead = global_dt() && C.n_owned == C.info.nel && !viscous_on(fine + 1);
         double *pm = ahead ? C.partial_min : nullptr;
         Timed t(this, fine + 1, MGCFD_LOOP_RESTRICT);
         const SumTask task = rms ? *rms : SumTask{};
         k().restrict_(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, cfl, pm, task);
+        viscous_wall(fine + 1, C.q);
         C.min_ahead = ahead;
         C.iters[MGCFD_LOOP_RESTRICT] += 2 * F.info.mgc + C.info.nel;   // mg_loops.cpp:61,117,172
     }
@@ -784,10 +831,11 @@ struct mgcfd_solver {
         if (!F.has_transfer) throw std::invalid_argument("level has no multigrid map");
         settle_residuals(C);
         settle_residuals(F);
-        const bool ahead = global_dt() && F.n_owned == F.info.nel;   // as in op_restrict
+        const bool ahead = global_dt() && F.n_owned == F.info.nel && !viscous_on(fine);   // as in op_restrict
         double *pm = ahead ? F.partial_min : nullptr;
         Timed t(this, fine, MGCFD_LOOP_PROLONG);
         k().prolong(stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, cfl, pm);
+        viscous_wall(fine, F.q);
         F.min_ahead = ahead;
         F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;  // mg_loops.cpp:728,842
     }
@@ -819,6 +867,7 @@ struct mgcfd_solver {
             Timed t(this, fine + 1, MGCFD_LOOP_RESTRICT);       // (booked on the coarse level, as op_restrict)
             k().restrict_fas(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
                              fine >= 1 ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p);
+            viscous_wall(fine + 1, C.q, C.fas_w0);
         }
         F.fluxes_zero = true; F.fluxes_stale = true;            // (T is used up)
         C.min_ahead = false;
@@ -839,10 +888,11 @@ struct mgcfd_solver {
         if (!F.has_transfer) throw std::invalid_argument("level has no multigrid map");
         settle_residuals(F);                                    // (an unwritten residual's operand is about to change)
         // (the look-ahead only where the sweep that follows takes it: level 0's fused stages under a global time step)
-        const bool ahead = global_dt() && !fas_forced(fine) && F.n_owned == F.info.nel;
+        const bool ahead = global_dt() && !fas_forced(fine) && !viscous_on(fine) && F.n_owned == F.info.nel;
         double *pm = ahead ? F.partial_min : nullptr;
         Timed t(this, fine, MGCFD_LOOP_PROLONG);
         k().prolong_fas(stream, F.dp, C.dp.stride, C.fas_w0, C.q, F.q, F.cbrt_vol, cfl, pm);
+        viscous_wall(fine, F.q);
         F.min_ahead = ahead;
         F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;
     }
@@ -1557,6 +1607,7 @@ static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mac
         lv.have_sumsq = false;
         lv.stage_out = nullptr;                 // (MGCFD_ARR_STAGE named a stage of the state that has just gone)
         if (lv.fas_p) HIP_CHECK(hipMemsetAsync(lv.fas_p, 0, sizeof(double) * 5 * lv.dp.stride, s->stream));   // (the forcing belonged to the old state)
+        s->viscous_wall(static_cast<int>(&lv - s->L.data()), lv.q);
     }
     HIP_CHECK(hipMemsetAsync(s->err, 0xFF, sizeof(unsigned long long), s->stream));
     s->check_seq = 0;
@@ -1673,7 +1724,7 @@ int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels)
             if (!lv.jst_buf) lv.jst_buf = lv.mem.alloc<double>(static_cast<size_t>(7 * lv.dp.stride));
         }
         if (n > 0 && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
-        if (n == 0 && !s->dual_time() && !s->fas) s->L[0].mem.release(s->L[0].new_of_old_dev);
+        if (n == 0 && !s->dual_time() && !s->fas && !s->viscous_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);
         for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->jst_levels = n;
         s->jst_kappa2 = n > 0 ? kappa2 : 0.0;
@@ -1687,6 +1738,97 @@ int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *le
     if (kappa4) *kappa4 = s->jst_kappa4;
     if (levels) *levels = s->jst_levels;
     return MGCFD_OK;
+}
+
+// ---- laminar viscous terms: viscosity, Prandtl number, wall condition, step limit and the levels they run on ----
+int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, double cfl_v, int levels)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (levels < 0) throw std::invalid_argument("viscous terms: levels must be 0 (off) or more");
+        if (levels > 0) {
+            if (!std::isfinite(mu) || !(mu > 0.0) || !std::isfinite(prandtl) || !(prandtl > 0.0) || !std::isfinite(cfl_v) || !(cfl_v > 0.0))
+                throw std::invalid_argument("viscous terms: mu, prandtl and cfl_v must be finite and positive");
+            if (wall != 0 && wall != 1) throw std::invalid_argument("viscous terms: wall must be 0 (slip) or 1 (no-slip, adiabatic)");
+            if (s->partitioned || s->comm)
+                throw std::invalid_argument("viscous terms: not on a partitioned solver or a rank (a level split over ranks would need the node stresses exchanged per stage)");
+        }
+        require_no_sweep_under_way(s, "viscous terms");
+        s->use_device();
+        s->fold_events();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        synchronize_with_group(s);
+        s->drop_graphs();
+        const int n = std::min(levels, static_cast<int>(s->L.size()));
+        for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
+            DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+            if (l >= n) {
+                lv.mem.release(lv.visc_s); lv.mem.release(lv.visc_g); lv.mem.release(lv.visc_wall);
+                lv.n_visc_wall = 0;
+                continue;
+            }
+            if (lv.visc_s) continue;
+            const size_t stride = static_cast<size_t>(lv.dp.stride);
+            lv.visc_s = lv.mem.alloc<double>(12 * stride);
+            HIP_CHECK(hipMemsetAsync(lv.visc_s, 0, sizeof(double) * 12 * stride, s->stream));
+            // g = (cbrt(vol) * cbrt(vol)) / vol from the volumes and the host libm's cube roots the step factor uses
+            std::vector<double> vol(stride), cb(stride), g(stride, 1.0);
+            HIP_CHECK(hipMemcpyAsync(vol.data(), lv.volumes, sizeof(double) * stride, hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipMemcpyAsync(cb.data(), lv.cbrt_vol, sizeof(double) * stride, hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            for (int64_t k = 0; k < lv.info.nel; k++) g[static_cast<size_t>(k)] = (cb[static_cast<size_t>(k)] * cb[static_cast<size_t>(k)]) / vol[static_cast<size_t>(k)];
+            lv.visc_g = lv.mem.upload(g);
+            // the wall nodes: the distinct b ends of the solid-wall edges, in the library's numbering, ascending
+            std::vector<int32_t> nodes;
+            nodes.reserve(static_cast<size_t>(lv.info.n_boundary));
+            for (int64_t k = 0; k < lv.info.n_boundary; k++)
+                nodes.push_back(lv.plan.new_of_old[static_cast<size_t>(lv.edges[static_cast<size_t>(lv.info.boundary_start + k)].b)]);
+            std::sort(nodes.begin(), nodes.end());
+            nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
+            lv.n_visc_wall = static_cast<int64_t>(nodes.size());
+            lv.visc_wall = lv.mem.upload(nodes);
+        }
+        if (n > 0 && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
+        if (n == 0 && !s->dual_time() && !s->jst_on(0) && !s->fas) s->L[0].mem.release(s->L[0].new_of_old_dev);
+        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
+        s->visc_levels = n;
+        s->visc_mu = n > 0 ? mu : 0.0;
+        s->visc_prandtl = n > 0 ? prandtl : 0.0;
+        s->visc_cfl = n > 0 ? cfl_v : 0.0;
+        s->visc_wall = n > 0 ? wall : 0;
+        // the no-slip condition holds from the start
+        for (int l = 0; l < n; l++) {
+            DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+            if (s->visc_wall) s->settle_residuals(lv);          // (an unwritten residual's operand is about to change)
+            s->viscous_wall(l, lv.q);
+        }
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_viscous(const mgcfd_solver *s, double *mu, double *prandtl, int *wall, double *cfl_v, int *levels)
+{
+    REQUIRE(s);
+    if (mu) *mu = s->visc_mu;
+    if (prandtl) *prandtl = s->visc_prandtl;
+    if (wall) *wall = s->visc_wall;
+    if (cfl_v) *cfl_v = s->visc_cfl;
+    if (levels) *levels = s->visc_levels;
+    return MGCFD_OK;
+}
+int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double ref_length, double *mu)
+{
+    REQUIRE(ff17); REQUIRE(mu);
+    return guarded([&] {
+        if (!std::isfinite(reynolds) || !(reynolds > 0.0) || !std::isfinite(ref_length) || !(ref_length > 0.0))
+            throw std::invalid_argument("viscosity from Reynolds number: reynolds and ref_length must be finite and positive");
+        const double rho = ff17[0];
+        const double vx = ff17[1] / rho, vy = ff17[2] / rho, vz = ff17[3] / rho;
+        const double speed = std::sqrt(vx * vx + vy * vy + vz * vz);
+        const double m = rho * speed * ref_length / reynolds;
+        if (!std::isfinite(m) || !(m > 0.0)) throw std::invalid_argument("viscosity from Reynolds number: the far field is at rest or not finite");
+        *mu = m;
+    });
 }
 
 // ---- FAS multigrid: the switch ----
@@ -1716,7 +1858,7 @@ int mgcfd_set_fas(mgcfd_solver *s, int on)
             }
         }
         if (on && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
-        if (!on && !s->dual_time() && !s->jst_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);
+        if (!on && !s->dual_time() && !s->jst_on(0) && !s->viscous_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);
         HIP_CHECK(hipStreamSynchronize(s->stream));
         for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->fas = on != 0;
@@ -1755,7 +1897,7 @@ int mgcfd_step_factor_local(mgcfd_solver *s, int level)
 }
 int mgcfd_step_factor_min_devptr(mgcfd_solver *s, int level, void **devptr)
 { REQUIRE(devptr); OP(*devptr = s->level(level).min_dt); }
-int mgcfd_step_factor_apply(mgcfd_solver *s, int level) { OP({ s->op_step_factor_apply(level); if (s->dual_time()) s->clamp_step_factors(level); }); }
+int mgcfd_step_factor_apply(mgcfd_solver *s, int level) { OP({ s->op_step_factor_apply(level); if (s->viscous_on(level)) s->viscous_clamp(level); if (s->dual_time()) s->clamp_step_factors(level); }); }
 int mgcfd_residual_sumsq(mgcfd_solver *s, int level, void **devptr)
 { REQUIRE(devptr); OP({ s->op_sumsq(level); *devptr = s->level(level).sumsq; }); }
 
@@ -1828,7 +1970,7 @@ static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 static void smooth_once(mgcfd_solver *s, int level)
 {
     DeviceLevel &lv = s->level(level);
-    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->fas_forced(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
+    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->viscous_on(level) && !s->fas_forced(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
         // Fused stages: flux + time_step in one launch each.  No copy<double>(old_variables, variables)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
@@ -1909,7 +2051,7 @@ static void run_sweep(mgcfd_solver *s, int level)
     }
     // (only the fused launches are replayed: the unfused ones — the two-phase flux variant — leave host-side flags
     //  behind, fluxes_stale, that a replay would not set)
-    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->fas && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
+    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->viscous_on(level) && !s->fas && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
     if (!graphable) {
         const int keep = s->opt_timing;
         if (!timed) s->opt_timing = 0;
@@ -1963,6 +2105,7 @@ static void require_no_smoothing(const mgcfd_solver *s, const char *who)
     if (s->smoothing()) throw std::invalid_argument(std::string(who) + ": not while residual smoothing is on (mgcfd_set_residual_smoothing; use mgcfd_smooth or the kernel-granular calls)");
     if (s->dual_time()) throw std::invalid_argument(std::string(who) + ": not while dual time stepping is on (mgcfd_set_dual_time; use mgcfd_smooth or the kernel-granular calls)");
     if (s->jst_on(0)) throw std::invalid_argument(std::string(who) + ": not while the JST dissipation is on (mgcfd_set_jst; use mgcfd_smooth or the kernel-granular calls)");
+    if (s->viscous_on(0)) throw std::invalid_argument(std::string(who) + ": not while the viscous terms are on (mgcfd_set_viscous; use mgcfd_smooth or the kernel-granular calls)");
     if (s->fas) throw std::invalid_argument(std::string(who) + ": not while FAS multigrid is on (mgcfd_set_fas; use mgcfd_smooth or the kernel-granular calls)");
 }
 // The same sweep split around the one collective a multi-GPU run needs (see mgcfd.h).
@@ -2213,7 +2356,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->fas && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->viscous_on(0) && !s->fas && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2362,6 +2505,10 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
         case MGCFD_ARR_FAS_FORCING: case MGCFD_ARR_FAS_START:
             if (!lv.fas_p) throw std::invalid_argument("MGCFD_ARR_FAS_*: levels >= 1 while FAS multigrid is on (mgcfd_set_fas)");
             return which == MGCFD_ARR_FAS_FORCING ? lv.fas_p : lv.fas_w0;
+        case MGCFD_ARR_VISCOUS_STRESS:
+            if (!lv.visc_s) throw std::invalid_argument("MGCFD_ARR_VISCOUS_STRESS: the viscous terms are off on this level (mgcfd_set_viscous)");
+            *ncols = 12;
+            return lv.visc_s;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2401,6 +2548,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
             throw std::invalid_argument("MGCFD_ARR_JST_*: read-only (every flux launch of a JST level overwrites them)");
         if (which == MGCFD_ARR_FAS_FORCING || which == MGCFD_ARR_FAS_START)
             throw std::invalid_argument("MGCFD_ARR_FAS_*: read-only (every FAS restriction overwrites them)");
+        if (which == MGCFD_ARR_VISCOUS_STRESS)
+            throw std::invalid_argument("MGCFD_ARR_VISCOUS_STRESS: read-only (every flux launch of a viscous level overwrites it)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -2455,6 +2604,7 @@ int mgcfd_accept_restricted(mgcfd_solver *s, int fine_level, const void *dev_src
         if (!fine.dp.child_ptr) throw std::invalid_argument("level has no coarser level");
         exact::launch_accept_restricted(s->stream, coarse.info.nel, coarse.dp.stride, fine.dp.child_ptr,
                                         static_cast<const double *>(dev_src), coarse.q);
+        s->viscous_wall(fine_level + 1, coarse.q);
         coarse.min_ahead = false;
     });
 }
@@ -2653,6 +2803,38 @@ int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *
         for (int k = 0; k < launches; k++) {
             if (kind == 0) s->k().jst_sensor(s->stream, lv.dp, st);
             else s->k().jst_dissipation(s->stream, lv.dp, st);
+        }
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
+        lv.fluxes_zero = false;
+        lv.fluxes_stale = false;
+        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+    });
+}
+
+// ... and for one of the viscous terms' launches: 0 the stress launch, 1 the viscous-flux launch (which adds into fluxes[], accumulating
+// over the launches: the state stays).  After one flux launch with both passes, so that every array holds a stage's numbers.
+int mgcfd_bench_viscous(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->viscous_on(level)) throw std::invalid_argument("the viscous terms are off on this level: switch them on first (mgcfd_set_viscous)");
+        if (kind < 0 || kind > 1) throw std::invalid_argument("viscous launch kind: 0 stress, 1 viscous flux");
+        Event a = s->get_event(), b = s->get_event();
+        s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
+        const ViscousStep st = s->viscous_step(lv);
+        s->k().viscous_stress(s->stream, lv.dp, st);
+        s->k().viscous_flux(s->stream, lv.dp, st);
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
+        for (int k = 0; k < launches; k++) {
+            if (kind == 0) s->k().viscous_stress(s->stream, lv.dp, st);
+            else s->k().viscous_flux(s->stream, lv.dp, st);
         }
         HIP_CHECK(hipEventRecord(b.get(), s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -4949,7 +5131,7 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         }
         if (!on) {
             for (DeviceLevel &lv : s->L) { lv.mem.release(lv.time_n); lv.mem.release(lv.time_n1); lv.flux_in = nullptr; }
-            if (!s->jst_on(0) && !s->fas) s->L[0].mem.release(s->L[0].new_of_old_dev);        // (the JST dissipation and FAS order the RMS the same way)
+            if (!s->jst_on(0) && !s->fas && !s->viscous_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);        // (the JST dissipation and FAS order the RMS the same way)
             s->dual_levels = 0;
         }
         for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)

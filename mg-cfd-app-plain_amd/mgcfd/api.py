@@ -25,7 +25,8 @@ RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
-       "fas_forcing": 12, "fas_start": 13}
+       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14}
+NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12}      # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -198,6 +199,11 @@ _SIGNATURES = [
     ("mgcfd_fas_restrict", C.c_int, [_vp, C.c_int]),
     ("mgcfd_fas_prolong", C.c_int, [_vp, C.c_int]),
     ("mgcfd_bench_fas", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_viscous", C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]),
+    ("mgcfd_get_viscous", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_int)]),
+    ("mgcfd_viscosity_from_reynolds", C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    ("mgcfd_bench_viscous", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -358,6 +364,19 @@ def free_stream_constants(mach: float, alpha_deg: float) -> np.ndarray:
     out = np.zeros(17)
     _check(lib, lib.mgcfd_free_stream_constants(float(mach), float(alpha_deg), _ptr(out)))
     return out
+
+
+VISCOUS_PRANDTL, VISCOUS_CFL = 0.72, 0.25         # MGCFD_VISCOUS_PRANDTL, MGCFD_VISCOUS_CFL
+
+
+def viscosity_from_reynolds(ff17, reynolds: float, ref_length: float = 1.0) -> float:
+    """Host only (mgcfd_viscosity_from_reynolds): ``mu = rho_inf * |V_inf| * ref_length / reynolds`` for the far field ``ff17``
+    (Solver.far_field(), free_stream_constants)."""
+    lib = load_library()
+    ff = np.ascontiguousarray(ff17, dtype=np.float64).reshape(17)
+    mu = C.c_double()
+    _check(lib, lib.mgcfd_viscosity_from_reynolds(_ptr(ff), float(reynolds), float(ref_length), C.byref(mu)))
+    return mu.value
 
 
 class Solver:
@@ -633,6 +652,20 @@ class Solver:
         """The up leg onto level ``fine``: the coarse level's correction, interpolated as ``prolong`` does (mgcfd_fas_prolong)."""
         self._c(self.lib.mgcfd_fas_prolong(self.handle, fine))
 
+    # ---- laminar viscous terms ----
+    def set_viscous(self, mu: float, prandtl: float = VISCOUS_PRANDTL, wall: bool = False, cfl_v: float = VISCOUS_CFL, levels: int = 1):
+        """Laminar viscous terms on levels ``0 .. levels-1`` (mgcfd_set_viscous): the Navier-Stokes stresses and the heat flux at
+        constant dynamic viscosity ``mu`` and Prandtl number ``prandtl`` added to every stage's fluxes, the step factors limited
+        by ``cfl_v`` times the viscous step, and with ``wall=True`` a no-slip adiabatic condition on the solid walls (momentum
+        zero at their nodes).  ``levels=0`` switches them off.  Captured graphs are dropped.  Not on partitioned solvers or ranks."""
+        self._c(self.lib.mgcfd_set_viscous(self.handle, float(mu), float(prandtl), 1 if wall else 0, float(cfl_v), int(levels)))
+
+    def viscous(self):
+        """``(mu, prandtl, wall, cfl_v, levels)`` in use, ``levels`` capped at the solver's; ``(0.0, 0.0, False, 0.0, 0)`` when off."""
+        mu, pr, cv, w, n = C.c_double(), C.c_double(), C.c_double(), C.c_int(), C.c_int()
+        self._c(self.lib.mgcfd_get_viscous(self.handle, C.byref(mu), C.byref(pr), C.byref(w), C.byref(cv), C.byref(n)))
+        return mu.value, pr.value, bool(w.value), cv.value, n.value
+
     def set_dual_time(self, dt: float, clamp: float = 2.0 / 3.0):
         """Time-accurate runs (mgcfd_set_dual_time): every stage's update carries the BDF source of the physical step ``dt`` and
         the pseudo step is clamped to ``clamp * dt / vol``; ``dt=0`` switches it off and releases the time levels.  The state
@@ -682,14 +715,17 @@ class Solver:
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
-              residual_smoothing=None, jst=None, fas: Optional[bool] = None) -> List[dict]:
+              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
         dict: ``alpha``, ``mach``, ``rms`` [cycles], ``loads`` [cycles, 6] and ``coefficients`` (CD CL CS CMx CMy CMz of the
         last cycle against that angle's far field).  ``time_step`` / ``cfl`` (None: as the solver has them) are set once,
         before the first angle, and stay (``set_time_step``); likewise ``residual_smoothing=(eps, iterations)``
-        (``set_residual_smoothing``), ``jst=(kappa2, kappa4, levels)`` (``set_jst``) and ``fas=True / False`` (``set_fas``)."""
+        (``set_residual_smoothing``), ``jst=(kappa2, kappa4, levels)`` (``set_jst``), ``fas=True / False`` (``set_fas``) and
+        ``viscous=(mu, prandtl, wall, cfl_v, levels)`` or a dict of ``set_viscous``'s keywords (``set_viscous``)."""
+        if viscous is not None:
+            self.set_viscous(**viscous) if isinstance(viscous, dict) else self.set_viscous(*viscous)
         if fas is not None:
             self.set_fas(fas)
         if jst is not None:
@@ -710,14 +746,14 @@ class Solver:
 
     # ---- state ----
     def get(self, l: int, name: str) -> np.ndarray:
-        ncols = 1 if name in ("step_factors", "volumes", "jst_sensor", "jst_radius") else NVAR
+        ncols = NCOLS.get(name, NVAR)
         out = np.zeros(self.nel(l) * ncols)
         self._c(self.lib.mgcfd_get_array(self.handle, l, ARR[name], _ptr(out)))
         return out.reshape(-1, ncols) if ncols > 1 else out
 
     def set(self, l: int, name: str, values: np.ndarray):
         a = np.ascontiguousarray(values, dtype=np.float64).ravel()
-        ncols = 1 if name in ("step_factors", "volumes", "jst_sensor", "jst_radius") else NVAR
+        ncols = NCOLS.get(name, NVAR)
         assert a.size == self.nel(l) * ncols
         self._c(self.lib.mgcfd_set_array(self.handle, l, ARR[name], _ptr(a)))
 
@@ -766,6 +802,13 @@ class Solver:
         return t.value
 
     FAS_LAUNCHES = {"restrict_fas": 0, "forcing": 1, "time_step_fas": 2, "prolong_fas": 3, "restrict": 4, "time_step": 5, "prolong": 6}
+
+    def bench_viscous(self, l: int, kind: int, launches: int) -> float:
+        """Mean GPU seconds of one viscous launch of ``kind`` (0 stress, 1 viscous flux) over ``launches`` back-to-back launches
+        under one event pair (mgcfd_bench_viscous); the viscous terms must be on for level ``l``."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_viscous(self.handle, l, kind, launches, C.byref(t)))
+        return t.value
 
     def bench_fas(self, fine: int, kind: str, launches: int) -> float:
         """Mean GPU seconds of one launch of ``kind`` (a key of ``FAS_LAUNCHES``) between levels ``fine`` and ``fine + 1`` over
