@@ -529,7 +529,8 @@ int mgcfd_get_fas(const mgcfd_solver *s, int *on);
  * wall other than 0 and 1; while a kernel-granular sweep is under way; levels > 0 on a solver made by mgcfd_create_partitioned*
  * or attached to a group or as a rank.  While it is on, mgcfd_sweep_begin*, mgcfd_sweep_flux0, mgcfd_sweep_stage and
  * mgcfd_sweep_end* return MGCFD_ERR_ARG, and mgcfd_group_create and mgcfd_rank_attach_* refuse the solver.
- * Out of scope: friction in the surface loads (mgcfd_surface_loads stays the pressure loads); an edge-direction correction of
+ * Friction in the surface loads: mgcfd_surface_loads_viscous and its neighbours (mgcfd_surface_loads stays the pressure loads).
+ * Out of scope: an edge-direction correction of
  * the face gradient (it needs node coordinates on the device); variable viscosity and turbulence models; viscous flux through
  * far-field faces; levels split over ranks; graphs and fused stages with viscosity on.
  * The weights are used as the solver holds them: on meshes whose variant makes the reference rescale them at load (every
@@ -621,6 +622,51 @@ int mgcfd_run_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3
  * CMx CMy CMz = M/(q S c).  ref_area S and ref_length c must be positive. */
 int mgcfd_load_coefficients(const double ff17[17], const double loads6[6], double ref_area, double ref_length,
                             double out6[6]);
+/* ---------------------------------------------------------------------------------
+ * Viscous surface loads — the friction half of the loads beside the pressure half, and the distribution along the wall.
+ * The wall nodes of a level are the distinct b ends of its solid-wall edges in ascending original id.  On a level the viscous
+ * terms are on for (mgcfd_set_viscous), every wall node i gets Sw_i: the twelve node stresses of pass 1 of the viscous terms
+ * (u v w | txx tyy tzz txy txz tyz | qx qy qz) evaluated on the level's CURRENT variables, with the expressions, associations and
+ * +0.0 starts of that pass, over the internal edges at i in the level's original edge order; MGCFD_ARR_VISCOUS_STRESS is not
+ * touched.  For a solid-wall edge (node b, weights (x, y, z)), r = coords[b] - ref_point and tau from Sw_b:
+ *   pressure six   exactly mgcfd_surface_loads' terms
+ *   friction six   gx = -((txx*x + txy*y) + txz*z),  gy = -((txy*x + tyy*y) + tyz*z),  gz = -((txz*x + tyz*y) + tzz*z),
+ *                  moment (ry*gz - rz*gy, rz*gx - rx*gz, rx*gy - ry*gx)
+ * and each of the twelve columns goes through mgcfd_surface_loads' summation tree.  Every operation is one IEEE-754 double
+ * operation, never contracted to FMA whatever MGCFD_OPT_EXACT says.  out12 = Fp(3) Mp(3) | Fv(3) Mv(3); the pressure six are bit
+ * for bit mgcfd_surface_loads'; the total is the caller's, one addition per component.  On a level the viscous terms are not on for
+ * the friction six are +0.0; a level without solid-wall edges gives twelve exact zeros and launches nothing.
+ * Sign: the friction term takes the convention of the pressure term — both are what the wall face feeds into its node's momentum
+ * residual with the boundary weights as the solver holds them, so Fp + Fv is one consistent vector.  On an fvcorr-variant mesh the
+ * weights point into the fluid: a shear flow u = (a z, 0, 0) over a wall at z = 0 gives Fv = (-mu a A, 0, 0), a pressure excess
+ * on the same wall Fp,z = +dp A.
+ * The first call for a level builds its wall plan (host work, allocations); it goes with the solver.  A solver made by
+ * mgcfd_create_partitioned* or attached to a group or as a rank: MGCFD_ERR_ARG from every call below.
+ * --------------------------------------------------------------------------------- */
+/* Pressure and friction loads of level `level`'s current `variables`.  ref_point NULL = the origin.  Synchronises. */
+int mgcfd_surface_loads_viscous(mgcfd_solver *s, int level, const double ref_point[3], double out12[12]);
+/* mgcfd_run_cycles_loads with rows of twelve: loads_out[c*12 .. c*12+11] = mgcfd_surface_loads_viscous of level 0 for the state at
+ * the end of cycle c, recorded on the device in a twelve-wide history and read back with the RMS.  Same RMS, final state, errors
+ * and NaN rows as mgcfd_run_cycles_loads.  MGCFD_OPT_GRAPH is accepted and the launches run directly. */
+int mgcfd_run_cycles_loads_viscous(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out);
+/* mgcfd_advance with rows of twelve (loads_out [steps][12], required): every step's loads are stored into the history on the
+ * device and read back once.  Same RMS, final state, errors and NaN rows as mgcfd_advance. */
+int mgcfd_advance_loads_viscous(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out,
+                                const double ref_point[3]);
+/* The number of wall nodes of a level (0 where it has no solid-wall edge). */
+int mgcfd_wall_node_count(mgcfd_solver *s, int level, int64_t *n);
+/* The surface distribution of level `level`'s current `variables`, one row per wall node: node_ids [n] (may be NULL) = the
+ * original ids, ascending; out [n][7] = ax ay az | dp | tx ty tz with a = the sum of the node's solid-wall edge weights (from +0.0,
+ * one addition per edge in mgcfd_get_edges order), dp = p_i - p_inf, t = -(tau . a) associated as the edge terms above (+0.0 on a
+ * level the viscous terms are not on for).  The t of all nodes add up to Fv, the dp a to Fp, up to rounding.  Synchronises. */
+#define MGCFD_WALL_COLUMNS 7
+int mgcfd_wall_distribution(mgcfd_solver *s, int level, int64_t *node_ids, double *out);
+/* Diagnostic: Sw itself, out [n][12] (node_ids as above).  MGCFD_ERR_ARG on a level the viscous terms are not on for.  Under
+ * MGCFD_OPT_EXACT = 1 the rows equal the wall nodes' rows of MGCFD_ARR_VISCOUS_STRESS after mgcfd_compute_fluxes on the same state. */
+int mgcfd_wall_stress(mgcfd_solver *s, int level, int64_t *node_ids, double *out);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of the wall-stress kernel (kind 0), the twelve-column loads kernel
+ * (1) or mgcfd_surface_loads' kernel (2) on a viscous level with solid walls, as mgcfd_bench_viscous times its launches. */
+int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

@@ -198,6 +198,46 @@ struct LoadsTerms {
     int64_t row = 0;
 };
 
+// The wall nodes of a level (the distinct b ends of its solid-wall edges, ascending original id) and, per wall node, its
+// internal incidences in the level's original edge order and its solid-wall edges in the order of the records
+// (preprocess.hpp: WallRows).  Node ids are the solver's numbering.
+struct WallNodes {
+    int64_t n = 0;                        // wall nodes
+    const int32_t *node = nullptr;        // [n]
+    const int32_t *int_ptr = nullptr;     // [n + 1] a wall node's internal incidences ...
+    const int32_t *int_nbr = nullptr;     // [entries] ... the other node ...
+    const double *int_n = nullptr;        // [entries][3] ... and the normal seen from the wall node: +e at an a end, -e at a b end
+    const int32_t *wall_ptr = nullptr;    // [n + 1] a wall node's solid-wall edges ...
+    const int32_t *wall_edge = nullptr;   // [records] ... as indices into the level's WallRecord list, ascending
+};
+
+// The node stresses of the wall nodes alone (k_wall_stress): pass 1 of the viscous terms on the level's current state,
+// into a compact table sw [12][n].
+struct WallStress {
+    WallNodes wn;
+    const double *volumes = nullptr;      // [stride]
+    double mu = 0.0, kappa = 0.0;
+    double *sw = nullptr;                 // [12][wn.n]
+};
+
+// Pressure and friction loads in one launch (k_surface_loads_viscous): twelve sums Fp(3) Mp(3) | Fv(3) Mv(3) over the
+// records of `base`; base.partial is [12][ceil(n / 256)], base.out 12 sums, base.ring rows of 12.
+struct LoadsTaskViscous {
+    LoadsTask base;
+    const int32_t *wall_of_rec = nullptr; // [n] the wall node (index into sw's columns) of every record
+    const double *sw = nullptr;           // [12][nw]; nullptr: the viscous terms are off for the level, the friction six are +0.0
+    int64_t nw = 0;
+};
+
+// The per-wall-node surface distribution (k_wall_distribution): out [n][7] = ax ay az | dp | tx ty tz.
+struct WallDistribution {
+    WallNodes wn;
+    const WallRecord *rec = nullptr;
+    double p_inf = 0.0;
+    const double *sw = nullptr;           // as in LoadsTaskViscous
+    double *out = nullptr;
+};
+
 // Long rows (preprocess.hpp: LevelPlan::tail_*): device arrays of the entries the per-node loop leaves to the workgroup.
 struct TailPlan {
     const int32_t *rows_main = nullptr;   // [n_slices] internal rows the per-node loop walks

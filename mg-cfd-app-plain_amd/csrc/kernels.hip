@@ -3149,45 +3149,48 @@ __global__ void k_append_scalar(const double *__restrict__ src, double *__restri
 // ------------------------------------------------------------------------------------------
 // The tree over the 256 lanes' six values; lane 0 holds the sums.  s = 128, 64 through LDS, s < 64 by shuffles within
 // wave 0 (lane t adds lane t + s: the same operand pairs).
-__device__ __forceinline__ void loads_tree(double v[6], double (*sh)[kBlock])
+// NC columns: six for the pressure loads, twelve with the friction loads beside them (k_surface_loads_viscous).
+template <int NC>
+__device__ __forceinline__ void loads_tree(double (&v)[NC], double (&sh)[NC][kBlock])
 {
 #pragma clang fp contract(off)
     const int t = threadIdx.x;
 #pragma unroll
-    for (int c = 0; c < 6; c++) sh[c][t] = v[c];
+    for (int c = 0; c < NC; c++) sh[c][t] = v[c];
     __syncthreads();
     if (t < 128) {
 #pragma unroll
-        for (int c = 0; c < 6; c++) v[c] += sh[c][t + 128];
+        for (int c = 0; c < NC; c++) v[c] += sh[c][t + 128];
     }
     __syncthreads();
     if (t < 128) {
 #pragma unroll
-        for (int c = 0; c < 6; c++) sh[c][t] = v[c];
+        for (int c = 0; c < NC; c++) sh[c][t] = v[c];
     }
     __syncthreads();
     if (t < 64) {
 #pragma unroll
-        for (int c = 0; c < 6; c++) v[c] += sh[c][t + 64];
+        for (int c = 0; c < NC; c++) v[c] += sh[c][t + 64];
         for (int s = 32; s > 0; s >>= 1) {
 #pragma unroll
-            for (int c = 0; c < 6; c++) v[c] += __shfl_down(v[c], s, 64);
+            for (int c = 0; c < NC; c++) v[c] += __shfl_down(v[c], s, 64);
         }
     }
     __syncthreads();                                                   // (sh is free again)
 }
 
-__device__ __forceinline__ void loads_store(const LoadsTask &task, const double v[6])
+template <int NC>
+__device__ __forceinline__ void loads_store(const LoadsTask &task, const double (&v)[NC])
 {
     if (task.out) {
 #pragma unroll
-        for (int c = 0; c < 6; c++) task.out[c] = v[c];
+        for (int c = 0; c < NC; c++) task.out[c] = v[c];
     }
     if (task.ring) {
         const int k = *task.count - 1;                                 // the row of the cycle whose RMS was appended last
         if (k >= 0 && k < task.cap) {
 #pragma unroll
-            for (int c = 0; c < 6; c++) task.ring[int64_t(k) * 6 + c] = v[c];
+            for (int c = 0; c < NC; c++) task.ring[int64_t(k) * NC + c] = v[c];
         }
     }
 }
@@ -3339,6 +3342,154 @@ k_loads_reduce(const double *__restrict__ table, int64_t row, LoadsTask task)
         n = m;
     }
     if (t == 0) loads_store(task, v);
+}
+
+// ------------------------------------------------------------------------------------------
+// Viscous surface loads (INTEGRATION.md "Viscous surface loads"): the friction the no-slip or slip wall of a viscous level
+// feeds into its nodes' momentum, g = -(tau . w) per solid-wall edge with tau the node's stresses, summed beside the
+// pressure terms through the same trees.  The stresses come from k_wall_stress: pass 1 of the viscous terms (the
+// expressions of k_viscous_stress_tile, in the same order) for the wall nodes alone, one lane per wall node over a CSR
+// row of its internal incidences, so that the cost follows the wall and not the level and S stays as the last flux launch
+// left it.  Never contracted to FMA: these kernels are always taken from the exact build.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock)
+k_wall_stress(int64_t stride, const double *__restrict__ q, WallStress a)
+{
+#pragma clang fp contract(off)
+    const int64_t k = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (k >= a.wn.n) return;
+    const int64_t i = a.wn.node[k];
+    const int32_t e0 = a.wn.int_ptr[k], e1 = a.wn.int_ptr[k + 1];
+    const Primitive me = primitive_of(q, stride, i);
+    const double vol = a.volumes[i];
+    double ux = 0.0, uy = 0.0, uz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0, wx = 0.0, wy = 0.0, wz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
+    for (int32_t e = e0; e < e1; e++) {
+        const Primitive ot = primitive_of(q, stride, a.wn.int_nbr[e]);
+        const double nx = a.wn.int_n[3 * int64_t(e)], ny = a.wn.int_n[3 * int64_t(e) + 1], nz = a.wn.int_n[3 * int64_t(e) + 2];
+        const double du = ot.u - me.u, dv = ot.v - me.v, dw = ot.w - me.w, dT = ot.T - me.T;
+        ux += du * nx; uy += du * ny; uz += du * nz;
+        vx += dv * nx; vy += dv * ny; vz += dv * nz;
+        wx += dw * nx; wy += dw * ny; wz += dw * nz;
+        tx += dT * nx; ty += dT * ny; tz += dT * nz;
+    }
+    const double gux = (0.5 * ux) / vol, guy = (0.5 * uy) / vol, guz = (0.5 * uz) / vol;
+    const double gvx = (0.5 * vx) / vol, gvy = (0.5 * vy) / vol, gvz = (0.5 * vz) / vol;
+    const double gwx = (0.5 * wx) / vol, gwy = (0.5 * wy) / vol, gwz = (0.5 * wz) / vol;
+    const double gtx = (0.5 * tx) / vol, gty = (0.5 * ty) / vol, gtz = (0.5 * tz) / vol;
+    const double div = (gux + gvy) + gwz;
+    const double tt = (2.0 / 3.0) * div;
+    double out[12];
+    out[0] = me.u; out[1] = me.v; out[2] = me.w;
+    out[3] = a.mu * (2.0 * gux - tt); out[4] = a.mu * (2.0 * gvy - tt); out[5] = a.mu * (2.0 * gwz - tt);
+    out[6] = a.mu * (guy + gvx); out[7] = a.mu * (guz + gwx); out[8] = a.mu * (gvz + gwy);
+    out[9] = a.kappa * gtx; out[10] = a.kappa * gty; out[11] = a.kappa * gtz;
+#pragma unroll
+    for (int f = 0; f < 12; f++) a.sw[f * a.wn.n + k] = out[f];
+}
+
+// k_surface_loads with the friction six beside the pressure six: one lane per solid-wall edge, twelve terms, the trees
+// of k_surface_loads over twelve columns (24 KB of LDS), the same ticket and stage B.  The pressure terms are
+// k_surface_loads' expressions; task.sw == nullptr (a level the viscous terms are not on for) leaves the friction +0.0.
+__global__ void __launch_bounds__(kBlock)
+k_surface_loads_viscous(int64_t stride, const double *__restrict__ q, LoadsTaskViscous task)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[12][kBlock];
+    __shared__ int last;
+    const LoadsTask &base = task.base;
+    const int t = threadIdx.x;
+    const int64_t e = int64_t(blockIdx.x) * kBlock + t;
+    double v[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (e < base.n) {
+        const WallRecord r = base.rec[e];
+        const int64_t b = r.node;
+        const double rho = q[b], mx = q[stride + b], my = q[2 * stride + b], mz = q[3 * stride + b], en = q[4 * stride + b];
+        const double vx = mx / rho, vy = my / rho, vz = mz / rho;
+        const double speed_sqd = vx * vx + vy * vy + vz * vz;
+        const double p = (kGamma - 1.0) * (en - 0.5 * rho * speed_sqd);
+        const double dp = p - base.p_inf;
+        const double fx = dp * r.x, fy = dp * r.y, fz = dp * r.z;
+        const double rx = r.cx - base.ref[0], ry = r.cy - base.ref[1], rz = r.cz - base.ref[2];
+        v[0] = fx; v[1] = fy; v[2] = fz;
+        v[3] = ry * fz - rz * fy;
+        v[4] = rz * fx - rx * fz;
+        v[5] = rx * fy - ry * fx;
+        if (task.sw) {
+            const double *s = task.sw + task.wall_of_rec[e];
+            const double txx = s[3 * task.nw], tyy = s[4 * task.nw], tzz = s[5 * task.nw];
+            const double txy = s[6 * task.nw], txz = s[7 * task.nw], tyz = s[8 * task.nw];
+            const double gx = -((txx * r.x + txy * r.y) + txz * r.z);
+            const double gy = -((txy * r.x + tyy * r.y) + tyz * r.z);
+            const double gz = -((txz * r.x + tyz * r.y) + tzz * r.z);
+            v[6] = gx; v[7] = gy; v[8] = gz;
+            v[9] = ry * gz - rz * gy;
+            v[10] = rz * gx - rx * gz;
+            v[11] = rx * gy - ry * gx;
+        }
+    }
+    loads_tree(v, sh);                                                 // stage A
+    const int nb = int(gridDim.x);
+    if (nb == 1) {
+        if (t == 0) loads_store(base, v);
+        return;
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int c = 0; c < 12; c++) base.partial[int64_t(c) * nb + blockIdx.x] = v[c];
+        const unsigned done = __hip_atomic_fetch_add(base.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        last = done == unsigned(nb - 1);
+        if (last) __hip_atomic_store(base.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the next call starts from zero)
+    }
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    for (int n = nb; n > 1;) {                                          // stage B, as in k_surface_loads
+        const int m = (n + kBlock - 1) / kBlock;
+        for (int k = 0; k < m; k++) {
+            const int i = k * kBlock + t;
+#pragma unroll
+            for (int c = 0; c < 12; c++) v[c] = i < n ? base.partial[int64_t(c) * nb + i] : 0.0;
+            loads_tree(v, sh);
+            if (t == 0) {
+#pragma unroll
+                for (int c = 0; c < 12; c++) base.partial[int64_t(c) * nb + k] = v[c];
+            }
+            __syncthreads();
+        }
+        n = m;
+    }
+    if (t == 0) loads_store(base, v);
+}
+
+// The surface distribution: one lane per wall node over its solid-wall edges in record order.  a = the sum of their
+// weights from +0.0, dp = p - p_inf by k_surface_loads' expressions, t = -(tau . a) associated as the edge terms are.
+__global__ void __launch_bounds__(kBlock)
+k_wall_distribution(int64_t stride, const double *__restrict__ q, WallDistribution a)
+{
+#pragma clang fp contract(off)
+    const int64_t k = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (k >= a.wn.n) return;
+    const int64_t b = a.wn.node[k];
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    for (int32_t j = a.wn.wall_ptr[k]; j < a.wn.wall_ptr[k + 1]; j++) {
+        const WallRecord &r = a.rec[a.wn.wall_edge[j]];
+        ax += r.x; ay += r.y; az += r.z;
+    }
+    const double rho = q[b], mx = q[stride + b], my = q[2 * stride + b], mz = q[3 * stride + b], en = q[4 * stride + b];
+    const double vx = mx / rho, vy = my / rho, vz = mz / rho;
+    const double speed_sqd = vx * vx + vy * vy + vz * vz;
+    const double p = (kGamma - 1.0) * (en - 0.5 * rho * speed_sqd);
+    double tx = 0.0, ty = 0.0, tz = 0.0;
+    if (a.sw) {
+        const double *s = a.sw + k;
+        const double txx = s[3 * a.wn.n], tyy = s[4 * a.wn.n], tzz = s[5 * a.wn.n];
+        const double txy = s[6 * a.wn.n], txz = s[7 * a.wn.n], tyz = s[8 * a.wn.n];
+        tx = -((txx * ax + txy * ay) + txz * az);
+        ty = -((txy * ax + tyy * ay) + tyz * az);
+        tz = -((txz * ax + tyz * ay) + tzz * az);
+    }
+    double *o = a.out + 7 * k;
+    o[0] = ax; o[1] = ay; o[2] = az; o[3] = p - a.p_inf; o[4] = tx; o[5] = ty; o[6] = tz;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4055,6 +4206,18 @@ void launch_surface_loads(hipStream_t st, int64_t stride, const double *q, const
     if (task.n <= 0) return;                                           // (the caller writes the zeros)
     hipLaunchKernelGGL(k_surface_loads, dim3(unsigned((task.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, stride, q, task);
 }
+
+void launch_wall_stress(hipStream_t st, int64_t stride, const double *q, const WallStress &a)
+{ if (a.wn.n > 0) hipLaunchKernelGGL(k_wall_stress, dim3(grid_for(a.wn.n)), dim3(kBlock), 0, st, stride, q, a); }
+
+void launch_surface_loads_viscous(hipStream_t st, int64_t stride, const double *q, const LoadsTaskViscous &task)
+{
+    if (task.base.n <= 0) return;
+    hipLaunchKernelGGL(k_surface_loads_viscous, dim3(unsigned((task.base.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, stride, q, task);
+}
+
+void launch_wall_distribution(hipStream_t st, int64_t stride, const double *q, const WallDistribution &a)
+{ if (a.wn.n > 0) hipLaunchKernelGGL(k_wall_distribution, dim3(grid_for(a.wn.n)), dim3(kBlock), 0, st, stride, q, a); }
 
 void launch_loads_terms(hipStream_t st, int64_t stride, const double *q, const LoadsTerms &task)
 {

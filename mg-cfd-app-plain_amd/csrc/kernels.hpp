@@ -69,6 +69,9 @@
                          double *coarse_q,                                                                        \
                          const double *cbrt_vol, double cfl, double *partial_min, const SumTask &rms);              \
     void launch_surface_loads(hipStream_t, int64_t stride, const double *q, const LoadsTask &task);                  \
+    void launch_wall_stress(hipStream_t, int64_t stride, const double *q, const WallStress &a);                      \
+    void launch_surface_loads_viscous(hipStream_t, int64_t stride, const double *q, const LoadsTaskViscous &task);   \
+    void launch_wall_distribution(hipStream_t, int64_t stride, const double *q, const WallDistribution &a);          \
     void launch_loads_terms(hipStream_t, int64_t stride, const double *q, const LoadsTerms &task);                   \
     void launch_loads_scatter(hipStream_t, int64_t n, const double *src, int64_t src_row, const int32_t *slot,       \
                               double *table, int64_t row);                                                           \

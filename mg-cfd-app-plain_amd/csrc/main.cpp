@@ -76,6 +76,9 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool no_slip = false;
     int viscous_levels = 1;
     bool viscous() const { return viscosity_given || reynolds_given; }
+    bool loads_friction = false;      // --loads-friction: the friction loads beside the pressure loads in surface_loads.* and polar.csv (one GPU)
+    bool output_surface = false;      // --output-surface: Cp and Cf per wall node of level 0 into surface.* (one GPU)
+    size_t loads_width() const { return loads_friction ? 12 : 6; }
     // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
     bool fas = false;
     // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
@@ -336,6 +339,11 @@ void print_help()
         "  --loads-reference=S,c,x,y,z      Reference area, length and moment point of --output-loads (default 1,1,0,0,0)\n"
         "  --mach=M                         Free-stream Mach number (default 1.2, the reference's; config key ff_mach)\n"
         "  --alpha=DEG                      Angle of attack in degrees, inside (-90, 90) (default 0; config key angle_of_attack)\n"
+        "  --loads-friction                 With the viscous terms and --output-loads or --polar: the thirteen columns are computed from the\n"
+        "                                   total of pressure and friction loads, and the friction loads Fxv ... Mzv and their\n"
+        "                                   coefficients CDv ... CMzv follow them.  One GPU\n"
+        "  --output-surface                 Write surface.* (CSV): one row per solid-wall node of level 0 in the final state, its\n"
+        "                                   coordinates, wall area vector, Cp and the tangential Cf vector.  One GPU\n"
         "  --polar=A0:A1:N                  N angles of attack from A0 to A1 inclusive, -g cycles each: the first starts from its\n"
         "                                   far field, every later one from the flow of the angle before it.  Writes polar.*\n"
         "                                   (CSV: alpha,mach,rms_last, the loads and coefficients of each angle's last cycle);\n"
@@ -440,6 +448,8 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"viscous-cfl", required_argument, nullptr, 1035},
         {"no-slip", no_argument, nullptr, 1036},
         {"viscous-levels", required_argument, nullptr, 1037},
+        {"loads-friction", no_argument, nullptr, 1038},
+        {"output-surface", no_argument, nullptr, 1039},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -577,6 +587,8 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 }
                 c.viscous_extras_given = true;
                 break;
+            case 1038: c.loads_friction = true; break;
+            case 1039: c.output_surface = true; break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
@@ -590,6 +602,14 @@ bool parse_arguments(int argc, char **argv, Config &c)
     }
     if (c.viscous_extras_given && !c.viscous()) {
         std::fprintf(stderr, "ERROR: --ref-length, --prandtl, --no-slip, --viscous-cfl and --viscous-levels need --viscosity MU or --reynolds RE (the viscous terms)\n");
+        return false;
+    }
+    if (c.loads_friction && !(c.viscous() && c.viscous_levels > 0 && (c.output_loads || c.polar))) {
+        std::fprintf(stderr, "ERROR: --loads-friction needs the viscous terms (--viscosity MU or --reynolds RE) and --output-loads or --polar\n");
+        return false;
+    }
+    if ((c.loads_friction || c.output_surface) && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: --loads-friction and --output-surface run on one GPU only\n");
         return false;
     }
     if (c.dual_extras_given && !c.dual_given) {
@@ -750,23 +770,37 @@ int validate_and_dump(const Config &conf, int levels, int mesh_variant, int64_t 
     return 0;
 }
 
+// The loads columns of a surface_loads.* or polar.csv row: Fx ... Mz and CD ... CMz; with --loads-friction `row` holds the
+// pressure six and the friction six, the twelve columns are those of their total (one addition per component) and the friction
+// loads and their coefficients follow.
+const char *const kFrictionColumns = ",Fxv,Fyv,Fzv,Mxv,Myv,Mzv,CDv,CLv,CSv,CMxv,CMyv,CMzv";
+int write_loads_columns(FILE *f, const Config &conf, const double ff17[17], const double *row)
+{
+    double total[6], coef[6];
+    for (int k = 0; k < 6; k++) total[k] = conf.loads_friction ? row[k] + row[6 + k] : row[k];
+    if (mgcfd_load_coefficients(ff17, total, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) return 1;
+    for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", total[k]);
+    for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
+    if (!conf.loads_friction) return 0;
+    if (mgcfd_load_coefficients(ff17, row + 6, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) return 1;
+    for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", row[6 + k]);
+    for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
+    return 0;
+}
+
 // --output-loads: one row per cycle (dual time stepping: per physical step), the loads and their coefficients (nothing on stdout: it stays the reference's)
 int write_loads_csv(const Config &conf, const double ff17[17], const std::vector<double> &loads)
 {
     const std::string path = output_filepath(conf, "surface_loads", 0);
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
-    std::fprintf(f, "cycle,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz\n");
+    std::fprintf(f, "cycle,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz%s\n", conf.loads_friction ? kFrictionColumns : "");
     for (int c = 0; c < conf.loads_rows(); c++) {
-        const double *row = loads.data() + static_cast<size_t>(c) * 6;
-        double coef[6];
-        if (mgcfd_load_coefficients(ff17, row, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) {
+        std::fprintf(f, "%d", c + 1);
+        if (write_loads_columns(f, conf, ff17, loads.data() + static_cast<size_t>(c) * conf.loads_width())) {
             std::fclose(f);
             return fail("computing the load coefficients");
         }
-        std::fprintf(f, "%d", c + 1);
-        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", row[k]);
-        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
         std::fprintf(f, "\n");
     }
     if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
@@ -774,23 +808,57 @@ int write_loads_csv(const Config &conf, const double ff17[17], const std::vector
 }
 
 // --polar: one row per angle — the RMS, loads and coefficients of its last cycle (nothing on stdout)
-struct PolarRow { double alpha, mach, rms_last, loads[6], ff17[17]; };
+struct PolarRow { double alpha, mach, rms_last, loads[12], ff17[17]; };
 int write_polar_csv(const Config &conf, const std::vector<PolarRow> &rows)
 {
     const std::string path = csv_filepath(conf, "polar.csv");
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
-    std::fprintf(f, "alpha,mach,rms_last,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz\n");
+    std::fprintf(f, "alpha,mach,rms_last,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz%s\n", conf.loads_friction ? kFrictionColumns : "");
     for (const PolarRow &r : rows) {
-        double coef[6];
-        if (mgcfd_load_coefficients(r.ff17, r.loads, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) {
+        std::fprintf(f, "%.17e,%.17e,%.17e", r.alpha, r.mach, r.rms_last);
+        if (write_loads_columns(f, conf, r.ff17, r.loads)) {
             std::fclose(f);
             return fail("computing the load coefficients");
         }
-        std::fprintf(f, "%.17e,%.17e,%.17e", r.alpha, r.mach, r.rms_last);
-        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", r.loads[k]);
-        for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
         std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
+    return 0;
+}
+
+// --output-surface: one row per wall node of level 0 in the state the run ends with — the node's original id and coordinates,
+// the sum a of its solid-wall edge weights, Cp = dp / q_inf and the tangential friction coefficient
+// Cf = (t - (t.n) n) / (|a| q_inf), n = a / |a| (mgcfd_wall_distribution; nothing on stdout)
+int write_surface_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh *mesh)
+{
+    int64_t n = 0;
+    double ff17[17];
+    mgcfd_level_desc desc;
+    if (mgcfd_wall_node_count(solver, 0, &n) != MGCFD_OK || mgcfd_get_far_field(solver, ff17) != MGCFD_OK ||
+        mgcfd_mesh_level(mesh, 0, &desc) != MGCFD_OK)
+        return fail("reading the wall nodes");
+    std::vector<int64_t> ids(static_cast<size_t>(n));
+    std::vector<double> table(static_cast<size_t>(n) * MGCFD_WALL_COLUMNS);
+    if (n > 0 && mgcfd_wall_distribution(solver, 0, ids.data(), table.data()) != MGCFD_OK) return fail("computing the surface distribution");
+    const double vx = ff17[1] / ff17[0], vy = ff17[2] / ff17[0], vz = ff17[3] / ff17[0];
+    const double q = 0.5 * ff17[0] * (vx * vx + vy * vy + vz * vz);
+    std::string path = conf.output_file_prefix;
+    if (!path.empty() && path.back() != '/') path += ".";
+    path += "surface.size=" + std::to_string(conf.mesh_duplicate_count) + "x.level=0";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail(("opening " + path).c_str());
+    std::fprintf(f, "node,x,y,z,ax,ay,az,Cp,Cfx,Cfy,Cfz\n");
+    for (int64_t k = 0; k < n; k++) {
+        const double *r = table.data() + static_cast<size_t>(k) * MGCFD_WALL_COLUMNS;
+        const int64_t i = ids[static_cast<size_t>(k)];
+        const double area = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        const double nx = r[0] / area, ny = r[1] / area, nz = r[2] / area;
+        const double tn = r[4] * nx + r[5] * ny + r[6] * nz;
+        const double cf[3] = {(r[4] - tn * nx) / (area * q), (r[5] - tn * ny) / (area * q), (r[6] - tn * nz) / (area * q)};
+        std::fprintf(f, "%ld", static_cast<long>(i));
+        for (int d = 0; d < 3; d++) std::fprintf(f, ",%.17e", desc.coords ? desc.coords[i * 3 + d] : 0.0);
+        std::fprintf(f, ",%.17e,%.17e,%.17e,%.17e,%.17e,%.17e,%.17e\n", r[0], r[1], r[2], r[3] / q, cf[0], cf[1], cf[2]);
     }
     if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
     return 0;
@@ -815,7 +883,7 @@ int run_all_cycles(const Config &conf, std::vector<double> &rms, std::vector<dou
             PolarRow row{};
             row.alpha = conf.angle(k); row.mach = conf.ff_mach;
             row.rms_last = rms.empty() ? std::nan("") : rms.back();
-            for (int q = 0; q < 6; q++) row.loads[q] = loads.empty() ? std::nan("") : loads[loads.size() - 6 + static_cast<size_t>(q)];
+            for (size_t q = 0; q < conf.loads_width(); q++) row.loads[q] = loads.empty() ? std::nan("") : loads[loads.size() - conf.loads_width() + q];
             polar_rows.push_back(row);
         }
     }
@@ -1006,7 +1074,7 @@ int main(int argc, char **argv)
     // ---- compute (src/euler3d_cpu_double.cpp:368-698) ----
     std::vector<double> rms(static_cast<size_t>(conf.total_cycles()));
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> loads((conf.output_loads || conf.polar) ? static_cast<size_t>(conf.loads_rows()) * 6 : 0);
+    std::vector<double> loads((conf.output_loads || conf.polar) ? static_cast<size_t>(conf.loads_rows()) * conf.loads_width() : 0);
     int steps_done = 0;               // dual time stepping: physical steps completed (an invalid state: the step it was found in)
     std::vector<PolarRow> polar_rows;
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
@@ -1030,8 +1098,10 @@ int main(int argc, char **argv)
                 const int per_call = std::max(1, MGCFD_MAX_ADVANCE_CYCLES / conf.num_cycles);
                 for (steps_done = 0; steps_done < conf.time_steps;) {
                     const int now = std::min(per_call, conf.time_steps - steps_done);
-                    const int rc_adv = mgcfd_advance(solver, now, conf.num_cycles, rms_out + size_t(steps_done) * size_t(conf.num_cycles),
-                                                     loads_out ? loads_out + size_t(steps_done) * 6 : nullptr, conf.loads_ref + 2);
+                    double *const rms_at = rms_out + size_t(steps_done) * size_t(conf.num_cycles);
+                    double *const loads_at = loads_out ? loads_out + size_t(steps_done) * conf.loads_width() : nullptr;
+                    const int rc_adv = conf.loads_friction ? mgcfd_advance_loads_viscous(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2)
+                                                           : mgcfd_advance(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2);
                     if (rc_adv != MGCFD_OK) {
                         int bad_step = -1;
                         mgcfd_get_dual_time(solver, nullptr, nullptr, nullptr, nullptr, &bad_step);
@@ -1042,6 +1112,7 @@ int main(int argc, char **argv)
                 }
                 return int(MGCFD_OK);
             }
+            if (loads_out && conf.loads_friction) return mgcfd_run_cycles_loads_viscous(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out);
             return loads_out ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out)
                              : mgcfd_run_cycles(solver, conf.num_cycles, rms_out);
         });
@@ -1083,6 +1154,7 @@ int main(int argc, char **argv)
         if (write_loads_csv(conf, ff17, loads)) return EXIT_FAILURE;
     }
     if (conf.polar && write_polar_csv(conf, polar_rows)) return EXIT_FAILURE;
+    if (conf.output_surface && write_surface_csv(conf, solver, mesh)) return EXIT_FAILURE;
 
     // ---- performance data (src/euler3d_cpu_double.cpp:778-785) ----
     std::string ih, il;

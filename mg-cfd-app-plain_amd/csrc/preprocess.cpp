@@ -1451,4 +1451,56 @@ std::string audit_level_plan(const mgcfd_level_desc &L, const LevelPlan &P, int6
     return rep;
 }
 
+WallRows build_wall_rows(const mgcfd_level_desc &lvl, const std::vector<mgcfd_edge> &edges, const std::vector<int32_t> &new_of_old)
+{
+    WallRows R;
+    const int64_t nel = lvl.nel;
+    auto checked = [&](int64_t node) {
+        if (node < 0 || node >= nel) throw std::invalid_argument("wall rows: an edge names a node out of range");
+        return static_cast<size_t>(node);
+    };
+    // the wall nodes and, per original id, their position among them
+    std::vector<int32_t> wall_index(static_cast<size_t>(nel), -1);
+    for (int64_t k = 0; k < lvl.n_boundary; k++) wall_index[checked(edges[static_cast<size_t>(lvl.boundary_start + k)].b)] = 0;
+    for (int64_t i = 0; i < nel; i++) {
+        if (wall_index[static_cast<size_t>(i)] < 0) continue;
+        wall_index[static_cast<size_t>(i)] = static_cast<int32_t>(R.original.size());
+        R.original.push_back(i);
+        R.node.push_back(new_of_old[static_cast<size_t>(i)]);
+    }
+    const size_t n = R.original.size();
+    // counting pass, then a filling pass in edge order: a row keeps the level's original edge order
+    R.int_ptr.assign(n + 1, 0);
+    R.wall_ptr.assign(n + 1, 0);
+    auto each_internal_end = [&](auto &&visit) {
+        for (int64_t k = 0; k < lvl.n_internal; k++) {
+            const mgcfd_edge &e = edges[static_cast<size_t>(lvl.internal_start + k)];
+            const int32_t wa = wall_index[checked(e.a)], wb = wall_index[checked(e.b)];
+            if (wa >= 0) visit(wa, e.b, e.x, e.y, e.z);
+            if (wb >= 0) visit(wb, e.a, -e.x, -e.y, -e.z);
+        }
+    };
+    each_internal_end([&](int32_t w, int64_t, double, double, double) { R.int_ptr[static_cast<size_t>(w) + 1]++; });
+    for (int64_t k = 0; k < lvl.n_boundary; k++)
+        R.wall_ptr[static_cast<size_t>(wall_index[static_cast<size_t>(edges[static_cast<size_t>(lvl.boundary_start + k)].b)]) + 1]++;
+    for (size_t w = 0; w < n; w++) { R.int_ptr[w + 1] += R.int_ptr[w]; R.wall_ptr[w + 1] += R.wall_ptr[w]; }
+    R.int_nbr.resize(static_cast<size_t>(R.int_ptr[n]));
+    R.int_n.resize(3 * static_cast<size_t>(R.int_ptr[n]));
+    std::vector<int32_t> at(R.int_ptr.begin(), R.int_ptr.end() - 1);
+    each_internal_end([&](int32_t w, int64_t other, double x, double y, double z) {
+        const size_t slot = static_cast<size_t>(at[static_cast<size_t>(w)]++);
+        R.int_nbr[slot] = new_of_old[static_cast<size_t>(other)];
+        R.int_n[3 * slot] = x; R.int_n[3 * slot + 1] = y; R.int_n[3 * slot + 2] = z;
+    });
+    R.wall_edge.resize(static_cast<size_t>(lvl.n_boundary));
+    R.wall_of_rec.resize(static_cast<size_t>(lvl.n_boundary));
+    at.assign(R.wall_ptr.begin(), R.wall_ptr.end() - 1);
+    for (int64_t k = 0; k < lvl.n_boundary; k++) {
+        const int32_t w = wall_index[static_cast<size_t>(edges[static_cast<size_t>(lvl.boundary_start + k)].b)];
+        R.wall_of_rec[static_cast<size_t>(k)] = w;
+        R.wall_edge[static_cast<size_t>(at[static_cast<size_t>(w)]++)] = static_cast<int32_t>(k);
+    }
+    return R;
+}
+
 } // namespace mgcfd

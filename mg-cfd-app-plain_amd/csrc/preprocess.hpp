@@ -200,6 +200,21 @@ void build_transfer_plan(const mgcfd_level_desc &fine, const std::vector<mgcfd_e
 // nel_coarse: size of the next-coarser level when a transfer plan was built into P, else -1.
 std::string audit_level_plan(const mgcfd_level_desc &lvl, const LevelPlan &plan, int64_t nel_coarse = -1);
 
+// The wall nodes of a level and their rows (device_plan.hpp: WallNodes), for the viscous surface loads: built on request, not
+// at creation.  The wall nodes are the distinct b ends of the solid-wall slice in ascending ORIGINAL id; int_* holds every
+// wall node's internal incidences in the level's original edge order (the other end in the solver's numbering, the normal
+// seen from the wall node: +e at an a end, -e at a b end), wall_* its solid-wall edges as positions in the slice, ascending.
+// Throws std::invalid_argument where an edge names a node outside [0, nel).
+struct WallRows {
+    std::vector<int64_t> original;     // [n] original ids, ascending
+    std::vector<int32_t> node;         // [n] the same nodes in the solver's numbering
+    std::vector<int32_t> int_ptr, int_nbr;
+    std::vector<double> int_n;         // [entries][3]
+    std::vector<int32_t> wall_ptr, wall_edge;
+    std::vector<int32_t> wall_of_rec;  // [n_boundary] the wall node (position in `original`) of every solid-wall edge
+};
+WallRows build_wall_rows(const mgcfd_level_desc &lvl, const std::vector<mgcfd_edge> &edges, const std::vector<int32_t> &new_of_old);
+
 // Edge-weight preconditioning exactly as the reference does before its loop
 // (src/Kernels/validation.cpp:28-75, src/euler3d_cpu_double.cpp:337-352).
 void adjust_and_dampen(const mgcfd_level_desc &lvl, int mesh_variant, std::vector<mgcfd_edge> &edges);

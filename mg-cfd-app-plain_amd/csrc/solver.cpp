@@ -146,6 +146,20 @@ struct RankLoads {
     std::vector<int32_t *> peer_slot;    // rank 0: device copies of the other ranks' slots
 };
 
+// The wall nodes of a level and what the viscous surface loads and the surface distribution keep on the device for them
+// (mgcfd_surface_loads_viscous, mgcfd_wall_distribution; INTEGRATION.md "Viscous surface loads"): made by the first such call
+// for the level, gone with the level.
+struct WallPlan {
+    std::vector<int64_t> original;       // the wall nodes' original ids, ascending
+    DeviceOwner mem;                     // every device array named below
+    WallNodes wn;
+    int32_t *wall_of_rec = nullptr;      // [n_wall_rec] the wall node of every solid-wall record
+    double *sw = nullptr;                // [12][wn.n] the wall nodes' stresses of the last k_wall_stress launch
+    double *partial = nullptr;           // [12][ceil(n_wall_rec / 256)]
+    unsigned *ticket = nullptr;
+    double *dist = nullptr;              // [wn.n][MGCFD_WALL_COLUMNS] the distribution's result
+};
+
 struct DeviceLevel {
     mgcfd_level_desc info{};             // sizes only (pointers nulled)
     std::vector<mgcfd_edge> edges;       // final edge weights, original order
@@ -206,6 +220,7 @@ struct DeviceLevel {
     double *loads_partial = nullptr;
     unsigned *loads_ticket = nullptr;
     std::unique_ptr<RankLoads> rl;       // a partitioned level whose ranks add their loads up
+    std::unique_ptr<WallPlan> wp;        // the viscous surface loads' and the surface distribution's plan (first call)
     DeviceOwner mem;                     // the one block behind every array listed at creation (LevelStaging), the three state
                                          // buffers, and what an option or a halo plan uploaded later
     int64_t iters[MGCFD_NUM_LOOPS] = {0};
@@ -299,9 +314,11 @@ struct mgcfd_solver {
     int *rms_count = nullptr;
     // surface loads: a [kRmsRing][6] history filled beside rms_ring (row = the cycle's RMS slot), the reference point and
     // a synchronous call's result on the device; the cycle appends to the history while loads_in_cycle is set
-    double *loads_ring = nullptr, *loads_dev = nullptr;                       // loads_dev: ref [3] | out [6]
+    double *loads_ring = nullptr, *loads_dev = nullptr;                       // loads_dev: ref [3] | out [12]
+    double *loads_ring12 = nullptr;                                           // [kRmsRing][12]: pressure and friction (mgcfd_run_cycles_loads_viscous)
     double loads_ref_host[3] = {0.0, 0.0, 0.0};
     bool loads_in_cycle = false;
+    bool loads_friction = false;                   // ... as twelve-wide rows, the friction six beside the pressure six
     bool partitioned = false;                      // made by mgcfd_create_partitioned* (loads: the group and rank forms, over all ranks)
     double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
     double fs_mach = kDefaultMach, fs_alpha_deg = kDefaultAlphaDeg;      // what ff17 was computed from (mgcfd_set_free_stream)
@@ -2235,6 +2252,60 @@ static void launch_loads(mgcfd_solver *s, DeviceLevel &lv, bool to_ring)
     exact::launch_surface_loads(s->stream, lv.dp.stride, lv.q, t);
 }
 
+// The wall plan of a level (allocations and uploads: never inside a capture or a cycle).
+static WallPlan &wall_plan(mgcfd_solver *s, DeviceLevel &lv)
+{
+    if (lv.wp) return *lv.wp;
+    const WallRows R = build_wall_rows(lv.info, lv.edges, lv.plan.new_of_old);
+    auto wp = std::make_unique<WallPlan>();
+    wp->original = R.original;
+    wp->wn.n = static_cast<int64_t>(R.node.size());
+    wp->wn.node = wp->mem.upload(R.node);
+    wp->wn.int_ptr = wp->mem.upload(R.int_ptr);
+    wp->wn.int_nbr = wp->mem.upload(R.int_nbr);
+    wp->wn.int_n = wp->mem.upload(R.int_n);
+    wp->wn.wall_ptr = wp->mem.upload(R.wall_ptr);
+    wp->wn.wall_edge = wp->mem.upload(R.wall_edge);
+    wp->wall_of_rec = wp->mem.upload(R.wall_of_rec);
+    wp->sw = wp->mem.alloc<double>(12 * R.node.size());
+    wp->partial = wp->mem.alloc<double>(12 * static_cast<size_t>((lv.n_wall_rec + 255) / 256));
+    wp->ticket = wp->mem.upload(std::vector<unsigned>(1, 0u));
+    wp->dist = wp->mem.alloc<double>(MGCFD_WALL_COLUMNS * R.node.size());
+    lv.wp = std::move(wp);
+    return *lv.wp;
+}
+
+// The wall nodes' stresses of level l's current `variables` into the plan's table (the level is viscous and has a plan).
+static void launch_wall_stress(mgcfd_solver *s, int l)
+{
+    DeviceLevel &lv = s->level(l);
+    WallStress a;
+    a.wn = lv.wp->wn; a.volumes = lv.volumes; a.sw = lv.wp->sw;
+    a.mu = s->visc_mu; a.kappa = (s->visc_mu * 1.4) / ((1.4 - 1.0) * s->visc_prandtl);
+    exact::launch_wall_stress(s->stream, lv.dp.stride, lv.q, a);
+}
+
+// Level l's pressure and friction loads of its current `variables` (the level has a plan), as launch_loads: twelve sums
+// into `out` (device) or, out == nullptr, into the twelve-wide history's row of the cycle whose RMS was appended last.  The
+// stress launch runs where the viscous terms are on for the level.
+static void launch_loads_twelve(mgcfd_solver *s, int l, double *out)
+{
+    DeviceLevel &lv = s->level(l);
+    const bool viscous = s->viscous_on(l);
+    LoadsTaskViscous t;
+    t.base.rec = lv.wall_rec; t.base.n = lv.n_wall_rec; t.base.p_inf = s->p_inf; t.base.ref = s->loads_dev;
+    t.base.partial = lv.wp->partial; t.base.ticket = lv.wp->ticket;
+    if (!out) { t.base.ring = s->loads_ring12; t.base.count = s->rms_count; t.base.cap = mgcfd_solver::kRmsRing; }
+    else t.base.out = out;
+    t.wall_of_rec = lv.wp->wall_of_rec; t.sw = viscous ? lv.wp->sw : nullptr; t.nw = lv.wp->wn.n;
+    exact::launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t);
+}
+static void launch_loads_viscous(mgcfd_solver *s, int l, double *out)
+{
+    if (s->viscous_on(l)) launch_wall_stress(s, l);
+    launch_loads_twelve(s, l, out);
+}
+
 // Loads need the whole level on one solver: refuse a partitioned solver or a rank.
 static void loads_require_whole(const mgcfd_solver *s);
 
@@ -2253,6 +2324,10 @@ static void ensure_loads_ring(mgcfd_solver *s)
 {
     if (!s->loads_ring) s->loads_ring = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
 }
+static void ensure_loads_ring12(mgcfd_solver *s)
+{
+    if (!s->loads_ring12) s->loads_ring12 = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 12);
+}
 
 static void loads_prepare(mgcfd_solver *s, const double *ref_point)
 {
@@ -2262,7 +2337,7 @@ static void loads_prepare(mgcfd_solver *s, const double *ref_point)
 
 static void loads_upload_ref(mgcfd_solver *s, const double *ref_point)
 {
-    if (!s->loads_dev) s->loads_dev = s->mem.alloc<double>(9);
+    if (!s->loads_dev) s->loads_dev = s->mem.alloc<double>(15);
     for (int k = 0; k < 3; k++) s->loads_ref_host[k] = ref_point ? ref_point[k] : 0.0;
     HIP_CHECK(hipMemcpyAsync(s->loads_dev, s->loads_ref_host, sizeof(double) * 3, hipMemcpyHostToDevice, s->stream));
 }
@@ -2328,24 +2403,29 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
         transfer(false, l, nullptr);                                       // :560-688
         if (l > 0) sweep(l);
     }
-    if (s->loads_in_cycle) launch_loads(s, s->L[0], true);                // (the state the cycle leaves: after the last prolongation)
+    // (the state the cycle leaves: after the last prolongation)
+    if (s->loads_in_cycle) { if (s->loads_friction) launch_loads_viscous(s, 0, nullptr); else launch_loads(s, s->L[0], true); }
 }
 
-// loads_out != nullptr (mgcfd_run_cycles_loads): also the level-0 surface loads at the end of every cycle, [cycles][6]
-static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out)
+// loads_out != nullptr (mgcfd_run_cycles_loads): also the level-0 surface loads at the end of every cycle, [cycles][6];
+// friction (mgcfd_run_cycles_loads_viscous): rows of twelve, the friction six beside the pressure six, launched directly
+static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out, bool friction = false)
 {
+    const size_t width = friction ? 12 : 6;
     REQUIRE(s);
     int code = MGCFD_OK, failed_cycle = -1, seq_before = 0, seq_per_cycle = 0;
     std::vector<double> loads;
     int rc = guarded([&] {
         s->use_device();
         ensure_rms_ring(s);
-        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = false; } } loads_off{s};
+        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = s->loads_friction = false; } } loads_off{s};
         if (loads_out) {
             loads_prepare(s, ref_point);
-            ensure_loads_ring(s);
+            if (friction) ensure_loads_ring12(s); else ensure_loads_ring(s);
             s->loads_in_cycle = s->L[0].n_wall_rec > 0;        // (no solid wall: zeros, nothing launched)
-            loads.reserve(static_cast<size_t>(cycles > 0 ? cycles : 0) * 6);
+            s->loads_friction = friction;
+            if (friction && s->loads_in_cycle) wall_plan(s, s->L[0]);
+            loads.reserve(static_cast<size_t>(cycles > 0 ? cycles : 0) * width);
         }
         const size_t nl = s->L.size();
         std::vector<double> sums;
@@ -2356,7 +2436,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->viscous_on(0) && !s->fas && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && !friction && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->viscous_on(0) && !s->fas && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2432,9 +2512,10 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             sums.resize(at + static_cast<size_t>(chunk));
             HIP_CHECK(hipMemcpyAsync(sums.data() + at, s->rms_ring, sizeof(double) * chunk, hipMemcpyDeviceToHost, s->stream));
             if (loads_out) {
-                loads.resize((at + static_cast<size_t>(chunk)) * 6, 0.0);
+                loads.resize((at + static_cast<size_t>(chunk)) * width, 0.0);
                 if (s->loads_in_cycle)
-                    HIP_CHECK(hipMemcpyAsync(loads.data() + at * 6, s->loads_ring, sizeof(double) * 6 * chunk, hipMemcpyDeviceToHost, s->stream));
+                    HIP_CHECK(hipMemcpyAsync(loads.data() + at * width, friction ? s->loads_ring12 : s->loads_ring, sizeof(double) * width * chunk,
+                                             hipMemcpyDeviceToHost, s->stream));
             }
             int seq = 0;
             code = s->read_error(nullptr, &seq);                           // synchronises
@@ -2465,7 +2546,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             const double nan = std::numeric_limits<double>::quiet_NaN();
             for (int c = 0; c < cycles; c++) {
                 const bool ok = c < static_cast<int>(sums.size()) && (failed_cycle < 0 || c < failed_cycle);
-                for (int k = 0; k < 6; k++) loads_out[c * 6 + k] = ok ? loads[static_cast<size_t>(c) * 6 + static_cast<size_t>(k)] : nan;
+                for (size_t k = 0; k < width; k++) loads_out[static_cast<size_t>(c) * width + k] = ok ? loads[static_cast<size_t>(c) * width + k] : nan;
             }
         }
         HIP_CHECK(hipGetLastError());
@@ -5045,6 +5126,22 @@ static void loads_require_whole(const mgcfd_solver *s)
         throw std::invalid_argument("surface loads: the solver is attached as a rank; the loads of a partitioned level come from the group and rank calls");
 }
 
+// the wall nodes' table after `fill` has launched what writes it: ids and rows to the host, synchronously
+template <typename Fill>
+static void wall_table(mgcfd_solver *s, int level, int64_t *node_ids, double *out, int columns, Fill fill)
+{
+    s->use_device();
+    DeviceLevel &lv = s->level(level);
+    loads_require_whole(s);
+    WallPlan &wp = wall_plan(s, lv);
+    if (node_ids) std::copy(wp.original.begin(), wp.original.end(), node_ids);
+    if (wp.wn.n == 0) return;
+    const double *table = fill(lv, wp);
+    HIP_CHECK(hipMemcpyAsync(out, table, sizeof(double) * static_cast<size_t>(columns) * static_cast<size_t>(wp.wn.n), hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    HIP_CHECK(hipGetLastError());
+}
+
 extern "C" {
 
 int mgcfd_surface_loads(mgcfd_solver *s, int level, const double ref_point[3], double out6[6])
@@ -5069,6 +5166,103 @@ int mgcfd_run_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3
 {
     REQUIRE(s); REQUIRE(loads_out);
     return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out);
+}
+
+// ---- viscous surface loads: the friction six beside the pressure six, the surface distribution ----
+int mgcfd_surface_loads_viscous(mgcfd_solver *s, int level, const double ref_point[3], double out12[12])
+{
+    REQUIRE(s); REQUIRE(out12);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        loads_prepare(s, ref_point);
+        double got[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (lv.n_wall_rec > 0) {                          // (no solid wall: exact zeros, nothing launched)
+            wall_plan(s, lv);
+            launch_loads_viscous(s, level, s->loads_dev + 3);
+            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            HIP_CHECK(hipGetLastError());
+        }
+        std::memcpy(out12, got, sizeof(got));
+    });
+}
+
+int mgcfd_run_cycles_loads_viscous(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
+{
+    REQUIRE(s); REQUIRE(loads_out);
+    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out, true);
+}
+
+int mgcfd_wall_node_count(mgcfd_solver *s, int level, int64_t *n)
+{
+    REQUIRE(s); REQUIRE(n);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        loads_require_whole(s);
+        *n = wall_plan(s, lv).wn.n;
+    });
+}
+
+int mgcfd_wall_distribution(mgcfd_solver *s, int level, int64_t *node_ids, double *out)
+{
+    REQUIRE(s); REQUIRE(out);
+    return guarded([&] {
+        wall_table(s, level, node_ids, out, MGCFD_WALL_COLUMNS, [&](DeviceLevel &lv, WallPlan &wp) {
+            const bool viscous = s->viscous_on(level);
+            if (viscous) launch_wall_stress(s, level);
+            WallDistribution a;
+            a.wn = wp.wn; a.rec = lv.wall_rec; a.p_inf = s->p_inf; a.sw = viscous ? wp.sw : nullptr; a.out = wp.dist;
+            exact::launch_wall_distribution(s->stream, lv.dp.stride, lv.q, a);
+            return wp.dist;
+        });
+    });
+}
+
+int mgcfd_wall_stress(mgcfd_solver *s, int level, int64_t *node_ids, double *out)
+{
+    REQUIRE(s); REQUIRE(out);
+    return guarded([&] {
+        if ((void)s->level(level), !s->viscous_on(level)) throw std::invalid_argument("mgcfd_wall_stress: the viscous terms are off on this level (mgcfd_set_viscous)");
+        wall_table(s, level, node_ids, out, 12, [&](DeviceLevel &, WallPlan &wp) { launch_wall_stress(s, level); return wp.sw; });
+        // the device table is [12][n]: rows of twelve for the caller
+        const size_t n = static_cast<size_t>(s->level(level).wp->wn.n);
+        const std::vector<double> cols(out, out + 12 * n);
+        for (size_t k = 0; k < n; k++)
+            for (size_t f = 0; f < 12; f++) out[k * 12 + f] = cols[f * n + k];
+    });
+}
+
+// Diagnostic: mean GPU time of `launches` back-to-back launches of k_wall_stress (kind 0), k_surface_loads_viscous (1) or
+// k_surface_loads (2) on the level's current state, as mgcfd_bench_viscous times its launches.
+int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->viscous_on(level)) throw std::invalid_argument("the viscous terms are off on this level: switch them on first (mgcfd_set_viscous)");
+        if (kind < 0 || kind > 2) throw std::invalid_argument("friction loads launch kind: 0 wall stress, 1 pressure and friction loads, 2 pressure loads");
+        if (lv.n_wall_rec == 0) throw std::invalid_argument("the level has no solid-wall edge");
+        loads_prepare(s, nullptr);
+        wall_plan(s, lv);
+        Event a = s->get_event(), b = s->get_event();
+        launch_loads_viscous(s, level, s->loads_dev + 3);
+        HIP_CHECK(hipEventRecord(a.get(), s->stream));
+        for (int k = 0; k < launches; k++) {
+            if (kind == 0) launch_wall_stress(s, level);
+            else if (kind == 1) launch_loads_twelve(s, level, s->loads_dev + 3);
+            else launch_loads(s, lv, false);
+        }
+        HIP_CHECK(hipEventRecord(b.get(), s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        s->free_events.push_back(std::move(a));
+        s->free_events.push_back(std::move(b));
+        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+    });
 }
 
 int mgcfd_load_coefficients(const double ff17[17], const double loads6[6], double ref_area, double ref_length, double out6[6])
@@ -5178,15 +5372,34 @@ static void dual_begin_step(mgcfd_solver *s)
     s->dual_levels = s->dual_levels == 0 ? 1 : 2;
 }
 int mgcfd_dual_time_begin_step(mgcfd_solver *s) { OP(dual_begin_step(s)); }
-int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
+// friction (mgcfd_advance_loads_viscous): rows of twelve, every step's launches store into a row of the twelve-wide history on
+// the device and the rows are read back when it is full and at the end
+static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double *ref_point, bool friction)
 {
     REQUIRE(s);
+    const size_t width = friction ? 12 : 6;
+    int held = 0;                               // history rows not yet read back, the last of them row `step`
+    auto read_rows = [&](int step) {
+        if (held == 0) return int(MGCFD_OK);
+        return guarded([&] {
+            HIP_CHECK(hipMemcpyAsync(loads_out + size_t(step + 1 - held) * 12, s->loads_ring12, sizeof(double) * 12 * size_t(held), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            held = 0;
+        });
+    };
     int rc = guarded([&] {
         require_dual_time(s, "mgcfd_advance");
         if (steps < 0 || cycles_per_step < 1) throw std::invalid_argument("mgcfd_advance (dual time): steps >= 0 and cycles_per_step >= 1");
         if (int64_t(steps) * cycles_per_step > MGCFD_MAX_ADVANCE_CYCLES)
             throw std::invalid_argument("mgcfd_advance (dual time): at most " + std::to_string(MGCFD_MAX_ADVANCE_CYCLES) + " cycles per call (steps * cycles_per_step)");
         if (loads_out) loads_require_whole(s);
+        if (loads_out && friction) {
+            s->use_device();
+            loads_upload_ref(s, ref_point);
+            ensure_loads_ring12(s);
+            if (s->L[0].n_wall_rec > 0) wall_plan(s, s->L[0]);
+            else std::fill(loads_out, loads_out + size_t(steps) * 12, 0.0);         // (no solid wall: zeros, nothing launched)
+        }
         s->dual_invalid_step = -1;
     });
     if (rc != MGCFD_OK) return rc;
@@ -5195,17 +5408,32 @@ int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_o
         double *rms = rms_out ? rms_out + size_t(step) * size_t(cycles_per_step) : nullptr;
         rc = mgcfd_dual_time_begin_step(s);
         if (rc == MGCFD_OK) rc = run_cycles_impl(s, cycles_per_step, rms, nullptr, nullptr);
-        if (rc == MGCFD_OK && loads_out) rc = mgcfd_surface_loads(s, 0, ref_point, loads_out + size_t(step) * 6);
+        if (rc == MGCFD_OK && loads_out && !friction) rc = mgcfd_surface_loads(s, 0, ref_point, loads_out + size_t(step) * 6);
+        if (rc == MGCFD_OK && loads_out && friction && s->L[0].n_wall_rec > 0) {
+            rc = guarded([&] { s->use_device(); launch_loads_viscous(s, 0, s->loads_ring12 + size_t(held) * 12); });
+            if (rc == MGCFD_OK) held++;
+            if (rc == MGCFD_OK && (held == mgcfd_solver::kRmsRing || step + 1 == steps)) rc = read_rows(step);
+        }
         if (rc == MGCFD_OK) continue;
+        if (friction && loads_out) (void)read_rows(step - 1);      // (the steps that completed keep their rows)
         // as mgcfd_run_cycles: what did not complete is NaN (the failing step's RMS entries are already), later steps do not run
         if (rc >= MGCFD_ERR_NAN && rc <= MGCFD_ERR_NEG_ENERGY) s->dual_invalid_step = step;
         for (int k = step + 1; rms_out && k < steps; k++)
             for (int c = 0; c < cycles_per_step; c++) rms_out[size_t(k) * size_t(cycles_per_step) + size_t(c)] = nan;
         for (int k = step; loads_out && k < steps; k++)
-            for (int c = 0; c < 6; c++) loads_out[size_t(k) * 6 + size_t(c)] = nan;
+            for (size_t c = 0; c < width; c++) loads_out[size_t(k) * width + c] = nan;
         return rc;
     }
     return MGCFD_OK;
+}
+int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
+{
+    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, false);
+}
+int mgcfd_advance_loads_viscous(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
+{
+    REQUIRE(loads_out);
+    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, true);
 }
 
 } // extern "C"

@@ -204,6 +204,13 @@ _SIGNATURES = [
                                     C.POINTER(C.c_int)]),
     ("mgcfd_viscosity_from_reynolds", C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     ("mgcfd_bench_viscous", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_surface_loads_viscous", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_run_cycles_loads_viscous", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_advance_loads_viscous", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_wall_node_count", C.c_int, [_vp, C.c_int, C.POINTER(_i64)]),
+    ("mgcfd_wall_distribution", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_wall_stress", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_bench_friction_loads", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 ]
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
@@ -355,6 +362,27 @@ def load_coefficients(ff17, loads, ref_area: float = 1.0, ref_length: float = 1.
         _check(lib, lib.mgcfd_load_coefficients(_ptr(ff), _ptr(row), float(ref_area), float(ref_length), _ptr(res)))
         out[k] = res
     return out.reshape(rows.shape)
+
+
+WALL_COLUMNS = 7      # MGCFD_WALL_COLUMNS: ax ay az | dp | tx ty tz
+
+
+def surface_coefficients(ff17, table):
+    """Host only: ``(Cp [n], Cf [n, 3])`` of a surface distribution ``table [n, 7]`` (Solver.wall_distribution) against the far
+    field ``ff17``: ``Cp = dp / q_inf`` and the tangential friction coefficient ``Cf = (t - (t.n) n) / (|a| q_inf)`` with
+    ``n = a / |a|`` and ``q_inf = 0.5 rho |V|^2``."""
+    ff = np.asarray(ff17, dtype=np.float64).reshape(17)
+    v = ff[1:4] / ff[0]
+    q = 0.5 * ff[0] * float(v @ v)
+    if not (q > 0.0 and np.isfinite(q)):
+        raise ValueError("surface_coefficients: the far field has no positive dynamic pressure")
+    tab = np.asarray(table, dtype=np.float64).reshape(-1, WALL_COLUMNS)
+    a, dp, t = tab[:, 0:3], tab[:, 3], tab[:, 4:7]
+    area = np.sqrt((a * a).sum(axis=1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = a / area[:, None]
+        cf = (t - (t * n).sum(axis=1)[:, None] * n) / (area * q)[:, None]
+    return dp / q, cf
 
 
 def free_stream_constants(mach: float, alpha_deg: float) -> np.ndarray:
@@ -555,24 +583,48 @@ class Solver:
     def smooth(self, l: int, sweeps: int = 1):
         self._c(self.lib.mgcfd_smooth(self.handle, l, sweeps))
 
-    def run_cycles(self, cycles: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
+    def run_cycles(self, cycles: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0), friction: bool = False):
         """The RMS of every cycle; with ``loads=True`` also the level-0 surface loads at the end of every cycle:
-        ``(rms, loads[cycles, 6])`` (Fx Fy Fz Mx My Mz about ``ref_point``; mgcfd_run_cycles_loads)."""
+        ``(rms, loads[cycles, 6])`` (Fx Fy Fz Mx My Mz about ``ref_point``; mgcfd_run_cycles_loads).  With ``friction=True`` as
+        well the rows are twelve wide, the pressure six then the friction six (mgcfd_run_cycles_loads_viscous)."""
         rms = np.zeros(max(cycles, 1))
         if not loads:
             self._c(self.lib.mgcfd_run_cycles(self.handle, cycles, _ptr(rms)))
             return rms[:cycles]
-        hist = np.zeros((max(cycles, 1), 6))
+        hist = np.zeros((max(cycles, 1), 12 if friction else 6))
         ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
-        self._c(self.lib.mgcfd_run_cycles_loads(self.handle, cycles, _ptr(ref), _ptr(rms), _ptr(hist)))
+        call = self.lib.mgcfd_run_cycles_loads_viscous if friction else self.lib.mgcfd_run_cycles_loads
+        self._c(call(self.handle, cycles, _ptr(ref), _ptr(rms), _ptr(hist)))
         return rms[:cycles], hist[:cycles]
 
-    def surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0)) -> np.ndarray:
-        """Fx Fy Fz Mx My Mz: the pressure loads on level ``level``'s solid walls in its current state (mgcfd_surface_loads)."""
-        out = np.zeros(6)
+    def surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0), friction: bool = False) -> np.ndarray:
+        """Fx Fy Fz Mx My Mz: the pressure loads on level ``level``'s solid walls in its current state (mgcfd_surface_loads).
+        ``friction=True``: twelve numbers, those six and then the friction force and moment (mgcfd_surface_loads_viscous)."""
+        out = np.zeros(12 if friction else 6)
         ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
-        self._c(self.lib.mgcfd_surface_loads(self.handle, level, _ptr(ref), _ptr(out)))
+        call = self.lib.mgcfd_surface_loads_viscous if friction else self.lib.mgcfd_surface_loads
+        self._c(call(self.handle, level, _ptr(ref), _ptr(out)))
         return out
+
+    def wall_node_count(self, level: int) -> int:
+        n = _i64(0)
+        self._c(self.lib.mgcfd_wall_node_count(self.handle, level, C.byref(n)))
+        return n.value
+
+    def wall_distribution(self, level: int):
+        """``(ids [n], table [n, 7])`` of level ``level``'s wall nodes in its current state (mgcfd_wall_distribution): the original
+        ids, ascending, and per node ``ax ay az | dp | tx ty tz``.  ``surface_coefficients`` turns the table into Cp and Cf."""
+        n = self.wall_node_count(level)
+        ids, out = np.zeros(max(n, 1), dtype=np.int64), np.zeros((max(n, 1), WALL_COLUMNS))
+        self._c(self.lib.mgcfd_wall_distribution(self.handle, level, _ptr(ids), _ptr(out)))
+        return ids[:n], out[:n]
+
+    def wall_stress(self, level: int):
+        """Diagnostic: ``(ids [n], Sw [n, 12])``, the wall nodes' stresses of a viscous level's current state (mgcfd_wall_stress)."""
+        n = self.wall_node_count(level)
+        ids, out = np.zeros(max(n, 1), dtype=np.int64), np.zeros((max(n, 1), 12))
+        self._c(self.lib.mgcfd_wall_stress(self.handle, level, _ptr(ids), _ptr(out)))
+        return ids[:n], out[:n]
 
     def load_coefficients(self, loads, ref_area: float = 1.0, ref_length: float = 1.0) -> np.ndarray:
         """CD CL CS CMx CMy CMz of one loads vector, or of every row of a ``[n, 6]`` history, against this solver's far field."""
@@ -691,15 +743,18 @@ class Solver:
         """A physical step begins: Wn1 <- Wn, Wn <- variables on every level (mgcfd_dual_time_begin_step)."""
         self._c(self.lib.mgcfd_dual_time_begin_step(self.handle))
 
-    def advance(self, steps: int, cycles_per_step: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0)):
+    def advance(self, steps: int, cycles_per_step: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0), friction: bool = False):
         """``steps`` physical steps of ``begin_step`` + ``cycles_per_step`` V-cycles (mgcfd_advance): the RMS of every cycle
         ``[steps, cycles_per_step]``; with ``loads=True`` also the level-0 surface loads at the end of every physical step:
         ``(rms, loads[steps, 6])``.  An invalid state raises MgcfdError with ``.rms``, ``.loads`` (NaN from the failing cycle on)
-        and ``.step`` (the physical step it was found in)."""
+        and ``.step`` (the physical step it was found in).  ``loads=True, friction=True``: rows of twelve, the pressure six then
+        the friction six (mgcfd_advance_loads_viscous)."""
+        friction = bool(loads and friction)
         rms = np.zeros(max(steps * cycles_per_step, 1))
-        out = np.zeros((max(steps, 1), 6))
+        out = np.zeros((max(steps, 1), 12 if friction else 6))
         ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
-        rc = self.lib.mgcfd_advance(self.handle, int(steps), int(cycles_per_step), _ptr(rms), _ptr(out) if loads else None, _ptr(ref))
+        call = self.lib.mgcfd_advance_loads_viscous if friction else self.lib.mgcfd_advance
+        rc = call(self.handle, int(steps), int(cycles_per_step), _ptr(rms), _ptr(out) if loads else None, _ptr(ref))
         if rc in (4, 5, 6):
             # an invalid state: the error carries what the call filled (NaN from the failing cycle on) and the physical step
             try:
@@ -808,6 +863,13 @@ class Solver:
         under one event pair (mgcfd_bench_viscous); the viscous terms must be on for level ``l``."""
         t = C.c_double()
         self._c(self.lib.mgcfd_bench_viscous(self.handle, l, kind, launches, C.byref(t)))
+        return t.value
+
+    def bench_friction_loads(self, l: int, kind: int, launches: int) -> float:
+        """Mean GPU seconds of one launch of ``kind`` (0 the wall-stress kernel, 1 the twelve-column loads kernel, 2 the pressure
+        loads kernel) over ``launches`` back-to-back launches (mgcfd_bench_friction_loads); level ``l`` must be viscous."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_friction_loads(self.handle, l, kind, launches, C.byref(t)))
         return t.value
 
     def bench_fas(self, fine: int, kind: str, launches: int) -> float:
