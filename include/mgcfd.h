@@ -719,9 +719,9 @@ int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *
  * into fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where they are off. */
 int mgcfd_bench_viscous(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Diagnostic: the same for one of FAS multigrid's launches between `fine_level` and the level above it, behind one
- * mgcfd_fas_restrict (kind 0: k_restrict_fas, 1: the forcing launch, 2: k_time_step_fas on the coarse level, 3: the FAS
- * prolongation) and for the launches they stand beside (4: k_restrict, 5: k_time_step on the coarse level, 6: the reference's
- * prolongation, which moves the fine state: re-initialise afterwards).  MGCFD_ERR_ARG while FAS is off. */
+ * mgcfd_fas_restrict (kind 0: k_restrict_fas, 1: the forcing launch, 2: the forced update k_time_step_src<0, true> on the
+ * coarse level, 3: the FAS prolongation) and for the launches they stand beside (4: k_restrict, 5: k_time_step on the coarse
+ * level, 6: the reference's prolongation, which moves the fine state: re-initialise afterwards).  MGCFD_ERR_ARG while FAS is off. */
 int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, double *avg_seconds);
 /* The same for the indirect_rw probe (src/Kernels/indirect_rw_loop.cpp:8-78; fluxes += ..., accumulating over the
  * launches): the empirical data-movement ceiling of the flux kernel on this level's tiles. */

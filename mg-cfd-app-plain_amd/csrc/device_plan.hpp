@@ -141,7 +141,7 @@ struct ViscousStep {
     double mu = 0.0, kappa = 0.0;             // kappa = (mu * GAMMA) / ((GAMMA - 1) * prandtl), formed on the host
 };
 
-// The physical-time source of dual time stepping (kernels.hip: k_time_step_dual, k_dual_source; mgcfd_set_dual_time):
+// The physical-time source of dual time stepping (kernels.hip: k_time_step_src, k_dual_source; mgcfd_set_dual_time):
 //   src = vol * ((3 (W - Wn) - (Wn - Wn1)) / (2 dt))   order 2 (BDF2);   src = vol * ((W - Wn) / dt)   order 1 (BDF1, Wn1 not read)
 struct DualSource {
     const double *w = nullptr;                // the stage's input state W [5][stride]: what the fluxes were computed from

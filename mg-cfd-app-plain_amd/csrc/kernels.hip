@@ -2166,6 +2166,32 @@ k_indirect_rw_tile(const double *__restrict__ q, const int32_t *__restrict__ til
 }
 
 // ------------------------------------------------------------------------------------------
+// The end of a node-wise update (k_time_step, k_time_step_src): the new state stored, and on request
+//   * residuals != nullptr: last stage — residuals = variables - old_variables (validation.cpp:77-89);
+//   * check: raise the check_for_invalid_variables flag (validation.cpp:107-138),
+//     err = (smallest offending ORIGINAL cell id << 8) | code.
+// q and residuals are not declared restrict: an update in place passes the array it read as q.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void finish_update(double *q, double *residuals, int64_t stride, int64_t i, const double (&r)[5],
+                                              double rho, double mx, double my, double mz, double en,
+                                              const int32_t *__restrict__ old_of_new, unsigned long long *__restrict__ err, int check)
+{
+    store_conserved(q, stride, i, rho, mx, my, mz, en);
+    if (residuals) {
+        residuals[i] = rho - r[0]; residuals[stride + i] = mx - r[1]; residuals[2 * stride + i] = my - r[2];
+        residuals[3 * stride + i] = mz - r[3]; residuals[4 * stride + i] = en - r[4];
+    }
+    if (check) {
+        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
+        int code = 0;
+        if (!finite) code = 1;
+        else if (rho < 0.0) code = 2;
+        else if (en < 0.0) code = 3;
+        if (code) atomicMin(err, err_key(check, old_of_new[i], code));
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // time_step (cfd_loops.cpp:241-268): variables = old + sf/(RK+1-j) * fluxes ; fluxes = 0.
 // Fused options (same operations, fewer passes over memory):
 //   * partial_min != nullptr: this is the first stage after compute_step_factor's first half —
@@ -2173,9 +2199,7 @@ k_indirect_rw_tile(const double *__restrict__ q, const int32_t *__restrict__ til
 //     step_factors[i] = min_dt / volumes[i] (cfd_loops.cpp:137-156);
 //   * zero_fluxes == 0: leave fluxes[] stale; the caller treats the array as logically zero and
 //     the next flux launch overwrites it (saves the 40 B/node of zero stores);
-//   * residuals != nullptr: last stage — residuals = variables - old_variables (validation.cpp:77-89);
-//   * check: raise the check_for_invalid_variables flag (validation.cpp:107-138),
-//     err = (smallest offending ORIGINAL cell id << 8) | code.
+//   * residuals and check: finish_update.
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock)
 k_time_step(int64_t nel, int64_t stride, double rk_div, double *__restrict__ step_factors,
@@ -2196,32 +2220,18 @@ k_time_step(int64_t nel, int64_t stride, double rk_div, double *__restrict__ ste
         sf = step_factors[i];
     }
     const double factor = sf / rk_div;
-    const double r0 = old_variables[i], r1 = old_variables[stride + i], r2 = old_variables[2 * stride + i],
-                 r3 = old_variables[3 * stride + i], r4 = old_variables[4 * stride + i];
-    const double rho = r0 + factor * fluxes[i];
-    const double mx = r1 + factor * fluxes[stride + i];
-    const double my = r2 + factor * fluxes[2 * stride + i];
-    const double mz = r3 + factor * fluxes[3 * stride + i];
-    const double en = r4 + factor * fluxes[4 * stride + i];
-    store_conserved(q, stride, i, rho, mx, my, mz, en);
+    const double r[5] = {old_variables[i], old_variables[stride + i], old_variables[2 * stride + i],
+                         old_variables[3 * stride + i], old_variables[4 * stride + i]};
+    const double rho = r[0] + factor * fluxes[i];
+    const double mx = r[1] + factor * fluxes[stride + i];
+    const double my = r[2] + factor * fluxes[2 * stride + i];
+    const double mz = r[3] + factor * fluxes[3 * stride + i];
+    const double en = r[4] + factor * fluxes[4 * stride + i];
     if (zero_fluxes) {
         fluxes[i] = 0.0; fluxes[stride + i] = 0.0; fluxes[2 * stride + i] = 0.0;
         fluxes[3 * stride + i] = 0.0; fluxes[4 * stride + i] = 0.0;
     }
-    if (residuals) {
-        residuals[i] = rho - r0; residuals[stride + i] = mx - r1; residuals[2 * stride + i] = my - r2;
-        residuals[3 * stride + i] = mz - r3; residuals[4 * stride + i] = en - r4;
-    }
-    if (check) {
-        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
-        int code = 0;
-        if (!finite) code = 1;
-        else if (rho < 0.0) code = 2;
-        else if (en < 0.0) code = 3;
-        if (code) {
-            atomicMin(err, err_key(check, old_of_new[i], code));
-        }
-    }
+    finish_update(q, residuals, stride, i, r, rho, mx, my, mz, en, old_of_new, err, check);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2239,28 +2249,33 @@ __device__ __forceinline__ double dual_source(double w, double wn, double wn1, d
     return vol * ((3.0 * a - b) / (2.0 * dt));
 }
 
-// time_step with F' = F - src in place of F, in the one launch: W, Wn, Wn1 (BDF2) and the volume are read beside what
-// k_time_step reads (128 B per node more; BDF1: 88), F' exists in registers only, fluxes[] is never written and stays
-// logically zero (the lazy zero of k_time_step), the residual and check_for_invalid_variables ride along as there.  The
-// step factors are final (the sweep clamped them: k_dual_clamp).  In place: W and q are the same array, every lane reads
-// its node before it writes it, so neither pointer is declared restrict.
-template <bool BDF2>
+// time_step with F' in place of F, in the one launch (SRC: 0 no source, 1 BDF1, 2 BDF2; FORCED: FAS multigrid's forcing P, below):
+//   F' = F - src          dual time stepping;
+//   F' = F + P            a FAS-forced level;
+//   F' = (F - src) + P    both: the forcing is the last addition.
+// W, Wn, Wn1 (BDF2) and the volume are read beside what k_time_step reads (128 B per node more; BDF1: 88), P likewise (40 B),
+// F' exists in registers only, fluxes[] is never written and stays logically zero (the lazy zero of k_time_step), the residual
+// and check_for_invalid_variables ride along as there.  The step factors are final (the sweep clamped them: k_dual_clamp).
+// In place: W and q are the same array, every lane reads its node before it writes it, so neither pointer is declared restrict.
+template <int SRC, bool FORCED>
 __global__ void __launch_bounds__(kBlock)
-k_time_step_dual(int64_t nel, int64_t stride, double rk_div, const double *__restrict__ step_factors,
-                 const double *__restrict__ fluxes, const double *old_variables, double *q,
-                 const int32_t *__restrict__ old_of_new, unsigned long long *__restrict__ err, int check,
-                 double *residuals, DualSource d)
+k_time_step_src(int64_t nel, int64_t stride, double rk_div, const double *__restrict__ step_factors,
+                const double *__restrict__ fluxes, const double *__restrict__ forcing, const double *old_variables, double *q,
+                const int32_t *__restrict__ old_of_new, unsigned long long *__restrict__ err, int check,
+                double *residuals, DualSource d)
 {
     const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
     if (i >= nel) return;
     const double factor = step_factors[i] / rk_div;
-    const double vol = d.volumes[i];
+    const double vol = SRC ? d.volumes[i] : 0.0;
     double fp[5], r[5];
 #pragma unroll
     for (int v = 0; v < 5; v++) {
         const int64_t at = v * stride + i;
-        const double wn1 = BDF2 ? d.wn1[at] : 0.0;
-        fp[v] = fluxes[at] - dual_source<BDF2>(d.w[at], d.wn[at], wn1, vol, d.dt);
+        double f = fluxes[at];
+        if (SRC) f = f - dual_source<SRC == 2>(d.w[at], d.wn[at], SRC == 2 ? d.wn1[at] : 0.0, vol, d.dt);
+        if (FORCED) f = f + forcing[at];
+        fp[v] = f;
         r[v] = old_variables[at];
     }
     const double rho = r[0] + factor * fp[0];
@@ -2268,19 +2283,7 @@ k_time_step_dual(int64_t nel, int64_t stride, double rk_div, const double *__res
     const double my = r[2] + factor * fp[2];
     const double mz = r[3] + factor * fp[3];
     const double en = r[4] + factor * fp[4];
-    store_conserved(q, stride, i, rho, mx, my, mz, en);
-    if (residuals) {
-        residuals[i] = rho - r[0]; residuals[stride + i] = mx - r[1]; residuals[2 * stride + i] = my - r[2];
-        residuals[3 * stride + i] = mz - r[3]; residuals[4 * stride + i] = en - r[4];
-    }
-    if (check) {
-        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
-        int code = 0;
-        if (!finite) code = 1;
-        else if (rho < 0.0) code = 2;
-        else if (en < 0.0) code = 3;
-        if (code) atomicMin(err, err_key(check, old_of_new[i], code));
-    }
+    finish_update(q, residuals, stride, i, r, rho, mx, my, mz, en, old_of_new, err, check);
 }
 
 // ... and with residual smoothing on: fluxes = F - src for every node of the level, before the Jacobi iterations, whose
@@ -2304,50 +2307,8 @@ k_dual_source(int64_t nel, int64_t stride, double *__restrict__ fluxes, DualSour
 // FAS multigrid (no reference counterpart; INTEGRATION.md "FAS multigrid"): on a level >= 1 every stage's update takes
 // F' = R + P for R, the level's total residual (fluxes, + the JST correction, - the dual-time source), P the forcing of the
 // cycle's down leg.  The forcing is the last addition; one IEEE operation per line of the definition (include/mgcfd.h).
+// The update itself is k_time_step_src<SRC, true>, above.
 // ------------------------------------------------------------------------------------------
-// time_step with F' = F + P, or (F - src) + P beside the dual-time source (SRC: 0 none, 1 BDF1, 2 BDF2), in the one launch:
-// F' exists in registers only, fluxes[] is never written and stays logically zero, the residual and
-// check_for_invalid_variables ride along as in k_time_step_dual.  The step factors are final.  In place, as there.
-template <int SRC>
-__global__ void __launch_bounds__(kBlock)
-k_time_step_fas(int64_t nel, int64_t stride, double rk_div, const double *__restrict__ step_factors,
-                const double *__restrict__ fluxes, const double *__restrict__ forcing, const double *old_variables, double *q,
-                const int32_t *__restrict__ old_of_new, unsigned long long *__restrict__ err, int check,
-                double *residuals, DualSource d)
-{
-    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
-    if (i >= nel) return;
-    const double factor = step_factors[i] / rk_div;
-    const double vol = SRC ? d.volumes[i] : 0.0;
-    double fp[5], r[5];
-#pragma unroll
-    for (int v = 0; v < 5; v++) {
-        const int64_t at = v * stride + i;
-        double f = fluxes[at];
-        if (SRC) f = f - dual_source<SRC == 2>(d.w[at], d.wn[at], SRC == 2 ? d.wn1[at] : 0.0, vol, d.dt);
-        fp[v] = f + forcing[at];
-        r[v] = old_variables[at];
-    }
-    const double rho = r[0] + factor * fp[0];
-    const double mx = r[1] + factor * fp[1];
-    const double my = r[2] + factor * fp[2];
-    const double mz = r[3] + factor * fp[3];
-    const double en = r[4] + factor * fp[4];
-    store_conserved(q, stride, i, rho, mx, my, mz, en);
-    if (residuals) {
-        residuals[i] = rho - r[0]; residuals[stride + i] = mx - r[1]; residuals[2 * stride + i] = my - r[2];
-        residuals[3 * stride + i] = mz - r[3]; residuals[4 * stride + i] = en - r[4];
-    }
-    if (check) {
-        const bool finite = isfinite(rho) && isfinite(mx) && isfinite(my) && isfinite(mz) && isfinite(en);
-        int code = 0;
-        if (!finite) code = 1;
-        else if (rho < 0.0) code = 2;
-        else if (en < 0.0) code = 3;
-        if (code) atomicMin(err, err_key(check, old_of_new[i], code));
-    }
-}
-
 // ... and with residual smoothing on: fluxes = F' for every node of the level before the Jacobi iterations, as k_dual_source
 // (which runs first where dual time is on); n = 5 * stride, padding included (P's padding is zero).
 __global__ void __launch_bounds__(kBlock)
@@ -4076,15 +4037,17 @@ void launch_time_step(hipStream_t st, int64_t nel, int64_t stride, int j, double
                        zero_fluxes);
 }
 
-// time_step under dual time stepping: final step factors, fluxes[] left as it is (logically zero afterwards)
-void launch_time_step_dual(hipStream_t st, int64_t nel, int64_t stride, int j, const double *sf, const double *fluxes,
-                           const double *old_variables, double *q, const int32_t *old_of_new, unsigned long long *err, int check,
-                           double *residuals, const DualSource &d)
+// time_step with a source term: final step factors, fluxes[] left as it is (logically zero afterwards).  F - src where d.order
+// is 1 or 2 (0: dual time off, d otherwise unused), + P where forcing is given (a FAS-forced level); one of the two at least.
+void launch_time_step_src(hipStream_t st, int64_t nel, int64_t stride, int j, const double *sf, const double *fluxes,
+                          const double *forcing, const double *old_variables, double *q, const int32_t *old_of_new,
+                          unsigned long long *err, int check, double *residuals, const DualSource &d)
 {
     const double rk_div = double(3 + 1 - j);
-    with_bool(d.order == 2, [&](auto bdf2) {
-        hipLaunchKernelGGL((k_time_step_dual<decltype(bdf2)::value>), dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, rk_div, sf, fluxes,
-                           old_variables, q, old_of_new, err, check, residuals, d);
+    with_constant<1, 2, 3, 4, 5>(d.order + (forcing ? 3 : 0), [&](auto c) {
+        constexpr int kind = decltype(c)::value;            // SRC + 3 * FORCED
+        hipLaunchKernelGGL((k_time_step_src<kind % 3, (kind >= 3)>), dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, rk_div, sf, fluxes,
+                           forcing, old_variables, q, old_of_new, err, check, residuals, d);
     });
 }
 
@@ -4283,18 +4246,6 @@ void launch_fas_forcing(hipStream_t st, int64_t nel_coarse, int64_t stride_coars
 
 void launch_fas_add_forcing(hipStream_t st, int64_t stride, double *fluxes, const double *forcing)
 { hipLaunchKernelGGL(k_fas_add_forcing, dim3(grid_for(stride * 5)), dim3(kBlock), 0, st, stride * 5, fluxes, forcing); }
-
-// time_step on a FAS-forced level: F + P, or (F - src) + P where d.order is 1 or 2 (0: dual time off, d otherwise unused)
-void launch_time_step_fas(hipStream_t st, int64_t nel, int64_t stride, int j, const double *sf, const double *fluxes,
-                          const double *forcing, const double *old_variables, double *q, const int32_t *old_of_new,
-                          unsigned long long *err, int check, double *residuals, const DualSource &d)
-{
-    const double rk_div = double(3 + 1 - j);
-    with_constant<0, 1, 2>(d.order, [&](auto src) {
-        hipLaunchKernelGGL((k_time_step_fas<decltype(src)::value>), dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, rk_div, sf, fluxes,
-                           forcing, old_variables, q, old_of_new, err, check, residuals, d);
-    });
-}
 
 } // namespace MGCFD_KERNEL_NS
 } // namespace mgcfd

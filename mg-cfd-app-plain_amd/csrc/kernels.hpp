@@ -31,10 +31,10 @@
     void launch_viscous_clamp(hipStream_t, int64_t nel, double k0, const double *rho, const double *g, double *sf);  \
     void launch_viscous_wall(hipStream_t, int64_t n, int64_t stride, const int32_t *nodes, double *q, double *q2,    \
                              const double *old_variables, double *residuals);                                        \
-    void launch_time_step_dual(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                   \
-                               const double *fluxes, const double *old_variables, double *q,                       \
-                               const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,    \
-                               const DualSource &);                                                                 \
+    void launch_time_step_src(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                     \
+                              const double *fluxes, const double *forcing, const double *old_variables, double *q,  \
+                              const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,     \
+                              const DualSource &);                                                                   \
     void launch_dual_source(hipStream_t, int64_t nel, int64_t stride, double *fluxes, const DualSource &);           \
     void launch_dual_clamp(hipStream_t, int64_t nel, double cdt, const double *volumes, double *sf);                 \
     void launch_dual_shift(hipStream_t, int64_t n, const double *q, double *wn, double *wn1, int first);             \
@@ -86,10 +86,6 @@
     void launch_fas_forcing(hipStream_t, int64_t nel_coarse, int64_t stride_coarse, const int32_t *child_ptr,        \
                             const double *fluxes, double *forcing);                                                  \
     void launch_fas_add_forcing(hipStream_t, int64_t stride, double *fluxes, const double *forcing);                 \
-    void launch_time_step_fas(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                     \
-                              const double *fluxes, const double *forcing, const double *old_variables, double *q,  \
-                              const int32_t *old_of_new, unsigned long long *err, int check, double *residuals,     \
-                              const DualSource &);                                                                   \
     void launch_prolong_fas(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_w0,         \
                             const double *coarse_q, double *fine_q, const double *cbrt_vol, double cfl,              \
                             double *partial_min);                                                                    \
@@ -113,10 +109,9 @@ struct Launchers {
     decltype(exact::launch_residual) *residual;                      decltype(exact::launch_sumsq) *sumsq;
     decltype(exact::launch_restrict) *restrict_;                     decltype(exact::launch_prolong) *prolong;
     decltype(exact::launch_step_factor_nodal) *step_factor_nodal;    decltype(exact::launch_smooth) *smooth;
-    decltype(exact::launch_time_step_dual) *time_step_dual;          decltype(exact::launch_dual_source) *dual_source;
+    decltype(exact::launch_time_step_src) *time_step_src;            decltype(exact::launch_dual_source) *dual_source;
     decltype(exact::launch_jst_sensor) *jst_sensor;                  decltype(exact::launch_jst_dissipation) *jst_dissipation;
     decltype(exact::launch_restrict_fas) *restrict_fas;              decltype(exact::launch_prolong_fas) *prolong_fas;
-    decltype(exact::launch_time_step_fas) *time_step_fas;
     decltype(exact::launch_viscous_stress) *viscous_stress;          decltype(exact::launch_viscous_flux) *viscous_flux;
 };
 }

@@ -197,7 +197,7 @@ struct DeviceLevel {
     int32_t *visc_wall = nullptr;
     int64_t n_visc_wall = 0;
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
-    int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while dual time is on: its RMS is summed in original numbering
+    int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while ordered_rms(): its RMS is summed in original numbering (settle_rms_order)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
     double *min_dt = nullptr;            // global-min time step scalar (after the reduction)
     double *partial_min = nullptr;       // one partial minimum per step-factor workgroup
@@ -390,6 +390,15 @@ struct mgcfd_solver {
     bool fas_forced(int l) const { return fas && l >= 1; }
     // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while any of them is on
     bool ordered_rms() const { return dual_time() || jst_on(0) || fas || viscous_on(0); }
+    // What the options above allow — every one of them that is on for a level replaces its fused flux + time_step stages by
+    // standalone launches, which leave host-side flags behind (fluxes_stale) that a graph replay would not set.  The callers
+    // add what is not physics: opt_fuse, the two-phase flux variant, the indirect_rw probe, timing and the level's flux flags.
+    //   fused stages on level l: FAS forces the levels >= 1 only (level 0 sweeps as ever) ...
+    bool options_allow_fused(int l) const { return !smoothing() && !dual_time() && !jst_on(l) && !viscous_on(l) && !fas_forced(l); }
+    //   ... but no sweep is graphed on any level while it is on; JST and viscous levels count one by one
+    bool options_allow_sweep_graph(int l) const { return options_allow_fused(l) && !fas; }
+    //   a whole cycle as one graph: every level's sweep must be (JST and the viscous terms run on levels 0 .. n-1: level 0 decides)
+    bool options_allow_cycle_graph() const { return options_allow_sweep_graph(0); }
     JstStep jst_step(DeviceLevel &lv) const
     {
         JstStep a;
@@ -431,9 +440,9 @@ struct mgcfd_solver {
     {
 #define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
-                                NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_dual, NS::launch_dual_source, \
+                                NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_src, NS::launch_dual_source, \
                                 NS::launch_jst_sensor, NS::launch_jst_dissipation, NS::launch_restrict_fas, NS::launch_prolong_fas, \
-                                NS::launch_time_step_fas, NS::launch_viscous_stress, NS::launch_viscous_flux}
+                                NS::launch_viscous_stress, NS::launch_viscous_flux}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -489,6 +498,24 @@ struct mgcfd_solver {
             s->pending.push_back(std::move(p));
         }
     };
+
+    // What every mgcfd_bench_* hook measures: the mean GPU seconds of `launches` back-to-back calls of `launch` between two
+    // events on the stream.  The hook checks its arguments and does its warm-up launches first, and sets the flags its
+    // launches leave behind afterwards.
+    template <typename F>
+    double timed_launches(int launches, F &&launch)
+    {
+        Event a = get_event(), b = get_event();
+        HIP_CHECK(hipEventRecord(a.get(), stream));
+        for (int k = 0; k < launches; k++) launch();
+        HIP_CHECK(hipEventRecord(b.get(), stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
+        free_events.push_back(std::move(a));
+        free_events.push_back(std::move(b));
+        return launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+    }
 
     // ---- operations ----------------------------------------------------------------------
     void op_copy_old(int l)
@@ -743,10 +770,12 @@ struct mgcfd_solver {
         if (!old) old = lv.old_variables;
         if (!out) out = lv.q;
         if (out == lv.q) lv.min_ahead = false;
+        double *const res = with_residual ? lv.residuals : nullptr;
+        bool stale = true;                          // fluxes[] is not written unless k_time_step zeroes it: logically zero, as after a lazy time_step
+        Timed t(this, l, MGCFD_LOOP_TIME_STEP);
         if (smoothing()) {
             // the smoothing works on final step factors: finish compute_step_factor first (the same division k_time_step would do)
             // (booked where k_time_step's own division is booked: under time_step)
-            Timed t(this, l, MGCFD_LOOP_TIME_STEP);
             if (apply_min == ApplyMin::Partials) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
             if (apply_min != ApplyMin::None) op_step_factor_apply(l);
             // dual time stepping: F' = F - src into fluxes[] first, in a node-wise launch of its own — the first iteration forms
@@ -761,49 +790,30 @@ struct mgcfd_solver {
                 a.next = m == irs_iters - 1 ? nullptr : lv.smooth_buf[m & 1];
                 if (!a.next) {
                     a.rk_div = double(MGCFD_RK + 1 - j); a.old_variables = old; a.q_out = out;
-                    a.residuals = with_residual ? lv.residuals : nullptr;
+                    a.residuals = res;
                     a.old_of_new = lv.dp.old_of_new; a.err = err; a.check = next_check();
                 }
-                k().smooth(stream, lv.dp, a);
+                k().smooth(stream, lv.dp, a);       // (never zeroes fluxes[]: with one iteration other tiles still read them)
             }
-            viscous_wall(l, out, nullptr, old, with_residual ? lv.residuals : nullptr);
-            lv.fluxes_stale = true;                 // (never zeroed by these launches: with one iteration other tiles still read them)
-            lv.fluxes_zero = true;
-            lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
-            return;
-        }
-        Timed t(this, l, MGCFD_LOOP_TIME_STEP);
-        if (fas_forced(l)) {
-            // the update with F + P, or (F - src) + P, for F, in the one launch; the step factors are final (op_step_factor)
-            if (apply_min != ApplyMin::None) throw std::invalid_argument("FAS multigrid: the step factors must be final before time_step");
+        } else if (fas_forced(l) || dual_time()) {
+            // the update with F - src, F + P or (F - src) + P for F, in the one launch; the step factors are final and, under
+            // dual time, clamped (op_step_factor)
+            if (apply_min != ApplyMin::None)
+                throw std::invalid_argument(fas_forced(l) ? "FAS multigrid: the step factors must be final before time_step"
+                                                          : "dual time: the step factors must be final before time_step");
             DualSource d;
             if (dual_time()) d = dual_source(lv); else d.order = 0;
-            k().time_step_fas(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, lv.fas_p, old, out, lv.dp.old_of_new, err, next_check(),
-                              with_residual ? lv.residuals : nullptr, d);
-            viscous_wall(l, out, nullptr, old, with_residual ? lv.residuals : nullptr);
-            lv.fluxes_stale = true;                 // (never written: logically zero, as after a lazy time_step)
-            lv.fluxes_zero = true;
-            lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
-            return;
+            k().time_step_src(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, fas_forced(l) ? lv.fas_p : nullptr, old, out,
+                              lv.dp.old_of_new, err, next_check(), res, d);
+        } else {
+            const double *pm = apply_min == ApplyMin::Partials ? lv.partial_min : (apply_min == ApplyMin::Scalar ? lv.min_dt : nullptr);
+            const int n_pm = apply_min == ApplyMin::Scalar ? 1 : static_cast<int>((lv.info.nel + 255) / 256);
+            const int check = next_check();
+            k().time_step(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, check, pm, n_pm, lv.volumes, res, lazy_zero ? 0 : 1);
+            stale = lazy_zero;
         }
-        if (dual_time()) {
-            // the update with F - src for F, in the one launch; the step factors are final and clamped (op_step_factor)
-            if (apply_min != ApplyMin::None) throw std::invalid_argument("dual time: the step factors must be final before time_step");
-            k().time_step_dual(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, next_check(),
-                               with_residual ? lv.residuals : nullptr, dual_source(lv));
-            viscous_wall(l, out, nullptr, old, with_residual ? lv.residuals : nullptr);
-            lv.fluxes_stale = true;                 // (never written: logically zero, as after a lazy time_step)
-            lv.fluxes_zero = true;
-            lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
-            return;
-        }
-        const double *pm = apply_min == ApplyMin::Partials ? lv.partial_min : (apply_min == ApplyMin::Scalar ? lv.min_dt : nullptr);
-        const int n_pm = apply_min == ApplyMin::Scalar ? 1 : static_cast<int>((lv.info.nel + 255) / 256);
-        double *res = with_residual ? lv.residuals : nullptr;
-        const int check = next_check();
-        k().time_step(stream, lv.info.nel, lv.dp.stride, j, lv.step_factors, lv.fluxes, old, out, lv.dp.old_of_new, err, check, pm, n_pm, lv.volumes, res, lazy_zero ? 0 : 1);
         viscous_wall(l, out, nullptr, old, res);
-        lv.fluxes_stale = lazy_zero;
+        lv.fluxes_stale = stale;
         lv.fluxes_zero = true;
         lv.iters[MGCFD_LOOP_TIME_STEP] += lv.info.nel;
     }
@@ -818,6 +828,16 @@ struct mgcfd_solver {
         DeviceLevel &lv = level(l);
         settle_residuals(lv);
         k().sumsq(stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
+    }
+    // ... of level 0 in the order the options of ordered_rms() fix on the original numbering (mgcfd.h): per-workgroup sums of 256
+    // original nodes into tile_sumsq (no fused stage fills it while one of them is on), then their sum, appended to `ring` if given
+    void op_sumsq_ordered(double *ring = nullptr, int *count = nullptr, int cap = 0)
+    {
+        DeviceLevel &l0 = level(0);
+        if (!l0.new_of_old_dev) throw std::logic_error("the ordered RMS sum without level 0's numbering on the device");
+        settle_residuals(l0);
+        exact::launch_sumsq_original(stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
+        exact::launch_sum_partials_append(stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq, ring, count, cap);
     }
     // rms (may be null): per-tile sums of squares of the fine level that the launch adds up on the side (cycle_once)
     void op_restrict(int fine, const SumTask *rms = nullptr)
@@ -1608,6 +1628,32 @@ static void require_no_sweep_under_way(const mgcfd_solver *s, const char *what =
         if (s->L[l].stage_next != 0 || s->L[l].sweep_flux0_done)
             throw std::invalid_argument(std::string(what) + ": a sweep is under way on level " + std::to_string(l) + " (mgcfd_sweep_flux0 / mgcfd_sweep_stage): finish it first");
 }
+// How every setter of a run-time option starts: no kernel-granular sweep under way (`what` names the option in the refusal), the
+// solver idle — its stream, and as a rank its message stream and the streams a group's graph forks to — its timings folded
+// and its captured graphs gone (captured launches carry the options they were captured with as kernel arguments).
+static void quiesce(mgcfd_solver *s, const char *what)
+{
+    require_no_sweep_under_way(s, what);
+    s->use_device();
+    s->fold_events();
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    synchronize_with_group(s);
+    s->drop_graphs();
+}
+// ... and how it ends where the option changes the kind of sweep a level runs: partial_min / sf_alt hold work done ahead
+// for the other kind
+static void drop_look_ahead(mgcfd_solver *s)
+{
+    for (DeviceLevel &lv : s->L) lv.min_ahead = false;
+}
+// Level 0's numbering for the ordered RMS sum (mgcfd_solver::ordered_rms, op_sumsq_ordered) is held exactly while an option that
+// orders the sum is on: every setter of such an option calls this once its new state is stored.
+static void settle_rms_order(mgcfd_solver *s)
+{
+    DeviceLevel &l0 = s->L[0];
+    if (!s->ordered_rms()) l0.mem.release(l0.new_of_old_dev);
+    else if (!l0.new_of_old_dev) l0.new_of_old_dev = l0.mem.upload(l0.plan.new_of_old);
+}
 // The solver is idle and its graphs are gone: the new far field, and with `reinitialise` the state mgcfd_create leaves.
 static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mach, double alpha_deg, int reinitialise)
 {
@@ -1639,12 +1685,7 @@ int mgcfd_set_free_stream(mgcfd_solver *s, double mach, double alpha_deg, int re
     const int rc = mgcfd_free_stream_constants(mach, alpha_deg, ff17);
     if (rc != MGCFD_OK) return rc;
     return guarded([&] {
-        require_no_sweep_under_way(s);
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);                  // (a rank: its message stream, and the streams a group's graph forks to)
-        s->drop_graphs();
+        quiesce(s, "free stream");
         apply_free_stream(s, ff17, mach, alpha_deg, reinitialise);
     });
 }
@@ -1662,19 +1703,14 @@ static void apply_time_step(mgcfd_solver *s, int mode, double cfl)
 {
     s->dt_mode = mode;
     s->cfl = cfl;
-    for (DeviceLevel &lv : s->L) lv.min_ahead = false;          // partial_min / sf_alt hold the old policy's work
+    drop_look_ahead(s);
 }
 int mgcfd_set_time_step(mgcfd_solver *s, int mode, double cfl)
 {
     REQUIRE(s);
     return guarded([&] {
         check_time_step(mode, cfl);
-        require_no_sweep_under_way(s, "time step");
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);
-        s->drop_graphs();
+        quiesce(s, "time step");
         apply_time_step(s, mode, cfl);
     });
 }
@@ -1696,12 +1732,7 @@ int mgcfd_set_residual_smoothing(mgcfd_solver *s, double eps, int iterations)
         if (iterations > 0 && (!std::isfinite(eps) || !(eps > 0.0))) throw std::invalid_argument("residual smoothing: eps must be finite and positive");
         if (iterations > 0 && (s->partitioned || s->comm))
             throw std::invalid_argument("residual smoothing: not on a partitioned solver or a rank (a level split over ranks would need a ghost exchange per iteration)");
-        require_no_sweep_under_way(s, "residual smoothing");
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);
-        s->drop_graphs();
+        quiesce(s, "residual smoothing");
         if (iterations > 0)
             for (DeviceLevel &lv : s->L)
                 for (double *&b : lv.smooth_buf)
@@ -1729,23 +1760,17 @@ int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels)
         if (levels > 0 && !(kappa2 > 0.0) && !(kappa4 > 0.0)) throw std::invalid_argument("JST dissipation: one of kappa2 and kappa4 must be positive");
         if (levels > 0 && (s->partitioned || s->comm))
             throw std::invalid_argument("JST dissipation: not on a partitioned solver or a rank (a level split over ranks would need L, nu and r exchanged per stage)");
-        require_no_sweep_under_way(s, "JST dissipation");
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);
-        s->drop_graphs();
+        quiesce(s, "JST dissipation");
         const int n = std::min(levels, static_cast<int>(s->L.size()));
         for (int l = 0; l < n; l++) {
             DeviceLevel &lv = s->L[static_cast<size_t>(l)];
             if (!lv.jst_buf) lv.jst_buf = lv.mem.alloc<double>(static_cast<size_t>(7 * lv.dp.stride));
         }
-        if (n > 0 && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
-        if (n == 0 && !s->dual_time() && !s->fas && !s->viscous_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);
-        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->jst_levels = n;
         s->jst_kappa2 = n > 0 ? kappa2 : 0.0;
         s->jst_kappa4 = n > 0 ? kappa4 : 0.0;
+        settle_rms_order(s);
+        drop_look_ahead(s);
     });
 }
 int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *levels)
@@ -1770,12 +1795,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
             if (s->partitioned || s->comm)
                 throw std::invalid_argument("viscous terms: not on a partitioned solver or a rank (a level split over ranks would need the node stresses exchanged per stage)");
         }
-        require_no_sweep_under_way(s, "viscous terms");
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);
-        s->drop_graphs();
+        quiesce(s, "viscous terms");
         const int n = std::min(levels, static_cast<int>(s->L.size()));
         for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
             DeviceLevel &lv = s->L[static_cast<size_t>(l)];
@@ -1805,14 +1825,13 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
             lv.n_visc_wall = static_cast<int64_t>(nodes.size());
             lv.visc_wall = lv.mem.upload(nodes);
         }
-        if (n > 0 && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
-        if (n == 0 && !s->dual_time() && !s->jst_on(0) && !s->fas) s->L[0].mem.release(s->L[0].new_of_old_dev);
-        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->visc_levels = n;
         s->visc_mu = n > 0 ? mu : 0.0;
         s->visc_prandtl = n > 0 ? prandtl : 0.0;
         s->visc_cfl = n > 0 ? cfl_v : 0.0;
         s->visc_wall = n > 0 ? wall : 0;
+        settle_rms_order(s);
+        drop_look_ahead(s);
         // the no-slip condition holds from the start
         for (int l = 0; l < n; l++) {
             DeviceLevel &lv = s->L[static_cast<size_t>(l)];
@@ -1856,12 +1875,7 @@ int mgcfd_set_fas(mgcfd_solver *s, int on)
         if (on && s->L.size() < 2) throw std::invalid_argument("FAS multigrid: a one-level solver has no coarse level to force");
         if (on && (s->partitioned || s->comm))
             throw std::invalid_argument("FAS multigrid: not on a partitioned solver or a rank (a level split over ranks would need T, P and D exchanged)");
-        require_no_sweep_under_way(s, "FAS multigrid");
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);
-        s->drop_graphs();
+        quiesce(s, "FAS multigrid");
         for (size_t l = 1; l < s->L.size(); l++) {
             DeviceLevel &lv = s->L[l];
             const size_t n = static_cast<size_t>(5 * lv.dp.stride);
@@ -1874,11 +1888,10 @@ int mgcfd_set_fas(mgcfd_solver *s, int on)
                 lv.mem.release(lv.fas_w0);
             }
         }
-        if (on && !s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
-        if (!on && !s->dual_time() && !s->jst_on(0) && !s->viscous_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);
         HIP_CHECK(hipStreamSynchronize(s->stream));
-        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->fas = on != 0;
+        settle_rms_order(s);
+        drop_look_ahead(s);
     });
 }
 int mgcfd_get_fas(const mgcfd_solver *s, int *on)
@@ -1924,14 +1937,8 @@ int mgcfd_calc_rms(mgcfd_solver *s, int level, double *rms)
     return guarded([&] {
         s->use_device();
         DeviceLevel &lv = s->level(level);
-        if (s->ordered_rms() && level == 0) {
-            // the order dual time stepping and the JST dissipation fix for the level-0 sum (mgcfd.h), as the cycle driver runs it
-            s->settle_residuals(lv);
-            exact::launch_sumsq_original(s->stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.new_of_old_dev, lv.tile_sumsq);
-            exact::launch_sum_partials_append(s->stream, static_cast<int>((lv.info.nel + 255) / 256), lv.tile_sumsq, lv.sumsq, nullptr, nullptr, 0);
-        } else {
-            s->op_sumsq(level);
-        }
+        if (s->ordered_rms() && level == 0) s->op_sumsq_ordered();     // (as the cycle driver runs it)
+        else s->op_sumsq(level);
         double sum = 0.0;
         HIP_CHECK(hipMemcpyAsync(&sum, lv.sumsq, sizeof(double), hipMemcpyDeviceToHost, s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -1987,7 +1994,7 @@ static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 static void smooth_once(mgcfd_solver *s, int level)
 {
     DeviceLevel &lv = s->level(level);
-    if (s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->viscous_on(level) && !s->fas_forced(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
+    if (s->opt_fuse && s->options_allow_fused(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && s->opt_timing != 1 && lv.fluxes_zero) {
         // Fused stages: flux + time_step in one launch each.  No copy<double>(old_variables, variables)
         // (:383): the sweep's start state stays where it is and BECOMES old_variables; the stages run
         // variables -> q_alt -> (the former old_variables buffer) -> q_alt, and the three buffers
@@ -2068,7 +2075,7 @@ static void run_sweep(mgcfd_solver *s, int level)
     }
     // (only the fused launches are replayed: the unfused ones — the two-phase flux variant — leave host-side flags
     //  behind, fluxes_stale, that a replay would not set)
-    const bool graphable = s->opt_graph && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(level) && !s->viscous_on(level) && !s->fas && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
+    const bool graphable = s->opt_graph && s->opt_fuse && s->options_allow_sweep_graph(level) && !(s->variant_for(lv) & 4) && !s->opt_indirect_rw && !timed && lv.fluxes_zero && !lv.fluxes_stale;
     if (!graphable) {
         const int keep = s->opt_timing;
         if (!timed) s->opt_timing = 0;
@@ -2386,12 +2393,7 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
                 exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
                                                   s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else if (s->ordered_rms()) {
-                // dual time stepping and the JST dissipation define the order of this sum on the original numbering (mgcfd.h):
-                // per-workgroup sums of 256 original nodes into tile_sumsq (no fused stage fills it while either is on), then their sum
-                s->settle_residuals(l0);
-                exact::launch_sumsq_original(s->stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
-                exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
-                                                  s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+                s->op_sumsq_ordered(s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else {
                 s->op_sumsq(0);
                 exact::launch_append_scalar(s->stream, l0.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
@@ -2436,7 +2438,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
             Event att0, att1;
             if (s->opt_timing == 4) { att0 = s->get_event(); att1 = s->get_event(); HIP_CHECK(hipEventRecord(att0.get(), s->stream)); }
-            bool graphable = s->opt_graph && !friction && s->opt_fuse && !s->smoothing() && !s->dual_time() && !s->jst_on(0) && !s->viscous_on(0) && !s->fas && !s->opt_indirect_rw && s->opt_timing == 0;
+            bool graphable = s->opt_graph && !friction && s->opt_fuse && s->options_allow_cycle_graph() && !s->opt_indirect_rw && s->opt_timing == 0;
             for (auto &lv : s->L) graphable = graphable && lv.fluxes_zero && !lv.fluxes_stale && !(s->variant_for(lv) & 4);
             graphable = graphable && nl <= 8;               // the graph key holds 8 levels' buffer rotations
             if (graphable) {
@@ -2810,7 +2812,6 @@ int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_secon
     return guarded([&] {
         s->use_device();
         DeviceLevel &lv = s->level(level);
-        Event a = s->get_event(), b = s->get_event();
         const int variant = s->variant_for(lv);
         if ((variant & 4) && !lv.dp.edge_flux)
             lv.dp.edge_flux = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
@@ -2818,16 +2819,8 @@ int mgcfd_bench_flux(mgcfd_solver *s, int level, int launches, double *avg_secon
             s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, variant, nullptr, nullptr);
         };
         go();
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) go();
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        *avg_seconds = s->timed_launches(launches, go);
         lv.fluxes_zero = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
@@ -2842,7 +2835,6 @@ int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int lau
         DeviceLevel &lv = s->level(level);
         if (!s->smoothing()) throw std::invalid_argument("residual smoothing is off: switch it on first (mgcfd_set_residual_smoothing)");
         if (kind < 0 || kind > 2) throw std::invalid_argument("residual smoothing launch kind: 0 first, 1 middle, 2 last");
-        Event a = s->get_event(), b = s->get_event();
         s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
         SmoothStep st;
         st.fluxes = lv.fluxes; st.step_factors = lv.step_factors; st.eps = s->irs_eps;
@@ -2851,17 +2843,9 @@ int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int lau
         if (kind >= 1) st.prev = lv.smooth_buf[0];
         st.next = kind == 1 ? lv.smooth_buf[1] : (kind == 0 ? lv.smooth_buf[0] : nullptr);
         if (kind == 2) { st.rk_div = double(MGCFD_RK + 1); st.old_variables = lv.q; st.q_out = lv.q_alt; st.old_of_new = lv.dp.old_of_new; st.err = s->err; }
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) s->k().smooth(s->stream, lv.dp, st);
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        *avg_seconds = s->timed_launches(launches, [&] { s->k().smooth(s->stream, lv.dp, st); });
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
@@ -2875,25 +2859,16 @@ int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *
         DeviceLevel &lv = s->level(level);
         if (!s->jst_on(level)) throw std::invalid_argument("the JST dissipation is off on this level: switch it on first (mgcfd_set_jst)");
         if (kind < 0 || kind > 1) throw std::invalid_argument("JST launch kind: 0 sensor, 1 dissipation");
-        Event a = s->get_event(), b = s->get_event();
         s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
         const JstStep st = s->jst_step(lv);
         s->k().jst_sensor(s->stream, lv.dp, st);
         s->k().jst_dissipation(s->stream, lv.dp, st);
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) {
+        *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) s->k().jst_sensor(s->stream, lv.dp, st);
             else s->k().jst_dissipation(s->stream, lv.dp, st);
-        }
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        });
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
@@ -2907,31 +2882,22 @@ int mgcfd_bench_viscous(mgcfd_solver *s, int level, int kind, int launches, doub
         DeviceLevel &lv = s->level(level);
         if (!s->viscous_on(level)) throw std::invalid_argument("the viscous terms are off on this level: switch them on first (mgcfd_set_viscous)");
         if (kind < 0 || kind > 1) throw std::invalid_argument("viscous launch kind: 0 stress, 1 viscous flux");
-        Event a = s->get_event(), b = s->get_event();
         s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
         const ViscousStep st = s->viscous_step(lv);
         s->k().viscous_stress(s->stream, lv.dp, st);
         s->k().viscous_flux(s->stream, lv.dp, st);
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) {
+        *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) s->k().viscous_stress(s->stream, lv.dp, st);
             else s->k().viscous_flux(s->stream, lv.dp, st);
-        }
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        });
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
 // ... and for one of FAS multigrid's launches between levels `fine_level` and `fine_level + 1`, behind one mgcfd_fas_restrict
 // (so that W0 equals the coarse state and the correction the prolongation interpolates is zero): kind 0 k_restrict_fas, 1 the
-// forcing launch, 2 k_time_step_fas on the coarse level (into the second state buffer, unchecked: the state stays), 3 the FAS
+// forcing launch, 2 k_time_step_src<0, true> on the coarse level (into the second state buffer, unchecked: the state stays), 3 the FAS
 // prolongation; and the launches they stand beside: 4 k_restrict, 5 k_time_step on the coarse level (likewise), 6 the
 // reference's prolongation (which moves the fine state launch after launch: re-initialise afterwards).
 int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, double *avg_seconds)
@@ -2946,14 +2912,12 @@ int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, dou
         s->settle_residuals(F);
         DualSource none;
         none.order = 0;
-        Event a = s->get_event(), b = s->get_event();
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) {
+        *avg_seconds = s->timed_launches(launches, [&] {
             switch (kind) {
                 case 0: s->k().restrict_fas(s->stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
                                             fine_level >= 1 ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p); break;
                 case 1: exact::launch_fas_forcing(s->stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p); break;
-                case 2: s->k().time_step_fas(s->stream, C.info.nel, C.dp.stride, 0, C.step_factors, C.fluxes, C.fas_p, C.q, C.q_alt, C.dp.old_of_new,
+                case 2: s->k().time_step_src(s->stream, C.info.nel, C.dp.stride, 0, C.step_factors, C.fluxes, C.fas_p, C.q, C.q_alt, C.dp.old_of_new,
                                              s->err, 0, nullptr, none); break;
                 case 3: s->k().prolong_fas(s->stream, F.dp, C.dp.stride, C.fas_w0, C.q, F.q, F.cbrt_vol, s->cfl, nullptr); break;
                 case 4: s->k().restrict_(s->stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol,
@@ -2962,16 +2926,9 @@ int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, dou
                                          nullptr, 0, C.volumes, nullptr, 0); break;
                 default: s->k().prolong(s->stream, F.dp, C.dp.stride, C.residuals, F.residuals, F.q, F.cbrt_vol, s->cfl, nullptr); break;
             }
-        }
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        });
         F.min_ahead = false;
         C.min_ahead = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
@@ -2984,22 +2941,13 @@ int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *av
         s->use_device();
         DeviceLevel &lv = s->level(level);
         s->settle_fluxes(lv);
-        Event a = s->get_event(), b = s->get_event();
         const int variant = s->variant_for(lv);
         auto go = [&] {
             s->k().indirect_rw(s->stream, lv.dp, lv.q, lv.fluxes, variant);
         };
         go();
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) go();
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        *avg_seconds = s->timed_launches(launches, go);
         lv.fluxes_zero = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
@@ -3017,19 +2965,10 @@ int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double 
         DeviceOwner scratch;
         double *src = scratch.alloc<double>(static_cast<size_t>(rd_total) + 512);
         HIP_CHECK(hipMemsetAsync(src, 0, (static_cast<size_t>(rd_total) + 512) * sizeof(double), s->stream));
-        Event a = s->get_event(), b = s->get_event();
         auto go = [&] { exact::launch_stream_tiles(s->stream, lv.dp.n_tiles, src, lv.fluxes, rd_total, wr_total); };
         go();
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) go();
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
+        *avg_seconds = s->timed_launches(launches, go);
         lv.fluxes_zero = false;
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
     });
 }
 
@@ -5247,21 +5186,12 @@ int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launche
         if (lv.n_wall_rec == 0) throw std::invalid_argument("the level has no solid-wall edge");
         loads_prepare(s, nullptr);
         wall_plan(s, lv);
-        Event a = s->get_event(), b = s->get_event();
         launch_loads_viscous(s, level, s->loads_dev + 3);
-        HIP_CHECK(hipEventRecord(a.get(), s->stream));
-        for (int k = 0; k < launches; k++) {
+        *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) launch_wall_stress(s, level);
             else if (kind == 1) launch_loads_twelve(s, level, s->loads_dev + 3);
             else launch_loads(s, lv, false);
-        }
-        HIP_CHECK(hipEventRecord(b.get(), s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, a.get(), b.get()));
-        s->free_events.push_back(std::move(a));
-        s->free_events.push_back(std::move(b));
-        *avg_seconds = launches > 0 ? double(ms) * 1e-3 / launches : 0.0;
+        });
     });
 }
 
@@ -5303,12 +5233,7 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         if (on && (!std::isfinite(clamp) || !(clamp > 0.0))) throw std::invalid_argument("dual time: the clamp must be finite and positive");
         if (on && (s->partitioned || s->comm))
             throw std::invalid_argument("dual time: not on a partitioned solver or a rank (levels split over ranks are out of scope)");
-        require_no_sweep_under_way(s, "dual time");
-        s->use_device();
-        s->fold_events();
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        synchronize_with_group(s);
-        s->drop_graphs();
+        quiesce(s, "dual time");
         if (on && !s->dual_time()) {
             // switched on: both levels start as the current state (sweeps before the first begin_step see BDF1 against it)
             for (DeviceLevel &lv : s->L) {
@@ -5316,7 +5241,6 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
                 if (!lv.time_n) lv.time_n = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
                 if (!lv.time_n1) lv.time_n1 = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
             }
-            if (!s->L[0].new_of_old_dev) s->L[0].new_of_old_dev = s->L[0].mem.upload(s->L[0].plan.new_of_old);
             for (DeviceLevel &lv : s->L) exact::launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, 1);
             HIP_CHECK(hipStreamSynchronize(s->stream));
             HIP_CHECK(hipGetLastError());
@@ -5325,12 +5249,12 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         }
         if (!on) {
             for (DeviceLevel &lv : s->L) { lv.mem.release(lv.time_n); lv.mem.release(lv.time_n1); lv.flux_in = nullptr; }
-            if (!s->jst_on(0) && !s->fas && !s->viscous_on(0)) s->L[0].mem.release(s->L[0].new_of_old_dev);        // (the JST dissipation and FAS order the RMS the same way)
             s->dual_levels = 0;
         }
-        for (DeviceLevel &lv : s->L) lv.min_ahead = false;      // (work done ahead belongs to the other kind of sweep)
         s->dual_dt = dt;
         s->dual_clamp = on ? clamp : 0.0;
+        settle_rms_order(s);
+        drop_look_ahead(s);
     });
 }
 int mgcfd_get_dual_time(const mgcfd_solver *s, double *dt, double *clamp, int *order, int *levels, int *invalid_step)

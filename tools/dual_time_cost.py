@@ -2,9 +2,9 @@
 """What dual time stepping (mgcfd_set_dual_time) costs on the bench level (bench.py's 67^3 lattice, 300,763 nodes) and on the
 4-level hierarchy of bench.py's V-cycle:
 
-  * the time_step launch, dual time on (k_time_step_dual, BDF2) against off (k_time_step), each bracketed by its own event
-    pair inside unfused sweeps (MGCFD_OPT_TIMING = 1, MGCFD_OPT_FUSE_UPDATE = 0): the same bracket on both, so the difference
-    is the kernels';
+  * the time_step launch, dual time on (k_time_step_src<2, false>: BDF2) against off (k_time_step), each bracketed by its own
+    event pair inside unfused sweeps (MGCFD_OPT_TIMING = 1, MGCFD_OPT_FUSE_UPDATE = 0): the same bracket on both, so the
+    difference is the kernels';
   * time per sweep and per V-cycle, dual time on against off, without and with residual smoothing (0.5, 2).  "off" is what a
     caller gets by default (fused stages); "off, unfused" runs the launches dual time replaces one for one.
 
@@ -88,7 +88,7 @@ def main():
             s.set_option("timing", 0)
         per_launch[dual] = statistics.median(v)
     lines.append(f"  time_step launch, dual time off   {1e6 * per_launch[False]:8.2f} us   (k_time_step, one event pair per launch, 300 launches)")
-    lines.append(f"  time_step launch, dual time on    {1e6 * per_launch[True]:8.2f} us   (k_time_step_dual, the same way)")
+    lines.append(f"  time_step launch, dual time on    {1e6 * per_launch[True]:8.2f} us   (k_time_step_src<2, false>, the same way)")
     lines.append(f"  ratio                             {per_launch[True] / per_launch[False]:8.2f}")
     t = alternated(s, settings, lambda n: s.smooth(0, n), a.sweeps, a.warmup, a.batches, a.dt)
     for k, name in zip(settings, names):

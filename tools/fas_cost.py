@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """What FAS multigrid (mgcfd_set_fas) costs on the 4-level hierarchy of bench.py's V-cycle (67^3 / 55^3 / 48^3 / 43^3):
 
-  * per level pair: time per k_restrict_fas, forcing, k_time_step_fas and FAS prolongation launch, each as back-to-back
-    launches under one event pair (mgcfd_bench_fas), beside k_restrict, k_time_step and the reference's prolongation between the
-    same levels, measured the same way in the same process, with the spread (min .. max) of the repeats and the bytes each
-    launch moves (algorithmic: what it must read and write once, ids included);
+  * per level pair: time per k_restrict_fas, forcing, forced update (k_time_step_src<0, true>) and FAS prolongation launch, each
+    as back-to-back launches under one event pair (mgcfd_bench_fas), beside k_restrict, k_time_step and the reference's
+    prolongation between the same levels, measured the same way in the same process, with the spread (min .. max) of the
+    repeats and the bytes each launch moves (algorithmic: what it must read and write once, ids included);
   * time per V-cycle with FAS on and off, plain and with residual smoothing (0.5, 2), and the cost ratios.
 
 The method of tools/jst_cost.py: clocks warm (a warm-up batch before every measurement), many launches per measurement (one event
