@@ -472,10 +472,65 @@ int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *le
  * run the cycle above.  mgcfd_fas_restrict(s, fine) does down-leg steps 1-4 (both levels' fluxes must be zero, as after
  * time_step), mgcfd_fas_prolong(s, fine) up-leg steps 1-2; MGCFD_ERR_ARG while FAS is off.  LoopNumIters: the extra residual
  * evaluations count, and are timed, as MGCFD_LOOP_FLUX; restrict and prolong count as before.
- * Out of scope: levels split over ranks or GPUs; captured graphs with FAS on; a fused flux + forced-update stage; W-cycles and
- * sweep counts per level; a volume-weighted state restriction. */
+ * Out of scope: levels split over ranks or GPUs; captured graphs with FAS on; a fused flux + forced-update stage; a
+ * volume-weighted state restriction.  (W- and F-cycles and sweep counts per level: mgcfd_set_cycle, below.) */
 int mgcfd_set_fas(mgcfd_solver *s, int on);
 int mgcfd_get_fas(const mgcfd_solver *s, int *on);
+/* The multigrid cycle: its shape (V, W or F), the sweeps per level before the down leg (pre) and after the up leg (post), cycles
+ * that start from a coarser level, the interpolation of a coarse state onto the next finer level, and a full-multigrid (FMG)
+ * start built from them.  Per solver; everything is off by default, and a solver on which none of these calls is made launches
+ * what it launched and computes the bits it computed.  n is the number of levels.  One cycle is visit(0, shape):
+ *   visit(l, kind):
+ *     pre[l] times: sweep(l)          l == 0: the cycle's RMS is taken after the LAST of these, defined as without this call
+ *     if l == n-1: return
+ *     down(l)                         mgcfd_restrict(l); with FAS on, the down leg from l (steps 1-4 above)
+ *     visit(l+1, kind)
+ *     if l+1 < n-1:                   the coarsest level is visited once per down leg
+ *       kind == W: visit(l+1, W);     kind == F: visit(l+1, V)
+ *     up(l)                           mgcfd_prolong(l); with FAS on, the up leg onto l (steps 1-2 above)
+ *     post[l] times: sweep(l)
+ *   A second visit of l+1 works on the same coarse problem: P_{l+1} and W0_{l+1} of the one down(l) stay, its own down(l+1)
+ *   forms P_{l+2} and W0_{l+2} anew.  sweep, down, up, forced stages and step factors are the operations defined above on the
+ *   arrays as they stand (dual-time source and clamp, JST, viscous terms and the wall launch included); with the reference's
+ *   transfers up(l) prolongs whatever residuals[l+1] the last sweep there left.  With three levels F and W are the same cycle.
+ * Defaults: shape V, pre[l] = 1, post[0] = 0, post[l] = 1 for 0 < l < n-1; post[n-1] is ignored (mgcfd_get_cycle reports 1 for
+ * it, 0 on a one-level solver).  That is the reference's cycle launch for launch, and while the configuration equals it fused
+ * stages, the step-factor look-ahead, captured graphs and the RMS folded into the first restriction stay as they are.  With any
+ * other configuration MGCFD_OPT_GRAPH is accepted and the launches run directly; the look-ahead is used exactly where the launch
+ * that wrote a level's current state left its minima behind.  mgcfd_run_cycles, mgcfd_run_cycles_loads[_viscous] and
+ * mgcfd_advance[_loads_viscous] run the configured cycle; loads are those of the state after the post[0] sweeps; one RMS per cycle.
+ * mgcfd_set_cycle(s, shape, pre, post): pre and post hold n entries each, NULL = the defaults.  It synchronises, drops every
+ * captured graph and allocates nothing.  MGCFD_ERR_ARG, and nothing changed: an unknown shape; pre[l] outside
+ * 1..MGCFD_MAX_CYCLE_SWEEPS; post[l] outside 0..MGCFD_MAX_CYCLE_SWEEPS; while a kernel-granular sweep is under way; a non-default
+ * configuration on a solver made by mgcfd_create_partitioned* or attached to a group or as a rank.  mgcfd_group_create and
+ * mgcfd_rank_attach_* refuse a solver with a non-default cycle.  mgcfd_get_cycle: any pointer may be NULL.
+ * mgcfd_run_cycles_from(s, top, cycles, rms_out) runs visit(top, shape) `cycles` times with level `top` in level 0's part; the
+ * levels below `top` are untouched.  With FAS on `top` is unforced: its stages take R_top(W) without P_top, down(top) step 1 uses
+ * T = R_top, and the stored P_top is neither read nor written.  rms_out[c] = sqrt(S / nel_top), S summed in dual time stepping's
+ * fixed order (above) over level top's ORIGINAL numbering whatever the other settings are; that numbering is uploaded at the
+ * first such call and goes with the solver.  top = 0 is mgcfd_run_cycles, with its own RMS rule.  MGCFD_ERR_ARG for top > 0:
+ * while dual time is on, beyond MGCFD_MAX_ADVANCE_CYCLES cycles, on a partitioned or attached solver.  An invalid state is
+ * reported as by mgcfd_run_cycles.
+ * mgcfd_prolong_state(s, fine): for every node i of level `fine` and component v
+ *     variables[fine][i][v] = 0.0 - (0.0 - wavg_i(variables[fine+1])[v])
+ * with wavg_i exactly what mgcfd_prolong and FAS's up leg form (entries, order, weights, the division by the weight sum, the
+ * coincident-node rule and the b-end quirk); the two subtractions only turn a -0.0 into +0.0.  The fine state is written, never
+ * read; `residuals` of both levels are untouched; on a viscous level with wall = 1 the wall launch follows.  Timed and counted as
+ * MGCFD_LOOP_PROLONG.  MGCFD_ERR_ARG on a partitioned or attached solver.
+ * mgcfd_full_multigrid(s, cycles, rms_out): mgcfd_restrict(l) for l = 0 .. n-2 (the state only, no sweeps), then for
+ * top = n-1 .. 1: mgcfd_run_cycles_from(top, cycles[top]) followed by mgcfd_prolong_state(top - 1).  cycles holds n entries,
+ * cycles[0] is ignored; rms_out (may be NULL) receives the concatenated histories.  MGCFD_ERR_ARG, and nothing changed: while
+ * dual time is on, on a partitioned or attached solver, a cycles[l] outside 0..MGCFD_MAX_ADVANCE_CYCLES, while a kernel-granular
+ * sweep is under way.  An invalid state stops it there and is returned.  The level-0 cycles are the caller's next call.
+ * Out of scope: split levels and groups; captured graphs of shaped cycles; FMG under dual time; a volume-weighted or
+ * higher-order state interpolation; per-level CFL numbers. */
+enum { MGCFD_CYCLE_V = 0, MGCFD_CYCLE_W = 1, MGCFD_CYCLE_F = 2 };
+#define MGCFD_MAX_CYCLE_SWEEPS 8
+int mgcfd_set_cycle(mgcfd_solver *s, int shape, const int *pre, const int *post);
+int mgcfd_get_cycle(const mgcfd_solver *s, int *shape, int *pre, int *post);
+int mgcfd_run_cycles_from(mgcfd_solver *s, int top, int cycles, double *rms_out);
+int mgcfd_prolong_state(mgcfd_solver *s, int fine_level);
+int mgcfd_full_multigrid(mgcfd_solver *s, const int *cycles, double *rms_out);
 /* Laminar viscous terms: the Navier-Stokes stresses, heat conduction and a no-slip wall.  No reference counterpart.  Per solver:
  * mu > 0 (dynamic viscosity in the solver's units, constant: no Sutherland law), prandtl > 0, wall (0 = slip, as without the
  * feature; 1 = no-slip, adiabatic), cfl_v > 0 (the viscous step limit, (c)) and levels >= 0: it runs on levels 0 .. levels-1

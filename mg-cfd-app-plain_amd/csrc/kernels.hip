@@ -3582,21 +3582,31 @@ k_restrict_fas(int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, c
 // FAS (the up leg of a FAS cycle): what is interpolated is D = W0 - W, the coarse level's start state minus its current one,
 // formed as the coarse value is loaded (`coarse_residuals` is W0, `coarse_q` is W), and the fine residual's place is taken by
 // +0.0: variables += 0.0 - wavg(D).  Same entries, order, weights and quirks.
-template <bool FAS>
+// STATE (mgcfd_prolong_state): what is interpolated is the coarse STATE itself (`coarse_residuals` is variables[fine + 1]) and
+// the fine node's own state and residual are not read at all: variables = 0.0 - (0.0 - wavg), which only turns a -0.0 into +0.0.
+enum { kProResiduals = 0, kProFas = 1, kProState = 2 };
+template <int MODE>
 __device__ __forceinline__ double pro_coarse(const double *__restrict__ coarse_residuals, const double *__restrict__ coarse_q, int64_t at)
 {
-    return FAS ? coarse_residuals[at] - coarse_q[at] : coarse_residuals[at];
+    return MODE == kProFas ? coarse_residuals[at] - coarse_q[at] : coarse_residuals[at];
+}
+// the fine node's new value: q + (f - wavg), or in the STATE mode 0.0 - (0.0 - wavg)
+template <int MODE>
+__device__ __forceinline__ double pro_result(double q, double f, double wavg)
+{
+    return MODE == kProState ? 0.0 - (0.0 - wavg) : q + (f - wavg);
 }
 
-template <bool FAS>
+template <int MODE>
 __global__ void __launch_bounds__(kBlock)
 k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__restrict__ slice_row0,
           const int32_t *__restrict__ rows_int, const double *__restrict__ pro_w, const int32_t *__restrict__ pro_p,
           const int32_t *__restrict__ pro_parent, const double *__restrict__ pro_wsum,
-          const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals /* not FAS */,
+          const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals /* the reference's mode only */,
           double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl,
           double *__restrict__ partial_min /* nullptr, or: look ahead as in k_restrict */, const double *__restrict__ coarse_q /* FAS only */)
 {
+    constexpr bool STATE = MODE == kProState, NO_F = MODE != kProResiduals;       // (only the reference's prolongation reads fine residuals)
     const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
@@ -3611,16 +3621,16 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
     const int32_t parent = pro_parent[ii];
     const int64_t sc = stride_coarse;
     // this node's own state and residual: needed at the end, requested now
-    const double q0 = fine_q[ii], q1 = fine_q[stride + ii], q2 = fine_q[2 * stride + ii], q3 = fine_q[3 * stride + ii],
-                 q4 = fine_q[4 * stride + ii];
-    const double f0 = FAS ? 0.0 : fine_residuals[ii], f1 = FAS ? 0.0 : fine_residuals[stride + ii], f2 = FAS ? 0.0 : fine_residuals[2 * stride + ii],
-                 f3 = FAS ? 0.0 : fine_residuals[3 * stride + ii], f4 = FAS ? 0.0 : fine_residuals[4 * stride + ii];
+    const double q0 = STATE ? 0.0 : fine_q[ii], q1 = STATE ? 0.0 : fine_q[stride + ii], q2 = STATE ? 0.0 : fine_q[2 * stride + ii],
+                 q3 = STATE ? 0.0 : fine_q[3 * stride + ii], q4 = STATE ? 0.0 : fine_q[4 * stride + ii];
+    const double f0 = NO_F ? 0.0 : fine_residuals[ii], f1 = NO_F ? 0.0 : fine_residuals[stride + ii], f2 = NO_F ? 0.0 : fine_residuals[2 * stride + ii],
+                 f3 = NO_F ? 0.0 : fine_residuals[3 * stride + ii], f4 = NO_F ? 0.0 : fine_residuals[4 * stride + ii];
     const double ws = pro_wsum[ii];
     // The node's own parent appears in every entry (and, through the reference's b1-for-a1 quirk,
     // as BOTH terms of every entry in which this node is the edge's 'b' end): fetch it once.
     const int64_t own = parent < 0 ? int64_t(~parent) : int64_t(parent);
-    const double o0 = pro_coarse<FAS>(coarse_residuals, coarse_q, own), o1 = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + own), o2 = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + own),
-                 o3 = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + own), o4 = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + own);
+    const double o0 = pro_coarse<MODE>(coarse_residuals, coarse_q, own), o1 = pro_coarse<MODE>(coarse_residuals, coarse_q, sc + own), o2 = pro_coarse<MODE>(coarse_residuals, coarse_q, 2 * sc + own),
+                 o3 = pro_coarse<MODE>(coarse_residuals, coarse_q, 3 * sc + own), o4 = pro_coarse<MODE>(coarse_residuals, coarse_q, 4 * sc + own);
     double r0, r1, r2, r3, r4;
     if (parent < 0) {
         r0 = o0; r1 = o1; r2 = o2; r3 = o3; r4 = o4;
@@ -3637,19 +3647,19 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
             double x0 = o0, x1 = o1, x2 = o2, x3 = o3, x4 = o4;
             if (p_other != parent) {                                   // the other end's parent: gather
                 const int64_t px = p_other;
-                x0 = pro_coarse<FAS>(coarse_residuals, coarse_q, px); x1 = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + px); x2 = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + px);
-                x3 = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + px); x4 = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + px);
+                x0 = pro_coarse<MODE>(coarse_residuals, coarse_q, px); x1 = pro_coarse<MODE>(coarse_residuals, coarse_q, sc + px); x2 = pro_coarse<MODE>(coarse_residuals, coarse_q, 2 * sc + px);
+                x3 = pro_coarse<MODE>(coarse_residuals, coarse_q, 3 * sc + px); x4 = pro_coarse<MODE>(coarse_residuals, coarse_q, 4 * sc + px);
             }
             r0 += w_other * x0; r1 += w_other * x1; r2 += w_other * x2; r3 += w_other * x3; r4 += w_other * x4;
         }
     }
     double sf = __longlong_as_double(0x7FF0000000000000LL);          // +inf
     if (active) {
-        const double n0 = q0 + (f0 - r0 / ws);
-        const double n1 = q1 + (f1 - r1 / ws);
-        const double n2 = q2 + (f2 - r2 / ws);
-        const double n3 = q3 + (f3 - r3 / ws);
-        const double n4 = q4 + (f4 - r4 / ws);
+        const double n0 = pro_result<MODE>(q0, f0, r0 / ws);
+        const double n1 = pro_result<MODE>(q1, f1, r1 / ws);
+        const double n2 = pro_result<MODE>(q2, f2, r2 / ws);
+        const double n3 = pro_result<MODE>(q3, f3, r3 / ws);
+        const double n4 = pro_result<MODE>(q4, f4, r4 / ws);
         store_conserved(fine_q, stride, i, n0, n1, n2, n3, n4);
         if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[i], cfl);
     }
@@ -3662,17 +3672,18 @@ k_prolong(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__r
 // hundred) are read from HBM once, 40 bytes each, and every entry then finds them in LDS instead
 // of gathering five scattered doubles through L1.  Same entries, same order, same arithmetic.
 // ------------------------------------------------------------------------------------------
-template <bool FAS>
+template <int MODE>
 __global__ void __launch_bounds__(kBlock)
 k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t *__restrict__ slice_row0,
                const int32_t *__restrict__ rows_int, const double *__restrict__ pro_w,
                const uint16_t *__restrict__ pro_s16, const uint16_t *__restrict__ pro_own16,
                const int32_t *__restrict__ pro_tile_n, const int32_t *__restrict__ pro_tile_ids,
                const int32_t *__restrict__ pro_parent, const double *__restrict__ pro_wsum,
-               const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals /* not FAS */,
+               const double *__restrict__ coarse_residuals, const double *__restrict__ fine_residuals /* the reference's mode only */,
                double *__restrict__ fine_q, const double *__restrict__ cbrt_vol, double cfl, double *__restrict__ partial_min,
                const double *__restrict__ coarse_q /* FAS only */)
 {
+    constexpr bool STATE = MODE == kProState, NO_F = MODE != kProResiduals;       // (only the reference's prolongation reads fine residuals)
     __shared__ double cr[kProCap * 5];
     const unsigned t = xcd_contiguous_block(blockIdx.x, gridDim.x);   // neighbouring tiles (they share coarse parents) on one XCD's L2
     const int tid = threadIdx.x;
@@ -3695,10 +3706,10 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
     const int32_t n_int = wave_live ? rows_int[slice] : 0;
     const int32_t parent = pro_parent[ii];
     const uint32_t own_slot = pro_own16[ii];
-    const double q0 = fine_q[ii], q1 = fine_q[stride + ii], q2 = fine_q[2 * stride + ii], q3 = fine_q[3 * stride + ii],
-                 q4 = fine_q[4 * stride + ii];
-    const double f0 = FAS ? 0.0 : fine_residuals[ii], f1 = FAS ? 0.0 : fine_residuals[stride + ii], f2 = FAS ? 0.0 : fine_residuals[2 * stride + ii],
-                 f3 = FAS ? 0.0 : fine_residuals[3 * stride + ii], f4 = FAS ? 0.0 : fine_residuals[4 * stride + ii];
+    const double q0 = STATE ? 0.0 : fine_q[ii], q1 = STATE ? 0.0 : fine_q[stride + ii], q2 = STATE ? 0.0 : fine_q[2 * stride + ii],
+                 q3 = STATE ? 0.0 : fine_q[3 * stride + ii], q4 = STATE ? 0.0 : fine_q[4 * stride + ii];
+    const double f0 = NO_F ? 0.0 : fine_residuals[ii], f1 = NO_F ? 0.0 : fine_residuals[stride + ii], f2 = NO_F ? 0.0 : fine_residuals[2 * stride + ii],
+                 f3 = NO_F ? 0.0 : fine_residuals[3 * stride + ii], f4 = NO_F ? 0.0 : fine_residuals[4 * stride + ii];
     const double ws = pro_wsum[ii];
     // the first row pair's entries go out before the staging barrier too (they do not depend on the staged residuals)
     const double *wr = pro_w + (int64_t(row0) << 7) + lane;
@@ -3708,14 +3719,14 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
     {
         // (a thread without a staged node of its own gathers node 0 and stores nothing: the load is never conditional)
         const int64_t c = c_first >= 0 ? c_first : 0;
-        const double d0 = pro_coarse<FAS>(coarse_residuals, coarse_q, c), d1 = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + c), d2 = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + c),
-                     d3 = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + c), d4 = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + c);
+        const double d0 = pro_coarse<MODE>(coarse_residuals, coarse_q, c), d1 = pro_coarse<MODE>(coarse_residuals, coarse_q, sc + c), d2 = pro_coarse<MODE>(coarse_residuals, coarse_q, 2 * sc + c),
+                     d3 = pro_coarse<MODE>(coarse_residuals, coarse_q, 3 * sc + c), d4 = pro_coarse<MODE>(coarse_residuals, coarse_q, 4 * sc + c);
         if (tid < n_ids) { double *d = cr + tid * 5; d[0] = d0; d[1] = d1; d[2] = d2; d[3] = d3; d[4] = d4; }
         for (int32_t k = tid + kBlock; k < n_ids; k += kBlock) {        // (a tile that refers to more than 256 coarse nodes: rare)
             const int64_t c2 = ids[k];
             double *d = cr + k * 5;
-            d[0] = pro_coarse<FAS>(coarse_residuals, coarse_q, c2); d[1] = pro_coarse<FAS>(coarse_residuals, coarse_q, sc + c2); d[2] = pro_coarse<FAS>(coarse_residuals, coarse_q, 2 * sc + c2);
-            d[3] = pro_coarse<FAS>(coarse_residuals, coarse_q, 3 * sc + c2); d[4] = pro_coarse<FAS>(coarse_residuals, coarse_q, 4 * sc + c2);
+            d[0] = pro_coarse<MODE>(coarse_residuals, coarse_q, c2); d[1] = pro_coarse<MODE>(coarse_residuals, coarse_q, sc + c2); d[2] = pro_coarse<MODE>(coarse_residuals, coarse_q, 2 * sc + c2);
+            d[3] = pro_coarse<MODE>(coarse_residuals, coarse_q, 3 * sc + c2); d[4] = pro_coarse<MODE>(coarse_residuals, coarse_q, 4 * sc + c2);
         }
     }
     __syncthreads();
@@ -3758,11 +3769,11 @@ k_prolong_tile(int64_t nel, int64_t stride, int64_t stride_coarse, const int32_t
     }
     double sf = __longlong_as_double(0x7FF0000000000000LL);          // +inf
     if (active) {
-        const double n0 = q0 + (f0 - r0 / ws);
-        const double n1 = q1 + (f1 - r1 / ws);
-        const double n2 = q2 + (f2 - r2 / ws);
-        const double n3 = q3 + (f3 - r3 / ws);
-        const double n4 = q4 + (f4 - r4 / ws);
+        const double n0 = pro_result<MODE>(q0, f0, r0 / ws);
+        const double n1 = pro_result<MODE>(q1, f1, r1 / ws);
+        const double n2 = pro_result<MODE>(q2, f2, r2 / ws);
+        const double n3 = pro_result<MODE>(q3, f3, r3 / ws);
+        const double n4 = pro_result<MODE>(q4, f4, r4 / ws);
         store_conserved(fine_q, stride, i, n0, n1, n2, n3, n4);
         if (partial_min) sf = local_step_factor(n0, n1, n2, n3, n4, cbrt_vol[i], cfl);
     }
@@ -4207,30 +4218,36 @@ void launch_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, 
                        cfl, partial_min, rms);
 }
 
-// FAS = false: coarse_a = the coarse residuals, fine_residuals given; FAS = true: coarse_a = W0, coarse_q = W, no fine residuals
-template <bool FAS>
+// kProResiduals: coarse_a = the coarse residuals, fine_residuals given; kProFas: coarse_a = W0, coarse_q = W, no fine residuals;
+// kProState: coarse_a = the coarse state, neither
+template <int MODE>
 static void launch_prolong_kind(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_a, const double *coarse_q,
                                 const double *fine_residuals, double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
 {
     // grid_for(nel) workgroups: the same partition k_step_factor_local's partial minima use
     if (p.pro_tiled) {
-        hipLaunchKernelGGL(k_prolong_tile<FAS>, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
+        hipLaunchKernelGGL(k_prolong_tile<MODE>, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
                            p.slice_row0, p.rows_int, p.pro_w, p.pro_s16, p.pro_own16, p.pro_tile_n, p.pro_tile_ids,
                            p.pro_parent, p.pro_wsum, coarse_a, fine_residuals, fine_q, cbrt_vol, cfl, partial_min, coarse_q);
         return;
     }
-    hipLaunchKernelGGL(k_prolong<FAS>, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
+    hipLaunchKernelGGL(k_prolong<MODE>, dim3(grid_for(p.nel)), dim3(kBlock), 0, st, p.nel, p.stride, stride_coarse,
                        p.slice_row0, p.rows_int, p.pro_w, p.pro_p, p.pro_parent, p.pro_wsum, coarse_a, fine_residuals, fine_q,
                        cbrt_vol, cfl, partial_min, coarse_q);
 }
 void launch_prolong(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_residuals,
                     const double *fine_residuals, double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
-{ launch_prolong_kind<false>(st, p, stride_coarse, coarse_residuals, nullptr, fine_residuals, fine_q, cbrt_vol, cfl, partial_min); }
+{ launch_prolong_kind<kProResiduals>(st, p, stride_coarse, coarse_residuals, nullptr, fine_residuals, fine_q, cbrt_vol, cfl, partial_min); }
 
 // the up leg of a FAS cycle: variables[fine] += 0.0 - wavg(W0 - W) of the coarse level
 void launch_prolong_fas(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_w0, const double *coarse_q,
                         double *fine_q, const double *cbrt_vol, double cfl, double *partial_min)
-{ launch_prolong_kind<true>(st, p, stride_coarse, coarse_w0, coarse_q, nullptr, fine_q, cbrt_vol, cfl, partial_min); }
+{ launch_prolong_kind<kProFas>(st, p, stride_coarse, coarse_w0, coarse_q, nullptr, fine_q, cbrt_vol, cfl, partial_min); }
+
+// mgcfd_prolong_state: variables[fine] = 0.0 - (0.0 - wavg(variables[fine + 1])); the fine level is only written
+void launch_prolong_state(hipStream_t st, const DevicePlan &p, int64_t stride_coarse, const double *coarse_q, double *fine_q,
+                          const double *cbrt_vol, double cfl, double *partial_min)
+{ launch_prolong_kind<kProState>(st, p, stride_coarse, coarse_q, nullptr, nullptr, fine_q, cbrt_vol, cfl, partial_min); }
 
 void launch_restrict_fas(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, int64_t stride_fine, const int32_t *child_ptr,
                          const int32_t *child, const int32_t *child4, const double *fine_q, const double *fine_r, const double *fine_p,

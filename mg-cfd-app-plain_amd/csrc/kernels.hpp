@@ -89,6 +89,8 @@
     void launch_prolong_fas(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_w0,         \
                             const double *coarse_q, double *fine_q, const double *cbrt_vol, double cfl,              \
                             double *partial_min);                                                                    \
+    void launch_prolong_state(hipStream_t, const DevicePlan &, int64_t stride_coarse, const double *coarse_q,        \
+                              double *fine_q, const double *cbrt_vol, double cfl, double *partial_min);              \
     } }
 
 MGCFD_DECLARE_LAUNCHERS(exact)
@@ -113,5 +115,6 @@ struct Launchers {
     decltype(exact::launch_jst_sensor) *jst_sensor;                  decltype(exact::launch_jst_dissipation) *jst_dissipation;
     decltype(exact::launch_restrict_fas) *restrict_fas;              decltype(exact::launch_prolong_fas) *prolong_fas;
     decltype(exact::launch_viscous_stress) *viscous_stress;          decltype(exact::launch_viscous_flux) *viscous_flux;
+    decltype(exact::launch_prolong_state) *prolong_state;
 };
 }

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <numeric>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -81,6 +82,11 @@ struct Config {                       // the reference's `config` (src/Base/conf
     size_t loads_width() const { return loads_friction ? 12 : 6; }
     // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
     bool fas = false;
+    // the multigrid cycle: --cycle V|W|F, --pre-sweeps LIST, --post-sweeps LIST (mgcfd_set_cycle before the first cycle) and
+    // --fmg-cycles LIST (mgcfd_full_multigrid before the -g cycles); the lists are expanded once the number of levels is known
+    int cycle_shape = MGCFD_CYCLE_V;
+    std::vector<int> pre_sweeps, post_sweeps, fmg_cycles;
+    bool cycle_given() const { return cycle_shape != MGCFD_CYCLE_V || !pre_sweeps.empty() || !post_sweeps.empty(); }
     // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
     // physical_time_step / time_steps / dual_time_clamp / bdf_order.  With DT given, -g is the number of cycles per physical step.
     bool dual_given = false;          // a DT was given: mgcfd_set_dual_time before the first cycle, mgcfd_advance for the cycles
@@ -151,6 +157,20 @@ bool parse_whole(const char *text, int lo, int hi, int *out)
     if (!parse_number(text, &v) || v < double(lo) || v > double(hi) || v != double(int(v))) return false;
     *out = int(v);
     return true;
+}
+// "N" or "N,N,...": whole numbers lo ... hi (the sweeps per level, the FMG cycles per level)
+bool parse_whole_list(const char *text, int lo, int hi, std::vector<int> *out)
+{
+    out->clear();
+    const std::string all(text);
+    for (size_t at = 0; at <= all.size();) {
+        const size_t comma = std::min(all.find(',', at), all.size());
+        int v = 0;
+        if (!parse_whole(all.substr(at, comma - at).c_str(), lo, hi, &v)) return false;
+        out->push_back(v);
+        at = comma + 1;
+    }
+    return !out->empty();
 }
 constexpr int kMaxTimeSteps = 1000000;
 constexpr int kMaxJstLevels = 64;
@@ -365,6 +385,17 @@ void print_help()
         "  --fas                            FAS multigrid (config key fas = Y): the coarse levels carry the fine level's residual as a\n"
         "                                   forcing term and return a correction, so the V-cycles converge to the fine grid's steady\n"
         "                                   state; one GPU, an input of two levels or more\n"
+        "  --cycle=V|W|F                    The shape of the multigrid cycle (default V, the reference's): W visits every coarser level\n"
+        "                                   twice per visit, F once as itself and once as a V-cycle; the coarsest level once per\n"
+        "                                   down leg.  One GPU\n"
+        "  --pre-sweeps=LIST                Sweeps per level before the restriction, 1 ... 8 (default 1): comma separated, one value\n"
+        "                                   per level, or one value for all levels.  One GPU\n"
+        "  --post-sweeps=LIST               Sweeps per level after the prolongation, 0 ... 8 (default 0 on level 0, 1 on the others):\n"
+        "                                   one value per level, or one value for all levels but the coarsest, which has none.  One GPU\n"
+        "  --fmg-cycles=LIST                A full-multigrid start before the -g cycles: the state is restricted to every level, then\n"
+        "                                   from the coarsest level up LIST cycles run from that level and its state is interpolated\n"
+        "                                   onto the next finer one.  One value per level 1 ... n-1, or one value for all, 0 ... 4096.\n"
+        "                                   One GPU; not with --physical-time-step or --polar\n"
         "  --jst-kappa2=X                   its second-difference coefficient, finite, zero or above, in units of the reference's\n"
         "                                   dissipation (config key jst_kappa2; implies --jst)\n"
         "  --jst-kappa4=X                   its fourth-difference coefficient, likewise (config key jst_kappa4; implies --jst)\n"
@@ -438,6 +469,10 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"bdf-order", required_argument, nullptr, 1025},
         {"jst", no_argument, nullptr, 1026},
         {"fas", no_argument, nullptr, 1030},
+        {"cycle", required_argument, nullptr, 1050},
+        {"pre-sweeps", required_argument, nullptr, 1051},
+        {"post-sweeps", required_argument, nullptr, 1052},
+        {"fmg-cycles", required_argument, nullptr, 1053},
         {"jst-kappa2", required_argument, nullptr, 1027},
         {"jst-kappa4", required_argument, nullptr, 1028},
         {"jst-levels", required_argument, nullptr, 1029},
@@ -554,6 +589,32 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 break;
             case 1026: c.jst_given = true; break;
             case 1030: c.fas = true; break;
+            case 1050: {
+                const std::string v(optarg);
+                if (v == "V" || v == "v") c.cycle_shape = MGCFD_CYCLE_V;
+                else if (v == "W" || v == "w") c.cycle_shape = MGCFD_CYCLE_W;
+                else if (v == "F" || v == "f") c.cycle_shape = MGCFD_CYCLE_F;
+                else { std::fprintf(stderr, "ERROR: --cycle=%s: expected V, W or F\n", optarg); return false; }
+                break;
+            }
+            case 1051:
+                if (!parse_whole_list(optarg, 1, MGCFD_MAX_CYCLE_SWEEPS, &c.pre_sweeps)) {
+                    std::fprintf(stderr, "ERROR: --pre-sweeps=%s: expected whole numbers 1 ... %d, comma separated\n", optarg, MGCFD_MAX_CYCLE_SWEEPS);
+                    return false;
+                }
+                break;
+            case 1052:
+                if (!parse_whole_list(optarg, 0, MGCFD_MAX_CYCLE_SWEEPS, &c.post_sweeps)) {
+                    std::fprintf(stderr, "ERROR: --post-sweeps=%s: expected whole numbers 0 ... %d, comma separated\n", optarg, MGCFD_MAX_CYCLE_SWEEPS);
+                    return false;
+                }
+                break;
+            case 1053:
+                if (!parse_whole_list(optarg, 0, MGCFD_MAX_ADVANCE_CYCLES, &c.fmg_cycles)) {
+                    std::fprintf(stderr, "ERROR: --fmg-cycles=%s: expected whole numbers 0 ... %d, comma separated\n", optarg, MGCFD_MAX_ADVANCE_CYCLES);
+                    return false;
+                }
+                break;
             case 1027:
             case 1028:
                 if (!parse_not_negative(optarg, optc == 1027 ? &c.jst_kappa2 : &c.jst_kappa4)) {
@@ -1015,6 +1076,14 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "ERROR: FAS multigrid (--fas) runs on one GPU only: levels split over GPUs, or one level per GPU, would need the residuals, the forcing and the corrections exchanged\n");
         return 1;
     }
+    if ((conf.cycle_given() || !conf.fmg_cycles.empty()) && conf.gpus > 1) {
+        std::fprintf(stderr, "ERROR: --cycle, --pre-sweeps, --post-sweeps and --fmg-cycles run on one GPU only: levels split over GPUs, or one level per GPU, run the default cycle\n");
+        return 1;
+    }
+    if (!conf.fmg_cycles.empty() && (conf.dual_given || conf.polar)) {
+        std::fprintf(stderr, "ERROR: a full-multigrid start (--fmg-cycles) does not run with --physical-time-step or --polar\n");
+        return 1;
+    }
     if (conf.dual_given && conf.polar) {
         std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --polar\n");
         return 1;
@@ -1052,6 +1121,21 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "ERROR: FAS multigrid (--fas) needs an input of two levels or more: with one level there is no coarse level to force and no correction to bring back\n");
         return 1;
     }
+    // the lists of the cycle flags, one entry per level
+    std::vector<int> pre(static_cast<size_t>(levels), 1), post(static_cast<size_t>(levels), 1), fmg(static_cast<size_t>(levels), 0);
+    post[0] = 0;
+    {
+        const size_t n = static_cast<size_t>(levels);
+        if (conf.pre_sweeps.size() == 1) pre.assign(n, conf.pre_sweeps[0]);
+        else if (conf.pre_sweeps.size() == n) pre = conf.pre_sweeps;
+        else if (!conf.pre_sweeps.empty()) { std::fprintf(stderr, "ERROR: --pre-sweeps: one value, or one per level (%d)\n", levels); return 1; }
+        if (conf.post_sweeps.size() == 1) std::fill(post.begin(), post.end() - 1, conf.post_sweeps[0]);      // (the coarsest level is left alone)
+        else if (conf.post_sweeps.size() == n) post = conf.post_sweeps;
+        else if (!conf.post_sweeps.empty()) { std::fprintf(stderr, "ERROR: --post-sweeps: one value, or one per level (%d)\n", levels); return 1; }
+        if (conf.fmg_cycles.size() == 1) std::fill(fmg.begin() + 1, fmg.end(), conf.fmg_cycles[0]);
+        else if (conf.fmg_cycles.size() + 1 == n) std::copy(conf.fmg_cycles.begin(), conf.fmg_cycles.end(), fmg.begin() + 1);
+        else if (!conf.fmg_cycles.empty()) { std::fprintf(stderr, "ERROR: --fmg-cycles: one value, or one per level 1 ... %d\n", levels - 1); return 1; }
+    }
     if (conf.gpus > 1) return run_on_several_gpus(conf, mesh, levels, mesh_variant, problem_size);
 
     mgcfd_solver *solver = nullptr;
@@ -1086,6 +1170,7 @@ int main(int argc, char **argv)
             return fail("setting the viscous terms");
     }
     if (conf.fas && mgcfd_set_fas(solver, 1) != MGCFD_OK) return fail("switching FAS multigrid on");
+    if (conf.cycle_given() && mgcfd_set_cycle(solver, conf.cycle_shape, pre.data(), post.data()) != MGCFD_OK) return fail("setting the multigrid cycle");
     const int rc = run_all_cycles(conf, rms, loads, polar_rows,
         [&](double mach, double alpha, int reinitialise) { return mgcfd_set_free_stream(solver, mach, alpha, reinitialise); },
         [&](double *rms_out, double *loads_out) {
@@ -1111,6 +1196,17 @@ int main(int argc, char **argv)
                     steps_done += now;
                 }
                 return int(MGCFD_OK);
+            }
+            if (!conf.fmg_cycles.empty()) {
+                // the full-multigrid start, behind the free stream: its histories go to stderr (stdout stays the reference's lines)
+                std::vector<double> fmg_rms(static_cast<size_t>(std::max(1, std::accumulate(fmg.begin() + 1, fmg.end(), 0))));
+                const int rc_fmg = mgcfd_full_multigrid(solver, fmg.data(), fmg_rms.data());
+                if (rc_fmg != MGCFD_OK) return rc_fmg;
+                size_t at = 0;
+                for (int top = levels - 1; top >= 1; at += static_cast<size_t>(fmg[static_cast<size_t>(top)]), top--)
+                    if (fmg[static_cast<size_t>(top)] > 0)
+                        std::fprintf(stderr, "[euler3d_gpu_double] full multigrid: %d cycles from level %d, RMS %.3e -> %.3e\n", fmg[static_cast<size_t>(top)], top,
+                                     fmg_rms[at], fmg_rms[at + static_cast<size_t>(fmg[static_cast<size_t>(top)]) - 1]);
             }
             if (loads_out && conf.loads_friction) return mgcfd_run_cycles_loads_viscous(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out);
             return loads_out ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out)

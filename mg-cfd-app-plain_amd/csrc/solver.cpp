@@ -387,7 +387,17 @@ struct mgcfd_solver {
     // of a level >= 1 takes R + P for its total residual R.  Such a level runs unfused stages (standalone flux launch + the
     // forced update): no fused stage, no look-ahead; no graph on any level.  Level 0 sweeps as ever.
     bool fas = false;
-    bool fas_forced(int l) const { return fas && l >= 1; }
+    // (a run of cycles from level cycle_top > 0, mgcfd_run_cycles_from: that level plays level 0's part and is unforced)
+    bool fas_forced(int l) const { return fas && l > cycle_top; }
+    // The cycle (mgcfd_set_cycle): its shape and the sweeps per level before the down leg and after the up leg.  Empty vectors
+    // are the defaults — pre 1, post 1 on the levels 0 < l < n-1, 0 on level 0 — and the setter stores the defaults as empty
+    // vectors, so that default_cycle() is the one question every caller asks.  A non-default cycle runs its launches directly.
+    int cycle_shape = MGCFD_CYCLE_V;
+    std::vector<int> cycle_pre, cycle_post;
+    int cycle_top = 0;                             // the level mgcfd_run_cycles_from is cycling from, 0 otherwise
+    bool default_cycle() const { return cycle_shape == MGCFD_CYCLE_V && cycle_pre.empty() && cycle_post.empty(); }
+    int pre_sweeps(int l) const { return cycle_pre.empty() ? 1 : cycle_pre[static_cast<size_t>(l)]; }
+    int post_sweeps(int l) const { return cycle_post.empty() ? (l == 0 ? 0 : 1) : cycle_post[static_cast<size_t>(l)]; }
     // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while any of them is on
     bool ordered_rms() const { return dual_time() || jst_on(0) || fas || viscous_on(0); }
     // What the options above allow — every one of them that is on for a level replaces its fused flux + time_step stages by
@@ -396,9 +406,9 @@ struct mgcfd_solver {
     //   fused stages on level l: FAS forces the levels >= 1 only (level 0 sweeps as ever) ...
     bool options_allow_fused(int l) const { return !smoothing() && !dual_time() && !jst_on(l) && !viscous_on(l) && !fas_forced(l); }
     //   ... but no sweep is graphed on any level while it is on; JST and viscous levels count one by one
-    bool options_allow_sweep_graph(int l) const { return options_allow_fused(l) && !fas; }
+    bool options_allow_sweep_graph(int l) const { return options_allow_fused(l) && !fas && default_cycle(); }
     //   a whole cycle as one graph: every level's sweep must be (JST and the viscous terms run on levels 0 .. n-1: level 0 decides)
-    bool options_allow_cycle_graph() const { return options_allow_sweep_graph(0); }
+    bool options_allow_cycle_graph() const { return options_allow_sweep_graph(0) && cycle_top == 0; }
     JstStep jst_step(DeviceLevel &lv) const
     {
         JstStep a;
@@ -442,7 +452,7 @@ struct mgcfd_solver {
                                 NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
                                 NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_src, NS::launch_dual_source, \
                                 NS::launch_jst_sensor, NS::launch_jst_dissipation, NS::launch_restrict_fas, NS::launch_prolong_fas, \
-                                NS::launch_viscous_stress, NS::launch_viscous_flux}
+                                NS::launch_viscous_stress, NS::launch_viscous_flux, NS::launch_prolong_state}
         static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
 #undef MGCFD_LAUNCHERS_OF
         return opt_exact ? kExact : kFast;
@@ -831,10 +841,11 @@ struct mgcfd_solver {
     }
     // ... of level 0 in the order the options of ordered_rms() fix on the original numbering (mgcfd.h): per-workgroup sums of 256
     // original nodes into tile_sumsq (no fused stage fills it while one of them is on), then their sum, appended to `ring` if given
-    void op_sumsq_ordered(double *ring = nullptr, int *count = nullptr, int cap = 0)
+    // (level > 0: the RMS of mgcfd_run_cycles_from, which uploads that level's numbering on first use)
+    void op_sumsq_ordered(double *ring = nullptr, int *count = nullptr, int cap = 0, int l = 0)
     {
-        DeviceLevel &l0 = level(0);
-        if (!l0.new_of_old_dev) throw std::logic_error("the ordered RMS sum without level 0's numbering on the device");
+        DeviceLevel &l0 = level(l);
+        if (!l0.new_of_old_dev) throw std::logic_error("the ordered RMS sum without the level's numbering on the device");
         settle_residuals(l0);
         exact::launch_sumsq_original(stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
         exact::launch_sum_partials_append(stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq, ring, count, cap);
@@ -903,7 +914,7 @@ struct mgcfd_solver {
         {
             Timed t(this, fine + 1, MGCFD_LOOP_RESTRICT);       // (booked on the coarse level, as op_restrict)
             k().restrict_fas(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
-                             fine >= 1 ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p);
+                             fas_forced(fine) ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p);
             viscous_wall(fine + 1, C.q, C.fas_w0);
         }
         F.fluxes_zero = true; F.fluxes_stale = true;            // (T is used up)
@@ -929,6 +940,24 @@ struct mgcfd_solver {
         double *pm = ahead ? F.partial_min : nullptr;
         Timed t(this, fine, MGCFD_LOOP_PROLONG);
         k().prolong_fas(stream, F.dp, C.dp.stride, C.fas_w0, C.q, F.q, F.cbrt_vol, cfl, pm);
+        viscous_wall(fine, F.q);
+        F.min_ahead = ahead;
+        F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;
+    }
+    // mgcfd_prolong_state: variables[fine] = 0.0 - (0.0 - wavg(variables[fine + 1])).  Neither level's residuals are touched and
+    // the fine state is only written, so the look-ahead minima are those of the state the launch writes, where the sweep that
+    // follows takes them (as op_fas_prolong).
+    void op_prolong_state(int fine)
+    {
+        DeviceLevel &F = level(fine);
+        DeviceLevel &C = level(fine + 1);
+        if (!F.has_transfer) throw std::invalid_argument("level has no multigrid map");
+        if (partitioned || comm) throw std::invalid_argument("mgcfd_prolong_state: not on a partitioned solver or a rank (split levels are out of scope)");
+        settle_residuals(F);                                    // (an unwritten residual's operand is about to change)
+        const bool ahead = global_dt() && !fas_forced(fine) && !viscous_on(fine) && F.n_owned == F.info.nel;
+        double *pm = ahead ? F.partial_min : nullptr;
+        Timed t(this, fine, MGCFD_LOOP_PROLONG);
+        k().prolong_state(stream, F.dp, C.dp.stride, C.q, F.q, F.cbrt_vol, cfl, pm);
         viscous_wall(fine, F.q);
         F.min_ahead = ahead;
         F.iters[MGCFD_LOOP_PROLONG] += F.info.n_internal + F.info.nel;
@@ -1917,6 +1946,7 @@ int mgcfd_restrict(mgcfd_solver *s, int fine_level) { OP(s->op_restrict(fine_lev
 int mgcfd_prolong(mgcfd_solver *s, int fine_level) { OP(s->op_prolong(fine_level)); }
 int mgcfd_fas_restrict(mgcfd_solver *s, int fine_level) { OP(s->op_fas_restrict(fine_level)); }
 int mgcfd_fas_prolong(mgcfd_solver *s, int fine_level) { OP(s->op_fas_prolong(fine_level)); }
+int mgcfd_prolong_state(mgcfd_solver *s, int fine_level) { OP({ s->level(fine_level + 1); s->op_prolong_state(fine_level); }); }
 int mgcfd_step_factor_local(mgcfd_solver *s, int level)
 {
     OP({
@@ -2350,9 +2380,10 @@ static void loads_upload_ref(mgcfd_solver *s, const double *ref_point)
 }
 
 // ---- cycle driver: src/euler3d_cpu_double.cpp:371-694 ----
-// One multigrid cycle of the reference's state machine, unrolled: sweeps on levels
-// 0,1,..,n-1,n-2,..,1 with restrictions on the way up and prolongations on the way down
-// (src/euler3d_cpu_double.cpp:371-694); the level-0 sum of squares is appended to the rms ring.
+// One multigrid cycle: the reference's state machine (sweeps on levels 0,1,..,n-1,n-2,..,1 with restrictions on the way
+// up and prolongations on the way down, src/euler3d_cpu_double.cpp:371-694) generalised to the configured shape and sweep
+// counts (mgcfd_set_cycle) and to a start level (mgcfd_run_cycles_from); the sum of squares of the level it starts from is
+// appended to the rms ring.
 static void cycle_once(mgcfd_solver *s, bool capturing)
 {
     const int n = static_cast<int>(s->L.size());
@@ -2376,36 +2407,51 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
         } catch (...) { s->opt_timing = keep; throw; }
         s->opt_timing = keep;
     };
-    for (int l = 0; l < n; l++) {
-        // (FAS keeps level 0's fused stages but fixes the order of the RMS sum: their per-tile sums are not asked for)
-        if (l == 0) { s->L[0].want_sumsq = !s->ordered_rms(); s->L[0].have_sumsq = false; }
-        sweep(l);                                                          // :383-508
-        if (l == 0) {                                                      // :509-512
-            DeviceLevel &l0 = s->L[0];
-            l0.want_sumsq = false;
-            if (l0.have_sumsq && n > 1) {
+    // visit(l, kind) of mgcfd.h.  With the default configuration from level 0 this is the reference's cycle launch for launch:
+    // sweeps on levels 0, 1, .., n-1, n-2, .., 1.  The step-factor look-ahead needs no care of its own here: a level's
+    // min_ahead is set by the launch that wrote its CURRENT variables and cleared by every other writer, whatever the order.
+    const int top = s->cycle_top;
+    std::function<void(int, int)> visit = [&](int l, int kind) {
+        DeviceLevel &lt = s->L[static_cast<size_t>(l)];
+        for (int k = s->pre_sweeps(l); k > 0; k--) {
+            const bool measured = l == top && k == 1;                          // the cycle's RMS: after the last of these
+            // (FAS keeps level 0's fused stages but fixes the order of the RMS sum: their per-tile sums are not asked for)
+            if (measured) { lt.want_sumsq = top == 0 && !s->ordered_rms(); lt.have_sumsq = false; }
+            sweep(l);                                                          // :383-508
+            if (!measured) continue;
+            lt.want_sumsq = false;                                             // :509-512
+            if (top > 0) {
+                // a cycle from a coarser level: always the fixed order on that level's original numbering
+                s->op_sumsq_ordered(s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing, top);
+            } else if (lt.have_sumsq && n > 1) {
                 // the last stage left per-tile sums of squares: the restriction that follows adds them up and appends
-                rms_task = SumTask{l0.tile_sumsq, static_cast<int>((l0.info.nel + 255) / 256), l0.sumsq, s->rms_ring, s->rms_count,
+                rms_task = SumTask{lt.tile_sumsq, static_cast<int>((lt.info.nel + 255) / 256), lt.sumsq, s->rms_ring, s->rms_count,
                                    mgcfd_solver::kRmsRing};
                 rms_pending = true;
-            } else if (l0.have_sumsq) {
+            } else if (lt.have_sumsq) {
                 // ... single level: one small launch does
-                exact::launch_sum_partials_append(s->stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq,
+                exact::launch_sum_partials_append(s->stream, static_cast<int>((lt.info.nel + 255) / 256), lt.tile_sumsq, lt.sumsq,
                                                   s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else if (s->ordered_rms()) {
                 s->op_sumsq_ordered(s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else {
                 s->op_sumsq(0);
-                exact::launch_append_scalar(s->stream, l0.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+                exact::launch_append_scalar(s->stream, lt.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             }
         }
-        if (l + 1 < n) { transfer(true, l, (l == 0 && rms_pending) ? &rms_task : nullptr); rms_pending = false; }   // :527-559
-    }
-    for (int l = n - 2; l >= 0; l--) {
-        transfer(false, l, nullptr);                                       // :560-688
-        if (l > 0) sweep(l);
-    }
-    // (the state the cycle leaves: after the last prolongation)
+        if (l == n - 1) return;
+        transfer(true, l, rms_pending ? &rms_task : nullptr);                  // :527-559
+        rms_pending = false;
+        visit(l + 1, kind);
+        if (l + 1 < n - 1) {                                                   // (the coarsest level is visited once per down leg)
+            if (kind == MGCFD_CYCLE_W) visit(l + 1, MGCFD_CYCLE_W);
+            else if (kind == MGCFD_CYCLE_F) visit(l + 1, MGCFD_CYCLE_V);
+        }
+        transfer(false, l, nullptr);                                           // :560-688
+        for (int k = s->post_sweeps(l); k > 0; k--) sweep(l);
+    };
+    visit(top, s->cycle_shape);
+    // (the state the cycle leaves: after the last prolongation and level 0's post-sweeps)
     if (s->loads_in_cycle) { if (s->loads_friction) launch_loads_viscous(s, 0, nullptr); else launch_loads(s, s->L[0], true); }
 }
 
@@ -2542,7 +2588,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             const double nan = std::numeric_limits<double>::quiet_NaN();
             for (int c = 0; c < cycles; c++)
                 rms_out[c] = (c < static_cast<int>(sums.size()) && (failed_cycle < 0 || c < failed_cycle))
-                                 ? std::sqrt(sums[static_cast<size_t>(c)] / double(s->L[0].n_owned)) : nan;
+                                 ? std::sqrt(sums[static_cast<size_t>(c)] / double(s->L[static_cast<size_t>(s->cycle_top)].n_owned)) : nan;
         }
         if (loads_out) {
             const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -2565,6 +2611,101 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
 }
 
 int mgcfd_run_cycles(mgcfd_solver *s, int cycles, double *rms_out) { return run_cycles_impl(s, cycles, rms_out, nullptr, nullptr); }
+
+// ---- the cycle: shape, sweeps per level, cycles from a coarser level, full multigrid ----
+int mgcfd_set_cycle(mgcfd_solver *s, int shape, const int *pre, const int *post)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        const int n = static_cast<int>(s->L.size());
+        if (shape != MGCFD_CYCLE_V && shape != MGCFD_CYCLE_W && shape != MGCFD_CYCLE_F)
+            throw std::invalid_argument("cycle: unknown shape " + std::to_string(shape));
+        std::vector<int> p(static_cast<size_t>(n), 1), q(static_cast<size_t>(n), 1);
+        q[0] = 0;
+        bool is_default = shape == MGCFD_CYCLE_V;
+        for (int l = 0; l < n; l++) {
+            if (pre) p[static_cast<size_t>(l)] = pre[l];
+            if (post && l < n - 1) q[static_cast<size_t>(l)] = post[l];            // (post[n-1] is ignored)
+            if (p[static_cast<size_t>(l)] < 1 || p[static_cast<size_t>(l)] > MGCFD_MAX_CYCLE_SWEEPS)
+                throw std::invalid_argument("cycle: pre[" + std::to_string(l) + "] must lie in 1.." + std::to_string(MGCFD_MAX_CYCLE_SWEEPS));
+            if (q[static_cast<size_t>(l)] < 0 || q[static_cast<size_t>(l)] > MGCFD_MAX_CYCLE_SWEEPS)
+                throw std::invalid_argument("cycle: post[" + std::to_string(l) + "] must lie in 0.." + std::to_string(MGCFD_MAX_CYCLE_SWEEPS));
+            is_default = is_default && p[static_cast<size_t>(l)] == 1 && (l == n - 1 || q[static_cast<size_t>(l)] == (l == 0 ? 0 : 1));
+        }
+        if (!is_default && (s->partitioned || s->comm))
+            throw std::invalid_argument("cycle: only the default cycle on a partitioned solver or a rank (split levels are out of scope)");
+        quiesce(s, "cycle");
+        s->cycle_shape = shape;
+        if (is_default) { s->cycle_pre.clear(); s->cycle_post.clear(); }
+        else { s->cycle_pre = std::move(p); s->cycle_post = std::move(q); }
+    });
+}
+int mgcfd_get_cycle(const mgcfd_solver *s, int *shape, int *pre, int *post)
+{
+    REQUIRE(s);
+    if (shape) *shape = s->cycle_shape;
+    const int n = static_cast<int>(s->L.size());
+    for (int l = 0; l < n; l++) {
+        if (pre) pre[l] = s->pre_sweeps(l);
+        if (post) post[l] = s->post_sweeps(l);                 // (the coarsest level's entry is ignored and stays its default)
+    }
+    return MGCFD_OK;
+}
+// The groups and ranks run the reference's cycle from their own drivers: a solver with another one is refused there.
+static void require_default_cycle(const mgcfd_solver *s, const char *who)
+{
+    if (!s->default_cycle()) throw std::invalid_argument(std::string(who) + ": not with a non-default cycle (mgcfd_set_cycle)");
+}
+
+int mgcfd_run_cycles_from(mgcfd_solver *s, int top, int cycles, double *rms_out)
+{
+    REQUIRE(s);
+    if (top == 0) return mgcfd_run_cycles(s, cycles, rms_out);
+    int rc = guarded([&] {
+        DeviceLevel &lv = s->level(top);
+        if (s->dual_time()) throw std::invalid_argument("mgcfd_run_cycles_from: a coarser start level while dual time is on is out of scope");
+        if (cycles > MGCFD_MAX_ADVANCE_CYCLES)
+            throw std::invalid_argument("mgcfd_run_cycles_from: at most " + std::to_string(MGCFD_MAX_ADVANCE_CYCLES) + " cycles per call");
+        if (s->partitioned || s->comm) throw std::invalid_argument("mgcfd_run_cycles_from: not on a partitioned solver or a rank (split levels are out of scope)");
+        require_no_sweep_under_way(s, "mgcfd_run_cycles_from");
+        s->use_device();
+        if (!lv.new_of_old_dev) lv.new_of_old_dev = lv.mem.upload(lv.plan.new_of_old);      // (goes with the solver)
+    });
+    if (rc != MGCFD_OK) return rc;
+    s->cycle_top = top;
+    rc = run_cycles_impl(s, cycles, rms_out, nullptr, nullptr);
+    s->cycle_top = 0;
+    s->L[static_cast<size_t>(top)].min_ahead = false;      // (work done ahead for an unforced sweep of this level: the next one may be forced)
+    return rc;
+}
+
+int mgcfd_full_multigrid(mgcfd_solver *s, const int *cycles, double *rms_out)
+{
+    REQUIRE(s); REQUIRE(cycles);
+    const int n = static_cast<int>(s->L.size());
+    // everything mgcfd_run_cycles_from and mgcfd_prolong_state would refuse, before the restrictions change a coarse state
+    int rc0 = guarded([&] {
+        if (n > 1 && s->dual_time()) throw std::invalid_argument("mgcfd_full_multigrid: not while dual time is on (out of scope)");
+        if (s->partitioned || s->comm) throw std::invalid_argument("mgcfd_full_multigrid: not on a partitioned solver or a rank (split levels are out of scope)");
+        for (int l = 1; l < n; l++)
+            if (cycles[l] < 0 || cycles[l] > MGCFD_MAX_ADVANCE_CYCLES)
+                throw std::invalid_argument("mgcfd_full_multigrid: cycles[" + std::to_string(l) + "] must lie in 0.." + std::to_string(MGCFD_MAX_ADVANCE_CYCLES));
+        require_no_sweep_under_way(s, "mgcfd_full_multigrid");
+    });
+    if (rc0 != MGCFD_OK) return rc0;
+    for (int l = 0; l + 1 < n; l++) {
+        const int rc = mgcfd_restrict(s, l);
+        if (rc != MGCFD_OK) return rc;
+    }
+    size_t at = 0;
+    for (int top = n - 1; top >= 1; top--) {
+        int rc = mgcfd_run_cycles_from(s, top, cycles[top], rms_out ? rms_out + at : nullptr);
+        at += static_cast<size_t>(cycles[top]);
+        if (rc == MGCFD_OK) rc = mgcfd_prolong_state(s, top - 1);
+        if (rc != MGCFD_OK) return rc;
+    }
+    return MGCFD_OK;
+}
 
 // ---- state access ----
 static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
@@ -3743,6 +3884,7 @@ int mgcfd_rank_attach_rccl(mgcfd_solver *s, int rank, int world, const void *id1
     return guarded([&] {
         if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
         require_no_smoothing(s, "mgcfd_rank_attach_rccl");
+        require_default_cycle(s, "mgcfd_rank_attach_rccl");
         s->use_device();
         rccl_load();
         Rccl::Id id;
@@ -3762,6 +3904,7 @@ int mgcfd_rank_attach_plain(mgcfd_solver *s, int rank, int world)
     return guarded([&] {
         if (rank < 0 || rank >= world) throw std::invalid_argument("rank out of range");
         require_no_smoothing(s, "mgcfd_rank_attach_plain");
+        require_default_cycle(s, "mgcfd_rank_attach_plain");
         mgcfd_comm c;
         c.rank = rank; c.world = world;
         s->comm = c;
@@ -4072,6 +4215,7 @@ int mgcfd_group_create(int n, mgcfd_solver *const *solvers, mgcfd_group **out)
         for (int r = 0; r < n; r++) {
             if (!solvers[r]) throw std::invalid_argument("null solver");
             require_no_smoothing(solvers[r], "mgcfd_group_create");
+            require_default_cycle(solvers[r], "mgcfd_group_create");
             g->ranks.push_back(solvers[r]);
         }
         // peer access between the devices of the group (xGMI): a copy between two devices then goes direct

@@ -211,7 +211,15 @@ _SIGNATURES = [
     ("mgcfd_wall_distribution", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_wall_stress", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_bench_friction_loads", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_cycle", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("mgcfd_get_cycle", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("mgcfd_run_cycles_from", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    ("mgcfd_prolong_state", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_full_multigrid", C.c_int, [_vp, C.POINTER(C.c_int), _vp]),
 ]
+
+CYCLE_SHAPES = {"V": 0, "W": 1, "F": 2}
+MAX_CYCLE_SWEEPS = 8
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _SIGNATURES)
 
 _lib: Optional[C.CDLL] = None
@@ -703,6 +711,53 @@ class Solver:
     def fas_prolong(self, fine):
         """The up leg onto level ``fine``: the coarse level's correction, interpolated as ``prolong`` does (mgcfd_fas_prolong)."""
         self._c(self.lib.mgcfd_fas_prolong(self.handle, fine))
+
+    # ---- the multigrid cycle: shape, sweeps per level, cycles from a coarser level, full multigrid ----
+    def set_cycle(self, shape="V", pre=None, post=None):
+        """The multigrid cycle (mgcfd_set_cycle): ``shape`` "V", "W" or "F" (or its number), ``pre`` / ``post`` the sweeps per
+        level before the down leg and after the up leg, one entry per level; None = the defaults (1 everywhere, no post-sweep on
+        level 0; the coarsest level's post entry is ignored).  A non-default cycle runs its launches directly."""
+        n = self.num_levels
+        number = CYCLE_SHAPES.get(shape.upper(), -1) if isinstance(shape, str) else int(shape)
+
+        def counts(v):
+            if v is None:
+                return None
+            v = [int(x) for x in v]
+            if len(v) != n:
+                raise ValueError(f"set_cycle: {n} entries per list, one per level (got {len(v)})")
+            return (C.c_int * n)(*v)
+        self._c(self.lib.mgcfd_set_cycle(self.handle, number, counts(pre), counts(post)))
+
+    def get_cycle(self):
+        """(shape, pre, post) as mgcfd_get_cycle reports them: the shape's letter and two lists, one entry per level."""
+        n = self.num_levels
+        shape, pre, post = C.c_int(0), (C.c_int * n)(), (C.c_int * n)()
+        self._c(self.lib.mgcfd_get_cycle(self.handle, C.byref(shape), pre, post))
+        return "VWF"[shape.value], list(pre), list(post)
+
+    def run_cycles_from(self, top: int, cycles: int) -> np.ndarray:
+        """``cycles`` cycles with level ``top`` in level 0's part (mgcfd_run_cycles_from); the levels below it are untouched.
+        Returns that level's RMS per cycle."""
+        rms = np.zeros(max(cycles, 1))
+        self._c(self.lib.mgcfd_run_cycles_from(self.handle, top, cycles, _ptr(rms)))
+        return rms[:cycles]
+
+    def prolong_state(self, fine: int):
+        """variables[fine] = the interpolated variables[fine + 1] (mgcfd_prolong_state); the fine state is only written."""
+        self._c(self.lib.mgcfd_prolong_state(self.handle, fine))
+
+    def full_multigrid(self, cycles) -> np.ndarray:
+        """A full-multigrid start (mgcfd_full_multigrid): the state restricted to every level, then from the coarsest level up
+        ``cycles[top]`` cycles from level top and its state interpolated onto top - 1.  ``cycles``: one entry per level, the
+        first ignored, or one number for all.  Returns the concatenated RMS histories; level-0 cycles are the next call."""
+        n = self.num_levels
+        c = [int(cycles)] * n if np.isscalar(cycles) else [int(x) for x in cycles]
+        if len(c) != n:
+            raise ValueError(f"full_multigrid: {n} entries, one per level (got {len(c)})")
+        rms = np.zeros(max(sum(max(x, 0) for x in c[1:]), 1))
+        self._c(self.lib.mgcfd_full_multigrid(self.handle, (C.c_int * n)(*c), _ptr(rms)))
+        return rms[:sum(c[1:])]
 
     # ---- laminar viscous terms ----
     def set_viscous(self, mu: float, prandtl: float = VISCOUS_PRANDTL, wall: bool = False, cfl_v: float = VISCOUS_CFL, levels: int = 1):
