@@ -59,7 +59,9 @@ enum { MGCFD_ARR_VARIABLES = 0, MGCFD_ARR_OLD_VARIABLES, MGCFD_ARR_FLUXES, MGCFD
        MGCFD_ARR_FAS_FORCING, MGCFD_ARR_FAS_START /* read-only, levels >= 1 while FAS multigrid is on (mgcfd_set_fas): the forcing P and
                                  the start state W0 [nel][5] of the last mgcfd_fas_restrict onto the level */,
        MGCFD_ARR_VISCOUS_STRESS /* read-only: the node stresses S [nel][12] of the last flux launch of a level the viscous terms are on
-                                 for (mgcfd_set_viscous): u v w | txx tyy tzz txy txz tyz | qx qy qz */ };
+                                 for (mgcfd_set_viscous): u v w | txx tyy tzz txy txz tyz | qx qy qz */,
+       MGCFD_ARR_EDDY_VISCOSITY /* the eddy viscosity mut [nel] of a viscous level under mgcfd_set_viscosity_model: the caller's to
+                                 write under MGCFD_EDDY_FIELD, read-only (the last stress launch's) under MGCFD_EDDY_SMAGORINSKY */ };
 
 /* Solver options (mgcfd_set_option) */
 enum {
@@ -532,7 +534,7 @@ int mgcfd_run_cycles_from(mgcfd_solver *s, int top, int cycles, double *rms_out)
 int mgcfd_prolong_state(mgcfd_solver *s, int fine_level);
 int mgcfd_full_multigrid(mgcfd_solver *s, const int *cycles, double *rms_out);
 /* Laminar viscous terms: the Navier-Stokes stresses, heat conduction and a no-slip wall.  No reference counterpart.  Per solver:
- * mu > 0 (dynamic viscosity in the solver's units, constant: no Sutherland law), prandtl > 0, wall (0 = slip, as without the
+ * mu > 0 (dynamic viscosity in the solver's units, constant unless mgcfd_set_viscosity_model sets a law), prandtl > 0, wall (0 = slip, as without the
  * feature; 1 = no-slip, adiabatic), cfl_v > 0 (the viscous step limit, (c)) and levels >= 0: it runs on levels 0 .. levels-1
  * (capped at the number of levels; 0 = off, the other arguments are then ignored), exactly mgcfd_set_jst's levels.  Off by
  * default; with it off the solver launches what it launched and computes the bits it computed.
@@ -586,7 +588,7 @@ int mgcfd_full_multigrid(mgcfd_solver *s, const int *cycles, double *rms_out);
  * mgcfd_sweep_end* return MGCFD_ERR_ARG, and mgcfd_group_create and mgcfd_rank_attach_* refuse the solver.
  * Friction in the surface loads: mgcfd_surface_loads_viscous and its neighbours (mgcfd_surface_loads stays the pressure loads).
  * Out of scope: an edge-direction correction of
- * the face gradient (it needs node coordinates on the device); variable viscosity and turbulence models; viscous flux through
+ * the face gradient (it needs node coordinates on the device); transported turbulence models (variable viscosity: mgcfd_set_viscosity_model); viscous flux through
  * far-field faces; levels split over ranks; graphs and fused stages with viscosity on.
  * The weights are used as the solver holds them: on meshes whose variant makes the reference rescale them at load (every
  * variant but fvcorr) the viscous terms inherit that rescaling as the inviscid ones do; physical statements are made on
@@ -600,6 +602,47 @@ int mgcfd_full_multigrid(mgcfd_solver *s, const int *cycles, double *rms_out);
 int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, double cfl_v, int levels);
 int mgcfd_get_viscous(const mgcfd_solver *s, double *mu, double *prandtl, int *wall, double *cfl_v, int *levels);
 int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double ref_length, double *mu);
+/* Viscosity model: Sutherland's law, a caller-supplied eddy-viscosity field, the Smagorinsky model.  No reference counterpart.
+ * One setting per solver, off by default (law 0, eddy 0): a solver on which the setter is never called launches and computes
+ * what it did.  It applies on exactly the levels mgcfd_set_viscous covers (mu, prandtl, wall, cfl_v and levels stay that
+ * call's) and has no effect while the viscous terms are off; either call may come first, and the model is kept while the terms
+ * are off.  Every operation below is one IEEE-754 double operation (+ - * / sqrt), never contracted under MGCFD_OPT_EXACT = 1.
+ *   law        MGCFD_VISCOSITY_CONSTANT: mu_i = mu;  MGCFD_VISCOSITY_SUTHERLAND: r = T_i / t_ref,
+ *              mu_i = ((mu * (r * sqrt(r))) * (1.0 + s_ratio)) / (r + s_ratio), with T = p / rho
+ *   t_ref > 0  the T at which mu(T) = mu; 0 on input takes the far field's p_inf / rho_inf in use at the call (the getter reports
+ *              the value taken; a later mgcfd_set_free_stream does not change it)
+ *   s_ratio    Sutherland's constant over the reference temperature (MGCFD_SUTHERLAND_S = 110.4 K / 288.15 K)
+ *   eddy       MGCFD_EDDY_NONE: mut_i = +0.0;  MGCFD_EDDY_FIELD: mut_i = MGCFD_ARR_EDDY_VISCOSITY[i], the caller's array;
+ *              MGCFD_EDDY_SMAGORINSKY: with G of pass 1, sxy = 0.5 * (G[u][y] + G[v][x]), sxz, syz likewise,
+ *              ss = ((G[u][x]^2 + G[v][y]^2) + G[w][z]^2) + 2.0 * ((sxy^2 + sxz^2) + syz^2),
+ *              mut_i = (((cs * cs) * d2_i) * rho_i) * sqrt(2.0 * ss), d2_i = cbrt(vol_i) * cbrt(vol_i) from the host's libm at
+ *              enable; written to MGCFD_ARR_EDDY_VISCOSITY[i] by every stress launch (a stage or mgcfd_compute_fluxes).  No wall
+ *              damping: near a no-slip wall the model overpredicts mut.
+ *   prandtl_t  the turbulent Prandtl number
+ * Pass 1 of the viscous terms then finishes S_i with me_i = mu_i + mut_i on the six stresses and
+ * kap_i = (GAMMA / (GAMMA - 1.0)) * (mu_i / prandtl + mut_i / prandtl_t) on the heat flux; S keeps its twelve columns, pass 2
+ * and everything behind it are unchanged.  The wall-stress pass of the friction loads applies the same expressions (eddy 1 read
+ * at the wall node, eddy 2 formed locally and stored nowhere), so mgcfd_wall_stress stays the wall rows of S.  The step limit
+ * becomes, in the same place: a = (4.0/3.0) * (mu_i + mut_i), b = GAMMA * (mu_i / prandtl + mut_i / prandtl_t), d = a < b ? b : a,
+ * sf_i = min(sf_i, ((cfl_v * rho_i) * g_i) / d) with mu_i from the level's variables at that moment and mut_i as the array
+ * stands (under Smagorinsky: the last stress launch's values, +0.0 from the enabling call until the first one).
+ * MGCFD_ARR_EDDY_VISCOSITY [nel][1] exists per covered level while eddy != 0: +0.0 at allocation and whenever the eddy mode
+ * changes; under MGCFD_EDDY_FIELD readable and writable (values are not checked; each level has its own array, nothing is
+ * restricted between levels), under MGCFD_EDDY_SMAGORINSKY read-only; otherwise MGCFD_ERR_ARG.  The arrays (and d2) are
+ * allocated while both the viscous terms and a non-default model are on and released when either goes off.
+ * The setter synchronises and drops captured graphs.  MGCFD_ERR_ARG, and nothing changed: an unknown law or eddy; t_ref negative
+ * or not finite; s_ratio (law 1), cs (eddy 2) or prandtl_t (eddy 1, 2) not finite and positive; while a kernel-granular sweep
+ * is under way; a non-default model on a solver made by mgcfd_create_partitioned* or attached to a group or as a rank.
+ * mgcfd_get_viscosity_model: any pointer may be NULL.
+ * Out of scope: wall damping, WALE and dynamic procedures; transported models and wall distance; restriction of an eddy field
+ * between levels; split levels, groups and ranks; graphs and fused stages with viscosity on. */
+enum { MGCFD_VISCOSITY_CONSTANT = 0, MGCFD_VISCOSITY_SUTHERLAND = 1 };
+enum { MGCFD_EDDY_NONE = 0, MGCFD_EDDY_FIELD = 1, MGCFD_EDDY_SMAGORINSKY = 2 };
+#define MGCFD_SUTHERLAND_S 0.3831
+#define MGCFD_SMAGORINSKY_CS 0.17
+#define MGCFD_PRANDTL_TURBULENT 0.9
+int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_ratio, int eddy, double cs, double prandtl_t);
+int mgcfd_get_viscosity_model(const mgcfd_solver *s, int *law, double *t_ref, double *s_ratio, int *eddy, double *cs, double *prandtl_t);
 int mgcfd_fas_restrict(mgcfd_solver *s, int fine_level);
 int mgcfd_fas_prolong(mgcfd_solver *s, int fine_level);
 
@@ -771,7 +814,9 @@ int mgcfd_bench_residual_smoothing(mgcfd_solver *s, int level, int kind, int lau
  * fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where it is off. */
 int mgcfd_bench_jst(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Diagnostic: the same for one of the viscous terms' launches (kind 0: the stress launch, 1: the viscous-flux launch, which adds
- * into fluxes[] launch after launch; the state stays), behind one flux launch with both passes.  MGCFD_ERR_ARG where they are off. */
+ * into fluxes[] launch after launch; the state stays; 2: the step limit's launch on the level's step factors, k_viscous_clamp or
+ * under a non-default viscosity model k_viscous_clamp_variable), behind one flux launch with both passes.  The stress launch is
+ * the instantiation the viscosity model selects.  MGCFD_ERR_ARG where they are off. */
 int mgcfd_bench_viscous(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Diagnostic: the same for one of FAS multigrid's launches between `fine_level` and the level above it, behind one
  * mgcfd_fas_restrict (kind 0: k_restrict_fas, 1: the forcing launch, 2: the forced update k_time_step_src<0, true> on the

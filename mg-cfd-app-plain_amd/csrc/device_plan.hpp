@@ -131,6 +131,21 @@ struct JstStep {
     double kappa2 = 0.0, kappa4 = 0.0;
 };
 
+// The viscosity model of a level (mgcfd_set_viscosity_model): how pass 1 of the viscous terms, the wall-stress pass and the
+// step limit form a node's viscosity mu_i and eddy viscosity mut_i.  law 0 and eddy 0 is the constant viscosity: nothing
+// here is read then.
+struct ViscosityModel {
+    int law = 0;                              // 0 constant, 1 Sutherland: mu_i = ((mu * (r * sqrt(r))) * one_plus_s) / (r + s), r = T_i / t_ref
+    int eddy = 0;                             // 0 none, 1 the caller's field (mut read), 2 Smagorinsky (mut written by the stress launch)
+    double t_ref = 1.0, s = 0.0, one_plus_s = 1.0;
+    double c2 = 0.0;                          // cs * cs
+    double cp = 0.0;                          // GAMMA / (GAMMA - 1.0)
+    double prandtl = 1.0, prandtl_t = 1.0;
+    double *mut = nullptr;                    // eddy_viscosity [stride]
+    const double *d2 = nullptr;               // [stride] cbrt(vol) * cbrt(vol), from the host
+    __host__ __device__ bool variable() const { return law != 0 || eddy != 0; }
+};
+
 // The two launches of the viscous terms (kernels.hip: k_viscous_stress_tile, k_viscous_flux_tile; mgcfd_set_viscous): the stress
 // launch writes s from w; the flux launch reads s and adds the viscous flux V into components 1..4 of fluxes.
 struct ViscousStep {
@@ -139,6 +154,16 @@ struct ViscousStep {
     const double *volumes = nullptr;          // [stride]
     double *fluxes = nullptr;                 // the stage's fluxes F (+ C) [5][stride] (flux launch only): F = F + V
     double mu = 0.0, kappa = 0.0;             // kappa = (mu * GAMMA) / ((GAMMA - 1) * prandtl), formed on the host
+    ViscosityModel model;                     // the stress launch only; constant: the launch reads none of it
+};
+
+// The variable step limit (k_viscous_clamp_variable): sf = min(sf, ((cfl_v * rho) * g) / d), d from mu_i and mut_i.
+struct ViscousClamp {
+    const double *q = nullptr;                // the level's variables [5][stride]
+    const double *g = nullptr;                // [stride] cbrt(vol)^2 / vol
+    double *step_factors = nullptr;
+    double mu = 0.0, cfl_v = 0.0;
+    ViscosityModel model;
 };
 
 // The physical-time source of dual time stepping (kernels.hip: k_time_step_src, k_dual_source; mgcfd_set_dual_time):
@@ -218,6 +243,7 @@ struct WallStress {
     const double *volumes = nullptr;      // [stride]
     double mu = 0.0, kappa = 0.0;
     double *sw = nullptr;                 // [12][wn.n]
+    ViscosityModel model;                 // as the stress launch applies it; model.mut is read under eddy 1 and never written
 };
 
 // Pressure and friction loads in one launch (k_surface_loads_viscous): twelve sums Fp(3) Mp(3) | Fv(3) Mv(3) over the

@@ -2651,6 +2651,8 @@ k_jst_dissipation_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, 
 //   k_viscous_stress_tile   A[phi][d] = sum (phi_j - phi_i) n_d for phi in (u, v, w, T = p / rho);  G = (0.5 A) / vol;
 //                           S_i = (u, v, w, txx, tyy, tzz, txy, txz, tyz, qx, qy, qz): Stokes' stresses at constant mu and
 //                           q = kappa grad T, finished per node so that pass 2 stages twelve doubles and not seventeen.
+//                           Under a viscosity model (mgcfd_set_viscosity_model) mu and kappa are per-node factors formed here,
+//                           where the gradients already are: the kernel's VAR instantiation.
 //   k_viscous_flux_tile     V_i[1..3] = sum tau_bar . n,  V_i[4] = sum (tau_bar . v_bar + q_bar) . n,  bars = 0.5 (S_i + S_j);
 //                           fluxes_i[1..4] = fluxes_i[1..4] + V_i[1..4].
 // LDS, one field per array as in k_smooth_tile (a slot's doubles 8 B apart): the stress launch stages u, v, w, T derived
@@ -2669,7 +2671,27 @@ __device__ __forceinline__ Primitive primitive_of(const double *__restrict__ q, 
     return r;
 }
 
-template <bool TAIL>
+// The viscosity model (mgcfd_set_viscosity_model; INTEGRATION.md "Variable viscosity"): a node's viscosity by the law and its
+// eddy viscosity under Smagorinsky, one IEEE operation each in the definition's order; the stress launch, the wall-stress
+// launch and the variable step limit share them.
+__device__ __forceinline__ double viscosity_of(const ViscosityModel &m, double mu, double T)
+{
+    if (m.law == 0) return mu;
+    const double r = T / m.t_ref;
+    return ((mu * (r * sqrt(r))) * m.one_plus_s) / (r + m.s);
+}
+__device__ __forceinline__ double smagorinsky_of(const ViscosityModel &m, double d2, double rho, double gux, double guy, double guz,
+                                                 double gvx, double gvy, double gvz, double gwx, double gwy, double gwz)
+{
+    const double sxy = 0.5 * (guy + gvx), sxz = 0.5 * (guz + gwx), syz = 0.5 * (gvz + gwy);
+    const double ss = ((gux * gux + gvy * gvy) + gwz * gwz) + 2.0 * ((sxy * sxy + sxz * sxz) + syz * syz);
+    return ((m.c2 * d2) * rho) * sqrt(2.0 * ss);
+}
+
+// VAR: the variable instantiation — after the row walk mu_i by the law, mut_i read (eddy 1) or formed and written (eddy 2; pad
+// lanes of the last tile write +0.0), me_i = mu_i + mut_i on the stresses and kap_i on the heat flux.  VAR = false is the
+// constant-viscosity kernel, which reads nothing of a.model.
+template <bool TAIL, bool VAR>
 __global__ void __launch_bounds__(kBlock, 4)
 k_viscous_stress_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
                       const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
@@ -2738,11 +2760,24 @@ k_viscous_stress_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, i
     const double div = (gux + gvy) + gwz;
     const double tt = (2.0 / 3.0) * div;
     const bool present = i < nel;
+    double mu_e = a.mu, kap = a.kappa;
+    if (VAR) {
+        const ViscosityModel &m = a.model;
+        const double mu_i = viscosity_of(m, a.mu, me.T);
+        double mut = 0.0;
+        if (m.eddy == 1) mut = m.mut[i];
+        else if (m.eddy == 2) {
+            mut = smagorinsky_of(m, m.d2[i], a.w[i], gux, guy, guz, gvx, gvy, gvz, gwx, gwy, gwz);
+            m.mut[i] = present ? mut : 0.0;
+        }
+        mu_e = mu_i + mut;
+        kap = m.cp * (mu_i / m.prandtl + mut / m.prandtl_t);
+    }
     double out[12];
     out[0] = me.u; out[1] = me.v; out[2] = me.w;
-    out[3] = a.mu * (2.0 * gux - tt); out[4] = a.mu * (2.0 * gvy - tt); out[5] = a.mu * (2.0 * gwz - tt);
-    out[6] = a.mu * (guy + gvx); out[7] = a.mu * (guz + gwx); out[8] = a.mu * (gvz + gwy);
-    out[9] = a.kappa * gtx; out[10] = a.kappa * gty; out[11] = a.kappa * gtz;
+    out[3] = mu_e * (2.0 * gux - tt); out[4] = mu_e * (2.0 * gvy - tt); out[5] = mu_e * (2.0 * gwz - tt);
+    out[6] = mu_e * (guy + gvx); out[7] = mu_e * (guz + gwx); out[8] = mu_e * (gvz + gwy);
+    out[9] = kap * gtx; out[10] = kap * gty; out[11] = kap * gtz;
 #pragma unroll
     for (int f = 0; f < 12; f++) a.s[f * stride + i] = present ? out[f] : 0.0;
 }
@@ -2840,6 +2875,24 @@ k_viscous_clamp(int64_t nel, double k0, const double *__restrict__ rho, const do
     if (i >= nel) return;
     const double sf = step_factors[i], cap = (k0 * rho[i]) * g[i];
     step_factors[i] = cap < sf ? cap : sf;              // (a NaN factor stays NaN, as the invalid-state check expects)
+}
+
+// The limit under a variable viscosity (mgcfd_set_viscosity_model): sf = min(sf, ((cfl_v * rho) * g) / d), d = max((4/3) (mu_i +
+// mut_i), GAMMA (mu_i / prandtl + mut_i / prandtl_t)) with mu_i by the law from the level's state and mut_i as the array holds it.
+__global__ void __launch_bounds__(kBlock)
+k_viscous_clamp_variable(int64_t nel, int64_t stride, ViscousClamp a)
+{
+#pragma clang fp contract(off)
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= nel) return;
+    const double rho = a.q[i];
+    const Derived dv = derive(rho, a.q[stride + i], a.q[2 * stride + i], a.q[3 * stride + i], a.q[4 * stride + i]);
+    const double mu_i = viscosity_of(a.model, a.mu, dv.p / rho);
+    const double mut = a.model.eddy != 0 ? a.model.mut[i] : 0.0;
+    const double da = (4.0 / 3.0) * (mu_i + mut), db = kGamma * (mu_i / a.model.prandtl + mut / a.model.prandtl_t);
+    const double d = da < db ? db : da;
+    const double sf = a.step_factors[i], cap = ((a.cfl_v * rho) * a.g[i]) / d;
+    a.step_factors[i] = cap < sf ? cap : sf;            // (a NaN factor stays NaN, as the invalid-state check expects)
 }
 
 // The no-slip wall: momentum +0.0 at the n listed nodes of q (and of q2, where given: FAS's copy of a restricted state);
@@ -3339,11 +3392,21 @@ k_wall_stress(int64_t stride, const double *__restrict__ q, WallStress a)
     const double gtx = (0.5 * tx) / vol, gty = (0.5 * ty) / vol, gtz = (0.5 * tz) / vol;
     const double div = (gux + gvy) + gwz;
     const double tt = (2.0 / 3.0) * div;
+    double mu_e = a.mu, kap = a.kappa;
+    if (a.model.variable()) {                          // the stress launch's model, eddy 2 formed here and stored nowhere
+        const ViscosityModel &m = a.model;
+        const double mu_i = viscosity_of(m, a.mu, me.T);
+        double mut = 0.0;
+        if (m.eddy == 1) mut = m.mut[i];
+        else if (m.eddy == 2) mut = smagorinsky_of(m, m.d2[i], q[i], gux, guy, guz, gvx, gvy, gvz, gwx, gwy, gwz);
+        mu_e = mu_i + mut;
+        kap = m.cp * (mu_i / m.prandtl + mut / m.prandtl_t);
+    }
     double out[12];
     out[0] = me.u; out[1] = me.v; out[2] = me.w;
-    out[3] = a.mu * (2.0 * gux - tt); out[4] = a.mu * (2.0 * gvy - tt); out[5] = a.mu * (2.0 * gwz - tt);
-    out[6] = a.mu * (guy + gvx); out[7] = a.mu * (guz + gwx); out[8] = a.mu * (gvz + gwy);
-    out[9] = a.kappa * gtx; out[10] = a.kappa * gty; out[11] = a.kappa * gtz;
+    out[3] = mu_e * (2.0 * gux - tt); out[4] = mu_e * (2.0 * gvy - tt); out[5] = mu_e * (2.0 * gwz - tt);
+    out[6] = mu_e * (guy + gvx); out[7] = mu_e * (guz + gwx); out[8] = mu_e * (gvz + gwy);
+    out[9] = kap * gtx; out[10] = kap * gty; out[11] = kap * gtz;
 #pragma unroll
     for (int f = 0; f < 12; f++) a.sw[f * a.wn.n + k] = out[f];
 }
@@ -4107,10 +4170,11 @@ void launch_jst_dissipation(hipStream_t st, const DevicePlan &p, const JstStep &
 // the two launches of the viscous terms: S from W; then fluxes[1..4] += V; the step-factor limit and the no-slip wall
 void launch_viscous_stress(hipStream_t st, const DevicePlan &p, const ViscousStep &a)
 {
-    with_bool(p.has_tail != 0, [&](auto tail) {
-        hipLaunchKernelGGL((k_viscous_stress_tile<decltype(tail)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+    // (constant viscosity: the instantiation without the model)
+    with_bool(p.has_tail != 0, [&](auto tail) { with_bool(a.model.variable(), [&](auto var) {
+        hipLaunchKernelGGL((k_viscous_stress_tile<decltype(tail)::value, decltype(var)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
                            p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
-    });
+    }); });
 }
 void launch_viscous_flux(hipStream_t st, const DevicePlan &p, const ViscousStep &a)
 {
@@ -4121,6 +4185,8 @@ void launch_viscous_flux(hipStream_t st, const DevicePlan &p, const ViscousStep 
 }
 void launch_viscous_clamp(hipStream_t st, int64_t nel, double k0, const double *rho, const double *g, double *sf)
 { hipLaunchKernelGGL(k_viscous_clamp, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, k0, rho, g, sf); }
+void launch_viscous_clamp_variable(hipStream_t st, int64_t nel, int64_t stride, const ViscousClamp &a)
+{ hipLaunchKernelGGL(k_viscous_clamp_variable, dim3(grid_for(nel)), dim3(kBlock), 0, st, nel, stride, a); }
 void launch_viscous_wall(hipStream_t st, int64_t n, int64_t stride, const int32_t *nodes, double *q, double *q2,
                          const double *old_variables, double *residuals)
 { if (n > 0) hipLaunchKernelGGL(k_viscous_wall, dim3(grid_for(n)), dim3(kBlock), 0, st, n, stride, nodes, q, q2, old_variables, residuals); }

@@ -29,6 +29,7 @@
     void launch_viscous_stress(hipStream_t, const DevicePlan &, const ViscousStep &);                                \
     void launch_viscous_flux(hipStream_t, const DevicePlan &, const ViscousStep &);                                  \
     void launch_viscous_clamp(hipStream_t, int64_t nel, double k0, const double *rho, const double *g, double *sf);  \
+    void launch_viscous_clamp_variable(hipStream_t, int64_t nel, int64_t stride, const ViscousClamp &);              \
     void launch_viscous_wall(hipStream_t, int64_t n, int64_t stride, const int32_t *nodes, double *q, double *q2,    \
                              const double *old_variables, double *residuals);                                        \
     void launch_time_step_src(hipStream_t, int64_t nel, int64_t stride, int j, const double *sf,                     \

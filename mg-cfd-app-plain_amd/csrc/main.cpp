@@ -77,6 +77,12 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool no_slip = false;
     int viscous_levels = 1;
     bool viscous() const { return viscosity_given || reynolds_given; }
+    // the viscosity model: --sutherland with --sutherland-tref X and --sutherland-s X, --smagorinsky [CS], --prandtl-turbulent X and
+    // the config keys sutherland (Y) / sutherland_tref / sutherland_s / smagorinsky (Y or CS) / prandtl_turbulent
+    bool sutherland = false, smagorinsky = false;
+    bool model_extras_given = false;                        // --sutherland-tref / --sutherland-s / --prandtl-turbulent
+    double sutherland_tref = 0.0, sutherland_s = MGCFD_SUTHERLAND_S, smagorinsky_cs = MGCFD_SMAGORINSKY_CS, prandtl_turbulent = MGCFD_PRANDTL_TURBULENT;
+    bool viscosity_model() const { return sutherland || smagorinsky; }
     bool loads_friction = false;      // --loads-friction: the friction loads beside the pressure loads in surface_loads.* and polar.csv (one GPU)
     bool output_surface = false;      // --output-surface: Cp and Cf per wall node of level 0 into surface.* (one GPU)
     size_t loads_width() const { return loads_friction ? 12 : 6; }
@@ -269,6 +275,17 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         }
         else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
     }
+    else if (key == "sutherland") { if (value == "Y") c.sutherland = true; }
+    else if (key == "smagorinsky") {
+        if (value == "Y") c.smagorinsky = true;
+        else if (parse_positive(value.c_str(), &c.smagorinsky_cs)) c.smagorinsky = true;
+        else if (value != "N") { std::fprintf(stderr, "ERROR: smagorinsky = '%s': expected Y or a finite constant above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "sutherland_tref" || key == "sutherland_s" || key == "prandtl_turbulent") {
+        double *dst = key == "sutherland_tref" ? &c.sutherland_tref : key == "sutherland_s" ? &c.sutherland_s : &c.prandtl_turbulent;
+        if (parse_positive(value.c_str(), dst)) c.model_extras_given = true;
+        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
+    }
     else if (key == "no_slip") { if (value == "Y") { c.no_slip = true; c.viscous_extras_given = true; } }
     else if (key == "viscous_levels") {
         if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.viscous_levels)) c.viscous_extras_given = true;
@@ -415,6 +432,12 @@ void print_help()
         "                                   config key viscous_cfl)\n"
         "  --viscous-levels=N               the multigrid levels 0 ... N-1 the viscous terms run on (default 1; 0 = off; config key\n"
         "                                   viscous_levels)\n"
+        "  --sutherland                     with the viscous terms: Sutherland's law mu(T), T = p / rho (config key sutherland = Y); one GPU\n"
+        "  --sutherland-tref=X              the T at which mu(T) = MU (default: the free stream's p / rho; config key sutherland_tref)\n"
+        "  --sutherland-s=X                 Sutherland's constant over the reference temperature (default 0.3831; config key sutherland_s)\n"
+        "  --smagorinsky[=CS]               with the viscous terms: the Smagorinsky eddy viscosity, constant CS (default 0.17), filter width\n"
+        "                                   cbrt(volume), no wall damping (config key smagorinsky = Y or CS); one GPU\n"
+        "  --prandtl-turbulent=X            the turbulent Prandtl number (default 0.9; config key prandtl_turbulent)\n"
         "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
         "                                   (config key physical_time_step): BDF2 in physical time, every step solved in pseudo-time\n"
         "                                   by -g cycles (-g becomes the cycles PER PHYSICAL STEP; an RMS line per cycle as ever,\n"
@@ -483,6 +506,11 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"viscous-cfl", required_argument, nullptr, 1035},
         {"no-slip", no_argument, nullptr, 1036},
         {"viscous-levels", required_argument, nullptr, 1037},
+        {"sutherland", no_argument, nullptr, 1040},
+        {"sutherland-tref", required_argument, nullptr, 1041},
+        {"sutherland-s", required_argument, nullptr, 1042},
+        {"prandtl-turbulent", required_argument, nullptr, 1043},
+        {"smagorinsky", optional_argument, nullptr, 1044},
         {"loads-friction", no_argument, nullptr, 1038},
         {"output-surface", no_argument, nullptr, 1039},
         {nullptr, 0, nullptr, 0}};
@@ -649,6 +677,28 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 c.viscous_extras_given = true;
                 break;
             case 1038: c.loads_friction = true; break;
+            case 1040: c.sutherland = true; break;
+            case 1041: case 1042: case 1043: {
+                static const char *const names[] = {"sutherland-tref", "sutherland-s", "prandtl-turbulent"};
+                double *const dst[] = {&c.sutherland_tref, &c.sutherland_s, &c.prandtl_turbulent};
+                if (!parse_positive(optarg, dst[optc - 1041])) {
+                    std::fprintf(stderr, "ERROR: --%s=%s: expected a finite number above zero\n", names[optc - 1041], optarg);
+                    return false;
+                }
+                c.model_extras_given = true;
+                break;
+            }
+            case 1044: {
+                // --smagorinsky, --smagorinsky=CS or --smagorinsky CS (the next word, where it does not start another option)
+                const char *arg = optarg;
+                if (!arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
+                if (arg && !parse_positive(arg, &c.smagorinsky_cs)) {
+                    std::fprintf(stderr, "ERROR: --smagorinsky=%s: expected a finite constant above zero\n", arg);
+                    return false;
+                }
+                c.smagorinsky = true;
+                break;
+            }
             case 1039: c.output_surface = true; break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
@@ -663,6 +713,14 @@ bool parse_arguments(int argc, char **argv, Config &c)
     }
     if (c.viscous_extras_given && !c.viscous()) {
         std::fprintf(stderr, "ERROR: --ref-length, --prandtl, --no-slip, --viscous-cfl and --viscous-levels need --viscosity MU or --reynolds RE (the viscous terms)\n");
+        return false;
+    }
+    if ((c.viscosity_model() || c.model_extras_given) && !c.viscous()) {
+        std::fprintf(stderr, "ERROR: --sutherland, --smagorinsky and their companions need --viscosity MU or --reynolds RE (the viscous terms)\n");
+        return false;
+    }
+    if (c.viscosity_model() && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: the viscosity model (--sutherland, --smagorinsky) runs on one GPU only: not with --gpus N or --gpus-partition\n");
         return false;
     }
     if (c.loads_friction && !(c.viscous() && c.viscous_levels > 0 && (c.output_loads || c.polar))) {
@@ -961,6 +1019,20 @@ int viscosity_of(const Config &conf, double *mu)
     return rc != MGCFD_OK ? rc : mgcfd_viscosity_from_reynolds(ff17, conf.reynolds, conf.ref_length, mu);
 }
 
+// Sutherland's reference of the run: --sutherland-tref as given, or p / rho of the free stream in use (the library's expression on
+// its far field; the angle of attack does not change it)
+int sutherland_tref_of(const Config &conf, double *t_ref)
+{
+    if (conf.sutherland_tref > 0.0) { *t_ref = conf.sutherland_tref; return MGCFD_OK; }
+    double f[17];
+    const int rc = mgcfd_free_stream_constants(conf.ff_mach, conf.angle(0), f);
+    if (rc != MGCFD_OK) return rc;
+    const double vx = f[1] / f[0], vy = f[2] / f[0], vz = f[3] / f[0];
+    const double speed_sqd = vx * vx + vy * vy + vz * vz;
+    *t_ref = ((1.4 - 1.0) * (f[4] - 0.5 * f[0] * speed_sqd)) / f[0];
+    return MGCFD_OK;
+}
+
 // --gpus N (multi_gpu.cpp): the same outputs as the one-GPU run from N ranks of this process
 int run_on_several_gpus(const Config &conf, mgcfd_mesh *mesh, int levels, int mesh_variant, int problem_size)
 {
@@ -1168,6 +1240,12 @@ int main(int argc, char **argv)
         double mu = 0.0;
         if (viscosity_of(conf, &mu) != MGCFD_OK || mgcfd_set_viscous(solver, mu, conf.prandtl, conf.no_slip ? 1 : 0, conf.viscous_cfl, conf.viscous_levels) != MGCFD_OK)
             return fail("setting the viscous terms");
+        double t_ref = 0.0;
+        if (conf.viscosity_model() && sutherland_tref_of(conf, &t_ref) != MGCFD_OK) return fail("setting the viscosity model");
+        if (conf.viscosity_model() &&
+            mgcfd_set_viscosity_model(solver, conf.sutherland ? MGCFD_VISCOSITY_SUTHERLAND : MGCFD_VISCOSITY_CONSTANT, t_ref, conf.sutherland_s,
+                                      conf.smagorinsky ? MGCFD_EDDY_SMAGORINSKY : MGCFD_EDDY_NONE, conf.smagorinsky_cs, conf.prandtl_turbulent) != MGCFD_OK)
+            return fail("setting the viscosity model");
     }
     if (conf.fas && mgcfd_set_fas(solver, 1) != MGCFD_OK) return fail("switching FAS multigrid on");
     if (conf.cycle_given() && mgcfd_set_cycle(solver, conf.cycle_shape, pre.data(), post.data()) != MGCFD_OK) return fail("setting the multigrid cycle");

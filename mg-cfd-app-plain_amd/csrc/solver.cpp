@@ -196,6 +196,10 @@ struct DeviceLevel {
     double *visc_s = nullptr, *visc_g = nullptr;
     int32_t *visc_wall = nullptr;
     int64_t n_visc_wall = 0;
+    // ... and, while a non-default viscosity model is set as well (mgcfd_set_viscosity_model): the eddy viscosity [stride] and
+    // d2 = cbrt(vol) * cbrt(vol) [stride]
+    double *visc_mut = nullptr, *visc_d2 = nullptr;
+    int eddy_mode = 0;                   // the model's eddy mode while visc_mut is held (MGCFD_ARR_EDDY_VISCOSITY: who may write it)
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while ordered_rms(): its RMS is summed in original numbering (settle_rms_order)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
@@ -367,12 +371,37 @@ struct mgcfd_solver {
         ViscousStep a;
         a.w = lv.q; a.s = lv.visc_s; a.volumes = lv.volumes; a.fluxes = lv.fluxes;
         a.mu = visc_mu; a.kappa = (visc_mu * 1.4) / ((1.4 - 1.0) * visc_prandtl);
+        a.model = viscosity_model(lv);
         return a;
     }
-    // sf = min(sf, (k0 * rho) * g) on final step factors, before dual time stepping's clamp
+    // The viscosity model (mgcfd_set_viscosity_model): the law of mu(T) and the eddy viscosity, applied per node by the stress
+    // launch, the wall-stress launch and the step limit on the levels the viscous terms cover.  Kept while the terms are off.
+    int vm_law = MGCFD_VISCOSITY_CONSTANT, vm_eddy = MGCFD_EDDY_NONE;
+    double vm_t_ref = 0.0, vm_s = MGCFD_SUTHERLAND_S, vm_cs = MGCFD_SMAGORINSKY_CS, vm_prandtl_t = MGCFD_PRANDTL_TURBULENT;
+    bool variable_viscosity() const { return vm_law != MGCFD_VISCOSITY_CONSTANT || vm_eddy != MGCFD_EDDY_NONE; }
+    ViscosityModel viscosity_model(const DeviceLevel &lv) const
+    {
+        ViscosityModel m;
+        if (!variable_viscosity()) return m;
+        m.law = vm_law; m.eddy = vm_eddy;
+        m.t_ref = vm_t_ref; m.s = vm_s; m.one_plus_s = 1.0 + vm_s;
+        m.c2 = vm_cs * vm_cs; m.cp = 1.4 / (1.4 - 1.0);
+        m.prandtl = visc_prandtl; m.prandtl_t = vm_prandtl_t;
+        m.mut = lv.visc_mut; m.d2 = lv.visc_d2;
+        return m;
+    }
+    // sf = min(sf, (k0 * rho) * g) on final step factors, before dual time stepping's clamp; under a non-default viscosity
+    // model the limit from mu_i and mut_i per node
     void viscous_clamp(int l)
     {
         DeviceLevel &lv = level(l);
+        if (variable_viscosity()) {
+            ViscousClamp a;
+            a.q = lv.q; a.g = lv.visc_g; a.step_factors = lv.step_factors;
+            a.mu = visc_mu; a.cfl_v = visc_cfl; a.model = viscosity_model(lv);
+            exact::launch_viscous_clamp_variable(stream, lv.info.nel, lv.dp.stride, a);
+            return;
+        }
         const double kv = std::max(4.0 / 3.0, 1.4 / visc_prandtl);
         exact::launch_viscous_clamp(stream, lv.info.nel, visc_cfl / (kv * visc_mu), lv.q, lv.visc_g, lv.step_factors);
     }
@@ -1811,6 +1840,36 @@ int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *le
     return MGCFD_OK;
 }
 
+// The eddy viscosity and d2 of a level are held exactly while the viscous terms cover it and a non-default viscosity model is
+// set: both setters call this once their new state is stored.  A new array holds +0.0; `zero` clears the ones that stay (the
+// eddy mode has changed: the values belonged to the old one).
+static void settle_viscosity_arrays(mgcfd_solver *s, bool zero)
+{
+    for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
+        DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+        if (!s->viscous_on(l) || !s->variable_viscosity()) {
+            lv.mem.release(lv.visc_mut); lv.mem.release(lv.visc_d2);
+            lv.eddy_mode = 0;
+            continue;
+        }
+        lv.eddy_mode = s->vm_eddy;
+        const size_t stride = static_cast<size_t>(lv.dp.stride);
+        if (lv.visc_mut) {
+            if (zero) HIP_CHECK(hipMemsetAsync(lv.visc_mut, 0, sizeof(double) * stride, s->stream));
+            continue;
+        }
+        lv.visc_mut = lv.mem.alloc<double>(stride);
+        HIP_CHECK(hipMemsetAsync(lv.visc_mut, 0, sizeof(double) * stride, s->stream));
+        // d2 = cbrt(vol) * cbrt(vol) from the host libm's cube roots the step factor uses (pad lanes: 1.0)
+        std::vector<double> cb(stride), d2(stride, 1.0);
+        HIP_CHECK(hipMemcpyAsync(cb.data(), lv.cbrt_vol, sizeof(double) * stride, hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        for (int64_t k = 0; k < lv.info.nel; k++) d2[static_cast<size_t>(k)] = cb[static_cast<size_t>(k)] * cb[static_cast<size_t>(k)];
+        lv.visc_d2 = lv.mem.upload(d2);
+    }
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+}
+
 // ---- laminar viscous terms: viscosity, Prandtl number, wall condition, step limit and the levels they run on ----
 int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, double cfl_v, int levels)
 {
@@ -1859,6 +1918,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
         s->visc_prandtl = n > 0 ? prandtl : 0.0;
         s->visc_cfl = n > 0 ? cfl_v : 0.0;
         s->visc_wall = n > 0 ? wall : 0;
+        settle_viscosity_arrays(s, false);
         settle_rms_order(s);
         drop_look_ahead(s);
         // the no-slip condition holds from the start
@@ -1879,6 +1939,48 @@ int mgcfd_get_viscous(const mgcfd_solver *s, double *mu, double *prandtl, int *w
     if (wall) *wall = s->visc_wall;
     if (cfl_v) *cfl_v = s->visc_cfl;
     if (levels) *levels = s->visc_levels;
+    return MGCFD_OK;
+}
+// ---- viscosity model: Sutherland's law, a caller's eddy-viscosity field, Smagorinsky ----
+int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_ratio, int eddy, double cs, double prandtl_t)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        auto positive = [](double x) { return std::isfinite(x) && x > 0.0; };
+        if (law != MGCFD_VISCOSITY_CONSTANT && law != MGCFD_VISCOSITY_SUTHERLAND)
+            throw std::invalid_argument("viscosity model: law must be MGCFD_VISCOSITY_CONSTANT or MGCFD_VISCOSITY_SUTHERLAND");
+        if (eddy != MGCFD_EDDY_NONE && eddy != MGCFD_EDDY_FIELD && eddy != MGCFD_EDDY_SMAGORINSKY)
+            throw std::invalid_argument("viscosity model: eddy must be MGCFD_EDDY_NONE, MGCFD_EDDY_FIELD or MGCFD_EDDY_SMAGORINSKY");
+        if (!std::isfinite(t_ref) || t_ref < 0.0) throw std::invalid_argument("viscosity model: t_ref must be finite and positive, or 0 for the far field's p / rho");
+        if (law == MGCFD_VISCOSITY_SUTHERLAND && !positive(s_ratio)) throw std::invalid_argument("viscosity model: Sutherland's s must be finite and positive");
+        if (eddy == MGCFD_EDDY_SMAGORINSKY && !positive(cs)) throw std::invalid_argument("viscosity model: the Smagorinsky constant cs must be finite and positive");
+        if (eddy != MGCFD_EDDY_NONE && !positive(prandtl_t)) throw std::invalid_argument("viscosity model: the turbulent Prandtl number must be finite and positive");
+        const bool variable = law != MGCFD_VISCOSITY_CONSTANT || eddy != MGCFD_EDDY_NONE;
+        const double t_taken = t_ref == 0.0 ? s->p_inf / s->ff.var[0] : t_ref;
+        if (!positive(t_taken)) throw std::invalid_argument("viscosity model: the far field's p / rho is not finite and positive");
+        if (variable && (s->partitioned || s->comm))
+            throw std::invalid_argument("viscosity model: not on a partitioned solver, a group member or a rank (the viscous terms do not run there)");
+        quiesce(s, "viscosity model");
+        const bool eddy_changed = eddy != s->vm_eddy;
+        s->vm_law = law; s->vm_eddy = eddy;
+        s->vm_t_ref = t_taken;
+        // (a value the model does not use is kept as given where it could be used, the default otherwise)
+        s->vm_s = positive(s_ratio) ? s_ratio : MGCFD_SUTHERLAND_S;
+        s->vm_cs = positive(cs) ? cs : MGCFD_SMAGORINSKY_CS;
+        s->vm_prandtl_t = positive(prandtl_t) ? prandtl_t : MGCFD_PRANDTL_TURBULENT;
+        settle_viscosity_arrays(s, eddy_changed);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_viscosity_model(const mgcfd_solver *s, int *law, double *t_ref, double *s_ratio, int *eddy, double *cs, double *prandtl_t)
+{
+    REQUIRE(s);
+    if (law) *law = s->vm_law;
+    if (t_ref) *t_ref = s->vm_t_ref;
+    if (s_ratio) *s_ratio = s->vm_s;
+    if (eddy) *eddy = s->vm_eddy;
+    if (cs) *cs = s->vm_cs;
+    if (prandtl_t) *prandtl_t = s->vm_prandtl_t;
     return MGCFD_OK;
 }
 int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double ref_length, double *mu)
@@ -2319,6 +2421,7 @@ static void launch_wall_stress(mgcfd_solver *s, int l)
     WallStress a;
     a.wn = lv.wp->wn; a.volumes = lv.volumes; a.sw = lv.wp->sw;
     a.mu = s->visc_mu; a.kappa = (s->visc_mu * 1.4) / ((1.4 - 1.0) * s->visc_prandtl);
+    a.model = s->viscosity_model(lv);
     exact::launch_wall_stress(s->stream, lv.dp.stride, lv.q, a);
 }
 
@@ -2733,6 +2836,10 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.visc_s) throw std::invalid_argument("MGCFD_ARR_VISCOUS_STRESS: the viscous terms are off on this level (mgcfd_set_viscous)");
             *ncols = 12;
             return lv.visc_s;
+        case MGCFD_ARR_EDDY_VISCOSITY:
+            if (!lv.visc_mut || !lv.eddy_mode) throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: no eddy viscosity on this level (mgcfd_set_viscosity_model with an eddy mode, on a level mgcfd_set_viscous covers)");
+            *ncols = 1;
+            return lv.visc_mut;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2774,6 +2881,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
             throw std::invalid_argument("MGCFD_ARR_FAS_*: read-only (every FAS restriction overwrites them)");
         if (which == MGCFD_ARR_VISCOUS_STRESS)
             throw std::invalid_argument("MGCFD_ARR_VISCOUS_STRESS: read-only (every flux launch of a viscous level overwrites it)");
+        if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SMAGORINSKY)
+            throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under Smagorinsky (every flux launch of a viscous level overwrites it)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -2813,6 +2922,8 @@ int mgcfd_array_written(mgcfd_solver *s, int level, int which)
         int nc = 0;
         (void)(s->settle_residuals(lv), array_ptr(lv, which, &nc));
         if (which == MGCFD_ARR_VOLUMES) throw std::invalid_argument("volumes are fixed at creation");
+        if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SMAGORINSKY)
+            throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under Smagorinsky (every flux launch of a viscous level overwrites it)");
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
     });
@@ -3022,14 +3133,15 @@ int mgcfd_bench_viscous(mgcfd_solver *s, int level, int kind, int launches, doub
         s->use_device();
         DeviceLevel &lv = s->level(level);
         if (!s->viscous_on(level)) throw std::invalid_argument("the viscous terms are off on this level: switch them on first (mgcfd_set_viscous)");
-        if (kind < 0 || kind > 1) throw std::invalid_argument("viscous launch kind: 0 stress, 1 viscous flux");
+        if (kind < 0 || kind > 2) throw std::invalid_argument("viscous launch kind: 0 stress, 1 viscous flux, 2 the step limit");
         s->k().flux(s->stream, lv.dp, lv.q, s->ff, lv.fluxes, 7, 0, s->variant_for(lv) & ~4, nullptr, nullptr);
         const ViscousStep st = s->viscous_step(lv);
         s->k().viscous_stress(s->stream, lv.dp, st);
         s->k().viscous_flux(s->stream, lv.dp, st);
         *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) s->k().viscous_stress(s->stream, lv.dp, st);
-            else s->k().viscous_flux(s->stream, lv.dp, st);
+            else if (kind == 1) s->k().viscous_flux(s->stream, lv.dp, st);
+            else s->viscous_clamp(level);            // (a minimum: the step factors stay what the first launch left)
         });
         lv.fluxes_zero = false;
         lv.fluxes_stale = false;

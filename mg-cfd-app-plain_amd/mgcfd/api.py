@@ -25,8 +25,8 @@ RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
-       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14}
-NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12}      # (every other array: NVAR)
+       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15}
+NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1}      # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -203,6 +203,9 @@ _SIGNATURES = [
     ("mgcfd_get_viscous", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                     C.POINTER(C.c_int)]),
     ("mgcfd_viscosity_from_reynolds", C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    ("mgcfd_set_viscosity_model", C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),
+    ("mgcfd_get_viscosity_model", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("mgcfd_bench_viscous", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_surface_loads_viscous", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_run_cycles_loads_viscous", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
@@ -403,6 +406,9 @@ def free_stream_constants(mach: float, alpha_deg: float) -> np.ndarray:
 
 
 VISCOUS_PRANDTL, VISCOUS_CFL = 0.72, 0.25         # MGCFD_VISCOUS_PRANDTL, MGCFD_VISCOUS_CFL
+SUTHERLAND_S, SMAGORINSKY_CS, PRANDTL_TURBULENT = 0.3831, 0.17, 0.9     # MGCFD_SUTHERLAND_S, MGCFD_SMAGORINSKY_CS, MGCFD_PRANDTL_TURBULENT
+_VISCOSITY_LAWS = {"constant": 0, "sutherland": 1}      # MGCFD_VISCOSITY_*
+_EDDY_MODES = {"none": 0, "field": 1, "smagorinsky": 2}   # MGCFD_EDDY_*
 
 
 def viscosity_from_reynolds(ff17, reynolds: float, ref_length: float = 1.0) -> float:
@@ -773,6 +779,26 @@ class Solver:
         self._c(self.lib.mgcfd_get_viscous(self.handle, C.byref(mu), C.byref(pr), C.byref(w), C.byref(cv), C.byref(n)))
         return mu.value, pr.value, bool(w.value), cv.value, n.value
 
+    def set_viscosity_model(self, law="constant", t_ref: Optional[float] = None, s: float = SUTHERLAND_S, eddy="none",
+                            cs: float = SMAGORINSKY_CS, prandtl_t: float = PRANDTL_TURBULENT):
+        """The viscosity model of the levels ``set_viscous`` covers (mgcfd_set_viscosity_model).  ``law``: ``"constant"`` or
+        ``"sutherland"`` (``mu(T) = mu * (T / t_ref)^1.5 * (1 + s) / (T / t_ref + s)`` with ``T = p / rho``; ``t_ref=None`` takes
+        the far field's ``p / rho`` in use now, ``s`` is Sutherland's constant over the reference temperature).  ``eddy``:
+        ``"none"``, ``"field"`` (the caller writes the level's ``"eddy_viscosity"`` array) or ``"smagorinsky"`` (constant ``cs``,
+        filter width ``cbrt(vol)``, no wall damping; ``"eddy_viscosity"`` is then read-only).  ``prandtl_t`` is the turbulent
+        Prandtl number.  The defaults switch the model off.  No effect while the viscous terms are off; kept across
+        ``set_viscous``.  Captured graphs are dropped.  Not on partitioned solvers, group members or ranks."""
+        self._c(self.lib.mgcfd_set_viscosity_model(self.handle, _VISCOSITY_LAWS.get(law, law), 0.0 if t_ref is None else float(t_ref),
+                                                   float(s), _EDDY_MODES.get(eddy, eddy), float(cs), float(prandtl_t)))
+
+    def viscosity_model(self) -> dict:
+        """``law``, ``t_ref`` (the value taken), ``s``, ``eddy``, ``cs`` and ``prandtl_t`` in use (mgcfd_get_viscosity_model)."""
+        law, eddy = C.c_int(), C.c_int()
+        t, s, cs, pt = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        self._c(self.lib.mgcfd_get_viscosity_model(self.handle, C.byref(law), C.byref(t), C.byref(s), C.byref(eddy), C.byref(cs), C.byref(pt)))
+        return {"law": {v: k for k, v in _VISCOSITY_LAWS.items()}[law.value], "t_ref": t.value, "s": s.value,
+                "eddy": {v: k for k, v in _EDDY_MODES.items()}[eddy.value], "cs": cs.value, "prandtl_t": pt.value}
+
     def set_dual_time(self, dt: float, clamp: float = 2.0 / 3.0):
         """Time-accurate runs (mgcfd_set_dual_time): every stage's update carries the BDF source of the physical step ``dt`` and
         the pseudo step is clamped to ``clamp * dt / vol``; ``dt=0`` switches it off and releases the time levels.  The state
@@ -825,7 +851,7 @@ class Solver:
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
-              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None) -> List[dict]:
+              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
@@ -833,7 +859,11 @@ class Solver:
         last cycle against that angle's far field).  ``time_step`` / ``cfl`` (None: as the solver has them) are set once,
         before the first angle, and stay (``set_time_step``); likewise ``residual_smoothing=(eps, iterations)``
         (``set_residual_smoothing``), ``jst=(kappa2, kappa4, levels)`` (``set_jst``), ``fas=True / False`` (``set_fas``) and
-        ``viscous=(mu, prandtl, wall, cfl_v, levels)`` or a dict of ``set_viscous``'s keywords (``set_viscous``)."""
+        ``viscous=(mu, prandtl, wall, cfl_v, levels)`` or a dict of ``set_viscous``'s keywords (``set_viscous``) and
+        ``viscosity_model=(law, t_ref, s, eddy, cs, prandtl_t)`` or a dict of ``set_viscosity_model``'s keywords; a ``t_ref`` of
+        None is then the far field's of the solver as the call finds it."""
+        if viscosity_model is not None:
+            self.set_viscosity_model(**viscosity_model) if isinstance(viscosity_model, dict) else self.set_viscosity_model(*viscosity_model)
         if viscous is not None:
             self.set_viscous(**viscous) if isinstance(viscous, dict) else self.set_viscous(*viscous)
         if fas is not None:
@@ -914,7 +944,7 @@ class Solver:
     FAS_LAUNCHES = {"restrict_fas": 0, "forcing": 1, "time_step_fas": 2, "prolong_fas": 3, "restrict": 4, "time_step": 5, "prolong": 6}
 
     def bench_viscous(self, l: int, kind: int, launches: int) -> float:
-        """Mean GPU seconds of one viscous launch of ``kind`` (0 stress, 1 viscous flux) over ``launches`` back-to-back launches
+        """Mean GPU seconds of one viscous launch of ``kind`` (0 stress, 1 viscous flux, 2 the step limit) over ``launches`` back-to-back launches
         under one event pair (mgcfd_bench_viscous); the viscous terms must be on for level ``l``."""
         t = C.c_double()
         self._c(self.lib.mgcfd_bench_viscous(self.handle, l, kind, launches, C.byref(t)))
