@@ -87,19 +87,14 @@ enum {
     MGCFD_OPT_FLUX_VARIANT = 4, /* -1 (default): automatic — 1 (the edge-length factor recomputed: never slower on an
                                    MI355X, faster once a level's rows outgrow the Infinity Cache).  Otherwise a bit set:
                                    bit 0: 0 edge-length factor streamed, 1 recomputed from the weights;
-                                   bit 1: 0 (default) node gather (every edge evaluated from both ends),
-                                   2 edge-once tiles (every edge evaluated once per tile; levels whose tiles
-                                   hold too many edges fall back to the node gather, see
-                                   mgcfd_level_has_edge_once);
                                    bit 2 (4): two-phase design point — edge fluxes written to memory, then a node-centred
-                                   sum (the reference's FLUX_FISSION idea); kernel-granular and unfused sweeps only.
-                                   bit 4 (16): indexed weights — a tile lists every edge's weights once, 24 B, and the
-                                   row entries (4 B) point at them; a design point: the second end point's gather
-                                   through L1 costs more than the bytes it saves (24 us against 17.5);
-                                   bit 5 (32): half rows — every internal edge of a tile evaluated once, by one of its
-                                   end points, the flux terms handed to the other through LDS (k_flux_half; levels that
-                                   qualify, see mgcfd_level_has_half_rows; others run the node gather).
+                                   sum (the reference's FLUX_FISSION idea); kernel-granular and unfused sweeps only;
+                                   bit 3 (8): the indirect_rw probe in its L1-gather form (32-bit neighbour codes).
                                    Every variant above gives bit-identical results.
+                                   bits 1 (2), 4 (16) and 5 (32): removed, refused.  They selected the edge-once tiles, the
+                                   indexed weights and the ordered half-row kernel, three bit-identical layouts that lost to
+                                   the node gather (EXPERIMENTS.md); a value >= 0 with one of them set returns MGCFD_ERR_ARG
+                                   and leaves the option as it was.
                                    bit 6 (64), with MGCFD_OPT_EXACT = 0 only (the bit-identical kernels ignore it): ORDER-FREE
                                    accumulation over the half-row plan (k_flux_free) — every internal edge of a tile evaluated
                                    once, the other end's share added to its LDS sum with fp64 LDS atomics, no ordered hand-over.
@@ -223,10 +218,9 @@ int mgcfd_plan_audit(const mgcfd_level_desc *levels, int nlevels, int mesh_varia
                      const int64_t *const *order_keys, char *report, int64_t report_cap);
 void mgcfd_destroy(mgcfd_solver *s);
 int mgcfd_set_option(mgcfd_solver *s, int option, int value);
-/* *yes = 1 when level `level` can run the edge-once flux variant (MGCFD_OPT_FLUX_VARIANT bit 1). */
-int mgcfd_level_has_edge_once(const mgcfd_solver *s, int level, int *yes);
-/* *yes = 1 when level `level` can run the half-row flux kernel (MGCFD_OPT_FLUX_VARIANT bit 5): no long rows, no halo node
- * left outside LDS, at most 5 edges evaluated per node. */
+/* *yes = 1 when the half-row plan of level `level` is uniform: no long rows, no halo node left outside LDS, at most 5 edges
+ * evaluated per lane.  A property of the plan: it tells which instantiation of the order-free kernel the level reaches (the
+ * one that requests every half row up front; other levels walk the rows beyond five in a loop or stage wide halos). */
 int mgcfd_level_has_half_rows(const mgcfd_solver *s, int level, int *yes);
 /* *yes = 1 when level `level` can run the order-free flux kernel (MGCFD_OPT_FLUX_VARIANT bit 6 with MGCFD_OPT_EXACT = 0): no halo
  * node left outside LDS; any number of edges per node (what a lane's five requested rows do not hold is walked in a loop). */

@@ -281,30 +281,22 @@ struct DevicePlan {
     int32_t *slice_row0 = nullptr, *rows_int = nullptr, *rows_bnd = nullptr, *nbr = nullptr;
     double *w = nullptr;                // [row][4 components][64 lanes]: signed, halved edge weights fx,fy,fz and k = -|e|*0.2f*0.5
     int32_t n_tiles = 0;
-    int32_t pad_row = 0;                // index of a row of padding after the last row (nbr16, w, gat16)
-    int32_t pad_chunk = 0;              // index of a chunk of padding after the last edge chunk (te_slots, te_w)
+    int32_t pad_row = 0;                // index of a row of padding after the last row (nbr16, w)
     uint16_t *nbr16 = nullptr;          // [row][64 lanes] tile-local codes
     int32_t *tile_halo = nullptr;        // [n_tiles][kHaloStride] ids of the staged halo nodes, -1 padded
     int32_t *tile_ovf_ptr = nullptr, *tile_ovf = nullptr;
-    // edge-once tiles (preprocess.hpp: LevelPlan::te_*); edge_once == 0: not available on this level
     int vin_ok = 0;                     // no tile has overflow nodes or more than 256 halo nodes: role-5 launches allowed
     int lds_complete = 0;               // every halo node of every tile is staged in LDS (no overflow table entries)
     int32_t halo_max = 0;               // the largest halo of a tile (k_flux_free: how many workgroups may share a CU)
-    int edge_once = 0;
-    int32_t *te_chunk_ptr = nullptr, *te_count = nullptr;
-    uint16_t *te_slots = nullptr, *gat16 = nullptr;
-    double *te_w = nullptr;
-    double *te_w3 = nullptr;            // [chunk*256 + p][3]: the same a-side weights as 24-byte records (k_flux_tile WMODE 2)
-    // half rows (preprocess.hpp: LevelPlan::hr_*); half == 0: not available on this level
-    int half = 0;
-    int free_rows = 0;                  // the half-row plan is present at all (k_flux_free; `half`: k_flux_half can run on it too)
+    // half rows (preprocess.hpp: LevelPlan::hr_*), k_flux_free's plan
+    int free_rows = 0;                  // the half-row plan is present
+    int half = 0;                       // ... and uniform (LevelPlan::half): the level reaches k_flux_free's short-row instantiations
     int32_t hr_max_rows = 0;            // the most half rows a slice holds
     int free_wide = 0;                  // some tile's halo exceeds kHaloStride: k_flux_free stages from free_halo ([n_tiles][kFreeHaloStride])
     int32_t *free_halo = nullptr;
     int32_t hr_pad_row = 0;             // index of a half row of padding after the last one
     int32_t *hr_row0 = nullptr;         // [n_slices+1]
     uint32_t *hr_code = nullptr;        // [half row][64]
-    uint16_t *hg16 = nullptr;
     double *hr_w = nullptr;             // [half row][3][64]
     int has_tail = 0;                   // long rows: some tile leaves entries to its workgroup (k_flux_tile<..., TAIL>)
     TailPlan tail;

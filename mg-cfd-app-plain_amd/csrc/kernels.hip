@@ -36,8 +36,8 @@
 namespace mgcfd {
 namespace MGCFD_KERNEL_NS {
 
-// Diagnostic build only (tools/phase_half.py, -DMGCFD_PHASES): thread 0 of every workgroup adds the wall-clock ticks
-// between phase boundaries of k_flux_half to its own slot.  The shipped build defines the marks away.
+// Diagnostic build only (-DMGCFD_PHASES): thread 0 of every workgroup adds the wall-clock ticks between the phase
+// boundaries (PH_MARK) of the flux kernel it runs to its own slot.  The shipped build defines the marks away.
 #ifdef MGCFD_PHASES
 __device__ unsigned long long g_phase[4096 * 8];
 __device__ unsigned long long g_phase_abs[4096 * 8];     // the LAST launch: [0] when every workgroup began, [1 + k] when it passed mark k (100 MHz ticks), [7] XCC_ID << 32 | HW_ID
@@ -473,45 +473,6 @@ __device__ __forceinline__ EdgeRow load_row(const uint16_t *__restrict__ nbr, co
     return e;
 }
 
-__device__ __forceinline__ EdgeRow pad_row_entry()
-{
-    EdgeRow e;
-    e.code = kT16Pad; e.fx = 0.0; e.fy = 0.0; e.fz = 0.0; e.k = 0.0;
-    return e;
-}
-
-// Indexed weights (WMODE 2): a tile's internal edges are listed ONCE (preprocess.cpp: te_*; 24 bytes each, the a-side
-// weights -0.5*e), and a row entry is 4 bytes: the neighbour's LDS slot (nbr16) and the position of the entry's edge in
-// its tile's list (gat16, role bit = this node is the edge's b end: it sees the negated weights).  Both end points of
-// an edge inside the tile read the same 24 bytes — the second one from L1/L2 — so a launch moves 24 B per edge and
-// tile + 4 B per entry instead of 26-34 B per entry (two per edge); the length factor is recomputed from the weights.
-struct RowRef { uint32_t code, pos; };
-
-__device__ __forceinline__ RowRef load_ref(const uint16_t *__restrict__ nbr16, const uint16_t *__restrict__ gat16, int64_t row, int lane)
-{
-    RowRef r;
-    r.code = nbr16[(row << 6) + lane];
-    r.pos = gat16[(row << 6) + lane];
-    return r;
-}
-
-__device__ __forceinline__ EdgeRow gather_weights(const double *__restrict__ tw, const RowRef &r)
-{
-    const uint32_t p = r.pos & kT16SlotMask;
-    const bool pad = p == kT16Pad;
-    const double *wp = tw + (pad ? 0u : p) * 3u;
-    const double x = wp[0], y = wp[1], z = wp[2];
-    const bool neg = (r.pos & kT16RoleB) != 0;
-    EdgeRow e;
-    e.code = r.code;
-    // (padding must carry zero weights: its +-0.0 contribution is what leaves a sum that started at +0.0 unchanged)
-    e.fx = pad ? 0.0 : (neg ? -x : x);
-    e.fy = pad ? 0.0 : (neg ? -y : y);
-    e.fz = pad ? 0.0 : (neg ? -z : z);
-    e.k = 0.0;
-    return e;
-}
-
 struct Flux5 { double d, mx, my, mz, en; };
 
 // One edge's contribution to THIS node's flux (flux_kernel.elemfunc.c:130-189 seen from this
@@ -660,7 +621,7 @@ __device__ __forceinline__ void boundary_rows(const NodeQ &me, const FluxC &fm, 
 // beside launch_flux reads the role off a stage's arguments.
 // TAIL: the level has long rows (TailPlan): the per-node loop stops at the tile's row limit and the workgroup
 // evaluates the remaining entries together (see below).
-// WMODE: 0 = the length factor k recomputed from the row's weights, 1 = k streamed with them, 2 = indexed weights (above).
+// LOADK: the length factor k is streamed with the row's weights; false: recomputed from them.
 // The workgroup's LDS: the staged records, the first stage's partial minima per wave, the last stage's per-wave sums
 // (559 records x 96 B + 32 + 64 B = 53,760 B = 42 of the 1,280-byte granules LDS is handed out in: three workgroups per CU).
 struct FluxTileLds {
@@ -681,7 +642,7 @@ static_assert(kTileCap4 - kTile < kBlock, "one halo id per thread");
 // The kernel's body as a function of the workgroup's position in the launch (`block`): k_flux_tile calls it with blockIdx.x
 // (tools/exp/sweep_flow.patch: a dataflow sweep calls it with the tile a workgroup has claimed).
 // SLIM (with FluxTileLds4): 80-byte records and the rows walked one at a time, for four workgroups per CU.
-template <int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH, bool SLIM = false, typename Lds = FluxTileLds>
+template <bool LOADK, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH, bool SLIM = false, typename Lds = FluxTileLds>
 __device__ __forceinline__ void
 flux_tile_body(Lds &lds, const unsigned block,
                const double *__restrict__ q, const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int32_t pad_row,
@@ -690,16 +651,12 @@ flux_tile_body(Lds &lds, const unsigned block,
                const uint16_t *__restrict__ nbr16, const double *__restrict__ w,
                const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf, const FarField &ff,
                double *__restrict__ fluxes, int classes, const FusedStep &fs, const TailPlan &tp,
-               const uint16_t *__restrict__ gat16, const int32_t *__restrict__ te_chunk_ptr, const double *__restrict__ te_w3,
                const StagePush &push /* PUSH instantiations only: the stage sends its own message (device_plan.hpp) */,
                const bool block_is_tile = false /* `block` IS the tile (tools/exp/sweep_flow.patch) */)
 {
-    constexpr bool LOADK = WMODE == 1;
     static_assert(!PUSH || FUSE, "only a fused stage sends its message");
     PH_BEGIN();
-    constexpr bool IDXW = WMODE == 2;
-    static_assert(!(IDXW && TAIL), "indexed weights: levels without long rows only");
-    static_assert(!SLIM || (!TAIL && !IDXW && !PUSH && ROLE != 5), "80-byte records: the stages without long rows, indexed weights, message or absorbed stage");
+    static_assert(!SLIM || (!TAIL && !PUSH && ROLE != 5), "80-byte records: the stages without long rows, message or absorbed stage");
     double2 *const tile = lds.tile;
 
     // FUSE: this launch is a whole Runge-Kutta stage — the node's complete flux never leaves
@@ -741,17 +698,6 @@ flux_tile_body(Lds &lds, const unsigned block,
     const int64_t hnode = has_halo ? int64_t(hid) : i;
     double o0, o1, o2, o3, o4, g0, g1, g2, g3, g4;
     EdgeRow e0, e1;
-    // indexed weights: the first four rows' references go out right behind the halo ids (the weights they point at are
-    // the second link of a chain as long as ids -> halo state); the tile's edge list starts at its first chunk
-    RowRef i0{}, i1{}, i2{}, i3{};
-    const double *tw = nullptr;
-    if (IDXW) {
-        i0 = load_ref(nbr16, gat16, n_int > 0 ? row0 : pad_row, lane);
-        i1 = load_ref(nbr16, gat16, n_int > 1 ? row0 + 1 : pad_row, lane);
-        i2 = load_ref(nbr16, gat16, n_int > 2 ? row0 + 2 : pad_row, lane);
-        i3 = load_ref(nbr16, gat16, n_int > 3 ? row0 + 3 : pad_row, lane);
-        tw = te_w3 + int64_t(te_chunk_ptr[t]) * (kEdgeChunk * 3);
-    }
     if (FUSE && ROLE == 5) {
         // The input state of this stage does not exist in memory: it is the first stage's time_step,
         // old + (min_dt/volume/vin_div) * flux, applied here to every staged node (own and halo) from the
@@ -770,11 +716,8 @@ flux_tile_body(Lds &lds, const unsigned block,
         const double h0 = fl[hnode], h1 = fl[stride + hnode], h2 = fl[2 * stride + hnode], h3 = fl[3 * stride + hnode],
                      h4 = fl[4 * stride + hnode];
         const double vh = fs.volumes[hnode];
-        if (IDXW) { e0 = gather_weights(tw, i0); e1 = gather_weights(tw, i1); }
-        else {
-            e0 = load_row<LOADK>(nbr16, w, n_int > 0 ? row0 : pad_row, lane);
-            e1 = load_row<LOADK>(nbr16, w, n_int > 1 ? row0 + 1 : pad_row, lane);
-        }
+        e0 = load_row<LOADK>(nbr16, w, n_int > 0 ? row0 : pad_row, lane);
+        e1 = load_row<LOADK>(nbr16, w, n_int > 1 ? row0 + 1 : pad_row, lane);
         double pm = pmv[0];
 #pragma unroll
         for (int u = 1; u < kPartPre; u++) pm = fmin(pm, pmv[u]);
@@ -800,11 +743,8 @@ flux_tile_body(Lds &lds, const unsigned block,
         g0 = q[hnode]; g1 = q[stride + hnode]; g2 = q[2 * stride + hnode]; g3 = q[3 * stride + hnode]; g4 = q[4 * stride + hnode];
         // (a row the slice does not have is read from pad_row, a row of padding after the last one: the
         //  load itself is never conditional, so the compiler can count the loads in flight exactly)
-        if (IDXW) { e0 = gather_weights(tw, i0); e1 = gather_weights(tw, i1); }
-        else {
-            e0 = load_row<LOADK>(nbr16, w, n_int > 0 ? row0 : pad_row, lane);
-            if (!SLIM) e1 = load_row<LOADK>(nbr16, w, n_int > 1 ? row0 + 1 : pad_row, lane);
-        }
+        e0 = load_row<LOADK>(nbr16, w, n_int > 0 ? row0 : pad_row, lane);
+        if (!SLIM) e1 = load_row<LOADK>(nbr16, w, n_int > 1 ? row0 + 1 : pad_row, lane);
     }
     // (the step-factor partials: wanted only at the staging barrier, so requested after everything on the critical chain)
     if (FUSE && ROLE == 0) {                         // (role 0 is launched only with fs.partial_min set)
@@ -928,16 +868,6 @@ flux_tile_body(Lds &lds, const unsigned block,
     {
         // every pair but the last, each prefetching the pair after it
         int32_t r = 0;
-        if (IDXW) {
-            // references two pairs ahead, the weights they point at one pair ahead
-            for (; r + 2 < n_int; r += 2) {
-                const RowRef i4 = load_ref(nbr16, gat16, r + 4 < n_int ? row0 + r + 4 : pad_row, lane);
-                const RowRef i5 = load_ref(nbr16, gat16, r + 5 < n_int ? row0 + r + 5 : pad_row, lane);
-                const EdgeRow e2 = gather_weights(tw, i2), e3 = gather_weights(tw, i3);
-                MGCFD_ROW_PAIR();
-                e0 = e2; e1 = e3; i2 = i4; i3 = i5;
-            }
-        } else
         for (; r + 2 < n_int; r += 2) {
             const EdgeRow e2 = load_row<LOADK>(nbr16, w, row0 + r + 2, lane);
             const EdgeRow e3 = load_row<LOADK>(nbr16, w, r + 3 < n_int ? row0 + r + 3 : pad_row, lane);
@@ -1158,7 +1088,7 @@ flux_tile_body(Lds &lds, const unsigned block,
     PH_MARK(3);
 }
 
-template <int MINW, int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false, bool SLIM = false>
+template <int MINW, bool LOADK, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false, bool SLIM = false>
 __global__ void __launch_bounds__(kBlock, MINW)
 k_flux_tile(// the first 16 dwords of the arguments are preloaded into SGPRs at wave launch (Makefile:
             // -amdgpu-kernarg-preload-count): what the first loads of the prologue need comes first
@@ -1168,198 +1098,14 @@ k_flux_tile(// the first 16 dwords of the arguments are preloaded into SGPRs at 
             const uint16_t *__restrict__ nbr16, const double *__restrict__ w,
             const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf, FarField ff,
             double *__restrict__ fluxes, int classes, FusedStep fs, TailPlan tp,
-            const uint16_t *__restrict__ gat16, const int32_t *__restrict__ te_chunk_ptr, const double *__restrict__ te_w3,
             StagePush push)
 {
     __shared__ std::conditional_t<SLIM, FluxTileLds4, FluxTileLds> lds;
-    flux_tile_body<WMODE, FUSE, ACC, ROLE, TAIL, PUSH, SLIM>(lds, blockIdx.x, q, tile_halo, n_tiles, pad_row, stride, nel, slice_row0, rows_int, rows_bnd, nbr16, w,
-                                                       tile_ovf_ptr, tile_ovf, ff, fluxes, classes, fs, tp, gat16, te_chunk_ptr, te_w3, push);
+    flux_tile_body<LOADK, FUSE, ACC, ROLE, TAIL, PUSH, SLIM>(lds, blockIdx.x, q, tile_halo, n_tiles, pad_row, stride, nel, slice_row0, rows_int, rows_bnd, nbr16, w,
+                                                       tile_ovf_ptr, tile_ovf, ff, fluxes, classes, fs, tp, push);
 }
 
-// ------------------------------------------------------------------------------------------
-// flux_edge_once: the same three loops with every internal edge evaluated ONCE per tile.
-//
-// k_flux_tile reads an edge's weights and evaluates its flux twice, once from each end.  Here a
-// tile lists the internal edges that touch it once (preprocess.cpp, te_*), in ORIGINAL edge
-// order; with the node records staged as before, thread p % 256 evaluates edge p of the list
-// (a-side form, flux_kernel.elemfunc.c:130-161) and keeps the five results in registers.  When
-// all edges are done the records are dead: the fluxes replace them in LDS (40 B each, position
-// p), and every node then sums its incident edges from LDS in its own row order = the reference's
-// accumulation order; the b end adds -F, which is what the reference's b-side expressions
-// (:170-189) evaluate to bit for bit (every term negates exactly).  An edge cut by a tile
-// boundary is evaluated by both tiles from identical operands.  Per tile this moves ~36 B per
-// listed edge + 2 B per row entry instead of 34 B per row entry (two per edge), and does ~0.6 of
-// the flux arithmetic.
-// ------------------------------------------------------------------------------------------
-struct TileEdge { uint32_t sa, sb; double fx, fy, fz, k; };
-constexpr int kGatherPre = 8;             // gather-list rows held in registers from the start of the kernel
-
-template <bool LOADK>
-__device__ __forceinline__ TileEdge load_tile_edge(const uint16_t *__restrict__ te_slots, const double *__restrict__ te_w,
-                                                   int64_t chunk, int tid)
-{
-    TileEdge e;
-    e.sa = te_slots[(chunk * 2) * kEdgeChunk + tid];
-    e.sb = te_slots[(chunk * 2 + 1) * kEdgeChunk + tid];
-    const double *wr = te_w + chunk * (4 * kEdgeChunk) + tid;
-    e.fx = wr[0]; e.fy = wr[kEdgeChunk]; e.fz = wr[2 * kEdgeChunk];
-    e.k = LOADK ? wr[3 * kEdgeChunk] : 0.0;
-    return e;
-}
-
-__device__ __forceinline__ TileEdge no_tile_edge()
-{
-    TileEdge e;
-    e.sa = kT16Pad; e.sb = kT16Pad; e.fx = 0.0; e.fy = 0.0; e.fz = 0.0; e.k = 0.0;
-    return e;
-}
-
-template <bool LOADK, bool FUSE, bool ACC>
-__global__ void __launch_bounds__(kBlock, 3)
-k_flux_edge_once(const double *__restrict__ q, const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int32_t pad_row,
-                 int64_t stride, int64_t nel, const int32_t *__restrict__ te_chunk_ptr,
-                 const int32_t *__restrict__ te_count, int32_t pad_chunk, int classes,
-                 const int32_t *__restrict__ slice_row0,
-                 const int32_t *__restrict__ rows_int, const int32_t *__restrict__ rows_bnd,
-                 const uint16_t *__restrict__ nbr16, const double *__restrict__ w, const uint16_t *__restrict__ gat16,
-                 const uint16_t *__restrict__ te_slots, const double *__restrict__ te_w,
-                 const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf, FarField ff,
-                 double *__restrict__ fluxes, FusedStep fs)
-{
-    __shared__ double2 tile[kTileCap * kLdsRecD2];
-
-    double min_dt = 0.0;
-    if (FUSE && fs.partial_min) min_dt = block_min_of_partials(fs.partial_min, fs.n_partial);
-
-    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave_base = tid & ~63;                 // first list position of this wave within a chunk
-    const int64_t base = int64_t(t) * kTile;
-    const int64_t i = base + tid;
-    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
-
-    // load issue order as in k_flux_tile: halo ids, own state, then the bulk prefetches (first two
-    // chunks of the edge list, the node's gather list), then the halo state by id; nothing under a branch
-    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
-    const int32_t hid = hrow[tid];                                     // -1: no halo node for this thread
-    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;   // halo larger than the workgroup (rare)
-    const double o0 = q[i], o1 = q[stride + i], o2 = q[2 * stride + i], o3 = q[3 * stride + i], o4 = q[4 * stride + i];
-    const int32_t n_te = te_count[t];
-    const int64_t chunk0 = te_chunk_ptr[t];
-    // (a chunk this wave has no edges in is read from pad_chunk, a chunk of padding after the last
-    //  one: the loads are never conditional, so the compiler can count the loads in flight exactly)
-    TileEdge e_cur = load_tile_edge<LOADK>(te_slots, te_w, wave_base < n_te ? chunk0 : pad_chunk, tid);
-    TileEdge e_nxt = load_tile_edge<LOADK>(te_slots, te_w, kEdgeChunk + wave_base < n_te ? chunk0 + 1 : pad_chunk, tid);
-
-    // the node's gather list (positions of its incident edges in the tile's list): the first rows
-    // are fetched now, long before phase 4 needs them
-    const int32_t row0 = slice_row0[slice];
-    const int32_t n_int = rows_int[slice];
-    const int32_t n_bnd = rows_bnd[slice];
-    const uint16_t *grow = gat16 + (int64_t(row0) << 6) + lane;
-    uint32_t gc[kGatherPre];
-#pragma unroll
-    for (int k = 0; k < kGatherPre; k++) gc[k] = gat16[(int64_t(k < n_int ? row0 + k : pad_row) << 6) + lane];
-
-    // ---- phase 1: stage + derive, as k_flux_tile ----
-    const bool has_halo = hid >= 0;
-    const int64_t hnode = has_halo ? int64_t(hid) : i;
-    {
-        const double g0 = q[hnode], g1 = q[stride + hnode], g2 = q[2 * stride + hnode], g3 = q[3 * stride + hnode],
-                     g4 = q[4 * stride + hnode];
-        lds_store_record(tile, uint32_t(tid), make_nodeq(o0, o1, o2, o3, o4));
-        lds_store_record(tile, uint32_t(kTile + tid), make_nodeq(g0, g1, g2, g3, g4));   // unconditional, see k_flux_tile
-    }
-    if (hid2 >= 0) lds_store_record(tile, uint32_t(kTile + kBlock + tid), load_and_derive(q, stride, hid2));
-    const int32_t ovf0 = tile_ovf_ptr[t];
-    __syncthreads();
-
-    // ---- phase 2: one edge per thread and chunk ----
-    Flux5 F[kMaxEdgeChunks];
-#pragma unroll
-    for (int c = 0; c < kMaxEdgeChunks; c++) {
-        TileEdge e_n2 = no_tile_edge();
-        if (c + 2 < kMaxEdgeChunks)                                    // compile-time
-            e_n2 = load_tile_edge<LOADK>(te_slots, te_w, (c + 2) * kEdgeChunk + wave_base < n_te ? chunk0 + c + 2 : pad_chunk, tid);
-        F[c].d = 0.0; F[c].mx = 0.0; F[c].my = 0.0; F[c].mz = 0.0; F[c].en = 0.0;
-        if (c * kEdgeChunk + wave_base < n_te) {                     // wave-uniform
-            const bool v = e_cur.sa != kT16Pad;                      // the list's last chunk is padded
-            const uint32_t sa = v ? e_cur.sa : uint32_t(tid), sb = v ? e_cur.sb : uint32_t(tid);
-            const bool oa = sa >= uint32_t(kTileCap), ob = sb >= uint32_t(kTileCap);
-            NodeQ A, B;
-            if (__builtin_expect(__any(oa || ob), 0)) {
-                // ragged cluster: an end point did not fit the LDS tile, read it from HBM
-                A = oa ? load_and_derive(q, stride, tile_ovf[ovf0 + int32_t(sa) - kTileCap]) : lds_load_record(tile, sa);
-                B = ob ? load_and_derive(q, stride, tile_ovf[ovf0 + int32_t(sb) - kTileCap]) : lds_load_record(tile, sb);
-            } else {
-                A = lds_load_record(tile, sa);
-                B = lds_load_record(tile, sb);
-            }
-            EdgeRow er;
-            er.code = 0;                                             // role a
-            er.fx = e_cur.fx; er.fy = e_cur.fy; er.fz = e_cur.fz; er.k = e_cur.k;
-            F[c] = edge_flux<LOADK>(A, flux_contribution(A), B, er);
-        }
-        e_cur = e_nxt; e_nxt = e_n2;
-    }
-
-    // ---- phase 3: the records are dead; the edge fluxes take their place ----
-    double *fb = reinterpret_cast<double *>(tile);
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < kMaxEdgeChunks; c++) {
-        if (c * kEdgeChunk + wave_base < n_te) {
-            double *slot = fb + (c * kEdgeChunk + tid) * 5;
-            slot[0] = F[c].d; slot[1] = F[c].mx; slot[2] = F[c].my; slot[3] = F[c].mz; slot[4] = F[c].en;
-        }
-    }
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-    if (ACC) {
-        a0 = fluxes[i]; a1 = fluxes[stride + i]; a2 = fluxes[2 * stride + i];
-        a3 = fluxes[3 * stride + i]; a4 = fluxes[4 * stride + i];
-    }
-    __syncthreads();
-
-    // ---- phase 4: every node sums its incident edges in row order ----
-    auto add_entry = [&](uint32_t code) {
-        const uint32_t p = code & kT16SlotMask;
-        if (p == kT16Pad) return;
-        const double *sl = fb + p * 5;
-        const double f0 = sl[0], f1 = sl[1], f2 = sl[2], f3 = sl[3], f4 = sl[4];
-        const bool neg = (code & kT16RoleB) != 0;                   // this node is the edge's b end
-        a0 = neg ? a0 - f0 : a0 + f0;  a1 = neg ? a1 - f1 : a1 + f1;  a2 = neg ? a2 - f2 : a2 + f2;
-        a3 = neg ? a3 - f3 : a3 + f3;  a4 = neg ? a4 - f4 : a4 + f4;
-    };
-#pragma unroll
-    for (int k = 0; k < kGatherPre; k++)
-        if (k < n_int) add_entry(gc[k]);
-    for (int32_t r = kGatherPre; r < n_int; r++) add_entry(grow[r << 6]);
-
-    if ((classes & 6) && n_bnd > 0) {
-        // boundary faces need the node's own derived state again (its LDS record is gone)
-        const NodeQ me = load_and_derive(q, stride, i);
-        boundary_rows(me, flux_contribution(me), ff, nbr16, w, int64_t(row0) + n_int, n_bnd, lane, classes, a0, a1, a2, a3, a4);
-    }
-
-    finish_node<FUSE>(i, nel, stride, a0, a1, a2, a3, a4, fluxes, fs, min_dt, t);
-}
-
-// ------------------------------------------------------------------------------------------
-// flux_half: the same three loops with every internal edge of a tile evaluated ONCE, by one of its end points.
-//
-// k_flux_tile streams a 26-34 byte row entry and evaluates the flux for BOTH end points of every edge; its time is the
-// time to move those bytes (the indirect_rw probe through the same tiles takes 0.96 of it).  Here the plan gives every
-// internal edge that touches a tile one EVALUATOR among its end points inside the tile (preprocess.hpp: half rows), so
-// a tile streams one 26-byte entry per edge.  With the node records staged as in k_flux_tile, every lane walks its
-// half rows — its own record in registers, the other end's from LDS, the same edge_flux as seen from this node — and
-// keeps the results (at most kHalfMaxRows x 5 values) in registers; when the whole workgroup is done the records
-// are dead and the results take their place in LDS (position = half row within the tile * 64 + lane, five arrays: conflict-free
-// stores); every node then adds its incident edges in its own row order = the reference's accumulation order, its own
-// evaluations as they are, those of its neighbours negated — which is what the reference's expressions for the other
-// end evaluate to bit for bit (every term negates exactly).  An edge cut by the tile boundary is evaluated by the tile
-// of each end, from identical operands.
-// ------------------------------------------------------------------------------------------
+// One entry of the half-row plan (preprocess.hpp: hr_code, hr_w): the code word and the evaluator's three weights; k is recomputed.
 __device__ __forceinline__ EdgeRow load_half_row(const uint32_t *__restrict__ code, const double *__restrict__ w3, int64_t row, int lane)
 {
     EdgeRow e;
@@ -1370,166 +1116,12 @@ __device__ __forceinline__ EdgeRow load_half_row(const uint32_t *__restrict__ co
     return e;
 }
 
-template <bool FUSE, bool ACC>
-__global__ void __launch_bounds__(kBlock, 3)
-k_flux_half(// (the first 16 dwords are preloaded into SGPRs: what the prologue's first loads need)
-            const double *__restrict__ q, const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int32_t hr_pad_row,
-            int64_t stride, int64_t nel, const int32_t *__restrict__ hr_row0, const uint32_t *__restrict__ hr_code,
-            const double *__restrict__ hr_w, const uint16_t *__restrict__ hg16, const int32_t *__restrict__ slice_row0,
-            const int32_t *__restrict__ rows_int, const int32_t *__restrict__ rows_bnd, int32_t pad_row,
-            const uint16_t *__restrict__ nbr16, const double *__restrict__ w, FarField ff, double *__restrict__ fluxes,
-            int classes, FusedStep fs)
-{
-    __shared__ double2 tile[kTileCap * kLdsRecD2 > kHalfLdsD2 ? kTileCap * kLdsRecD2 : kHalfLdsD2];   // (the flux terms need a little more than the records)
-
-    PH_BEGIN();
-    double min_dt = 0.0;
-    if (FUSE && fs.partial_min) min_dt = block_min_of_partials(fs.partial_min, fs.n_partial);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
-    const int64_t i = int64_t(t) * kTile + tid;
-    const int32_t slice = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(i >> 6));
-
-    // load issue order as in k_flux_tile: halo ids, own state, the first two half rows, then the halo state by id;
-    // nothing under a branch
-    const int32_t *hrow = tile_halo + int64_t(t) * kHaloStride;
-    const int32_t hid = hrow[tid];
-    const int32_t hid2 = tid < kHaloStride - kBlock ? hrow[kBlock + tid] : -1;
-    const int32_t h0 = hr_row0[slice];
-    const int32_t h0_tile = hr_row0[slice & ~3];               // the tile's first half row: flux-term positions count from it
-    const int32_t n_h = (classes & 1) ? hr_row0[slice + 1] - h0 : 0;
-    const int32_t row0 = slice_row0[slice];
-    const int32_t n_int = (classes & 1) ? rows_int[slice] : 0;
-    const int32_t n_bnd = rows_bnd[slice];
-    const double o0 = q[i], o1 = q[stride + i], o2 = q[2 * stride + i], o3 = q[3 * stride + i], o4 = q[4 * stride + i];
-    EdgeRow e0 = load_half_row(hr_code, hr_w, n_h > 0 ? h0 : hr_pad_row, lane);
-    EdgeRow e1 = load_half_row(hr_code, hr_w, n_h > 1 ? h0 + 1 : hr_pad_row, lane);
-    const int64_t hnode = hid >= 0 ? int64_t(hid) : i;
-    const double g0 = q[hnode], g1 = q[stride + hnode], g2 = q[2 * stride + hnode], g3 = q[3 * stride + hnode], g4 = q[4 * stride + hnode];
-
-    // ---- phase 1: stage + derive, as k_flux_tile ----
-#ifdef MGCFD_ABL_DERIVE        /* diagnostic: nothing derived (results wrong) */
-    auto fake = [](double r, double mx, double my, double mz, double en) { NodeQ n; n.rho = r; n.mx = mx; n.my = my; n.mz = mz; n.en = en; n.vx = mx; n.vy = my; n.vz = mz; n.p = en; n.speed = r; n.c = r; return n; };
-    const NodeQ me = fake(o0, o1, o2, o3, o4);
-    lds_store_record(tile, uint32_t(tid), me);
-    lds_store_record(tile, uint32_t(kTile + tid), fake(g0, g1, g2, g3, g4));
-#else
-    const NodeQ me = make_nodeq(o0, o1, o2, o3, o4);
-    lds_store_record(tile, uint32_t(tid), me);
-    lds_store_record(tile, uint32_t(kTile + tid), make_nodeq(g0, g1, g2, g3, g4));     // unconditional, see k_flux_tile
-#endif
-    if (hid2 >= 0) lds_store_record(tile, uint32_t(kTile + kBlock + tid), load_and_derive(q, stride, hid2));
-    __syncthreads();
-    PH_MARK(0);
-
-    // ---- phase 2: this node's half rows one at a time, the two after it in flight.  (One at a time, and the node's own
-    //      flux contribution recomputed per edge: the results of up to kHalfMaxRows edges wait in registers, and the
-    //      kernel is bound by the bytes it moves, not by its arithmetic.) ----
-    Flux5 F[kHalfMaxRows];
-#pragma unroll
-    for (int j = 0; j < kHalfMaxRows; j++) { F[j].d = 0.0; F[j].mx = 0.0; F[j].my = 0.0; F[j].mz = 0.0; F[j].en = 0.0; }
-    uint32_t live = 0;                              // bit j: half row j of this lane holds an edge
-#pragma unroll
-    for (int j = 0; j < kHalfMaxRows; j++) {
-        if (j < n_h) {                              // (uniform over the wave)
-            EdgeRow e2 = pad_row_entry();
-            if (j + 2 < kHalfMaxRows)               // compile time
-                e2 = load_half_row(hr_code, hr_w, j + 2 < n_h ? h0 + j + 2 : hr_pad_row, lane);
-            const uint32_t s0 = e0.code & kT16SlotMask;
-            const bool v0 = s0 != kT16Pad;
-            const NodeQ n0 = lds_load_record(tile, v0 ? s0 : uint32_t(tid));
-            // an evaluation another node owns (the plan found no room in that node's lane): its record comes from LDS too
-            NodeQ m0 = me;
-            if (__builtin_expect(__any((e0.code & kHalfForeign) != 0), 0)) {
-                if (e0.code & kHalfForeign) m0 = lds_load_record(tile, (e0.code >> 16) & 0xFFu);
-            }
-#ifdef MGCFD_ABL_EVAL          /* diagnostic: the evaluation replaced by a few adds (results wrong) */
-            F[j].d = m0.rho + n0.rho + e0.fx; F[j].mx = m0.mx + n0.mx + e0.fy; F[j].my = m0.my + n0.my + e0.fz; F[j].mz = m0.mz + n0.mz + n0.c; F[j].en = m0.en + n0.en + n0.p + n0.vx + n0.speed;
-#else
-            F[j] = edge_flux<false>(m0, flux_contribution(m0), n0, e0);
-#endif
-            live |= (v0 ? 1u : 0u) << j;
-            e0 = e1; e1 = e2;
-        }
-    }
-    // the node's gather list: requested now, wanted after the hand-over
-    uint32_t gc[kGatherPre];
-#pragma unroll
-    for (int k = 0; k < kGatherPre; k++) gc[k] = hg16[(int64_t(k < n_int ? row0 + k : pad_row) << 6) + lane];
-
-    // ---- phase 3: the records are dead; the edge fluxes take their place ----
-    double *fb = reinterpret_cast<double *>(tile);
-    PH_MARK(1);
-    __syncthreads();
-    PH_MARK(2);
-#pragma unroll
-    for (int j = 0; j < kHalfMaxRows; j++) {
-        if (live & (1u << j)) {
-            double *slot = fb + (h0 - h0_tile + j) * kSlice + lane;
-            slot[0] = F[j].d; slot[kHalfSlots] = F[j].mx; slot[2 * kHalfSlots] = F[j].my; slot[3 * kHalfSlots] = F[j].mz; slot[4 * kHalfSlots] = F[j].en;
-        }
-    }
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-    if (ACC) {
-        a0 = fluxes[i]; a1 = fluxes[stride + i]; a2 = fluxes[2 * stride + i];
-        a3 = fluxes[3 * stride + i]; a4 = fluxes[4 * stride + i];
-    }
-    __syncthreads();
-    PH_MARK(3);
-
-    // ---- phase 4: every node adds its incident edges in row order ----
-    auto add_entry = [&](uint32_t code) {
-        const uint32_t p = code & kT16SlotMask;
-        if (p == kT16Pad) return;
-        const double *sl = fb + p;
-        const double f0 = sl[0], f1 = sl[kHalfSlots], f2 = sl[2 * kHalfSlots], f3 = sl[3 * kHalfSlots], f4 = sl[4 * kHalfSlots];
-        const bool neg = (code & kT16RoleB) != 0;                   // evaluated by the other end point
-        a0 = neg ? a0 - f0 : a0 + f0;  a1 = neg ? a1 - f1 : a1 + f1;  a2 = neg ? a2 - f2 : a2 + f2;
-        a3 = neg ? a3 - f3 : a3 + f3;  a4 = neg ? a4 - f4 : a4 + f4;
-    };
-#pragma unroll
-    for (int k = 0; k < kGatherPre; k++)
-        if (k < n_int) add_entry(gc[k]);
-    for (int32_t r = kGatherPre; r < n_int; r++) add_entry(hg16[(int64_t(row0 + r) << 6) + lane]);
-
-    PH_MARK(4);
-    if ((classes & 6) && n_bnd > 0) {
-        // (inline, as in k_flux_tile: handing the five sums to boundary_rows by reference parks two of them in scratch)
-        const FluxC fm = flux_contribution(me);
-        const int64_t first_bnd = int64_t(row0) + rows_int[slice];
-        for (int32_t r = 0; r < n_bnd; r++) {
-            const EdgeRow e = load_row<false>(nbr16, w, first_bnd + r, lane);
-            const double fx = e.fx, fy = e.fy, fz = e.fz;
-            if (e.code == kT16Wall && (classes & 2)) {
-                // flux_boundary_kernel.elemfunc.c:37-64: pressure force only
-                a0 += 0.0;
-                a1 += fx * me.p;
-                a2 += fy * me.p;
-                a3 += fz * me.p;
-                a4 += 0.0;
-            } else if (e.code == kT16Far && (classes & 4)) {
-                // flux_wall_kernel.elemfunc.c:51-88: average with the far-field state
-                a0 += fx * (ff.var[1] + me.mx) + fy * (ff.var[2] + me.my) + fz * (ff.var[3] + me.mz);
-                a4 += fx * (ff.fc_de[0] + fm.ex) + fy * (ff.fc_de[1] + fm.ey) + fz * (ff.fc_de[2] + fm.ez);
-                a1 += fx * (ff.fc_mx[0] + fm.xx) + fy * (ff.fc_mx[1] + fm.xy) + fz * (ff.fc_mx[2] + fm.xz);
-                a2 += fx * (ff.fc_my[0] + fm.xy) + fy * (ff.fc_my[1] + fm.yy) + fz * (ff.fc_my[2] + fm.yz);
-                a3 += fx * (ff.fc_mz[0] + fm.xz) + fy * (ff.fc_mz[1] + fm.yz) + fz * (ff.fc_mz[2] + fm.zz);
-            }
-        }
-    }
-
-    finish_node<FUSE>(i, nel, stride, a0, a1, a2, a3, a4, fluxes, fs, min_dt, t);
-    PH_MARK(5);
-}
-
 #ifdef MGCFD_ORDER_FREE
 // ------------------------------------------------------------------------------------------
 // flux_free (the `fast` namespace only: MGCFD_OPT_EXACT = 0, MGCFD_OPT_FLUX_VARIANT bit 6): compute_flux_edge +
 // boundary + far-field faces with ORDER-FREE accumulation.
 //
-// Every byte-saving layout of the bit-identical kernels (edge-once tiles, indexed weights, half rows) lost what it
+// Every byte-saving layout of the bit-identical kernels that was tried (EXPERIMENTS.md; since removed) lost what it
 // saved to the hand-over that keeps the reference's summation ORDER: a second pass over LDS and two more barriers.
 // north_star's bound is 1e-10, not bits, so this kernel drops the order and nothing else: a tile streams ONE 28-byte
 // entry per internal edge that touches it (the half-row plan, preprocess.hpp: the evaluator of an edge inside the tile
@@ -3893,7 +3485,7 @@ struct FluxLaunch {
     dim3 grid; int64_t nel_arg;         // the launch's workgroups; the nodes it treats as present (FusedStep::nel_active)
 };
 
-template <int WMODE, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false, bool SLIM = false>
+template <bool LOADK, bool FUSE, bool ACC, int ROLE, bool TAIL, bool PUSH = false, bool SLIM = false>
 static void launch_tile(const FluxLaunch &a, const StagePush &push = StagePush{})
 {
     const DevicePlan &p = a.p;
@@ -3901,10 +3493,9 @@ static void launch_tile(const FluxLaunch &a, const StagePush &push = StagePush{}
     // do not fit them — the kernel-granular '+=' launch and the split sweep's absorbed first stage, both off the sweep path —
     // are built for 2 waves per SIMD instead of spilling 20-36 bytes per lane.  (SLIM: four workgroups of 40,896 B per CU.)
     constexpr int MINW = SLIM ? 4 : ((TAIL && (ACC || ROLE == 5)) ? 2 : 3);
-    hipLaunchKernelGGL((k_flux_tile<MINW, WMODE, FUSE, ACC, ROLE, TAIL, PUSH, SLIM>), a.grid, dim3(kBlock), 0, a.st, a.q, p.tile_halo,
+    hipLaunchKernelGGL((k_flux_tile<MINW, LOADK, FUSE, ACC, ROLE, TAIL, PUSH, SLIM>), a.grid, dim3(kBlock), 0, a.st, a.q, p.tile_halo,
                        uint32_t(a.grid.x), p.pad_row, p.stride, a.nel_arg, p.slice_row0, p.rows_int, p.rows_bnd,
-                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, a.ff, a.fluxes, a.classes, a.fs, p.tail, p.gat16,
-                       p.te_chunk_ptr, p.te_w3, push);
+                       p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, a.ff, a.fluxes, a.classes, a.fs, p.tail, push);
 }
 
 #ifdef MGCFD_ORDER_FREE
@@ -3961,7 +3552,7 @@ void launch_flux(hipStream_t st, const DevicePlan &p, const double *q, const Far
     if (push && fused && part && !fs.vin_flux) {
         check_first_stage_input(role, q, fs);
         with_bool(loadk, [&](auto K) { with_bool(tail, [&](auto T) { with_constant<0, 1, 2, 3, 4>(role, [&](auto R) {
-            launch_tile<decltype(K)::value ? 1 : 0, true, false, decltype(R)::value, decltype(T)::value, true>(a, *push);
+            launch_tile<decltype(K)::value, true, false, decltype(R)::value, decltype(T)::value, true>(a, *push);
         }); }); });
         return;
     }
@@ -4004,48 +3595,22 @@ void launch_flux(hipStream_t st, const DevicePlan &p, const double *q, const Far
         return;
     }
 #endif
-    // variant bit 5 (32): half rows — every edge evaluated once per tile by one of its end points (k_flux_half); the
-    // split sweep's absorbed first stage (role 5) stays with the node gather
-    if ((variant & 32) && p.half && (classes & 1) && !(fused && fs.vin_flux) && !part) {
-        with_kind(fused, accumulate, [&](auto F, auto A) {
-            hipLaunchKernelGGL((k_flux_half<decltype(F)::value, decltype(A)::value>), a.grid, dim3(kBlock), 0, st, q, p.tile_halo, uint32_t(p.n_tiles),
-                               p.hr_pad_row, p.stride, p.nel, p.hr_row0, p.hr_code, p.hr_w, p.hg16, p.slice_row0,
-                               p.rows_int, p.rows_bnd, p.pad_row, p.nbr16, p.w, ff, fluxes, classes, fs);
-        });
-        return;
-    }
-    // variants 2, 3: every edge evaluated once per tile (needs the internal class and a level whose
-    // tiles fit the edge-once limits; otherwise the node gather below)
-    if ((variant & 2) && p.edge_once && (classes & 1) && !part) {
-        with_bool(loadk, [&](auto K) { with_kind(fused, accumulate, [&](auto F, auto A) {
-            hipLaunchKernelGGL((k_flux_edge_once<decltype(K)::value, decltype(F)::value, decltype(A)::value>), a.grid, dim3(kBlock), 0, st, q, p.tile_halo,
-                               uint32_t(p.n_tiles), p.pad_row, p.stride, p.nel, p.te_chunk_ptr, p.te_count,
-                               p.pad_chunk, classes, p.slice_row0, p.rows_int, p.rows_bnd, p.nbr16, p.w, p.gat16,
-                               p.te_slots, p.te_w, p.tile_ovf_ptr, p.tile_ovf, ff, fluxes, fs);
-        }); });
-        return;
-    }
-    // variant bit 4 (16): indexed weights — every edge's weights once per tile (needs the tile edge lists: p.edge_once)
-    const bool indexed = (variant & 16) && p.edge_once && p.te_w3 && !tail;
 #ifndef MGCFD_ORDER_FREE
     // kVariantStageWg4 (the bit-identical stages, solver.cpp): four workgroups per CU with 80-byte records where every tile
     // halo fits kTileCap4 - kTile slots — roles 0-4 of levels without long rows, k recomputed or streamed
-    if (fused && (variant & kVariantStageWg4) && stage_wg4_fits(p) && !indexed && role != 5) {
+    if (fused && (variant & kVariantStageWg4) && stage_wg4_fits(p) && role != 5) {
         with_bool(loadk, [&](auto K) { with_constant<0, 1, 2, 3, 4>(role, [&](auto R) {
-            launch_tile<decltype(K)::value ? 1 : 0, true, false, decltype(R)::value, false, false, true>(a);
+            launch_tile<decltype(K)::value, true, false, decltype(R)::value, false, false, true>(a);
         }); });
         return;
     }
 #endif
-    // the node gather: WMODE 2 on levels without long rows only; a launch that is no stage has no role (1)
-    with_constant<0, 1, 2>(indexed ? 2 : (loadk ? 1 : 0), [&](auto W) { with_bool(tail, [&](auto T) {
-        constexpr int WMODE = decltype(W)::value;
-        constexpr bool TAIL = decltype(T)::value;
-        if constexpr (!(WMODE == 2 && TAIL)) {
-            if (fused) with_constant<0, 1, 2, 3, 4, 5>(role, [&](auto R) { launch_tile<WMODE, true, false, decltype(R)::value, TAIL>(a); });
-            else if (accumulate) launch_tile<WMODE, false, true, 1, TAIL>(a);
-            else launch_tile<WMODE, false, false, 1, TAIL>(a);
-        }
+    // the node gather; a launch that is no stage has no role (1)
+    with_bool(loadk, [&](auto K) { with_bool(tail, [&](auto T) {
+        constexpr bool LOADK = decltype(K)::value, TAIL = decltype(T)::value;
+        if (fused) with_constant<0, 1, 2, 3, 4, 5>(role, [&](auto R) { launch_tile<LOADK, true, false, decltype(R)::value, TAIL>(a); });
+        else if (accumulate) launch_tile<LOADK, false, true, 1, TAIL>(a);
+        else launch_tile<LOADK, false, false, 1, TAIL>(a);
     }); });
 }
 

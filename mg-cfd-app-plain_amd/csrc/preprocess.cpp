@@ -645,24 +645,17 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
     P.tile_ovf_ptr.assign(static_cast<size_t>(P.n_tiles) + 1, 0);
     P.tile_halo.clear();
     P.tile_ovf.clear();
-    P.gat16.assign(P.nbr.size(), static_cast<uint16_t>(kT16Pad));
-    P.te_chunk_ptr.assign(static_cast<size_t>(P.n_tiles) + 1, 0);
-    P.te_count.assign(static_cast<size_t>(P.n_tiles), 0);
-    P.te_slots.clear();
-    P.te_w.clear();
-    P.edge_once = true;
     {
         // The tiles are independent of each other: contiguous ranges of them are worked through by a thread each into a part of
         // its own (appended lists, prefix arrays counted from the range's start), and the parts are joined in tile order — the
         // plan is the same whatever the number of threads (round 4: this loop was most of the drop-in's start-up time).
         struct Part {
-            std::vector<int32_t> tile_halo, tile_ovf, tile_halo_ptr, tile_ovf_ptr, te_chunk_ptr, hr_row0;
-            std::vector<uint16_t> te_slots;
-            std::vector<double> te_w, hr_w;
+            std::vector<int32_t> tile_halo, tile_ovf, tile_halo_ptr, tile_ovf_ptr, hr_row0;
+            std::vector<double> hr_w;
             std::vector<uint32_t> hr_code;
-            bool edge_once = true, free_rows = true, free_wide = false;
-            int32_t halo_max = 0, te_max = 0, hr_max_rows = 0, hr_max_tile_rows = 0;
-            int64_t halo_total = 0, te_total = 0, halo_overflow_refs = 0, hr_entries = 0, hr_foreign = 0;
+            bool free_rows = true, free_wide = false;
+            int32_t halo_max = 0, hr_max_rows = 0, hr_max_tile_rows = 0;
+            int64_t halo_total = 0, halo_overflow_refs = 0, hr_entries = 0, hr_foreign = 0;
             std::exception_ptr error;
         };
         P.free_rows = true;
@@ -671,7 +664,6 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
         P.free_halo.assign(static_cast<size_t>(P.n_tiles) * kFreeHaloStride, -1);
         P.hr_row0.assign(static_cast<size_t>(P.n_slices) + 1, 0);
         P.hr_code.clear(); P.hr_w.clear(); P.hr_foreign = 0;
-        P.hg16.assign(P.nbr.size(), static_cast<uint16_t>(kT16Pad));
         P.hr_entries = 0;
         const int32_t halo_cap = kTileCap - kTile;
         const int32_t ovf_cap = int32_t(kT16Far) - kTileCap;          // overflow slots a 15-bit code can name
@@ -680,11 +672,9 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
             const int32_t s_begin = t_begin * (kTile / kSlice);
             Q.tile_halo_ptr.assign(static_cast<size_t>(t_end - t_begin) + 1, 0);
             Q.tile_ovf_ptr.assign(static_cast<size_t>(t_end - t_begin) + 1, 0);
-            Q.te_chunk_ptr.assign(static_cast<size_t>(t_end - t_begin) + 1, 0);
             Q.hr_row0.assign(static_cast<size_t>(t_end - t_begin) * (kTile / kSlice) + 1, 0);
-            std::vector<int32_t> halo, tile_edges;
-            std::vector<std::array<int64_t, 4>> half_ents;      // {edge, entry index, thread of the node, its half row or -1}
-            std::vector<std::pair<int32_t, int32_t>> half_where;
+            std::vector<int32_t> halo;
+            std::vector<std::array<int64_t, 4>> half_ents;      // the evaluations the tile's nodes own: {edge, entry index, thread of the node, placed}
             std::vector<int32_t> halo_all;                  // a tile's halo ids, ALL of them ascending (the order-free kernel's own numbering)
             for (int32_t t = t_begin; t < t_end; t++) {
                 const int32_t base = t * kTile;
@@ -759,47 +749,6 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
                     }
                     P.nbr16[static_cast<size_t>(e)] = static_cast<uint16_t>(c16);
                 }
-                // edge-once list: the tile's internal edges, once each, ascending original index.  A node's
-                // incident edges keep their relative order in it, so summing a node's entries by position
-                // is the reference's accumulation order.
-                tile_edges.clear();
-                for (int64_t e = e0; e < e1; e++)
-                    if (entry_edge[static_cast<size_t>(e)] >= 0) tile_edges.push_back(entry_edge[static_cast<size_t>(e)]);
-                std::sort(tile_edges.begin(), tile_edges.end());
-                tile_edges.erase(std::unique(tile_edges.begin(), tile_edges.end()), tile_edges.end());
-                const int32_t n_te = static_cast<int32_t>(tile_edges.size());
-                P.te_count[static_cast<size_t>(t)] = n_te;
-                Q.te_max = std::max(Q.te_max, n_te);
-                Q.te_total += n_te;
-                if (n_te > kMaxEdgeChunks * kEdgeChunk) Q.edge_once = false;
-                if (Q.edge_once) {
-                    auto slot_of = [&](int32_t id) -> uint16_t {
-                        if (id >= base && id < base + kTile) return static_cast<uint16_t>(id - base);
-                        return static_cast<uint16_t>(kTile + halo_pos(id));   // >= kTileCap: overflow table, as in nbr16
-                    };
-                    const size_t chunk0 = static_cast<size_t>(Q.te_chunk_ptr[static_cast<size_t>(t - t_begin)]);
-                    const size_t n_chunks = (static_cast<size_t>(n_te) + kEdgeChunk - 1) / kEdgeChunk;
-                    Q.te_slots.resize((chunk0 + n_chunks) * 2 * kEdgeChunk, static_cast<uint16_t>(kT16Pad));
-                    Q.te_w.resize((chunk0 + n_chunks) * 4 * kEdgeChunk, 0.0);
-                    for (int32_t p = 0; p < n_te; p++) {
-                        const mgcfd_edge &E = edges[static_cast<size_t>(L.internal_start + tile_edges[static_cast<size_t>(p)])];
-                        const size_t c = chunk0 + static_cast<size_t>(p / kEdgeChunk), ln = static_cast<size_t>(p % kEdgeChunk);
-                        Q.te_slots[(c * 2 + 0) * kEdgeChunk + ln] = slot_of(P.new_of_old[static_cast<size_t>(E.a)]);
-                        Q.te_slots[(c * 2 + 1) * kEdgeChunk + ln] = slot_of(P.new_of_old[static_cast<size_t>(E.b)]);
-                        const double ewt = std::sqrt(E.x * E.x + E.y * E.y + E.z * E.z);
-                        Q.te_w[(c * 4 + 0) * kEdgeChunk + ln] = -0.5 * E.x;
-                        Q.te_w[(c * 4 + 1) * kEdgeChunk + ln] = -0.5 * E.y;
-                        Q.te_w[(c * 4 + 2) * kEdgeChunk + ln] = -0.5 * E.z;
-                        Q.te_w[(c * 4 + 3) * kEdgeChunk + ln] = -ewt * kSmoothing * 0.5;
-                    }
-                    for (int64_t e = e0; e < e1; e++) {
-                        const int32_t ge = entry_edge[static_cast<size_t>(e)];
-                        if (ge < 0) continue;
-                        const uint32_t p = static_cast<uint32_t>(std::lower_bound(tile_edges.begin(), tile_edges.end(), ge) - tile_edges.begin());
-                        P.gat16[static_cast<size_t>(e)] = static_cast<uint16_t>(p | ((P.nbr[static_cast<size_t>(e)] & kRoleB) ? kT16RoleB : 0u));
-                    }
-                    Q.te_chunk_ptr[static_cast<size_t>(t - t_begin) + 1] = static_cast<int32_t>(chunk0 + n_chunks);
-                }
                 // half rows: every entry of this tile whose node OWNS the evaluation of its edge (half_eval_a, decided before
                 // the nodes were ordered) is placed in a (half row, lane) slot of the tile: in the node's own lane while its
                 // slice has rows left (the evaluator then has its record in registers), otherwise in any lane with a free
@@ -826,19 +775,17 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
                             const int8_t who = half_eval_a[static_cast<size_t>(ge)];        // -1: both end points (each in its tile), 1: a, 0: b
                             const bool is_a = (P.nbr[static_cast<size_t>(e)] & kRoleB) == 0;
                             const bool evaluates = who < 0 || (who == 1) == is_a;
-                            if (evaluates) own[tid]++;
-                            half_ents.push_back({ge, e, tid, evaluates ? 1 : 0});
+                            if (evaluates) { own[tid]++; half_ents.push_back({ge, e, tid, 0}); }
                         }
                     }
                     int32_t n_eval = 0, own_slice[kTile / kSlice] = {0}, lanes[kTile / kSlice] = {0};
                     for (int32_t tid = 0; tid < n_here; tid++) { n_eval += own[tid]; own_slice[tid / kSlice] += own[tid]; lanes[tid / kSlice]++; }
                     // rows per slice: proportional to what the slice's nodes own, then one more wherever the capacity is short
                     int32_t rows_h[kTile / kSlice] = {0};
-                    // First with at most kHalfMaxRows rows per slice — what a lane of the ordered half-row kernel keeps in registers
-                    // and what the order-free kernel requests up front: a slice that owns more spills its surplus into the other
-                    // slices' lanes (foreign entries) and the level stays eligible for k_flux_half.  Only a tile whose evaluations do
-                    // not fit 5 rows x its lanes gets longer slices (up to kFreeMaxRows: the order-free kernel walks them in a loop).
-                    // (Round 3 went straight to the long slices and so took non-uniform levels away from k_flux_half: advisor finding.)
+                    // First with at most kHalfMaxRows rows per slice — what the order-free kernel requests up front: a slice that
+                    // owns more spills its surplus into the other slices' lanes (foreign entries) and the level stays uniform
+                    // (LevelPlan::half).  Only a tile whose evaluations do not fit 5 rows x its lanes gets longer slices (up to
+                    // kFreeMaxRows: the order-free kernel walks them in a loop).
                     auto distribute = [&](int32_t row_cap) {
                         int32_t cap_total = 0;
                         for (int32_t sl = 0; sl < kTile / kSlice; sl++) {
@@ -867,7 +814,6 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
                         Q.hr_code.resize(rows_end * kSlice, kHalfPad);
                         Q.hr_w.resize(rows_end * 3 * kSlice, 0.0);
                         int32_t used[kTile] = {0};
-                        half_where.clear();                                   // (edge, position of its flux terms) of this tile's evaluations
                         auto place = [&](const std::array<int64_t, 4> &en, int32_t host) {
                             const int32_t owner = static_cast<int32_t>(en[2]);
                             const int32_t sl = host / kSlice, lane = host % kSlice, j = used[host]++;
@@ -886,33 +832,22 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
                             Q.hr_w[(hrow * 3 + 0) * kSlice + lane] = W.x;
                             Q.hr_w[(hrow * 3 + 1) * kSlice + lane] = W.y;
                             Q.hr_w[(hrow * 3 + 2) * kSlice + lane] = W.z;
-                            const int32_t pos = static_cast<int32_t>(hrow - static_cast<size_t>(Q.hr_row0[static_cast<size_t>(s0 - s_begin)])) * kSlice + lane;
-                            P.hg16[static_cast<size_t>(e)] = static_cast<uint16_t>(pos);
-                            half_where.emplace_back(static_cast<int32_t>(en[0]), pos);
                             Q.hr_entries++;
                             if (host != owner) Q.hr_foreign++;
                         };
                         // own lane first (entries come node by node, in the node's row order) ...
                         for (auto &en : half_ents) {
-                            if (en[3] != 1) continue;
                             const int32_t tid = static_cast<int32_t>(en[2]);
-                            if (used[tid] < rows_h[tid / kSlice]) { place(en, tid); en[3] = 2; }
+                            if (used[tid] < rows_h[tid / kSlice]) { place(en, tid); en[3] = 1; }
                         }
                         // ... the rest wherever a slot is free
                         int32_t host = 0;
                         for (auto &en : half_ents) {
-                            if (en[3] != 1) continue;
+                            if (en[3]) continue;
                             while (host < n_here && used[host] >= rows_h[host / kSlice]) host++;
                             if (host >= n_here) throw std::logic_error("half rows: no free slot left in the tile");
                             place(en, host);
-                            en[3] = 2;
-                        }
-                        std::sort(half_where.begin(), half_where.end());
-                        for (const auto &en : half_ents) {
-                            if (en[3] != 0) continue;                        // the other end point owns the evaluation: its position, negated
-                            auto it = std::lower_bound(half_where.begin(), half_where.end(), std::make_pair(static_cast<int32_t>(en[0]), int32_t(-1)));
-                            if (it == half_where.end() || it->first != static_cast<int32_t>(en[0])) throw std::logic_error("half rows: an edge without an evaluator in its tile");
-                            P.hg16[static_cast<size_t>(en[1])] = static_cast<uint16_t>(uint32_t(it->second) | kT16RoleB);
+                            en[3] = 1;
                         }
                     }
                 }
@@ -936,28 +871,24 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
         }
         for (const Part &Q : parts) if (Q.error) std::rethrow_exception(Q.error);     // (the lowest tile range's error first)
         // join the parts in tile order
-        int64_t halo_total = 0, te_total = 0;
+        int64_t halo_total = 0;
         {
             int32_t t0 = 0;
             for (int k = 0; k < n_threads; k++) {
                 const Part &Q = parts[static_cast<size_t>(k)];
                 const int32_t nt = static_cast<int32_t>(Q.tile_halo_ptr.size()) - 1;
                 const int32_t halo0 = static_cast<int32_t>(P.tile_halo.size()), ovf0 = static_cast<int32_t>(P.tile_ovf.size());
-                const int32_t chunk0 = P.te_chunk_ptr[static_cast<size_t>(t0)], row0 = P.hr_row0[static_cast<size_t>(t0) * (kTile / kSlice)];
+                const int32_t row0 = P.hr_row0[static_cast<size_t>(t0) * (kTile / kSlice)];
                 for (int32_t t = 0; t < nt; t++) {
                     P.tile_halo_ptr[static_cast<size_t>(t0 + t) + 1] = halo0 + Q.tile_halo_ptr[static_cast<size_t>(t) + 1];
                     P.tile_ovf_ptr[static_cast<size_t>(t0 + t) + 1] = ovf0 + Q.tile_ovf_ptr[static_cast<size_t>(t) + 1];
-                    P.te_chunk_ptr[static_cast<size_t>(t0 + t) + 1] = chunk0 + Q.te_chunk_ptr[static_cast<size_t>(t) + 1];
                 }
                 for (size_t q = 1; q < Q.hr_row0.size(); q++) P.hr_row0[static_cast<size_t>(t0) * (kTile / kSlice) + q] = row0 + Q.hr_row0[q];
                 P.tile_halo.insert(P.tile_halo.end(), Q.tile_halo.begin(), Q.tile_halo.end());
                 P.tile_ovf.insert(P.tile_ovf.end(), Q.tile_ovf.begin(), Q.tile_ovf.end());
-                // (a part's lists end where its last tile's chunks / half rows end: resize() inside the loop keeps them exact)
-                P.te_slots.insert(P.te_slots.end(), Q.te_slots.begin(), Q.te_slots.end());
-                P.te_w.insert(P.te_w.end(), Q.te_w.begin(), Q.te_w.end());
+                // (a part's lists end where its last tile's half rows end: resize() inside the loop keeps them exact)
                 P.hr_code.insert(P.hr_code.end(), Q.hr_code.begin(), Q.hr_code.end());
                 P.hr_w.insert(P.hr_w.end(), Q.hr_w.begin(), Q.hr_w.end());
-                P.edge_once = P.edge_once && Q.edge_once;
                 if (P.free_rows) {
                     // (one thread stops looking at half rows at the first tile that cannot have them; a part stopped at ITS first
                     //  such tile, so the parts up to and including the first failing one are what one thread would have seen)
@@ -969,20 +900,13 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
                     P.free_rows = Q.free_rows;
                 }
                 P.halo_max = std::max(P.halo_max, Q.halo_max);
-                P.te_max = std::max(P.te_max, Q.te_max);
                 P.halo_overflow_refs += Q.halo_overflow_refs;
                 halo_total += Q.halo_total;
-                te_total += Q.te_total;
                 t0 += nt;
             }
         }
         P.halo_mean = P.n_tiles ? double(halo_total) / double(P.n_tiles) : 0.0;
         P.halo_total = halo_total;
-        P.te_mean = P.n_tiles ? double(te_total) / double(P.n_tiles) : 0.0;
-        if (!P.edge_once) {
-            P.te_slots.clear(); P.te_w.clear(); P.gat16.clear();
-            P.te_chunk_ptr.assign(static_cast<size_t>(P.n_tiles) + 1, 0);
-        }
     }
 
     lap("tile loop");
@@ -1080,11 +1004,11 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
     P.tail_tile_ptr[static_cast<size_t>(P.n_tiles)] = static_cast<int32_t>(P.tail_rec.size() / 6);
     P.tail_total = static_cast<int64_t>(P.tail_rec.size() / 6);
     if (!P.has_tail) { P.tail_begin.clear(); P.tail_count.clear(); }
-    // the ordered half-row kernel: levels without long rows whose every slice fits the per-thread row limit and every tile the
-    // flux terms' LDS image; the order-free kernel (free_rows) takes any row count
+    // a uniform half-row plan: no long rows, every slice within the rows a lane requests up front, every tile within
+    // kHalfTileRows; the order-free kernel (free_rows) takes any row count
     P.half = P.free_rows && !P.free_wide && !P.has_tail && P.hr_max_rows <= kHalfMaxRows && P.hr_max_tile_rows <= kHalfTileRows;
     if (!P.free_rows || !P.free_wide) { P.free_halo.clear(); P.free_halo.shrink_to_fit(); }
-    if (!P.free_rows) { P.hr_row0.clear(); P.hr_code.clear(); P.hr_w.clear(); P.hg16.clear(); P.hr_entries = 0; P.hr_foreign = 0; }
+    if (!P.free_rows) { P.hr_row0.clear(); P.hr_code.clear(); P.hr_w.clear(); P.hr_entries = 0; P.hr_foreign = 0; }
     else P.hr_padding = int64_t(P.hr_row0.back()) * kSlice - P.hr_entries;
 
     lap("long rows");
@@ -1268,8 +1192,8 @@ void build_transfer_plan(const mgcfd_level_desc &F, const std::vector<mgcfd_edge
 // ------------------------------------------------------------------------------------------
 // Bounds audit of a freshly built plan (before the solver drops the host copies): every index the kernels form from
 // the plan's tables — LDS slots, halo and overflow positions, half-row owners, list entries, children, staged coarse
-// nodes — against the size of what it indexes, as kernels.hip forms it (k_flux_tile and its role-5 form, k_flux_half,
-// k_flux_free, k_flux_edge_once, k_restrict, k_prolong_tile).  Returns "" when everything is in range, else one line
+// nodes — against the size of what it indexes, as kernels.hip forms it (k_flux_tile and its role-5 form,
+// k_flux_free, k_restrict, k_prolong_tile).  Returns "" when everything is in range, else one line
 // per kind of violation (the first few of each).  Host only: tests/test_host_plan_audit.py, tools/plan_stats.cpp.
 // ------------------------------------------------------------------------------------------
 // A digest of every array the per-tile part of the plan produces (FNV-1a over their bytes): the plan must not depend on how many
@@ -1284,13 +1208,12 @@ uint64_t plan_digest(const LevelPlan &P)
     auto vec = [&](const auto &v) { const uint64_t n = v.size(); eat(&n, sizeof(n)); if (n) eat(v.data(), n * sizeof(v[0])); };
     vec(P.old_of_new); vec(P.slice_row0); vec(P.rows_int); vec(P.rows_bnd); vec(P.nbr); vec(P.nbr16);
     vec(P.tile_halo_ptr); vec(P.tile_halo); vec(P.tile_ovf_ptr); vec(P.tile_ovf);
-    vec(P.te_chunk_ptr); vec(P.te_count); vec(P.te_slots); vec(P.te_w); vec(P.gat16);
-    vec(P.free_halo); vec(P.hr_row0); vec(P.hr_code); vec(P.hr_w); vec(P.hg16);
+    vec(P.free_halo); vec(P.hr_row0); vec(P.hr_code); vec(P.hr_w);
     vec(P.rows_main); vec(P.tail_tile_ptr); vec(P.tail_rec); vec(P.tail_begin); vec(P.tail_count);
     // ... and the transfer plan (build_transfer_plan: inverse distances and its per-tile part on host threads as well)
     vec(P.child_ptr); vec(P.child); vec(P.pro); vec(P.pro_parent); vec(P.pro_wsum); vec(P.pro_tile_n); vec(P.pro_tile_ids); vec(P.pro_s16); vec(P.pro_own16);
-    const int64_t scalars[] = {P.halo_max, P.te_max, P.hr_max_rows, P.hr_max_tile_rows, P.halo_overflow_refs, P.hr_entries, P.hr_foreign, P.halo_total,
-                               int64_t(P.edge_once), int64_t(P.free_rows), int64_t(P.free_wide), int64_t(P.half), int64_t(P.has_tail)};
+    const int64_t scalars[] = {P.halo_max, P.hr_max_rows, P.hr_max_tile_rows, P.halo_overflow_refs, P.hr_entries, P.hr_foreign, P.halo_total,
+                               int64_t(P.free_rows), int64_t(P.free_wide), int64_t(P.half), int64_t(P.has_tail)};
     eat(scalars, sizeof(scalars));
     return h;
 }
@@ -1369,7 +1292,7 @@ std::string audit_level_plan(const mgcfd_level_desc &L, const LevelPlan &P, int6
         }
         if (P.free_rows) {
             const int32_t r0 = P.hr_row0[size_t(s0)], r1 = P.hr_row0[size_t(s0) + kTile / kSlice];
-            if (P.half && r1 - r0 > kHalfTileRows) bad(9, "tile " + S(t) + ": " + S(r1 - r0) + " half rows exceed what the flux terms' LDS image holds");
+            if (P.half && r1 - r0 > kHalfTileRows) bad(9, "tile " + S(t) + ": " + S(r1 - r0) + " half rows exceed what a uniform plan (half) holds");
             if (!P.free_wide && n_ovf != 0) bad(9, "tile " + S(t) + ": half rows on a tile with unstaged halo nodes and no table of their own");
             for (int32_t sl = s0; sl < s0 + kTile / kSlice; sl++) {
                 const int32_t n_h = P.hr_row0[size_t(sl) + 1] - P.hr_row0[size_t(sl)];
@@ -1392,28 +1315,7 @@ std::string audit_level_plan(const mgcfd_level_desc &L, const LevelPlan &P, int6
                         if (((c & kHalfForeign) != 0) != (own != host)) bad(10, "tile " + S(t) + ": the foreign flag of a half row disagrees with its owner");
                         if ((c & kHalfMirror) && (c & kT16SlotMask) >= uint32_t(kTile)) bad(10, "tile " + S(t) + ": a half row hands -F to a node outside the tile");
                     }
-                for (int64_t row = P.slice_row0[size_t(sl)]; row < P.slice_row0[size_t(sl)] + P.rows_int[size_t(sl)]; row++)
-                    for (int lane = 0; lane < kSlice; lane++) {
-                        const uint32_t g = P.hg16[size_t(row) * kSlice + lane] & kT16SlotMask;
-                        if (g != kT16Pad && int32_t(g) >= (r1 - r0) * kSlice) bad(11, "tile " + S(t) + ": a gather position beyond the tile's flux terms");
-                    }
             }
-        }
-        if (P.edge_once) {
-            const int32_t n_te = P.te_count[size_t(t)];
-            const int32_t chunks = P.te_chunk_ptr[size_t(t) + 1] - P.te_chunk_ptr[size_t(t)];
-            if (n_te > chunks * kEdgeChunk || chunks > kMaxEdgeChunks) bad(12, "tile " + S(t) + ": " + S(n_te) + " listed edges in " + S(chunks) + " chunks");
-            for (int32_t pp = 0; pp < n_te; pp++) {
-                const size_t c = size_t(P.te_chunk_ptr[size_t(t)]) + size_t(pp / kEdgeChunk), ln = size_t(pp % kEdgeChunk);
-                code_ok(P.te_slots[(c * 2 + 0) * kEdgeChunk + ln], -1, "edge list (a)");
-                code_ok(P.te_slots[(c * 2 + 1) * kEdgeChunk + ln], -1, "edge list (b)");
-            }
-            for (int32_t sl = s0; sl < s0 + kTile / kSlice; sl++)
-                for (int64_t row = P.slice_row0[size_t(sl)]; row < P.slice_row0[size_t(sl)] + P.rows_int[size_t(sl)]; row++)
-                    for (int lane = 0; lane < kSlice; lane++) {
-                        const uint32_t g = P.gat16[size_t(row) * kSlice + lane] & kT16SlotMask;
-                        if (g != kT16Pad && int32_t(g) >= n_te) bad(12, "tile " + S(t) + ": a row refers to listed edge " + S(g) + " of " + S(n_te));
-                    }
         }
     }
     // role 5 (k_flux_tile absorbing the first stage's time_step) reads old_variables / vin_flux / volumes at every staged node and

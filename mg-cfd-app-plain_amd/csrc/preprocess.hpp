@@ -29,29 +29,21 @@ constexpr int kTileCap = 559;
 // ... and what the four-workgroups-per-CU form of the bit-identical stages stages (80-byte records, kernels.hip: FluxTileLds4):
 // 510 * 80 B + 96 B = 40,896 B = 32 granules = a quarter of the CU.  Levels whose every tile halo fits 254 slots run it.
 constexpr int kTileCap4 = 510;
-// edge-once tiles: a tile's internal edges are evaluated in chunks of one edge per thread; the
-// fluxes of up to kMaxEdgeChunks chunks wait in registers, then replace the node records in LDS
-// (kMaxEdgeChunks * 256 * 40 B must fit kTileCap * 96 B)
 constexpr int kHaloStride = kTileCap - kTile;   // halo ids a tile can stage (device table: fixed stride, -1 padded)
 static_assert(kTileCap >= 2 * kTile, "every thread has a halo slot (the kernels stage one unconditionally)");
 static_assert(kHaloStride <= 2 * kTile, "the staging code reads at most two halo ids per thread");
 // prolongation tiles: distinct coarse nodes (own parents + neighbours' parents) a fine tile may stage in LDS (40 B each)
 constexpr int kProCap = 768;
-constexpr int kEdgeChunk = 256;
-constexpr int kMaxEdgeChunks = 5;
 constexpr uint32_t kHalfForeign = 1u << 24;
 constexpr uint32_t kHalfMirror = 1u << 25;    // the edge lies inside the tile and this is its only evaluation: the other end takes the
-                                              // negated terms (k_flux_free adds them to that node's LDS sum; k_flux_half hands them over by position)
+                                              // negated terms (k_flux_free adds them to that node's LDS sum)
 constexpr uint32_t kHalfPad = 0x00007FFFu;   // (low 15 bits = kT16Pad)
-constexpr int kHalfMaxRows = 5;            // half rows (edges a node evaluates) a thread keeps the results of in registers
+constexpr int kHalfMaxRows = 5;            // half rows (edges a node evaluates) a thread of k_flux_free requests up front
 constexpr int kFreeHaloStride = 2 * kTile; // halo ids a tile of the order-free kernel can stage from its OWN table (two per thread: 56-byte LDS images,
                                            // 768 of them + the sums = 53,248 B, three workgroups per CU) where some tile's halo exceeds kHaloStride
 constexpr int kFreeCap4Halo = 290;         // the largest halo with which four workgroups of the order-free kernel share a CU (kernels.hip: kFreeCap4 - kTile)
 constexpr int kFreeMaxRows = 32;           // ... and what a slice may hold at all: the order-free kernel walks the rows beyond five in a loop
-constexpr int kHalfTileRows = 21;          // half rows of a tile's four slices together (21 * 64 * 40 B = the whole LDS tile)
-constexpr int kHalfSlots = kHalfTileRows * kSlice;   // flux-term slots of a tile in LDS: 5 fields x 1344 x 8 B = 52.5 KiB (its own array in k_flux_half)
-constexpr int kHalfLdsD2 = (5 * kHalfSlots + 1) / 2;   // double2 the half-row kernel's flux terms take in LDS (they replace the node records)
-static_assert(kMaxEdgeChunks * kEdgeChunk * 40 <= kTileCap * 96, "edge fluxes must fit the LDS tile");
+constexpr int kHalfTileRows = 21;          // half rows of a tile's four slices together on a uniform level (LevelPlan::half)
 
 // neighbour codes in Sell::nbr
 constexpr int32_t kRoleB = 1 << 30;     // set when THIS node is the edge's 'b' end (else it is 'a')
@@ -96,26 +88,15 @@ struct LevelPlan {
     //   internal, this node = b:  (x,y,z) = +0.5*e   k = same
     //   wall (-1):                (x,y,z) = e                                  (flux_boundary_kernel.elemfunc.c:37-45)
     //   far field (-2):           (x,y,z) = 0.5*e                              (flux_wall_kernel.elemfunc.c:51-53)
-    // ---- edge-once tiles: every internal edge that touches a tile, listed once per tile in
-    //      ORIGINAL edge order; entry p of tile t is evaluated by thread p % 256 in chunk p / 256 ----
-    bool edge_once = false;               // false: some tile holds more than kMaxEdgeChunks*256 edges (node gather only)
-    int32_t te_max = 0; double te_mean = 0.0;
-    std::vector<int32_t> te_chunk_ptr;    // [n_tiles+1] first chunk of each tile
-    std::vector<int32_t> te_count;        // [n_tiles] edges of each tile
-    std::vector<uint16_t> te_slots;       // [chunk][2][256] LDS slot (as nbr16, no role bit) of end points a and b; kT16Pad = no edge
-    std::vector<double> te_w;             // [chunk][4][256] a-side weights: -0.5*e (x,y,z) and k = -|e|*smoothing*0.5
-    std::vector<uint16_t> gat16;          // [rows*64] internal rows: position p of the entry's edge in its tile's list
-                                          //   | kT16RoleB when this node is the edge's b end (it gets -F); kT16Pad
-    // ---- half rows (k_flux_half): every internal edge that touches a tile is EVALUATED by exactly one of its end points
+    // ---- half rows (k_flux_free): every internal edge that touches a tile is EVALUATED by exactly one of its end points
     //      in the tile (an edge inside the tile by the less loaded of the two, an edge cut by the tile boundary by the end
     //      inside), so a tile streams one 28-byte row entry per edge instead of one of 26-34 bytes per end point, and
-    //      evaluates each edge once.  The evaluator leaves the five flux terms in LDS at position (half row within the tile) * 64 + lane;
-    //      every node then adds its incident edges in row order from there (hg16: position | kT16RoleB when the entry's
-    //      edge was evaluated by the OTHER end point: that node adds the negated terms, which is what the reference's
-    //      expressions for the other end evaluate to bit for bit) ----
+    //      evaluates each edge once.  The evaluator adds the five flux terms to its own node's sum and, for an edge inside
+    //      the tile, the negated terms to the other end's (which is what the reference's expressions for the other end
+    //      evaluate to bit for bit) ----
     bool free_rows = false;               // the half-row plan exists (k_flux_free can run): every tile's halo is staged in LDS
-    bool half = false;                    // ... and k_flux_half can run on it too: no slice needs more than kHalfMaxRows rows, no tile more than
-                                          // kHalfTileRows, no long rows
+    bool half = false;                    // ... and is uniform: no slice needs more than kHalfMaxRows rows, no tile more than
+                                          // kHalfTileRows, no wide halos, no long rows
     int32_t hr_max_rows = 0, hr_max_tile_rows = 0;
     bool free_wide = false;               // some tile's halo exceeds kHaloStride: the order-free kernel stages from free_halo, and the half rows' slots
                                           // count positions in THAT list (256 + position among ALL the tile's halo ids, ascending)
@@ -126,7 +107,6 @@ struct LevelPlan {
                                           //   sits in another node's lane (that lane reads the owner's record from LDS too), kHalfMirror when
                                           //   the other end lies in the tile and leaves the evaluation to this entry; kHalfPad
     std::vector<double> hr_w;             // [half rows][3][64] the evaluator's weights (as w.x, w.y, w.z of its own entry)
-    std::vector<uint16_t> hg16;           // [rows*64] internal rows: where the entry's flux terms are | kT16RoleB = subtract; kT16Pad
     int64_t hr_entries = 0, hr_padding = 0, hr_foreign = 0;
     // ---- long rows: a node's internal entries beyond its tile's row limit.  The per-node loop stops at the limit;
     //      the whole workgroup then evaluates the remaining entries one per thread, leaves the five results in a

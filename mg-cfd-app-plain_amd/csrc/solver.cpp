@@ -636,29 +636,12 @@ struct mgcfd_solver {
         LevelPlan &P = lv.plan;
         const int v = opt_variant;
         auto take = [&lv](auto &vec) { auto *p = lv.mem.upload(vec); vec.clear(); vec.shrink_to_fit(); return p; };
-        // order-free / half rows: MGCFD_OPT_EXACT = 0 (the automatic variant takes the order-free kernel), or bits 5 / 6
-        if (lv.dp.free_rows && !lv.dp.hr_code && (!opt_exact || (v >= 0 && (v & (32 | 64))))) {
+        // the half-row plan: MGCFD_OPT_EXACT = 0 (the automatic variant takes the order-free kernel), or bit 6
+        if (lv.dp.free_rows && !lv.dp.hr_code && (!opt_exact || (v >= 0 && (v & 64)))) {
             lv.dp.hr_row0 = lv.mem.upload(P.hr_row0);
             lv.dp.hr_code = take(P.hr_code);
             lv.dp.hr_w = take(P.hr_w);
             if (lv.dp.free_wide) lv.dp.free_halo = take(P.free_halo);
-        }
-        if (lv.dp.free_rows && !lv.dp.hg16 && v >= 0 && (v & 32)) lv.dp.hg16 = take(P.hg16);
-        // edge-once tiles (bit 1) and indexed weights (bit 4)
-        if (lv.dp.edge_once && !lv.dp.gat16 && v >= 0 && (v & (2 | 16))) {
-            lv.dp.te_chunk_ptr = lv.mem.upload(P.te_chunk_ptr);
-            lv.dp.te_count = lv.mem.upload(P.te_count);
-            lv.dp.gat16 = take(P.gat16);
-            {   // the a-side weights as 24-byte records, one per listed edge (k_flux_tile WMODE 2: indexed weights)
-                const size_t n_chunks = P.te_w.size() / (4 * kEdgeChunk);
-                std::vector<double> w3(n_chunks * kEdgeChunk * 3);
-                for (size_t c = 0; c < n_chunks; c++)
-                    for (size_t ln = 0; ln < size_t(kEdgeChunk); ln++)
-                        for (size_t k = 0; k < 3; k++) w3[(c * kEdgeChunk + ln) * 3 + k] = P.te_w[(c * 4 + k) * kEdgeChunk + ln];
-                lv.dp.te_w3 = lv.mem.upload(w3);
-            }
-            lv.dp.te_slots = take(P.te_slots);
-            lv.dp.te_w = take(P.te_w);
         }
         // the two-phase design point (bit 2)
         if (!lv.dp.fe_ab && v >= 0 && (v & 4)) {
@@ -1131,10 +1114,9 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
         popt.long_rows = !std::getenv("MGCFD_NO_LONG_ROWS");      // (diagnostic: per-node rows only, overflow entries gathered in the loop)
         build_level_plan(d, lv.edges, popt, lv.plan);
         if (std::getenv("MGCFD_VERBOSE"))
-            std::fprintf(stderr, "[mgcfd] level %d: %ld nodes, %d tiles, halo mean %.0f max %d (cap %d), overflow refs %ld, ELL padding %.1f%%, tile edges mean %.0f max %d (edge-once %s)\n",
+            std::fprintf(stderr, "[mgcfd] level %d: %ld nodes, %d tiles, halo mean %.0f max %d (cap %d), overflow refs %ld, ELL padding %.1f%%\n",
                          l, (long)d.nel, lv.plan.n_tiles, lv.plan.halo_mean, lv.plan.halo_max, kTileCap - kTile,
-                         (long)lv.plan.halo_overflow_refs, 100.0 * lv.plan.pad_fraction, lv.plan.te_mean, lv.plan.te_max,
-                         lv.plan.edge_once ? "yes" : "no");
+                         (long)lv.plan.halo_overflow_refs, 100.0 * lv.plan.pad_fraction);
         if (std::getenv("MGCFD_VERBOSE"))
             std::fprintf(stderr, "[mgcfd] level %d: half rows %s: %ld evaluations (%.2f per node), %ld in another node's lane, %ld padding slots (%.1f%%)\n", l, lv.plan.half ? "yes" : "no",
                          (long)lv.plan.hr_entries, double(lv.plan.hr_entries) / double(d.nel), (long)lv.plan.hr_foreign, (long)lv.plan.hr_padding,
@@ -1174,7 +1156,7 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
     });
     lap("transfer plans");
     // What the device gets, level by level, listed and repacked with no call into the runtime (LevelStaging): a host thread
-    // per level.  What only a non-default option reaches — the order-free / half-row plan, the edge-once lists, the
+    // per level.  What only a non-default option reaches — the order-free kernel's half-row plan, the
     // two-phase arrays, the 32-bit neighbour codes — stays on the host until an option asks for it (upload_optional_plans):
     // 60 % of the bytes.
     std::vector<LevelStaging> staging(static_cast<size_t>(nlevels));
@@ -1244,7 +1226,6 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
         st.upload(lv.dp.tile_ovf, P.tile_ovf);
         lv.row_bytes = int64_t(P.slice_row0.back()) * kSlice * 34;
         lv.dp.pad_row = P.slice_row0.back();
-        lv.dp.pad_chunk = P.te_chunk_ptr.empty() ? 0 : P.te_chunk_ptr.back();
         lv.dp.n_edges = d.n_internal;
         lv.dp.n_edges_pad = (d.n_internal + 255) / 256 * 256;
         lv.plan.row_edge.resize(P.row_edge.size() + 2 * kSlice, -1);                     // two rows of padding
@@ -1262,12 +1243,6 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
         lv.dp.vin_ok = (P.halo_overflow_refs == 0 && P.halo_max <= kTile) ? 1 : 0;
         lv.dp.lds_complete = P.halo_overflow_refs == 0 ? 1 : 0;
         lv.dp.halo_max = P.halo_max;
-        lv.dp.edge_once = (P.edge_once && !std::getenv("MGCFD_NO_EDGE_ONCE")) ? 1 : 0;
-        if (lv.dp.edge_once) {
-            lv.plan.te_slots.resize(P.te_slots.size() + 2 * kEdgeChunk, static_cast<uint16_t>(kT16Pad));   // one chunk of padding
-            lv.plan.te_w.resize(P.te_w.size() + 4 * kEdgeChunk, 0.0);
-            lv.plan.gat16.resize(P.gat16.size() + 2 * kSlice, static_cast<uint16_t>(kT16Pad));   // two rows of padding
-        }
         lv.dp.half = (P.half && !std::getenv("MGCFD_NO_HALF_ROWS")) ? 1 : 0;
         lv.dp.free_rows = (P.free_rows && !std::getenv("MGCFD_NO_HALF_ROWS")) ? 1 : 0;
         lv.dp.hr_max_rows = P.hr_max_rows;
@@ -1277,16 +1252,9 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
             lv.dp.hr_pad_row = P.hr_row0.back();
             lv.plan.hr_code.resize(P.hr_code.size() + 2 * kSlice, kHalfPad);      // two half rows of padding
             lv.plan.hr_w.resize(P.hr_w.size() + 2 * 3 * kSlice, 0.0);
-            lv.plan.hg16.resize(P.hg16.size() + 2 * kSlice, static_cast<uint16_t>(kT16Pad));
         } else {
             lv.plan.hr_code.clear(); lv.plan.hr_code.shrink_to_fit();
             lv.plan.hr_w.clear(); lv.plan.hr_w.shrink_to_fit();
-            lv.plan.hg16.clear(); lv.plan.hg16.shrink_to_fit();
-        }
-        if (!lv.dp.edge_once) {
-            lv.plan.te_slots.clear(); lv.plan.te_slots.shrink_to_fit();
-            lv.plan.te_w.clear(); lv.plan.te_w.shrink_to_fit();
-            lv.plan.gat16.clear(); lv.plan.gat16.shrink_to_fit();
         }
         if (lv.has_transfer) {
             st.upload(lv.dp.child_ptr, P.child_ptr);
@@ -1563,7 +1531,12 @@ int mgcfd_set_option(mgcfd_solver *s, int option, int value)
                 break;
             case MGCFD_OPT_INDIRECT_RW: s->opt_indirect_rw = value != 0; break;
             case MGCFD_OPT_CHECK_INVALID: s->opt_check = value != 0; break;
-            case MGCFD_OPT_FLUX_VARIANT: s->opt_variant = value; s->upload_optional_plans(); break;
+            case MGCFD_OPT_FLUX_VARIANT:
+                // (the layouts of bits 1, 4 and 5 are gone: refused by name, never run as another kernel; the option keeps its value)
+                if (value >= 0 && (value & 2)) throw std::invalid_argument("MGCFD_OPT_FLUX_VARIANT bit 1 (2): the edge-once layout was removed");
+                if (value >= 0 && (value & 16)) throw std::invalid_argument("MGCFD_OPT_FLUX_VARIANT bit 4 (16): the indexed-weights layout was removed");
+                if (value >= 0 && (value & 32)) throw std::invalid_argument("MGCFD_OPT_FLUX_VARIANT bit 5 (32): the ordered half-row layout was removed");
+                s->opt_variant = value; s->upload_optional_plans(); break;
             case MGCFD_OPT_FUSE_UPDATE: s->opt_fuse = value != 0; break;
             case MGCFD_OPT_GRAPH: s->opt_graph = value != 0; break;
             case MGCFD_OPT_RANK_SPLIT: s->opt_rank_split = value < 0 ? 0 : (value > 2 ? 2 : value); break;
@@ -1591,13 +1564,6 @@ int mgcfd_level_stage_wg4(const mgcfd_solver *s, int level, int *yes)
     REQUIRE(s); REQUIRE(yes);
     if (level < 0 || level >= static_cast<int>(s->L.size())) { g_last_error = "level out of range"; return MGCFD_ERR_ARG; }
     *yes = s->stage_wg4_for(s->L[static_cast<size_t>(level)]) ? 1 : 0;
-    return MGCFD_OK;
-}
-int mgcfd_level_has_edge_once(const mgcfd_solver *s, int level, int *yes)
-{
-    REQUIRE(s); REQUIRE(yes);
-    if (level < 0 || level >= static_cast<int>(s->L.size())) { g_last_error = "level out of range"; return MGCFD_ERR_ARG; }
-    *yes = s->L[static_cast<size_t>(level)].dp.edge_once;
     return MGCFD_OK;
 }
 int mgcfd_level_tiling(const mgcfd_solver *s, int level, int64_t out[10])
@@ -2310,7 +2276,7 @@ static int sweep_end_impl(mgcfd_solver *s, int level, bool scalar)
         };
         StageArgs first;
         first.apply_min = apply;
-        if (lv.sweep_flux0_done && global_dt && lv.dp.vin_ok && !((s->variant_for(lv) & 2) && lv.dp.edge_once)) {
+        if (lv.sweep_flux0_done && global_dt && lv.dp.vin_ok) {
             // the second stage applies the first stage's time_step (on the fluxes of sweep_flux0) to its own
             // input while it stages it: no separate time_step launch, the first stage's result never touches memory
             first.vin_flux = lv.fluxes;

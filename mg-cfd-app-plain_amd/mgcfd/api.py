@@ -85,7 +85,6 @@ _SIGNATURES = [
     ("mgcfd_destroy", None, [_vp]),
     ("mgcfd_live_device_resources", C.c_int, [C.POINTER(_i64)]),
     ("mgcfd_set_option", C.c_int, [_vp, C.c_int, C.c_int]),
-    ("mgcfd_level_has_edge_once", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     ("mgcfd_level_has_half_rows", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     ("mgcfd_pending_invalid_state", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("mgcfd_level_has_order_free", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
@@ -524,11 +523,6 @@ class Solver:
         yes = C.c_int(0)
         self._c(self.lib.mgcfd_level_stage_wg4(self.handle, l, C.byref(yes)))
         return bool(yes.value)
-
-    def has_edge_once(self, l: int) -> bool:
-        v = C.c_int()
-        self._c(self.lib.mgcfd_level_has_edge_once(self.handle, l, C.byref(v)))
-        return bool(v.value)
 
     def get_option(self, name: str) -> int:
         v = C.c_int()

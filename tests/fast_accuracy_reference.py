@@ -298,7 +298,7 @@ def build_cases(oracle, mesh3_dir, fvcorr_dir):
     m1 = meshgen.make_multigrid((9,), "m6wing", seed=3, cavity_radius=0.15, jitter=0.2, area_noise=0.05, volume_noise=0.05)
     cases["m6wing_1lvl"] = (mgcfd.generated_to_levels(m1), m1.mesh_variant, 0, ("perturbed", "wide"))
     # (the (11, 6) lattice has long rows — a tail list — and its plan does not tell whether a lane holds more than five half rows;
-    #  (12, 6) is the smallest without a tail that the ordered half-row kernel declines, which leaves that one reason)
+    #  (12, 6) is the smallest without a tail whose plan is not uniform (has_half_rows false), which leaves that one reason)
     mx = meshgen.make_mixed_multigrid((12, 6), "m6wing", seed=2, jitter=0.2, area_noise=0.05, volume_noise=0.05)
     cases["mixed"] = (mgcfd.generated_to_levels(mx), mx.mesh_variant, 0, ("perturbed", "wide"))
     tet = meshgen.MultigridMesh(mesh_name="m6wing")

@@ -48,3 +48,29 @@ def test_reference_main_runs_on_the_gpu_library(case, tmp_path):
     # the library really was in the process (the binding has no host fallback: without it the link would not resolve)
     ldd = subprocess.run(["ldd", EXE], capture_output=True, text=True).stdout
     assert "libmgcfd_hip.so" in ldd
+
+
+def test_removed_flux_layouts_are_refused_by_name():
+    """MGCFD_OPT_FLUX_VARIANT bits 1, 4 and 5 (edge-once tiles, indexed weights, the ordered half-row kernel) are gone:
+    a value with one of them set is an argument error that names the layout and leaves the option and the solver as they
+    were — never another kernel under the removed name.  Every other value is accepted as before."""
+    import numpy as np
+    import mgcfd
+    d, _, dup = _case("fvcorr_1lvl")
+    mesh = mgcfd.Mesh("input.dat", os.path.join(d, "input"), dup)
+    s = mgcfd.Solver.from_mesh(mesh)
+    held = s.get_option("flux_variant")
+    for v, layout in ((2, "edge-once"), (3, "edge-once"), (16, "indexed"), (32, "half-row"), (33, "half-row"), (2 | 64, "edge-once")):
+        with pytest.raises(mgcfd.MgcfdError) as err:
+            s.set_option("flux_variant", v)
+        assert err.value.code == 1 and layout in str(err.value) and "removed" in str(err.value), (v, str(err.value))
+        assert s.get_option("flux_variant") == held, v
+    fresh = mgcfd.Solver.from_mesh(mesh)
+    s.smooth(0, 1)
+    fresh.smooth(0, 1)
+    assert np.array_equal(s.get(0, "variables").view(np.int64), fresh.get(0, "variables").view(np.int64))
+    fresh.close()
+    for v in (-1, 0, 1, 4, 5, 8, 64, 65):
+        s.set_option("flux_variant", v)
+        assert s.get_option("flux_variant") == v
+    s.close()

@@ -111,7 +111,7 @@ def instantiation(s, l, wg3=False, no_roles=False):
     til = s.tiling(l)
     wide = til["halo_max"] > til["halo_capacity"]
     cap4 = til["halo_max"] <= FREE_CAP4_HALO and not wg3 and not wide
-    # (the ordered half-row kernel declines a level without long rows only for more than five half rows per lane)
+    # (has_half_rows is false on a level without long rows or wide halos only for more than five half rows per lane)
     long_rows = (not wide) and til["list_entries"] == 0 and not s.has_half_rows(l)
     cap = "WIDE(768)" if wide else ("CAP546" if cap4 else "CAP559")
     name = f"{cap}{' LONG' if long_rows and not wide else ''}"

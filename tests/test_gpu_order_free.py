@@ -197,7 +197,7 @@ def test_order_free_on_levels_of_non_uniform_degree(oracle):
     s = mgcfd.Solver.from_arrays(levels, mg.mesh_variant)
     s.set_option("exact", 0)
     s.set_option("flux_variant", FREE)
-    assert s.has_order_free(0) and not s.has_half_rows(0)       # (more than five evaluations per lane somewhere: the ordered half-row kernel declines)
+    assert s.has_order_free(0) and not s.has_half_rows(0)       # (more than five evaluations per lane somewhere: the half-row plan is not uniform)
     q = bench.perturbed_state(nel, s.far_field()[:5])
     s.set(0, "variables", q)
     s.zero_fluxes(0)

@@ -10,7 +10,7 @@ print(json.dumps(bench.mixed_mesh_roofline(make_solver, False), indent=1))
 mg, levels = bench.build_workload(67, mesh="mixed")
 s = mgcfd.Solver.from_arrays(levels, mg.mesh_variant)
 s.set(0, "variables", bench.perturbed_state(s.nel(0), s.far_field()[:5]))
-print("half rows:", s.has_half_rows(0), "order-free plan:", s.has_order_free(0), "edge once:", s.has_edge_once(0))
+print("half rows:", s.has_half_rows(0), "order-free plan:", s.has_order_free(0))
 for name, exact, v in (("exact", 1, -1), ("contracted", 0, 1), ("order-free", 0, 65)):
     s.set_option("exact", exact); s.set_option("flux_variant", v)
     s.bench_flux(0, 500)

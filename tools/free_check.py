@@ -11,7 +11,7 @@ launches = int(sys.argv[2]) if len(sys.argv) > 2 else 500
 mg, levels = bench.build_workload(lattice)
 s = mgcfd.Solver.from_arrays(levels, mg.mesh_variant)
 nel, n_int = s.nel(0), s.num_internal_edges(0)
-print("half rows available:", s.has_half_rows(0))
+print("uniform half-row plan:", s.has_half_rows(0))
 q0 = bench.perturbed_state(nel, s.far_field()[:5])
 out = {}
 for name, exact, v in (("exact", 1, 1), ("contracted", 0, 1), ("free", 0, 64 | 1)):
@@ -30,7 +30,7 @@ res = {}
 s.set(0, "variables", q0)
 s.set_option("exact", 0); s.set_option("flux_variant", 65); s.bench_flux(0, 2000)      # clocks up
 for rnd in range(5):
-    for name, exact, v in (("exact", 1, 1), ("contracted", 0, 1), ("half", 0, 33), ("free", 0, 65)):
+    for name, exact, v in (("exact", 1, 1), ("contracted", 0, 1), ("free", 0, 65)):
         s.set_option("exact", exact); s.set_option("flux_variant", v)
         res.setdefault(name, []).append(s.bench_flux(0, launches))
 for name, ts in res.items():
