@@ -611,7 +611,7 @@ int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double
  *              ss = ((G[u][x]^2 + G[v][y]^2) + G[w][z]^2) + 2.0 * ((sxy^2 + sxz^2) + syz^2),
  *              mut_i = (((cs * cs) * d2_i) * rho_i) * sqrt(2.0 * ss), d2_i = cbrt(vol_i) * cbrt(vol_i) from the host's libm at
  *              enable; written to MGCFD_ARR_EDDY_VISCOSITY[i] by every stress launch (a stage or mgcfd_compute_fluxes).  No wall
- *              damping: near a no-slip wall the model overpredicts mut.
+ *              damping unless mgcfd_set_wall_damping is on: near a no-slip wall the model overpredicts mut.
  *   prandtl_t  the turbulent Prandtl number
  * Pass 1 of the viscous terms then finishes S_i with me_i = mu_i + mut_i on the six stresses and
  * kap_i = (GAMMA / (GAMMA - 1.0)) * (mu_i / prandtl + mut_i / prandtl_t) on the heat flux; S keeps its twelve columns, pass 2
@@ -628,7 +628,8 @@ int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double
  * or not finite; s_ratio (law 1), cs (eddy 2) or prandtl_t (eddy 1, 2) not finite and positive; while a kernel-granular sweep
  * is under way; a non-default model on a solver made by mgcfd_create_partitioned* or attached to a group or as a rank.
  * mgcfd_get_viscosity_model: any pointer may be NULL.
- * Out of scope: wall damping, WALE and dynamic procedures; transported models and wall distance; restriction of an eddy field
+ * The wall-limited length scale of eddy 2 is mgcfd_set_wall_damping's ("Wall distance" below).
+ * Out of scope: WALE and dynamic procedures; transported models; restriction of an eddy field
  * between levels; split levels, groups and ranks; graphs and fused stages with viscosity on. */
 enum { MGCFD_VISCOSITY_CONSTANT = 0, MGCFD_VISCOSITY_SUTHERLAND = 1 };
 enum { MGCFD_EDDY_NONE = 0, MGCFD_EDDY_FIELD = 1, MGCFD_EDDY_SMAGORINSKY = 2 };
@@ -759,6 +760,60 @@ int mgcfd_wall_stress(mgcfd_solver *s, int level, int64_t *node_ids, double *out
 /* Diagnostic: mean GPU time of `launches` back-to-back launches of the wall-stress kernel (kind 0), the twelve-column loads kernel
  * (1) or mgcfd_surface_loads' kernel (2) on a viscous level with solid walls, as mgcfd_bench_viscous times its launches. */
 int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
+ * Wall distance — every node's distance to the nearest solid-wall NODE of its level, the wall spacing and the wall-limited
+ * Smagorinsky length scale.  No reference counterpart.  Off by default: a solver that makes none of these calls launches what
+ * it launched and computes the same bits.  Every operation is one IEEE-754 double operation (+ - * / sqrt, compare), never
+ * contracted to FMA whatever MGCFD_OPT_EXACT says.
+ * With W_0 < W_1 < .. < W_{m-1} the level's wall nodes in ascending original id (the list of mgcfd_wall_node_count and
+ * mgcfd_wall_stress) and x the level's coordinates as given at creation, for every node i:
+ *   best = +inf; near = -1
+ *   for j = 0 .. m-1:   dx = x_i - x_Wj;  dy = y_i - y_Wj;  dz = z_i - z_Wj;  r2 = (dx*dx + dy*dy) + dz*dz
+ *                       if r2 < best: best = r2; near = j
+ *   d_i = sqrt(best);   nearest_i = near < 0 ? -1 : W_near   (an original id)
+ * The strict < gives a tie to the lowest wall id; a NaN r2 is never taken; a level without wall nodes has d = +inf and nearest
+ * = -1 everywhere; a wall node has d = +0.0 and is its own nearest node.  The minimum is exact over all wall nodes: no search
+ * radius, no approximation.  It is the distance to the nearest wall node, not to a wall face: the mesh format has no wall
+ * faces, so d overestimates the face distance by up to the wall's own node spacing.
+ * Wall spacing: for wall node W_k, over its internal incidences in the level's original edge order, h_k = the minimum of d_n
+ * over the other ends n with d_n > 0.0, +0.0 where there is none (what y+ = h * sqrt(rho_w * tau_w) / mu_w needs).
+ * Wall damping of MGCFD_EDDY_SMAGORINSKY (the Mason-Thomson / Smagorinsky-Lilly length-scale limit; there is no exp on the
+ * device, hence not van Driest's exponential):
+ *   a = (cs*cs) * d2_i;  kd = kappa * d_i;  w2 = kd * kd;  l2_i = w2 < a ? w2 : a      (once per node when the setting takes effect)
+ *   mut_i = (l2_i * rho_i) * sqrt(2.0 * ss)
+ * With d_i = +inf this is bit for bit the undamped mut_i; at a wall node mut_i = +0.0.  The wall-stress pass of the friction
+ * loads applies the same expression; the step limit reads MGCFD_ARR_EDDY_VISCOSITY as before; nothing else of the viscosity
+ * model changes.
+ * mgcfd_compute_wall_distance: levels 0 .. levels-1 hold d afterwards (12 bytes per node on the device); levels that hold it are
+ * not recomputed.  The coordinates go to the device for the computation only.  mgcfd_get_wall_distance: how many leading levels
+ * hold it.  mgcfd_release_wall_distance frees it on every level.
+ * MGCFD_ARR_WALL_DISTANCE [nel][1]: read-only through mgcfd_get_array (original numbering) and mgcfd_array_devptr (the layout of
+ * the other one-column arrays); it exists on a level exactly while the level holds the distance, MGCFD_ERR_ARG otherwise.
+ * mgcfd_wall_nearest: nearest [nel] in original numbering, original ids, -1 without a wall.  mgcfd_wall_spacing: node_ids [n]
+ * (may be NULL) and h [n] in the order of mgcfd_wall_stress; both need the level to hold the distance.  Both synchronise.
+ * mgcfd_set_wall_damping: kept like the viscosity model, either call may come first; no effect unless the viscous terms cover a
+ * level and the eddy mode is MGCFD_EDDY_SMAGORINSKY.  Whichever of mgcfd_set_viscous, mgcfd_set_viscosity_model and
+ * mgcfd_set_wall_damping makes it effective on a level that does not hold the distance computes it there; every such setter
+ * synchronises, drops captured graphs and forms l2 again.  mgcfd_get_wall_damping: any pointer may be NULL.
+ * MGCFD_ERR_ARG, and nothing changed: levels outside 1 .. mgcfd_num_levels; a level in range created without coordinates (also
+ * from a setter that would make the damping effective there); kappa not finite and positive; mgcfd_release_wall_distance while
+ * the damping is in effect on some level; while a kernel-granular sweep is under way; a solver made by mgcfd_create_partitioned*
+ * or attached to a group or as a rank (a rank holds part of the wall only); a NULL nearest or h.
+ * Out of scope: the distance to wall faces or a projection onto them; van Driest's exponential; transported models; restricting
+ * d between levels; partitioned levels, groups and ranks; graphs and fused stages with viscosity on.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_ARR_WALL_DISTANCE 16        /* behind the array enum's last entry */
+#define MGCFD_WALL_KAPPA 0.41
+int mgcfd_compute_wall_distance(mgcfd_solver *s, int levels);
+int mgcfd_get_wall_distance(const mgcfd_solver *s, int *levels);
+int mgcfd_release_wall_distance(mgcfd_solver *s);
+int mgcfd_wall_nearest(mgcfd_solver *s, int level, int64_t *nearest);
+int mgcfd_wall_spacing(mgcfd_solver *s, int level, int64_t *node_ids, double *h);
+int mgcfd_set_wall_damping(mgcfd_solver *s, int on, double kappa);
+int mgcfd_get_wall_damping(const mgcfd_solver *s, int *on, double *kappa);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of the wall-distance kernel on a level that holds the distance
+ * (the coordinates are uploaded for the call), as mgcfd_bench_viscous times its launches. */
+int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *avg_seconds);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

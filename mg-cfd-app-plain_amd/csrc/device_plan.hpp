@@ -142,7 +142,8 @@ struct ViscosityModel {
     double cp = 0.0;                          // GAMMA / (GAMMA - 1.0)
     double prandtl = 1.0, prandtl_t = 1.0;
     double *mut = nullptr;                    // eddy_viscosity [stride]
-    const double *d2 = nullptr;               // [stride] cbrt(vol) * cbrt(vol), from the host
+    const double *d2 = nullptr;               // [stride] cbrt(vol) * cbrt(vol), from the host; damped: l2 (k_wall_length) in its place
+    int damped = 0;                           // eddy 2 under wall damping (mgcfd_set_wall_damping): d2 holds l2_i = min(c2 d2_i, (kappa d_i)^2)
     __host__ __device__ bool variable() const { return law != 0 || eddy != 0; }
 };
 
@@ -234,6 +235,30 @@ struct WallNodes {
     const double *int_n = nullptr;        // [entries][3] ... and the normal seen from the wall node: +e at an a end, -e at a b end
     const int32_t *wall_ptr = nullptr;    // [n + 1] a wall node's solid-wall edges ...
     const int32_t *wall_edge = nullptr;   // [records] ... as indices into the level's WallRecord list, ascending
+};
+
+// The wall distance of a level (k_wall_distance; mgcfd_compute_wall_distance): every node's distance to the nearest of the m
+// wall nodes and that wall node's index in the wall list, an exact all-pairs minimum in ascending list order.
+struct WallDistance {
+    const double *x = nullptr;            // [3][stride] the nodes' coordinates in the solver's numbering (pad lanes: finite)
+    const double *wx = nullptr;           // [3][m] the wall nodes' coordinates in list order
+    int32_t m = 0;
+    double *d = nullptr;                  // [stride] pad lanes +inf
+    int32_t *nearest = nullptr;           // [stride] index into the wall list, -1 without a wall and in pad lanes
+};
+
+// The wall spacing (k_wall_spacing): per wall node the smallest positive distance among the other ends of its internal incidences.
+struct WallSpacing {
+    WallNodes wn;
+    const double *d = nullptr;            // [stride] the level's wall distance
+    double *h = nullptr;                  // [wn.n]
+};
+
+// The wall-limited Smagorinsky length scale (k_wall_length): l2_i = min(c2 d2_i, (kappa d_i)^2) per node.
+struct WallLength {
+    const double *d2 = nullptr, *d = nullptr;   // [stride] each
+    double c2 = 0.0, kappa = 0.0;
+    double *l2 = nullptr;                 // [stride]
 };
 
 // The node stresses of the wall nodes alone (k_wall_stress): pass 1 of the viscous terms on the level's current state,

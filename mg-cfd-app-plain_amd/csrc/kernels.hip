@@ -2272,12 +2272,14 @@ __device__ __forceinline__ double viscosity_of(const ViscosityModel &m, double m
     const double r = T / m.t_ref;
     return ((mu * (r * sqrt(r))) * m.one_plus_s) / (r + m.s);
 }
+// (d2: the node's entry of m.d2 — d2_i, or under wall damping l2_i as k_wall_length left it, which stands for c2 * d2_i)
 __device__ __forceinline__ double smagorinsky_of(const ViscosityModel &m, double d2, double rho, double gux, double guy, double guz,
                                                  double gvx, double gvy, double gvz, double gwx, double gwy, double gwz)
 {
     const double sxy = 0.5 * (guy + gvx), sxz = 0.5 * (guz + gwx), syz = 0.5 * (gvz + gwy);
     const double ss = ((gux * gux + gvy * gvy) + gwz * gwz) + 2.0 * ((sxy * sxy + sxz * sxz) + syz * syz);
-    return ((m.c2 * d2) * rho) * sqrt(2.0 * ss);
+    const double l2 = m.damped ? d2 : m.c2 * d2;
+    return (l2 * rho) * sqrt(2.0 * ss);
 }
 
 // VAR: the variable instantiation — after the row walk mu_i by the law, mut_i read (eddy 1) or formed and written (eddy 2; pad
@@ -3001,6 +3003,88 @@ k_wall_stress(int64_t stride, const double *__restrict__ q, WallStress a)
     out[9] = kap * gtx; out[10] = kap * gty; out[11] = kap * gtz;
 #pragma unroll
     for (int f = 0; f < 12; f++) a.sw[f * a.wn.n + k] = out[f];
+}
+
+// ------------------------------------------------------------------------------------------
+// Wall distance (INTEGRATION.md "Wall distance"): every node's distance to the nearest wall NODE of its level, an exact
+// all-pairs minimum — no search radius, no tree.  One lane per node in the solver's numbering, one tile per workgroup; the
+// node's coordinates and the running (best, near) stay in registers.  The wall nodes' coordinates pass through LDS in
+// chunks of kWallChunk, one field per array: every lane of a wave reads the same address, which the LDS serves as a
+// broadcast, at full rate for 8- and 16-byte reads (the walk is unrolled by four so that the loads of a field pair up).
+// r2 = (dx dx + dy dy) + dz dz, one IEEE operation each; the strict < over ascending list positions, within and across
+// chunks, gives a tie to the lowest wall id.  Slots behind the list's end hold NaN: a NaN r2 is never taken, so the walk
+// runs to a multiple of four without a bound per point.  Never contracted to FMA: always taken from the exact build.
+// ------------------------------------------------------------------------------------------
+constexpr int kWallChunk = 256;
+static_assert(kWallChunk == kBlock, "k_wall_distance: every thread stages one wall node of a chunk");
+
+__global__ void __launch_bounds__(kBlock)
+k_wall_distance(uint32_t n_tiles, int64_t stride, int64_t nel, WallDistance a)
+{
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double sx[kWallChunk], sy[kWallChunk], sz[kWallChunk];
+    const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
+    const int tid = threadIdx.x;
+    const int64_t i = int64_t(t) * kBlock + tid;                  // < stride = 256 * n_tiles
+    const double x = a.x[i], y = a.x[stride + i], z = a.x[2 * stride + i];
+    double best = __builtin_inf();
+    int32_t near = -1;
+    for (int32_t c0 = 0; c0 < a.m; c0 += kWallChunk) {
+        const int32_t j = c0 + tid;
+        const bool in = j < a.m;
+        const double wx = in ? a.wx[j] : __builtin_nan(""), wy = in ? a.wx[int64_t(a.m) + j] : __builtin_nan(""),
+                     wz = in ? a.wx[2 * int64_t(a.m) + j] : __builtin_nan("");
+        __syncthreads();                                          // (the chunk before has been walked by every wave)
+        sx[tid] = wx; sy[tid] = wy; sz[tid] = wz;
+        __syncthreads();
+        const int32_t left = a.m - c0;
+        const int32_t n4 = ((left < kWallChunk ? left : kWallChunk) + 3) & ~3;
+        for (int32_t k = 0; k < n4; k += 4) {
+            double r2[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const double dx = x - sx[k + u], dy = y - sy[k + u], dz = z - sz[k + u];
+                r2[u] = (dx * dx + dy * dy) + dz * dz;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (r2[u] < best) { best = r2[u]; near = c0 + k + u; }
+        }
+    }
+    const bool present = i < nel;
+    a.d[i] = present ? sqrt(best) : __builtin_inf();
+    a.nearest[i] = present ? near : -1;
+}
+
+// The wall spacing: for wall node k the smallest d_n > 0.0 over the other ends n of its internal incidences in row order,
+// +0.0 where there is none.
+__global__ void __launch_bounds__(kBlock)
+k_wall_spacing(WallSpacing a)
+{
+    const int64_t k = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (k >= a.wn.n) return;
+    const int32_t e0 = a.wn.int_ptr[k], e1 = a.wn.int_ptr[k + 1];
+    double h = 0.0;
+    bool found = false;
+    for (int32_t e = e0; e < e1; e++) {
+        const double dn = a.d[a.wn.int_nbr[e]];
+        if (dn > 0.0 && (!found || dn < h)) { h = dn; found = true; }
+    }
+    a.h[k] = h;
+}
+
+// The wall-limited length scale of the Smagorinsky model: l2_i = min(c2 d2_i, (kappa d_i)^2), the whole padded length (a pad
+// lane's d is +inf: c2 * 1.0).
+__global__ void __launch_bounds__(kBlock)
+k_wall_length(int64_t stride, WallLength a)
+{
+#pragma clang fp contract(off)
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= stride) return;
+    const double c = a.c2 * a.d2[i];
+    const double kd = a.kappa * a.d[i];
+    const double w2 = kd * kd;
+    a.l2[i] = w2 < c ? w2 : c;
 }
 
 // k_surface_loads with the friction six beside the pressure six: one lane per solid-wall edge, twelve terms, the trees
@@ -3814,6 +3898,13 @@ void launch_surface_loads(hipStream_t st, int64_t stride, const double *q, const
 
 void launch_wall_stress(hipStream_t st, int64_t stride, const double *q, const WallStress &a)
 { if (a.wn.n > 0) hipLaunchKernelGGL(k_wall_stress, dim3(grid_for(a.wn.n)), dim3(kBlock), 0, st, stride, q, a); }
+// (the grid is the level's tiles: stride = 256 * n_tiles)
+void launch_wall_distance(hipStream_t st, int64_t nel, int64_t stride, const WallDistance &a)
+{ hipLaunchKernelGGL(k_wall_distance, dim3(unsigned(stride / kBlock)), dim3(kBlock), 0, st, uint32_t(stride / kBlock), stride, nel, a); }
+void launch_wall_spacing(hipStream_t st, const WallSpacing &a)
+{ if (a.wn.n > 0) hipLaunchKernelGGL(k_wall_spacing, dim3(grid_for(a.wn.n)), dim3(kBlock), 0, st, a); }
+void launch_wall_length(hipStream_t st, int64_t stride, const WallLength &a)
+{ hipLaunchKernelGGL(k_wall_length, dim3(grid_for(stride)), dim3(kBlock), 0, st, stride, a); }
 
 void launch_surface_loads_viscous(hipStream_t st, int64_t stride, const double *q, const LoadsTaskViscous &task)
 {

@@ -71,6 +71,9 @@
                          const double *cbrt_vol, double cfl, double *partial_min, const SumTask &rms);              \
     void launch_surface_loads(hipStream_t, int64_t stride, const double *q, const LoadsTask &task);                  \
     void launch_wall_stress(hipStream_t, int64_t stride, const double *q, const WallStress &a);                      \
+    void launch_wall_distance(hipStream_t, int64_t nel, int64_t stride, const WallDistance &a);                      \
+    void launch_wall_spacing(hipStream_t, const WallSpacing &a);                                                     \
+    void launch_wall_length(hipStream_t, int64_t stride, const WallLength &a);                                       \
     void launch_surface_loads_viscous(hipStream_t, int64_t stride, const double *q, const LoadsTaskViscous &task);   \
     void launch_wall_distribution(hipStream_t, int64_t stride, const double *q, const WallDistribution &a);          \
     void launch_loads_terms(hipStream_t, int64_t stride, const double *q, const LoadsTerms &task);                   \

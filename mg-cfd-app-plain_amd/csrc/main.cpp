@@ -83,6 +83,9 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool model_extras_given = false;                        // --sutherland-tref / --sutherland-s / --prandtl-turbulent
     double sutherland_tref = 0.0, sutherland_s = MGCFD_SUTHERLAND_S, smagorinsky_cs = MGCFD_SMAGORINSKY_CS, prandtl_turbulent = MGCFD_PRANDTL_TURBULENT;
     bool viscosity_model() const { return sutherland || smagorinsky; }
+    // --wall-damping[=KAPPA] / wall_damping = Y | KAPPA: the wall-limited length scale of --smagorinsky (mgcfd_set_wall_damping)
+    bool wall_damping = false;
+    double wall_kappa = MGCFD_WALL_KAPPA;
     bool loads_friction = false;      // --loads-friction: the friction loads beside the pressure loads in surface_loads.* and polar.csv (one GPU)
     bool output_surface = false;      // --output-surface: Cp and Cf per wall node of level 0 into surface.* (one GPU)
     size_t loads_width() const { return loads_friction ? 12 : 6; }
@@ -281,6 +284,11 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         else if (parse_positive(value.c_str(), &c.smagorinsky_cs)) c.smagorinsky = true;
         else if (value != "N") { std::fprintf(stderr, "ERROR: smagorinsky = '%s': expected Y or a finite constant above zero\n", value.c_str()); c.config_bad = true; }
     }
+    else if (key == "wall_damping") {
+        if (value == "Y") c.wall_damping = true;
+        else if (parse_positive(value.c_str(), &c.wall_kappa)) c.wall_damping = true;
+        else if (value != "N") { std::fprintf(stderr, "ERROR: wall_damping = '%s': expected Y or a finite constant above zero\n", value.c_str()); c.config_bad = true; }
+    }
     else if (key == "sutherland_tref" || key == "sutherland_s" || key == "prandtl_turbulent") {
         double *dst = key == "sutherland_tref" ? &c.sutherland_tref : key == "sutherland_s" ? &c.sutherland_s : &c.prandtl_turbulent;
         if (parse_positive(value.c_str(), dst)) c.model_extras_given = true;
@@ -438,6 +446,8 @@ void print_help()
         "  --smagorinsky[=CS]               with the viscous terms: the Smagorinsky eddy viscosity, constant CS (default 0.17), filter width\n"
         "                                   cbrt(volume), no wall damping (config key smagorinsky = Y or CS); one GPU\n"
         "  --prandtl-turbulent=X            the turbulent Prandtl number (default 0.9; config key prandtl_turbulent)\n"
+        "  --wall-damping[=KAPPA]           with --smagorinsky: the length scale min(CS cbrt(volume), KAPPA d), d the distance to the nearest\n"
+        "                                   solid-wall node, KAPPA default 0.41 (config key wall_damping = Y or KAPPA); needs .coords files\n"
         "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
         "                                   (config key physical_time_step): BDF2 in physical time, every step solved in pseudo-time\n"
         "                                   by -g cycles (-g becomes the cycles PER PHYSICAL STEP; an RMS line per cycle as ever,\n"
@@ -511,6 +521,7 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"sutherland-s", required_argument, nullptr, 1042},
         {"prandtl-turbulent", required_argument, nullptr, 1043},
         {"smagorinsky", optional_argument, nullptr, 1044},
+        {"wall-damping", optional_argument, nullptr, 1045},
         {"loads-friction", no_argument, nullptr, 1038},
         {"output-surface", no_argument, nullptr, 1039},
         {nullptr, 0, nullptr, 0}};
@@ -699,6 +710,17 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 c.smagorinsky = true;
                 break;
             }
+            case 1045: {
+                // --wall-damping, --wall-damping=KAPPA or --wall-damping KAPPA, as --smagorinsky takes its constant
+                const char *arg = optarg;
+                if (!arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
+                if (arg && !parse_positive(arg, &c.wall_kappa)) {
+                    std::fprintf(stderr, "ERROR: --wall-damping=%s: expected a finite constant above zero\n", arg);
+                    return false;
+                }
+                c.wall_damping = true;
+                break;
+            }
             case 1039: c.output_surface = true; break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
@@ -721,6 +743,10 @@ bool parse_arguments(int argc, char **argv, Config &c)
     }
     if (c.viscosity_model() && c.gpus > 1) {
         std::fprintf(stderr, "ERROR: the viscosity model (--sutherland, --smagorinsky) runs on one GPU only: not with --gpus N or --gpus-partition\n");
+        return false;
+    }
+    if (c.wall_damping && !c.smagorinsky) {
+        std::fprintf(stderr, "ERROR: --wall-damping needs --smagorinsky (it limits that model's length scale)\n");
         return false;
     }
     if (c.loads_friction && !(c.viscous() && c.viscous_levels > 0 && (c.output_loads || c.polar))) {
@@ -1246,6 +1272,7 @@ int main(int argc, char **argv)
             mgcfd_set_viscosity_model(solver, conf.sutherland ? MGCFD_VISCOSITY_SUTHERLAND : MGCFD_VISCOSITY_CONSTANT, t_ref, conf.sutherland_s,
                                       conf.smagorinsky ? MGCFD_EDDY_SMAGORINSKY : MGCFD_EDDY_NONE, conf.smagorinsky_cs, conf.prandtl_turbulent) != MGCFD_OK)
             return fail("setting the viscosity model");
+        if (conf.wall_damping && mgcfd_set_wall_damping(solver, 1, conf.wall_kappa) != MGCFD_OK) return fail("setting the wall damping");
     }
     if (conf.fas && mgcfd_set_fas(solver, 1) != MGCFD_OK) return fail("switching FAS multigrid on");
     if (conf.cycle_given() && mgcfd_set_cycle(solver, conf.cycle_shape, pre.data(), post.data()) != MGCFD_OK) return fail("setting the multigrid cycle");

@@ -200,6 +200,14 @@ struct DeviceLevel {
     // d2 = cbrt(vol) * cbrt(vol) [stride]
     double *visc_mut = nullptr, *visc_d2 = nullptr;
     int eddy_mode = 0;                   // the model's eddy mode while visc_mut is held (MGCFD_ARR_EDDY_VISCOSITY: who may write it)
+    // the wall distance (mgcfd_compute_wall_distance), held until mgcfd_release_wall_distance: d [stride], the nearest wall
+    // node's index in the wall list [stride] and that list's original ids on the host; the level's coordinates as given at
+    // creation stay on the host (original numbering, empty where the level came without) and visit the device per computation
+    std::vector<double> coords;
+    double *wall_d = nullptr;
+    int32_t *wall_near = nullptr;
+    std::vector<int64_t> wall_ids;
+    double *visc_l2 = nullptr;           // [stride] while the wall damping is in effect on the level: l2 (k_wall_length)
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while ordered_rms(): its RMS is summed in original numbering (settle_rms_order)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
@@ -388,8 +396,14 @@ struct mgcfd_solver {
         m.c2 = vm_cs * vm_cs; m.cp = 1.4 / (1.4 - 1.0);
         m.prandtl = visc_prandtl; m.prandtl_t = vm_prandtl_t;
         m.mut = lv.visc_mut; m.d2 = lv.visc_d2;
+        if (lv.visc_l2) { m.d2 = lv.visc_l2; m.damped = 1; }       // (held exactly while the wall damping is in effect here)
         return m;
     }
+    // The wall damping of the Smagorinsky model (mgcfd_set_wall_damping): kept like the viscosity model; in effect on the levels
+    // the viscous terms cover while the eddy mode is Smagorinsky.
+    int wd_on = 0;
+    double wd_kappa = MGCFD_WALL_KAPPA;
+    bool damping_in_effect() const { return wd_on && vm_eddy == MGCFD_EDDY_SMAGORINSKY && visc_levels > 0; }
     // sf = min(sf, (k0 * rho) * g) on final step factors, before dual time stepping's clamp; under a non-default viscosity
     // model the limit from mu_i and mut_i per node
     void viscous_clamp(int l)
@@ -1167,6 +1181,7 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
         lv.info = d;
         lv.info.volumes = nullptr; lv.info.coords = nullptr; lv.info.edges = nullptr; lv.info.mg_map = nullptr;
         const int64_t nel = d.nel;
+        if (d.coords) lv.coords.assign(d.coords, d.coords + 3 * nel);       // (the wall distance's, should it be asked for)
         const LevelPlan &P = lv.plan;
         const int64_t stride = int64_t(P.n_slices) * kSlice;
         std::vector<double> vol(static_cast<size_t>(stride), 1.0), cb(static_cast<size_t>(stride), 1.0);
@@ -1806,9 +1821,71 @@ int mgcfd_get_jst(const mgcfd_solver *s, double *kappa2, double *kappa4, int *le
     return MGCFD_OK;
 }
 
+// ---- wall distance: the nearest-wall-node field of a level, the wall-limited Smagorinsky length scale ----
+// The level's wall distance where it does not hold one yet (allocations, uploads and a synchronisation: never inside a capture
+// or a cycle).  The coordinates, permuted to the solver's numbering, and the wall nodes' live on the device for the launch only.
+static void compute_level_wall_distance(mgcfd_solver *s, DeviceLevel &lv)
+{
+    if (lv.wall_d) return;
+    if (lv.coords.empty()) throw std::invalid_argument("wall distance: the level was created without coordinates");
+    const int64_t nel = lv.info.nel, stride = lv.dp.stride;
+    if (stride % kTile != 0 || stride < nel) throw std::logic_error("wall distance: the level's stride is not a whole number of tiles");
+    // the wall nodes: the distinct b ends of the solid-wall edges in ascending original id (WallRows::original)
+    std::vector<int64_t> ids;
+    ids.reserve(static_cast<size_t>(lv.info.n_boundary));
+    for (int64_t k = 0; k < lv.info.n_boundary; k++) {
+        const int64_t b = lv.edges[static_cast<size_t>(lv.info.boundary_start + k)].b;
+        if (b < 0 || b >= nel) throw std::invalid_argument("wall distance: a solid-wall edge names a node out of range");
+        ids.push_back(b);
+    }
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const size_t m = ids.size(), st = static_cast<size_t>(stride);
+    std::vector<double> x(3 * st, 0.0), wx(3 * m);
+    for (int64_t n = 0; n < nel; n++) {
+        const size_t o = static_cast<size_t>(lv.plan.old_of_new[static_cast<size_t>(n)]);
+        for (size_t c = 0; c < 3; c++) x[c * st + static_cast<size_t>(n)] = lv.coords[3 * o + c];
+    }
+    for (size_t j = 0; j < m; j++)
+        for (size_t c = 0; c < 3; c++) wx[c * m + j] = lv.coords[3 * static_cast<size_t>(ids[j]) + c];
+    DeviceOwner visiting, kept;                      // (the coordinates go when this returns, d and nearest stay with the level)
+    WallDistance a;
+    a.x = visiting.upload(x); a.wx = visiting.upload(wx); a.m = static_cast<int32_t>(m);
+    a.d = kept.alloc<double>(st); a.nearest = kept.alloc<int32_t>(st);
+    exact::launch_wall_distance(s->stream, nel, stride, a);
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    HIP_CHECK(hipGetLastError());
+    lv.mem.absorb(std::move(kept));
+    lv.wall_d = a.d; lv.wall_near = a.nearest; lv.wall_ids = std::move(ids);
+}
+// A setter about to store (visc_levels, eddy, on) asks first: MGCFD_ERR_ARG with nothing changed where the damping would take
+// effect on a level that neither holds the distance nor came with coordinates.
+static void require_damping_possible(const mgcfd_solver *s, int visc_levels, int eddy, int on)
+{
+    if (!on || eddy != MGCFD_EDDY_SMAGORINSKY) return;
+    for (int l = 0; l < visc_levels && l < static_cast<int>(s->L.size()); l++)
+        if (!s->L[static_cast<size_t>(l)].wall_d && s->L[static_cast<size_t>(l)].coords.empty())
+            throw std::invalid_argument("wall damping: level " + std::to_string(l) + " was created without coordinates (the damping would take effect there)");
+}
+// l2 of a level is held exactly while the wall damping is in effect on it, and formed again by every setter that could have
+// changed cs, kappa or the levels: called once the new state is stored and d2 is settled.
+static void settle_wall_damping(mgcfd_solver *s)
+{
+    for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
+        DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+        if (!s->damping_in_effect() || !s->viscous_on(l)) { lv.mem.release(lv.visc_l2); continue; }
+        compute_level_wall_distance(s, lv);
+        if (!lv.visc_l2) lv.visc_l2 = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.stride));
+        WallLength a;
+        a.d2 = lv.visc_d2; a.d = lv.wall_d; a.c2 = s->vm_cs * s->vm_cs; a.kappa = s->wd_kappa; a.l2 = lv.visc_l2;
+        exact::launch_wall_length(s->stream, lv.dp.stride, a);
+    }
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+}
+
 // The eddy viscosity and d2 of a level are held exactly while the viscous terms cover it and a non-default viscosity model is
 // set: both setters call this once their new state is stored.  A new array holds +0.0; `zero` clears the ones that stay (the
-// eddy mode has changed: the values belonged to the old one).
+// eddy mode has changed: the values belonged to the old one).  The wall damping's l2 follows (settle_wall_damping).
 static void settle_viscosity_arrays(mgcfd_solver *s, bool zero)
 {
     for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
@@ -1834,6 +1911,7 @@ static void settle_viscosity_arrays(mgcfd_solver *s, bool zero)
         lv.visc_d2 = lv.mem.upload(d2);
     }
     HIP_CHECK(hipStreamSynchronize(s->stream));
+    settle_wall_damping(s);
 }
 
 // ---- laminar viscous terms: viscosity, Prandtl number, wall condition, step limit and the levels they run on ----
@@ -1849,6 +1927,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
             if (s->partitioned || s->comm)
                 throw std::invalid_argument("viscous terms: not on a partitioned solver or a rank (a level split over ranks would need the node stresses exchanged per stage)");
         }
+        require_damping_possible(s, levels, s->vm_eddy, s->wd_on);
         quiesce(s, "viscous terms");
         const int n = std::min(levels, static_cast<int>(s->L.size()));
         for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
@@ -1926,6 +2005,7 @@ int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_r
         if (!positive(t_taken)) throw std::invalid_argument("viscosity model: the far field's p / rho is not finite and positive");
         if (variable && (s->partitioned || s->comm))
             throw std::invalid_argument("viscosity model: not on a partitioned solver, a group member or a rank (the viscous terms do not run there)");
+        require_damping_possible(s, s->visc_levels, eddy, s->wd_on);
         quiesce(s, "viscosity model");
         const bool eddy_changed = eddy != s->vm_eddy;
         s->vm_law = law; s->vm_eddy = eddy;
@@ -2806,6 +2886,10 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.visc_mut || !lv.eddy_mode) throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: no eddy viscosity on this level (mgcfd_set_viscosity_model with an eddy mode, on a level mgcfd_set_viscous covers)");
             *ncols = 1;
             return lv.visc_mut;
+        case MGCFD_ARR_WALL_DISTANCE:
+            if (!lv.wall_d) throw std::invalid_argument("MGCFD_ARR_WALL_DISTANCE: the level does not hold the wall distance (mgcfd_compute_wall_distance)");
+            *ncols = 1;
+            return lv.wall_d;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2849,6 +2933,7 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
             throw std::invalid_argument("MGCFD_ARR_VISCOUS_STRESS: read-only (every flux launch of a viscous level overwrites it)");
         if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SMAGORINSKY)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under Smagorinsky (every flux launch of a viscous level overwrites it)");
+        if (which == MGCFD_ARR_WALL_DISTANCE) throw std::invalid_argument("MGCFD_ARR_WALL_DISTANCE: read-only (geometry, from mgcfd_compute_wall_distance)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -2890,6 +2975,7 @@ int mgcfd_array_written(mgcfd_solver *s, int level, int which)
         if (which == MGCFD_ARR_VOLUMES) throw std::invalid_argument("volumes are fixed at creation");
         if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SMAGORINSKY)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under Smagorinsky (every flux launch of a viscous level overwrites it)");
+        if (which == MGCFD_ARR_WALL_DISTANCE) throw std::invalid_argument("MGCFD_ARR_WALL_DISTANCE: read-only (geometry, from mgcfd_compute_wall_distance)");
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
     });
@@ -5414,6 +5500,123 @@ int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launche
             else if (kind == 1) launch_loads_twelve(s, level, s->loads_dev + 3);
             else launch_loads(s, lv, false);
         });
+    });
+}
+
+// ---- wall distance, wall spacing, wall damping (INTEGRATION.md "Wall distance") ----
+// what every call below that computes or frees refuses: a rank holds part of the wall only
+static void wall_distance_require_whole(const mgcfd_solver *s)
+{
+    if (s->partitioned || s->comm)
+        throw std::invalid_argument("wall distance: not on a partitioned solver, a group member or a rank (a rank holds part of the wall only)");
+}
+int mgcfd_compute_wall_distance(mgcfd_solver *s, int levels)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (levels < 1 || levels > static_cast<int>(s->L.size())) throw std::invalid_argument("wall distance: levels must be 1 .. mgcfd_num_levels");
+        wall_distance_require_whole(s);
+        for (int l = 0; l < levels; l++)
+            if (!s->L[static_cast<size_t>(l)].wall_d && s->L[static_cast<size_t>(l)].coords.empty())
+                throw std::invalid_argument("wall distance: level " + std::to_string(l) + " was created without coordinates");
+        require_no_sweep_under_way(s, "wall distance");
+        s->use_device();
+        for (int l = 0; l < levels; l++) compute_level_wall_distance(s, s->L[static_cast<size_t>(l)]);
+    });
+}
+int mgcfd_get_wall_distance(const mgcfd_solver *s, int *levels)
+{
+    REQUIRE(s);
+    int n = 0;
+    while (n < static_cast<int>(s->L.size()) && s->L[static_cast<size_t>(n)].wall_d) n++;
+    if (levels) *levels = n;
+    return MGCFD_OK;
+}
+int mgcfd_release_wall_distance(mgcfd_solver *s)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        wall_distance_require_whole(s);
+        if (s->damping_in_effect()) throw std::invalid_argument("wall distance: the wall damping is in effect (mgcfd_set_wall_damping): switch it off first");
+        require_no_sweep_under_way(s, "wall distance");
+        s->use_device();
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        for (DeviceLevel &lv : s->L) {
+            lv.mem.release(lv.wall_d); lv.mem.release(lv.wall_near);
+            lv.wall_ids.clear(); lv.wall_ids.shrink_to_fit();
+        }
+    });
+}
+int mgcfd_wall_nearest(mgcfd_solver *s, int level, int64_t *nearest)
+{
+    REQUIRE(s); REQUIRE(nearest);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!lv.wall_d) throw std::invalid_argument("mgcfd_wall_nearest: the level does not hold the wall distance (mgcfd_compute_wall_distance)");
+        std::vector<int32_t> near(static_cast<size_t>(lv.dp.stride));
+        HIP_CHECK(hipMemcpyAsync(near.data(), lv.wall_near, sizeof(int32_t) * near.size(), hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        for (int64_t n = 0; n < lv.info.nel; n++) {
+            const int32_t j = near[static_cast<size_t>(n)];
+            nearest[lv.plan.old_of_new[static_cast<size_t>(n)]] = j < 0 ? -1 : lv.wall_ids[static_cast<size_t>(j)];
+        }
+    });
+}
+int mgcfd_wall_spacing(mgcfd_solver *s, int level, int64_t *node_ids, double *h)
+{
+    REQUIRE(s); REQUIRE(h);
+    return guarded([&] {
+        if (!s->level(level).wall_d) throw std::invalid_argument("mgcfd_wall_spacing: the level does not hold the wall distance (mgcfd_compute_wall_distance)");
+        // (the plan's distribution table is free between calls: its first column block takes h)
+        wall_table(s, level, node_ids, h, 1, [&](DeviceLevel &lv, WallPlan &wp) {
+            WallSpacing a;
+            a.wn = wp.wn; a.d = lv.wall_d; a.h = wp.dist;
+            exact::launch_wall_spacing(s->stream, a);
+            return wp.dist;
+        });
+    });
+}
+int mgcfd_set_wall_damping(mgcfd_solver *s, int on, double kappa)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (on != 0 && on != 1) throw std::invalid_argument("wall damping: on must be 0 or 1");
+        if (!std::isfinite(kappa) || !(kappa > 0.0)) throw std::invalid_argument("wall damping: kappa must be finite and positive");
+        if (on) wall_distance_require_whole(s);
+        require_damping_possible(s, s->visc_levels, s->vm_eddy, on);
+        quiesce(s, "wall damping");
+        s->wd_on = on; s->wd_kappa = kappa;
+        settle_wall_damping(s);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_wall_damping(const mgcfd_solver *s, int *on, double *kappa)
+{
+    REQUIRE(s);
+    if (on) *on = s->wd_on;
+    if (kappa) *kappa = s->wd_kappa;
+    return MGCFD_OK;
+}
+int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!lv.wall_d) throw std::invalid_argument("mgcfd_bench_wall_distance: the level does not hold the wall distance (mgcfd_compute_wall_distance)");
+        const size_t st = static_cast<size_t>(lv.dp.stride), m = lv.wall_ids.size();
+        std::vector<double> x(3 * st, 0.0), wx(3 * m);
+        for (int64_t n = 0; n < lv.info.nel; n++)
+            for (size_t c = 0; c < 3; c++) x[c * st + static_cast<size_t>(n)] = lv.coords[3 * static_cast<size_t>(lv.plan.old_of_new[static_cast<size_t>(n)]) + c];
+        for (size_t j = 0; j < m; j++)
+            for (size_t c = 0; c < 3; c++) wx[c * m + j] = lv.coords[3 * static_cast<size_t>(lv.wall_ids[j]) + c];
+        DeviceOwner visiting;
+        WallDistance a;
+        a.x = visiting.upload(x); a.wx = visiting.upload(wx); a.m = static_cast<int32_t>(m);
+        a.d = lv.wall_d; a.nearest = lv.wall_near;             // (the launches write what the arrays hold)
+        *avg_seconds = s->timed_launches(launches, [&] { exact::launch_wall_distance(s->stream, lv.info.nel, lv.dp.stride, a); });
+        HIP_CHECK(hipStreamSynchronize(s->stream));
     });
 }
 

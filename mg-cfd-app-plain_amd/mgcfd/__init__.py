@@ -6,4 +6,4 @@
 from . import meshgen  # noqa: F401
 from .api import (EXPORTED_SYMBOLS, LIB_PATH, LOOPS, Group, MgcfdError, Mesh, Solver,  # noqa: F401
                   free_stream_constants, generated_to_levels, live_device_resources, load_coefficients, load_library, plan_audit,
-                  rccl_unique_id, surface_coefficients, viscosity_from_reynolds)
+                  rccl_unique_id, surface_coefficients, viscosity_from_reynolds, wall_yplus)

@@ -25,8 +25,8 @@ RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
-       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15}
-NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1}      # (every other array: NVAR)
+       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16}
+NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1}    # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -213,6 +213,14 @@ _SIGNATURES = [
     ("mgcfd_wall_distribution", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_wall_stress", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_bench_friction_loads", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_compute_wall_distance", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_get_wall_distance", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("mgcfd_release_wall_distance", C.c_int, [_vp]),
+    ("mgcfd_wall_nearest", C.c_int, [_vp, C.c_int, _vp]),
+    ("mgcfd_wall_spacing", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_set_wall_damping", C.c_int, [_vp, C.c_int, C.c_double]),
+    ("mgcfd_get_wall_damping", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("mgcfd_bench_wall_distance", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_cycle", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_get_cycle", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_run_cycles_from", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -393,6 +401,23 @@ def surface_coefficients(ff17, table):
         n = a / area[:, None]
         cf = (t - (t * n).sum(axis=1)[:, None] * n) / (area * q)[:, None]
     return dp / q, cf
+
+
+WALL_KAPPA = 0.41     # MGCFD_WALL_KAPPA
+
+
+def wall_yplus(table, h, rho_w, mu_w):
+    """Host only: ``y+ [n]`` of the first node off the wall from a surface distribution ``table [n, 7]``
+    (Solver.wall_distribution), the wall spacing ``h [n]`` (Solver.wall_spacing) and the wall's density and viscosity (scalars or
+    ``[n]``): ``tau = |t - (t.n) n| / |a|`` with ``n = a / |a|`` and ``y+ = h * sqrt(rho_w * tau) / mu_w``."""
+    tab = np.asarray(table, dtype=np.float64).reshape(-1, WALL_COLUMNS)
+    a, t = tab[:, 0:3], tab[:, 4:7]
+    area = np.sqrt((a * a).sum(axis=1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = a / area[:, None]
+        tt = t - (t * n).sum(axis=1)[:, None] * n
+        tau = np.sqrt((tt * tt).sum(axis=1)) / area
+        return np.asarray(h, dtype=np.float64) * np.sqrt(np.asarray(rho_w, dtype=np.float64) * tau) / np.asarray(mu_w, dtype=np.float64)
 
 
 def free_stream_constants(mach: float, alpha_deg: float) -> np.ndarray:
@@ -634,6 +659,55 @@ class Solver:
         self._c(self.lib.mgcfd_wall_stress(self.handle, level, _ptr(ids), _ptr(out)))
         return ids[:n], out[:n]
 
+    # ---- wall distance ----
+    def compute_wall_distance(self, levels: Optional[int] = None):
+        """Levels ``0 .. levels-1`` (None: all) hold the wall distance afterwards (mgcfd_compute_wall_distance): per node the exact
+        distance to the nearest wall node of its level, readable as the ``"wall_distance"`` array.  Levels that hold it are not
+        computed again.  Needs the levels' coordinates; not on partitioned solvers, group members or ranks."""
+        self._c(self.lib.mgcfd_compute_wall_distance(self.handle, self.num_levels if levels is None else int(levels)))
+
+    def wall_distance_levels(self) -> int:
+        """How many leading levels hold the wall distance (mgcfd_get_wall_distance)."""
+        n = C.c_int()
+        self._c(self.lib.mgcfd_get_wall_distance(self.handle, C.byref(n)))
+        return n.value
+
+    def release_wall_distance(self):
+        """Frees the wall distance on every level (mgcfd_release_wall_distance); refused while the wall damping is in effect."""
+        self._c(self.lib.mgcfd_release_wall_distance(self.handle))
+
+    def wall_nearest(self, l: int) -> np.ndarray:
+        """``[nel]`` original ids of every node's nearest wall node, the lowest id on a tie, -1 without a wall (mgcfd_wall_nearest)."""
+        out = np.zeros(max(self.nel(l), 1), dtype=np.int64)
+        self._c(self.lib.mgcfd_wall_nearest(self.handle, l, _ptr(out)))
+        return out[:self.nel(l)]
+
+    def wall_spacing(self, l: int):
+        """``(ids [n], h [n])``: per wall node, in ``wall_stress``'s order, the smallest positive wall distance among its edge
+        neighbours, +0.0 where there is none (mgcfd_wall_spacing).  ``wall_yplus`` turns it into y+."""
+        n = self.wall_node_count(l)
+        ids, h = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1))
+        self._c(self.lib.mgcfd_wall_spacing(self.handle, l, _ptr(ids), _ptr(h)))
+        return ids[:n], h[:n]
+
+    def set_wall_damping(self, on: bool = True, kappa: float = WALL_KAPPA):
+        """Wall damping of the Smagorinsky model (mgcfd_set_wall_damping): the length scale becomes ``min(cs * delta, kappa * d)``
+        with ``d`` the wall distance, so ``mut`` is +0.0 on the wall.  Kept like the viscosity model; in effect on the levels
+        ``set_viscous`` covers while ``eddy="smagorinsky"``; the setter that makes it effective computes a missing distance."""
+        self._c(self.lib.mgcfd_set_wall_damping(self.handle, int(bool(on)), float(kappa)))
+
+    def wall_damping(self):
+        """``(on, kappa)`` (mgcfd_get_wall_damping)."""
+        on, k = C.c_int(), C.c_double()
+        self._c(self.lib.mgcfd_get_wall_damping(self.handle, C.byref(on), C.byref(k)))
+        return bool(on.value), k.value
+
+    def bench_wall_distance(self, l: int, launches: int) -> float:
+        """Mean GPU seconds of one wall-distance launch on level ``l``, which must hold the distance (mgcfd_bench_wall_distance)."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_wall_distance(self.handle, l, launches, C.byref(t)))
+        return t.value
+
     def load_coefficients(self, loads, ref_area: float = 1.0, ref_length: float = 1.0) -> np.ndarray:
         """CD CL CS CMx CMy CMz of one loads vector, or of every row of a ``[n, 6]`` history, against this solver's far field."""
         return load_coefficients(self.far_field(), loads, ref_area, ref_length)
@@ -845,7 +919,7 @@ class Solver:
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
-              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None) -> List[dict]:
+              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None, wall_damping=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
@@ -855,7 +929,10 @@ class Solver:
         (``set_residual_smoothing``), ``jst=(kappa2, kappa4, levels)`` (``set_jst``), ``fas=True / False`` (``set_fas``) and
         ``viscous=(mu, prandtl, wall, cfl_v, levels)`` or a dict of ``set_viscous``'s keywords (``set_viscous``) and
         ``viscosity_model=(law, t_ref, s, eddy, cs, prandtl_t)`` or a dict of ``set_viscosity_model``'s keywords; a ``t_ref`` of
-        None is then the far field's of the solver as the call finds it."""
+        None is then the far field's of the solver as the call finds it; ``wall_damping=(on, kappa)`` or a dict of
+        ``set_wall_damping``'s keywords likewise (``set_wall_damping``)."""
+        if wall_damping is not None:
+            self.set_wall_damping(**wall_damping) if isinstance(wall_damping, dict) else self.set_wall_damping(*wall_damping)
         if viscosity_model is not None:
             self.set_viscosity_model(**viscosity_model) if isinstance(viscosity_model, dict) else self.set_viscosity_model(*viscosity_model)
         if viscous is not None:
