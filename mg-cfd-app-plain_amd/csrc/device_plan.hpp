@@ -25,7 +25,7 @@ struct FarField {
     double fc_mx[3], fc_my[3], fc_mz[3], fc_de[3];
 };
 
-// Where a halo "push" stores (kernels.hip: k_halo_push): the state buffers of up to kMaxPushPeers neighbouring ranks
+// Where a halo "push" stores (kernels_plain.hip: k_halo_push): the state buffers of up to kMaxPushPeers neighbouring ranks
 // (peer access over xGMI, or the same device), the peers' segments of the message being consecutive slot ranges.
 constexpr int kMaxPushPeers = 8;
 struct PushPeers {
@@ -35,7 +35,7 @@ struct PushPeers {
     int n = 0;
 };
 
-// The flags a push raises in its peers once its stores are on their way (ranks in different processes: kernels.hip,
+// The flags a push raises in its peers once its stores are on their way (ranks in different processes: kernels_plain.hip,
 // k_halo_push with flags, k_flags_wait): flag[p] = the word in peer p's memory, value = this message's sequence number.
 struct PushFlags {
     unsigned long long *flag[kMaxPushPeers] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

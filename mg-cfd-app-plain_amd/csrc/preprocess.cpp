@@ -356,7 +356,7 @@ void build_level_plan(const mgcfd_level_desc &L, const std::vector<mgcfd_edge> &
     else { order.resize(static_cast<size_t>(nel)); std::iota(order.begin(), order.end(), 0); }
     // ---- dispatch order of the tiles ----
     // A launch deals its workgroups to the XCDs round-robin and gives every XCD one contiguous range of tiles
-    // (kernels.hip: xcd_contiguous_block), so within a range the tiles start in index order.  A level of more tiles than
+    // (kernel_device.hpp: xcd_contiguous_block), so within a range the tiles start in index order.  A level of more tiles than
     // the chip holds workgroups (768 of the bit-identical kernel: three per CU) runs in 1.15-1.5 rounds, and what starts
     // last decides when the launch ends.  So the cheapest tiles of every range — as many as do not fit the first round —
     // go to its end, the costliest of them first; every other tile keeps its place (neighbours in space stay neighbours in

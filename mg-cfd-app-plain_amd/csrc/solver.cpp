@@ -307,7 +307,7 @@ struct mgcfd_solver {
     int opt_rank_split = 1;
     bool opt_lazy_residual = !(std::getenv("MGCFD_LAZY_RESIDUAL") && std::atoi(std::getenv("MGCFD_LAZY_RESIDUAL")) == 0);
     // check_for_invalid_variables: every checked launch carries its sequence number since the host last read the
-    // error word, so the EARLIEST failing time_step wins, as in the reference (kernels.hip: err_key)
+    // error word, so the EARLIEST failing time_step wins, as in the reference (kernel_device.hpp: err_key)
     int check_seq = 0;
     int64_t invalid_cell = -1; int invalid_cycle = -1;                     // where the last reported invalid state was found
     int next_check() { if (!opt_check) return 0; if (check_seq < (1 << 22)) check_seq++; return check_seq; }
@@ -413,18 +413,18 @@ struct mgcfd_solver {
             ViscousClamp a;
             a.q = lv.q; a.g = lv.visc_g; a.step_factors = lv.step_factors;
             a.mu = visc_mu; a.cfl_v = visc_cfl; a.model = viscosity_model(lv);
-            exact::launch_viscous_clamp_variable(stream, lv.info.nel, lv.dp.stride, a);
+            launch_viscous_clamp_variable(stream, lv.info.nel, lv.dp.stride, a);
             return;
         }
         const double kv = std::max(4.0 / 3.0, 1.4 / visc_prandtl);
-        exact::launch_viscous_clamp(stream, lv.info.nel, visc_cfl / (kv * visc_mu), lv.q, lv.visc_g, lv.step_factors);
+        launch_viscous_clamp(stream, lv.info.nel, visc_cfl / (kv * visc_mu), lv.q, lv.visc_g, lv.step_factors);
     }
     // the no-slip wall behind a launch that wrote q (and q2: FAS's copy of it); residuals where that launch wrote them
     void viscous_wall(int l, double *q, double *q2 = nullptr, const double *old = nullptr, double *residuals = nullptr)
     {
         if (!viscous_on(l) || !visc_wall) return;
         DeviceLevel &lv = level(l);
-        exact::launch_viscous_wall(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, q, q2, old, residuals);
+        launch_viscous_wall(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, q, q2, old, residuals);
     }
     // FAS multigrid (mgcfd_set_fas): the V-cycle's transfers become the FAS legs (op_fas_restrict, op_fas_prolong) and every stage
     // of a level >= 1 takes R + P for its total residual R.  Such a level runs unfused stages (standalone flux launch + the
@@ -491,13 +491,13 @@ struct mgcfd_solver {
     void use_device() const { HIP_CHECK(hipSetDevice(device)); }
     const Launchers &k() const                                  // the kernels of this solver's numeric flavour
     {
-#define MGCFD_LAUNCHERS_OF(NS) {NS::launch_step_factor_local, NS::launch_step_factor_apply, NS::launch_step_factor_legacy, NS::launch_flux, \
-                                NS::launch_indirect_rw, NS::launch_time_step, NS::launch_residual, NS::launch_sumsq, NS::launch_restrict, NS::launch_prolong, \
-                                NS::launch_step_factor_nodal, NS::launch_smooth, NS::launch_time_step_src, NS::launch_dual_source, \
-                                NS::launch_jst_sensor, NS::launch_jst_dissipation, NS::launch_restrict_fas, NS::launch_prolong_fas, \
-                                NS::launch_viscous_stress, NS::launch_viscous_flux, NS::launch_prolong_state}
-        static constexpr Launchers kExact MGCFD_LAUNCHERS_OF(exact), kFast MGCFD_LAUNCHERS_OF(fast);
-#undef MGCFD_LAUNCHERS_OF
+        // (one table per flavour from the one list of kernels.hpp, every entry set by its member's name)
+#define MGCFD_EXACT_ENTRY(member, launcher, params) t.member = exact::launcher;
+#define MGCFD_FAST_ENTRY(member, launcher, params) t.member = fast::launcher;
+        static constexpr Launchers kExact = [] { Launchers t{}; MGCFD_FLAVOURED_LAUNCHERS(MGCFD_EXACT_ENTRY) return t; }();
+        static constexpr Launchers kFast = [] { Launchers t{}; MGCFD_FLAVOURED_LAUNCHERS(MGCFD_FAST_ENTRY) return t; }();
+#undef MGCFD_EXACT_ENTRY
+#undef MGCFD_FAST_ENTRY
         return opt_exact ? kExact : kFast;
     }
     DeviceLevel &level(int l)
@@ -586,7 +586,7 @@ struct mgcfd_solver {
         if (fuse_copy_old) settle_residuals(lv);
         double *old = fuse_copy_old ? lv.old_variables : nullptr;
         k().step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, cfl, lv.step_factors, lv.partial_min, old);
-        if (reduce_to_scalar) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
+        if (reduce_to_scalar) launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
     }
     void op_step_factor_apply(int l)
     {
@@ -640,7 +640,7 @@ struct mgcfd_solver {
     void clamp_step_factors(int l)
     {
         DeviceLevel &lv = level(l);
-        exact::launch_dual_clamp(stream, lv.info.nel, dual_clamp * dual_dt, lv.volumes, lv.step_factors);
+        launch_dual_clamp(stream, lv.info.nel, dual_clamp * dual_dt, lv.volumes, lv.step_factors);
     }
     // The parts of a level's plan that only a non-default option reaches are uploaded when an option first asks for them
     // (at creation: nothing but the 32-bit neighbour codes of levels whose indirect_rw probe runs the L1-gather form).  Called
@@ -812,13 +812,13 @@ struct mgcfd_solver {
         if (smoothing()) {
             // the smoothing works on final step factors: finish compute_step_factor first (the same division k_time_step would do)
             // (booked where k_time_step's own division is booked: under time_step)
-            if (apply_min == ApplyMin::Partials) exact::launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
+            if (apply_min == ApplyMin::Partials) launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
             if (apply_min != ApplyMin::None) op_step_factor_apply(l);
             // dual time stepping: F' = F - src into fluxes[] first, in a node-wise launch of its own — the first iteration forms
             // D = sf * F' for halo nodes too, which would read three more states per staged node inside k_smooth_tile
             if (dual_time()) k().dual_source(stream, lv.info.nel, lv.dp.stride, lv.fluxes, dual_source(lv));
             // FAS: the forcing is the last addition, F' = (F - src) + P, node-wise as the source
-            if (fas_forced(l)) exact::launch_fas_add_forcing(stream, lv.dp.stride, lv.fluxes, lv.fas_p);
+            if (fas_forced(l)) launch_fas_add_forcing(stream, lv.dp.stride, lv.fluxes, lv.fas_p);
             SmoothStep a;
             a.fluxes = lv.fluxes; a.step_factors = lv.step_factors; a.eps = irs_eps;
             for (int m = 0; m < irs_iters; m++) {
@@ -873,8 +873,8 @@ struct mgcfd_solver {
         DeviceLevel &l0 = level(l);
         if (!l0.new_of_old_dev) throw std::logic_error("the ordered RMS sum without the level's numbering on the device");
         settle_residuals(l0);
-        exact::launch_sumsq_original(stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
-        exact::launch_sum_partials_append(stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq, ring, count, cap);
+        launch_sumsq_original(stream, l0.info.nel, l0.dp.stride, l0.residuals, l0.new_of_old_dev, l0.tile_sumsq);
+        launch_sum_partials_append(stream, static_cast<int>((l0.info.nel + 255) / 256), l0.tile_sumsq, l0.sumsq, ring, count, cap);
     }
     // rms (may be null): per-tile sums of squares of the fine level that the launch adds up on the side (cycle_once)
     void op_restrict(int fine, const SumTask *rms = nullptr)
@@ -949,7 +949,7 @@ struct mgcfd_solver {
         op_total_residual(fine + 1);                            // R(W0): variables[fine + 1] is W0 now
         {
             Timed t(this, fine + 1, MGCFD_LOOP_FLUX);
-            exact::launch_fas_forcing(stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p);
+            launch_fas_forcing(stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p);
         }
         C.fluxes_zero = true; C.fluxes_stale = true;
     }
@@ -1366,8 +1366,8 @@ static std::unique_ptr<mgcfd_solver> build_solver(const mgcfd_level_desc *levels
         HIP_CHECK(hipMemsetAsync(lv.residuals, 0, sizeof(double) * 5 * stride, s->stream));
         HIP_CHECK(hipMemsetAsync(lv.step_factors, 0, sizeof(double) * stride, s->stream));
         HIP_CHECK(hipMemsetAsync(lv.sf_alt, 0, sizeof(double) * stride, s->stream));
-        exact::launch_init_variables(s->stream, stride, s->ff, lv.q);
-        exact::launch_init_variables(s->stream, stride, s->ff, lv.q_alt);     // valid numbers in the padded tail
+        launch_init_variables(s->stream, stride, s->ff, lv.q);
+        launch_init_variables(s->stream, stride, s->ff, lv.q_alt);     // valid numbers in the padded tail
     });
     s->use_device();
     HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -1703,8 +1703,8 @@ static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mac
     if (!reinitialise) return;                  // warm start: the state stays
     for (DeviceLevel &lv : s->L) {
         s->settle_residuals(lv);                // (residuals[] keeps what the last sweep left: its operands are about to change)
-        exact::launch_init_variables(s->stream, lv.dp.stride, s->ff, lv.q);
-        exact::launch_init_variables(s->stream, lv.dp.stride, s->ff, lv.q_alt);     // valid numbers in the padded tail
+        launch_init_variables(s->stream, lv.dp.stride, s->ff, lv.q);
+        launch_init_variables(s->stream, lv.dp.stride, s->ff, lv.q_alt);     // valid numbers in the padded tail
         lv.min_ahead = false;
         lv.have_sumsq = false;
         lv.stage_out = nullptr;                 // (MGCFD_ARR_STAGE named a stage of the state that has just gone)
@@ -1852,7 +1852,7 @@ static void compute_level_wall_distance(mgcfd_solver *s, DeviceLevel &lv)
     WallDistance a;
     a.x = visiting.upload(x); a.wx = visiting.upload(wx); a.m = static_cast<int32_t>(m);
     a.d = kept.alloc<double>(st); a.nearest = kept.alloc<int32_t>(st);
-    exact::launch_wall_distance(s->stream, nel, stride, a);
+    launch_wall_distance(s->stream, nel, stride, a);
     HIP_CHECK(hipStreamSynchronize(s->stream));
     HIP_CHECK(hipGetLastError());
     lv.mem.absorb(std::move(kept));
@@ -1878,7 +1878,7 @@ static void settle_wall_damping(mgcfd_solver *s)
         if (!lv.visc_l2) lv.visc_l2 = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.stride));
         WallLength a;
         a.d2 = lv.visc_d2; a.d = lv.wall_d; a.c2 = s->vm_cs * s->vm_cs; a.kappa = s->wd_kappa; a.l2 = lv.visc_l2;
-        exact::launch_wall_length(s->stream, lv.dp.stride, a);
+        launch_wall_length(s->stream, lv.dp.stride, a);
     }
     HIP_CHECK(hipStreamSynchronize(s->stream));
 }
@@ -2137,7 +2137,7 @@ int mgcfd_check_for_invalid_variables(mgcfd_solver *s, int level, int64_t *bad_c
     int rc = guarded([&] {
         s->use_device();
         DeviceLevel &lv = s->level(level);
-        exact::launch_check_invalid(s->stream, lv.info.nel, lv.dp.stride, lv.q, lv.dp.old_of_new, s->err);
+        launch_check_invalid(s->stream, lv.info.nel, lv.dp.stride, lv.q, lv.dp.old_of_new, s->err);
         code = s->read_error(bad_cell);
     });
     if (rc != MGCFD_OK) return rc;
@@ -2160,7 +2160,7 @@ int mgcfd_pending_invalid_state(mgcfd_solver *s, int64_t *bad_cell)
 static ApplyMin first_stage_min(mgcfd_solver *s, DeviceLevel &lv)
 {
     if (lv.plan.n_tiles <= 2048) return ApplyMin::Partials;
-    exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
+    launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
     return ApplyMin::Scalar;
 }
 
@@ -2328,7 +2328,7 @@ static int sweep_begin_impl(mgcfd_solver *s, int level, bool scalar)
         } else {
             s->op_step_factor(level, true, false);
         }
-        if (global_dt && scalar) exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
+        if (global_dt && scalar) launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, lv.min_dt);
     });
 }
 int mgcfd_sweep_flux0(mgcfd_solver *s, int level)
@@ -2434,7 +2434,7 @@ static void launch_loads(mgcfd_solver *s, DeviceLevel &lv, bool to_ring)
     t.partial = lv.loads_partial; t.ticket = lv.loads_ticket;
     if (to_ring) { t.ring = s->loads_ring; t.count = s->rms_count; t.cap = mgcfd_solver::kRmsRing; }
     else t.out = s->loads_dev + 3;
-    exact::launch_surface_loads(s->stream, lv.dp.stride, lv.q, t);
+    launch_surface_loads(s->stream, lv.dp.stride, lv.q, t);
 }
 
 // The wall plan of a level (allocations and uploads: never inside a capture or a cycle).
@@ -2468,7 +2468,7 @@ static void launch_wall_stress(mgcfd_solver *s, int l)
     a.wn = lv.wp->wn; a.volumes = lv.volumes; a.sw = lv.wp->sw;
     a.mu = s->visc_mu; a.kappa = (s->visc_mu * 1.4) / ((1.4 - 1.0) * s->visc_prandtl);
     a.model = s->viscosity_model(lv);
-    exact::launch_wall_stress(s->stream, lv.dp.stride, lv.q, a);
+    launch_wall_stress(s->stream, lv.dp.stride, lv.q, a);
 }
 
 // Level l's pressure and friction loads of its current `variables` (the level has a plan), as launch_loads: twelve sums
@@ -2484,7 +2484,7 @@ static void launch_loads_twelve(mgcfd_solver *s, int l, double *out)
     if (!out) { t.base.ring = s->loads_ring12; t.base.count = s->rms_count; t.base.cap = mgcfd_solver::kRmsRing; }
     else t.base.out = out;
     t.wall_of_rec = lv.wp->wall_of_rec; t.sw = viscous ? lv.wp->sw : nullptr; t.nw = lv.wp->wn.n;
-    exact::launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t);
+    launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t);
 }
 static void launch_loads_viscous(mgcfd_solver *s, int l, double *out)
 {
@@ -2579,13 +2579,13 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
                 rms_pending = true;
             } else if (lt.have_sumsq) {
                 // ... single level: one small launch does
-                exact::launch_sum_partials_append(s->stream, static_cast<int>((lt.info.nel + 255) / 256), lt.tile_sumsq, lt.sumsq,
+                launch_sum_partials_append(s->stream, static_cast<int>((lt.info.nel + 255) / 256), lt.tile_sumsq, lt.sumsq,
                                                   s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else if (s->ordered_rms()) {
                 s->op_sumsq_ordered(s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             } else {
                 s->op_sumsq(0);
-                exact::launch_append_scalar(s->stream, lt.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+                launch_append_scalar(s->stream, lt.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             }
         }
         if (l == n - 1) return;
@@ -2989,7 +2989,7 @@ int mgcfd_accept_restricted(mgcfd_solver *s, int fine_level, const void *dev_src
         DeviceLevel &fine = s->level(fine_level);
         DeviceLevel &coarse = s->level(fine_level + 1);
         if (!fine.dp.child_ptr) throw std::invalid_argument("level has no coarser level");
-        exact::launch_accept_restricted(s->stream, coarse.info.nel, coarse.dp.stride, fine.dp.child_ptr,
+        launch_accept_restricted(s->stream, coarse.info.nel, coarse.dp.stride, fine.dp.child_ptr,
                                         static_cast<const double *>(dev_src), coarse.q);
         s->viscous_wall(fine_level + 1, coarse.q);
         coarse.min_ahead = false;
@@ -3033,8 +3033,8 @@ static void halo_move(mgcfd_solver *s, int level, int plan, int which, void *dev
     if (which == MGCFD_ARR_VARIABLES && !pack) lv.min_ahead = false;
     const auto &hp = lv.halo_plans[static_cast<size_t>(plan)];
     if (hp.second > 0 && !dev_buf) throw std::invalid_argument("null message buffer");
-    if (pack) exact::launch_halo_pack(s->stream, hp.second, lv.dp.stride, hp.first, field, static_cast<double *>(dev_buf));
-    else exact::launch_halo_unpack(s->stream, hp.second, lv.dp.stride, hp.first, static_cast<const double *>(dev_buf), field);
+    if (pack) launch_halo_pack(s->stream, hp.second, lv.dp.stride, hp.first, field, static_cast<double *>(dev_buf));
+    else launch_halo_unpack(s->stream, hp.second, lv.dp.stride, hp.first, static_cast<const double *>(dev_buf), field);
 }
 int mgcfd_halo_pack(mgcfd_solver *s, int level, int plan, int which, void *dev_buf)
 { REQUIRE(s); return guarded([&] { halo_move(s, level, plan, which, dev_buf, true); }); }
@@ -3221,7 +3221,7 @@ int mgcfd_bench_fas(mgcfd_solver *s, int fine_level, int kind, int launches, dou
             switch (kind) {
                 case 0: s->k().restrict_fas(s->stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
                                             fine_level >= 1 ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p); break;
-                case 1: exact::launch_fas_forcing(s->stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p); break;
+                case 1: launch_fas_forcing(s->stream, C.info.nel, C.dp.stride, F.dp.child_ptr, C.fluxes, C.fas_p); break;
                 case 2: s->k().time_step_src(s->stream, C.info.nel, C.dp.stride, 0, C.step_factors, C.fluxes, C.fas_p, C.q, C.q_alt, C.dp.old_of_new,
                                              s->err, 0, nullptr, none); break;
                 case 3: s->k().prolong_fas(s->stream, F.dp, C.dp.stride, C.fas_w0, C.q, F.q, F.cbrt_vol, s->cfl, nullptr); break;
@@ -3258,7 +3258,7 @@ int mgcfd_bench_indirect_rw(mgcfd_solver *s, int level, int launches, double *av
 
 // The practical ceiling of that launch's data movement: a tile-shaped stream of exactly the bytes SURVEY.md §8d prices
 // (40 B per internal edge + 40 B per node read from a scratch buffer of that size, 40 B per node written into `fluxes`), one
-// workgroup per tile of the level, nothing dependent and nothing computed (kernels.hip: k_stream_tiles).
+// workgroup per tile of the level, nothing dependent and nothing computed (kernels_plain.hip: k_stream_tiles).
 int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double *avg_seconds)
 {
     REQUIRE(s); REQUIRE(avg_seconds);
@@ -3270,7 +3270,7 @@ int mgcfd_bench_stream_ceiling(mgcfd_solver *s, int level, int launches, double 
         DeviceOwner scratch;
         double *src = scratch.alloc<double>(static_cast<size_t>(rd_total) + 512);
         HIP_CHECK(hipMemsetAsync(src, 0, (static_cast<size_t>(rd_total) + 512) * sizeof(double), s->stream));
-        auto go = [&] { exact::launch_stream_tiles(s->stream, lv.dp.n_tiles, src, lv.fluxes, rd_total, wr_total); };
+        auto go = [&] { launch_stream_tiles(s->stream, lv.dp.n_tiles, src, lv.fluxes, rd_total, wr_total); };
         go();
         *avg_seconds = s->timed_launches(launches, go);
         lv.fluxes_zero = false;
@@ -3484,7 +3484,7 @@ static void halo_start(mgcfd_solver *s, int level, const double *field, int b)
     HaloExchange &hx = *lv.hx;
     mgcfd_comm &c = comm_of(s);
     if (hx.total_send() > 0)
-        exact::launch_halo_pack(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, field, hx.send_buf[b]);
+        launch_halo_pack(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, field, hx.send_buf[b]);
     HIP_CHECK(hipEventRecord(hx.packed[b].get(), s->stream));
     if (c.rccl) {
         HIP_CHECK(hipStreamWaitEvent(hx.comm_stream.get(), hx.packed[b].get(), 0));
@@ -3546,7 +3546,7 @@ static void halo_finish(mgcfd_solver *s, int level, double *field, int b)
     HaloExchange &hx = *lv.hx;
     HIP_CHECK(hipStreamWaitEvent(s->stream, hx.arrived[b].get(), 0));
     if (hx.total_recv() > 0)
-        exact::launch_halo_unpack(s->stream, hx.total_recv(), lv.dp.stride, hx.recv_idx, hx.recv_buf[b], field);
+        launch_halo_unpack(s->stream, hx.total_recv(), lv.dp.stride, hx.recv_idx, hx.recv_buf[b], field);
 }
 
 // (MGCFD_PART_LOOK_AHEAD=0: the last stage of a partitioned sweep does not compute the next sweep's step-factor minima —
@@ -3621,7 +3621,7 @@ static void sweep_first_half(mgcfd_solver *s, int level, double *min_out = nullp
     const bool global_dt = s->global_dt();
     if (global_dt && lv.min_ahead) lv.iters[MGCFD_LOOP_COMPUTE_STEP] += lv.info.nel;      // the previous sweep's last stage looked ahead
     else s->op_step_factor(level, true, false);             // first half of compute_step_factor (a ghost's factor is its owner's business)
-    if (global_dt) exact::launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, min_out ? min_out : lv.min_dt);
+    if (global_dt) launch_min_reduce(s->stream, lv.info.nel, lv.partial_min, min_out ? min_out : lv.min_dt);
 }
 
 // one sweep of an RCCL rank, as issued (and as captured): every exchange it starts it also finishes
@@ -3739,7 +3739,7 @@ static void push_and_record(mgcfd_solver *s, int level, const double *field, con
 {
     DeviceLevel &lv = s->level(level);
     HaloExchange &hx = *lv.hx;
-    if (hx.total_send() > 0) exact::launch_halo_push(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, hx.push_target, field, pp);
+    if (hx.total_send() > 0) launch_halo_push(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, hx.push_target, field, pp);
     HIP_CHECK(hipEventRecord(hx.bdone[ev].get(), s->stream));
 }
 
@@ -3825,7 +3825,7 @@ static void group_sweeps_threaded(mgcfd_group *g, int level, int sweeps, bool wi
             step([&] {
                 if (global_dt) {
                     for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced.get(), 0));
-                    exact::launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
+                    launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
                 }
                 // the peers' buffers of this sweep's three stages, read while nobody rotates (a rank rotates in its last stage's
                 // second part, two barriers from here; its previous rotation lies before the barrier just passed)
@@ -3840,7 +3840,7 @@ static void group_sweeps_threaded(mgcfd_group *g, int level, int sweeps, bool wi
             }
             if (with_rms) step([&] {
                 exact::launch_sumsq(s->stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
-                exact::launch_append_scalar(s->stream, lv.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+                launch_append_scalar(s->stream, lv.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
             });
         }
         step([&] { wait_for_peers(g, s, level, 2); HIP_CHECK(hipGetLastError()); });
@@ -3868,7 +3868,7 @@ static void group_sweep_once(mgcfd_group *g, int level)
             dst->use_device();
             HaloExchange &hd = *dst->level(level).hx;
             for (mgcfd_solver *src : g->ranks) if (src != dst) HIP_CHECK(hipStreamWaitEvent(dst->stream, src->level(level).hx->reduced.get(), 0));
-            exact::launch_min_over_peers(dst->stream, hd.peer_scalars[par], n, hd.gmin);
+            launch_min_over_peers(dst->stream, hd.peer_scalars[par], n, hd.gmin);
         }
     }
     const bool direct = g->ranks[0]->level(level).hx->direct;
@@ -3938,7 +3938,7 @@ static void ipc_wait(mgcfd_solver *s, HaloExchange &hx, int slot)
     FlagRows rows;
     rows.n = static_cast<int>(hx.peer.size());
     for (int k = 0; k < rows.n; k++) rows.row[k] = hx.peer[static_cast<size_t>(k)];       // (a rank's row is its rank)
-    exact::launch_flags_wait(s->stream, hx.flags, rows, slot, hx.seq, hx.ipc_timeouts);
+    launch_flags_wait(s->stream, hx.flags, rows, slot, hx.seq, hx.ipc_timeouts);
 }
 
 // all-reduce(MIN) of lv.min_dt over every rank through the flags: the minima end up in hx.gmins[parity][0..world)
@@ -3957,8 +3957,8 @@ static const double *ipc_allreduce_min(mgcfd_solver *s, DeviceLevel &lv)
         mp.flag[r] = hx.all_flag[r];
         if (r != c.rank) rows.row[rows.n++] = r;
     }
-    exact::launch_min_publish(s->stream, lv.min_dt, mp);
-    exact::launch_flags_wait(s->stream, hx.flags, rows, 3, hx.sweep_seq, hx.ipc_timeouts);
+    launch_min_publish(s->stream, lv.min_dt, mp);
+    launch_flags_wait(s->stream, hx.flags, rows, 3, hx.sweep_seq, hx.ipc_timeouts);
     return hx.gmins + mp.parity * kMaxIpcRanks;
 }
 
@@ -3979,7 +3979,7 @@ static void ipc_push(mgcfd_solver *s, DeviceLevel &lv, const double *field, int 
     pp.first[pp.n] = hx.total_send();
     hx.seq++;
     pf.value = hx.seq;
-    exact::launch_halo_push_flags(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, hx.push_target, field, pp, pf, hx.ticket);
+    launch_halo_push_flags(s->stream, hx.total_send(), lv.dp.stride, hx.send_idx, hx.push_target, field, pp, pf, hx.ticket);
 }
 
 static void rank_sweep_once_ipc(mgcfd_solver *s, int level)
@@ -4532,7 +4532,7 @@ static int group_sweeps_impl(mgcfd_group *g, int level, int sweeps, double *rms_
                             s->use_device();
                             DeviceLevel &lv = s->level(level);
                             exact::launch_sumsq(s->stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
-                            exact::launch_append_scalar(s->stream, lv.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+                            launch_append_scalar(s->stream, lv.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
                         }
                 }
                 for (mgcfd_solver *s : g->ranks) { s->use_device(); wait_for_peers(g, s, level, 2); }
@@ -4747,7 +4747,7 @@ static void loads_reduce(mgcfd_solver *s0, RankLoads &r0, bool to_ring)
     t.n = r0.total; t.partial = r0.partial; t.ticket = r0.ticket;
     if (to_ring) { t.ring = s0->loads_ring; t.count = s0->rms_count; t.cap = mgcfd_solver::kRmsRing; }
     else t.out = s0->loads_dev + 3;
-    exact::launch_loads_reduce(s0->stream, r0.table, r0.row, t);
+    launch_loads_reduce(s0->stream, r0.table, r0.row, t);
 }
 
 // In-process groups.  Before the first launch, once per set of slots: every rank of the level has slots, all name the same
@@ -4799,7 +4799,7 @@ static void group_loads_terms(mgcfd_group *g, mgcfd_solver *s, int level)
     if (r0.total == 0) return;
     DeviceLevel &lv = s->level(level);
     if (s != s0) HIP_CHECK(hipStreamWaitEvent(s->stream, r0.read.get(), 0));      // (rank 0's own stream is behind its reduce anyway)
-    exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, lv.rl->slot, r0.table, r0.row));
+    launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, lv.rl->slot, r0.table, r0.row));
     HIP_CHECK(hipEventRecord(lv.rl->terms.get(), s->stream));
 }
 
@@ -4825,7 +4825,7 @@ static void append_level0_sumsq(mgcfd_solver *s)
 {
     DeviceLevel &lv = s->level(0);
     exact::launch_sumsq(s->stream, lv.info.nel, lv.dp.stride, lv.residuals, lv.partials, lv.n_partials, lv.sumsq, lv.dp.old_of_new, lv.n_owned);
-    exact::launch_append_scalar(s->stream, lv.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
+    launch_append_scalar(s->stream, lv.sumsq, s->rms_ring, s->rms_count, mgcfd_solver::kRmsRing);
 }
 
 // one V-cycle of every rank of an in-process group (one host thread issues it)
@@ -4890,7 +4890,7 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms, boo
             step([&] {
                 if (global_dt) {
                     for (mgcfd_solver *src : g->ranks) if (src != s) HIP_CHECK(hipStreamWaitEvent(s->stream, src->level(level).hx->reduced.get(), 0));
-                    exact::launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
+                    launch_min_over_peers(s->stream, hx.peer_scalars[par], n, hx.gmin);
                 }
                 for (int j = 0; j < MGCFD_RK; j++) to[j] = make_push_peers(g, s, level, [&](DeviceLevel &pl) { return stage_buffers(pl, j).out; });
             });
@@ -5161,13 +5161,13 @@ static void rank_loads_once(mgcfd_solver *s, int level, bool to_ring)
     if (rl.total == 0) return;
     if (c.rank != 0) {
         if (lv.n_wall_rec == 0) return;
-        exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, nullptr, rl.compact, lv.n_wall_rec));
+        launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, nullptr, rl.compact, lv.n_wall_rec));
         RCCL_CHECK(g_rccl.GroupStart());
         RCCL_CHECK(g_rccl.Send(rl.compact, static_cast<size_t>(6 * lv.n_wall_rec), Rccl::kDouble, 0, c.rccl, s->stream));
         RCCL_CHECK(g_rccl.GroupEnd());
         return;
     }
-    exact::launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, rl.slot, rl.table, rl.row));
+    launch_loads_terms(s->stream, lv.dp.stride, lv.q, loads_terms_of(s, lv, rl.slot, rl.table, rl.row));
     if (c.world > 1) {
         RCCL_CHECK(g_rccl.GroupStart());
         int64_t off = 0;
@@ -5179,7 +5179,7 @@ static void rank_loads_once(mgcfd_solver *s, int level, bool to_ring)
         RCCL_CHECK(g_rccl.GroupEnd());
         off = 0;
         for (size_t r = 1; r < rl.counts.size(); r++) {
-            exact::launch_loads_scatter(s->stream, rl.counts[r], rl.compact + 6 * off, rl.counts[r], rl.peer_slot[r], rl.table, rl.row);
+            launch_loads_scatter(s->stream, rl.counts[r], rl.compact + 6 * off, rl.counts[r], rl.peer_slot[r], rl.table, rl.row);
             off += rl.counts[r];
         }
     }
@@ -5461,7 +5461,7 @@ int mgcfd_wall_distribution(mgcfd_solver *s, int level, int64_t *node_ids, doubl
             if (viscous) launch_wall_stress(s, level);
             WallDistribution a;
             a.wn = wp.wn; a.rec = lv.wall_rec; a.p_inf = s->p_inf; a.sw = viscous ? wp.sw : nullptr; a.out = wp.dist;
-            exact::launch_wall_distribution(s->stream, lv.dp.stride, lv.q, a);
+            launch_wall_distribution(s->stream, lv.dp.stride, lv.q, a);
             return wp.dist;
         });
     });
@@ -5572,7 +5572,7 @@ int mgcfd_wall_spacing(mgcfd_solver *s, int level, int64_t *node_ids, double *h)
         wall_table(s, level, node_ids, h, 1, [&](DeviceLevel &lv, WallPlan &wp) {
             WallSpacing a;
             a.wn = wp.wn; a.d = lv.wall_d; a.h = wp.dist;
-            exact::launch_wall_spacing(s->stream, a);
+            launch_wall_spacing(s->stream, a);
             return wp.dist;
         });
     });
@@ -5615,7 +5615,7 @@ int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *
         WallDistance a;
         a.x = visiting.upload(x); a.wx = visiting.upload(wx); a.m = static_cast<int32_t>(m);
         a.d = lv.wall_d; a.nearest = lv.wall_near;             // (the launches write what the arrays hold)
-        *avg_seconds = s->timed_launches(launches, [&] { exact::launch_wall_distance(s->stream, lv.info.nel, lv.dp.stride, a); });
+        *avg_seconds = s->timed_launches(launches, [&] { launch_wall_distance(s->stream, lv.info.nel, lv.dp.stride, a); });
         HIP_CHECK(hipStreamSynchronize(s->stream));
     });
 }
@@ -5666,7 +5666,7 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
                 if (!lv.time_n) lv.time_n = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
                 if (!lv.time_n1) lv.time_n1 = lv.mem.alloc<double>(static_cast<size_t>(5 * lv.dp.stride));
             }
-            for (DeviceLevel &lv : s->L) exact::launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, 1);
+            for (DeviceLevel &lv : s->L) launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, 1);
             HIP_CHECK(hipStreamSynchronize(s->stream));
             HIP_CHECK(hipGetLastError());
             s->dual_levels = 0;
@@ -5717,7 +5717,7 @@ static void dual_begin_step(mgcfd_solver *s)
     require_dual_time(s, "mgcfd_dual_time_begin_step");
     require_no_sweep_under_way(s, "dual time");
     for (DeviceLevel &lv : s->L)
-        exact::launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, s->dual_levels == 0 ? 1 : 0);
+        launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, s->dual_levels == 0 ? 1 : 0);
     s->dual_levels = s->dual_levels == 0 ? 1 : 2;
 }
 int mgcfd_dual_time_begin_step(mgcfd_solver *s) { OP(dual_begin_step(s)); }

@@ -43,6 +43,52 @@ def test_hip_kernels_are_in_the_library(mgcfd_mod):
     assert b"gfx950" in blob and b"k_flux_tile" in blob
 
 
+# The launchers that exist once (kernels_plain.hip); every other launcher is in kernels.hpp's MGCFD_FLAVOURED_LAUNCHERS.
+PLAIN_LAUNCHERS = """init_variables min_reduce stream_tiles viscous_clamp viscous_clamp_variable viscous_wall dual_clamp dual_shift
+check_invalid halo_pack halo_unpack halo_push halo_push_flags flags_wait min_publish append_scalar sumsq_original min_over_peers
+accept_restricted sum_partials_append surface_loads wall_stress wall_distance wall_spacing wall_length surface_loads_viscous
+wall_distribution loads_terms loads_scatter loads_reduce fas_forcing fas_add_forcing""".split()
+
+
+def test_single_flavour_kernels_exist_once_and_flavoured_launchers_twice(mgcfd_mod):
+    """A launcher has two flavours exactly if kernels.hpp's one list names it: the library holds it in mgcfd::exact and in
+    mgcfd::fast.  Every other launcher, and every kernel of kernels_plain.hip, exists once, in mgcfd, and under neither
+    flavour's namespace — in the symbol tables and anywhere else in the file (the device code objects' names)."""
+    csrc = os.path.join(ROOT, "mg-cfd-app-plain_amd", "csrc")
+    hpp = open(os.path.join(csrc, "kernels.hpp")).read()
+    # the one list: the lines of the macro's definition, each entry MGCFD_L(X, name, ...) or X(member, launch_name, ...)
+    body = re.search(r"#define MGCFD_FLAVOURED_LAUNCHERS\(X\)(.*?)\n\n", hpp, re.S).group(1)
+    flavoured = ["launch_" + n for n in re.findall(r"\bMGCFD_L\(X,\s*(\w+)\s*,", body)] + re.findall(r"\bX\(\w+,\s*(launch_\w+)\s*,", body)
+    assert len(flavoured) == 21 and len(set(flavoured)) == 21
+    plain = re.findall(r"^void (launch_\w+)\(", hpp.split("// The launchers of kernels_plain.hip.")[1], re.M)
+    assert sorted(plain) == sorted("launch_" + n for n in PLAIN_LAUNCHERS) and len(plain) == 32
+    assert not set(plain) & set(flavoured)
+    plain_kernels = re.findall(r"^(?:__global__ void )?(k_\w+)\(", open(os.path.join(csrc, "kernels_plain.hip")).read(), re.M)
+    assert len(plain_kernels) == 32 and len(set(plain_kernels)) == 32
+    assert not re.findall(r"^k_\w+\(", hpp, re.M)
+
+    syms = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-W", "--symbols", mgcfd_mod.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    # (Num: Value Size Type Bind Vis Ndx Name; the symbol table alone, so that a name counts once)
+    rows = [line.split() for line in syms.split("Symbol table '.symtab'")[1].splitlines()]
+    defined = [r[7] for r in rows if len(r) == 8 and r[0].endswith(":") and r[6] != "UND" and r[3] in ("FUNC", "OBJECT")]
+    assert len(defined) > 500
+    blob = open(mgcfd_mod.LIB_PATH, "rb").read()
+    item = lambda name: f"{len(name)}{name}"            # the Itanium ABI's length-prefixed source name
+    # (a) nothing under a flavour's namespace carries a plain name: launcher, kernel or the kernel's host stub
+    for name in plain + plain_kernels + ["__device_stub__" + k for k in plain_kernels]:
+        for ns in ("N5mgcfd4fast", "N5mgcfd5exact"):
+            needle = ns + item(name)
+            assert not [s for s in defined if needle in s], f"{needle} is a symbol of the library"
+            assert needle.encode() not in blob, f"{needle} occurs in the library"
+    # (b) each plain launcher is defined exactly once, in mgcfd
+    for name in plain:
+        assert len([s for s in defined if s.startswith("_ZN5mgcfd" + item(name) + "E")]) == 1, name
+    # (c) each listed launcher is defined in both flavours
+    for name in flavoured:
+        for ns in ("5exact", "4fast"):
+            assert len([s for s in defined if s.startswith("_ZN5mgcfd" + ns + item(name) + "E")]) == 1, (ns, name)
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_reader_matches_reference(mgcfd_mod, case):
     d = os.path.join(GOLDEN, case)

@@ -11,7 +11,7 @@ if not rows:
     sys.exit(f"no *kernel_trace.csv under {sys.argv[1]}")
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 def short(n):
-    n = n.replace("void ", "").replace("mgcfd::exact::", "").replace("mgcfd::fast::", "")
+    n = n.replace("void ", "").replace("mgcfd::exact::", "").replace("mgcfd::fast::", "").replace("mgcfd::", "")   # (kernels_plain.hip's: mgcfd:: alone)
     return n.split("(")[0][:60]
 # the last 40 % of the launches: steady cycles
 rows = rows[int(len(rows) * 0.6):]
