@@ -629,7 +629,7 @@ int mgcfd_viscosity_from_reynolds(const double ff17[17], double reynolds, double
  * is under way; a non-default model on a solver made by mgcfd_create_partitioned* or attached to a group or as a rank.
  * mgcfd_get_viscosity_model: any pointer may be NULL.
  * The wall-limited length scale of eddy 2 is mgcfd_set_wall_damping's ("Wall distance" below).
- * Out of scope: WALE and dynamic procedures; transported models; restriction of an eddy field
+ * Out of scope: WALE and dynamic procedures; transported models (the Spalart-Allmaras model below is one); restriction of an eddy field
  * between levels; split levels, groups and ranks; graphs and fused stages with viscosity on. */
 enum { MGCFD_VISCOSITY_CONSTANT = 0, MGCFD_VISCOSITY_SUTHERLAND = 1 };
 enum { MGCFD_EDDY_NONE = 0, MGCFD_EDDY_FIELD = 1, MGCFD_EDDY_SMAGORINSKY = 2 };
@@ -799,7 +799,7 @@ int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launche
  * from a setter that would make the damping effective there); kappa not finite and positive; mgcfd_release_wall_distance while
  * the damping is in effect on some level; while a kernel-granular sweep is under way; a solver made by mgcfd_create_partitioned*
  * or attached to a group or as a rank (a rank holds part of the wall only); a NULL nearest or h.
- * Out of scope: the distance to wall faces or a projection onto them; van Driest's exponential; transported models; restricting
+ * Out of scope: the distance to wall faces or a projection onto them; van Driest's exponential; transported models (the Spalart-Allmaras model below is one); restricting
  * d between levels; partitioned levels, groups and ranks; graphs and fused stages with viscosity on.
  * --------------------------------------------------------------------------------- */
 #define MGCFD_ARR_WALL_DISTANCE 16        /* behind the array enum's last entry */
@@ -814,6 +814,46 @@ int mgcfd_get_wall_damping(const mgcfd_solver *s, int *on, double *kappa);
 /* Diagnostic: mean GPU time of `launches` back-to-back launches of the wall-distance kernel on a level that holds the distance
  * (the coordinates are uploaded for the call), as mgcfd_bench_viscous times its launches. */
 int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
+ * Spalart-Allmaras model: a transported eddy viscosity.  No reference counterpart; INTEGRATION.md "Spalart-Allmaras model"
+ * holds the definition, line by line (the noft2 form with the 2012 limiter of S~; every operation one IEEE-754 double
+ * operation, never contracted whatever MGCFD_OPT_EXACT says).  Selected as the eddy mode MGCFD_EDDY_SPALART_ALLMARAS of
+ * mgcfd_set_viscosity_model (cs is ignored, prandtl_t is used); off by default, and a solver that never selects it launches and
+ * computes what it did.  nu_tilde (nt) is a sixth transported quantity beside the state, on the levels mgcfd_set_viscous covers:
+ *   level 0         pass 1 (k_sa_gradient_tile) behind the flux launch and the JST pair, before the stress launch: G of
+ *                   (u, v, w, nt), the vorticity magnitude, nu_i and mut_i = (rho_i nt_i) fv1 into MGCFD_ARR_EDDY_VISCOSITY, which
+ *                   the stress launch, the wall-stress pass and the step limit read as under MGCFD_EDDY_FIELD;
+ *                   pass 2 (k_sa_transport_tile) before the stage's update of the five variables: upwind convection, diffusion on
+ *                   averaged node gradients, production, destruction (point-implicit), nt_out = max(nt_old + dn, +0.0), +0.0
+ *                   where d == 0.0.  mgcfd_compute_fluxes runs pass 1; mgcfd_time_step on level 0 runs pass 2 first.
+ *   covered l >= 1  behind every restriction into the level (k_sa_restrict): nt averaged over the children as the state is, mut
+ *                   from it and the restricted state; frozen until the next restriction.  Nothing of nt is prolonged.
+ * The nt update is not smoothed (residual smoothing) and has no FAS forcing; JST, FAS, residual smoothing and the cycle control
+ * compose with the model otherwise.  The wall distance is needed on every covered level: whichever setter makes the mode
+ * effective on a level that does not hold it computes it there, and mgcfd_release_wall_distance is refused meanwhile.
+ * At enable, and on mgcfd_set_free_stream(.., reinitialise = 1): nt = (ratio * mu) / rho_inf on every node of every covered
+ * level, +0.0 where d == 0.0, and mut formed from it.  mgcfd_set_sa_free_stream sets ratio (MGCFD_SA_RATIO by default; kept
+ * while the mode is off) and with reinitialise != 0 applies it at once.
+ * MGCFD_ARR_SA_NU_TILDE [nel][1]: readable and writable on covered levels (mgcfd_set_array, mgcfd_array_devptr +
+ * mgcfd_array_written; a write on level 0 is a restart).  MGCFD_ARR_SA_GRADIENT [nel][5] = G[nt][x] G[nt][y] G[nt][z] | om | nu of
+ * the last pass 1: read-only, level 0.  MGCFD_ARR_EDDY_VISCOSITY is read-only under the mode.
+ * MGCFD_ERR_ARG, and nothing changed: ratio not finite and positive; the mode requested while dual time stepping is on, and dual
+ * time stepping requested while the mode is on (nt has no BDF source); a level the mode would take effect on created without
+ * coordinates; a solver made by mgcfd_create_partitioned* or attached to a group or as a rank; while a kernel-granular sweep is
+ * under way.
+ * Out of scope: SA-neg, ft2, trip terms, rotation corrections, DES lengths; transport on coarse levels; nt under dual time, in
+ * the residual smoothing or the FAS forcing; far-field nt flux; an edge-direction correction of the face gradient.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_EDDY_SPALART_ALLMARAS 4         /* (3 is left unassigned: mgcfd_set_viscosity_model has always refused it, and callers rely on that) */
+#define MGCFD_ARR_SA_NU_TILDE 17
+#define MGCFD_ARR_SA_GRADIENT 18
+#define MGCFD_SA_RATIO 3.0
+int mgcfd_set_sa_free_stream(mgcfd_solver *s, double ratio, int reinitialise);
+int mgcfd_get_sa_free_stream(const mgcfd_solver *s, double *ratio);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of one of the model's kernels (kind 0: pass 1, 1: pass 2 into
+ * the spare buffer, so nt stays, 2: k_sa_restrict into level `level` from the level below it), as mgcfd_bench_viscous times
+ * its launches.  MGCFD_ERR_ARG where the model is not in effect. */
+int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

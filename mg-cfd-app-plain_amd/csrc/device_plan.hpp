@@ -167,6 +167,28 @@ struct ViscousClamp {
     ViscosityModel model;
 };
 
+// The Spalart-Allmaras model (kernels_sa.hip: k_sa_gradient_tile, k_sa_transport_tile, k_sa_restrict; eddy mode
+// MGCFD_EDDY_SPALART_ALLMARAS): pass 1 writes grad and mut from w and nt; pass 2 reads w, nt, grad and writes nt_out.
+struct SaStep {
+    const double *w = nullptr;                // the stage's input state W [5][stride]: what the fluxes were computed from
+    const double *nt = nullptr;               // [stride] nu_tilde at the stage's input
+    double *grad = nullptr;                   // sa_gradient [5][stride]: G[nt][x] G[nt][y] G[nt][z] | om | nu
+    double *mut = nullptr;                    // eddy_viscosity [stride] (pass 1 and the restriction write it)
+    const double *volumes = nullptr;          // [stride]
+    double mu = 0.0;
+    ViscosityModel model;                     // the law alone is read (viscosity_of)
+    double cv1_3 = 0.0;                       // (cv1 * cv1) * cv1, formed on the host like the four below
+    // pass 2
+    const double *nt_old = nullptr;           // [stride] nu_tilde at the sweep's start
+    double *nt_out = nullptr;                 // [stride] the stage's result (never nt itself: other tiles still stage it)
+    const double *d = nullptr;                // [stride] the wall distance
+    const double *g = nullptr;                // [stride] cbrt(vol)^2 / vol
+    const double *step_factors = nullptr;     // [stride] the sweep's final factors
+    double cw1 = 0.0, c6 = 0.0, inv_sigma = 0.0, ks = 0.0;
+    double cfl_v = 0.0;
+    double rk_div = 1.0;                      // double(RK+1-j)
+};
+
 // The physical-time source of dual time stepping (kernels.hip: k_time_step_src, k_dual_source; mgcfd_set_dual_time):
 //   src = vol * ((3 (W - Wn) - (Wn - Wn1)) / (2 dt))   order 2 (BDF2);   src = vol * ((W - Wn) / dt)   order 1 (BDF1, Wn1 not read)
 struct DualSource {

@@ -36,6 +36,9 @@ namespace {
 
 constexpr double kGamma = 1.4;                // src/Base/const.h:9
 constexpr int kBlock = 256;
+// doubles per LDS field of the node-gather tile kernels (k_smooth_tile and every kernel on its walk): one field per array
+constexpr int kSmoothRow = 560;
+static_assert(kSmoothRow >= kTileCap, "every staged slot has a place");
 
 // ---- per-node derived state -------------------------------------------------------------
 // cfd_loops.h:121-148.  Same expressions, same association as the reference.

@@ -1740,9 +1740,6 @@ k_dual_source(int64_t nel, int64_t stride, double *__restrict__ fluxes, DualSour
 // the same pair).  44-56 registers, no scratch; seven workgroups per CU by LDS (the launch bound asks for six at least):
 // nothing here waits on arithmetic, so the loads in flight are what matters.
 // ------------------------------------------------------------------------------------------
-constexpr int kSmoothRow = 560;
-static_assert(kSmoothRow >= kTileCap, "every staged slot has a place");
-
 template <bool FIRST, bool LAST, bool TAIL>
 __global__ void __launch_bounds__(kBlock, 6)
 k_smooth_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,

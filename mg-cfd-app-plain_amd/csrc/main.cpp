@@ -82,7 +82,11 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool sutherland = false, smagorinsky = false;
     bool model_extras_given = false;                        // --sutherland-tref / --sutherland-s / --prandtl-turbulent
     double sutherland_tref = 0.0, sutherland_s = MGCFD_SUTHERLAND_S, smagorinsky_cs = MGCFD_SMAGORINSKY_CS, prandtl_turbulent = MGCFD_PRANDTL_TURBULENT;
-    bool viscosity_model() const { return sutherland || smagorinsky; }
+    bool viscosity_model() const { return sutherland || smagorinsky || spalart_allmaras; }
+    // --spalart-allmaras[=RATIO] / spalart_allmaras = Y | RATIO: the transported eddy viscosity (MGCFD_EDDY_SPALART_ALLMARAS),
+    // RATIO the free-stream nu_tilde over nu (mgcfd_set_sa_free_stream)
+    bool spalart_allmaras = false;
+    double sa_ratio = MGCFD_SA_RATIO;
     // --wall-damping[=KAPPA] / wall_damping = Y | KAPPA: the wall-limited length scale of --smagorinsky (mgcfd_set_wall_damping)
     bool wall_damping = false;
     double wall_kappa = MGCFD_WALL_KAPPA;
@@ -284,6 +288,11 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         else if (parse_positive(value.c_str(), &c.smagorinsky_cs)) c.smagorinsky = true;
         else if (value != "N") { std::fprintf(stderr, "ERROR: smagorinsky = '%s': expected Y or a finite constant above zero\n", value.c_str()); c.config_bad = true; }
     }
+    else if (key == "spalart_allmaras") {
+        if (value == "Y") c.spalart_allmaras = true;
+        else if (parse_positive(value.c_str(), &c.sa_ratio)) c.spalart_allmaras = true;
+        else if (value != "N") { std::fprintf(stderr, "ERROR: spalart_allmaras = '%s': expected Y or a finite ratio above zero\n", value.c_str()); c.config_bad = true; }
+    }
     else if (key == "wall_damping") {
         if (value == "Y") c.wall_damping = true;
         else if (parse_positive(value.c_str(), &c.wall_kappa)) c.wall_damping = true;
@@ -446,6 +455,9 @@ void print_help()
         "  --smagorinsky[=CS]               with the viscous terms: the Smagorinsky eddy viscosity, constant CS (default 0.17), filter width\n"
         "                                   cbrt(volume), no wall damping (config key smagorinsky = Y or CS); one GPU\n"
         "  --prandtl-turbulent=X            the turbulent Prandtl number (default 0.9; config key prandtl_turbulent)\n"
+        "  --spalart-allmaras[=RATIO]       with the viscous terms: the Spalart-Allmaras model (noft2), nu_tilde transported on level 0 and\n"
+        "                                   restricted to the coarser viscous levels; RATIO = free-stream nu_tilde / nu, default 3 (config key\n"
+        "                                   spalart_allmaras = Y or RATIO); needs .coords files; one GPU; not with --smagorinsky or --physical-time-step\n"
         "  --wall-damping[=KAPPA]           with --smagorinsky: the length scale min(CS cbrt(volume), KAPPA d), d the distance to the nearest\n"
         "                                   solid-wall node, KAPPA default 0.41 (config key wall_damping = Y or KAPPA); needs .coords files\n"
         "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
@@ -522,6 +534,7 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"prandtl-turbulent", required_argument, nullptr, 1043},
         {"smagorinsky", optional_argument, nullptr, 1044},
         {"wall-damping", optional_argument, nullptr, 1045},
+        {"spalart-allmaras", optional_argument, nullptr, 1046},
         {"loads-friction", no_argument, nullptr, 1038},
         {"output-surface", no_argument, nullptr, 1039},
         {nullptr, 0, nullptr, 0}};
@@ -721,6 +734,17 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 c.wall_damping = true;
                 break;
             }
+            case 1046: {
+                // --spalart-allmaras, --spalart-allmaras=RATIO or --spalart-allmaras RATIO, as --smagorinsky takes its constant
+                const char *arg = optarg;
+                if (!arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
+                if (arg && !parse_positive(arg, &c.sa_ratio)) {
+                    std::fprintf(stderr, "ERROR: --spalart-allmaras=%s: expected a finite ratio above zero\n", arg);
+                    return false;
+                }
+                c.spalart_allmaras = true;
+                break;
+            }
             case 1039: c.output_surface = true; break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
@@ -743,6 +767,14 @@ bool parse_arguments(int argc, char **argv, Config &c)
     }
     if (c.viscosity_model() && c.gpus > 1) {
         std::fprintf(stderr, "ERROR: the viscosity model (--sutherland, --smagorinsky) runs on one GPU only: not with --gpus N or --gpus-partition\n");
+        return false;
+    }
+    if (c.spalart_allmaras && c.smagorinsky) {
+        std::fprintf(stderr, "ERROR: --spalart-allmaras and --smagorinsky are two eddy-viscosity models: give one of them\n");
+        return false;
+    }
+    if (c.spalart_allmaras && c.dual_given) {
+        std::fprintf(stderr, "ERROR: --spalart-allmaras does not run with --physical-time-step (nu_tilde has no physical-time source)\n");
         return false;
     }
     if (c.wall_damping && !c.smagorinsky) {
@@ -1268,9 +1300,11 @@ int main(int argc, char **argv)
             return fail("setting the viscous terms");
         double t_ref = 0.0;
         if (conf.viscosity_model() && sutherland_tref_of(conf, &t_ref) != MGCFD_OK) return fail("setting the viscosity model");
+        if (conf.spalart_allmaras && mgcfd_set_sa_free_stream(solver, conf.sa_ratio, 0) != MGCFD_OK) return fail("setting the Spalart-Allmaras free stream");
         if (conf.viscosity_model() &&
             mgcfd_set_viscosity_model(solver, conf.sutherland ? MGCFD_VISCOSITY_SUTHERLAND : MGCFD_VISCOSITY_CONSTANT, t_ref, conf.sutherland_s,
-                                      conf.smagorinsky ? MGCFD_EDDY_SMAGORINSKY : MGCFD_EDDY_NONE, conf.smagorinsky_cs, conf.prandtl_turbulent) != MGCFD_OK)
+                                      conf.spalart_allmaras ? MGCFD_EDDY_SPALART_ALLMARAS : (conf.smagorinsky ? MGCFD_EDDY_SMAGORINSKY : MGCFD_EDDY_NONE),
+                                      conf.smagorinsky_cs, conf.prandtl_turbulent) != MGCFD_OK)
             return fail("setting the viscosity model");
         if (conf.wall_damping && mgcfd_set_wall_damping(solver, 1, conf.wall_kappa) != MGCFD_OK) return fail("setting the wall damping");
     }

@@ -29,6 +29,7 @@
 
 #include "device_owner.hpp"
 #include "kernels.hpp"
+#include "kernels_sa.hpp"
 #include "mesh.hpp"
 #include "mgcfd.h"
 #include "preprocess.hpp"
@@ -208,6 +209,9 @@ struct DeviceLevel {
     int32_t *wall_near = nullptr;
     std::vector<int64_t> wall_ids;
     double *visc_l2 = nullptr;           // [stride] while the wall damping is in effect on the level: l2 (k_wall_length)
+    // the Spalart-Allmaras model, held while it is in effect on the level: nu_tilde [stride] and, on level 0, its value at the
+    // sweep's start, the spare buffer a stage's pass 2 writes (swapped with sa_nt behind it) and sa_gradient [5][stride]
+    double *sa_nt = nullptr, *sa_old = nullptr, *sa_spare = nullptr, *sa_grad = nullptr;
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while ordered_rms(): its RMS is summed in original numbering (settle_rms_order)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
@@ -391,7 +395,8 @@ struct mgcfd_solver {
     {
         ViscosityModel m;
         if (!variable_viscosity()) return m;
-        m.law = vm_law; m.eddy = vm_eddy;
+        m.law = vm_law;
+        m.eddy = vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS ? MGCFD_EDDY_FIELD : vm_eddy;   // (the model's kernels write mut; every consumer reads it)
         m.t_ref = vm_t_ref; m.s = vm_s; m.one_plus_s = 1.0 + vm_s;
         m.c2 = vm_cs * vm_cs; m.cp = 1.4 / (1.4 - 1.0);
         m.prandtl = visc_prandtl; m.prandtl_t = vm_prandtl_t;
@@ -404,6 +409,50 @@ struct mgcfd_solver {
     int wd_on = 0;
     double wd_kappa = MGCFD_WALL_KAPPA;
     bool damping_in_effect() const { return wd_on && vm_eddy == MGCFD_EDDY_SMAGORINSKY && visc_levels > 0; }
+    // The Spalart-Allmaras model (eddy mode MGCFD_EDDY_SPALART_ALLMARAS; INTEGRATION.md "Spalart-Allmaras model"): in effect on
+    // the levels the viscous terms cover; transport on level 0, a restricted nt and a frozen mut on the others.
+    double sa_ratio = MGCFD_SA_RATIO;
+    bool sa_on(int l) const { return vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS && viscous_on(l); }
+    bool sa_in_effect() const { return vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS && visc_levels > 0; }
+    SaStep sa_step(const DeviceLevel &lv, int j = 0) const
+    {
+        const double cb1 = 0.1355, cb2 = 0.622, sigma = 2.0 / 3.0, kappa = 0.41, cv1 = 7.1;
+        SaStep a;
+        a.w = lv.q; a.nt = lv.sa_nt; a.grad = lv.sa_grad; a.mut = lv.visc_mut; a.volumes = lv.volumes;
+        a.mu = visc_mu; a.model = viscosity_model(lv);
+        a.cv1_3 = (cv1 * cv1) * cv1;
+        a.nt_old = lv.sa_old; a.nt_out = lv.sa_spare; a.d = lv.wall_d; a.g = lv.visc_g; a.step_factors = lv.step_factors;
+        a.cw1 = cb1 / (kappa * kappa) + (1.0 + cb2) / sigma; a.c6 = 64.0; a.inv_sigma = 1.0 / sigma; a.ks = (1.0 + cb2) / sigma;
+        a.cfl_v = visc_cfl; a.rk_div = double(MGCFD_RK + 1 - j);
+        return a;
+    }
+    // nt at the sweep's start, beside every copy of variables into old_variables
+    void sa_copy_old(int l)
+    {
+        if (l != 0 || !sa_on(l)) return;
+        DeviceLevel &lv = level(l);
+        HIP_CHECK(hipMemcpyAsync(lv.sa_old, lv.sa_nt, sizeof(double) * lv.dp.stride, hipMemcpyDeviceToDevice, stream));
+    }
+    // pass 2 of stage j, before the update of the five variables: into the spare buffer, which becomes nt
+    void sa_transport(int l, int j)
+    {
+        if (l != 0 || !sa_on(l)) return;
+        DeviceLevel &lv = level(l);
+        launch_sa_transport(stream, lv.dp, sa_step(lv, j));
+        std::swap(lv.sa_nt, lv.sa_spare);
+    }
+    // behind a restriction into level `coarse`: nt averaged over the children, mut from it and the restricted state
+    void sa_restrict(int coarse)
+    {
+        if (!sa_on(coarse)) return;
+        DeviceLevel &F = level(coarse - 1), &C = level(coarse);
+        launch_sa_restrict(stream, C.info.nel, C.dp.stride, F.dp.child_ptr, F.dp.child, F.sa_nt, C.sa_nt, sa_step(C));
+    }
+    // nt = (ratio * mu) / rho_inf, +0.0 on the wall, and mut from it (d given); mut from nt as it stands (d == nullptr)
+    void sa_form(DeviceLevel &lv, bool initialise)
+    {
+        launch_sa_init(stream, lv.info.nel, lv.dp.stride, (sa_ratio * visc_mu) / ff.var[0], initialise ? lv.wall_d : nullptr, lv.sa_nt, sa_step(lv));
+    }
     // sf = min(sf, (k0 * rho) * g) on final step factors, before dual time stepping's clamp; under a non-default viscosity
     // model the limit from mu_i and mut_i per node
     void viscous_clamp(int l)
@@ -576,6 +625,7 @@ struct mgcfd_solver {
         DeviceLevel &lv = level(l);
         settle_residuals(lv);
         HIP_CHECK(hipMemcpyAsync(lv.old_variables, lv.q, sizeof(double) * 5 * lv.dp.stride, hipMemcpyDeviceToDevice, stream));
+        sa_copy_old(l);
     }
     // first half of compute_step_factor; reduce_to_scalar also folds the workgroups' partial
     // minima into the one fp64 scalar the kernel-granular API / the all-reduce hook work on
@@ -585,6 +635,7 @@ struct mgcfd_solver {
         lv.min_ahead = false;                       // partial_min is rewritten (same values if it was ahead)
         if (fuse_copy_old) settle_residuals(lv);
         double *old = fuse_copy_old ? lv.old_variables : nullptr;
+        if (old) sa_copy_old(l);
         k().step_factor_local(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, cfl, lv.step_factors, lv.partial_min, old);
         if (reduce_to_scalar) launch_min_reduce(stream, lv.info.nel, lv.partial_min, lv.min_dt);
     }
@@ -619,7 +670,7 @@ struct mgcfd_solver {
         bool apply_pending = false;
         if (!global_dt()) {
             double *old = (fused && copy_old) ? lv.old_variables : nullptr;
-            if (old) settle_residuals(lv);
+            if (old) { settle_residuals(lv); sa_copy_old(l); }
             if (legacy_dt()) k().step_factor_legacy(stream, lv.info.nel, lv.dp.stride, lv.q, lv.volumes, cfl, lv.step_factors, old);
             else k().step_factor_nodal(stream, lv.info.nel, lv.dp.stride, lv.q, lv.cbrt_vol, lv.volumes, cfl, lv.step_factors, old);
         } else {
@@ -721,6 +772,8 @@ struct mgcfd_solver {
             k().jst_dissipation(stream, lv.dp, a);
         }
         if ((classes & 1) && viscous_on(l)) {
+            // the Spalart-Allmaras model's pass 1 first: the stress launch reads the mut it writes
+            if (l == 0 && sa_on(l)) launch_sa_gradient(stream, lv.dp, sa_step(lv));
             // viscous terms: S of the same state, then fluxes[1..4] += V, behind C (both passes keep row order in either flavour)
             const ViscousStep a = viscous_step(lv);
             k().viscous_stress(stream, lv.dp, a);
@@ -807,6 +860,7 @@ struct mgcfd_solver {
         if (!out) out = lv.q;
         if (out == lv.q) lv.min_ahead = false;
         double *const res = with_residual ? lv.residuals : nullptr;
+        sa_transport(l, j);                          // (reads the stage's input W, which an in-place update overwrites)
         bool stale = true;                          // fluxes[] is not written unless k_time_step zeroes it: logically zero, as after a lazy time_step
         Timed t(this, l, MGCFD_LOOP_TIME_STEP);
         if (smoothing()) {
@@ -895,6 +949,7 @@ struct mgcfd_solver {
         const SumTask task = rms ? *rms : SumTask{};
         k().restrict_(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, C.q, C.cbrt_vol, cfl, pm, task);
         viscous_wall(fine + 1, C.q);
+        sa_restrict(fine + 1);
         C.min_ahead = ahead;
         C.iters[MGCFD_LOOP_RESTRICT] += 2 * F.info.mgc + C.info.nel;   // mg_loops.cpp:61,117,172
     }
@@ -942,6 +997,7 @@ struct mgcfd_solver {
             k().restrict_fas(stream, C.info.nel, C.dp.stride, F.dp.stride, F.dp.child_ptr, F.dp.child, F.dp.child4, F.q, F.fluxes,
                              fas_forced(fine) ? F.fas_p : nullptr, C.q, C.fas_w0, C.fas_p);
             viscous_wall(fine + 1, C.q, C.fas_w0);
+            sa_restrict(fine + 1);
         }
         F.fluxes_zero = true; F.fluxes_stale = true;            // (T is used up)
         C.min_ahead = false;
@@ -1710,6 +1766,7 @@ static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mac
         lv.stage_out = nullptr;                 // (MGCFD_ARR_STAGE named a stage of the state that has just gone)
         if (lv.fas_p) HIP_CHECK(hipMemsetAsync(lv.fas_p, 0, sizeof(double) * 5 * lv.dp.stride, s->stream));   // (the forcing belonged to the old state)
         s->viscous_wall(static_cast<int>(&lv - s->L.data()), lv.q);
+        if (s->sa_on(static_cast<int>(&lv - s->L.data()))) s->sa_form(lv, true);
     }
     HIP_CHECK(hipMemsetAsync(s->err, 0xFF, sizeof(unsigned long long), s->stream));
     s->check_seq = 0;
@@ -1867,6 +1924,48 @@ static void require_damping_possible(const mgcfd_solver *s, int visc_levels, int
         if (!s->L[static_cast<size_t>(l)].wall_d && s->L[static_cast<size_t>(l)].coords.empty())
             throw std::invalid_argument("wall damping: level " + std::to_string(l) + " was created without coordinates (the damping would take effect there)");
 }
+// ... and likewise for the Spalart-Allmaras model, which needs the distance on every level it takes effect on and has no BDF
+// source under dual time stepping.
+static void require_sa_possible(const mgcfd_solver *s, int visc_levels, int eddy)
+{
+    if (eddy != MGCFD_EDDY_SPALART_ALLMARAS) return;
+    if (s->dual_time()) throw std::invalid_argument("Spalart-Allmaras model: not while dual time stepping is on (nu_tilde has no BDF source)");
+    for (int l = 0; l < visc_levels && l < static_cast<int>(s->L.size()); l++)
+        if (!s->L[static_cast<size_t>(l)].wall_d && s->L[static_cast<size_t>(l)].coords.empty())
+            throw std::invalid_argument("Spalart-Allmaras model: level " + std::to_string(l) + " was created without coordinates (the model needs the wall distance there)");
+}
+// nt of a level — and on level 0, where the transport runs, its two companions and sa_gradient — is held exactly while the
+// model is in effect on it; a level that comes
+// into the model (or every level, `all`: the eddy mode has just changed) starts from the free-stream value.  Called once the
+// new state is stored and mut is settled.
+static void settle_sa(mgcfd_solver *s, bool all)
+{
+    for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
+        DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+        if (!s->sa_on(l)) {
+            lv.mem.release(lv.sa_nt); lv.mem.release(lv.sa_old); lv.mem.release(lv.sa_spare); lv.mem.release(lv.sa_grad);
+            continue;
+        }
+        compute_level_wall_distance(s, lv);
+        const size_t stride = static_cast<size_t>(lv.dp.stride);
+        const bool fresh = !lv.sa_nt;
+        if (fresh) {
+            lv.sa_nt = lv.mem.alloc<double>(stride);
+            if (l == 0) {                            // (transport runs on level 0 only: the others hold nt alone)
+                lv.sa_old = lv.mem.alloc<double>(stride); lv.sa_spare = lv.mem.alloc<double>(stride);
+                lv.sa_grad = lv.mem.alloc<double>(5 * stride);
+                HIP_CHECK(hipMemsetAsync(lv.sa_spare, 0, sizeof(double) * stride, s->stream));
+                HIP_CHECK(hipMemsetAsync(lv.sa_grad, 0, sizeof(double) * 5 * stride, s->stream));
+            }
+        }
+        if (fresh || all) {
+            s->sa_form(lv, true);
+            if (l == 0) HIP_CHECK(hipMemcpyAsync(lv.sa_old, lv.sa_nt, sizeof(double) * stride, hipMemcpyDeviceToDevice, s->stream));
+        }
+    }
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+}
+
 // l2 of a level is held exactly while the wall damping is in effect on it, and formed again by every setter that could have
 // changed cs, kappa or the levels: called once the new state is stored and d2 is settled.
 static void settle_wall_damping(mgcfd_solver *s)
@@ -1928,6 +2027,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
                 throw std::invalid_argument("viscous terms: not on a partitioned solver or a rank (a level split over ranks would need the node stresses exchanged per stage)");
         }
         require_damping_possible(s, levels, s->vm_eddy, s->wd_on);
+        require_sa_possible(s, levels, s->vm_eddy);
         quiesce(s, "viscous terms");
         const int n = std::min(levels, static_cast<int>(s->L.size()));
         for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
@@ -1972,6 +2072,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
             if (s->visc_wall) s->settle_residuals(lv);          // (an unwritten residual's operand is about to change)
             s->viscous_wall(l, lv.q);
         }
+        settle_sa(s, false);                                    // (behind the wall rule: mut of a new level is formed from the state it leaves)
         HIP_CHECK(hipStreamSynchronize(s->stream));
         HIP_CHECK(hipGetLastError());
     });
@@ -1994,8 +2095,8 @@ int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_r
         auto positive = [](double x) { return std::isfinite(x) && x > 0.0; };
         if (law != MGCFD_VISCOSITY_CONSTANT && law != MGCFD_VISCOSITY_SUTHERLAND)
             throw std::invalid_argument("viscosity model: law must be MGCFD_VISCOSITY_CONSTANT or MGCFD_VISCOSITY_SUTHERLAND");
-        if (eddy != MGCFD_EDDY_NONE && eddy != MGCFD_EDDY_FIELD && eddy != MGCFD_EDDY_SMAGORINSKY)
-            throw std::invalid_argument("viscosity model: eddy must be MGCFD_EDDY_NONE, MGCFD_EDDY_FIELD or MGCFD_EDDY_SMAGORINSKY");
+        if (eddy != MGCFD_EDDY_NONE && eddy != MGCFD_EDDY_FIELD && eddy != MGCFD_EDDY_SMAGORINSKY && eddy != MGCFD_EDDY_SPALART_ALLMARAS)
+            throw std::invalid_argument("viscosity model: eddy must be MGCFD_EDDY_NONE, MGCFD_EDDY_FIELD, MGCFD_EDDY_SMAGORINSKY or MGCFD_EDDY_SPALART_ALLMARAS");
         if (!std::isfinite(t_ref) || t_ref < 0.0) throw std::invalid_argument("viscosity model: t_ref must be finite and positive, or 0 for the far field's p / rho");
         if (law == MGCFD_VISCOSITY_SUTHERLAND && !positive(s_ratio)) throw std::invalid_argument("viscosity model: Sutherland's s must be finite and positive");
         if (eddy == MGCFD_EDDY_SMAGORINSKY && !positive(cs)) throw std::invalid_argument("viscosity model: the Smagorinsky constant cs must be finite and positive");
@@ -2006,6 +2107,7 @@ int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_r
         if (variable && (s->partitioned || s->comm))
             throw std::invalid_argument("viscosity model: not on a partitioned solver, a group member or a rank (the viscous terms do not run there)");
         require_damping_possible(s, s->visc_levels, eddy, s->wd_on);
+        require_sa_possible(s, s->visc_levels, eddy);
         quiesce(s, "viscosity model");
         const bool eddy_changed = eddy != s->vm_eddy;
         s->vm_law = law; s->vm_eddy = eddy;
@@ -2015,6 +2117,7 @@ int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_r
         s->vm_cs = positive(cs) ? cs : MGCFD_SMAGORINSKY_CS;
         s->vm_prandtl_t = positive(prandtl_t) ? prandtl_t : MGCFD_PRANDTL_TURBULENT;
         settle_viscosity_arrays(s, eddy_changed);
+        settle_sa(s, eddy_changed);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -2890,6 +2993,14 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.wall_d) throw std::invalid_argument("MGCFD_ARR_WALL_DISTANCE: the level does not hold the wall distance (mgcfd_compute_wall_distance)");
             *ncols = 1;
             return lv.wall_d;
+        case MGCFD_ARR_SA_NU_TILDE:
+            if (!lv.sa_nt) throw std::invalid_argument("MGCFD_ARR_SA_NU_TILDE: the Spalart-Allmaras model is not in effect on this level (mgcfd_set_viscosity_model with MGCFD_EDDY_SPALART_ALLMARAS, on a level mgcfd_set_viscous covers)");
+            *ncols = 1;
+            return lv.sa_nt;
+        case MGCFD_ARR_SA_GRADIENT:
+            if (!lv.sa_grad) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: level 0 while the Spalart-Allmaras model is in effect");
+            *ncols = 5;
+            return lv.sa_grad;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -2934,6 +3045,9 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SMAGORINSKY)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under Smagorinsky (every flux launch of a viscous level overwrites it)");
         if (which == MGCFD_ARR_WALL_DISTANCE) throw std::invalid_argument("MGCFD_ARR_WALL_DISTANCE: read-only (geometry, from mgcfd_compute_wall_distance)");
+        if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SPALART_ALLMARAS)
+            throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under the Spalart-Allmaras model (formed from MGCFD_ARR_SA_NU_TILDE)");
+        if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -2950,6 +3064,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         // a restart: a time level written is a time level held
         if (which == MGCFD_ARR_TIME_N) s->dual_levels = std::max(s->dual_levels, 1);
         if (which == MGCFD_ARR_TIME_N1) s->dual_levels = 2;
+        // a restart: mut of the new nt and the level's state, as the enabling call forms it
+        if (which == MGCFD_ARR_SA_NU_TILDE) { s->sa_form(lv, false); HIP_CHECK(hipStreamSynchronize(s->stream)); }
     });
 }
 int mgcfd_array_devptr(mgcfd_solver *s, int level, int which, void **devptr, int64_t *count)
@@ -2976,8 +3092,12 @@ int mgcfd_array_written(mgcfd_solver *s, int level, int which)
         if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SMAGORINSKY)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under Smagorinsky (every flux launch of a viscous level overwrites it)");
         if (which == MGCFD_ARR_WALL_DISTANCE) throw std::invalid_argument("MGCFD_ARR_WALL_DISTANCE: read-only (geometry, from mgcfd_compute_wall_distance)");
+        if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SPALART_ALLMARAS)
+            throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under the Spalart-Allmaras model (formed from MGCFD_ARR_SA_NU_TILDE)");
+        if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
+        if (which == MGCFD_ARR_SA_NU_TILDE) { s->use_device(); s->sa_form(lv, false); }
     });
 }
 // One level per rank: take a restricted `variables` array computed by the rank that holds the finer level.
@@ -5538,6 +5658,7 @@ int mgcfd_release_wall_distance(mgcfd_solver *s)
     return guarded([&] {
         wall_distance_require_whole(s);
         if (s->damping_in_effect()) throw std::invalid_argument("wall distance: the wall damping is in effect (mgcfd_set_wall_damping): switch it off first");
+        if (s->sa_in_effect()) throw std::invalid_argument("wall distance: the Spalart-Allmaras model is in effect (mgcfd_set_viscosity_model): switch it off first");
         require_no_sweep_under_way(s, "wall distance");
         s->use_device();
         HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -5597,6 +5718,45 @@ int mgcfd_get_wall_damping(const mgcfd_solver *s, int *on, double *kappa)
     if (on) *on = s->wd_on;
     if (kappa) *kappa = s->wd_kappa;
     return MGCFD_OK;
+}
+// ---- Spalart-Allmaras model: the free-stream ratio and the launches' times (INTEGRATION.md "Spalart-Allmaras model") ----
+int mgcfd_set_sa_free_stream(mgcfd_solver *s, double ratio, int reinitialise)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (!std::isfinite(ratio) || !(ratio > 0.0)) throw std::invalid_argument("Spalart-Allmaras model: the free-stream ratio must be finite and positive");
+        quiesce(s, "Spalart-Allmaras free stream");
+        s->sa_ratio = ratio;
+        if (!reinitialise) return;
+        for (int l = 0; l < static_cast<int>(s->L.size()); l++)
+            if (s->sa_on(l)) s->sa_form(s->L[static_cast<size_t>(l)], true);
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_sa_free_stream(const mgcfd_solver *s, double *ratio)
+{
+    REQUIRE(s);
+    if (ratio) *ratio = s->sa_ratio;
+    return MGCFD_OK;
+}
+int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->sa_on(level)) throw std::invalid_argument("the Spalart-Allmaras model is not in effect on this level (mgcfd_set_viscosity_model, mgcfd_set_viscous)");
+        if (kind < 0 || kind > 2) throw std::invalid_argument("Spalart-Allmaras launch kind: 0 gradient, 1 transport, 2 restrict");
+        if ((kind == 2) != (level > 0)) throw std::invalid_argument("Spalart-Allmaras launch kind: the gradient and the transport run on level 0, the restriction into a level >= 1");
+        if (kind == 2) { *avg_seconds = s->timed_launches(launches, [&] { s->sa_restrict(level); }); return; }
+        const SaStep a = s->sa_step(lv);
+        launch_sa_gradient(s->stream, lv.dp, a);            // (every array holds a stage's numbers; the transport writes the spare buffer: nt stays)
+        *avg_seconds = s->timed_launches(launches, [&] {
+            if (kind == 0) launch_sa_gradient(s->stream, lv.dp, a);
+            else launch_sa_transport(s->stream, lv.dp, a);
+        });
+    });
 }
 int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *avg_seconds)
 {
@@ -5658,6 +5818,8 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         if (on && (!std::isfinite(clamp) || !(clamp > 0.0))) throw std::invalid_argument("dual time: the clamp must be finite and positive");
         if (on && (s->partitioned || s->comm))
             throw std::invalid_argument("dual time: not on a partitioned solver or a rank (levels split over ranks are out of scope)");
+        if (on && s->vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS)
+            throw std::invalid_argument("dual time: not while the Spalart-Allmaras model is selected (nu_tilde has no BDF source)");
         quiesce(s, "dual time");
         if (on && !s->dual_time()) {
             // switched on: both levels start as the current state (sweeps before the first begin_step see BDF1 against it)

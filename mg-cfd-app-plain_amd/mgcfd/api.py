@@ -25,8 +25,10 @@ RK = 3
 LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "indirect_rw")
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
-       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16}
-NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1}    # (every other array: NVAR)
+       "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16,
+       "sa_nu_tilde": 17, "sa_gradient": 18}
+NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1,
+         "sa_nu_tilde": 1, "sa_gradient": 5}    # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -221,6 +223,9 @@ _SIGNATURES = [
     ("mgcfd_set_wall_damping", C.c_int, [_vp, C.c_int, C.c_double]),
     ("mgcfd_get_wall_damping", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("mgcfd_bench_wall_distance", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_sa_free_stream", C.c_int, [_vp, C.c_double, C.c_int]),
+    ("mgcfd_get_sa_free_stream", C.c_int, [_vp, C.POINTER(C.c_double)]),
+    ("mgcfd_bench_sa", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_cycle", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_get_cycle", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_run_cycles_from", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -433,6 +438,9 @@ VISCOUS_PRANDTL, VISCOUS_CFL = 0.72, 0.25         # MGCFD_VISCOUS_PRANDTL, MGCFD
 SUTHERLAND_S, SMAGORINSKY_CS, PRANDTL_TURBULENT = 0.3831, 0.17, 0.9     # MGCFD_SUTHERLAND_S, MGCFD_SMAGORINSKY_CS, MGCFD_PRANDTL_TURBULENT
 _VISCOSITY_LAWS = {"constant": 0, "sutherland": 1}      # MGCFD_VISCOSITY_*
 _EDDY_MODES = {"none": 0, "field": 1, "smagorinsky": 2}   # MGCFD_EDDY_*
+_TRANSPORTED_EDDY_MODES = {"spalart-allmaras": 4}         # MGCFD_EDDY_SPALART_ALLMARAS: a model with a transported quantity of its own
+_ALL_EDDY_MODES = {**_EDDY_MODES, **_TRANSPORTED_EDDY_MODES}
+SA_RATIO = 3.0                                      # MGCFD_SA_RATIO
 
 
 def viscosity_from_reynolds(ff17, reynolds: float, ref_length: float = 1.0) -> float:
@@ -702,6 +710,25 @@ class Solver:
         self._c(self.lib.mgcfd_get_wall_damping(self.handle, C.byref(on), C.byref(k)))
         return bool(on.value), k.value
 
+    def set_sa_free_stream(self, ratio: float = SA_RATIO, reinitialise: bool = False):
+        """The free-stream value of the Spalart-Allmaras model (mgcfd_set_sa_free_stream): ``nu_tilde = ratio * mu / rho_inf``, which
+        the enabling call and ``set_free_stream(reinitialise=True)`` write on every covered level (+0.0 on the wall);
+        ``reinitialise`` writes it now.  Kept while the model is off."""
+        self._c(self.lib.mgcfd_set_sa_free_stream(self.handle, float(ratio), int(bool(reinitialise))))
+
+    def sa_free_stream(self) -> float:
+        """``ratio`` in use (mgcfd_get_sa_free_stream)."""
+        r = C.c_double()
+        self._c(self.lib.mgcfd_get_sa_free_stream(self.handle, C.byref(r)))
+        return r.value
+
+    def bench_sa(self, l: int, kind, launches: int) -> float:
+        """Mean GPU seconds of one launch of the Spalart-Allmaras model's ``"gradient"`` or ``"transport"`` kernel (level 0) or of
+        its ``"restrict"`` kernel into level ``l >= 1`` (mgcfd_bench_sa)."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_sa(self.handle, l, {"gradient": 0, "transport": 1, "restrict": 2}.get(kind, kind), launches, C.byref(t)))
+        return t.value
+
     def bench_wall_distance(self, l: int, launches: int) -> float:
         """Mean GPU seconds of one wall-distance launch on level ``l``, which must hold the distance (mgcfd_bench_wall_distance)."""
         t = C.c_double()
@@ -854,10 +881,12 @@ class Solver:
         the far field's ``p / rho`` in use now, ``s`` is Sutherland's constant over the reference temperature).  ``eddy``:
         ``"none"``, ``"field"`` (the caller writes the level's ``"eddy_viscosity"`` array) or ``"smagorinsky"`` (constant ``cs``,
         filter width ``cbrt(vol)``, no wall damping; ``"eddy_viscosity"`` is then read-only).  ``prandtl_t`` is the turbulent
-        Prandtl number.  The defaults switch the model off.  No effect while the viscous terms are off; kept across
+        Prandtl number.  ``"spalart-allmaras"`` transports ``nu_tilde`` (the ``"sa_nu_tilde"`` array) on level 0, restricts it to the
+        other covered levels and writes ``"eddy_viscosity"``, which is then read-only; ``cs`` is ignored; the wall distance is
+        computed where it is missing; refused under dual time stepping.  The defaults switch the model off.  No effect while the viscous terms are off; kept across
         ``set_viscous``.  Captured graphs are dropped.  Not on partitioned solvers, group members or ranks."""
         self._c(self.lib.mgcfd_set_viscosity_model(self.handle, _VISCOSITY_LAWS.get(law, law), 0.0 if t_ref is None else float(t_ref),
-                                                   float(s), _EDDY_MODES.get(eddy, eddy), float(cs), float(prandtl_t)))
+                                                   float(s), _ALL_EDDY_MODES.get(eddy, eddy), float(cs), float(prandtl_t)))
 
     def viscosity_model(self) -> dict:
         """``law``, ``t_ref`` (the value taken), ``s``, ``eddy``, ``cs`` and ``prandtl_t`` in use (mgcfd_get_viscosity_model)."""
@@ -865,7 +894,7 @@ class Solver:
         t, s, cs, pt = C.c_double(), C.c_double(), C.c_double(), C.c_double()
         self._c(self.lib.mgcfd_get_viscosity_model(self.handle, C.byref(law), C.byref(t), C.byref(s), C.byref(eddy), C.byref(cs), C.byref(pt)))
         return {"law": {v: k for k, v in _VISCOSITY_LAWS.items()}[law.value], "t_ref": t.value, "s": s.value,
-                "eddy": {v: k for k, v in _EDDY_MODES.items()}[eddy.value], "cs": cs.value, "prandtl_t": pt.value}
+                "eddy": {v: k for k, v in _ALL_EDDY_MODES.items()}[eddy.value], "cs": cs.value, "prandtl_t": pt.value}
 
     def set_dual_time(self, dt: float, clamp: float = 2.0 / 3.0):
         """Time-accurate runs (mgcfd_set_dual_time): every stage's update carries the BDF source of the physical step ``dt`` and
