@@ -854,6 +854,58 @@ int mgcfd_get_sa_free_stream(const mgcfd_solver *s, double *ratio);
  * the spare buffer, so nt stays, 2: k_sa_restrict into level `level` from the level below it), as mgcfd_bench_viscous times
  * its launches.  MGCFD_ERR_ARG where the model is not in effect. */
 int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
+ * Wall thermal conditions and heat loads.  No reference counterpart; INTEGRATION.md "Wall thermal conditions" holds the
+ * definition.  Every operation is one IEEE-754 double operation (+ - * sqrt), never contracted whatever MGCFD_OPT_EXACT says.
+ * Off by default: a solver that never calls mgcfd_set_wall_temperature launches what it launched and computes the same bits.
+ * mgcfd_set_wall_temperature is kept like the viscosity model: either setter may come first, and the setting is in effect on the
+ * levels mgcfd_set_viscous covers, and only while its `wall` is 1.
+ *   MGCFD_WALL_ADIABATIC    value ignored: the no-slip wall of mgcfd_set_viscous as it is.
+ *   MGCFD_WALL_ISOTHERMAL   value = Tw > 0 in the solver's units (T = p / rho).  ew = Tw / (GAMMA - 1.0), formed once on the host.
+ *                           Wherever the no-slip launch runs (behind every writer of a covered level's variables, on FAS's W0, at
+ *                           enable, after mgcfd_set_free_stream(.., reinitialise = 1)) one launch (k_viscous_wall_isothermal) takes
+ *                           its place: momentum +0.0, variables[i][4] = variables[i][0] * ew (W0: from W0's own density), and
+ *                           where the update wrote residuals, residuals[i][4] = variables[i][4] - old_variables[i][4] beside the
+ *                           three momentum residuals.  Density stays.  Setting the mode or a new Tw applies the launch at once;
+ *                           going back to adiabatic leaves the state as it stands.
+ *   MGCFD_WALL_HEAT_FLUX    value = qw, finite, positive heats the fluid.  The wall rule is the adiabatic one.  With a_i the sum of
+ *                           wall node i's solid-wall edge weights (mgcfd_wall_distribution's a) and area_i = sqrt((ax*ax + ay*ay)
+ *                           + az*az), formed on the host when the mode comes into effect, one launch (k_wall_heat_flux) directly
+ *                           behind the viscous-flux launch of every stage does fluxes[i][4] = fluxes[i][4] + qw * area_i
+ *                           (mgcfd_compute_fluxes, mgcfd_compute_flux_edge, FAS's total residual included).
+ * Heat loads: with Sw of mgcfd_surface_loads_viscous (its qx qy qz carry the conductivity of whatever viscosity model is on), a
+ * solid-wall edge (node b, weights (x, y, z)) gives h = -((qx*x + qy*y) + qz*z) and s = sqrt((x*x + y*y) + z*z); the two columns
+ * go through the summation tree beside the twelve: out14 = Fp Mp | Fv Mv | Q A, the first twelve bit for bit
+ * mgcfd_surface_loads_viscous'.  Q is the heat rate the fluid receives from the wall, A the wall's area: on an fvcorr-variant mesh
+ * T = T0 + c z over a wall at z = 0 gives Q = -kappa c A.  On a level the viscous terms are not on for Q = +0.0 (A is still
+ * summed); a level without solid-wall edges gives fourteen exact zeros and launches nothing.
+ * mgcfd_wall_heat: one row per wall node in mgcfd_wall_distribution's order, out [n][3] = h_i T_i area_i with
+ * h_i = -((qx*ax + qy*ay) + qz*az) (+0.0 on a level the viscous terms are not on for), T_i = p_i / rho_i.
+ * The cycle and advance forms give the RMS, final state, errors and NaN rows of their twelve-column siblings.
+ * mgcfd_free_stream_temperature (host only): t_static = p / rho of the far field by derive()'s expressions, t_total = t_static *
+ * (1.0 + 0.2 * M*M) with M*M = speed_sqd / (GAMMA * t_static), from the 17 values alone.  Either pointer may be NULL.
+ * MGCFD_ERR_ARG, and nothing changed: an unknown mode; Tw not finite and positive, qw not finite; while a kernel-granular sweep
+ * is under way; a solver made by mgcfd_create_partitioned* or attached to a group or as a rank (every call of this section).
+ * The setter synchronises and drops captured graphs.  mgcfd_set_array on variables is not followed by the wall launch.
+ * Out of scope: a wall temperature per node; radiative or catalytic walls; partitioned levels, groups and ranks; graphs and fused
+ * stages with the terms on; thermal conditions on slip walls.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_WALL_ADIABATIC 0
+#define MGCFD_WALL_ISOTHERMAL 1
+#define MGCFD_WALL_HEAT_FLUX 2
+int mgcfd_set_wall_temperature(mgcfd_solver *s, int mode, double value);
+int mgcfd_get_wall_temperature(const mgcfd_solver *s, int *mode, double *value);
+int mgcfd_free_stream_temperature(const double ff17[17], double *t_static, double *t_total);   /* host only */
+int mgcfd_surface_loads_heat(mgcfd_solver *s, int level, const double ref_point[3], double out14[14]);
+int mgcfd_run_cycles_loads_heat(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out /* [cycles][14] */);
+int mgcfd_advance_loads_heat(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out /* [steps][14] */,
+                             const double ref_point[3]);
+#define MGCFD_WALL_HEAT_COLUMNS 3
+int mgcfd_wall_heat(mgcfd_solver *s, int level, int64_t *node_ids, double *out /* [n][3] */);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of the isothermal wall launch (kind 0), the adiabatic one (1), the
+ * heat-flux launch (2), the fourteen-column loads (3) or k_wall_heat (4) on a no-slip viscous level with solid walls, as
+ * mgcfd_bench_viscous times its launches.  Kinds 0 and 2 take the value in effect, or 1.0 where the mode is another. */
+int mgcfd_bench_wall_heat(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

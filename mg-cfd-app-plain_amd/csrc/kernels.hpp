@@ -104,7 +104,8 @@ void launch_wall_stress(hipStream_t, int64_t stride, const double *q, const Wall
 void launch_wall_distance(hipStream_t, int64_t nel, int64_t stride, const WallDistance &a);
 void launch_wall_spacing(hipStream_t, const WallSpacing &a);
 void launch_wall_length(hipStream_t, int64_t stride, const WallLength &a);
-void launch_surface_loads_viscous(hipStream_t, int64_t stride, const double *q, const LoadsTaskViscous &task);
+// (columns = 14: the heat loads' Q and A behind the twelve, task.base.partial [14][..], rows of 14)
+void launch_surface_loads_viscous(hipStream_t, int64_t stride, const double *q, const LoadsTaskViscous &task, int columns = 12);
 void launch_wall_distribution(hipStream_t, int64_t stride, const double *q, const WallDistribution &a);
 void launch_loads_terms(hipStream_t, int64_t stride, const double *q, const LoadsTerms &task);
 void launch_loads_scatter(hipStream_t, int64_t n, const double *src, int64_t src_row, const int32_t *slot,
@@ -116,5 +117,5 @@ void launch_fas_add_forcing(hipStream_t, int64_t stride, double *fluxes, const d
 }
 
 // The rule: a launcher has two flavours exactly if MGCFD_FLAVOURED_LAUNCHERS lists it (launch_diag_fast_math beside the
-// list: fast only).  Everything else exists once, in kernels_plain.hip (the Spalart-Allmaras model's: kernels_sa.hip, kernels_sa.hpp), compiled with -ffp-contract=off: never contracted,
+// list: fast only).  Everything else exists once, in kernels_plain.hip (the Spalart-Allmaras model's: kernels_sa.hip, kernels_sa.hpp; the wall thermal conditions': kernels_wall_heat.hip, kernels_wall_heat.hpp), compiled with -ffp-contract=off: never contracted,
 // whichever flavour the solver runs.  So an `exact::` or `fast::` at a call site is always a deliberate choice of flavour.

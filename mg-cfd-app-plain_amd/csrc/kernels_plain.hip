@@ -658,16 +658,20 @@ k_wall_length(int64_t stride, WallLength a)
 // k_surface_loads with the friction six beside the pressure six: one lane per solid-wall edge, twelve terms, the trees
 // of k_surface_loads over twelve columns (24 KB of LDS), the same ticket and stage B.  The pressure terms are
 // k_surface_loads' expressions; task.sw == nullptr (a level the viscous terms are not on for) leaves the friction +0.0.
+// NC = 12, or 14 with the heat loads' two columns behind them (mgcfd_surface_loads_heat): h = -(q . w) from the node's heat flux
+// in Sw and the face area s = |w|, the same trees over fourteen columns (28 KB of LDS).  task.sw == nullptr leaves h +0.0 too.
+template <int NC>
 __global__ void __launch_bounds__(kBlock)
 k_surface_loads_viscous(int64_t stride, const double *__restrict__ q, LoadsTaskViscous task)
 {
 #pragma clang fp contract(off)
-    __shared__ double sh[12][kBlock];
+    static_assert(NC == 12 || NC == 14, "twelve columns, or fourteen with the heat loads");
+    __shared__ double sh[NC][kBlock];
     __shared__ int last;
     const LoadsTask &base = task.base;
     const int t = threadIdx.x;
     const int64_t e = int64_t(blockIdx.x) * kBlock + t;
-    double v[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double v[NC] = {};
     if (e < base.n) {
         const WallRecord r = base.rec[e];
         const int64_t b = r.node;
@@ -693,7 +697,12 @@ k_surface_loads_viscous(int64_t stride, const double *__restrict__ q, LoadsTaskV
             v[9] = ry * gz - rz * gy;
             v[10] = rz * gx - rx * gz;
             v[11] = rx * gy - ry * gx;
+            if constexpr (NC == 14) {
+                const double qx = s[9 * task.nw], qy = s[10 * task.nw], qz = s[11 * task.nw];
+                v[12] = -((qx * r.x + qy * r.y) + qz * r.z);
+            }
         }
+        if constexpr (NC == 14) v[13] = sqrt((r.x * r.x + r.y * r.y) + r.z * r.z);
     }
     loads_tree(v, sh);                                                 // stage A
     const int nb = int(gridDim.x);
@@ -703,7 +712,7 @@ k_surface_loads_viscous(int64_t stride, const double *__restrict__ q, LoadsTaskV
     }
     if (t == 0) {
 #pragma unroll
-        for (int c = 0; c < 12; c++) base.partial[int64_t(c) * nb + blockIdx.x] = v[c];
+        for (int c = 0; c < NC; c++) base.partial[int64_t(c) * nb + blockIdx.x] = v[c];
         const unsigned done = __hip_atomic_fetch_add(base.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         last = done == unsigned(nb - 1);
         if (last) __hip_atomic_store(base.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the next call starts from zero)
@@ -716,11 +725,11 @@ k_surface_loads_viscous(int64_t stride, const double *__restrict__ q, LoadsTaskV
         for (int k = 0; k < m; k++) {
             const int i = k * kBlock + t;
 #pragma unroll
-            for (int c = 0; c < 12; c++) v[c] = i < n ? base.partial[int64_t(c) * nb + i] : 0.0;
+            for (int c = 0; c < NC; c++) v[c] = i < n ? base.partial[int64_t(c) * nb + i] : 0.0;
             loads_tree(v, sh);
             if (t == 0) {
 #pragma unroll
-                for (int c = 0; c < 12; c++) base.partial[int64_t(c) * nb + k] = v[c];
+                for (int c = 0; c < NC; c++) base.partial[int64_t(c) * nb + k] = v[c];
             }
             __syncthreads();
         }
@@ -875,10 +884,13 @@ void launch_wall_spacing(hipStream_t st, const WallSpacing &a)
 void launch_wall_length(hipStream_t st, int64_t stride, const WallLength &a)
 { hipLaunchKernelGGL(k_wall_length, dim3(grid_for(stride)), dim3(kBlock), 0, st, stride, a); }
 
-void launch_surface_loads_viscous(hipStream_t st, int64_t stride, const double *q, const LoadsTaskViscous &task)
+// columns: 12, or 14 with the heat loads' two columns behind them (task.base.partial [14][..], rows of 14)
+void launch_surface_loads_viscous(hipStream_t st, int64_t stride, const double *q, const LoadsTaskViscous &task, int columns)
 {
     if (task.base.n <= 0) return;
-    hipLaunchKernelGGL(k_surface_loads_viscous, dim3(unsigned((task.base.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, stride, q, task);
+    const dim3 grid(unsigned((task.base.n + kBlock - 1) / kBlock));
+    if (columns == 14) hipLaunchKernelGGL(k_surface_loads_viscous<14>, grid, dim3(kBlock), 0, st, stride, q, task);
+    else hipLaunchKernelGGL(k_surface_loads_viscous<12>, grid, dim3(kBlock), 0, st, stride, q, task);
 }
 
 void launch_wall_distribution(hipStream_t st, int64_t stride, const double *q, const WallDistribution &a)

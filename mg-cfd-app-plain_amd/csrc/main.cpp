@@ -92,7 +92,14 @@ struct Config {                       // the reference's `config` (src/Base/conf
     double wall_kappa = MGCFD_WALL_KAPPA;
     bool loads_friction = false;      // --loads-friction: the friction loads beside the pressure loads in surface_loads.* and polar.csv (one GPU)
     bool output_surface = false;      // --output-surface: Cp and Cf per wall node of level 0 into surface.* (one GPU)
-    size_t loads_width() const { return loads_friction ? 12 : 6; }
+    // wall thermal conditions (mgcfd_set_wall_temperature): --wall-temperature T, --wall-temperature-ratio R (times the static
+    // free-stream temperature in use) or --wall-heat-flux Q, with --no-slip and the viscous terms; one of them at most
+    int wall_thermal_flags = 0;       // how many of the three were given
+    int wall_mode = 0;                // MGCFD_WALL_*
+    double wall_value = 0.0;          // T, R or Q as given
+    bool wall_ratio = false;          // ... it is R
+    bool loads_heat = false;          // --loads-heat: Q, A and the mean Stanton number behind the friction columns; qw, T, St in surface.* (one GPU)
+    size_t loads_width() const { return loads_heat ? 14 : (loads_friction ? 12 : 6); }
     // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
     bool fas = false;
     // the multigrid cycle: --cycle V|W|F, --pre-sweeps LIST, --post-sweeps LIST (mgcfd_set_cycle before the first cycle) and
@@ -142,6 +149,19 @@ bool parse_positive(const char *text, double *out)
     double v = 0.0;
     if (!parse_number(text, &v) || !(v > 0.0)) return false;
     *out = v;
+    return true;
+}
+
+// one of the three wall thermal settings: which = 0 --wall-temperature T, 1 --wall-temperature-ratio R (both above zero),
+// 2 --wall-heat-flux Q (any finite number); counts how many were given
+bool set_wall_thermal(Config &c, int which, const char *text)
+{
+    double v = 0.0;
+    if (which == 2 ? !parse_number(text, &v) : !parse_positive(text, &v)) return false;
+    c.wall_thermal_flags++;
+    c.wall_mode = which == 2 ? MGCFD_WALL_HEAT_FLUX : MGCFD_WALL_ISOTHERMAL;
+    c.wall_value = v;
+    c.wall_ratio = which == 1;
     return true;
 }
 
@@ -304,6 +324,13 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
     }
     else if (key == "no_slip") { if (value == "Y") { c.no_slip = true; c.viscous_extras_given = true; } }
+    else if (key == "wall_temperature" || key == "wall_temperature_ratio" || key == "wall_heat_flux") {
+        if (!set_wall_thermal(c, key == "wall_heat_flux" ? 2 : (key == "wall_temperature_ratio" ? 1 : 0), value.c_str())) {
+            std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number%s\n", key.c_str(), value.c_str(), key == "wall_heat_flux" ? "" : " above zero");
+            c.config_bad = true;
+        }
+    }
+    else if (key == "loads_heat") { if (value == "Y") c.loads_heat = true; }
     else if (key == "viscous_levels") {
         if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.viscous_levels)) c.viscous_extras_given = true;
         else { std::fprintf(stderr, "ERROR: viscous_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
@@ -398,6 +425,15 @@ void print_help()
         "                                   coefficients CDv ... CMzv follow them.  One GPU\n"
         "  --output-surface                 Write surface.* (CSV): one row per solid-wall node of level 0 in the final state, its\n"
         "                                   coordinates, wall area vector, Cp and the tangential Cf vector.  One GPU\n"
+        "  --wall-temperature=T             With --no-slip: the wall is held at temperature T (T = p / rho) instead of adiabatic\n"
+        "                                   (config key wall_temperature).  One GPU\n"
+        "  --wall-temperature-ratio=R       ... at R times the static free-stream temperature in use after --mach / --alpha\n"
+        "                                   (config key wall_temperature_ratio)\n"
+        "  --wall-heat-flux=Q               With --no-slip: the wall feeds the heat flux Q into the fluid, of either sign (config key\n"
+        "                                   wall_heat_flux).  The three exclude each other\n"
+        "  --loads-heat                     With --loads-friction: surface_loads.* and polar.csv rows gain Q (the heat rate the fluid\n"
+        "                                   receives from the wall), A (the wall's area) and St_mean; surface.* rows gain qw, T and\n"
+        "                                   St (config key loads_heat = Y).  One GPU\n"
         "  --polar=A0:A1:N                  N angles of attack from A0 to A1 inclusive, -g cycles each: the first starts from its\n"
         "                                   far field, every later one from the flow of the angle before it.  Writes polar.*\n"
         "                                   (CSV: alpha,mach,rms_last, the loads and coefficients of each angle's last cycle);\n"
@@ -537,6 +573,10 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"spalart-allmaras", optional_argument, nullptr, 1046},
         {"loads-friction", no_argument, nullptr, 1038},
         {"output-surface", no_argument, nullptr, 1039},
+        {"wall-temperature", required_argument, nullptr, 1047},
+        {"wall-temperature-ratio", required_argument, nullptr, 1048},
+        {"wall-heat-flux", required_argument, nullptr, 1049},
+        {"loads-heat", no_argument, nullptr, 1054},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -746,6 +786,15 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 break;
             }
             case 1039: c.output_surface = true; break;
+            case 1047: case 1048: case 1049: {
+                static const char *const names[] = {"wall-temperature", "wall-temperature-ratio", "wall-heat-flux"};
+                if (!set_wall_thermal(c, optc - 1047, optarg)) {
+                    std::fprintf(stderr, "ERROR: --%s=%s: expected a finite number%s\n", names[optc - 1047], optarg, optc == 1049 ? "" : " above zero");
+                    return false;
+                }
+                break;
+            }
+            case 1054: c.loads_heat = true; break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
@@ -787,6 +836,22 @@ bool parse_arguments(int argc, char **argv, Config &c)
     }
     if ((c.loads_friction || c.output_surface) && c.gpus > 1) {
         std::fprintf(stderr, "ERROR: --loads-friction and --output-surface run on one GPU only\n");
+        return false;
+    }
+    if (c.wall_thermal_flags > 1) {
+        std::fprintf(stderr, "ERROR: --wall-temperature, --wall-temperature-ratio and --wall-heat-flux are three conditions of the one wall: give one of them\n");
+        return false;
+    }
+    if (c.wall_thermal_flags > 0 && !(c.viscous() && c.viscous_levels > 0 && c.no_slip)) {
+        std::fprintf(stderr, "ERROR: --wall-temperature, --wall-temperature-ratio and --wall-heat-flux need --no-slip and the viscous terms (--viscosity MU or --reynolds RE)\n");
+        return false;
+    }
+    if (c.loads_heat && !c.loads_friction) {
+        std::fprintf(stderr, "ERROR: --loads-heat needs --loads-friction (the heat loads stand behind the friction loads)\n");
+        return false;
+    }
+    if ((c.wall_thermal_flags > 0 || c.loads_heat) && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: the wall thermal conditions and --loads-heat run on one GPU only: not with --gpus N\n");
         return false;
     }
     if (c.dual_extras_given && !c.dual_given) {
@@ -951,6 +1016,28 @@ int validate_and_dump(const Config &conf, int levels, int mesh_variant, int64_t 
 // pressure six and the friction six, the twelve columns are those of their total (one addition per component) and the friction
 // loads and their coefficients follow.
 const char *const kFrictionColumns = ",Fxv,Fyv,Fzv,Mxv,Myv,Mzv,CDv,CLv,CSv,CMxv,CMyv,CMzv";
+// ... and with --loads-heat the heat rate the fluid receives from the wall, the wall's area and the mean Stanton number
+// St_mean = (Q / A) / (rho_inf |V_inf| cp (T_total - Tw)), cp = GAMMA / (GAMMA - 1), Tw = the wall temperature of
+// --wall-temperature[-ratio], the static free-stream temperature under any other wall
+const char *const kHeatColumns = ",Q,A,St_mean";
+std::string loads_header(const Config &conf) { return std::string(conf.loads_friction ? kFrictionColumns : "") + (conf.loads_heat ? kHeatColumns : ""); }
+// the wall temperature of the run against the far field ff17: as given, or the ratio times the static free-stream temperature;
+// *isothermal: the wall is held at it
+int wall_temperature_of(const Config &conf, const double ff17[17], double *tw, bool *isothermal, double *t_total)
+{
+    double t_static = 0.0;
+    const int rc = mgcfd_free_stream_temperature(ff17, &t_static, t_total);
+    if (rc != MGCFD_OK) return rc;
+    *isothermal = conf.wall_thermal_flags > 0 && conf.wall_mode == MGCFD_WALL_ISOTHERMAL;
+    *tw = *isothermal ? (conf.wall_ratio ? conf.wall_value * t_static : conf.wall_value) : t_static;
+    return MGCFD_OK;
+}
+// rho_inf |V_inf| cp
+double stanton_scale(const double ff17[17])
+{
+    const double vx = ff17[1] / ff17[0], vy = ff17[2] / ff17[0], vz = ff17[3] / ff17[0];
+    return ff17[0] * std::sqrt(vx * vx + vy * vy + vz * vz) * (1.4 / (1.4 - 1.0));
+}
 int write_loads_columns(FILE *f, const Config &conf, const double ff17[17], const double *row)
 {
     double total[6], coef[6];
@@ -962,6 +1049,11 @@ int write_loads_columns(FILE *f, const Config &conf, const double ff17[17], cons
     if (mgcfd_load_coefficients(ff17, row + 6, conf.loads_ref[0], conf.loads_ref[1], coef) != MGCFD_OK) return 1;
     for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", row[6 + k]);
     for (int k = 0; k < 6; k++) std::fprintf(f, ",%.17e", coef[k]);
+    if (!conf.loads_heat) return 0;
+    double tw = 0.0, t_total = 0.0;
+    bool isothermal = false;
+    if (wall_temperature_of(conf, ff17, &tw, &isothermal, &t_total) != MGCFD_OK) return 1;
+    std::fprintf(f, ",%.17e,%.17e,%.17e", row[12], row[13], (row[12] / row[13]) / (stanton_scale(ff17) * (t_total - tw)));
     return 0;
 }
 
@@ -971,7 +1063,7 @@ int write_loads_csv(const Config &conf, const double ff17[17], const std::vector
     const std::string path = output_filepath(conf, "surface_loads", 0);
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
-    std::fprintf(f, "cycle,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz%s\n", conf.loads_friction ? kFrictionColumns : "");
+    std::fprintf(f, "cycle,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz%s\n", loads_header(conf).c_str());
     for (int c = 0; c < conf.loads_rows(); c++) {
         std::fprintf(f, "%d", c + 1);
         if (write_loads_columns(f, conf, ff17, loads.data() + static_cast<size_t>(c) * conf.loads_width())) {
@@ -985,13 +1077,13 @@ int write_loads_csv(const Config &conf, const double ff17[17], const std::vector
 }
 
 // --polar: one row per angle — the RMS, loads and coefficients of its last cycle (nothing on stdout)
-struct PolarRow { double alpha, mach, rms_last, loads[12], ff17[17]; };
+struct PolarRow { double alpha, mach, rms_last, loads[14], ff17[17]; };
 int write_polar_csv(const Config &conf, const std::vector<PolarRow> &rows)
 {
     const std::string path = csv_filepath(conf, "polar.csv");
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
-    std::fprintf(f, "alpha,mach,rms_last,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz%s\n", conf.loads_friction ? kFrictionColumns : "");
+    std::fprintf(f, "alpha,mach,rms_last,Fx,Fy,Fz,Mx,My,Mz,CD,CL,CS,CMx,CMy,CMz%s\n", loads_header(conf).c_str());
     for (const PolarRow &r : rows) {
         std::fprintf(f, "%.17e,%.17e,%.17e", r.alpha, r.mach, r.rms_last);
         if (write_loads_columns(f, conf, r.ff17, r.loads)) {
@@ -1018,6 +1110,12 @@ int write_surface_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh
     std::vector<int64_t> ids(static_cast<size_t>(n));
     std::vector<double> table(static_cast<size_t>(n) * MGCFD_WALL_COLUMNS);
     if (n > 0 && mgcfd_wall_distribution(solver, 0, ids.data(), table.data()) != MGCFD_OK) return fail("computing the surface distribution");
+    // --loads-heat: qw = h / area, T and St = qw / (rho_inf |V_inf| cp (T_total - Tw)) per node, Tw the held wall temperature or the node's own T
+    std::vector<double> heat(conf.loads_heat ? static_cast<size_t>(n) * MGCFD_WALL_HEAT_COLUMNS : 0);
+    double tw = 0.0, t_total = 0.0;
+    bool isothermal = false;
+    if (conf.loads_heat && ((n > 0 && mgcfd_wall_heat(solver, 0, nullptr, heat.data()) != MGCFD_OK) || wall_temperature_of(conf, ff17, &tw, &isothermal, &t_total) != MGCFD_OK))
+        return fail("computing the wall heat table");
     const double vx = ff17[1] / ff17[0], vy = ff17[2] / ff17[0], vz = ff17[3] / ff17[0];
     const double q = 0.5 * ff17[0] * (vx * vx + vy * vy + vz * vz);
     std::string path = conf.output_file_prefix;
@@ -1025,7 +1123,7 @@ int write_surface_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh
     path += "surface.size=" + std::to_string(conf.mesh_duplicate_count) + "x.level=0";
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) return fail(("opening " + path).c_str());
-    std::fprintf(f, "node,x,y,z,ax,ay,az,Cp,Cfx,Cfy,Cfz\n");
+    std::fprintf(f, "node,x,y,z,ax,ay,az,Cp,Cfx,Cfy,Cfz%s\n", conf.loads_heat ? ",qw,T,St" : "");
     for (int64_t k = 0; k < n; k++) {
         const double *r = table.data() + static_cast<size_t>(k) * MGCFD_WALL_COLUMNS;
         const int64_t i = ids[static_cast<size_t>(k)];
@@ -1035,7 +1133,13 @@ int write_surface_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh
         const double cf[3] = {(r[4] - tn * nx) / (area * q), (r[5] - tn * ny) / (area * q), (r[6] - tn * nz) / (area * q)};
         std::fprintf(f, "%ld", static_cast<long>(i));
         for (int d = 0; d < 3; d++) std::fprintf(f, ",%.17e", desc.coords ? desc.coords[i * 3 + d] : 0.0);
-        std::fprintf(f, ",%.17e,%.17e,%.17e,%.17e,%.17e,%.17e,%.17e\n", r[0], r[1], r[2], r[3] / q, cf[0], cf[1], cf[2]);
+        std::fprintf(f, ",%.17e,%.17e,%.17e,%.17e,%.17e,%.17e,%.17e", r[0], r[1], r[2], r[3] / q, cf[0], cf[1], cf[2]);
+        if (conf.loads_heat) {
+            const double *h = heat.data() + static_cast<size_t>(k) * MGCFD_WALL_HEAT_COLUMNS;
+            const double qw = h[0] / h[2];
+            std::fprintf(f, ",%.17e,%.17e,%.17e", qw, h[1], qw / (stanton_scale(ff17) * (t_total - (isothermal ? tw : h[1]))));
+        }
+        std::fprintf(f, "\n");
     }
     if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
     return 0;
@@ -1307,6 +1411,13 @@ int main(int argc, char **argv)
                                       conf.smagorinsky_cs, conf.prandtl_turbulent) != MGCFD_OK)
             return fail("setting the viscosity model");
         if (conf.wall_damping && mgcfd_set_wall_damping(solver, 1, conf.wall_kappa) != MGCFD_OK) return fail("setting the wall damping");
+        if (conf.wall_thermal_flags > 0) {
+            // (the ratio against the free stream in use after --mach / --alpha; the angle of attack does not change its temperature)
+            double f[17], t_static = 0.0;
+            if (mgcfd_free_stream_constants(conf.ff_mach, conf.angle(0), f) != MGCFD_OK || mgcfd_free_stream_temperature(f, &t_static, nullptr) != MGCFD_OK ||
+                mgcfd_set_wall_temperature(solver, conf.wall_mode, conf.wall_ratio ? conf.wall_value * t_static : conf.wall_value) != MGCFD_OK)
+                return fail("setting the wall thermal condition");
+        }
     }
     if (conf.fas && mgcfd_set_fas(solver, 1) != MGCFD_OK) return fail("switching FAS multigrid on");
     if (conf.cycle_given() && mgcfd_set_cycle(solver, conf.cycle_shape, pre.data(), post.data()) != MGCFD_OK) return fail("setting the multigrid cycle");
@@ -1324,7 +1435,8 @@ int main(int argc, char **argv)
                     const int now = std::min(per_call, conf.time_steps - steps_done);
                     double *const rms_at = rms_out + size_t(steps_done) * size_t(conf.num_cycles);
                     double *const loads_at = loads_out ? loads_out + size_t(steps_done) * conf.loads_width() : nullptr;
-                    const int rc_adv = conf.loads_friction ? mgcfd_advance_loads_viscous(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2)
+                    const int rc_adv = conf.loads_heat && loads_at ? mgcfd_advance_loads_heat(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2)
+                                     : conf.loads_friction ? mgcfd_advance_loads_viscous(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2)
                                                            : mgcfd_advance(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2);
                     if (rc_adv != MGCFD_OK) {
                         int bad_step = -1;
@@ -1347,6 +1459,7 @@ int main(int argc, char **argv)
                         std::fprintf(stderr, "[euler3d_gpu_double] full multigrid: %d cycles from level %d, RMS %.3e -> %.3e\n", fmg[static_cast<size_t>(top)], top,
                                      fmg_rms[at], fmg_rms[at + static_cast<size_t>(fmg[static_cast<size_t>(top)]) - 1]);
             }
+            if (loads_out && conf.loads_heat) return mgcfd_run_cycles_loads_heat(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out);
             if (loads_out && conf.loads_friction) return mgcfd_run_cycles_loads_viscous(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out);
             return loads_out ? mgcfd_run_cycles_loads(solver, conf.num_cycles, conf.loads_ref + 2, rms_out, loads_out)
                              : mgcfd_run_cycles(solver, conf.num_cycles, rms_out);

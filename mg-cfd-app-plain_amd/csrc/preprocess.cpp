@@ -1405,4 +1405,32 @@ WallRows build_wall_rows(const mgcfd_level_desc &lvl, const std::vector<mgcfd_ed
     return R;
 }
 
+std::vector<double> wall_areas(const mgcfd_level_desc &lvl, const std::vector<mgcfd_edge> &edges, const std::vector<int32_t> &new_of_old,
+                               const std::vector<int32_t> &nodes)
+{
+    const int64_t nel = lvl.nel;
+    // per node of the solver's numbering, its position in the list
+    std::vector<int32_t> at(static_cast<size_t>(nel), -1);
+    for (size_t k = 0; k < nodes.size(); k++) {
+        if (nodes[k] < 0 || nodes[k] >= nel) throw std::invalid_argument("wall areas: a listed node out of range");
+        if (at[static_cast<size_t>(nodes[k])] >= 0) throw std::invalid_argument("wall areas: a node listed twice");
+        at[static_cast<size_t>(nodes[k])] = static_cast<int32_t>(k);
+    }
+    std::vector<double> a(3 * nodes.size(), 0.0);
+    for (int64_t k = 0; k < lvl.n_boundary; k++) {
+        const mgcfd_edge &e = edges[static_cast<size_t>(lvl.boundary_start + k)];
+        if (e.b < 0 || e.b >= nel) throw std::invalid_argument("wall areas: an edge names a node out of range");
+        const int32_t node = new_of_old[static_cast<size_t>(e.b)];
+        if (node < 0 || node >= nel || at[static_cast<size_t>(node)] < 0) throw std::invalid_argument("wall areas: a solid-wall edge at a node that is not listed");
+        double *s = a.data() + 3 * static_cast<size_t>(at[static_cast<size_t>(node)]);
+        s[0] += e.x; s[1] += e.y; s[2] += e.z;
+    }
+    std::vector<double> area(nodes.size());
+    for (size_t k = 0; k < nodes.size(); k++) {
+        const double ax = a[3 * k], ay = a[3 * k + 1], az = a[3 * k + 2];
+        area[k] = std::sqrt((ax * ax + ay * ay) + az * az);
+    }
+    return area;
+}
+
 } // namespace mgcfd

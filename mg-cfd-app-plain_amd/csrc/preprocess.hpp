@@ -195,6 +195,14 @@ struct WallRows {
 };
 WallRows build_wall_rows(const mgcfd_level_desc &lvl, const std::vector<mgcfd_edge> &edges, const std::vector<int32_t> &new_of_old);
 
+// The wall nodes' areas for the heat-flux wall (mgcfd_set_wall_temperature): for every node of `nodes` (the level's wall nodes in
+// the solver's numbering, each once) a = the sum of its solid-wall edge weights from +0.0 in slice order, one addition per edge
+// and component (mgcfd_wall_distribution's a), area = sqrt((ax*ax + ay*ay) + az*az); the result is aligned with `nodes`.
+// Throws std::invalid_argument where an edge names a node outside [0, nel), a node is listed twice or out of range, or a
+// solid-wall edge ends at a node that is not listed.
+std::vector<double> wall_areas(const mgcfd_level_desc &lvl, const std::vector<mgcfd_edge> &edges, const std::vector<int32_t> &new_of_old,
+                               const std::vector<int32_t> &nodes);
+
 // Edge-weight preconditioning exactly as the reference does before its loop
 // (src/Kernels/validation.cpp:28-75, src/euler3d_cpu_double.cpp:337-352).
 void adjust_and_dampen(const mgcfd_level_desc &lvl, int mesh_variant, std::vector<mgcfd_edge> &edges);

@@ -30,6 +30,7 @@
 #include "device_owner.hpp"
 #include "kernels.hpp"
 #include "kernels_sa.hpp"
+#include "kernels_wall_heat.hpp"
 #include "mesh.hpp"
 #include "mgcfd.h"
 #include "preprocess.hpp"
@@ -159,6 +160,9 @@ struct WallPlan {
     double *partial = nullptr;           // [12][ceil(n_wall_rec / 256)]
     unsigned *ticket = nullptr;
     double *dist = nullptr;              // [wn.n][MGCFD_WALL_COLUMNS] the distribution's result
+    // the heat loads (mgcfd_surface_loads_heat, mgcfd_wall_heat), made by the first such call for the level
+    double *partial14 = nullptr;         // [14][ceil(n_wall_rec / 256)]
+    double *heat = nullptr;              // [wn.n][MGCFD_WALL_HEAT_COLUMNS] the heat table's result
 };
 
 struct DeviceLevel {
@@ -197,6 +201,7 @@ struct DeviceLevel {
     double *visc_s = nullptr, *visc_g = nullptr;
     int32_t *visc_wall = nullptr;
     int64_t n_visc_wall = 0;
+    double *wall_area = nullptr;         // [n_visc_wall] while the heat-flux wall is in effect on the level (mgcfd_set_wall_temperature)
     // ... and, while a non-default viscosity model is set as well (mgcfd_set_viscosity_model): the eddy viscosity [stride] and
     // d2 = cbrt(vol) * cbrt(vol) [stride]
     double *visc_mut = nullptr, *visc_d2 = nullptr;
@@ -335,6 +340,8 @@ struct mgcfd_solver {
     double loads_ref_host[3] = {0.0, 0.0, 0.0};
     bool loads_in_cycle = false;
     bool loads_friction = false;                   // ... as twelve-wide rows, the friction six beside the pressure six
+    bool loads_heat = false;                       // ... as fourteen-wide rows, Q and A behind them (mgcfd_run_cycles_loads_heat)
+    double *loads_ring14 = nullptr, *loads_dev14 = nullptr;                   // [kRmsRing][14]; a synchronous call's out [14]
     bool partitioned = false;                      // made by mgcfd_create_partitioned* (loads: the group and rank forms, over all ranks)
     double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
     double fs_mach = kDefaultMach, fs_alpha_deg = kDefaultAlphaDeg;      // what ff17 was computed from (mgcfd_set_free_stream)
@@ -468,12 +475,26 @@ struct mgcfd_solver {
         const double kv = std::max(4.0 / 3.0, 1.4 / visc_prandtl);
         launch_viscous_clamp(stream, lv.info.nel, visc_cfl / (kv * visc_mu), lv.q, lv.visc_g, lv.step_factors);
     }
-    // the no-slip wall behind a launch that wrote q (and q2: FAS's copy of it); residuals where that launch wrote them
+    // Wall thermal conditions (mgcfd_set_wall_temperature; INTEGRATION.md "Wall thermal conditions"): kept like the viscosity
+    // model; in effect on the levels the viscous terms cover while their wall is the no-slip one.  wt_ew = Tw / (GAMMA - 1.0).
+    int wt_mode = MGCFD_WALL_ADIABATIC;
+    double wt_value = 0.0, wt_ew = 0.0;
+    bool wall_thermal(int mode) const { return wt_mode == mode && visc_wall && visc_levels > 0; }
+    // the no-slip wall behind a launch that wrote q (and q2: FAS's copy of it); residuals where that launch wrote them; the
+    // isothermal wall's launch in its place while that mode is in effect
     void viscous_wall(int l, double *q, double *q2 = nullptr, const double *old = nullptr, double *residuals = nullptr)
     {
         if (!viscous_on(l) || !visc_wall) return;
         DeviceLevel &lv = level(l);
-        launch_viscous_wall(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, q, q2, old, residuals);
+        if (wt_mode == MGCFD_WALL_ISOTHERMAL) launch_viscous_wall_isothermal(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, wt_ew, q, q2, old, residuals);
+        else launch_viscous_wall(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, q, q2, old, residuals);
+    }
+    // the heat-flux wall's addition into fluxes[][4], directly behind the viscous-flux launch
+    void wall_heat_flux(int l)
+    {
+        DeviceLevel &lv = level(l);
+        if (!wall_thermal(MGCFD_WALL_HEAT_FLUX) || !lv.wall_area) return;
+        launch_wall_heat_flux(stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, lv.wall_area, wt_value, lv.fluxes);
     }
     // FAS multigrid (mgcfd_set_fas): the V-cycle's transfers become the FAS legs (op_fas_restrict, op_fas_prolong) and every stage
     // of a level >= 1 takes R + P for its total residual R.  Such a level runs unfused stages (standalone flux launch + the
@@ -778,6 +799,7 @@ struct mgcfd_solver {
             const ViscousStep a = viscous_step(lv);
             k().viscous_stress(stream, lv.dp, a);
             k().viscous_flux(stream, lv.dp, a);
+            wall_heat_flux(l);
         }
         if (dual_time()) lv.flux_in = lv.q;
         lv.fluxes_zero = false;
@@ -2013,6 +2035,20 @@ static void settle_viscosity_arrays(mgcfd_solver *s, bool zero)
     settle_wall_damping(s);
 }
 
+// The wall areas of a level are held exactly while the heat-flux wall is in effect on it (mgcfd_set_wall_temperature): both
+// setters call this once their new state is stored and the level's wall nodes are settled.
+static void settle_wall_areas(mgcfd_solver *s)
+{
+    for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
+        DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+        if (!s->wall_thermal(MGCFD_WALL_HEAT_FLUX) || !s->viscous_on(l)) { lv.mem.release(lv.wall_area); continue; }
+        if (lv.wall_area) continue;
+        std::vector<int32_t> nodes(static_cast<size_t>(lv.n_visc_wall));
+        if (!nodes.empty()) HIP_CHECK(hipMemcpy(nodes.data(), lv.visc_wall, sizeof(int32_t) * nodes.size(), hipMemcpyDeviceToHost));
+        lv.wall_area = lv.mem.upload(wall_areas(lv.info, lv.edges, lv.plan.new_of_old, nodes));
+    }
+}
+
 // ---- laminar viscous terms: viscosity, Prandtl number, wall condition, step limit and the levels they run on ----
 int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, double cfl_v, int levels)
 {
@@ -2063,6 +2099,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
         s->visc_prandtl = n > 0 ? prandtl : 0.0;
         s->visc_cfl = n > 0 ? cfl_v : 0.0;
         s->visc_wall = n > 0 ? wall : 0;
+        settle_wall_areas(s);
         settle_viscosity_arrays(s, false);
         settle_rms_order(s);
         drop_look_ahead(s);
@@ -2086,6 +2123,62 @@ int mgcfd_get_viscous(const mgcfd_solver *s, double *mu, double *prandtl, int *w
     if (cfl_v) *cfl_v = s->visc_cfl;
     if (levels) *levels = s->visc_levels;
     return MGCFD_OK;
+}
+// ---- wall thermal conditions: adiabatic, isothermal and heat-flux no-slip walls (INTEGRATION.md "Wall thermal conditions") ----
+// what every call of the section refuses: a rank holds part of the wall only
+static void wall_heat_require_whole(const mgcfd_solver *s)
+{
+    if (s->partitioned || s->comm)
+        throw std::invalid_argument("wall thermal conditions: not on a partitioned solver, a group member or a rank (a rank holds part of the wall only)");
+}
+int mgcfd_set_wall_temperature(mgcfd_solver *s, int mode, double value)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (mode != MGCFD_WALL_ADIABATIC && mode != MGCFD_WALL_ISOTHERMAL && mode != MGCFD_WALL_HEAT_FLUX)
+            throw std::invalid_argument("wall temperature: mode must be MGCFD_WALL_ADIABATIC, MGCFD_WALL_ISOTHERMAL or MGCFD_WALL_HEAT_FLUX");
+        if (mode == MGCFD_WALL_ISOTHERMAL && (!std::isfinite(value) || !(value > 0.0)))
+            throw std::invalid_argument("wall temperature: the wall temperature must be finite and positive");
+        if (mode == MGCFD_WALL_HEAT_FLUX && !std::isfinite(value)) throw std::invalid_argument("wall temperature: the wall heat flux must be finite");
+        wall_heat_require_whole(s);
+        quiesce(s, "wall temperature");
+        s->wt_mode = mode;
+        s->wt_value = mode == MGCFD_WALL_ADIABATIC ? 0.0 : value;
+        s->wt_ew = mode == MGCFD_WALL_ISOTHERMAL ? value / (1.4 - 1.0) : 0.0;
+        settle_wall_areas(s);
+        // the isothermal wall holds from the start (going back to adiabatic leaves the state as it stands)
+        if (s->wall_thermal(MGCFD_WALL_ISOTHERMAL))
+            for (int l = 0; l < s->visc_levels; l++) {
+                DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+                s->settle_residuals(lv);                            // (an unwritten residual's operand is about to change)
+                s->viscous_wall(l, lv.q);
+            }
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_wall_temperature(const mgcfd_solver *s, int *mode, double *value)
+{
+    REQUIRE(s);
+    if (mode) *mode = s->wt_mode;
+    if (value) *value = s->wt_value;
+    return MGCFD_OK;
+}
+int mgcfd_free_stream_temperature(const double ff17[17], double *t_static, double *t_total)
+{
+    REQUIRE(ff17);
+    return guarded([&] {
+        // derive()'s pressure on ff_variable; M*M = speed_sqd / (GAMMA * T)
+        const double rho = ff17[0];
+        const double vx = ff17[1] / rho, vy = ff17[2] / rho, vz = ff17[3] / rho;
+        const double speed_sqd = vx * vx + vy * vy + vz * vz;
+        const double p = (1.4 - 1.0) * (ff17[4] - 0.5 * rho * speed_sqd);
+        const double t = p / rho;
+        if (!std::isfinite(t) || !(t > 0.0)) throw std::invalid_argument("free-stream temperature: the far field's p / rho is not finite and positive");
+        const double m2 = speed_sqd / (1.4 * t);
+        if (t_static) *t_static = t;
+        if (t_total) *t_total = t * (1.0 + 0.2 * m2);
+    });
 }
 // ---- viscosity model: Sutherland's law, a caller's eddy-viscosity field, Smagorinsky ----
 int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_ratio, int eddy, double cs, double prandtl_t)
@@ -2577,22 +2670,31 @@ static void launch_wall_stress(mgcfd_solver *s, int l)
 // Level l's pressure and friction loads of its current `variables` (the level has a plan), as launch_loads: twelve sums
 // into `out` (device) or, out == nullptr, into the twelve-wide history's row of the cycle whose RMS was appended last.  The
 // stress launch runs where the viscous terms are on for the level.
-static void launch_loads_twelve(mgcfd_solver *s, int l, double *out)
+// heat (mgcfd_surface_loads_heat): fourteen sums, Q and A behind the twelve, into `out` or the fourteen-wide history
+static void launch_loads_twelve(mgcfd_solver *s, int l, double *out, bool heat = false)
 {
     DeviceLevel &lv = s->level(l);
     const bool viscous = s->viscous_on(l);
     LoadsTaskViscous t;
     t.base.rec = lv.wall_rec; t.base.n = lv.n_wall_rec; t.base.p_inf = s->p_inf; t.base.ref = s->loads_dev;
-    t.base.partial = lv.wp->partial; t.base.ticket = lv.wp->ticket;
-    if (!out) { t.base.ring = s->loads_ring12; t.base.count = s->rms_count; t.base.cap = mgcfd_solver::kRmsRing; }
+    t.base.partial = heat ? lv.wp->partial14 : lv.wp->partial; t.base.ticket = lv.wp->ticket;
+    if (!out) { t.base.ring = heat ? s->loads_ring14 : s->loads_ring12; t.base.count = s->rms_count; t.base.cap = mgcfd_solver::kRmsRing; }
     else t.base.out = out;
     t.wall_of_rec = lv.wp->wall_of_rec; t.sw = viscous ? lv.wp->sw : nullptr; t.nw = lv.wp->wn.n;
-    launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t);
+    launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t, heat ? 14 : 12);
 }
-static void launch_loads_viscous(mgcfd_solver *s, int l, double *out)
+static void launch_loads_viscous(mgcfd_solver *s, int l, double *out, bool heat = false)
 {
     if (s->viscous_on(l)) launch_wall_stress(s, l);
-    launch_loads_twelve(s, l, out);
+    launch_loads_twelve(s, l, out, heat);
+}
+// The wall plan with what the heat loads add to it (allocations: never inside a capture or a cycle).
+static WallPlan &wall_plan_heat(mgcfd_solver *s, DeviceLevel &lv)
+{
+    WallPlan &wp = wall_plan(s, lv);
+    if (!wp.partial14) wp.partial14 = wp.mem.alloc<double>(14 * static_cast<size_t>((lv.n_wall_rec + 255) / 256));
+    if (!wp.heat) wp.heat = wp.mem.alloc<double>(MGCFD_WALL_HEAT_COLUMNS * static_cast<size_t>(wp.wn.n));
+    return wp;
 }
 
 // Loads need the whole level on one solver: refuse a partitioned solver or a rank.
@@ -2616,6 +2718,10 @@ static void ensure_loads_ring(mgcfd_solver *s)
 static void ensure_loads_ring12(mgcfd_solver *s)
 {
     if (!s->loads_ring12) s->loads_ring12 = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 12);
+}
+static void ensure_loads_ring14(mgcfd_solver *s)
+{
+    if (!s->loads_ring14) s->loads_ring14 = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 14);
 }
 
 static void loads_prepare(mgcfd_solver *s, const double *ref_point)
@@ -2704,27 +2810,29 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
     };
     visit(top, s->cycle_shape);
     // (the state the cycle leaves: after the last prolongation and level 0's post-sweeps)
-    if (s->loads_in_cycle) { if (s->loads_friction) launch_loads_viscous(s, 0, nullptr); else launch_loads(s, s->L[0], true); }
+    if (s->loads_in_cycle) { if (s->loads_friction) launch_loads_viscous(s, 0, nullptr, s->loads_heat); else launch_loads(s, s->L[0], true); }
 }
 
 // loads_out != nullptr (mgcfd_run_cycles_loads): also the level-0 surface loads at the end of every cycle, [cycles][6];
-// friction (mgcfd_run_cycles_loads_viscous): rows of twelve, the friction six beside the pressure six, launched directly
-static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out, bool friction = false)
+// friction (mgcfd_run_cycles_loads_viscous): rows of twelve, the friction six beside the pressure six, launched directly;
+// heat (with friction: mgcfd_run_cycles_loads_heat): rows of fourteen, Q and A behind the twelve
+static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out, bool friction = false, bool heat = false)
 {
-    const size_t width = friction ? 12 : 6;
+    const size_t width = heat ? 14 : (friction ? 12 : 6);
     REQUIRE(s);
     int code = MGCFD_OK, failed_cycle = -1, seq_before = 0, seq_per_cycle = 0;
     std::vector<double> loads;
     int rc = guarded([&] {
         s->use_device();
         ensure_rms_ring(s);
-        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = s->loads_friction = false; } } loads_off{s};
+        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = s->loads_friction = s->loads_heat = false; } } loads_off{s};
         if (loads_out) {
             loads_prepare(s, ref_point);
-            if (friction) ensure_loads_ring12(s); else ensure_loads_ring(s);
+            if (heat) ensure_loads_ring14(s); else if (friction) ensure_loads_ring12(s); else ensure_loads_ring(s);
             s->loads_in_cycle = s->L[0].n_wall_rec > 0;        // (no solid wall: zeros, nothing launched)
             s->loads_friction = friction;
-            if (friction && s->loads_in_cycle) wall_plan(s, s->L[0]);
+            s->loads_heat = heat;
+            if (friction && s->loads_in_cycle) { if (heat) wall_plan_heat(s, s->L[0]); else wall_plan(s, s->L[0]); }
             loads.reserve(static_cast<size_t>(cycles > 0 ? cycles : 0) * width);
         }
         const size_t nl = s->L.size();
@@ -2814,7 +2922,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             if (loads_out) {
                 loads.resize((at + static_cast<size_t>(chunk)) * width, 0.0);
                 if (s->loads_in_cycle)
-                    HIP_CHECK(hipMemcpyAsync(loads.data() + at * width, friction ? s->loads_ring12 : s->loads_ring, sizeof(double) * width * chunk,
+                    HIP_CHECK(hipMemcpyAsync(loads.data() + at * width, heat ? s->loads_ring14 : (friction ? s->loads_ring12 : s->loads_ring), sizeof(double) * width * chunk,
                                              hipMemcpyDeviceToHost, s->stream));
             }
             int seq = 0;
@@ -5623,6 +5731,91 @@ int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launche
     });
 }
 
+// ---- heat loads: Q and A behind the twelve, the heat table (INTEGRATION.md "Wall thermal conditions") ----
+int mgcfd_surface_loads_heat(mgcfd_solver *s, int level, const double ref_point[3], double out14[14])
+{
+    REQUIRE(s); REQUIRE(out14);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        loads_prepare(s, ref_point);
+        double got[14] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (lv.n_wall_rec > 0) {                          // (no solid wall: exact zeros, nothing launched)
+            wall_plan_heat(s, lv);
+            if (!s->loads_dev14) s->loads_dev14 = s->mem.alloc<double>(14);
+            launch_loads_viscous(s, level, s->loads_dev14, true);
+            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev14, sizeof(got), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            HIP_CHECK(hipGetLastError());
+        }
+        std::memcpy(out14, got, sizeof(got));
+    });
+}
+
+int mgcfd_run_cycles_loads_heat(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
+{
+    REQUIRE(s); REQUIRE(loads_out);
+    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out, true, true);
+}
+
+int mgcfd_wall_heat(mgcfd_solver *s, int level, int64_t *node_ids, double *out)
+{
+    REQUIRE(s); REQUIRE(out);
+    return guarded([&] {
+        wall_table(s, level, node_ids, out, MGCFD_WALL_HEAT_COLUMNS, [&](DeviceLevel &lv, WallPlan &) {
+            WallPlan &wp = wall_plan_heat(s, lv);
+            const bool viscous = s->viscous_on(level);
+            if (viscous) launch_wall_stress(s, level);
+            WallDistribution a;
+            a.wn = wp.wn; a.rec = lv.wall_rec; a.p_inf = s->p_inf; a.sw = viscous ? wp.sw : nullptr; a.out = wp.heat;
+            launch_wall_heat(s->stream, lv.dp.stride, lv.q, a);
+            return wp.heat;
+        });
+    });
+}
+
+// Diagnostic: mean GPU time of `launches` back-to-back launches of the isothermal wall launch (kind 0), the adiabatic one (1) —
+// both on the level's second state buffer, so the state stays — the heat-flux launch (2: it adds into fluxes[], accumulating),
+// the fourteen-column loads (3) or k_wall_heat (4), as mgcfd_bench_viscous times its launches.
+int mgcfd_bench_wall_heat(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        loads_require_whole(s);
+        if (!s->viscous_on(level) || !s->visc_wall) throw std::invalid_argument("the viscous terms with a no-slip wall are off on this level: switch them on first (mgcfd_set_viscous)");
+        if (kind < 0 || kind > 4) throw std::invalid_argument("wall heat launch kind: 0 isothermal wall, 1 adiabatic wall, 2 heat-flux wall, 3 fourteen-column loads, 4 heat table");
+        if (lv.n_wall_rec == 0) throw std::invalid_argument("the level has no solid-wall edge");
+        require_no_sweep_under_way(s, "wall heat");
+        loads_upload_ref(s, nullptr);
+        WallPlan &wp = wall_plan_heat(s, lv);
+        if (!s->loads_dev14) s->loads_dev14 = s->mem.alloc<double>(14);
+        const double ew = s->wt_mode == MGCFD_WALL_ISOTHERMAL ? s->wt_ew : 1.0 / (1.4 - 1.0);
+        const double qw = s->wt_mode == MGCFD_WALL_HEAT_FLUX ? s->wt_value : 1.0;
+        DeviceOwner local;
+        const double *area = lv.wall_area;
+        if (kind == 2 && !area) {
+            std::vector<int32_t> nodes(static_cast<size_t>(lv.n_visc_wall));
+            HIP_CHECK(hipMemcpy(nodes.data(), lv.visc_wall, sizeof(int32_t) * nodes.size(), hipMemcpyDeviceToHost));
+            area = local.upload(wall_areas(lv.info, lv.edges, lv.plan.new_of_old, nodes));
+        }
+        if (kind == 2) s->settle_fluxes(lv);
+        launch_loads_viscous(s, level, s->loads_dev14, true);
+        WallDistribution a;
+        a.wn = wp.wn; a.rec = lv.wall_rec; a.p_inf = s->p_inf; a.sw = wp.sw; a.out = wp.heat;
+        *avg_seconds = s->timed_launches(launches, [&] {
+            if (kind == 0) launch_viscous_wall_isothermal(s->stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, ew, lv.q_alt, nullptr, nullptr, nullptr);
+            else if (kind == 1) launch_viscous_wall(s->stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, lv.q_alt, nullptr, nullptr, nullptr);
+            else if (kind == 2) launch_wall_heat_flux(s->stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, area, qw, lv.fluxes);
+            else if (kind == 3) launch_loads_twelve(s, level, s->loads_dev14, true);
+            else launch_wall_heat(s->stream, lv.dp.stride, lv.q, a);
+        });
+        if (kind == 2) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
+        HIP_CHECK(hipStreamSynchronize(s->stream));         // (before the local area goes)
+    });
+}
+
 // ---- wall distance, wall spacing, wall damping (INTEGRATION.md "Wall distance") ----
 // what every call below that computes or frees refuses: a rank holds part of the wall only
 static void wall_distance_require_whole(const mgcfd_solver *s)
@@ -5885,15 +6078,18 @@ static void dual_begin_step(mgcfd_solver *s)
 int mgcfd_dual_time_begin_step(mgcfd_solver *s) { OP(dual_begin_step(s)); }
 // friction (mgcfd_advance_loads_viscous): rows of twelve, every step's launches store into a row of the twelve-wide history on
 // the device and the rows are read back when it is full and at the end
-static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double *ref_point, bool friction)
+// heat (with friction: mgcfd_advance_loads_heat): rows of fourteen in the fourteen-wide history
+static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double *ref_point, bool friction,
+                        bool heat = false)
 {
     REQUIRE(s);
-    const size_t width = friction ? 12 : 6;
+    const size_t width = heat ? 14 : (friction ? 12 : 6);
     int held = 0;                               // history rows not yet read back, the last of them row `step`
     auto read_rows = [&](int step) {
         if (held == 0) return int(MGCFD_OK);
         return guarded([&] {
-            HIP_CHECK(hipMemcpyAsync(loads_out + size_t(step + 1 - held) * 12, s->loads_ring12, sizeof(double) * 12 * size_t(held), hipMemcpyDeviceToHost, s->stream));
+            HIP_CHECK(hipMemcpyAsync(loads_out + size_t(step + 1 - held) * width, heat ? s->loads_ring14 : s->loads_ring12, sizeof(double) * width * size_t(held),
+                                     hipMemcpyDeviceToHost, s->stream));
             HIP_CHECK(hipStreamSynchronize(s->stream));
             held = 0;
         });
@@ -5907,9 +6103,9 @@ static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double 
         if (loads_out && friction) {
             s->use_device();
             loads_upload_ref(s, ref_point);
-            ensure_loads_ring12(s);
-            if (s->L[0].n_wall_rec > 0) wall_plan(s, s->L[0]);
-            else std::fill(loads_out, loads_out + size_t(steps) * 12, 0.0);         // (no solid wall: zeros, nothing launched)
+            if (heat) ensure_loads_ring14(s); else ensure_loads_ring12(s);
+            if (s->L[0].n_wall_rec > 0) { if (heat) wall_plan_heat(s, s->L[0]); else wall_plan(s, s->L[0]); }
+            else std::fill(loads_out, loads_out + size_t(steps) * width, 0.0);      // (no solid wall: zeros, nothing launched)
         }
         s->dual_invalid_step = -1;
     });
@@ -5921,7 +6117,7 @@ static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double 
         if (rc == MGCFD_OK) rc = run_cycles_impl(s, cycles_per_step, rms, nullptr, nullptr);
         if (rc == MGCFD_OK && loads_out && !friction) rc = mgcfd_surface_loads(s, 0, ref_point, loads_out + size_t(step) * 6);
         if (rc == MGCFD_OK && loads_out && friction && s->L[0].n_wall_rec > 0) {
-            rc = guarded([&] { s->use_device(); launch_loads_viscous(s, 0, s->loads_ring12 + size_t(held) * 12); });
+            rc = guarded([&] { s->use_device(); launch_loads_viscous(s, 0, (heat ? s->loads_ring14 : s->loads_ring12) + size_t(held) * width, heat); });
             if (rc == MGCFD_OK) held++;
             if (rc == MGCFD_OK && (held == mgcfd_solver::kRmsRing || step + 1 == steps)) rc = read_rows(step);
         }
@@ -5945,6 +6141,11 @@ int mgcfd_advance_loads_viscous(mgcfd_solver *s, int steps, int cycles_per_step,
 {
     REQUIRE(loads_out);
     return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, true);
+}
+int mgcfd_advance_loads_heat(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
+{
+    REQUIRE(loads_out);
+    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, true, true);
 }
 
 } // extern "C"

@@ -5,5 +5,5 @@
 """
 from . import meshgen  # noqa: F401
 from .api import (EXPORTED_SYMBOLS, LIB_PATH, LOOPS, Group, MgcfdError, Mesh, Solver,  # noqa: F401
-                  free_stream_constants, generated_to_levels, live_device_resources, load_coefficients, load_library, plan_audit,
+                  free_stream_constants, free_stream_temperature, generated_to_levels, heat_coefficients, live_device_resources, load_coefficients, load_library, plan_audit,
                   rccl_unique_id, surface_coefficients, viscosity_from_reynolds, wall_yplus)

@@ -226,6 +226,14 @@ _SIGNATURES = [
     ("mgcfd_set_sa_free_stream", C.c_int, [_vp, C.c_double, C.c_int]),
     ("mgcfd_get_sa_free_stream", C.c_int, [_vp, C.POINTER(C.c_double)]),
     ("mgcfd_bench_sa", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_wall_temperature", C.c_int, [_vp, C.c_int, C.c_double]),
+    ("mgcfd_get_wall_temperature", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("mgcfd_free_stream_temperature", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("mgcfd_surface_loads_heat", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_run_cycles_loads_heat", C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_advance_loads_heat", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    ("mgcfd_wall_heat", C.c_int, [_vp, C.c_int, _vp, _vp]),
+    ("mgcfd_bench_wall_heat", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_cycle", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_get_cycle", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_run_cycles_from", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -443,6 +451,38 @@ _ALL_EDDY_MODES = {**_EDDY_MODES, **_TRANSPORTED_EDDY_MODES}
 SA_RATIO = 3.0                                      # MGCFD_SA_RATIO
 
 
+WALL_HEAT_COLUMNS = 3     # MGCFD_WALL_HEAT_COLUMNS: h | T | area
+_WALL_MODES = {"adiabatic": 0, "isothermal": 1, "heat-flux": 2}      # MGCFD_WALL_*
+_GAMMA = 1.4
+
+
+def free_stream_temperature(ff17):
+    """Host only (mgcfd_free_stream_temperature): ``(t_static, t_total)`` of the far field ``ff17`` in the solver's units,
+    ``T = p / rho`` and ``t_total = t_static * (1 + 0.2 M^2)``."""
+    lib = load_library()
+    ff = np.ascontiguousarray(ff17, dtype=np.float64).reshape(17)
+    ts, tt = C.c_double(), C.c_double()
+    _check(lib, lib.mgcfd_free_stream_temperature(_ptr(ff), C.byref(ts), C.byref(tt)))
+    return ts.value, tt.value
+
+
+def heat_coefficients(ff17, table, t_wall=None):
+    """Host only: ``(qw [n], St [n])`` of a heat table ``table [n, 3]`` (Solver.wall_heat) against the far field ``ff17``: the
+    wall heat flux ``qw = h / area`` (positive heats the fluid) and the Stanton number
+    ``St = qw / (rho_inf |V_inf| cp (T_total - Tw))`` with ``cp = GAMMA / (GAMMA - 1)`` and ``Tw = t_wall``, or the node's own
+    ``T`` where ``t_wall`` is None."""
+    ff = np.asarray(ff17, dtype=np.float64).reshape(17)
+    v = ff[1:4] / ff[0]
+    speed = float(np.sqrt(v @ v))
+    _, t_total = free_stream_temperature(ff)
+    tab = np.asarray(table, dtype=np.float64).reshape(-1, WALL_HEAT_COLUMNS)
+    tw = tab[:, 1] if t_wall is None else np.float64(t_wall)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        qw = tab[:, 0] / tab[:, 2]
+        st = qw / (ff[0] * speed * (_GAMMA / (_GAMMA - 1.0)) * (t_total - tw))
+    return qw, st
+
+
 def viscosity_from_reynolds(ff17, reynolds: float, ref_length: float = 1.0) -> float:
     """Host only (mgcfd_viscosity_from_reynolds): ``mu = rho_inf * |V_inf| * ref_length / reynolds`` for the far field ``ff17``
     (Solver.far_field(), free_stream_constants)."""
@@ -624,26 +664,30 @@ class Solver:
     def smooth(self, l: int, sweeps: int = 1):
         self._c(self.lib.mgcfd_smooth(self.handle, l, sweeps))
 
-    def run_cycles(self, cycles: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0), friction: bool = False):
+    def run_cycles(self, cycles: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0), friction: bool = False, heat: bool = False):
         """The RMS of every cycle; with ``loads=True`` also the level-0 surface loads at the end of every cycle:
         ``(rms, loads[cycles, 6])`` (Fx Fy Fz Mx My Mz about ``ref_point``; mgcfd_run_cycles_loads).  With ``friction=True`` as
-        well the rows are twelve wide, the pressure six then the friction six (mgcfd_run_cycles_loads_viscous)."""
+        well the rows are twelve wide, the pressure six then the friction six (mgcfd_run_cycles_loads_viscous); with ``heat=True``
+        fourteen wide, the heat rate ``Q`` and the wall area ``A`` behind the twelve (mgcfd_run_cycles_loads_heat)."""
         rms = np.zeros(max(cycles, 1))
         if not loads:
             self._c(self.lib.mgcfd_run_cycles(self.handle, cycles, _ptr(rms)))
             return rms[:cycles]
-        hist = np.zeros((max(cycles, 1), 12 if friction else 6))
+        hist = np.zeros((max(cycles, 1), 14 if heat else 12 if friction else 6))
         ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
-        call = self.lib.mgcfd_run_cycles_loads_viscous if friction else self.lib.mgcfd_run_cycles_loads
+        call = (self.lib.mgcfd_run_cycles_loads_heat if heat else
+                self.lib.mgcfd_run_cycles_loads_viscous if friction else self.lib.mgcfd_run_cycles_loads)
         self._c(call(self.handle, cycles, _ptr(ref), _ptr(rms), _ptr(hist)))
         return rms[:cycles], hist[:cycles]
 
-    def surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0), friction: bool = False) -> np.ndarray:
+    def surface_loads(self, level: int, ref_point=(0.0, 0.0, 0.0), friction: bool = False, heat: bool = False) -> np.ndarray:
         """Fx Fy Fz Mx My Mz: the pressure loads on level ``level``'s solid walls in its current state (mgcfd_surface_loads).
-        ``friction=True``: twelve numbers, those six and then the friction force and moment (mgcfd_surface_loads_viscous)."""
-        out = np.zeros(12 if friction else 6)
+        ``friction=True``: twelve numbers, those six and then the friction force and moment (mgcfd_surface_loads_viscous).
+        ``heat=True``: fourteen, the twelve and then the heat rate ``Q`` the fluid receives from the wall and the wall's area ``A``
+        (mgcfd_surface_loads_heat)."""
+        out = np.zeros(14 if heat else 12 if friction else 6)
         ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
-        call = self.lib.mgcfd_surface_loads_viscous if friction else self.lib.mgcfd_surface_loads
+        call = self.lib.mgcfd_surface_loads_heat if heat else self.lib.mgcfd_surface_loads_viscous if friction else self.lib.mgcfd_surface_loads
         self._c(call(self.handle, level, _ptr(ref), _ptr(out)))
         return out
 
@@ -659,6 +703,35 @@ class Solver:
         ids, out = np.zeros(max(n, 1), dtype=np.int64), np.zeros((max(n, 1), WALL_COLUMNS))
         self._c(self.lib.mgcfd_wall_distribution(self.handle, level, _ptr(ids), _ptr(out)))
         return ids[:n], out[:n]
+
+    def wall_heat(self, level: int):
+        """``(ids [n], table [n, 3])`` of level ``level``'s wall nodes in its current state (mgcfd_wall_heat): the original ids,
+        ascending, and per node ``h | T | area`` — the heat rate the fluid receives through the node's wall faces, ``T = p / rho``
+        and the area of those faces.  ``heat_coefficients`` turns the table into the wall heat flux and the Stanton number."""
+        n = self.wall_node_count(level)
+        ids, out = np.zeros(max(n, 1), dtype=np.int64), np.zeros((max(n, 1), WALL_HEAT_COLUMNS))
+        self._c(self.lib.mgcfd_wall_heat(self.handle, level, _ptr(ids), _ptr(out)))
+        return ids[:n], out[:n]
+
+    def set_wall_temperature(self, mode="adiabatic", value: float = 0.0):
+        """The thermal condition of the no-slip wall (mgcfd_set_wall_temperature): ``"adiabatic"`` (the default), ``"isothermal"``
+        with ``value`` the wall temperature in the solver's units (``T = p / rho``) or ``"heat-flux"`` with ``value`` the heat flux
+        into the fluid.  Kept like the viscosity model; in effect on the levels ``set_viscous`` covers while its ``wall`` is 1."""
+        self._c(self.lib.mgcfd_set_wall_temperature(self.handle, int(_WALL_MODES.get(mode, mode)), float(value)))
+
+    def wall_temperature(self):
+        """``(mode, value)`` (mgcfd_get_wall_temperature); the mode by name."""
+        m, v = C.c_int(), C.c_double()
+        self._c(self.lib.mgcfd_get_wall_temperature(self.handle, C.byref(m), C.byref(v)))
+        return {i: k for k, i in _WALL_MODES.items()}[m.value], v.value
+
+    def bench_wall_heat(self, l: int, kind: int, launches: int) -> float:
+        """Mean GPU seconds of one launch of ``kind`` (0 the isothermal wall launch, 1 the adiabatic one, 2 the heat-flux launch, 3
+        the fourteen-column loads kernel, 4 the heat table's kernel) over ``launches`` back-to-back launches
+        (mgcfd_bench_wall_heat); level ``l`` must be viscous with no-slip walls."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_wall_heat(self.handle, l, kind, launches, C.byref(t)))
+        return t.value
 
     def wall_stress(self, level: int):
         """Diagnostic: ``(ids [n], Sw [n, 12])``, the wall nodes' stresses of a viscous level's current state (mgcfd_wall_stress)."""
@@ -921,17 +994,20 @@ class Solver:
         """A physical step begins: Wn1 <- Wn, Wn <- variables on every level (mgcfd_dual_time_begin_step)."""
         self._c(self.lib.mgcfd_dual_time_begin_step(self.handle))
 
-    def advance(self, steps: int, cycles_per_step: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0), friction: bool = False):
+    def advance(self, steps: int, cycles_per_step: int, loads: bool = False, ref_point=(0.0, 0.0, 0.0), friction: bool = False,
+                heat: bool = False):
         """``steps`` physical steps of ``begin_step`` + ``cycles_per_step`` V-cycles (mgcfd_advance): the RMS of every cycle
         ``[steps, cycles_per_step]``; with ``loads=True`` also the level-0 surface loads at the end of every physical step:
         ``(rms, loads[steps, 6])``.  An invalid state raises MgcfdError with ``.rms``, ``.loads`` (NaN from the failing cycle on)
         and ``.step`` (the physical step it was found in).  ``loads=True, friction=True``: rows of twelve, the pressure six then
-        the friction six (mgcfd_advance_loads_viscous)."""
+        the friction six (mgcfd_advance_loads_viscous); ``loads=True, heat=True``: rows of fourteen, ``Q`` and ``A`` behind them
+        (mgcfd_advance_loads_heat)."""
+        heat = bool(loads and heat)
         friction = bool(loads and friction)
         rms = np.zeros(max(steps * cycles_per_step, 1))
-        out = np.zeros((max(steps, 1), 12 if friction else 6))
+        out = np.zeros((max(steps, 1), 14 if heat else 12 if friction else 6))
         ref = np.ascontiguousarray(ref_point, dtype=np.float64).reshape(3)
-        call = self.lib.mgcfd_advance_loads_viscous if friction else self.lib.mgcfd_advance
+        call = self.lib.mgcfd_advance_loads_heat if heat else self.lib.mgcfd_advance_loads_viscous if friction else self.lib.mgcfd_advance
         rc = call(self.handle, int(steps), int(cycles_per_step), _ptr(rms), _ptr(out) if loads else None, _ptr(ref))
         if rc in (4, 5, 6):
             # an invalid state: the error carries what the call filled (NaN from the failing cycle on) and the physical step
@@ -948,7 +1024,8 @@ class Solver:
 
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
-              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None, wall_damping=None) -> List[dict]:
+              residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None, wall_damping=None,
+              wall_temperature=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
@@ -959,7 +1036,10 @@ class Solver:
         ``viscous=(mu, prandtl, wall, cfl_v, levels)`` or a dict of ``set_viscous``'s keywords (``set_viscous``) and
         ``viscosity_model=(law, t_ref, s, eddy, cs, prandtl_t)`` or a dict of ``set_viscosity_model``'s keywords; a ``t_ref`` of
         None is then the far field's of the solver as the call finds it; ``wall_damping=(on, kappa)`` or a dict of
-        ``set_wall_damping``'s keywords likewise (``set_wall_damping``)."""
+        ``set_wall_damping``'s keywords likewise (``set_wall_damping``), and ``wall_temperature=(mode, value)`` or a dict of
+        ``set_wall_temperature``'s keywords (``set_wall_temperature``)."""
+        if wall_temperature is not None:
+            self.set_wall_temperature(**wall_temperature) if isinstance(wall_temperature, dict) else self.set_wall_temperature(*wall_temperature)
         if wall_damping is not None:
             self.set_wall_damping(**wall_damping) if isinstance(wall_damping, dict) else self.set_wall_damping(*wall_damping)
         if viscosity_model is not None:
