@@ -581,8 +581,8 @@ int mgcfd_full_multigrid(mgcfd_solver *s, const int *cycles, double *rms_out);
  * or attached to a group or as a rank.  While it is on, mgcfd_sweep_begin*, mgcfd_sweep_flux0, mgcfd_sweep_stage and
  * mgcfd_sweep_end* return MGCFD_ERR_ARG, and mgcfd_group_create and mgcfd_rank_attach_* refuse the solver.
  * Friction in the surface loads: mgcfd_surface_loads_viscous and its neighbours (mgcfd_surface_loads stays the pressure loads).
- * Out of scope: an edge-direction correction of
- * the face gradient (it needs node coordinates on the device); transported turbulence models (variable viscosity: mgcfd_set_viscosity_model); viscous flux through
+ * The face gradient is the plain average of the two node gradients unless mgcfd_set_face_gradient selects the corrected one.
+ * Out of scope: transported turbulence models (variable viscosity: mgcfd_set_viscosity_model); viscous flux through
  * far-field faces; levels split over ranks; graphs and fused stages with viscosity on.
  * The weights are used as the solver holds them: on meshes whose variant makes the reference rescale them at load (every
  * variant but fvcorr) the viscous terms inherit that rescaling as the inviscid ones do; physical statements are made on
@@ -842,7 +842,7 @@ int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *
  * coordinates; a solver made by mgcfd_create_partitioned* or attached to a group or as a rank; while a kernel-granular sweep is
  * under way.
  * Out of scope: SA-neg, ft2, trip terms, rotation corrections, DES lengths; transport on coarse levels; nt under dual time, in
- * the residual smoothing or the FAS forcing; far-field nt flux; an edge-direction correction of the face gradient.
+ * the residual smoothing or the FAS forcing; far-field nt flux.
  * --------------------------------------------------------------------------------- */
 #define MGCFD_EDDY_SPALART_ALLMARAS 4         /* (3 is left unassigned: mgcfd_set_viscosity_model has always refused it, and callers rely on that) */
 #define MGCFD_ARR_SA_NU_TILDE 17
@@ -906,6 +906,40 @@ int mgcfd_wall_heat(mgcfd_solver *s, int level, int64_t *node_ids, double *out /
  * heat-flux launch (2), the fourteen-column loads (3) or k_wall_heat (4) on a no-slip viscous level with solid walls, as
  * mgcfd_bench_viscous times its launches.  Kinds 0 and 2 take the value in effect, or 1.0 where the mode is another. */
 int mgcfd_bench_wall_heat(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
+ * Corrected face gradients for the viscous and Spalart-Allmaras diffusion.  No reference counterpart; INTEGRATION.md "Corrected
+ * face gradients" holds the definition, line by line (every operation one IEEE-754 double operation, never contracted whatever
+ * MGCFD_OPT_EXACT says).  The averaged face gradient turns the Laplacian into a wide stencil on a uniform lattice and damps no
+ * odd-even mode; MGCFD_FACE_GRADIENT_CORRECTED replaces its along-edge component by the two-point difference, as a correction
+ * added to the fluxes directly behind F = F + V:  F[1..3] += Vc,  F[4] = (F[4] + Wk) + Hc  (the heat-flux wall's launch follows),
+ * and under the Spalart-Allmaras model Qd + Qdc stands where Qd stood.  Off by default (a solver that never selects it launches
+ * and computes what it did); kept like the viscosity model: either setter may come first, the mode survives the terms going
+ * off, and it is in effect on the levels mgcfd_set_viscous covers.  Such a level holds G, me, kap [14][stride] and its
+ * coordinates [3][stride] on the device exactly while the mode is in effect on it.  Two launches per viscous-flux launch
+ * (k_face_gradient_nodes_tile directly behind the stress launch, k_face_gradient_correction_tile directly behind the viscous-flux launch) on every
+ * path: the sweeps, mgcfd_compute_fluxes, mgcfd_compute_flux_edge and FAS's total residual.
+ * The corrected operator is stiffer: callers that name no cfl_v take MGCFD_VISCOUS_CFL_CORRECTED under the mode
+ * (mgcfd_set_viscous itself takes what it is given).
+ * MGCFD_ARR_VISCOUS_GRADIENT [nel][12] = G[u][xyz] G[v][xyz] G[w][xyz] G[T][xyz] of the last such launch: read-only, on covered
+ * levels while the mode is in effect.
+ * The setter synchronises and drops captured graphs.  MGCFD_ERR_ARG, and nothing changed: an unknown mode; a covered level
+ * created without coordinates (checked by whichever setter makes the mode effective); the corrected mode on a solver made by
+ * mgcfd_create_partitioned* or attached to a group or as a rank; while a kernel-granular sweep is under way.
+ * Unchanged: the node gradients, S and the wall-stress pass; the friction and heat loads and the wall tables; coarse-level SA
+ * (no transport there); the viscous step limit's formula.
+ * Out of scope: correcting the wall-stress pass and the loads; viscous or nt flux through boundary faces; partitioned levels,
+ * groups and ranks; graphs and fused stages with the terms on; other non-orthogonal correction variants.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_FACE_GRADIENT_AVERAGED 0
+#define MGCFD_FACE_GRADIENT_CORRECTED 1
+#define MGCFD_VISCOUS_CFL_CORRECTED 0.2
+#define MGCFD_ARR_VISCOUS_GRADIENT 19
+int mgcfd_set_face_gradient(mgcfd_solver *s, int mode);
+int mgcfd_get_face_gradient(const mgcfd_solver *s, int *mode);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of the node-gradient launch (kind 0) or the correction launch
+ * (kind 1; the level's fluxes keep accumulating: numbers, not a state) on a level the mode is in effect on, as
+ * mgcfd_bench_viscous times its launches. */
+int mgcfd_bench_face_gradient(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

@@ -188,6 +188,24 @@ struct SaStep {
     double cfl_v = 0.0;
     double rk_div = 1.0;                      // double(RK+1-j)
 };
+// ... and pass 2 under the corrected face gradient (mgcfd_set_face_gradient): an argument type of its own, so that every kernel
+// that takes SaStep keeps its arguments
+struct SaStepCorrected : SaStep {
+    const double *x = nullptr;                // [3][stride] the level's coordinates as given at creation
+};
+
+// The two launches of the corrected face gradient (kernels_face_gradient.hip: k_face_gradient_nodes_tile,
+// k_face_gradient_correction_tile; mgcfd_set_face_gradient): the first writes g from w behind the stress launch, the second reads
+// w, g and x and adds the correction into components 1..4 of fluxes behind the viscous-flux launch.
+struct FaceGradientStep {
+    const double *w = nullptr;                // the stage's input state W [5][stride]: what the fluxes were computed from
+    double *g = nullptr;                      // [14][stride]: G[u][xyz] G[v] G[w] G[T] | me | kap per node
+    const double *x = nullptr;                // [3][stride] the level's coordinates as given at creation
+    const double *volumes = nullptr;          // [stride]
+    double *fluxes = nullptr;                 // the stage's fluxes F (+ C + V) [5][stride] (correction only)
+    double mu = 0.0, kappa = 0.0;             // as ViscousStep's
+    ViscosityModel model;                     // the first launch only; mut is read as it stands behind the stress launch
+};
 
 // The physical-time source of dual time stepping (kernels.hip: k_time_step_src, k_dual_source; mgcfd_set_dual_time):
 //   src = vol * ((3 (W - Wn) - (Wn - Wn1)) / (2 dt))   order 2 (BDF2);   src = vol * ((W - Wn) / dt)   order 1 (BDF1, Wn1 not read)

@@ -117,5 +117,5 @@ void launch_fas_add_forcing(hipStream_t, int64_t stride, double *fluxes, const d
 }
 
 // The rule: a launcher has two flavours exactly if MGCFD_FLAVOURED_LAUNCHERS lists it (launch_diag_fast_math beside the
-// list: fast only).  Everything else exists once, in kernels_plain.hip (the Spalart-Allmaras model's: kernels_sa.hip, kernels_sa.hpp; the wall thermal conditions': kernels_wall_heat.hip, kernels_wall_heat.hpp), compiled with -ffp-contract=off: never contracted,
+// list: fast only).  Everything else exists once, in kernels_plain.hip (the Spalart-Allmaras model's: kernels_sa.hip, kernels_sa.hpp; the wall thermal conditions': kernels_wall_heat.hip, kernels_wall_heat.hpp; the corrected face gradient's: kernels_face_gradient.hip, kernels_face_gradient.hpp), compiled with -ffp-contract=off: never contracted,
 // whichever flavour the solver runs.  So an `exact::` or `fast::` at a call site is always a deliberate choice of flavour.

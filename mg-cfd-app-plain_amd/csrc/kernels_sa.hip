@@ -1,6 +1,8 @@
 // kernels_sa.hip — the kernels of the Spalart-Allmaras model with their launchers (kernels_sa.hpp: the prototypes in namespace
 // mgcfd).  Compiled ONCE, with -ffp-contract=off, as kernels_plain.hip is: nothing here is ever contracted, whichever flavour the
 // solver runs, so what these kernels produce is a bitwise function of their input.
+#include <type_traits>
+
 #include "kernel_device.hpp"
 #include "kernels_sa.hpp"
 
@@ -124,15 +126,19 @@ k_sa_gradient_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int6
     a.mut[i] = present ? mut : 0.0;
 }
 
-template <bool TAIL>
-__global__ void __launch_bounds__(kBlock, 4)
+// CORR: under the corrected face gradient (mgcfd_set_face_gradient) the coordinates are staged too (eleven fields, 49,280 B) and
+// Qdc, the along-edge correction of the diffusion, is summed beside Qd: STEP = SaStepCorrected.  STEP = SaStep is the averaged kernel.
+template <bool TAIL, class STEP>
+__global__ void __launch_bounds__(kBlock, (std::is_same<STEP, SaStepCorrected>::value ? 3 : 4))
 k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
                     const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
                     const double *__restrict__ w, const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf,
-                    TailPlan tp, SaStep a)
+                    TailPlan tp, STEP a)
 {
 #pragma clang fp contract(off)
-    __shared__ double rec[8][kSmoothRow];                              // u, v, w, nt, nu, G[nt][x], G[nt][y], G[nt][z]
+    constexpr bool CORR = std::is_same<STEP, SaStepCorrected>::value;
+    constexpr int NF = CORR ? 11 : 8;
+    __shared__ double rec[NF][kSmoothRow];                             // u, v, w, nt, nu, G[nt][x], G[nt][y], G[nt][z] (CORR: x, y, z)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const unsigned t = xcd_contiguous_block(blockIdx.x, n_tiles);
@@ -145,17 +151,18 @@ k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int
     const int32_t n_int = (TAIL ? tp.rows_main : rows_int)[slice];
     const int32_t ovf0 = tile_ovf_ptr[t];
     const int64_t hnode = hid >= 0 ? int64_t(hid) : i;                 // (no halo node: a copy of the own one in the unused slot)
-    struct Node { double f[8]; };
+    struct Node { double f[NF]; };
     auto load = [&](int64_t n) {
         const double rho = a.w[n];
         Node q;
         q.f[0] = a.w[stride + n] / rho; q.f[1] = a.w[2 * stride + n] / rho; q.f[2] = a.w[3 * stride + n] / rho; q.f[3] = a.nt[n];
         q.f[4] = a.grad[4 * stride + n]; q.f[5] = a.grad[n]; q.f[6] = a.grad[stride + n]; q.f[7] = a.grad[2 * stride + n];
+        if constexpr (CORR) { q.f[8] = a.x[n]; q.f[9] = a.x[stride + n]; q.f[10] = a.x[2 * stride + n]; }
         return q;
     };
     auto stage = [&](uint32_t slot, const Node &q) {
 #pragma unroll
-        for (int f = 0; f < 8; f++) rec[f][slot] = q.f[f];
+        for (int f = 0; f < NF; f++) rec[f][slot] = q.f[f];
     };
     const int64_t first_row = n_int > 0 ? row0 : 0;                    // (row 0 exists on every level; unused when n_int == 0)
     uint32_t c = nbr16[(first_row << 6) + lane];
@@ -169,7 +176,7 @@ k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int
     __syncthreads();
 
     const double nt_i = me.f[3], nu_i = me.f[4];
-    double qc = 0.0, qd = 0.0;
+    double qc = 0.0, qd = 0.0, qdc = 0.0;
     auto add = [&](uint32_t code, double hx, double hy, double hz) {
         const uint32_t s = code & kT16SlotMask;
         if (s == kT16Pad) return;
@@ -177,7 +184,7 @@ k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int
         if (s >= uint32_t(kTileCap)) ot = load(tile_ovf[ovf0 + int32_t(s) - kTileCap]);
         else {
 #pragma unroll
-            for (int f = 0; f < 8; f++) ot.f[f] = rec[f][s];
+            for (int f = 0; f < NF; f++) ot.f[f] = rec[f][s];
         }
         const double nx = -2.0 * hx, ny = -2.0 * hy, nz = -2.0 * hz;   // the rows hold -+0.5 e
         const double ub = 0.5 * (me.f[0] + ot.f[0]), vb = 0.5 * (me.f[1] + ot.f[1]), wb = 0.5 * (me.f[2] + ot.f[2]);
@@ -187,6 +194,15 @@ k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int
         const double nb = 0.5 * ((nu_i + nt_i) + (ot.f[4] + ot.f[3]));
         const double gxb = 0.5 * (me.f[5] + ot.f[5]), gyb = 0.5 * (me.f[6] + ot.f[6]), gzb = 0.5 * (me.f[7] + ot.f[7]);
         qd += nb * ((gxb * nx + gyb * ny) + gzb * nz);
+        if constexpr (CORR) {
+            const double dxx = ot.f[8] - me.f[8], dxy = ot.f[9] - me.f[9], dxz = ot.f[10] - me.f[10];
+            const double len = sqrt((dxx * dxx + dxy * dxy) + dxz * dxz);
+            if (len == 0.0) return;                                    // coincident nodes: nothing to Qdc
+            const double tx = dxx / len, ty = dxy / len, tz = dxz / len;
+            const double cnt = (ot.f[3] - nt_i) / len - ((gxb * tx + gyb * ty) + gzb * tz);
+            const double tn = (tx * nx + ty * ny) + tz * nz;
+            qdc += nb * (cnt * tn);
+        }
     };
     for (int32_t r = 0; r < n_int; r++) {                             // code and weights one row ahead of the sums
         const bool more = r + 1 < n_int;
@@ -228,7 +244,7 @@ k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int
     const double nd = nt_i / d_i;
     const double gg = (me.f[5] * me.f[5] + me.f[6] * me.f[6]) + me.f[7] * me.f[7];
     const double src = ((cb1 * st) * nt_i - (a.cw1 * fw) * (nd * nd)) + (cb2 * a.inv_sigma) * gg;
-    const double q = (qc + a.inv_sigma * qd) + vol * src;
+    const double q = (qc + a.inv_sigma * (CORR ? qd + qdc : qd)) + vol * src;
     double jac = ((2.0 * a.cw1) * fw) * (nt_i / (d_i * d_i)) - cb1 * st;
     jac = jac > 0.0 ? jac : 0.0;
     const double cap = (a.cfl_v * a.g[i]) / (a.ks * (nu_i + nt_i));
@@ -293,14 +309,17 @@ void launch_sa_gradient(hipStream_t st, const DevicePlan &p, const SaStep &a)
         hipLaunchKernelGGL((k_sa_gradient_tile<false>), dim3(p.n_tiles), dim3(kBlock), 0, st,
                            p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
 }
-void launch_sa_transport(hipStream_t st, const DevicePlan &p, const SaStep &a)
+void launch_sa_transport(hipStream_t st, const DevicePlan &p, const SaStep &a, const double *x)
 {
-    if (p.has_tail)
-        hipLaunchKernelGGL((k_sa_transport_tile<true>), dim3(p.n_tiles), dim3(kBlock), 0, st,
-                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
-    else
-        hipLaunchKernelGGL((k_sa_transport_tile<false>), dim3(p.n_tiles), dim3(kBlock), 0, st,
-                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
+    auto go = [&](auto tail, const auto &step) {
+        hipLaunchKernelGGL((k_sa_transport_tile<decltype(tail)::value, std::decay_t<decltype(step)>>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, step);
+    };
+    if (x) {                                                           // (the corrected face gradient: Qdc beside Qd)
+        SaStepCorrected c;
+        static_cast<SaStep &>(c) = a; c.x = x;
+        if (p.has_tail) go(std::true_type{}, c); else go(std::false_type{}, c);
+    } else { if (p.has_tail) go(std::true_type{}, a); else go(std::false_type{}, a); }
 }
 void launch_sa_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, const int32_t *child_ptr, const int32_t *child,
                         const double *fine_nt, double *coarse_nt, const SaStep &a)

@@ -98,6 +98,10 @@ struct Config {                       // the reference's `config` (src/Base/conf
     int wall_mode = 0;                // MGCFD_WALL_*
     double wall_value = 0.0;          // T, R or Q as given
     bool wall_ratio = false;          // ... it is R
+    // --face-gradient averaged|corrected (config key face_gradient; mgcfd_set_face_gradient): the face gradient of the viscous and
+    // Spalart-Allmaras diffusion.  Corrected without --viscous-cfl: MGCFD_VISCOUS_CFL_CORRECTED.  One GPU
+    int face_gradient = MGCFD_FACE_GRADIENT_AVERAGED;
+    bool face_gradient_given = false, viscous_cfl_given = false;
     bool loads_heat = false;          // --loads-heat: Q, A and the mean Stanton number behind the friction columns; qw, T, St in surface.* (one GPU)
     size_t loads_width() const { return loads_heat ? 14 : (loads_friction ? 12 : 6); }
     // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
@@ -149,6 +153,16 @@ bool parse_positive(const char *text, double *out)
     double v = 0.0;
     if (!parse_number(text, &v) || !(v > 0.0)) return false;
     *out = v;
+    return true;
+}
+
+// --face-gradient / face_gradient: "averaged" or "corrected"
+bool set_face_gradient(Config &c, const char *text)
+{
+    const std::string v(text ? text : "");
+    if (v != "averaged" && v != "corrected") return false;
+    c.face_gradient = v == "corrected" ? MGCFD_FACE_GRADIENT_CORRECTED : MGCFD_FACE_GRADIENT_AVERAGED;
+    c.face_gradient_given = true;
     return true;
 }
 
@@ -299,6 +313,7 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         double *dst = key == "viscosity" ? &c.viscosity : key == "reynolds" ? &c.reynolds : key == "ref_length" ? &c.ref_length : key == "prandtl" ? &c.prandtl : &c.viscous_cfl;
         if (parse_positive(value.c_str(), dst)) {
             if (key == "viscosity") c.viscosity_given = true; else if (key == "reynolds") c.reynolds_given = true; else c.viscous_extras_given = true;
+            if (key == "viscous_cfl") c.viscous_cfl_given = true;
         }
         else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
     }
@@ -331,6 +346,9 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         }
     }
     else if (key == "loads_heat") { if (value == "Y") c.loads_heat = true; }
+    else if (key == "face_gradient") {
+        if (!set_face_gradient(c, value.c_str())) { std::fprintf(stderr, "ERROR: face_gradient = '%s': expected averaged or corrected\n", value.c_str()); c.config_bad = true; }
+    }
     else if (key == "viscous_levels") {
         if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.viscous_levels)) c.viscous_extras_given = true;
         else { std::fprintf(stderr, "ERROR: viscous_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
@@ -431,6 +449,10 @@ void print_help()
         "                                   (config key wall_temperature_ratio)\n"
         "  --wall-heat-flux=Q               With --no-slip: the wall feeds the heat flux Q into the fluid, of either sign (config key\n"
         "                                   wall_heat_flux).  The three exclude each other\n"
+        "  --face-gradient=averaged|corrected  The face gradient of the viscous and Spalart-Allmaras diffusion: the average of the\n"
+        "                                   two node gradients (the default), or that with its along-edge component replaced by the\n"
+        "                                   two-point difference, which damps odd-even modes; corrected takes --viscous-cfl 0.2\n"
+        "                                   unless said otherwise (config key face_gradient).  Needs the viscous terms.  One GPU\n"
         "  --loads-heat                     With --loads-friction: surface_loads.* and polar.csv rows gain Q (the heat rate the fluid\n"
         "                                   receives from the wall), A (the wall's area) and St_mean; surface.* rows gain qw, T and\n"
         "                                   St (config key loads_heat = Y).  One GPU\n"
@@ -577,6 +599,7 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"wall-temperature-ratio", required_argument, nullptr, 1048},
         {"wall-heat-flux", required_argument, nullptr, 1049},
         {"loads-heat", no_argument, nullptr, 1054},
+        {"face-gradient", required_argument, nullptr, 1055},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -730,6 +753,7 @@ bool parse_arguments(int argc, char **argv, Config &c)
                     return false;
                 }
                 if (optc == 1031) c.viscosity_given = true; else if (optc == 1032) c.reynolds_given = true; else c.viscous_extras_given = true;
+                if (optc == 1035) c.viscous_cfl_given = true;
                 break;
             }
             case 1036: c.no_slip = true; c.viscous_extras_given = true; break;
@@ -795,6 +819,12 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 break;
             }
             case 1054: c.loads_heat = true; break;
+            case 1055:
+                if (!set_face_gradient(c, optarg)) {
+                    std::fprintf(stderr, "ERROR: --face-gradient=%s: expected averaged or corrected\n", optarg);
+                    return false;
+                }
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
@@ -854,6 +884,15 @@ bool parse_arguments(int argc, char **argv, Config &c)
         std::fprintf(stderr, "ERROR: the wall thermal conditions and --loads-heat run on one GPU only: not with --gpus N\n");
         return false;
     }
+    if (c.face_gradient_given && !(c.viscous() && c.viscous_levels > 0)) {
+        std::fprintf(stderr, "ERROR: --face-gradient needs the viscous terms (--viscosity MU or --reynolds RE): it is their face gradient\n");
+        return false;
+    }
+    if (c.face_gradient_given && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: --face-gradient runs on one GPU only: not with --gpus N\n");
+        return false;
+    }
+    if (c.face_gradient == MGCFD_FACE_GRADIENT_CORRECTED && !c.viscous_cfl_given) c.viscous_cfl = MGCFD_VISCOUS_CFL_CORRECTED;   // (the corrected operator is stiffer)
     if (c.dual_extras_given && !c.dual_given) {
         std::fprintf(stderr, "ERROR: --time-steps, --dual-time-clamp and --bdf-order need --physical-time-step DT (dual time stepping)\n");
         return false;
@@ -1400,6 +1439,7 @@ int main(int argc, char **argv)
     if (conf.jst_given && mgcfd_set_jst(solver, conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
     if (conf.viscous()) {
         double mu = 0.0;
+        if (conf.face_gradient_given && mgcfd_set_face_gradient(solver, conf.face_gradient) != MGCFD_OK) return fail("setting the face gradient");
         if (viscosity_of(conf, &mu) != MGCFD_OK || mgcfd_set_viscous(solver, mu, conf.prandtl, conf.no_slip ? 1 : 0, conf.viscous_cfl, conf.viscous_levels) != MGCFD_OK)
             return fail("setting the viscous terms");
         double t_ref = 0.0;

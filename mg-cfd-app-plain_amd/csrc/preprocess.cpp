@@ -1433,4 +1433,18 @@ std::vector<double> wall_areas(const mgcfd_level_desc &lvl, const std::vector<mg
     return area;
 }
 
+std::vector<double> permuted_coordinates(const std::vector<double> &coords, const std::vector<int32_t> &old_of_new, int64_t nel, int64_t stride)
+{
+    if (nel < 0 || stride < nel || coords.size() != 3 * static_cast<size_t>(nel) || old_of_new.size() < static_cast<size_t>(nel))
+        throw std::invalid_argument("permuted coordinates: the sizes do not fit the level");
+    const size_t st = static_cast<size_t>(stride);
+    std::vector<double> x(3 * st, 0.0);
+    for (int64_t n = 0; n < nel; n++) {
+        const int32_t o = old_of_new[static_cast<size_t>(n)];
+        if (o < 0 || o >= nel) throw std::invalid_argument("permuted coordinates: the numbering names a node out of range");
+        for (size_t c = 0; c < 3; c++) x[c * st + static_cast<size_t>(n)] = coords[3 * static_cast<size_t>(o) + c];
+    }
+    return x;
+}
+
 } // namespace mgcfd

@@ -203,6 +203,12 @@ WallRows build_wall_rows(const mgcfd_level_desc &lvl, const std::vector<mgcfd_ed
 std::vector<double> wall_areas(const mgcfd_level_desc &lvl, const std::vector<mgcfd_edge> &edges, const std::vector<int32_t> &new_of_old,
                                const std::vector<int32_t> &nodes);
 
+// The level's coordinates as the corrected face gradient's kernels read them (mgcfd_set_face_gradient): [3][stride], field c of
+// node n (the solver's numbering) = coords[3 * old_of_new[n] + c], +0.0 in the pad lanes n >= nel.  Throws std::invalid_argument
+// where the sizes do not fit (coords of 3 * nel doubles, old_of_new of at least nel entries, stride >= nel) or old_of_new names
+// a node outside [0, nel).
+std::vector<double> permuted_coordinates(const std::vector<double> &coords, const std::vector<int32_t> &old_of_new, int64_t nel, int64_t stride);
+
 // Edge-weight preconditioning exactly as the reference does before its loop
 // (src/Kernels/validation.cpp:28-75, src/euler3d_cpu_double.cpp:337-352).
 void adjust_and_dampen(const mgcfd_level_desc &lvl, int mesh_variant, std::vector<mgcfd_edge> &edges);

@@ -29,6 +29,7 @@
 
 #include "device_owner.hpp"
 #include "kernels.hpp"
+#include "kernels_face_gradient.hpp"
 #include "kernels_sa.hpp"
 #include "kernels_wall_heat.hpp"
 #include "mesh.hpp"
@@ -217,6 +218,9 @@ struct DeviceLevel {
     // the Spalart-Allmaras model, held while it is in effect on the level: nu_tilde [stride] and, on level 0, its value at the
     // sweep's start, the spare buffer a stage's pass 2 writes (swapped with sa_nt behind it) and sa_gradient [5][stride]
     double *sa_nt = nullptr, *sa_old = nullptr, *sa_spare = nullptr, *sa_grad = nullptr;
+    // the corrected face gradient (mgcfd_set_face_gradient), held while it is in effect on the level: G, me, kap [14][stride] and
+    // the coordinates in the solver's numbering [3][stride]
+    double *fg_g = nullptr, *fg_x = nullptr;
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while ordered_rms(): its RMS is summed in original numbering (settle_rms_order)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
@@ -445,7 +449,7 @@ struct mgcfd_solver {
     {
         if (l != 0 || !sa_on(l)) return;
         DeviceLevel &lv = level(l);
-        launch_sa_transport(stream, lv.dp, sa_step(lv, j));
+        launch_sa_transport(stream, lv.dp, sa_step(lv, j), lv.fg_x);   // (fg_x: held exactly while the corrected face gradient is in effect here)
         std::swap(lv.sa_nt, lv.sa_spare);
     }
     // behind a restriction into level `coarse`: nt averaged over the children, mut from it and the restricted state
@@ -474,6 +478,19 @@ struct mgcfd_solver {
         }
         const double kv = std::max(4.0 / 3.0, 1.4 / visc_prandtl);
         launch_viscous_clamp(stream, lv.info.nel, visc_cfl / (kv * visc_mu), lv.q, lv.visc_g, lv.step_factors);
+    }
+    // The face gradient of the diffusion terms (mgcfd_set_face_gradient; INTEGRATION.md "Corrected face gradients"): kept like the
+    // viscosity model; in effect on the levels the viscous terms cover.  Corrected: the node-gradient launch behind the stress
+    // launch and the correction launch behind the viscous-flux launch, wherever the two run.
+    int fg_mode = MGCFD_FACE_GRADIENT_AVERAGED;
+    bool fg_on(int l) const { return fg_mode == MGCFD_FACE_GRADIENT_CORRECTED && viscous_on(l); }
+    FaceGradientStep face_gradient_step(const DeviceLevel &lv) const
+    {
+        FaceGradientStep a;
+        a.w = lv.q; a.g = lv.fg_g; a.x = lv.fg_x; a.volumes = lv.volumes; a.fluxes = lv.fluxes;
+        a.mu = visc_mu; a.kappa = (visc_mu * 1.4) / ((1.4 - 1.0) * visc_prandtl);
+        a.model = viscosity_model(lv);
+        return a;
     }
     // Wall thermal conditions (mgcfd_set_wall_temperature; INTEGRATION.md "Wall thermal conditions"): kept like the viscosity
     // model; in effect on the levels the viscous terms cover while their wall is the no-slip one.  wt_ew = Tw / (GAMMA - 1.0).
@@ -798,7 +815,11 @@ struct mgcfd_solver {
             // viscous terms: S of the same state, then fluxes[1..4] += V, behind C (both passes keep row order in either flavour)
             const ViscousStep a = viscous_step(lv);
             k().viscous_stress(stream, lv.dp, a);
+            // the corrected face gradient: G, me, kap of the same state directly behind the stress launch (mut as it left it) ...
+            if (fg_on(l)) launch_face_gradient_nodes(stream, lv.dp, face_gradient_step(lv));
             k().viscous_flux(stream, lv.dp, a);
+            // ... and fluxes[1..4] += Vc, Wk, Hc directly behind F = F + V
+            if (fg_on(l)) launch_face_gradient_correction(stream, lv.dp, face_gradient_step(lv));
             wall_heat_flux(l);
         }
         if (dual_time()) lv.flux_in = lv.q;
@@ -2049,6 +2070,31 @@ static void settle_wall_areas(mgcfd_solver *s)
     }
 }
 
+// A setter about to store (visc_levels, mode) asks first: MGCFD_ERR_ARG with nothing changed where the corrected face gradient
+// would take effect on a level created without coordinates.
+static void require_face_gradient_possible(const mgcfd_solver *s, int visc_levels, int mode)
+{
+    if (mode != MGCFD_FACE_GRADIENT_CORRECTED) return;
+    for (int l = 0; l < visc_levels && l < static_cast<int>(s->L.size()); l++)
+        if (s->L[static_cast<size_t>(l)].coords.empty())
+            throw std::invalid_argument("face gradient: level " + std::to_string(l) + " was created without coordinates (the corrected gradient would take effect there)");
+}
+// G and the coordinates of a level are held exactly while the corrected face gradient is in effect on it: both setters call
+// this once their new state is stored.  A new G holds +0.0.
+static void settle_face_gradient(mgcfd_solver *s)
+{
+    for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
+        DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+        if (!s->fg_on(l)) { lv.mem.release(lv.fg_g); lv.mem.release(lv.fg_x); continue; }
+        if (lv.fg_g) continue;
+        const size_t stride = static_cast<size_t>(lv.dp.stride);
+        lv.fg_g = lv.mem.alloc<double>(14 * stride);
+        HIP_CHECK(hipMemsetAsync(lv.fg_g, 0, sizeof(double) * 14 * stride, s->stream));
+        lv.fg_x = lv.mem.upload(permuted_coordinates(lv.coords, lv.plan.old_of_new, lv.info.nel, lv.dp.stride));
+    }
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+}
+
 // ---- laminar viscous terms: viscosity, Prandtl number, wall condition, step limit and the levels they run on ----
 int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, double cfl_v, int levels)
 {
@@ -2064,6 +2110,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
         }
         require_damping_possible(s, levels, s->vm_eddy, s->wd_on);
         require_sa_possible(s, levels, s->vm_eddy);
+        require_face_gradient_possible(s, levels, s->fg_mode);
         quiesce(s, "viscous terms");
         const int n = std::min(levels, static_cast<int>(s->L.size()));
         for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
@@ -2101,6 +2148,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
         s->visc_wall = n > 0 ? wall : 0;
         settle_wall_areas(s);
         settle_viscosity_arrays(s, false);
+        settle_face_gradient(s);
         settle_rms_order(s);
         drop_look_ahead(s);
         // the no-slip condition holds from the start
@@ -2155,6 +2203,47 @@ int mgcfd_set_wall_temperature(mgcfd_solver *s, int mode, double value)
             }
         HIP_CHECK(hipStreamSynchronize(s->stream));
         HIP_CHECK(hipGetLastError());
+    });
+}
+// ---- the face gradient of the diffusion terms: averaged or corrected (INTEGRATION.md "Corrected face gradients") ----
+int mgcfd_set_face_gradient(mgcfd_solver *s, int mode)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (mode != MGCFD_FACE_GRADIENT_AVERAGED && mode != MGCFD_FACE_GRADIENT_CORRECTED)
+            throw std::invalid_argument("face gradient: mode must be MGCFD_FACE_GRADIENT_AVERAGED or MGCFD_FACE_GRADIENT_CORRECTED");
+        if (mode == MGCFD_FACE_GRADIENT_CORRECTED && (s->partitioned || s->comm))
+            throw std::invalid_argument("face gradient: not on a partitioned solver, a group member or a rank (the viscous terms do not run there)");
+        require_face_gradient_possible(s, s->visc_levels, mode);
+        quiesce(s, "face gradient");
+        s->fg_mode = mode;
+        settle_face_gradient(s);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_face_gradient(const mgcfd_solver *s, int *mode)
+{
+    REQUIRE(s);
+    if (mode) *mode = s->fg_mode;
+    return MGCFD_OK;
+}
+// Diagnostic: kind 0 the node-gradient launch, 1 the correction launch (fluxes keeps accumulating: numbers, not a state).
+int mgcfd_bench_face_gradient(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->fg_on(level)) throw std::invalid_argument("the corrected face gradient is not in effect on this level (mgcfd_set_face_gradient, mgcfd_set_viscous)");
+        if (kind < 0 || kind > 1) throw std::invalid_argument("face gradient launch kind: 0 node gradients, 1 correction");
+        s->settle_fluxes(lv);
+        const FaceGradientStep a = s->face_gradient_step(lv);
+        launch_face_gradient_nodes(s->stream, lv.dp, a);    // (every array holds a stage's numbers)
+        *avg_seconds = s->timed_launches(launches, [&] {
+            if (kind == 0) launch_face_gradient_nodes(s->stream, lv.dp, a);
+            else launch_face_gradient_correction(s->stream, lv.dp, a);
+        });
+        lv.fluxes_zero = false; lv.fluxes_stale = false;
     });
 }
 int mgcfd_get_wall_temperature(const mgcfd_solver *s, int *mode, double *value)
@@ -3109,6 +3198,10 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.sa_grad) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: level 0 while the Spalart-Allmaras model is in effect");
             *ncols = 5;
             return lv.sa_grad;
+        case MGCFD_ARR_VISCOUS_GRADIENT:
+            if (!lv.fg_g) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: the corrected face gradient is not in effect on this level (mgcfd_set_face_gradient, on a level mgcfd_set_viscous covers)");
+            *ncols = 12;
+            return lv.fg_g;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -3156,6 +3249,7 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SPALART_ALLMARAS)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under the Spalart-Allmaras model (formed from MGCFD_ARR_SA_NU_TILDE)");
         if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
+        if (which == MGCFD_ARR_VISCOUS_GRADIENT) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: read-only (every flux launch of the level overwrites it)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -3203,6 +3297,7 @@ int mgcfd_array_written(mgcfd_solver *s, int level, int which)
         if (which == MGCFD_ARR_EDDY_VISCOSITY && lv.eddy_mode == MGCFD_EDDY_SPALART_ALLMARAS)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under the Spalart-Allmaras model (formed from MGCFD_ARR_SA_NU_TILDE)");
         if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
+        if (which == MGCFD_ARR_VISCOUS_GRADIENT) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: read-only (every flux launch of the level overwrites it)");
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
         if (which == MGCFD_ARR_SA_NU_TILDE) { s->use_device(); s->sa_form(lv, false); }
@@ -5947,7 +6042,7 @@ int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *a
         launch_sa_gradient(s->stream, lv.dp, a);            // (every array holds a stage's numbers; the transport writes the spare buffer: nt stays)
         *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) launch_sa_gradient(s->stream, lv.dp, a);
-            else launch_sa_transport(s->stream, lv.dp, a);
+            else launch_sa_transport(s->stream, lv.dp, a, lv.fg_x);
         });
     });
 }

@@ -26,9 +26,9 @@ LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
        "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16,
-       "sa_nu_tilde": 17, "sa_gradient": 18}
+       "sa_nu_tilde": 17, "sa_gradient": 18, "viscous_gradient": 19}
 NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1,
-         "sa_nu_tilde": 1, "sa_gradient": 5}    # (every other array: NVAR)
+         "sa_nu_tilde": 1, "sa_gradient": 5, "viscous_gradient": 12}    # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -234,6 +234,9 @@ _SIGNATURES = [
     ("mgcfd_advance_loads_heat", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     ("mgcfd_wall_heat", C.c_int, [_vp, C.c_int, _vp, _vp]),
     ("mgcfd_bench_wall_heat", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_face_gradient", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_get_face_gradient", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("mgcfd_bench_face_gradient", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_cycle", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_get_cycle", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_run_cycles_from", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -443,6 +446,8 @@ def free_stream_constants(mach: float, alpha_deg: float) -> np.ndarray:
 
 
 VISCOUS_PRANDTL, VISCOUS_CFL = 0.72, 0.25         # MGCFD_VISCOUS_PRANDTL, MGCFD_VISCOUS_CFL
+VISCOUS_CFL_CORRECTED = 0.2                       # MGCFD_VISCOUS_CFL_CORRECTED
+_FACE_GRADIENTS = {"averaged": 0, "corrected": 1}  # MGCFD_FACE_GRADIENT_*
 SUTHERLAND_S, SMAGORINSKY_CS, PRANDTL_TURBULENT = 0.3831, 0.17, 0.9     # MGCFD_SUTHERLAND_S, MGCFD_SMAGORINSKY_CS, MGCFD_PRANDTL_TURBULENT
 _VISCOSITY_LAWS = {"constant": 0, "sutherland": 1}      # MGCFD_VISCOSITY_*
 _EDDY_MODES = {"none": 0, "field": 1, "smagorinsky": 2}   # MGCFD_EDDY_*
@@ -725,6 +730,28 @@ class Solver:
         self._c(self.lib.mgcfd_get_wall_temperature(self.handle, C.byref(m), C.byref(v)))
         return {i: k for k, i in _WALL_MODES.items()}[m.value], v.value
 
+    def set_face_gradient(self, mode="corrected"):
+        """The face gradient of the viscous and Spalart-Allmaras diffusion (mgcfd_set_face_gradient): ``"averaged"`` (the default:
+        the plain average of the two node gradients) or ``"corrected"`` (its along-edge component replaced by the two-point
+        difference, which damps the odd-even mode the averaged one cannot see).  Kept like the viscosity model; in effect on the
+        levels ``set_viscous`` covers, which must have come with coordinates.  The corrected operator is stiffer: a later
+        ``set_viscous`` that names no ``cfl_v`` takes ``VISCOUS_CFL_CORRECTED``.  Captured graphs are dropped.  Not on
+        partitioned solvers, group members or ranks."""
+        self._c(self.lib.mgcfd_set_face_gradient(self.handle, int(_FACE_GRADIENTS.get(mode, mode))))
+
+    def face_gradient(self) -> str:
+        """The mode in use by name (mgcfd_get_face_gradient)."""
+        m = C.c_int()
+        self._c(self.lib.mgcfd_get_face_gradient(self.handle, C.byref(m)))
+        return {v: k for k, v in _FACE_GRADIENTS.items()}[m.value]
+
+    def bench_face_gradient(self, l: int, kind, launches: int) -> float:
+        """Mean GPU seconds of one launch of the corrected face gradient's ``"nodes"`` (0) or ``"correction"`` (1) kernel on
+        level ``l``, where the mode must be in effect (mgcfd_bench_face_gradient)."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_face_gradient(self.handle, l, {"nodes": 0, "correction": 1}.get(kind, kind), launches, C.byref(t)))
+        return t.value
+
     def bench_wall_heat(self, l: int, kind: int, launches: int) -> float:
         """Mean GPU seconds of one launch of ``kind`` (0 the isothermal wall launch, 1 the adiabatic one, 2 the heat-flux launch, 3
         the fourteen-column loads kernel, 4 the heat table's kernel) over ``launches`` back-to-back launches
@@ -934,11 +961,14 @@ class Solver:
         return rms[:sum(c[1:])]
 
     # ---- laminar viscous terms ----
-    def set_viscous(self, mu: float, prandtl: float = VISCOUS_PRANDTL, wall: bool = False, cfl_v: float = VISCOUS_CFL, levels: int = 1):
+    def set_viscous(self, mu: float, prandtl: float = VISCOUS_PRANDTL, wall: bool = False, cfl_v: Optional[float] = None, levels: int = 1):
         """Laminar viscous terms on levels ``0 .. levels-1`` (mgcfd_set_viscous): the Navier-Stokes stresses and the heat flux at
         constant dynamic viscosity ``mu`` and Prandtl number ``prandtl`` added to every stage's fluxes, the step factors limited
         by ``cfl_v`` times the viscous step, and with ``wall=True`` a no-slip adiabatic condition on the solid walls (momentum
-        zero at their nodes).  ``levels=0`` switches them off.  Captured graphs are dropped.  Not on partitioned solvers or ranks."""
+        zero at their nodes).  ``levels=0`` switches them off.  Captured graphs are dropped.  Not on partitioned solvers or ranks.
+        ``cfl_v=None`` is ``VISCOUS_CFL``, or ``VISCOUS_CFL_CORRECTED`` while ``face_gradient()`` is ``"corrected"``."""
+        if cfl_v is None:
+            cfl_v = VISCOUS_CFL_CORRECTED if self.face_gradient() == "corrected" else VISCOUS_CFL
         self._c(self.lib.mgcfd_set_viscous(self.handle, float(mu), float(prandtl), 1 if wall else 0, float(cfl_v), int(levels)))
 
     def viscous(self):
@@ -1025,7 +1055,7 @@ class Solver:
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
               residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None, wall_damping=None,
-              wall_temperature=None) -> List[dict]:
+              wall_temperature=None, face_gradient=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
@@ -1037,7 +1067,10 @@ class Solver:
         ``viscosity_model=(law, t_ref, s, eddy, cs, prandtl_t)`` or a dict of ``set_viscosity_model``'s keywords; a ``t_ref`` of
         None is then the far field's of the solver as the call finds it; ``wall_damping=(on, kappa)`` or a dict of
         ``set_wall_damping``'s keywords likewise (``set_wall_damping``), and ``wall_temperature=(mode, value)`` or a dict of
-        ``set_wall_temperature``'s keywords (``set_wall_temperature``)."""
+        ``set_wall_temperature``'s keywords (``set_wall_temperature``); ``face_gradient="averaged" / "corrected"``
+        (``set_face_gradient``) is set before the viscous terms, so that a ``viscous`` without ``cfl_v`` takes the mode's default."""
+        if face_gradient is not None:
+            self.set_face_gradient(face_gradient)
         if wall_temperature is not None:
             self.set_wall_temperature(**wall_temperature) if isinstance(wall_temperature, dict) else self.set_wall_temperature(*wall_temperature)
         if wall_damping is not None:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build a library variant from a patched copy of csrc/kernels.hip:
    tools/exp_build.py NAME 'old text' 'new text' ['old2' 'new2' ...]   ->  csrc/build/exp/libmgcfd_hip_NAME.so
-(timing experiments only; kernels_plain.o, kernels_sa.o, kernels_wall_heat.o and the host objects of the current build are reused)."""
+(timing experiments only; kernels_plain.o, kernels_sa.o, kernels_wall_heat.o, kernels_face_gradient.o and the host objects of the current build are reused)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mg-cfd-app-plain_amd", "csrc")
@@ -22,7 +22,7 @@ for ns, contract in (("exact", "off"), ("fast", "fast")):
                            "-mllvm", "-amdgpu-kernarg-preload-count=16",      # (as the Makefile's DEVFLAGS: without it every launch reads 0.5 us slower)
                            f"-ffp-contract={contract}", f"-DMGCFD_KERNEL_NS={ns}"] + (["-DMGCFD_ORDER_FREE=1"] if ns == "fast" else []) + [ f"-I{ROOT}/include", f"-I{CSRC}", "-c", f, "-o", o])
     objs.append(o)
-host = [os.path.join(CSRC, "build", x) for x in ("kernels_plain.o", "kernels_sa.o", "kernels_wall_heat.o", "solver.o", "mesh.o", "preprocess.o")]
+host = [os.path.join(CSRC, "build", x) for x in ("kernels_plain.o", "kernels_sa.o", "kernels_wall_heat.o", "kernels_face_gradient.o", "solver.o", "mesh.o", "preprocess.o")]
 lib = os.path.join(OUT, f"libmgcfd_hip_{name}.so")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + host)
 print("built", lib)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build a library variant of the CURRENT csrc/kernels.hip with extra compiler flags (the -DMGCFD_EXP_* experiment switches):
    tools/exp_flags.py NAME -DMGCFD_EXP_X[=v] ...   ->  csrc/build/exp/libmgcfd_hip_NAME.so
-(timing experiments only; kernels_plain.o, kernels_sa.o, kernels_wall_heat.o and the host objects of the current build are reused; select with MGCFD_LIB=...)."""
+(timing experiments only; kernels_plain.o, kernels_sa.o, kernels_wall_heat.o, kernels_face_gradient.o and the host objects of the current build are reused; select with MGCFD_LIB=...)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mg-cfd-app-plain_amd", "csrc")
@@ -19,7 +19,7 @@ for ns, contract in (("exact", "off"), ("fast", "fast")):
     objs.append(o)
 for p in procs:
     if p.wait() != 0: sys.exit(1)
-host = [os.path.join(CSRC, "build", x) for x in ("kernels_plain.o", "kernels_sa.o", "kernels_wall_heat.o", "solver.o", "mesh.o", "preprocess.o")]
+host = [os.path.join(CSRC, "build", x) for x in ("kernels_plain.o", "kernels_sa.o", "kernels_wall_heat.o", "kernels_face_gradient.o", "solver.o", "mesh.o", "preprocess.o")]
 lib = os.path.join(OUT, f"libmgcfd_hip_{name}.so")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + host)
 print("built", lib)
