@@ -841,8 +841,8 @@ int mgcfd_bench_wall_distance(mgcfd_solver *s, int level, int launches, double *
  * time stepping requested while the mode is on (nt has no BDF source); a level the mode would take effect on created without
  * coordinates; a solver made by mgcfd_create_partitioned* or attached to a group or as a rank; while a kernel-granular sweep is
  * under way.
- * Out of scope: SA-neg, ft2, trip terms, rotation corrections, DES lengths; transport on coarse levels; nt under dual time, in
- * the residual smoothing or the FAS forcing; far-field nt flux.
+ * Out of scope: SA-neg, ft2, trip terms, rotation corrections; transport on coarse levels; nt in the residual smoothing or the
+ * FAS forcing; far-field nt flux.  (nt under dual time and the DES lengths: mgcfd_set_sa_unsteady, below.)
  * --------------------------------------------------------------------------------- */
 #define MGCFD_EDDY_SPALART_ALLMARAS 4         /* (3 is left unassigned: mgcfd_set_viscosity_model has always refused it, and callers rely on that) */
 #define MGCFD_ARR_SA_NU_TILDE 17
@@ -854,6 +854,56 @@ int mgcfd_get_sa_free_stream(const mgcfd_solver *s, double *ratio);
  * the spare buffer, so nt stays, 2: k_sa_restrict into level `level` from the level below it), as mgcfd_bench_viscous times
  * its launches.  MGCFD_ERR_ARG where the model is not in effect. */
 int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
+ * Unsteady Spalart-Allmaras: nt under dual time stepping, the DES97 and delayed-DES lengths.  No reference counterpart;
+ * INTEGRATION.md "Unsteady Spalart-Allmaras" holds the definition, line by line (every operation one IEEE-754 double operation,
+ * never contracted whatever MGCFD_OPT_EXACT says).  One call, per solver, kept like the viscosity model while the model or the
+ * viscous terms are off; the default (0, MGCFD_SA_LENGTH_WALL, MGCFD_SA_CDES) launches and computes what the model did, and keeps
+ * its refusals.
+ *   time_accurate = 1   lifts the two refusals between the model and mgcfd_set_dual_time.  While the model, dual time stepping and
+ *                       time_accurate are all in effect, level 0 holds nt at the two last physical time levels (ntn, ntn1) and
+ *                       pass 2 takes, behind Q:
+ *                           a = nt_i - ntn_i;  b = ntn_i - ntn1_i
+ *                           order 2: ts = (3.0 * a - b) / (2.0 * dt), cj = 1.5 / dt;   order 1: ts = a / dt, cj = 1.0 / dt
+ *                           Q' = Q - vol_i * ts;   dn = (fac * Q') / (1.0 + (fac * vol_i) * (jac + cj))
+ *                       with the order the state's source uses at that moment (cj formed once on the host).  Both levels are set
+ *                       to nt when the combination takes effect, on mgcfd_dual_time_reset and on a reinitialising
+ *                       mgcfd_set_free_stream; mgcfd_dual_time_begin_step does ntn1 <- ntn, ntn <- nt beside the state's levels
+ *                       and forms mut of every covered level again from nt and the state, as a write of nt does, so that a
+ *                       physical step is a function of variables, Wn, Wn1, nt, ntn and ntn1 alone.
+ *                       MGCFD_ARR_SA_TIME_N / _SA_TIME_N1 [nel][1] (level 0) are readable and writable; a write marks the level
+ *                       held, as one of MGCFD_ARR_TIME_N / _TIME_N1 does (a restart).
+ *   length              the model length d~ that pass 2 reads wherever it read the wall distance d (the wall test, kd2, nd, jac);
+ *                       the start value's wall test, the wall-stress pass and y+ keep d.  With delta_i the longest internal edge
+ *                       at node i of level 0, sqrt((dx*dx + dy*dy) + dz*dz) from the coordinates as given (+inf at a node without
+ *                       internal edges), and lim_i = c_des * delta_i:
+ *       MGCFD_SA_LENGTH_WALL  d~ = d.
+ *       MGCFD_SA_LENGTH_DES   DES97: d_i == 0.0: +0.0;  d_i <= lim_i: d_i;  otherwise lim_i.  One node-wise launch (k_sa_length)
+ *                             when the setting takes effect and when it changes.
+ *       MGCFD_SA_LENGTH_DDES  delayed DES (Spalart et al. 2006): the same launch first, then every pass 1 writes it
+ *                             (k_sa_gradient_tile<TAIL, true>, which sums all nine velocity-gradient components):
+ *                                 su = (G[u][x]*G[u][x] + G[u][y]*G[u][y]) + G[u][z]*G[u][z];  sv, sw likewise;  sq = sqrt((su + sv) + sw)
+ *                                 kd = kappa * d_i;  kd2 = kd * kd;  rd = (nt_i * fv1 + nu_i) / (sq * kd2)
+ *                                 e = 8.0 * rd;  z = (e * e) * e;  z = z < 20.0 ? z : 20.0;  fd = 1.0 - tanh_fixed(z)
+ *                                 d_i == 0.0: +0.0;  d_i == +inf: lim_i;  d_i <= lim_i: d_i;  otherwise d_i - fd * (d_i - lim_i)
+ *                             tanh_fixed(z): q = z * (1.0 / 512.0); p = 1/8!; for k = 7 .. 1: p = 1/k! + q * p; p = 1.0 + q * p;
+ *                             ten times p = p * p; (p - 1.0) / (p + 1.0).
+ *                       MGCFD_ARR_SA_LENGTH [nel][1] (level 0, read-only) exists while length != WALL and the model is in effect.
+ * MGCFD_ERR_ARG, and nothing changed: length outside 0..2; time_accurate not 0 or 1; c_des not finite and positive; while a
+ * kernel-granular sweep is under way; a solver made by mgcfd_create_partitioned* or attached to a group or as a rank;
+ * time_accurate = 0 while dual time stepping is on and the model is in effect.  The setter synchronises and drops captured graphs.
+ * Out of scope: IDDES, SA-neg, ft2, the low-Reynolds correction Psi; transport, time levels or d~ on coarse levels; nt in the
+ * residual smoothing or the FAS forcing; partitioned levels, groups and ranks.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_SA_LENGTH_WALL 0      /* d~ = d */
+#define MGCFD_SA_LENGTH_DES  1      /* DES97 */
+#define MGCFD_SA_LENGTH_DDES 2      /* delayed DES (Spalart et al. 2006) */
+#define MGCFD_SA_CDES 0.65
+#define MGCFD_ARR_SA_TIME_N 20
+#define MGCFD_ARR_SA_TIME_N1 21
+#define MGCFD_ARR_SA_LENGTH 22
+int mgcfd_set_sa_unsteady(mgcfd_solver *s, int time_accurate, int length, double c_des);
+int mgcfd_get_sa_unsteady(const mgcfd_solver *s, int *time_accurate, int *length, double *c_des);
 /* ---------------------------------------------------------------------------------
  * Wall thermal conditions and heat loads.  No reference counterpart; INTEGRATION.md "Wall thermal conditions" holds the
  * definition.  Every operation is one IEEE-754 double operation (+ - * sqrt), never contracted whatever MGCFD_OPT_EXACT says.

@@ -193,6 +193,27 @@ struct SaStep {
 struct SaStepCorrected : SaStep {
     const double *x = nullptr;                // [3][stride] the level's coordinates as given at creation
 };
+// ... and pass 2 with the physical-time source of nt (mgcfd_set_sa_unsteady with time_accurate, under dual time stepping):
+//   a = nt - ntn;  b = ntn - ntn1;  ts = (3 a - b) / (2 dt)  (order 2)  |  a / dt  (order 1, ntn1 not read);  Q' = Q - vol * ts
+//   dn = (fac * Q') / (1.0 + (fac * vol) * (jac + cj))
+// Again argument types of their own: the untimed instantiations keep their arguments and their code.
+struct SaTime {
+    const double *ntn = nullptr, *ntn1 = nullptr;   // [stride] nu_tilde at the last physical time level and the one before it
+    double dt = 0.0;                          // the physical step
+    double cj = 0.0;                          // 1.5 / dt (order 2) or 1.0 / dt (order 1), formed once on the host
+    int order = 1;
+};
+struct SaStepTimed : SaStep { SaTime t; };
+struct SaStepCorrectedTimed : SaStepCorrected { SaTime t; };
+// Pass 1 under delayed DES (MGCFD_SA_LENGTH_DDES): the shielded model length d~ per node, written every stage.  The DES97 length
+// (k_sa_length) takes the same arguments.
+struct SaShield {
+    const double *d = nullptr;                // [stride] the wall distance
+    const double *delta = nullptr;            // [stride] the longest internal edge at the node (+inf: none)
+    double c_des = 0.0;
+    double *length = nullptr;                 // [stride] d~
+};
+struct SaStepShielded : SaStep { SaShield sh; };
 
 // The two launches of the corrected face gradient (kernels_face_gradient.hip: k_face_gradient_nodes_tile,
 // k_face_gradient_correction_tile; mgcfd_set_face_gradient): the first writes g from w behind the stress launch, the second reads

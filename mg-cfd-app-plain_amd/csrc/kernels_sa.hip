@@ -38,12 +38,39 @@ __device__ __forceinline__ double sa_fv1(double chi, double cv1_3)
     return chi3 / (chi3 + cv1_3);
 }
 
-template <bool TAIL>
-__global__ void __launch_bounds__(kBlock, 4)
+// tanh of z in [0, 20] by a fixed algorithm (INTEGRATION.md "Unsteady Spalart-Allmaras"): exp(z / 512) by its Taylor polynomial
+// of degree 8, squared ten times to exp(2 z), then (p - 1) / (p + 1).  No exp on the device.
+__device__ __forceinline__ double sa_tanh_fixed(double z)
+{
+    const double q = z * (1.0 / 512.0);
+    double p = 1.0 / 40320.0;
+    p = 1.0 / 5040.0 + q * p;
+    p = 1.0 / 720.0 + q * p;
+    p = 1.0 / 120.0 + q * p;
+    p = 1.0 / 24.0 + q * p;
+    p = 1.0 / 6.0 + q * p;
+    p = 1.0 / 2.0 + q * p;
+    p = 1.0 / 1.0 + q * p;
+    p = 1.0 + q * p;
+#pragma unroll
+    for (int k = 0; k < 10; k++) p = p * p;
+    return (p - 1.0) / (p + 1.0);
+}
+// The DES97 length: d~ = min(d, c_des * delta), +0.0 on the wall, lim where d = +inf.
+__device__ __forceinline__ double sa_length_des(double d, double lim)
+{
+    if (d == 0.0) return 0.0;
+    return d <= lim ? d : lim;
+}
+
+// SHIELD: under delayed DES (mgcfd_set_sa_unsteady with MGCFD_SA_LENGTH_DDES) the three diagonal sums are taken too and the
+// shielded length d~ is written per node: STEP = SaStepShielded.  STEP = SaStep is the plain kernel.
+template <bool TAIL, bool SHIELD>
+__global__ void __launch_bounds__(kBlock, (SHIELD ? 5 : 4))
 k_sa_gradient_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
                    const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
                    const double *__restrict__ w, const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf,
-                   TailPlan tp, SaStep a)
+                   TailPlan tp, std::conditional_t<SHIELD, SaStepShielded, SaStep> a)
 {
 #pragma clang fp contract(off)
     __shared__ double rec[4][kSmoothRow];                              // u, v, w, nt
@@ -80,6 +107,7 @@ k_sa_gradient_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int6
     __syncthreads();
 
     double uy = 0.0, uz = 0.0, vx = 0.0, vz = 0.0, wx = 0.0, wy = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;   // (the curl takes the six off-diagonal sums)
+    double ux = 0.0, vy = 0.0, wz = 0.0;                               // (SHIELD: the diagonal too)
     auto add = [&](uint32_t code, double hx, double hy, double hz) {
         const uint32_t s = code & kT16SlotMask;
         if (s == kT16Pad) return;
@@ -92,6 +120,7 @@ k_sa_gradient_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int6
         vx += dv * nx; vz += dv * nz;
         wx += dw * nx; wy += dw * ny;
         tx += dn * nx; ty += dn * ny; tz += dn * nz;
+        if constexpr (SHIELD) { ux += du * nx; vy += dv * ny; wz += dw * nz; }
     };
     for (int32_t r = 0; r < n_int; r++) {                             // code and weights one row ahead of the sums
         const bool more = r + 1 < n_int;
@@ -121,22 +150,53 @@ k_sa_gradient_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int6
     const double nu = mu_i / rho;
     const double chi = me.nt / nu;
     const double mut = (rho * me.nt) * sa_fv1(chi, a.cv1_3);
+    if constexpr (SHIELD) {
+        constexpr double kappa = 0.41;
+        const double fv1 = sa_fv1(chi, a.cv1_3);
+        const double gux = (0.5 * ux) / vol, gvy = (0.5 * vy) / vol, gwz = (0.5 * wz) / vol;
+        const double su = (gux * gux + guy * guy) + guz * guz;
+        const double sv = (gvx * gvx + gvy * gvy) + gvz * gvz;
+        const double sw = (gwx * gwx + gwy * gwy) + gwz * gwz;
+        const double sq = sqrt((su + sv) + sw);
+        const double d_i = a.sh.d[i];
+        const double lim = a.sh.c_des * a.sh.delta[i];
+        const double kd = kappa * d_i;
+        const double kd2 = kd * kd;
+        const double rd = (me.nt * fv1 + nu) / (sq * kd2);
+        const double e = 8.0 * rd;
+        double z = (e * e) * e;
+        z = z < 20.0 ? z : 20.0;                                       // (inf and NaN give 20.0)
+        const double fd = 1.0 - sa_tanh_fixed(z);
+        double len;
+        if (d_i == 0.0) len = 0.0;
+        else if (d_i == __builtin_huge_val()) len = lim;
+        else if (d_i <= lim) len = d_i;
+        else len = d_i - fd * (d_i - lim);
+        a.sh.length[i] = present ? len : 0.0;
+    }
     a.grad[i] = present ? gtx : 0.0; a.grad[stride + i] = present ? gty : 0.0; a.grad[2 * stride + i] = present ? gtz : 0.0;
     a.grad[3 * stride + i] = present ? om : 0.0; a.grad[4 * stride + i] = present ? nu : 0.0;
     a.mut[i] = present ? mut : 0.0;
 }
 
+template <class STEP> struct sa_timed : std::false_type {};
+template <> struct sa_timed<SaStepTimed> : std::true_type {};
+template <> struct sa_timed<SaStepCorrectedTimed> : std::true_type {};
+
+// TIMED (STEP = SaStepTimed, SaStepCorrectedTimed): the physical-time source of nt under dual time stepping; the own node's two time
+// levels are read from memory behind the sums, nothing more is staged.
 // CORR: under the corrected face gradient (mgcfd_set_face_gradient) the coordinates are staged too (eleven fields, 49,280 B) and
 // Qdc, the along-edge correction of the diffusion, is summed beside Qd: STEP = SaStepCorrected.  STEP = SaStep is the averaged kernel.
 template <bool TAIL, class STEP>
-__global__ void __launch_bounds__(kBlock, (std::is_same<STEP, SaStepCorrected>::value ? 3 : 4))
+__global__ void __launch_bounds__(kBlock, (std::is_base_of<SaStepCorrected, STEP>::value ? 3 : 4))
 k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int64_t stride, int64_t nel,
                     const int32_t *__restrict__ slice_row0, const int32_t *__restrict__ rows_int, const uint16_t *__restrict__ nbr16,
                     const double *__restrict__ w, const int32_t *__restrict__ tile_ovf_ptr, const int32_t *__restrict__ tile_ovf,
                     TailPlan tp, STEP a)
 {
 #pragma clang fp contract(off)
-    constexpr bool CORR = std::is_same<STEP, SaStepCorrected>::value;
+    constexpr bool CORR = std::is_base_of<SaStepCorrected, STEP>::value;
+    constexpr bool TIMED = sa_timed<STEP>::value;
     constexpr int NF = CORR ? 11 : 8;
     __shared__ double rec[NF][kSmoothRow];                             // u, v, w, nt, nu, G[nt][x], G[nt][y], G[nt][z] (CORR: x, y, z)
     const int tid = threadIdx.x;
@@ -251,7 +311,16 @@ k_sa_transport_tile(const int32_t *__restrict__ tile_halo, uint32_t n_tiles, int
     const double sf = a.step_factors[i];
     const double sft = cap < sf ? cap : sf;
     const double fac = sft / a.rk_div;
-    const double dn = (fac * q) / (1.0 + (fac * vol) * jac);
+    double dn;
+    if constexpr (TIMED) {
+        const double ntn = a.t.ntn[i];
+        const double ta = nt_i - ntn;
+        double ts;
+        if (a.t.order == 2) { const double tb = ntn - a.t.ntn1[i]; ts = (3.0 * ta - tb) / (2.0 * a.t.dt); }
+        else ts = ta / a.t.dt;
+        const double qt = q - vol * ts;
+        dn = (fac * qt) / (1.0 + (fac * vol) * (jac + a.t.cj));
+    } else dn = (fac * q) / (1.0 + (fac * vol) * jac);
     const double x = a.nt_old[i] + dn;
     a.nt_out[i] = x < 0.0 ? 0.0 : x;                                   // (a NaN stays NaN)
 }
@@ -297,30 +366,56 @@ k_sa_init(int64_t nel, int64_t stride, double nt0, const double *__restrict__ d,
     a.mut[i] = (rho * v) * sa_fv1(v / (mu_i / rho), a.cv1_3);
 }
 
+// d~ of DES97 per node, which is also delayed DES's length until the first pass 1 writes it; pad lanes +0.0.
+__global__ void __launch_bounds__(kBlock)
+k_sa_length(int64_t nel, int64_t stride, SaShield a)
+{
+#pragma clang fp contract(off)
+    const int64_t i = blockIdx.x * int64_t(kBlock) + threadIdx.x;
+    if (i >= stride) return;
+    a.length[i] = i < nel ? sa_length_des(a.d[i], a.c_des * a.delta[i]) : 0.0;
+}
+
 // ==========================================================================================
 // launchers
 // ==========================================================================================
-void launch_sa_gradient(hipStream_t st, const DevicePlan &p, const SaStep &a)
+void launch_sa_gradient(hipStream_t st, const DevicePlan &p, const SaStep &a, const SaShield *shield)
 {
-    if (p.has_tail)
-        hipLaunchKernelGGL((k_sa_gradient_tile<true>), dim3(p.n_tiles), dim3(kBlock), 0, st,
-                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
-    else
-        hipLaunchKernelGGL((k_sa_gradient_tile<false>), dim3(p.n_tiles), dim3(kBlock), 0, st,
-                           p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, a);
-}
-void launch_sa_transport(hipStream_t st, const DevicePlan &p, const SaStep &a, const double *x)
-{
-    auto go = [&](auto tail, const auto &step) {
-        hipLaunchKernelGGL((k_sa_transport_tile<decltype(tail)::value, std::decay_t<decltype(step)>>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+    auto go = [&](auto tail, auto sh, const auto &step) {
+        hipLaunchKernelGGL((k_sa_gradient_tile<decltype(tail)::value, decltype(sh)::value>), dim3(p.n_tiles), dim3(kBlock), 0, st,
                            p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, step);
     };
-    if (x) {                                                           // (the corrected face gradient: Qdc beside Qd)
+    if (shield) {                                                      // (delayed DES: d~ beside sa_gradient)
+        SaStepShielded c;
+        static_cast<SaStep &>(c) = a; c.sh = *shield;
+        if (p.has_tail) go(std::true_type{}, std::true_type{}, c); else go(std::false_type{}, std::true_type{}, c);
+    } else { if (p.has_tail) go(std::true_type{}, std::false_type{}, a); else go(std::false_type{}, std::false_type{}, a); }
+}
+void launch_sa_transport(hipStream_t st, const DevicePlan &p, const SaStep &a, const double *x, const SaTime *time)
+{
+    auto go = [&](const auto &step) {
+        auto launch = [&](auto tail) {
+            hipLaunchKernelGGL((k_sa_transport_tile<decltype(tail)::value, std::decay_t<decltype(step)>>), dim3(p.n_tiles), dim3(kBlock), 0, st,
+                               p.tile_halo, uint32_t(p.n_tiles), p.stride, p.nel, p.slice_row0, p.rows_int, p.nbr16, p.w, p.tile_ovf_ptr, p.tile_ovf, p.tail, step);
+        };
+        if (p.has_tail) launch(std::true_type{}); else launch(std::false_type{});
+    };
+    if (x && time) {                                                   // (the corrected face gradient: Qdc beside Qd; the physical-time source)
+        SaStepCorrectedTimed c;
+        static_cast<SaStep &>(c) = a; c.x = x; c.t = *time;
+        go(c);
+    } else if (x) {
         SaStepCorrected c;
         static_cast<SaStep &>(c) = a; c.x = x;
-        if (p.has_tail) go(std::true_type{}, c); else go(std::false_type{}, c);
-    } else { if (p.has_tail) go(std::true_type{}, a); else go(std::false_type{}, a); }
+        go(c);
+    } else if (time) {
+        SaStepTimed c;
+        static_cast<SaStep &>(c) = a; c.t = *time;
+        go(c);
+    } else go(a);
 }
+void launch_sa_length(hipStream_t st, int64_t nel, int64_t stride, const SaShield &a)
+{ hipLaunchKernelGGL(k_sa_length, dim3(grid_for(stride)), dim3(kBlock), 0, st, nel, stride, a); }
 void launch_sa_restrict(hipStream_t st, int64_t nel_coarse, int64_t stride_coarse, const int32_t *child_ptr, const int32_t *child,
                         const double *fine_nt, double *coarse_nt, const SaStep &a)
 { hipLaunchKernelGGL(k_sa_restrict, dim3(grid_for(nel_coarse)), dim3(kBlock), 0, st, nel_coarse, stride_coarse, child_ptr, child, fine_nt, coarse_nt, a); }

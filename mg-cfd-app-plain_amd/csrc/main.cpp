@@ -87,6 +87,11 @@ struct Config {                       // the reference's `config` (src/Base/conf
     // RATIO the free-stream nu_tilde over nu (mgcfd_set_sa_free_stream)
     bool spalart_allmaras = false;
     double sa_ratio = MGCFD_SA_RATIO;
+    // --sa-time-accurate, --sa-length wall|des|ddes, --sa-cdes X and the config keys sa_time_accurate (Y) / sa_length / sa_cdes:
+    // the unsteady model (mgcfd_set_sa_unsteady), with --spalart-allmaras; --sa-time-accurate lets it run with --physical-time-step
+    bool sa_time_accurate = false, sa_unsteady_given = false;
+    int sa_length = MGCFD_SA_LENGTH_WALL;
+    double sa_cdes = MGCFD_SA_CDES;
     // --wall-damping[=KAPPA] / wall_damping = Y | KAPPA: the wall-limited length scale of --smagorinsky (mgcfd_set_wall_damping)
     bool wall_damping = false;
     double wall_kappa = MGCFD_WALL_KAPPA;
@@ -163,6 +168,14 @@ bool set_face_gradient(Config &c, const char *text)
     if (v != "averaged" && v != "corrected") return false;
     c.face_gradient = v == "corrected" ? MGCFD_FACE_GRADIENT_CORRECTED : MGCFD_FACE_GRADIENT_AVERAGED;
     c.face_gradient_given = true;
+    return true;
+}
+// --sa-length / sa_length: the model length of the Spalart-Allmaras model by name
+bool set_sa_length(Config &c, const char *text)
+{
+    const std::string v(text ? text : "");
+    if (v != "wall" && v != "des" && v != "ddes") return false;
+    c.sa_length = v == "ddes" ? MGCFD_SA_LENGTH_DDES : (v == "des" ? MGCFD_SA_LENGTH_DES : MGCFD_SA_LENGTH_WALL);
     return true;
 }
 
@@ -327,6 +340,15 @@ void set_param(Config &c, const std::string &key, const std::string &value)
         if (value == "Y") c.spalart_allmaras = true;
         else if (parse_positive(value.c_str(), &c.sa_ratio)) c.spalart_allmaras = true;
         else if (value != "N") { std::fprintf(stderr, "ERROR: spalart_allmaras = '%s': expected Y or a finite ratio above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "sa_time_accurate") { if (value == "Y") { c.sa_time_accurate = true; c.sa_unsteady_given = true; } }
+    else if (key == "sa_length") {
+        if (set_sa_length(c, value.c_str())) c.sa_unsteady_given = true;
+        else { std::fprintf(stderr, "ERROR: sa_length = '%s': expected wall, des or ddes\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "sa_cdes") {
+        if (parse_positive(value.c_str(), &c.sa_cdes)) c.sa_unsteady_given = true;
+        else { std::fprintf(stderr, "ERROR: sa_cdes = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
     }
     else if (key == "wall_damping") {
         if (value == "Y") c.wall_damping = true;
@@ -515,7 +537,11 @@ void print_help()
         "  --prandtl-turbulent=X            the turbulent Prandtl number (default 0.9; config key prandtl_turbulent)\n"
         "  --spalart-allmaras[=RATIO]       with the viscous terms: the Spalart-Allmaras model (noft2), nu_tilde transported on level 0 and\n"
         "                                   restricted to the coarser viscous levels; RATIO = free-stream nu_tilde / nu, default 3 (config key\n"
-        "                                   spalart_allmaras = Y or RATIO); needs .coords files; one GPU; not with --smagorinsky or --physical-time-step\n"
+        "                                   spalart_allmaras = Y or RATIO); needs .coords files; one GPU; not with --smagorinsky; with\n"
+        "                                   --physical-time-step only together with --sa-time-accurate\n"
+        "  --sa-time-accurate               with --spalart-allmaras: nu_tilde takes the BDF source of --physical-time-step (config key sa_time_accurate = Y)\n"
+        "  --sa-length=wall|des|ddes        with --spalart-allmaras: the model length, the wall distance (default), DES97 or delayed DES (config key sa_length)\n"
+        "  --sa-cdes=X                      ... and its constant, finite and above zero, default 0.65 (config key sa_cdes)\n"
         "  --wall-damping[=KAPPA]           with --smagorinsky: the length scale min(CS cbrt(volume), KAPPA d), d the distance to the nearest\n"
         "                                   solid-wall node, KAPPA default 0.41 (config key wall_damping = Y or KAPPA); needs .coords files\n"
         "  --physical-time-step=DT          dual time stepping: a time-accurate run with physical step DT, finite and above zero\n"
@@ -600,6 +626,9 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"wall-heat-flux", required_argument, nullptr, 1049},
         {"loads-heat", no_argument, nullptr, 1054},
         {"face-gradient", required_argument, nullptr, 1055},
+        {"sa-time-accurate", no_argument, nullptr, 1056},
+        {"sa-length", required_argument, nullptr, 1057},
+        {"sa-cdes", required_argument, nullptr, 1058},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -825,6 +854,21 @@ bool parse_arguments(int argc, char **argv, Config &c)
                     return false;
                 }
                 break;
+            case 1056: c.sa_time_accurate = true; c.sa_unsteady_given = true; break;
+            case 1057:
+                if (!set_sa_length(c, optarg)) {
+                    std::fprintf(stderr, "ERROR: --sa-length=%s: expected wall, des or ddes\n", optarg);
+                    return false;
+                }
+                c.sa_unsteady_given = true;
+                break;
+            case 1058:
+                if (!parse_positive(optarg, &c.sa_cdes)) {
+                    std::fprintf(stderr, "ERROR: --sa-cdes=%s: expected a finite number above zero\n", optarg);
+                    return false;
+                }
+                c.sa_unsteady_given = true;
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
@@ -852,8 +896,12 @@ bool parse_arguments(int argc, char **argv, Config &c)
         std::fprintf(stderr, "ERROR: --spalart-allmaras and --smagorinsky are two eddy-viscosity models: give one of them\n");
         return false;
     }
-    if (c.spalart_allmaras && c.dual_given) {
-        std::fprintf(stderr, "ERROR: --spalart-allmaras does not run with --physical-time-step (nu_tilde has no physical-time source)\n");
+    if (c.sa_unsteady_given && !c.spalart_allmaras) {
+        std::fprintf(stderr, "ERROR: --sa-time-accurate, --sa-length and --sa-cdes need --spalart-allmaras (they are settings of that model)\n");
+        return false;
+    }
+    if (c.spalart_allmaras && c.dual_given && !c.sa_time_accurate) {
+        std::fprintf(stderr, "ERROR: --spalart-allmaras does not run with --physical-time-step (nu_tilde has no physical-time source) unless --sa-time-accurate gives it one\n");
         return false;
     }
     if (c.wall_damping && !c.smagorinsky) {
@@ -1445,6 +1493,8 @@ int main(int argc, char **argv)
         double t_ref = 0.0;
         if (conf.viscosity_model() && sutherland_tref_of(conf, &t_ref) != MGCFD_OK) return fail("setting the viscosity model");
         if (conf.spalart_allmaras && mgcfd_set_sa_free_stream(solver, conf.sa_ratio, 0) != MGCFD_OK) return fail("setting the Spalart-Allmaras free stream");
+        if (conf.sa_unsteady_given && mgcfd_set_sa_unsteady(solver, conf.sa_time_accurate ? 1 : 0, conf.sa_length, conf.sa_cdes) != MGCFD_OK)
+            return fail("setting the unsteady Spalart-Allmaras model");
         if (conf.viscosity_model() &&
             mgcfd_set_viscosity_model(solver, conf.sutherland ? MGCFD_VISCOSITY_SUTHERLAND : MGCFD_VISCOSITY_CONSTANT, t_ref, conf.sutherland_s,
                                       conf.spalart_allmaras ? MGCFD_EDDY_SPALART_ALLMARAS : (conf.smagorinsky ? MGCFD_EDDY_SMAGORINSKY : MGCFD_EDDY_NONE),

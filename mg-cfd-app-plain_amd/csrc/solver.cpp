@@ -218,6 +218,10 @@ struct DeviceLevel {
     // the Spalart-Allmaras model, held while it is in effect on the level: nu_tilde [stride] and, on level 0, its value at the
     // sweep's start, the spare buffer a stage's pass 2 writes (swapped with sa_nt behind it) and sa_gradient [5][stride]
     double *sa_nt = nullptr, *sa_old = nullptr, *sa_spare = nullptr, *sa_grad = nullptr;
+    // the unsteady model (mgcfd_set_sa_unsteady), level 0 only: nu_tilde at the two last physical time levels [stride] each, held
+    // while the model, dual time stepping and time_accurate are all in effect; the longest internal edge per node and the model
+    // length d~ [stride] each, held while the model is in effect and the length is not the wall distance
+    double *sa_ntn = nullptr, *sa_ntn1 = nullptr, *sa_delta = nullptr, *sa_len = nullptr;
     // the corrected face gradient (mgcfd_set_face_gradient), held while it is in effect on the level: G, me, kap [14][stride] and
     // the coordinates in the solver's numbering [3][stride]
     double *fg_g = nullptr, *fg_x = nullptr;
@@ -425,6 +429,37 @@ struct mgcfd_solver {
     double sa_ratio = MGCFD_SA_RATIO;
     bool sa_on(int l) const { return vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS && viscous_on(l); }
     bool sa_in_effect() const { return vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS && visc_levels > 0; }
+    // The unsteady model (mgcfd_set_sa_unsteady; INTEGRATION.md "Unsteady Spalart-Allmaras"): kept like the viscosity model.
+    int sa_time_accurate = 0, sa_length = MGCFD_SA_LENGTH_WALL;
+    double sa_cdes = MGCFD_SA_CDES;
+    bool sa_timed() const { return sa_time_accurate && dual_time() && sa_on(0); }
+    bool sa_model_length() const { return sa_length != MGCFD_SA_LENGTH_WALL && sa_on(0); }
+    SaShield sa_shield(const DeviceLevel &lv) const
+    {
+        SaShield a;
+        a.d = lv.wall_d; a.delta = lv.sa_delta; a.c_des = sa_cdes; a.length = lv.sa_len;
+        return a;
+    }
+    SaTime sa_time(const DeviceLevel &lv) const
+    {
+        SaTime t;
+        t.ntn = lv.sa_ntn; t.ntn1 = lv.sa_ntn1; t.dt = dual_dt;
+        t.order = (dual_order == 2 && dual_levels == 2) ? 2 : 1;
+        t.cj = (t.order == 2 ? 1.5 : 1.0) / dual_dt;
+        return t;
+    }
+    // pass 1 of level 0: under delayed DES the instantiation that writes d~ too
+    void sa_gradient(DeviceLevel &lv)
+    {
+        if (lv.sa_len && sa_length == MGCFD_SA_LENGTH_DDES) { const SaShield sh = sa_shield(lv); launch_sa_gradient(stream, lv.dp, sa_step(lv), &sh); }
+        else launch_sa_gradient(stream, lv.dp, sa_step(lv));
+    }
+    // pass 2 of level 0 with the arguments `a`: with the physical-time source where the time levels are held
+    void sa_launch_transport(DeviceLevel &lv, const SaStep &a)
+    {
+        if (lv.sa_ntn) { const SaTime t = sa_time(lv); launch_sa_transport(stream, lv.dp, a, lv.fg_x, &t); }
+        else launch_sa_transport(stream, lv.dp, a, lv.fg_x);
+    }
     SaStep sa_step(const DeviceLevel &lv, int j = 0) const
     {
         const double cb1 = 0.1355, cb2 = 0.622, sigma = 2.0 / 3.0, kappa = 0.41, cv1 = 7.1;
@@ -432,7 +467,8 @@ struct mgcfd_solver {
         a.w = lv.q; a.nt = lv.sa_nt; a.grad = lv.sa_grad; a.mut = lv.visc_mut; a.volumes = lv.volumes;
         a.mu = visc_mu; a.model = viscosity_model(lv);
         a.cv1_3 = (cv1 * cv1) * cv1;
-        a.nt_old = lv.sa_old; a.nt_out = lv.sa_spare; a.d = lv.wall_d; a.g = lv.visc_g; a.step_factors = lv.step_factors;
+        a.nt_old = lv.sa_old; a.nt_out = lv.sa_spare; a.g = lv.visc_g; a.step_factors = lv.step_factors;
+        a.d = lv.sa_len ? lv.sa_len : lv.wall_d;                     // (sa_len: the model length d~, level 0 alone)
         a.cw1 = cb1 / (kappa * kappa) + (1.0 + cb2) / sigma; a.c6 = 64.0; a.inv_sigma = 1.0 / sigma; a.ks = (1.0 + cb2) / sigma;
         a.cfl_v = visc_cfl; a.rk_div = double(MGCFD_RK + 1 - j);
         return a;
@@ -449,7 +485,7 @@ struct mgcfd_solver {
     {
         if (l != 0 || !sa_on(l)) return;
         DeviceLevel &lv = level(l);
-        launch_sa_transport(stream, lv.dp, sa_step(lv, j), lv.fg_x);   // (fg_x: held exactly while the corrected face gradient is in effect here)
+        sa_launch_transport(lv, sa_step(lv, j));                       // (fg_x: held exactly while the corrected face gradient is in effect here)
         std::swap(lv.sa_nt, lv.sa_spare);
     }
     // behind a restriction into level `coarse`: nt averaged over the children, mut from it and the restricted state
@@ -811,7 +847,7 @@ struct mgcfd_solver {
         }
         if ((classes & 1) && viscous_on(l)) {
             // the Spalart-Allmaras model's pass 1 first: the stress launch reads the mut it writes
-            if (l == 0 && sa_on(l)) launch_sa_gradient(stream, lv.dp, sa_step(lv));
+            if (l == 0 && sa_on(l)) sa_gradient(lv);
             // viscous terms: S of the same state, then fluxes[1..4] += V, behind C (both passes keep row order in either flavour)
             const ViscousStep a = viscous_step(lv);
             k().viscous_stress(stream, lv.dp, a);
@@ -1810,6 +1846,7 @@ static void apply_free_stream(mgcfd_solver *s, const double ff17[17], double mac
         if (lv.fas_p) HIP_CHECK(hipMemsetAsync(lv.fas_p, 0, sizeof(double) * 5 * lv.dp.stride, s->stream));   // (the forcing belonged to the old state)
         s->viscous_wall(static_cast<int>(&lv - s->L.data()), lv.q);
         if (s->sa_on(static_cast<int>(&lv - s->L.data()))) s->sa_form(lv, true);
+        if (lv.sa_ntn) launch_dual_shift(s->stream, lv.dp.stride, lv.sa_nt, lv.sa_ntn, lv.sa_ntn1, 1);     // (both time levels: the new nt)
     }
     HIP_CHECK(hipMemsetAsync(s->err, 0xFF, sizeof(unsigned long long), s->stream));
     s->check_seq = 0;
@@ -1972,7 +2009,8 @@ static void require_damping_possible(const mgcfd_solver *s, int visc_levels, int
 static void require_sa_possible(const mgcfd_solver *s, int visc_levels, int eddy)
 {
     if (eddy != MGCFD_EDDY_SPALART_ALLMARAS) return;
-    if (s->dual_time()) throw std::invalid_argument("Spalart-Allmaras model: not while dual time stepping is on (nu_tilde has no BDF source)");
+    if (s->dual_time() && !s->sa_time_accurate)
+        throw std::invalid_argument("Spalart-Allmaras model: not while dual time stepping is on (nu_tilde has no BDF source; mgcfd_set_sa_unsteady with time_accurate gives it one)");
     for (int l = 0; l < visc_levels && l < static_cast<int>(s->L.size()); l++)
         if (!s->L[static_cast<size_t>(l)].wall_d && s->L[static_cast<size_t>(l)].coords.empty())
             throw std::invalid_argument("Spalart-Allmaras model: level " + std::to_string(l) + " was created without coordinates (the model needs the wall distance there)");
@@ -2005,6 +2043,45 @@ static void settle_sa(mgcfd_solver *s, bool all)
             s->sa_form(lv, true);
             if (l == 0) HIP_CHECK(hipMemcpyAsync(lv.sa_old, lv.sa_nt, sizeof(double) * stride, hipMemcpyDeviceToDevice, s->stream));
         }
+    }
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+}
+
+// The unsteady model's arrays on level 0 (mgcfd_set_sa_unsteady): the two time levels of nt are held exactly while the model,
+// dual time stepping and time_accurate are all in effect, and start as nt; delta and d~ exactly while the model is in effect and
+// the length is not the wall distance.  Every setter that can complete or end either combination calls this once its new state
+// is stored and nt is settled; `length_changed`: the length or c_des has changed, so d~ is formed again.
+static void settle_sa_unsteady(mgcfd_solver *s, bool length_changed = false)
+{
+    DeviceLevel &lv = s->L[0];
+    const size_t stride = static_cast<size_t>(lv.dp.stride);
+    if (!s->sa_timed()) { lv.mem.release(lv.sa_ntn); lv.mem.release(lv.sa_ntn1); }
+    else if (!lv.sa_ntn) {
+        lv.sa_ntn = lv.mem.alloc<double>(stride); lv.sa_ntn1 = lv.mem.alloc<double>(stride);
+        launch_dual_shift(s->stream, lv.dp.stride, lv.sa_nt, lv.sa_ntn, lv.sa_ntn1, 1);
+    }
+    if (!s->sa_model_length()) { lv.mem.release(lv.sa_delta); lv.mem.release(lv.sa_len); }
+    else {
+        const bool fresh = !lv.sa_len;
+        if (fresh) {
+            // delta: the longest internal edge at the node from the coordinates as given (a node without internal edges: +inf)
+            std::vector<double> delta(stride, std::numeric_limits<double>::infinity()), longest(static_cast<size_t>(lv.info.nel), -1.0);
+            for (int64_t k = 0; k < lv.info.n_internal; k++) {
+                const auto &e = lv.edges[static_cast<size_t>(lv.info.internal_start + k)];
+                const size_t a = static_cast<size_t>(e.a), b = static_cast<size_t>(e.b);
+                const double dx = lv.coords[3 * b] - lv.coords[3 * a], dy = lv.coords[3 * b + 1] - lv.coords[3 * a + 1], dz = lv.coords[3 * b + 2] - lv.coords[3 * a + 2];
+                const double len = std::sqrt((dx * dx + dy * dy) + dz * dz);
+                if (len > longest[a]) longest[a] = len;
+                if (len > longest[b]) longest[b] = len;
+            }
+            for (int64_t n = 0; n < lv.info.nel; n++) {
+                const double v = longest[static_cast<size_t>(lv.plan.old_of_new[static_cast<size_t>(n)])];
+                if (v >= 0.0) delta[static_cast<size_t>(n)] = v;
+            }
+            lv.sa_delta = lv.mem.upload(delta);
+            lv.sa_len = lv.mem.alloc<double>(stride);
+        }
+        if (fresh || length_changed) launch_sa_length(s->stream, lv.info.nel, lv.dp.stride, s->sa_shield(lv));
     }
     HIP_CHECK(hipStreamSynchronize(s->stream));
 }
@@ -2158,6 +2235,7 @@ int mgcfd_set_viscous(mgcfd_solver *s, double mu, double prandtl, int wall, doub
             s->viscous_wall(l, lv.q);
         }
         settle_sa(s, false);                                    // (behind the wall rule: mut of a new level is formed from the state it leaves)
+        settle_sa_unsteady(s);
         HIP_CHECK(hipStreamSynchronize(s->stream));
         HIP_CHECK(hipGetLastError());
     });
@@ -2300,6 +2378,7 @@ int mgcfd_set_viscosity_model(mgcfd_solver *s, int law, double t_ref, double s_r
         s->vm_prandtl_t = positive(prandtl_t) ? prandtl_t : MGCFD_PRANDTL_TURBULENT;
         settle_viscosity_arrays(s, eddy_changed);
         settle_sa(s, eddy_changed);
+        settle_sa_unsteady(s);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -3198,6 +3277,14 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.sa_grad) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: level 0 while the Spalart-Allmaras model is in effect");
             *ncols = 5;
             return lv.sa_grad;
+        case MGCFD_ARR_SA_TIME_N: case MGCFD_ARR_SA_TIME_N1:
+            if (!lv.sa_ntn) throw std::invalid_argument("MGCFD_ARR_SA_TIME_N / _SA_TIME_N1: level 0 while the Spalart-Allmaras model, dual time stepping and mgcfd_set_sa_unsteady's time_accurate are all in effect");
+            *ncols = 1;
+            return which == MGCFD_ARR_SA_TIME_N ? lv.sa_ntn : lv.sa_ntn1;
+        case MGCFD_ARR_SA_LENGTH:
+            if (!lv.sa_len) throw std::invalid_argument("MGCFD_ARR_SA_LENGTH: level 0 while the Spalart-Allmaras model is in effect with a DES or DDES length (mgcfd_set_sa_unsteady)");
+            *ncols = 1;
+            return lv.sa_len;
         case MGCFD_ARR_VISCOUS_GRADIENT:
             if (!lv.fg_g) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: the corrected face gradient is not in effect on this level (mgcfd_set_face_gradient, on a level mgcfd_set_viscous covers)");
             *ncols = 12;
@@ -3250,6 +3337,7 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under the Spalart-Allmaras model (formed from MGCFD_ARR_SA_NU_TILDE)");
         if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
         if (which == MGCFD_ARR_VISCOUS_GRADIENT) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: read-only (every flux launch of the level overwrites it)");
+        if (which == MGCFD_ARR_SA_LENGTH) throw std::invalid_argument("MGCFD_ARR_SA_LENGTH: read-only (formed from the wall distance, the mesh and, under delayed DES, every pass 1)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -3264,8 +3352,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
         // a restart: a time level written is a time level held
-        if (which == MGCFD_ARR_TIME_N) s->dual_levels = std::max(s->dual_levels, 1);
-        if (which == MGCFD_ARR_TIME_N1) s->dual_levels = 2;
+        if (which == MGCFD_ARR_TIME_N || which == MGCFD_ARR_SA_TIME_N) s->dual_levels = std::max(s->dual_levels, 1);
+        if (which == MGCFD_ARR_TIME_N1 || which == MGCFD_ARR_SA_TIME_N1) s->dual_levels = 2;
         // a restart: mut of the new nt and the level's state, as the enabling call forms it
         if (which == MGCFD_ARR_SA_NU_TILDE) { s->sa_form(lv, false); HIP_CHECK(hipStreamSynchronize(s->stream)); }
     });
@@ -3298,9 +3386,12 @@ int mgcfd_array_written(mgcfd_solver *s, int level, int which)
             throw std::invalid_argument("MGCFD_ARR_EDDY_VISCOSITY: read-only under the Spalart-Allmaras model (formed from MGCFD_ARR_SA_NU_TILDE)");
         if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
         if (which == MGCFD_ARR_VISCOUS_GRADIENT) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: read-only (every flux launch of the level overwrites it)");
+        if (which == MGCFD_ARR_SA_LENGTH) throw std::invalid_argument("MGCFD_ARR_SA_LENGTH: read-only (formed from the wall distance, the mesh and, under delayed DES, every pass 1)");
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
         if (which == MGCFD_ARR_SA_NU_TILDE) { s->use_device(); s->sa_form(lv, false); }
+        if (which == MGCFD_ARR_SA_TIME_N) s->dual_levels = std::max(s->dual_levels, 1);
+        if (which == MGCFD_ARR_SA_TIME_N1) s->dual_levels = 2;
     });
 }
 // One level per rank: take a restricted `variables` array computed by the rank that holds the finer level.
@@ -6028,6 +6119,34 @@ int mgcfd_get_sa_free_stream(const mgcfd_solver *s, double *ratio)
     if (ratio) *ratio = s->sa_ratio;
     return MGCFD_OK;
 }
+// ---- the unsteady model: nt under dual time stepping, the DES97 and delayed-DES lengths (INTEGRATION.md "Unsteady Spalart-Allmaras") ----
+int mgcfd_set_sa_unsteady(mgcfd_solver *s, int time_accurate, int length, double c_des)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (time_accurate != 0 && time_accurate != 1) throw std::invalid_argument("unsteady Spalart-Allmaras: time_accurate must be 0 or 1");
+        if (length != MGCFD_SA_LENGTH_WALL && length != MGCFD_SA_LENGTH_DES && length != MGCFD_SA_LENGTH_DDES)
+            throw std::invalid_argument("unsteady Spalart-Allmaras: length must be MGCFD_SA_LENGTH_WALL, MGCFD_SA_LENGTH_DES or MGCFD_SA_LENGTH_DDES");
+        if (!std::isfinite(c_des) || !(c_des > 0.0)) throw std::invalid_argument("unsteady Spalart-Allmaras: c_des must be finite and positive");
+        if (s->partitioned || s->comm)
+            throw std::invalid_argument("unsteady Spalart-Allmaras: not on a partitioned solver, a group member or a rank (the model does not run there)");
+        if (!time_accurate && s->dual_time() && s->sa_in_effect())
+            throw std::invalid_argument("unsteady Spalart-Allmaras: time_accurate cannot go off while dual time stepping is on and the model is in effect (nu_tilde would have no BDF source)");
+        quiesce(s, "unsteady Spalart-Allmaras");
+        const bool length_changed = length != s->sa_length || c_des != s->sa_cdes;
+        s->sa_time_accurate = time_accurate; s->sa_length = length; s->sa_cdes = c_des;
+        settle_sa_unsteady(s, length_changed);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_sa_unsteady(const mgcfd_solver *s, int *time_accurate, int *length, double *c_des)
+{
+    REQUIRE(s);
+    if (time_accurate) *time_accurate = s->sa_time_accurate;
+    if (length) *length = s->sa_length;
+    if (c_des) *c_des = s->sa_cdes;
+    return MGCFD_OK;
+}
 int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
 {
     REQUIRE(s); REQUIRE(avg_seconds);
@@ -6039,10 +6158,10 @@ int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *a
         if ((kind == 2) != (level > 0)) throw std::invalid_argument("Spalart-Allmaras launch kind: the gradient and the transport run on level 0, the restriction into a level >= 1");
         if (kind == 2) { *avg_seconds = s->timed_launches(launches, [&] { s->sa_restrict(level); }); return; }
         const SaStep a = s->sa_step(lv);
-        launch_sa_gradient(s->stream, lv.dp, a);            // (every array holds a stage's numbers; the transport writes the spare buffer: nt stays)
-        *avg_seconds = s->timed_launches(launches, [&] {
-            if (kind == 0) launch_sa_gradient(s->stream, lv.dp, a);
-            else launch_sa_transport(s->stream, lv.dp, a, lv.fg_x);
+        s->sa_gradient(lv);                                 // (every array holds a stage's numbers; the transport writes the spare buffer: nt stays)
+        *avg_seconds = s->timed_launches(launches, [&] {    // (the instantiations the settings select)
+            if (kind == 0) s->sa_gradient(lv);
+            else s->sa_launch_transport(lv, a);
         });
     });
 }
@@ -6106,8 +6225,8 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         if (on && (!std::isfinite(clamp) || !(clamp > 0.0))) throw std::invalid_argument("dual time: the clamp must be finite and positive");
         if (on && (s->partitioned || s->comm))
             throw std::invalid_argument("dual time: not on a partitioned solver or a rank (levels split over ranks are out of scope)");
-        if (on && s->vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS)
-            throw std::invalid_argument("dual time: not while the Spalart-Allmaras model is selected (nu_tilde has no BDF source)");
+        if (on && s->vm_eddy == MGCFD_EDDY_SPALART_ALLMARAS && !s->sa_time_accurate)
+            throw std::invalid_argument("dual time: not while the Spalart-Allmaras model is selected (nu_tilde has no BDF source; mgcfd_set_sa_unsteady with time_accurate gives it one)");
         quiesce(s, "dual time");
         if (on && !s->dual_time()) {
             // switched on: both levels start as the current state (sweeps before the first begin_step see BDF1 against it)
@@ -6128,6 +6247,7 @@ int mgcfd_set_dual_time(mgcfd_solver *s, double dt, double clamp)
         }
         s->dual_dt = dt;
         s->dual_clamp = on ? clamp : 0.0;
+        settle_sa_unsteady(s);
         settle_rms_order(s);
         drop_look_ahead(s);
     });
@@ -6159,6 +6279,8 @@ int mgcfd_dual_time_reset(mgcfd_solver *s)
         require_dual_time(s, "mgcfd_dual_time_reset");
         require_no_sweep_under_way(s, "dual time");
         s->dual_levels = 0;
+        DeviceLevel &l0 = s->L[0];
+        if (l0.sa_ntn) { s->use_device(); launch_dual_shift(s->stream, l0.dp.stride, l0.sa_nt, l0.sa_ntn, l0.sa_ntn1, 1); }   // (nt's time levels: nt)
     });
 }
 // Wn1 <- Wn, Wn <- variables on every level (the first step: both <- variables); asynchronous on the solver's stream
@@ -6168,6 +6290,14 @@ static void dual_begin_step(mgcfd_solver *s)
     require_no_sweep_under_way(s, "dual time");
     for (DeviceLevel &lv : s->L)
         launch_dual_shift(s->stream, 5 * lv.dp.stride, lv.q, lv.time_n, lv.time_n1, s->dual_levels == 0 ? 1 : 0);
+    DeviceLevel &l0 = s->L[0];
+    if (l0.sa_ntn) {
+        launch_dual_shift(s->stream, l0.dp.stride, l0.sa_nt, l0.sa_ntn, l0.sa_ntn1, s->dual_levels == 0 ? 1 : 0);   // (nt beside the state)
+        // mut as a write of nt forms it, on every covered level: the step limit of the step's first sweep reads the array as it
+        // stands, and so a physical step is a function of variables, Wn, Wn1, nt, ntn and ntn1 alone (a restart continues in bits)
+        for (int l = 0; l < static_cast<int>(s->L.size()); l++)
+            if (s->sa_on(l)) s->sa_form(s->L[static_cast<size_t>(l)], false);
+    }
     s->dual_levels = s->dual_levels == 0 ? 1 : 2;
 }
 int mgcfd_dual_time_begin_step(mgcfd_solver *s) { OP(dual_begin_step(s)); }

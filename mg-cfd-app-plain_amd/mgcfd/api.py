@@ -26,9 +26,9 @@ LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
        "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16,
-       "sa_nu_tilde": 17, "sa_gradient": 18, "viscous_gradient": 19}
+       "sa_nu_tilde": 17, "sa_gradient": 18, "viscous_gradient": 19, "sa_time_n": 20, "sa_time_n1": 21, "sa_length": 22}
 NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1,
-         "sa_nu_tilde": 1, "sa_gradient": 5, "viscous_gradient": 12}    # (every other array: NVAR)
+         "sa_nu_tilde": 1, "sa_gradient": 5, "viscous_gradient": 12, "sa_time_n": 1, "sa_time_n1": 1, "sa_length": 1}    # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -226,6 +226,8 @@ _SIGNATURES = [
     ("mgcfd_set_sa_free_stream", C.c_int, [_vp, C.c_double, C.c_int]),
     ("mgcfd_get_sa_free_stream", C.c_int, [_vp, C.POINTER(C.c_double)]),
     ("mgcfd_bench_sa", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_sa_unsteady", C.c_int, [_vp, C.c_int, C.c_int, C.c_double]),
+    ("mgcfd_get_sa_unsteady", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("mgcfd_set_wall_temperature", C.c_int, [_vp, C.c_int, C.c_double]),
     ("mgcfd_get_wall_temperature", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("mgcfd_free_stream_temperature", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -454,6 +456,8 @@ _EDDY_MODES = {"none": 0, "field": 1, "smagorinsky": 2}   # MGCFD_EDDY_*
 _TRANSPORTED_EDDY_MODES = {"spalart-allmaras": 4}         # MGCFD_EDDY_SPALART_ALLMARAS: a model with a transported quantity of its own
 _ALL_EDDY_MODES = {**_EDDY_MODES, **_TRANSPORTED_EDDY_MODES}
 SA_RATIO = 3.0                                      # MGCFD_SA_RATIO
+SA_CDES = 0.65                                      # MGCFD_SA_CDES
+_SA_LENGTHS = {"wall": 0, "des": 1, "ddes": 2}      # MGCFD_SA_LENGTH_*
 
 
 WALL_HEAT_COLUMNS = 3     # MGCFD_WALL_HEAT_COLUMNS: h | T | area
@@ -821,6 +825,20 @@ class Solver:
         r = C.c_double()
         self._c(self.lib.mgcfd_get_sa_free_stream(self.handle, C.byref(r)))
         return r.value
+
+    def set_sa_unsteady(self, time_accurate: bool = False, length="wall", c_des: float = SA_CDES):
+        """The unsteady Spalart-Allmaras model (mgcfd_set_sa_unsteady).  ``time_accurate`` lets the model and ``set_dual_time`` be on
+        together: ``nu_tilde`` then takes the BDF source of the physical step, with its time levels in ``"sa_time_n"`` and
+        ``"sa_time_n1"`` (``advance`` and ``begin_step`` shift them beside the state's).  ``length``: ``"wall"`` (the wall distance),
+        ``"des"`` (DES97: ``min(d, c_des * delta)``) or ``"ddes"`` (delayed DES, shielded by ``fd``); the model length is the
+        read-only ``"sa_length"`` on level 0.  Kept while the model or the viscous terms are off."""
+        self._c(self.lib.mgcfd_set_sa_unsteady(self.handle, int(bool(time_accurate)), int(_SA_LENGTHS.get(length, length)), float(c_des)))
+
+    def sa_unsteady(self) -> dict:
+        """``{"time_accurate", "length", "c_des"}`` in use (mgcfd_get_sa_unsteady)."""
+        t, m, c = C.c_int(), C.c_int(), C.c_double()
+        self._c(self.lib.mgcfd_get_sa_unsteady(self.handle, C.byref(t), C.byref(m), C.byref(c)))
+        return {"time_accurate": bool(t.value), "length": {v: k for k, v in _SA_LENGTHS.items()}[m.value], "c_des": c.value}
 
     def bench_sa(self, l: int, kind, launches: int) -> float:
         """Mean GPU seconds of one launch of the Spalart-Allmaras model's ``"gradient"`` or ``"transport"`` kernel (level 0) or of
