@@ -905,6 +905,77 @@ int mgcfd_bench_sa(mgcfd_solver *s, int level, int kind, int launches, double *a
 int mgcfd_set_sa_unsteady(mgcfd_solver *s, int time_accurate, int length, double c_des);
 int mgcfd_get_sa_unsteady(const mgcfd_solver *s, int *time_accurate, int *length, double *c_des);
 /* ---------------------------------------------------------------------------------
+ * Flow statistics: time means and resolved Reynolds stresses of level 0, accumulated on the device.  No reference counterpart;
+ * INTEGRATION.md "Flow statistics" holds the definition.  Off by default, per solver: a solver that never calls
+ * mgcfd_set_statistics allocates nothing and launches what it launched.
+ *
+ * A sample is level 0's current `variables` taken with a weight w > 0.  For node i, by k_wall_distribution's expressions:
+ *     u = mx / rho;  v = my / rho;  w_ = mz / rho;  speed_sqd = u*u + v*v + w_*w_;  p = (gamma - 1) * (en - 0.5 * rho * speed_sqd)
+ *     x = (rho, u, v, w_, p, mut),  mut = MGCFD_ARR_EDDY_VISCOSITY[i] where level 0 holds an eddy viscosity in effect, else +0.0
+ *     (the array is then not read).
+ * Per solver: samples (int64) and wsum (double, from +0.0).  Per node: six means m[0..5] and seven co-moments c[0..6] for the
+ * pairs uu vv ww uv uw vw pp, all from +0.0.  On the host, in double, never contracted:
+ *     wsum_new = wsum + w;  a = w / wsum_new          (both reach the kernel as arguments: no division by the weight on the device)
+ * Per node, every operation one IEEE-754 double operation in this association, never contracted whatever MGCFD_OPT_EXACT says:
+ *     d[k] = x[k] - m[k]                 k = 0..5      (against the OLD mean)
+ *     m[k] = m[k] + a * d[k]
+ *     e[k] = x[k] - m[k]                 k = 1..4      (against the NEW mean)
+ *     c[pair(r,s)] = c[pair(r,s)] + (w * d[r]) * e[s]  (r,s) over (u,u) (v,v) (w,w) (u,v) (u,w) (v,w) (p,p)
+ * (West's weighted incremental form.)  The first sample gives m = x, up to the sign of a zero, and c = +0.0; a constant signal keeps
+ * c at exact zeros.  The Reynolds stresses are c / wsum.  Averages are plain (Reynolds) averages of the primitives, not Favre averages.
+ *
+ * Wall statistics (MGCFD_STATISTICS_VOLUME_AND_WALL): for every wall node of level 0 the dp | tx ty tz columns of
+ * mgcfd_wall_distribution's row for the same state, four means and the four per-column second moments (w * d[k]) * e[k] by the same
+ * recurrence with the same a and w: a table [n_wall][8] = mean dp tx ty tz | M2 dp tx ty tz in mgcfd_wall_distribution's order
+ * (t = +0.0 where the viscous terms are off).  A sample launches the wall-stress and wall-distribution kernels into a table of the
+ * solver's own, then the per-wall-node accumulation.
+ *
+ * While a mode is on, mgcfd_advance and its _loads_viscous / _loads_heat forms take one sample with weight = dt (the physical step
+ * in effect) after every physical step whose cycles completed, behind the loads launch and without a synchronisation of their own; a
+ * step that goes invalid is not sampled.  mgcfd_statistics_sample works with or without dual time stepping.  The setting survives
+ * mgcfd_set_viscous, mgcfd_set_viscosity_model, mgcfd_set_dual_time and mgcfd_set_free_stream in any order: the mut column follows
+ * whether an eddy viscosity is in effect at the sample.
+ *
+ * MGCFD_ARR_STATISTICS_MEAN / _MOMENTS (level 0, while a mode is on) are readable and writable like the time levels (mgcfd_get_array,
+ * mgcfd_set_array, mgcfd_array_devptr + mgcfd_array_written).  A restart: mgcfd_set_statistics, mgcfd_set_array of the two arrays,
+ * mgcfd_statistics_restore(samples, wsum) and, in mode 2, mgcfd_set_wall_statistics; the run then continues in bits.
+ *
+ * MGCFD_ERR_ARG, and nothing changed: a mode outside 0..2; the arrays, a sample, a reset or a restore while the mode is off; a weight
+ * not finite or <= 0; a restore with samples < 0, wsum negative or not finite, or exactly one of the two zero; the wall calls outside
+ * mode 2 (a level without solid walls: n = 0, nothing launched); a solver made by mgcfd_create_partitioned* or attached to a group or
+ * as a rank; a kernel-granular sweep under way.
+ * Out of scope: Favre averages; triple correlations and budgets; temperature and nu_tilde means; phase or windowed averages and a
+ * sampling interval; point probes and spectra; load statistics; coarse levels; partitioned levels, groups and ranks; captured graphs
+ * containing the sample launch.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_ARR_STATISTICS_MEAN    23   /* [nel][6]  rho u v w p mut            level 0, while statistics are on */
+#define MGCFD_ARR_STATISTICS_MOMENTS 24   /* [nel][7]  uu vv ww uv uw vw pp (co-moments, not yet divided by wsum) */
+#define MGCFD_STATISTICS_OFF 0
+#define MGCFD_STATISTICS_VOLUME 1
+#define MGCFD_STATISTICS_VOLUME_AND_WALL 2
+#define MGCFD_WALL_STATISTICS_COLUMNS 8
+/* 0 releases everything; 1 / 2 allocate (zeroed, samples = 0, wsum = +0.0); 1 <-> 2 keeps the volume accumulators and (re)zeroes the
+ * wall table.  Synchronises. */
+int mgcfd_set_statistics(mgcfd_solver *s, int mode);
+int mgcfd_get_statistics(const mgcfd_solver *s, int *mode, int64_t *samples, double *wsum);
+/* accumulators, samples and wsum back to zero; asynchronous on the solver's stream */
+int mgcfd_statistics_reset(mgcfd_solver *s);
+/* one sample of level 0's current state; asynchronous on the solver's stream */
+int mgcfd_statistics_sample(mgcfd_solver *s, double weight);
+/* a restart: after mgcfd_set_array of the two arrays */
+int mgcfd_statistics_restore(mgcfd_solver *s, int64_t samples, double wsum);
+/* node_ids [n] (may be NULL) and out [n][MGCFD_WALL_STATISTICS_COLUMNS], n = mgcfd_wall_node_count(s, 0); synchronises */
+int mgcfd_wall_statistics(mgcfd_solver *s, int64_t *node_ids, double *out);
+/* a restart: in [n][MGCFD_WALL_STATISTICS_COLUMNS] in mgcfd_wall_statistics' order */
+int mgcfd_set_wall_statistics(mgcfd_solver *s, const double *in);
+/* host only: out8 [n][8] = Ruu Rvv Rww Ruv Ruw Rvw | p_rms | k from moments7 [n][7]:
+ * R = c / wsum, p_rms = sqrt(cpp / wsum), k = 0.5 * ((Ruu + Rvv) + Rww).  wsum must be finite and positive. */
+int mgcfd_statistics_derive(double wsum, const double *moments7, int64_t n, double *out8);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of the volume sample (kind 0) or the wall accumulation (kind 1) on
+ * level 0's current state, as mgcfd_bench_viscous times its launches.  The launches run with a = w = 0.0, so the accumulators of a
+ * finite state stay as they are (up to the sign of a zero), as do samples and wsum.  Kind 1 needs mode 2 and a solid wall. */
+int mgcfd_bench_statistics(mgcfd_solver *s, int kind, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
  * Wall thermal conditions and heat loads.  No reference counterpart; INTEGRATION.md "Wall thermal conditions" holds the
  * definition.  Every operation is one IEEE-754 double operation (+ - * sqrt), never contracted whatever MGCFD_OPT_EXACT says.
  * Off by default: a solver that never calls mgcfd_set_wall_temperature launches what it launched and computes the same bits.

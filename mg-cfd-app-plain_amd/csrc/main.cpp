@@ -122,6 +122,11 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool dual_extras_given = false;   // one of the three companions was given (they need DT)
     double dual_dt = 0.0, dual_clamp = MGCFD_DUAL_TIME_CLAMP;
     int time_steps = 1, bdf_order = 2;
+    // flow statistics (mgcfd_set_statistics): --output-statistics writes statistics.* (and, with --output-surface,
+    // surface_statistics.*) from the samples mgcfd_advance takes; --statistics-start K: the first K physical steps are not sampled.
+    // Dual-time runs on one GPU only.
+    bool output_statistics = false, statistics_start_given = false;
+    int statistics_start = 0;
     int steps() const { return dual_given ? time_steps : 1; }
     int total_cycles() const { return (num_cycles > 0 ? num_cycles : 0) * steps(); }      // RMS lines of the run
     int loads_rows() const { return dual_given ? time_steps : (num_cycles > 0 ? num_cycles : 0); }   // one row per physical step
@@ -553,7 +558,12 @@ void print_help()
         "  --time-steps=N                   its number of physical steps (default 1; config key time_steps)\n"
         "  --dual-time-clamp=X              the pseudo step is clamped to X * DT / volume (default 2/3; config key dual_time_clamp)\n"
         "  --bdf-order=1|2                  1 keeps the first-order formula throughout (default 2: BDF1 on the first step, then BDF2;\n"
-        "                                   config key bdf_order)\n");
+        "                                   config key bdf_order)\n"
+        "  --output-statistics              with --physical-time-step: time means and Reynolds stresses of level 0, one sample of\n"
+        "                                   weight DT per physical step, into statistics.* (CSV): node, x, y, z, the means of\n"
+        "                                   rho u v w p mut, Ruu Rvv Rww Ruv Ruw Rvw, p_rms, k.  With --output-surface also\n"
+        "                                   surface_statistics.* (CSV): mean and rms of Cp and Cf per wall node.  One GPU\n"
+        "  --statistics-start=K             the first K physical steps are not sampled (default 0; below --time-steps)\n");
 }
 
 bool parse_arguments(int argc, char **argv, Config &c)
@@ -629,6 +639,8 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"sa-time-accurate", no_argument, nullptr, 1056},
         {"sa-length", required_argument, nullptr, 1057},
         {"sa-cdes", required_argument, nullptr, 1058},
+        {"output-statistics", no_argument, nullptr, 1059},
+        {"statistics-start", required_argument, nullptr, 1060},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -869,6 +881,14 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 }
                 c.sa_unsteady_given = true;
                 break;
+            case 1059: c.output_statistics = true; break;
+            case 1060:
+                if (!parse_whole(optarg, 0, kMaxTimeSteps, &c.statistics_start)) {
+                    std::fprintf(stderr, "ERROR: --statistics-start=%s: expected a whole number 0 ... %d\n", optarg, kMaxTimeSteps);
+                    return false;
+                }
+                c.statistics_start_given = true;
+                break;
             default: std::printf("Unknown command line parameter '%c'\n", optc);
         }
     }
@@ -943,6 +963,22 @@ bool parse_arguments(int argc, char **argv, Config &c)
     if (c.face_gradient == MGCFD_FACE_GRADIENT_CORRECTED && !c.viscous_cfl_given) c.viscous_cfl = MGCFD_VISCOUS_CFL_CORRECTED;   // (the corrected operator is stiffer)
     if (c.dual_extras_given && !c.dual_given) {
         std::fprintf(stderr, "ERROR: --time-steps, --dual-time-clamp and --bdf-order need --physical-time-step DT (dual time stepping)\n");
+        return false;
+    }
+    if (c.statistics_start_given && !c.output_statistics) {
+        std::fprintf(stderr, "ERROR: --statistics-start needs --output-statistics (it is the step the statistics begin behind)\n");
+        return false;
+    }
+    if (c.output_statistics && !c.dual_given) {
+        std::fprintf(stderr, "ERROR: --output-statistics needs --physical-time-step DT (the statistics are time averages of a dual-time run)\n");
+        return false;
+    }
+    if (c.output_statistics && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: --output-statistics runs on one GPU only: not with --gpus N\n");
+        return false;
+    }
+    if (c.output_statistics && c.statistics_start >= c.time_steps) {
+        std::fprintf(stderr, "ERROR: --statistics-start=%d: must be below --time-steps (%d), or no step is sampled\n", c.statistics_start, c.time_steps);
         return false;
     }
     if (c.dual_given && (c.num_cycles < 1 || c.num_cycles > MGCFD_MAX_ADVANCE_CYCLES)) {
@@ -1228,6 +1264,81 @@ int write_surface_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh
         }
         std::fprintf(f, "\n");
     }
+    if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
+    return 0;
+}
+
+// --output-statistics: one row per node of level 0 in original order — id, coordinates, the means of rho u v w p mut, the resolved
+// Reynolds stresses, p_rms and k (mgcfd_statistics_derive) — and a last comment line with the samples and the sum of their weights
+int write_statistics_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh *mesh)
+{
+    int mode = 0;
+    int64_t samples = 0;
+    double wsum = 0.0;
+    mgcfd_level_desc desc;
+    if (mgcfd_get_statistics(solver, &mode, &samples, &wsum) != MGCFD_OK || mode == MGCFD_STATISTICS_OFF || mgcfd_mesh_level(mesh, 0, &desc) != MGCFD_OK)
+        return fail("reading the flow statistics");
+    const size_t nel = static_cast<size_t>(mgcfd_level_nel(solver, 0));
+    std::vector<double> mean(nel * 6), mom(nel * 7), derived(nel * 8);
+    if (mgcfd_get_array(solver, 0, MGCFD_ARR_STATISTICS_MEAN, mean.data()) != MGCFD_OK || mgcfd_get_array(solver, 0, MGCFD_ARR_STATISTICS_MOMENTS, mom.data()) != MGCFD_OK ||
+        mgcfd_statistics_derive(wsum, mom.data(), static_cast<int64_t>(nel), derived.data()) != MGCFD_OK)
+        return fail("reading the flow statistics");
+    std::string path = conf.output_file_prefix;
+    if (!path.empty() && path.back() != '/') path += ".";
+    path += "statistics.size=" + std::to_string(conf.mesh_duplicate_count) + "x.level=0";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail(("opening " + path).c_str());
+    std::fprintf(f, "node,x,y,z,rho,u,v,w,p,mut,Ruu,Rvv,Rww,Ruv,Ruw,Rvw,p_rms,k\n");
+    for (size_t i = 0; i < nel; i++) {
+        std::fprintf(f, "%ld", static_cast<long>(i));
+        for (size_t d = 0; d < 3; d++) std::fprintf(f, ",%.17e", desc.coords ? desc.coords[i * 3 + d] : 0.0);
+        for (size_t k = 0; k < 6; k++) std::fprintf(f, ",%.17e", mean[i * 6 + k]);
+        for (size_t k = 0; k < 8; k++) std::fprintf(f, ",%.17e", derived[i * 8 + k]);
+        std::fprintf(f, "\n");
+    }
+    std::fprintf(f, "# samples = %ld, wsum = %.17e\n", static_cast<long>(samples), wsum);
+    if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
+    return 0;
+}
+
+// ... with --output-surface: one row per wall node of level 0 — id, coordinates, the mean Cp and the tangential mean Cf (write_surface_csv's
+// expressions on the mean dp and t), the rms of Cp and, per component, the rms of t over |a| q_inf (the table holds no cross moments,
+// so the fluctuation is not projected) — and the same last line
+int write_surface_statistics_csv(const Config &conf, mgcfd_solver *solver, const mgcfd_mesh *mesh)
+{
+    int64_t n = 0, samples = 0;
+    double ff17[17], wsum = 0.0;
+    mgcfd_level_desc desc;
+    if (mgcfd_wall_node_count(solver, 0, &n) != MGCFD_OK || mgcfd_get_far_field(solver, ff17) != MGCFD_OK || mgcfd_mesh_level(mesh, 0, &desc) != MGCFD_OK ||
+        mgcfd_get_statistics(solver, nullptr, &samples, &wsum) != MGCFD_OK)
+        return fail("reading the wall statistics");
+    std::vector<int64_t> ids(static_cast<size_t>(n));
+    std::vector<double> dist(static_cast<size_t>(n) * MGCFD_WALL_COLUMNS), table(static_cast<size_t>(n) * MGCFD_WALL_STATISTICS_COLUMNS);
+    if (n > 0 && (mgcfd_wall_distribution(solver, 0, ids.data(), dist.data()) != MGCFD_OK || mgcfd_wall_statistics(solver, nullptr, table.data()) != MGCFD_OK))
+        return fail("reading the wall statistics");
+    const double vx = ff17[1] / ff17[0], vy = ff17[2] / ff17[0], vz = ff17[3] / ff17[0];
+    const double q = 0.5 * ff17[0] * (vx * vx + vy * vy + vz * vz);
+    std::string path = conf.output_file_prefix;
+    if (!path.empty() && path.back() != '/') path += ".";
+    path += "surface_statistics.size=" + std::to_string(conf.mesh_duplicate_count) + "x.level=0";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return fail(("opening " + path).c_str());
+    std::fprintf(f, "node,x,y,z,Cp_mean,Cfx_mean,Cfy_mean,Cfz_mean,Cp_rms,Cfx_rms,Cfy_rms,Cfz_rms\n");
+    for (int64_t k = 0; k < n; k++) {
+        const double *a = dist.data() + static_cast<size_t>(k) * MGCFD_WALL_COLUMNS;
+        const double *r = table.data() + static_cast<size_t>(k) * MGCFD_WALL_STATISTICS_COLUMNS;
+        const int64_t i = ids[static_cast<size_t>(k)];
+        const double area = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        const double nx = a[0] / area, ny = a[1] / area, nz = a[2] / area;
+        const double tn = r[1] * nx + r[2] * ny + r[3] * nz;
+        std::fprintf(f, "%ld", static_cast<long>(i));
+        for (int d = 0; d < 3; d++) std::fprintf(f, ",%.17e", desc.coords ? desc.coords[i * 3 + d] : 0.0);
+        std::fprintf(f, ",%.17e,%.17e,%.17e,%.17e", r[0] / q, (r[1] - tn * nx) / (area * q), (r[2] - tn * ny) / (area * q), (r[3] - tn * nz) / (area * q));
+        std::fprintf(f, ",%.17e", std::sqrt(r[4] / wsum) / q);
+        for (int d = 0; d < 3; d++) std::fprintf(f, ",%.17e", std::sqrt(r[5 + d] / wsum) / (area * q));
+        std::fprintf(f, "\n");
+    }
+    std::fprintf(f, "# samples = %ld, wsum = %.17e\n", static_cast<long>(samples), wsum);
     if (std::fclose(f) != 0) return fail(("writing " + path).c_str());
     return 0;
 }
@@ -1522,7 +1633,13 @@ int main(int argc, char **argv)
                 if (rc_on != MGCFD_OK) return rc_on;
                 const int per_call = std::max(1, MGCFD_MAX_ADVANCE_CYCLES / conf.num_cycles);
                 for (steps_done = 0; steps_done < conf.time_steps;) {
-                    const int now = std::min(per_call, conf.time_steps - steps_done);
+                    int now = std::min(per_call, conf.time_steps - steps_done);
+                    // --output-statistics: a call ends where the sampling begins, and the statistics go on behind it
+                    if (conf.output_statistics && steps_done < conf.statistics_start) now = std::min(now, conf.statistics_start - steps_done);
+                    if (conf.output_statistics && steps_done == conf.statistics_start) {
+                        const int rc_st = mgcfd_set_statistics(solver, conf.output_surface ? MGCFD_STATISTICS_VOLUME_AND_WALL : MGCFD_STATISTICS_VOLUME);
+                        if (rc_st != MGCFD_OK) return rc_st;
+                    }
                     double *const rms_at = rms_out + size_t(steps_done) * size_t(conf.num_cycles);
                     double *const loads_at = loads_out ? loads_out + size_t(steps_done) * conf.loads_width() : nullptr;
                     const int rc_adv = conf.loads_heat && loads_at ? mgcfd_advance_loads_heat(solver, now, conf.num_cycles, rms_at, loads_at, conf.loads_ref + 2)
@@ -1593,6 +1710,8 @@ int main(int argc, char **argv)
     }
     if (conf.polar && write_polar_csv(conf, polar_rows)) return EXIT_FAILURE;
     if (conf.output_surface && write_surface_csv(conf, solver, mesh)) return EXIT_FAILURE;
+    if (conf.output_statistics && write_statistics_csv(conf, solver, mesh)) return EXIT_FAILURE;
+    if (conf.output_statistics && conf.output_surface && write_surface_statistics_csv(conf, solver, mesh)) return EXIT_FAILURE;
 
     // ---- performance data (src/euler3d_cpu_double.cpp:778-785) ----
     std::string ih, il;

@@ -31,6 +31,7 @@
 #include "kernels.hpp"
 #include "kernels_face_gradient.hpp"
 #include "kernels_sa.hpp"
+#include "kernels_statistics.hpp"
 #include "kernels_wall_heat.hpp"
 #include "mesh.hpp"
 #include "mgcfd.h"
@@ -225,6 +226,11 @@ struct DeviceLevel {
     // the corrected face gradient (mgcfd_set_face_gradient), held while it is in effect on the level: G, me, kap [14][stride] and
     // the coordinates in the solver's numbering [3][stride]
     double *fg_g = nullptr, *fg_x = nullptr;
+    // the flow statistics (mgcfd_set_statistics), level 0 only, held while a mode is on: the means [6][stride] and the co-moments
+    // [7][stride]; in mode 2 on a level with solid walls also the wall table [n_wall][8] and the distribution table [n_wall][7] its
+    // samples are formed in
+    double *stat_mean = nullptr, *stat_mom = nullptr, *stat_wall = nullptr, *stat_dist = nullptr;
+    bool stat_made_wp = false;           // the wall plan below was first made for the wall statistics: it goes with them
     double *fas_p = nullptr, *fas_w0 = nullptr;     // [5][stride] each, levels >= 1 while FAS multigrid is on: the forcing P and the start state W0
     int32_t *new_of_old_dev = nullptr;   // [nel] level 0 while ordered_rms(): its RMS is summed in original numbering (settle_rms_order)
     double *step_factors = nullptr, *volumes = nullptr, *cbrt_vol = nullptr;                  // [stride]
@@ -518,6 +524,11 @@ struct mgcfd_solver {
     // The face gradient of the diffusion terms (mgcfd_set_face_gradient; INTEGRATION.md "Corrected face gradients"): kept like the
     // viscosity model; in effect on the levels the viscous terms cover.  Corrected: the node-gradient launch behind the stress
     // launch and the correction launch behind the viscous-flux launch, wherever the two run.
+    // The flow statistics (mgcfd_set_statistics; INTEGRATION.md "Flow statistics"): the mode, the samples taken and the sum of their
+    // weights.  The accumulators are level 0's (stat_mean, stat_mom, stat_wall).
+    int stat_mode = MGCFD_STATISTICS_OFF;
+    int64_t stat_samples = 0;
+    double stat_wsum = 0.0;
     int fg_mode = MGCFD_FACE_GRADIENT_AVERAGED;
     bool fg_on(int l) const { return fg_mode == MGCFD_FACE_GRADIENT_CORRECTED && viscous_on(l); }
     FaceGradientStep face_gradient_step(const DeviceLevel &lv) const
@@ -3289,6 +3300,10 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.fg_g) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: the corrected face gradient is not in effect on this level (mgcfd_set_face_gradient, on a level mgcfd_set_viscous covers)");
             *ncols = 12;
             return lv.fg_g;
+        case MGCFD_ARR_STATISTICS_MEAN: case MGCFD_ARR_STATISTICS_MOMENTS:
+            if (!lv.stat_mean) throw std::invalid_argument("MGCFD_ARR_STATISTICS_MEAN / _MOMENTS: level 0 while the flow statistics are on (mgcfd_set_statistics)");
+            *ncols = which == MGCFD_ARR_STATISTICS_MEAN ? 6 : 7;
+            return which == MGCFD_ARR_STATISTICS_MEAN ? lv.stat_mean : lv.stat_mom;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -6301,6 +6316,202 @@ static void dual_begin_step(mgcfd_solver *s)
     s->dual_levels = s->dual_levels == 0 ? 1 : 2;
 }
 int mgcfd_dual_time_begin_step(mgcfd_solver *s) { OP(dual_begin_step(s)); }
+
+// ---- flow statistics: time means and Reynolds stresses of level 0 (INTEGRATION.md "Flow statistics") ----
+static void statistics_require_whole(const mgcfd_solver *s)
+{
+    if (s->partitioned || s->comm)
+        throw std::invalid_argument("flow statistics: not on a partitioned solver, a group member or a rank (levels split over ranks are out of scope)");
+}
+static void statistics_require_on(const mgcfd_solver *s, const char *who)
+{
+    statistics_require_whole(s);
+    if (s->stat_mode == MGCFD_STATISTICS_OFF) throw std::invalid_argument(std::string(who) + ": the flow statistics are off (mgcfd_set_statistics)");
+    require_no_sweep_under_way(s, "flow statistics");
+}
+static void statistics_require_wall(const mgcfd_solver *s, const char *who)
+{
+    statistics_require_on(s, who);
+    if (s->stat_mode != MGCFD_STATISTICS_VOLUME_AND_WALL)
+        throw std::invalid_argument(std::string(who) + ": the wall statistics are off (mgcfd_set_statistics with MGCFD_STATISTICS_VOLUME_AND_WALL)");
+}
+// the wall table and the distribution table its samples are formed in: held exactly in mode 2 on a level with solid walls; zeroed
+static void statistics_settle_wall(mgcfd_solver *s)
+{
+    DeviceLevel &lv = s->L[0];
+    if (s->stat_mode != MGCFD_STATISTICS_VOLUME_AND_WALL || lv.n_wall_rec == 0) {
+        lv.mem.release(lv.stat_wall); lv.mem.release(lv.stat_dist);
+        if (lv.stat_made_wp) { lv.wp.reset(); lv.stat_made_wp = false; }   // (the next call that needs the plan makes it again)
+        return;
+    }
+    if (!lv.wp) lv.stat_made_wp = true;
+    const size_t n = static_cast<size_t>(wall_plan(s, lv).wn.n);
+    if (!lv.stat_wall) lv.stat_wall = lv.mem.alloc<double>(MGCFD_WALL_STATISTICS_COLUMNS * n);
+    if (!lv.stat_dist) lv.stat_dist = lv.mem.alloc<double>(MGCFD_WALL_COLUMNS * n);
+    HIP_CHECK(hipMemsetAsync(lv.stat_wall, 0, sizeof(double) * MGCFD_WALL_STATISTICS_COLUMNS * n, s->stream));
+}
+static void statistics_zero_volume(mgcfd_solver *s)
+{
+    DeviceLevel &lv = s->L[0];
+    const size_t stride = static_cast<size_t>(lv.dp.stride);
+    HIP_CHECK(hipMemsetAsync(lv.stat_mean, 0, sizeof(double) * 6 * stride, s->stream));
+    HIP_CHECK(hipMemsetAsync(lv.stat_mom, 0, sizeof(double) * 7 * stride, s->stream));
+}
+// the launches of one sample with the factors a and w: the volume accumulation, and in mode 2 on a level with solid walls the
+// wall-stress and wall-distribution launches into the solver's own table and the wall accumulation
+static void statistics_launch_volume(mgcfd_solver *s, double a, double w)
+{
+    DeviceLevel &lv = s->L[0];
+    const double *mut = (lv.visc_mut && lv.eddy_mode) ? lv.visc_mut : nullptr;
+    launch_statistics_sample(s->stream, lv.info.nel, lv.dp.stride, lv.q, mut, lv.stat_mean, lv.stat_mom, a, w);
+}
+static void statistics_launch_wall(mgcfd_solver *s, double a, double w, bool form = true)
+{
+    DeviceLevel &lv = s->L[0];
+    if (!lv.stat_wall) return;
+    if (form) {
+        const bool viscous = s->viscous_on(0);
+        if (viscous) launch_wall_stress(s, 0);
+        WallDistribution d;
+        d.wn = lv.wp->wn; d.rec = lv.wall_rec; d.p_inf = s->p_inf; d.sw = viscous ? lv.wp->sw : nullptr; d.out = lv.stat_dist;
+        launch_wall_distribution(s->stream, lv.dp.stride, lv.q, d);
+    }
+    launch_statistics_wall(s->stream, lv.wp->wn.n, lv.stat_dist, lv.stat_wall, a, w);
+}
+// one sample of level 0's current state with weight w (checked by the caller); asynchronous on the solver's stream
+static void statistics_sample(mgcfd_solver *s, double w)
+{
+    s->use_device();
+    const double wsum_new = s->stat_wsum + w;
+    const double a = w / wsum_new;
+    statistics_launch_volume(s, a, w);
+    statistics_launch_wall(s, a, w);
+    HIP_CHECK(hipGetLastError());
+    s->stat_wsum = wsum_new;
+    s->stat_samples++;
+}
+int mgcfd_set_statistics(mgcfd_solver *s, int mode)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (mode != MGCFD_STATISTICS_OFF && mode != MGCFD_STATISTICS_VOLUME && mode != MGCFD_STATISTICS_VOLUME_AND_WALL)
+            throw std::invalid_argument("flow statistics: the mode is MGCFD_STATISTICS_OFF, MGCFD_STATISTICS_VOLUME or MGCFD_STATISTICS_VOLUME_AND_WALL");
+        statistics_require_whole(s);
+        quiesce(s, "flow statistics");
+        DeviceLevel &lv = s->L[0];
+        const int was = s->stat_mode;
+        s->stat_mode = mode;
+        if (mode == MGCFD_STATISTICS_OFF) {
+            lv.mem.release(lv.stat_mean); lv.mem.release(lv.stat_mom);
+            s->stat_samples = 0; s->stat_wsum = 0.0;
+        } else if (was == MGCFD_STATISTICS_OFF) {
+            const size_t stride = static_cast<size_t>(lv.dp.stride);
+            lv.stat_mean = lv.mem.alloc<double>(6 * stride);
+            lv.stat_mom = lv.mem.alloc<double>(7 * stride);
+            statistics_zero_volume(s);
+            s->stat_samples = 0; s->stat_wsum = 0.0;
+        }
+        statistics_settle_wall(s);
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_statistics(const mgcfd_solver *s, int *mode, int64_t *samples, double *wsum)
+{
+    REQUIRE(s);
+    if (mode) *mode = s->stat_mode;
+    if (samples) *samples = s->stat_samples;
+    if (wsum) *wsum = s->stat_wsum;
+    return MGCFD_OK;
+}
+int mgcfd_statistics_reset(mgcfd_solver *s)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        statistics_require_on(s, "mgcfd_statistics_reset");
+        s->use_device();
+        statistics_zero_volume(s);
+        DeviceLevel &lv = s->L[0];
+        if (lv.stat_wall)
+            HIP_CHECK(hipMemsetAsync(lv.stat_wall, 0, sizeof(double) * MGCFD_WALL_STATISTICS_COLUMNS * static_cast<size_t>(lv.wp->wn.n), s->stream));
+        s->stat_samples = 0; s->stat_wsum = 0.0;
+    });
+}
+int mgcfd_statistics_sample(mgcfd_solver *s, double weight)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        statistics_require_on(s, "mgcfd_statistics_sample");
+        if (!std::isfinite(weight) || !(weight > 0.0)) throw std::invalid_argument("mgcfd_statistics_sample: the weight must be finite and positive");
+        statistics_sample(s, weight);
+    });
+}
+int mgcfd_statistics_restore(mgcfd_solver *s, int64_t samples, double wsum)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        statistics_require_on(s, "mgcfd_statistics_restore");
+        if (samples < 0) throw std::invalid_argument("mgcfd_statistics_restore: samples must be >= 0");
+        if (!std::isfinite(wsum) || wsum < 0.0) throw std::invalid_argument("mgcfd_statistics_restore: wsum must be finite and >= 0");
+        if ((samples == 0) != (wsum == 0.0)) throw std::invalid_argument("mgcfd_statistics_restore: samples and wsum are zero together or not at all");
+        s->stat_samples = samples;
+        s->stat_wsum = wsum == 0.0 ? 0.0 : wsum;           // (+0.0)
+    });
+}
+int mgcfd_wall_statistics(mgcfd_solver *s, int64_t *node_ids, double *out)
+{
+    REQUIRE(s); REQUIRE(out);
+    return guarded([&] {
+        statistics_require_wall(s, "mgcfd_wall_statistics");
+        wall_table(s, 0, node_ids, out, MGCFD_WALL_STATISTICS_COLUMNS, [&](DeviceLevel &lv, WallPlan &) { return lv.stat_wall; });
+    });
+}
+int mgcfd_set_wall_statistics(mgcfd_solver *s, const double *in)
+{
+    REQUIRE(s); REQUIRE(in);
+    return guarded([&] {
+        statistics_require_wall(s, "mgcfd_set_wall_statistics");
+        s->use_device();
+        DeviceLevel &lv = s->L[0];
+        if (!lv.stat_wall) return;                          // (no solid wall: n = 0)
+        HIP_CHECK(hipMemcpyAsync(lv.stat_wall, in, sizeof(double) * MGCFD_WALL_STATISTICS_COLUMNS * static_cast<size_t>(lv.wp->wn.n), hipMemcpyHostToDevice, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+    });
+}
+int mgcfd_statistics_derive(double wsum, const double *moments7, int64_t n, double *out8)
+{
+    REQUIRE(moments7); REQUIRE(out8);
+    if (!std::isfinite(wsum) || !(wsum > 0.0) || n < 0) {
+        g_last_error = "mgcfd_statistics_derive: wsum must be finite and positive, n >= 0";
+        return MGCFD_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const double *c = moments7 + 7 * i;
+        double *o = out8 + 8 * i;
+        for (int k = 0; k < 6; k++) o[k] = c[k] / wsum;
+        o[6] = std::sqrt(c[6] / wsum);
+        o[7] = 0.5 * ((o[0] + o[1]) + o[2]);
+    }
+    return MGCFD_OK;
+}
+int mgcfd_bench_statistics(mgcfd_solver *s, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        statistics_require_on(s, "mgcfd_bench_statistics");
+        if (kind < 0 || kind > 1) throw std::invalid_argument("flow statistics launch kind: 0 volume sample, 1 wall accumulation");
+        s->use_device();
+        if (kind == 1) {
+            statistics_require_wall(s, "mgcfd_bench_statistics");
+            if (!s->L[0].stat_wall) throw std::invalid_argument("the level has no solid-wall edge");
+            statistics_launch_wall(s, 0.0, 0.0);            // (the distribution table holds the current state's rows)
+        }
+        *avg_seconds = s->timed_launches(launches, [&] {
+            if (kind == 0) statistics_launch_volume(s, 0.0, 0.0);
+            else statistics_launch_wall(s, 0.0, 0.0, false);
+        });
+    });
+}
 // friction (mgcfd_advance_loads_viscous): rows of twelve, every step's launches store into a row of the twelve-wide history on
 // the device and the rows are read back when it is full and at the end
 // heat (with friction: mgcfd_advance_loads_heat): rows of fourteen in the fourteen-wide history
@@ -6341,11 +6552,18 @@ static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double 
         rc = mgcfd_dual_time_begin_step(s);
         if (rc == MGCFD_OK) rc = run_cycles_impl(s, cycles_per_step, rms, nullptr, nullptr);
         if (rc == MGCFD_OK && loads_out && !friction) rc = mgcfd_surface_loads(s, 0, ref_point, loads_out + size_t(step) * 6);
+        // the flow statistics: one sample of the completed step with weight dt, behind the loads launch
+        const auto sample = [&] { if (s->stat_mode != MGCFD_STATISTICS_OFF) statistics_sample(s, s->dual_dt); };
         if (rc == MGCFD_OK && loads_out && friction && s->L[0].n_wall_rec > 0) {
-            rc = guarded([&] { s->use_device(); launch_loads_viscous(s, 0, (heat ? s->loads_ring14 : s->loads_ring12) + size_t(held) * width, heat); });
+            rc = guarded([&] {
+                s->use_device();
+                launch_loads_viscous(s, 0, (heat ? s->loads_ring14 : s->loads_ring12) + size_t(held) * width, heat);
+                sample();
+            });
             if (rc == MGCFD_OK) held++;
             if (rc == MGCFD_OK && (held == mgcfd_solver::kRmsRing || step + 1 == steps)) rc = read_rows(step);
         }
+        else if (rc == MGCFD_OK) rc = guarded(sample);
         if (rc == MGCFD_OK) continue;
         if (friction && loads_out) (void)read_rows(step - 1);      // (the steps that completed keep their rows)
         // as mgcfd_run_cycles: what did not complete is NaN (the failing step's RMS entries are already), later steps do not run

@@ -26,9 +26,11 @@ LOOPS = ("flux", "update", "compute_step", "time_step", "restrict", "prolong", "
 ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_factors": 4, "volumes": 5, "stage": 6,
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
        "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16,
-       "sa_nu_tilde": 17, "sa_gradient": 18, "viscous_gradient": 19, "sa_time_n": 20, "sa_time_n1": 21, "sa_length": 22}
+       "sa_nu_tilde": 17, "sa_gradient": 18, "viscous_gradient": 19, "sa_time_n": 20, "sa_time_n1": 21, "sa_length": 22,
+       "statistics_mean": 23, "statistics_moments": 24}
 NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1,
-         "sa_nu_tilde": 1, "sa_gradient": 5, "viscous_gradient": 12, "sa_time_n": 1, "sa_time_n1": 1, "sa_length": 1}    # (every other array: NVAR)
+         "sa_nu_tilde": 1, "sa_gradient": 5, "viscous_gradient": 12, "sa_time_n": 1, "sa_time_n1": 1, "sa_length": 1,
+         "statistics_mean": 6, "statistics_moments": 7}    # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
@@ -228,6 +230,15 @@ _SIGNATURES = [
     ("mgcfd_bench_sa", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_sa_unsteady", C.c_int, [_vp, C.c_int, C.c_int, C.c_double]),
     ("mgcfd_get_sa_unsteady", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("mgcfd_set_statistics", C.c_int, [_vp, C.c_int]),
+    ("mgcfd_get_statistics", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_double)]),
+    ("mgcfd_statistics_reset", C.c_int, [_vp]),
+    ("mgcfd_statistics_sample", C.c_int, [_vp, C.c_double]),
+    ("mgcfd_statistics_restore", C.c_int, [_vp, _i64, C.c_double]),
+    ("mgcfd_wall_statistics", C.c_int, [_vp, _vp, _vp]),
+    ("mgcfd_set_wall_statistics", C.c_int, [_vp, _vp]),
+    ("mgcfd_statistics_derive", C.c_int, [C.c_double, _vp, _i64, _vp]),
+    ("mgcfd_bench_statistics", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_wall_temperature", C.c_int, [_vp, C.c_int, C.c_double]),
     ("mgcfd_get_wall_temperature", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("mgcfd_free_stream_temperature", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -458,6 +469,8 @@ _ALL_EDDY_MODES = {**_EDDY_MODES, **_TRANSPORTED_EDDY_MODES}
 SA_RATIO = 3.0                                      # MGCFD_SA_RATIO
 SA_CDES = 0.65                                      # MGCFD_SA_CDES
 _SA_LENGTHS = {"wall": 0, "des": 1, "ddes": 2}      # MGCFD_SA_LENGTH_*
+_STATISTICS_MODES = {"off": 0, "volume": 1, "wall": 2}   # MGCFD_STATISTICS_*
+WALL_STATISTICS_COLUMNS = 8                         # MGCFD_WALL_STATISTICS_COLUMNS: mean dp tx ty tz | M2 dp tx ty tz
 
 
 WALL_HEAT_COLUMNS = 3     # MGCFD_WALL_HEAT_COLUMNS: h | T | area
@@ -845,6 +858,67 @@ class Solver:
         its ``"restrict"`` kernel into level ``l >= 1`` (mgcfd_bench_sa)."""
         t = C.c_double()
         self._c(self.lib.mgcfd_bench_sa(self.handle, l, {"gradient": 0, "transport": 1, "restrict": 2}.get(kind, kind), launches, C.byref(t)))
+        return t.value
+
+    # ---- flow statistics ----
+    def set_statistics(self, mode="volume"):
+        """The flow statistics of level 0 (mgcfd_set_statistics): ``"off"``, ``"volume"`` (time means of ``rho u v w p mut`` in
+        ``"statistics_mean"`` and the co-moments ``uu vv ww uv uw vw pp`` in ``"statistics_moments"``) or ``"wall"`` (those and the
+        mean and second moment of ``dp | tx ty tz`` per wall node, ``wall_statistics``).  While a mode is on ``advance`` takes one
+        sample with weight ``dt`` after every completed physical step; ``statistics_sample`` takes one by hand."""
+        self._c(self.lib.mgcfd_set_statistics(self.handle, int(_STATISTICS_MODES.get(mode, mode))))
+
+    def statistics(self) -> dict:
+        """``{"mode", "samples", "wsum"}`` (mgcfd_get_statistics); the mode by name."""
+        m, n, w = C.c_int(), _i64(), C.c_double()
+        self._c(self.lib.mgcfd_get_statistics(self.handle, C.byref(m), C.byref(n), C.byref(w)))
+        return {"mode": {v: k for k, v in _STATISTICS_MODES.items()}[m.value], "samples": n.value, "wsum": w.value}
+
+    def statistics_reset(self):
+        """Accumulators, samples and wsum back to zero (mgcfd_statistics_reset)."""
+        self._c(self.lib.mgcfd_statistics_reset(self.handle))
+
+    def statistics_sample(self, weight: float):
+        """One sample of level 0's current state with ``weight > 0`` (mgcfd_statistics_sample)."""
+        self._c(self.lib.mgcfd_statistics_sample(self.handle, float(weight)))
+
+    def statistics_restore(self, samples: int, wsum: float):
+        """A restart (mgcfd_statistics_restore): after ``set`` of the two arrays."""
+        self._c(self.lib.mgcfd_statistics_restore(self.handle, int(samples), float(wsum)))
+
+    def wall_statistics(self):
+        """``(ids [n], table [n, 8])`` of level 0's wall nodes (mgcfd_wall_statistics): the original ids, ascending, and per node
+        ``mean dp tx ty tz | M2 dp tx ty tz``; the variances are ``M2 / wsum``."""
+        n = self.wall_node_count(0)
+        ids, out = np.zeros(max(n, 1), dtype=np.int64), np.zeros((max(n, 1), WALL_STATISTICS_COLUMNS))
+        self._c(self.lib.mgcfd_wall_statistics(self.handle, _ptr(ids), _ptr(out)))
+        return ids[:n], out[:n]
+
+    def set_wall_statistics(self, table):
+        """A restart (mgcfd_set_wall_statistics): ``table [n, 8]`` in ``wall_statistics``' order."""
+        n = self.wall_node_count(0)
+        t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, WALL_STATISTICS_COLUMNS)
+        if len(t) != n:
+            raise ValueError(f"set_wall_statistics: {len(t)} rows for {n} wall nodes")
+        if n == 0:
+            t = np.zeros((1, WALL_STATISTICS_COLUMNS))
+        self._c(self.lib.mgcfd_set_wall_statistics(self.handle, _ptr(t)))
+
+    def flow_statistics(self) -> dict:
+        """``{"mean" [nel, 6], "reynolds" [nel, 6], "p_rms" [nel], "k" [nel], "samples", "wsum"}`` of level 0: the means of
+        ``rho u v w p mut``, the resolved Reynolds stresses ``uu vv ww uv uw vw``, the rms of the pressure fluctuation and the
+        resolved turbulent kinetic energy (mgcfd_statistics_derive on ``"statistics_moments"``)."""
+        st = self.statistics()
+        mean, mom = self.get(0, "statistics_mean"), np.ascontiguousarray(self.get(0, "statistics_moments"))
+        out = np.zeros((len(mom), 8))
+        self._c(self.lib.mgcfd_statistics_derive(st["wsum"], _ptr(mom), len(mom), _ptr(out)))
+        return {"mean": mean, "reynolds": out[:, :6].copy(), "p_rms": out[:, 6].copy(), "k": out[:, 7].copy(),
+                "samples": st["samples"], "wsum": st["wsum"]}
+
+    def bench_statistics(self, kind, launches: int) -> float:
+        """Mean GPU seconds of one launch of the ``"volume"`` sample or the ``"wall"`` accumulation (mgcfd_bench_statistics)."""
+        t = C.c_double()
+        self._c(self.lib.mgcfd_bench_statistics(self.handle, {"volume": 0, "wall": 1}.get(kind, kind), launches, C.byref(t)))
         return t.value
 
     def bench_wall_distance(self, l: int, launches: int) -> float:
