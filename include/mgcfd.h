@@ -1061,6 +1061,77 @@ int mgcfd_get_face_gradient(const mgcfd_solver *s, int *mode);
  * (kind 1; the level's fluxes keep accumulating: numbers, not a state) on a level the mode is in effect on, as
  * mgcfd_bench_viscous times its launches. */
 int mgcfd_bench_face_gradient(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
+/* ---------------------------------------------------------------------------------
+ * Upwind fluxes: limited MUSCL reconstruction and Roe's flux-difference splitting on the internal edges, per level.  No
+ * reference counterpart; INTEGRATION.md "Upwind fluxes" (§23) holds the same definition with its reasons.  Every operation below
+ * is one IEEE-754 double operation in the order written, never contracted whatever MGCFD_OPT_EXACT says.  Off by default: a
+ * solver the setter is never called on launches what it launched before and computes the same bits.
+ *   levels        levels 0 .. levels-1 take the upwind flux on their internal edges; the others keep the reference's scheme
+ *   muscl_levels  levels 0 .. muscl_levels-1 (<= levels) reconstruct; the other upwind levels are first order
+ *   limiter       MGCFD_LIMITER_NONE, _BARTH_JESPERSEN or _VENKATAKRISHNAN;  k: Venkatakrishnan's constant
+ *   entropy_fix   Harten's fraction, 0 .. 1; 0: none.  (MGCFD_UPWIND_VENKAT_K and _ENTROPY_FIX are conventions, not measurements.)
+ * Stage j of an upwind level forms F from its input state W:  B = what the reference's solid-wall and far-field loops leave in
+ * zeroed fluxes, in their own order;  F_i = B_i + U_i;  U_i starts at +0.0 and takes one addition per internal edge at i in the
+ * level's original edge order.  Per node q = (rho, u, v, w, p): u = W1 / rho ..., p the reference's pressure expression.  Per
+ * edge end (i, j, n seen from i: +e at end a, -e at end b), x the coordinates as given at creation, dx = x_j - x_i per component:
+ *   pass 1 (MUSCL levels)
+ *     A[v][d] += (q_j[v] - q_i[v]) * n[d];  G[v][d] = (0.5 * A[v][d]) / vol_i
+ *     qmax[v] = q_j[v] if q_j[v] > qmax[v];  qmin[v] = q_j[v] if q_j[v] < qmin[v]      both from q_i[v]
+ *     a second walk over the same ends:  d2 = 0.5 * ((G[v][0]*dx + G[v][1]*dy) + G[v][2]*dz)
+ *       d2 > 0: d1 = qmax[v] - q_i[v];  d2 < 0: d1 = qmin[v] - q_i[v];  otherwise (zero, NaN) t = 1.0
+ *       Barth-Jespersen   r = d1 / d2;  t = r if r < 1.0, else 1.0
+ *       Venkatakrishnan   e2 = ((k*k)*k) * vol_i;  d11 = d1*d1;  d22 = (2.0*d2)*d2
+ *                         t = ((d11 + e2)*d2 + d22*d1) / (d2 * (((d11 + d22) + d1*d2) + e2))
+ *       psi[v] = t if t < psi[v], from 1.0 (no limiter: no walk, psi = 1.0)
+ *     Gl[v][d] = psi[v] * G[v][d]        MGCFD_ARR_UPWIND_GRADIENT [nel][15] (3*v + d), MGCFD_ARR_UPWIND_LIMITER [nel][5]: read-only
+ *   pass 2
+ *     qL[v] = q_i[v] + 0.5 * ((Gl_i[v][0]*dx + Gl_i[v][1]*dy) + Gl_i[v][2]*dz);  qR[v] = q_j[v] - 0.5 * ((Gl_j[v][0]*dx + ...) + ...)
+ *     unless rhoL > 0, pL > 0, rhoR > 0 and pR > 0 (and on a first-order level): qL = q_i, qR = q_j in all variables
+ *     s = +1 if the first component of n that is != 0 is > 0, else -1;  m = s * n;  (qa, qb) = (qL, qR) for s > 0, else (qR, qL)
+ *     U_i[k] = U_i[k] - s * Phi[k]      (the fluxes hold MINUS the outflow, as the reference's internal loop leaves them: its
+ *                                        end a takes -0.5 e . (F_a + F_b)); both ends of an edge evaluate Phi on the same bits
+ *   Phi(qa, qb, m):  area = sqrt((mx*mx + my*my) + mz*mz), area == 0: Phi = 0;  nh = m / area
+ *     per state: un = (u*nhx + v*nhy) + w*nhz;  E = p / (GAMMA - 1.0) + (0.5*rho) * ((u*u + v*v) + w*w);  ru = rho * un
+ *                Fn = (ru, ru*u + p*nhx, ru*v + p*nhy, ru*w + p*nhz, (E + p)*un);  H = (E + p) / rho
+ *     ra = sqrt(rho_a), rb = sqrt(rho_b), den = ra + rb;  ut = (ra*u_a + rb*u_b) / den, vt, wt, Ht alike
+ *     q2 = (ut*ut + vt*vt) + wt*wt;  c2 = (GAMMA - 1.0) * (Ht - 0.5*q2);  ct = sqrt(c2);  unt = (ut*nhx + vt*nhy) + wt*nhz;  rt = ra*rb
+ *     drho, du, dv, dw, dp = b - a;  dun = (du*nhx + dv*nhy) + dw*nhz
+ *     l1 = |unt - ct|, l2 = |unt|, l3 = |unt + ct|;  d = entropy_fix * (l2 + ct);  each l < d becomes (l*l + d*d) / (2.0*d)
+ *     rc = rt*ct;  a1 = (dp - rc*dun) / (2.0*c2);  a2 = drho - dp / c2;  a3 = (dp + rc*dun) / (2.0*c2)
+ *     k1 = l1*a1, k2 = l2*a2, ks = l2*rt, k3 = l3*a3
+ *     D[0] = (k1 + k2) + k3
+ *     D[1] = ((k1*(ut - ct*nhx) + k2*ut) + ks*(du - dun*nhx)) + k3*(ut + ct*nhx);   D[2], D[3] alike with v, w and nhy, nhz
+ *     D[4] = ((k1*(Ht - ct*unt) + k2*(0.5*q2)) + ks*(((ut*du + vt*dv) + wt*dw) - unt*dun)) + k3*(Ht + ct*unt)
+ *     Phi[k] = area * (0.5 * (Fn_a[k] + Fn_b[k]) - 0.5 * D[k])
+ *   A c2 that is not positive yields NaN or infinities, which the invalid-state check catches as ever.
+ * Everything behind F is unchanged and sees B + U: time_step, residual smoothing, the dual-time source, FAS, V, SA, loads, RMS;
+ * step factors are unchanged.  While level 0 is an upwind level the RMS is summed in the fixed order (as under JST).
+ * On an upwind level op_flux is: settle the fluxes, the flux launch with classes = 6, pass 1 (MUSCL levels), pass 2, then the
+ * viscous and SA terms as ever.  No fused stage, no look-ahead and no captured graph on such a level (MGCFD_OPT_GRAPH is accepted;
+ * the launches run directly); timed as MGCFD_LOOP_FLUX; iteration counts unchanged.  mgcfd_compute_fluxes gives B + U,
+ * mgcfd_compute_flux_edge adds U alone.  Kernels: kernels_upwind.hip, compiled once; MGCFD_OPT_EXACT = 0 changes nothing in them.
+ * The setter synchronises, drops captured graphs and keeps the state; a level's Gl and psi are one allocation, made when a MUSCL
+ * level first covers it; its coordinates [3][stride] are on the device exactly while a MUSCL level (or the corrected face
+ * gradient, which shares the copy) is in effect on it.  MGCFD_ERR_ARG with nothing changed: negative levels, muscl_levels >
+ * levels, an unknown limiter, k not finite and positive, entropy_fix not in 0 .. 1; a MUSCL level created without coordinates;
+ * JST on (and mgcfd_set_jst refuses while the upwind flux is on); a kernel-granular sweep under way; a solver made by
+ * mgcfd_create_partitioned*, in a group or attached as a rank.  While on, the mgcfd_sweep_* split calls, mgcfd_group_create
+ * and mgcfd_rank_attach_* refuse the solver.
+ * Out of scope: split levels, groups and ranks; graphs and fused stages with it on; HLLC or AUSM; characteristic boundary
+ * conditions; reconstruction of nu_tilde; freezing the limiter.
+ * --------------------------------------------------------------------------------- */
+#define MGCFD_LIMITER_NONE 0
+#define MGCFD_LIMITER_BARTH_JESPERSEN 1
+#define MGCFD_LIMITER_VENKATAKRISHNAN 2
+#define MGCFD_UPWIND_VENKAT_K 5.0
+#define MGCFD_UPWIND_ENTROPY_FIX 0.1
+#define MGCFD_ARR_UPWIND_GRADIENT 25
+#define MGCFD_ARR_UPWIND_LIMITER 26
+int mgcfd_set_upwind(mgcfd_solver *s, int levels, int muscl_levels, int limiter, double k, double entropy_fix);
+int mgcfd_get_upwind(const mgcfd_solver *s, int *levels, int *muscl_levels, int *limiter, double *k, double *entropy_fix);
+/* Diagnostic: mean GPU time of `launches` back-to-back launches of pass 1 (kind 0, a MUSCL level) or pass 2 in the level's
+ * instantiation (kind 1; the level's fluxes keep accumulating: numbers, not a state), as mgcfd_bench_jst times its launches. */
+int mgcfd_bench_upwind(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds);
 /* Where the last MGCFD_ERR_NAN / NEG_DENSITY / NEG_ENERGY was found: *cell = original cell id (the reference's
  * "Cell %ld"), *cycle = 0-based cycle of the mgcfd_run_cycles call (-1: not known — graph replay, or found by another call). */
 int mgcfd_invalid_state_location(const mgcfd_solver *s, int64_t *cell, int *cycle);

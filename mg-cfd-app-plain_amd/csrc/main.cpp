@@ -69,6 +69,12 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool jst_given = false;           // mgcfd_set_jst before the first cycle
     double jst_kappa2 = MGCFD_JST_KAPPA2, jst_kappa4 = MGCFD_JST_KAPPA4;
     int jst_levels = 1;
+    // upwind fluxes: --upwind / --upwind-levels N / --muscl-levels N / --limiter NAME / --venkat-k X / --entropy-fix X and the config
+    // keys upwind (Y) / upwind_levels / muscl_levels / limiter / venkat_k / entropy_fix; each of the five values implies --upwind
+    bool upwind_given = false;        // mgcfd_set_upwind before the first cycle
+    int upwind_levels = 1, muscl_levels_said = -1, limiter = MGCFD_LIMITER_VENKATAKRISHNAN;
+    double venkat_k = MGCFD_UPWIND_VENKAT_K, entropy_fix = MGCFD_UPWIND_ENTROPY_FIX;
+    int muscl_levels() const { return muscl_levels_said < 0 ? upwind_levels : muscl_levels_said; }   // (not said: every upwind level reconstructs)
     // laminar viscous terms: --viscosity MU or --reynolds RE (with --ref-length L), --prandtl X, --no-slip, --viscous-cfl X,
     // --viscous-levels N and the config keys viscosity / reynolds / ref_length / prandtl / no_slip (Y) / viscous_cfl / viscous_levels
     bool viscosity_given = false, reynolds_given = false;   // one of the two switches the terms on: mgcfd_set_viscous before the first cycle
@@ -166,6 +172,17 @@ bool parse_positive(const char *text, double *out)
     return true;
 }
 
+// --limiter / limiter: "none", "barth-jespersen" or "venkatakrishnan"
+bool set_limiter(Config &c, const char *text)
+{
+    const std::string v(text);
+    if (v == "none") c.limiter = MGCFD_LIMITER_NONE;
+    else if (v == "barth-jespersen") c.limiter = MGCFD_LIMITER_BARTH_JESPERSEN;
+    else if (v == "venkatakrishnan") c.limiter = MGCFD_LIMITER_VENKATAKRISHNAN;
+    else return false;
+    c.upwind_given = true;
+    return true;
+}
 // --face-gradient / face_gradient: "averaged" or "corrected"
 bool set_face_gradient(Config &c, const char *text)
 {
@@ -326,6 +343,22 @@ void set_param(Config &c, const std::string &key, const std::string &value)
     else if (key == "jst_levels") {
         if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.jst_levels)) c.jst_given = true;
         else { std::fprintf(stderr, "ERROR: jst_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
+    }
+    else if (key == "upwind") { if (value == "Y") c.upwind_given = true; }
+    else if (key == "upwind_levels" || key == "muscl_levels") {
+        if (parse_whole(value.c_str(), 0, kMaxJstLevels, key == "upwind_levels" ? &c.upwind_levels : &c.muscl_levels_said)) c.upwind_given = true;
+        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a whole number 0 ... %d\n", key.c_str(), value.c_str(), kMaxJstLevels); c.config_bad = true; }
+    }
+    else if (key == "limiter") {
+        if (!set_limiter(c, value.c_str())) { std::fprintf(stderr, "ERROR: limiter = '%s': expected none, barth-jespersen or venkatakrishnan\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "venkat_k") {
+        if (parse_positive(value.c_str(), &c.venkat_k)) c.upwind_given = true;
+        else { std::fprintf(stderr, "ERROR: venkat_k = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
+    }
+    else if (key == "entropy_fix") {
+        if (parse_not_negative(value.c_str(), &c.entropy_fix) && c.entropy_fix <= 1.0) c.upwind_given = true;
+        else { std::fprintf(stderr, "ERROR: entropy_fix = '%s': expected a number 0 ... 1\n", value.c_str()); c.config_bad = true; }
     }
     else if (key == "viscosity" || key == "reynolds" || key == "ref_length" || key == "prandtl" || key == "viscous_cfl") {
         double *dst = key == "viscosity" ? &c.viscosity : key == "reynolds" ? &c.reynolds : key == "ref_length" ? &c.ref_length : key == "prandtl" ? &c.prandtl : &c.viscous_cfl;
@@ -515,6 +548,16 @@ void print_help()
         "                                   from the coarsest level up LIST cycles run from that level and its state is interpolated\n"
         "                                   onto the next finer one.  One value per level 1 ... n-1, or one value for all, 0 ... 4096.\n"
         "                                   One GPU; not with --physical-time-step or --polar\n"
+        "  --upwind                         upwind fluxes (config key upwind = Y): Roe's flux-difference splitting on the internal edges\n"
+        "                                   in place of the reference's central flux and scalar dissipation, on limited MUSCL states;\n"
+        "                                   one GPU; not on a level --jst covers\n"
+        "  --upwind-levels=N                the multigrid levels 0 ... N-1 it runs on (default 1; 0 = off; config key upwind_levels)\n"
+        "  --muscl-levels=N                 the levels 0 ... N-1 that reconstruct (default: every upwind level; they need .coords files;\n"
+        "                                   the others are first order; config key muscl_levels)\n"
+        "  --limiter=NAME                   none, barth-jespersen or venkatakrishnan (the default; config key limiter)\n"
+        "  --venkat-k=X                     Venkatakrishnan's constant, above zero (default 5; config key venkat_k)\n"
+        "  --entropy-fix=X                  Harten's fraction 0 ... 1, 0 = none (default 0.1; config key entropy_fix); each of the five\n"
+        "                                   values implies --upwind\n"
         "  --jst-kappa2=X                   its second-difference coefficient, finite, zero or above, in units of the reference's\n"
         "                                   dissipation (config key jst_kappa2; implies --jst)\n"
         "  --jst-kappa4=X                   its fourth-difference coefficient, likewise (config key jst_kappa4; implies --jst)\n"
@@ -641,6 +684,12 @@ bool parse_arguments(int argc, char **argv, Config &c)
         {"sa-cdes", required_argument, nullptr, 1058},
         {"output-statistics", no_argument, nullptr, 1059},
         {"statistics-start", required_argument, nullptr, 1060},
+        {"upwind", no_argument, nullptr, 1061},
+        {"upwind-levels", required_argument, nullptr, 1062},
+        {"muscl-levels", required_argument, nullptr, 1063},
+        {"limiter", required_argument, nullptr, 1064},
+        {"venkat-k", required_argument, nullptr, 1065},
+        {"entropy-fix", required_argument, nullptr, 1066},
         {nullptr, 0, nullptr, 0}};
     int optc;
     while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
@@ -745,6 +794,35 @@ bool parse_arguments(int argc, char **argv, Config &c)
                 break;
             case 1026: c.jst_given = true; break;
             case 1030: c.fas = true; break;
+            case 1061: c.upwind_given = true; break;
+            case 1062:
+            case 1063:
+                if (!parse_whole(optarg, 0, kMaxJstLevels, optc == 1062 ? &c.upwind_levels : &c.muscl_levels_said)) {
+                    std::fprintf(stderr, "ERROR: --%s-levels=%s: expected a whole number 0 ... %d\n", optc == 1062 ? "upwind" : "muscl", optarg, kMaxJstLevels);
+                    return false;
+                }
+                c.upwind_given = true;
+                break;
+            case 1064:
+                if (!set_limiter(c, optarg)) {
+                    std::fprintf(stderr, "ERROR: --limiter=%s: expected none, barth-jespersen or venkatakrishnan\n", optarg);
+                    return false;
+                }
+                break;
+            case 1065:
+                if (!parse_positive(optarg, &c.venkat_k)) {
+                    std::fprintf(stderr, "ERROR: --venkat-k=%s: expected a finite number above zero\n", optarg);
+                    return false;
+                }
+                c.upwind_given = true;
+                break;
+            case 1066:
+                if (!parse_not_negative(optarg, &c.entropy_fix) || c.entropy_fix > 1.0) {
+                    std::fprintf(stderr, "ERROR: --entropy-fix=%s: expected a number 0 ... 1\n", optarg);
+                    return false;
+                }
+                c.upwind_given = true;
+                break;
             case 1050: {
                 const std::string v(optarg);
                 if (v == "V" || v == "v") c.cycle_shape = MGCFD_CYCLE_V;
@@ -950,6 +1028,18 @@ bool parse_arguments(int argc, char **argv, Config &c)
     }
     if ((c.wall_thermal_flags > 0 || c.loads_heat) && c.gpus > 1) {
         std::fprintf(stderr, "ERROR: the wall thermal conditions and --loads-heat run on one GPU only: not with --gpus N\n");
+        return false;
+    }
+    if (c.upwind_given && c.muscl_levels() > c.upwind_levels) {
+        std::fprintf(stderr, "ERROR: --muscl-levels %d exceeds --upwind-levels %d: a level reconstructs for the upwind flux only\n", c.muscl_levels(), c.upwind_levels);
+        return false;
+    }
+    if (c.upwind_given && c.upwind_levels > 0 && c.jst_given && c.jst_levels > 0) {
+        std::fprintf(stderr, "ERROR: --upwind and --jst on the same level: Roe's flux carries its own dissipation (give one of them, or --jst-levels 0)\n");
+        return false;
+    }
+    if (c.upwind_given && c.upwind_levels > 0 && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: the upwind flux (--upwind) runs on one GPU only: not with --gpus N or --gpus-partition (a level split over GPUs would need its limited gradient exchanged per stage)\n");
         return false;
     }
     if (c.face_gradient_given && !(c.viscous() && c.viscous_levels > 0)) {
@@ -1539,7 +1629,9 @@ int main(int argc, char **argv)
     }
 
     const auto t_start = std::chrono::steady_clock::now();
-    if (conf.gpus <= 1) mgcfd_device_warm_up(conf.device);      // (the runtime comes up while the files are read)
+    // (a reconstructing run first learns whether its levels came with coordinates: no GPU work before that)
+    const bool needs_coords = conf.upwind_given && conf.upwind_levels > 0 && conf.muscl_levels() > 0;
+    if (conf.gpus <= 1 && !needs_coords) mgcfd_device_warm_up(conf.device);      // (the runtime comes up while the files are read)
     mgcfd_mesh *mesh = nullptr;
     if (mgcfd_mesh_load_ex(conf.input_file.c_str(), conf.input_file_directory.c_str(), conf.mesh_duplicate_count,
                            conf.legacy_ordering ? MGCFD_MESH_LEGACY_ORDERING : 0, &mesh) != MGCFD_OK)
@@ -1549,6 +1641,15 @@ int main(int argc, char **argv)
     const int problem_size = mgcfd_mesh_size(mesh);
 
     const double t_read = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    if (needs_coords)
+        for (int l = 0; l < levels && l < conf.muscl_levels(); l++) {
+            mgcfd_level_desc d;
+            if (mgcfd_mesh_level(mesh, l, &d) != MGCFD_OK) return fail("reading input");
+            if (!d.coords) {
+                std::fprintf(stderr, "ERROR: the upwind flux (--upwind) reconstructs on level %d, whose coords were not read (no .coords file, or a single-level fvcorr input, which reads none): give --muscl-levels %d\n", l, l);
+                return 1;
+            }
+        }
     if (conf.fas && levels < 2) {
         std::fprintf(stderr, "ERROR: FAS multigrid (--fas) needs an input of two levels or more: with one level there is no coarse level to force and no correction to bring back\n");
         return 1;
@@ -1596,6 +1697,8 @@ int main(int argc, char **argv)
     if (conf.time_step_given && mgcfd_set_time_step(solver, conf.time_step_mode, conf.cfl) != MGCFD_OK) return fail("setting the time step");
     if (conf.smoothing_given && mgcfd_set_residual_smoothing(solver, conf.smoothing_eps, conf.smoothing_iterations) != MGCFD_OK) return fail("setting the residual smoothing");
     if (conf.jst_given && mgcfd_set_jst(solver, conf.jst_kappa2, conf.jst_kappa4, conf.jst_levels) != MGCFD_OK) return fail("setting the JST dissipation");
+    if (conf.upwind_given && mgcfd_set_upwind(solver, conf.upwind_levels, conf.muscl_levels(), conf.limiter, conf.venkat_k, conf.entropy_fix) != MGCFD_OK)
+        return fail("setting the upwind flux");
     if (conf.viscous()) {
         double mu = 0.0;
         if (conf.face_gradient_given && mgcfd_set_face_gradient(solver, conf.face_gradient) != MGCFD_OK) return fail("setting the face gradient");

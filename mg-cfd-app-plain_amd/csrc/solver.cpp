@@ -30,6 +30,7 @@
 #include "device_owner.hpp"
 #include "kernels.hpp"
 #include "kernels_face_gradient.hpp"
+#include "kernels_upwind.hpp"
 #include "kernels_sa.hpp"
 #include "kernels_statistics.hpp"
 #include "kernels_wall_heat.hpp"
@@ -226,6 +227,9 @@ struct DeviceLevel {
     // the corrected face gradient (mgcfd_set_face_gradient), held while it is in effect on the level: G, me, kap [14][stride] and
     // the coordinates in the solver's numbering [3][stride]
     double *fg_g = nullptr, *fg_x = nullptr;
+    // the upwind flux (mgcfd_set_upwind): Gl [15][stride] and psi [5][stride] in one allocation, made when a MUSCL level first
+    // covers this level; the coordinates are fg_x, held while the corrected face gradient OR a MUSCL level is in effect here
+    double *up_buf = nullptr;
     // the flow statistics (mgcfd_set_statistics), level 0 only, held while a mode is on: the means [6][stride] and the co-moments
     // [7][stride]; in mode 2 on a level with solid walls also the wall table [n_wall][8] and the distribution table [n_wall][7] its
     // samples are formed in
@@ -392,6 +396,22 @@ struct mgcfd_solver {
     double jst_kappa2 = 0.0, jst_kappa4 = 0.0;
     int jst_levels = 0;
     bool jst_on(int l) const { return l < jst_levels; }
+    // Upwind fluxes (mgcfd_set_upwind; INTEGRATION.md "Upwind fluxes"): on levels 0 .. up_levels-1 the internal edges take Roe's
+    // flux in place of the reference's — the flux launch runs the wall and far-field faces alone, then pass 2 adds U — and on
+    // levels 0 .. up_muscl-1 pass 1 first forms the limited gradient pass 2 reconstructs with.  Such a level runs unfused stages
+    // outside graphs, as a JST level does.
+    int up_levels = 0, up_muscl = 0, up_limiter = MGCFD_LIMITER_NONE;
+    double up_k = 0.0, up_fix = 0.0;
+    bool upwind_on(int l) const { return l < up_levels; }
+    bool muscl_on(int l) const { return l < up_muscl; }
+    UpwindStep upwind_step(const DeviceLevel &lv) const
+    {
+        UpwindStep a;
+        a.w = lv.q; a.x = lv.fg_x; a.volumes = lv.volumes; a.fluxes = lv.fluxes;
+        a.gl = lv.up_buf; a.psi = lv.up_buf ? lv.up_buf + 15 * lv.dp.stride : nullptr;
+        a.limiter = up_limiter; a.k3 = (up_k * up_k) * up_k; a.entropy_fix = up_fix;
+        return a;
+    }
     // Laminar viscous terms (mgcfd_set_viscous): on levels 0 .. visc_levels-1 every flux launch (behind the JST pair, where on)
     // is followed by the stress and the viscous-flux launch, which add V into fluxes[], the final step factors take the
     // viscous limit, and with visc_wall every launch that writes such a level's variables is followed by the no-slip launch.
@@ -576,12 +596,12 @@ struct mgcfd_solver {
     int pre_sweeps(int l) const { return cycle_pre.empty() ? 1 : cycle_pre[static_cast<size_t>(l)]; }
     int post_sweeps(int l) const { return cycle_post.empty() ? (l == 0 ? 0 : 1) : cycle_post[static_cast<size_t>(l)]; }
     // the level-0 RMS of a cycle is summed in the order fixed on the original numbering (mgcfd.h) while any of them is on
-    bool ordered_rms() const { return dual_time() || jst_on(0) || fas || viscous_on(0); }
+    bool ordered_rms() const { return dual_time() || jst_on(0) || fas || viscous_on(0) || upwind_on(0); }
     // What the options above allow — every one of them that is on for a level replaces its fused flux + time_step stages by
     // standalone launches, which leave host-side flags behind (fluxes_stale) that a graph replay would not set.  The callers
     // add what is not physics: opt_fuse, the two-phase flux variant, the indirect_rw probe, timing and the level's flux flags.
     //   fused stages on level l: FAS forces the levels >= 1 only (level 0 sweeps as ever) ...
-    bool options_allow_fused(int l) const { return !smoothing() && !dual_time() && !jst_on(l) && !viscous_on(l) && !fas_forced(l); }
+    bool options_allow_fused(int l) const { return !smoothing() && !dual_time() && !jst_on(l) && !viscous_on(l) && !fas_forced(l) && !upwind_on(l); }
     //   ... but no sweep is graphed on any level while it is on; JST and viscous levels count one by one
     bool options_allow_sweep_graph(int l) const { return options_allow_fused(l) && !fas && default_cycle(); }
     //   a whole cycle as one graph: every level's sweep must be (JST and the viscous terms run on levels 0 .. n-1: level 0 decides)
@@ -844,12 +864,23 @@ struct mgcfd_solver {
     {
         DeviceLevel &lv = level(l);
         Timed t(this, l, MGCFD_LOOP_FLUX, (classes & 1) != 0);
-        if (classes != 7) settle_fluxes(lv);                // a partial launch leaves other nodes' memory as it is
+        // a partial launch leaves other nodes' memory as it is; on an upwind level pass 2 adds into memory whatever the classes
+        if (classes != 7 || upwind_on(l)) settle_fluxes(lv);
         const int accumulate = lv.fluxes_zero ? 0 : 1;     // 0.0 + x: same bits either way
         const int variant = variant_for(lv);
         if ((variant & 4) && !lv.dp.edge_flux)              // two-phase design point: edge-flux scratch on first use
             lv.dp.edge_flux = lv.mem.alloc<double>(static_cast<size_t>(lv.dp.n_edges_pad) * 5 + 8);
-        k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr, nullptr);
+        if (upwind_on(l)) {
+            // upwind level: B from the wall and far-field faces alone, then F = B + U (pass 1 on a MUSCL level, pass 2)
+            if (classes & 6) k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes & 6, accumulate, variant, nullptr, nullptr);
+            if (classes & 1) {
+                const UpwindStep a = upwind_step(lv);
+                if (muscl_on(l)) launch_upwind_gradient(stream, lv.dp, a);
+                launch_upwind_flux(stream, lv.dp, a, muscl_on(l));
+            }
+        } else {
+            k().flux(stream, lv.dp, lv.q, ff, lv.fluxes, classes, accumulate, variant, nullptr, nullptr);
+        }
         if ((classes & 1) && jst_on(l)) {
             // JST: L, nu, r of the state the fluxes were computed from, then fluxes += C (both passes keep row order in either flavour)
             const JstStep a = jst_step(lv);
@@ -1947,6 +1978,8 @@ int mgcfd_set_jst(mgcfd_solver *s, double kappa2, double kappa4, int levels)
         if (levels > 0 && !(kappa2 > 0.0) && !(kappa4 > 0.0)) throw std::invalid_argument("JST dissipation: one of kappa2 and kappa4 must be positive");
         if (levels > 0 && (s->partitioned || s->comm))
             throw std::invalid_argument("JST dissipation: not on a partitioned solver or a rank (a level split over ranks would need L, nu and r exchanged per stage)");
+        if (levels > 0 && s->up_levels > 0)
+            throw std::invalid_argument("JST dissipation: not on a level the upwind flux is on (mgcfd_set_upwind: Roe's flux carries its own dissipation)");
         quiesce(s, "JST dissipation");
         const int n = std::min(levels, static_cast<int>(s->L.size()));
         for (int l = 0; l < n; l++) {
@@ -2167,18 +2200,20 @@ static void require_face_gradient_possible(const mgcfd_solver *s, int visc_level
         if (s->L[static_cast<size_t>(l)].coords.empty())
             throw std::invalid_argument("face gradient: level " + std::to_string(l) + " was created without coordinates (the corrected gradient would take effect there)");
 }
-// G and the coordinates of a level are held exactly while the corrected face gradient is in effect on it: both setters call
-// this once their new state is stored.  A new G holds +0.0.
+// G of a level is held exactly while the corrected face gradient is in effect on it, its coordinates while that or a MUSCL level
+// of the upwind flux is: the three setters call this once their new state is stored.  A new G holds +0.0.
 static void settle_face_gradient(mgcfd_solver *s)
 {
     for (int l = 0; l < static_cast<int>(s->L.size()); l++) {
         DeviceLevel &lv = s->L[static_cast<size_t>(l)];
-        if (!s->fg_on(l)) { lv.mem.release(lv.fg_g); lv.mem.release(lv.fg_x); continue; }
+        // (the coordinates serve the upwind flux's MUSCL levels too: held while either is in effect here)
+        if (!s->fg_on(l) && !s->muscl_on(l)) lv.mem.release(lv.fg_x);
+        else if (!lv.fg_x) lv.fg_x = lv.mem.upload(permuted_coordinates(lv.coords, lv.plan.old_of_new, lv.info.nel, lv.dp.stride));
+        if (!s->fg_on(l)) { lv.mem.release(lv.fg_g); continue; }
         if (lv.fg_g) continue;
         const size_t stride = static_cast<size_t>(lv.dp.stride);
         lv.fg_g = lv.mem.alloc<double>(14 * stride);
         HIP_CHECK(hipMemsetAsync(lv.fg_g, 0, sizeof(double) * 14 * stride, s->stream));
-        lv.fg_x = lv.mem.upload(permuted_coordinates(lv.coords, lv.plan.old_of_new, lv.info.nel, lv.dp.stride));
     }
     HIP_CHECK(hipStreamSynchronize(s->stream));
 }
@@ -2331,6 +2366,84 @@ int mgcfd_bench_face_gradient(mgcfd_solver *s, int level, int kind, int launches
         *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) launch_face_gradient_nodes(s->stream, lv.dp, a);
             else launch_face_gradient_correction(s->stream, lv.dp, a);
+        });
+        lv.fluxes_zero = false; lv.fluxes_stale = false;
+    });
+}
+// ---- upwind fluxes: Roe's flux on the internal edges, limited MUSCL reconstruction (INTEGRATION.md "Upwind fluxes") ----
+int mgcfd_set_upwind(mgcfd_solver *s, int levels, int muscl_levels, int limiter, double k, double entropy_fix)
+{
+    REQUIRE(s);
+    return guarded([&] {
+        if (levels < 0 || muscl_levels < 0) throw std::invalid_argument("upwind flux: levels and muscl_levels must be 0 (off) or more");
+        if (muscl_levels > levels) throw std::invalid_argument("upwind flux: muscl_levels must not exceed levels (a level reconstructs for Roe's flux only)");
+        if (limiter != MGCFD_LIMITER_NONE && limiter != MGCFD_LIMITER_BARTH_JESPERSEN && limiter != MGCFD_LIMITER_VENKATAKRISHNAN)
+            throw std::invalid_argument("upwind flux: unknown limiter " + std::to_string(limiter));
+        if (!std::isfinite(k) || !(k > 0.0)) throw std::invalid_argument("upwind flux: Venkatakrishnan's k must be finite and positive");
+        if (!std::isfinite(entropy_fix) || entropy_fix < 0.0 || entropy_fix > 1.0)
+            throw std::invalid_argument("upwind flux: entropy_fix must lie in 0 .. 1 (0: none)");
+        const int n = std::min(levels, static_cast<int>(s->L.size())), nm = std::min(muscl_levels, n);
+        if (n > 0 && (s->partitioned || s->comm))
+            throw std::invalid_argument("upwind flux: not on a partitioned solver, a group member or a rank (a level split over ranks would need Gl exchanged per stage)");
+        if (n > 0 && s->jst_levels > 0)
+            throw std::invalid_argument("upwind flux: not on a level the JST dissipation is on (mgcfd_set_jst: Roe's flux carries its own dissipation)");
+        for (int l = 0; l < nm; l++)
+            if (s->L[static_cast<size_t>(l)].coords.empty())
+                throw std::invalid_argument("upwind flux: level " + std::to_string(l) + " was created without coordinates (a MUSCL level reconstructs along the edge)");
+        quiesce(s, "upwind flux");
+        if (nm > 0) {
+            // the reconstructing flux kernel declares more LDS than every device grants: ask before the first launch
+            int lds = 0;
+            HIP_CHECK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device));
+            if (lds < kUpwindMusclLds)
+                throw std::invalid_argument("upwind flux: a MUSCL level needs " + std::to_string(kUpwindMusclLds) + " bytes of LDS per workgroup; the device grants " + std::to_string(lds));
+        }
+        for (int l = 0; l < nm; l++) {
+            DeviceLevel &lv = s->L[static_cast<size_t>(l)];
+            if (lv.up_buf) continue;
+            const size_t stride = static_cast<size_t>(lv.dp.stride);
+            lv.up_buf = lv.mem.alloc<double>(20 * stride);
+            HIP_CHECK(hipMemsetAsync(lv.up_buf, 0, sizeof(double) * 20 * stride, s->stream));
+        }
+        s->up_levels = n;
+        s->up_muscl = nm;
+        s->up_limiter = n > 0 ? limiter : MGCFD_LIMITER_NONE;
+        s->up_k = n > 0 ? k : 0.0;
+        s->up_fix = n > 0 ? entropy_fix : 0.0;
+        settle_face_gradient(s);                            // (the coordinates of the MUSCL levels; synchronises)
+        settle_rms_order(s);
+        drop_look_ahead(s);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int mgcfd_get_upwind(const mgcfd_solver *s, int *levels, int *muscl_levels, int *limiter, double *k, double *entropy_fix)
+{
+    REQUIRE(s);
+    if (levels) *levels = s->up_levels;
+    if (muscl_levels) *muscl_levels = s->up_muscl;
+    if (limiter) *limiter = s->up_limiter;
+    if (k) *k = s->up_k;
+    if (entropy_fix) *entropy_fix = s->up_fix;
+    return MGCFD_OK;
+}
+// Diagnostic: kind 0 the gradient launch (a MUSCL level), 1 the flux launch of the level's instantiation (fluxes keeps
+// accumulating: numbers, not a state).
+int mgcfd_bench_upwind(mgcfd_solver *s, int level, int kind, int launches, double *avg_seconds)
+{
+    REQUIRE(s); REQUIRE(avg_seconds);
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        if (!s->upwind_on(level)) throw std::invalid_argument("the upwind flux is off on this level: switch it on first (mgcfd_set_upwind)");
+        if (kind < 0 || kind > 1) throw std::invalid_argument("upwind launch kind: 0 gradient, 1 flux");
+        if (kind == 0 && !s->muscl_on(level)) throw std::invalid_argument("upwind launch kind 0: the level does not reconstruct (mgcfd_set_upwind's muscl_levels)");
+        s->settle_fluxes(lv);
+        const UpwindStep a = s->upwind_step(lv);
+        const bool muscl = s->muscl_on(level);
+        if (muscl) launch_upwind_gradient(s->stream, lv.dp, a);    // (every array holds a stage's numbers)
+        *avg_seconds = s->timed_launches(launches, [&] {
+            if (kind == 0) launch_upwind_gradient(s->stream, lv.dp, a);
+            else launch_upwind_flux(s->stream, lv.dp, a, muscl);
         });
         lv.fluxes_zero = false; lv.fluxes_stale = false;
     });
@@ -2682,6 +2795,7 @@ static void require_no_smoothing(const mgcfd_solver *s, const char *who)
     if (s->smoothing()) throw std::invalid_argument(std::string(who) + ": not while residual smoothing is on (mgcfd_set_residual_smoothing; use mgcfd_smooth or the kernel-granular calls)");
     if (s->dual_time()) throw std::invalid_argument(std::string(who) + ": not while dual time stepping is on (mgcfd_set_dual_time; use mgcfd_smooth or the kernel-granular calls)");
     if (s->jst_on(0)) throw std::invalid_argument(std::string(who) + ": not while the JST dissipation is on (mgcfd_set_jst; use mgcfd_smooth or the kernel-granular calls)");
+    if (s->upwind_on(0)) throw std::invalid_argument(std::string(who) + ": not while the upwind flux is on (mgcfd_set_upwind; use mgcfd_smooth or the kernel-granular calls)");
     if (s->viscous_on(0)) throw std::invalid_argument(std::string(who) + ": not while the viscous terms are on (mgcfd_set_viscous; use mgcfd_smooth or the kernel-granular calls)");
     if (s->fas) throw std::invalid_argument(std::string(who) + ": not while FAS multigrid is on (mgcfd_set_fas; use mgcfd_smooth or the kernel-granular calls)");
 }
@@ -3304,6 +3418,10 @@ static double *array_ptr(DeviceLevel &lv, int which, int *ncols)
             if (!lv.stat_mean) throw std::invalid_argument("MGCFD_ARR_STATISTICS_MEAN / _MOMENTS: level 0 while the flow statistics are on (mgcfd_set_statistics)");
             *ncols = which == MGCFD_ARR_STATISTICS_MEAN ? 6 : 7;
             return which == MGCFD_ARR_STATISTICS_MEAN ? lv.stat_mean : lv.stat_mom;
+        case MGCFD_ARR_UPWIND_GRADIENT: case MGCFD_ARR_UPWIND_LIMITER:
+            if (!lv.up_buf) throw std::invalid_argument("MGCFD_ARR_UPWIND_*: no MUSCL level of the upwind flux has covered this level (mgcfd_set_upwind)");
+            *ncols = which == MGCFD_ARR_UPWIND_GRADIENT ? 15 : 5;
+            return which == MGCFD_ARR_UPWIND_GRADIENT ? lv.up_buf : lv.up_buf + 15 * lv.dp.stride;
         case MGCFD_ARR_STAGE:
             if (!lv.stage_out) throw std::invalid_argument("MGCFD_ARR_STAGE: no mgcfd_sweep_stage has run on this level");
             return lv.stage_out;
@@ -3353,6 +3471,8 @@ int mgcfd_set_array(mgcfd_solver *s, int level, int which, const double *in)
         if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
         if (which == MGCFD_ARR_VISCOUS_GRADIENT) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: read-only (every flux launch of the level overwrites it)");
         if (which == MGCFD_ARR_SA_LENGTH) throw std::invalid_argument("MGCFD_ARR_SA_LENGTH: read-only (formed from the wall distance, the mesh and, under delayed DES, every pass 1)");
+        if (which == MGCFD_ARR_UPWIND_GRADIENT || which == MGCFD_ARR_UPWIND_LIMITER)
+            throw std::invalid_argument("MGCFD_ARR_UPWIND_*: read-only (every flux launch of a MUSCL level overwrites them)");
         const int64_t stride = lv.dp.stride;
         // keep the padded tail of every field as it is on the device (valid numbers)
         std::vector<double> tmp(static_cast<size_t>(stride) * nc);
@@ -3402,6 +3522,8 @@ int mgcfd_array_written(mgcfd_solver *s, int level, int which)
         if (which == MGCFD_ARR_SA_GRADIENT) throw std::invalid_argument("MGCFD_ARR_SA_GRADIENT: read-only (every flux launch of level 0 overwrites it)");
         if (which == MGCFD_ARR_VISCOUS_GRADIENT) throw std::invalid_argument("MGCFD_ARR_VISCOUS_GRADIENT: read-only (every flux launch of the level overwrites it)");
         if (which == MGCFD_ARR_SA_LENGTH) throw std::invalid_argument("MGCFD_ARR_SA_LENGTH: read-only (formed from the wall distance, the mesh and, under delayed DES, every pass 1)");
+        if (which == MGCFD_ARR_UPWIND_GRADIENT || which == MGCFD_ARR_UPWIND_LIMITER)
+            throw std::invalid_argument("MGCFD_ARR_UPWIND_*: read-only (every flux launch of a MUSCL level overwrites them)");
         if (which == MGCFD_ARR_FLUXES) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
         if (which == MGCFD_ARR_VARIABLES) lv.min_ahead = false;
         if (which == MGCFD_ARR_SA_NU_TILDE) { s->use_device(); s->sa_form(lv, false); }

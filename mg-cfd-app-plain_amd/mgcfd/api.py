@@ -27,11 +27,13 @@ ARR = {"variables": 0, "old_variables": 1, "fluxes": 2, "residuals": 3, "step_fa
        "time_n": 7, "time_n1": 8, "jst_laplacian": 9, "jst_sensor": 10, "jst_radius": 11,
        "fas_forcing": 12, "fas_start": 13, "viscous_stress": 14, "eddy_viscosity": 15, "wall_distance": 16,
        "sa_nu_tilde": 17, "sa_gradient": 18, "viscous_gradient": 19, "sa_time_n": 20, "sa_time_n1": 21, "sa_length": 22,
-       "statistics_mean": 23, "statistics_moments": 24}
+       "statistics_mean": 23, "statistics_moments": 24, "upwind_gradient": 25, "upwind_limiter": 26}
 NCOLS = {"step_factors": 1, "volumes": 1, "jst_sensor": 1, "jst_radius": 1, "viscous_stress": 12, "eddy_viscosity": 1, "wall_distance": 1,
          "sa_nu_tilde": 1, "sa_gradient": 5, "viscous_gradient": 12, "sa_time_n": 1, "sa_time_n1": 1, "sa_length": 1,
-         "statistics_mean": 6, "statistics_moments": 7}    # (every other array: NVAR)
+         "statistics_mean": 6, "statistics_moments": 7, "upwind_gradient": 15, "upwind_limiter": 5}    # (every other array: NVAR)
 OPT = {"exact": 0, "timing": 1, "indirect_rw": 2, "check_invalid": 3, "flux_variant": 4, "fuse_update": 5, "graph": 6, "rank_split": 7, "stage_wg4": 8}
+LIMITERS = {"none": 0, "barth-jespersen": 1, "venkatakrishnan": 2}
+UPWIND_VENKAT_K, UPWIND_ENTROPY_FIX = 5.0, 0.1          # MGCFD_UPWIND_VENKAT_K, MGCFD_UPWIND_ENTROPY_FIX
 ERR_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_IO", 3: "ERR_HIP", 4: "ERR_NAN", 5: "ERR_NEG_DENSITY",
              6: "ERR_NEG_ENERGY", 7: "ERR_VALIDATION"}
 
@@ -250,6 +252,9 @@ _SIGNATURES = [
     ("mgcfd_set_face_gradient", C.c_int, [_vp, C.c_int]),
     ("mgcfd_get_face_gradient", C.c_int, [_vp, C.POINTER(C.c_int)]),
     ("mgcfd_bench_face_gradient", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    ("mgcfd_set_upwind", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
+    ("mgcfd_get_upwind", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("mgcfd_bench_upwind", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("mgcfd_set_cycle", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_get_cycle", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mgcfd_run_cycles_from", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -359,7 +364,8 @@ def _level_descs(levels: Sequence[dict]):
     for l, L in enumerate(levels):
         vol = np.ascontiguousarray(L["volumes"], dtype=np.float64)
         edges = np.ascontiguousarray(L["edges"], dtype=EDGE_DTYPE)
-        crd = None if L.get("coords") is None else np.ascontiguousarray(L["coords"], dtype=np.float64)
+        # (an empty array is "no coordinates", as Mesh.level hands them out for a level loaded without its .coords file)
+        crd = None if L.get("coords") is None or np.size(L["coords"]) == 0 else np.ascontiguousarray(L["coords"], dtype=np.float64)
         mp = None if L.get("mg_map") is None else np.ascontiguousarray(L["mg_map"], dtype=np.int64)
         keep += [vol, edges, crd, mp]
         d = descs[l]
@@ -977,6 +983,30 @@ class Solver:
         state stays; captured graphs are dropped.  Not on partitioned solvers or ranks."""
         self._c(self.lib.mgcfd_set_jst(self.handle, float(kappa2), float(kappa4), int(levels)))
 
+    def set_upwind(self, levels: int = 1, muscl_levels: Optional[int] = None, limiter="venkatakrishnan", k: float = UPWIND_VENKAT_K,
+                   entropy_fix: float = UPWIND_ENTROPY_FIX):
+        """Roe's upwind flux on the internal edges of levels ``0 .. levels-1`` (mgcfd_set_upwind), reconstructed with the
+        limited Green-Gauss gradient on levels ``0 .. muscl_levels-1`` (None: every upwind level); ``limiter`` is ``"none"``,
+        ``"barth-jespersen"`` or ``"venkatakrishnan"`` (with its constant ``k``), ``entropy_fix`` Harten's fraction (0: none).
+        ``levels=0`` switches it off.  Excludes the JST dissipation."""
+        levels = int(levels)
+        muscl = levels if muscl_levels is None else int(muscl_levels)
+        self._c(self.lib.mgcfd_set_upwind(self.handle, levels, muscl, int(LIMITERS.get(limiter, limiter)), float(k), float(entropy_fix)))
+
+    def upwind(self):
+        """(levels, muscl_levels, limiter by name, k, entropy_fix) in use (mgcfd_get_upwind); (0, 0, "none", 0.0, 0.0) while off."""
+        n, m, lim = C.c_int(0), C.c_int(0), C.c_int(0)
+        k, fix = C.c_double(0.0), C.c_double(0.0)
+        self._c(self.lib.mgcfd_get_upwind(self.handle, C.byref(n), C.byref(m), C.byref(lim), C.byref(k), C.byref(fix)))
+        return n.value, m.value, {v: name for name, v in LIMITERS.items()}[lim.value], k.value, fix.value
+
+    def bench_upwind(self, l: int, kind, launches: int) -> float:
+        """Mean GPU seconds of ``launches`` back-to-back launches of pass 1 (``kind`` 0 / "gradient", a MUSCL level) or pass 2
+        (1 / "flux") on level ``l``, where the upwind flux must be on (mgcfd_bench_upwind)."""
+        t = C.c_double(0.0)
+        self._c(self.lib.mgcfd_bench_upwind(self.handle, l, {"gradient": 0, "flux": 1}.get(kind, kind), launches, C.byref(t)))
+        return t.value
+
     def jst(self):
         """``(kappa2, kappa4, levels)`` in use, ``levels`` capped at the solver's; ``(0.0, 0.0, 0)`` when off."""
         k2, k4, n = C.c_double(), C.c_double(), C.c_int()
@@ -1147,7 +1177,7 @@ class Solver:
     def polar(self, alphas, cycles: int, mach: Optional[float] = None, warm_start: bool = True, ref_point=(0.0, 0.0, 0.0),
               ref_area: float = 1.0, ref_length: float = 1.0, time_step=None, cfl: Optional[float] = None,
               residual_smoothing=None, jst=None, fas: Optional[bool] = None, viscous=None, viscosity_model=None, wall_damping=None,
-              wall_temperature=None, face_gradient=None) -> List[dict]:
+              wall_temperature=None, face_gradient=None, upwind=None) -> List[dict]:
         """An alpha polar: for every angle of ``alphas`` (degrees) ``set_free_stream`` then ``run_cycles(cycles, loads=True)``.
         The first angle starts from its own far field; a later one continues from the flow of the angle before it
         (``warm_start=True``) or starts again from its far field.  ``mach=None`` keeps the solver's Mach number.  Per angle a
@@ -1160,7 +1190,8 @@ class Solver:
         None is then the far field's of the solver as the call finds it; ``wall_damping=(on, kappa)`` or a dict of
         ``set_wall_damping``'s keywords likewise (``set_wall_damping``), and ``wall_temperature=(mode, value)`` or a dict of
         ``set_wall_temperature``'s keywords (``set_wall_temperature``); ``face_gradient="averaged" / "corrected"``
-        (``set_face_gradient``) is set before the viscous terms, so that a ``viscous`` without ``cfl_v`` takes the mode's default."""
+        (``set_face_gradient``) is set before the viscous terms, so that a ``viscous`` without ``cfl_v`` takes the mode's default;
+        ``upwind=(levels, muscl_levels, limiter, k, entropy_fix)`` or a dict of ``set_upwind``'s keywords (``set_upwind``)."""
         if face_gradient is not None:
             self.set_face_gradient(face_gradient)
         if wall_temperature is not None:
@@ -1175,6 +1206,8 @@ class Solver:
             self.set_fas(fas)
         if jst is not None:
             self.set_jst(*jst)
+        if upwind is not None:
+            self.set_upwind(**upwind) if isinstance(upwind, dict) else self.set_upwind(*upwind)
         if residual_smoothing is not None:
             self.set_residual_smoothing(*residual_smoothing)
         if time_step is not None or cfl is not None:
