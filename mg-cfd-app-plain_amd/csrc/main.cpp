@@ -27,6 +27,7 @@
 
 namespace {
 
+// What the run was asked for.  Which flag or config key sets which field, and how its value is read: kOptions, below.
 struct Config {                       // the reference's `config` (src/Base/config.h:27-47)
     std::string config_filepath, input_file, input_file_directory, papi_config_file, output_file_prefix;
     int mesh_duplicate_count = 1;
@@ -35,108 +36,97 @@ struct Config {                       // the reference's `config` (src/Base/conf
     bool output_variables = false, output_old_variables = false, output_step_factors = false,
          output_edge_fluxes = false, output_fluxes = false, output_volumes = false;
     // extensions (not in the reference)
-    bool timers = true;               // --no-timers: fused fast path (one launch per Runge-Kutta stage); Times.csv holds only Total
-    bool loop_timers = false;         // --loop-timers: EVERY loop its own launch between two events, as the reference's -DTIME build brackets
+    bool timers = true;               // off: fused fast path (one launch per Runge-Kutta stage); Times.csv holds only Total
+    bool loop_timers = false;         // EVERY loop its own launch between two events, as the reference's -DTIME build brackets
                                       // them (src/Monitoring/timer.cpp:58-195); default: fused stages, the per-loop times ATTRIBUTED
                                       // from every 32nd sweep / transfer of a level, which runs per loop under events (MGCFD_OPT_TIMING = 4)
-    bool fast_math = false;           // --fast: allow FMA contraction (MGCFD_OPT_EXACT = 0)
-    bool indirect_rw = true;          // the reference runs the probe every RK stage; --no-indirect-rw skips it
-    bool legacy_ordering = false;     // --legacy-ordering: the reference's -DLEGACY_ORDERING edge sort (a compile-time flag there)
+    bool fast_math = false;           // allow FMA contraction (MGCFD_OPT_EXACT = 0)
+    bool indirect_rw = true;          // the reference runs the probe every RK stage
+    bool legacy_ordering = false;     // the reference's -DLEGACY_ORDERING edge sort (a compile-time flag there)
     int device = 0;
-    int gpus = 1;                     // --gpus N: a single-level input partitioned over N GPUs, a multigrid input one level per GPU
-    bool gpus_share_device = false;   // --gpus-share-device: all N ranks on --device (rehearsal on a one-GPU box)
-    bool gpus_partition = false;      // --gpus-partition: split every level of a multigrid input over the N GPUs (the default when N > levels)
-    bool output_loads = false;        // --output-loads: the level-0 surface loads of every cycle into surface_loads.* (one GPU, or --gpus N --gpus-partition)
-    double loads_ref[5] = {1.0, 1.0, 0.0, 0.0, 0.0};   // --loads-reference=S,c,x,y,z: reference area, length and moment point
+    int gpus = 1;                     // N: a single-level input partitioned over N GPUs, a multigrid input one level per GPU
+    bool gpus_share_device = false;   // all N ranks on the one device (rehearsal on a one-GPU box)
+    bool gpus_partition = false;      // split every level of a multigrid input over the N GPUs (the default when N > levels)
+    bool output_loads = false;        // the level-0 surface loads of every cycle into surface_loads.*
+    double loads_ref[5] = {1.0, 1.0, 0.0, 0.0, 0.0};   // S,c,x,y,z: reference area, length and moment point
     // the free stream (the reference compiles it in: ff_mach = 1.2, deg_angle_of_attack = 0, src/Base/const.h:14-15)
-    bool free_stream_given = false;   // --mach / --alpha / ff_mach / angle_of_attack: mgcfd_set_free_stream before the first cycle
+    bool free_stream_given = false;   // mgcfd_set_free_stream before the first cycle
     double ff_mach = 1.2, angle_of_attack = 0.0;
-    bool polar = false;               // --polar A0:A1:N: N angles from A0 to A1 inclusive, -g cycles each, polar.csv
+    bool polar = false;               // polar_n angles from polar_a0 to polar_a1 inclusive, num_cycles each, polar.csv
     double polar_a0 = 0.0, polar_a1 = 0.0;
     int polar_n = 0;
     // the time step (the reference ties it to the mesh name and the literal 0.5, src/euler3d_cpu_double.cpp:388-395)
-    bool time_step_given = false;     // --time-step / --cfl / time_step / cfl: mgcfd_set_time_step before the first cycle
+    bool time_step_given = false;     // mgcfd_set_time_step before the first cycle
     int time_step_mode = MGCFD_DT_REFERENCE;
     double cfl = 0.5;
-    bool config_bad = false;          // a config file's value (time step, residual smoothing) was refused: the run ends right after parsing
-    // implicit residual smoothing: --residual-smoothing EPS / --smoothing-iterations N / residual_smoothing / smoothing_iterations
+    bool config_bad = false;          // a config file's value was refused: the run ends right after parsing
+    // implicit residual smoothing
     bool smoothing_given = false;     // an EPS was given: mgcfd_set_residual_smoothing before the first cycle
     bool smoothing_iterations_given = false;
     double smoothing_eps = 0.0;
     int smoothing_iterations = 2;     // (the default when only EPS is given)
-    // JST dissipation: --jst / --jst-kappa2 X / --jst-kappa4 X / --jst-levels N and the config keys jst (Y) / jst_kappa2 / jst_kappa4 /
-    // jst_levels; each of the three values implies --jst
+    // JST dissipation; each of its three values switches it on
     bool jst_given = false;           // mgcfd_set_jst before the first cycle
     double jst_kappa2 = MGCFD_JST_KAPPA2, jst_kappa4 = MGCFD_JST_KAPPA4;
     int jst_levels = 1;
-    // upwind fluxes: --upwind / --upwind-levels N / --muscl-levels N / --limiter NAME / --venkat-k X / --entropy-fix X and the config
-    // keys upwind (Y) / upwind_levels / muscl_levels / limiter / venkat_k / entropy_fix; each of the five values implies --upwind
+    // upwind fluxes; each of their five values switches them on
     bool upwind_given = false;        // mgcfd_set_upwind before the first cycle
     int upwind_levels = 1, muscl_levels_said = -1, limiter = MGCFD_LIMITER_VENKATAKRISHNAN;
     double venkat_k = MGCFD_UPWIND_VENKAT_K, entropy_fix = MGCFD_UPWIND_ENTROPY_FIX;
     int muscl_levels() const { return muscl_levels_said < 0 ? upwind_levels : muscl_levels_said; }   // (not said: every upwind level reconstructs)
-    // laminar viscous terms: --viscosity MU or --reynolds RE (with --ref-length L), --prandtl X, --no-slip, --viscous-cfl X,
-    // --viscous-levels N and the config keys viscosity / reynolds / ref_length / prandtl / no_slip (Y) / viscous_cfl / viscous_levels
+    // laminar viscous terms
     bool viscosity_given = false, reynolds_given = false;   // one of the two switches the terms on: mgcfd_set_viscous before the first cycle
     bool viscous_extras_given = false;                      // one of the companions was given (they need MU or RE)
     double viscosity = 0.0, reynolds = 0.0, ref_length = 1.0, prandtl = MGCFD_VISCOUS_PRANDTL, viscous_cfl = MGCFD_VISCOUS_CFL;
     bool no_slip = false;
     int viscous_levels = 1;
     bool viscous() const { return viscosity_given || reynolds_given; }
-    // the viscosity model: --sutherland with --sutherland-tref X and --sutherland-s X, --smagorinsky [CS], --prandtl-turbulent X and
-    // the config keys sutherland (Y) / sutherland_tref / sutherland_s / smagorinsky (Y or CS) / prandtl_turbulent
+    // the viscosity model: Sutherland's law, and the Smagorinsky or Spalart-Allmaras eddy viscosity
     bool sutherland = false, smagorinsky = false;
-    bool model_extras_given = false;                        // --sutherland-tref / --sutherland-s / --prandtl-turbulent
+    bool model_extras_given = false;                        // a companion of the models was given (they need the viscous terms)
     double sutherland_tref = 0.0, sutherland_s = MGCFD_SUTHERLAND_S, smagorinsky_cs = MGCFD_SMAGORINSKY_CS, prandtl_turbulent = MGCFD_PRANDTL_TURBULENT;
     bool viscosity_model() const { return sutherland || smagorinsky || spalart_allmaras; }
-    // --spalart-allmaras[=RATIO] / spalart_allmaras = Y | RATIO: the transported eddy viscosity (MGCFD_EDDY_SPALART_ALLMARAS),
-    // RATIO the free-stream nu_tilde over nu (mgcfd_set_sa_free_stream)
-    bool spalart_allmaras = false;
-    double sa_ratio = MGCFD_SA_RATIO;
-    // --sa-time-accurate, --sa-length wall|des|ddes, --sa-cdes X and the config keys sa_time_accurate (Y) / sa_length / sa_cdes:
-    // the unsteady model (mgcfd_set_sa_unsteady), with --spalart-allmaras; --sa-time-accurate lets it run with --physical-time-step
+    bool spalart_allmaras = false;    // the transported eddy viscosity (MGCFD_EDDY_SPALART_ALLMARAS)
+    double sa_ratio = MGCFD_SA_RATIO; // the free-stream nu_tilde over nu (mgcfd_set_sa_free_stream)
+    // the unsteady Spalart-Allmaras model (mgcfd_set_sa_unsteady); time-accurate, it runs under dual time stepping
     bool sa_time_accurate = false, sa_unsteady_given = false;
     int sa_length = MGCFD_SA_LENGTH_WALL;
     double sa_cdes = MGCFD_SA_CDES;
-    // --wall-damping[=KAPPA] / wall_damping = Y | KAPPA: the wall-limited length scale of --smagorinsky (mgcfd_set_wall_damping)
-    bool wall_damping = false;
+    bool wall_damping = false;        // the wall-limited length scale of the Smagorinsky model (mgcfd_set_wall_damping)
     double wall_kappa = MGCFD_WALL_KAPPA;
-    bool loads_friction = false;      // --loads-friction: the friction loads beside the pressure loads in surface_loads.* and polar.csv (one GPU)
-    bool output_surface = false;      // --output-surface: Cp and Cf per wall node of level 0 into surface.* (one GPU)
-    // wall thermal conditions (mgcfd_set_wall_temperature): --wall-temperature T, --wall-temperature-ratio R (times the static
-    // free-stream temperature in use) or --wall-heat-flux Q, with --no-slip and the viscous terms; one of them at most
+    bool loads_friction = false;      // the friction loads beside the pressure loads in surface_loads.* and polar.csv
+    bool output_surface = false;      // Cp and Cf per wall node of level 0 into surface.*
+    // wall thermal conditions (mgcfd_set_wall_temperature): a temperature, a ratio to the static free-stream temperature in use,
+    // or a heat flux; one of them at most
     int wall_thermal_flags = 0;       // how many of the three were given
     int wall_mode = 0;                // MGCFD_WALL_*
     double wall_value = 0.0;          // T, R or Q as given
     bool wall_ratio = false;          // ... it is R
-    // --face-gradient averaged|corrected (config key face_gradient; mgcfd_set_face_gradient): the face gradient of the viscous and
-    // Spalart-Allmaras diffusion.  Corrected without --viscous-cfl: MGCFD_VISCOUS_CFL_CORRECTED.  One GPU
+    // the face gradient of the viscous and Spalart-Allmaras diffusion (mgcfd_set_face_gradient).  Corrected, and no viscous_cfl
+    // given: MGCFD_VISCOUS_CFL_CORRECTED
     int face_gradient = MGCFD_FACE_GRADIENT_AVERAGED;
     bool face_gradient_given = false, viscous_cfl_given = false;
-    bool loads_heat = false;          // --loads-heat: Q, A and the mean Stanton number behind the friction columns; qw, T, St in surface.* (one GPU)
+    bool loads_heat = false;          // Q, A and the mean Stanton number behind the friction columns; qw, T, St in surface.*
     size_t loads_width() const { return loads_heat ? 14 : (loads_friction ? 12 : 6); }
-    // FAS multigrid: --fas and the config key fas (Y): mgcfd_set_fas before the first cycle; one GPU, two levels or more
-    bool fas = false;
-    // the multigrid cycle: --cycle V|W|F, --pre-sweeps LIST, --post-sweeps LIST (mgcfd_set_cycle before the first cycle) and
-    // --fmg-cycles LIST (mgcfd_full_multigrid before the -g cycles); the lists are expanded once the number of levels is known
+    bool fas = false;                 // FAS multigrid: mgcfd_set_fas before the first cycle
+    // the multigrid cycle (mgcfd_set_cycle before the first cycle) and the full-multigrid start (mgcfd_full_multigrid before the
+    // cycles); the lists are expanded once the number of levels is known
     int cycle_shape = MGCFD_CYCLE_V;
     std::vector<int> pre_sweeps, post_sweeps, fmg_cycles;
     bool cycle_given() const { return cycle_shape != MGCFD_CYCLE_V || !pre_sweeps.empty() || !post_sweeps.empty(); }
-    // dual time stepping: --physical-time-step DT / --time-steps N / --dual-time-clamp X / --bdf-order 1|2 and the config keys
-    // physical_time_step / time_steps / dual_time_clamp / bdf_order.  With DT given, -g is the number of cycles per physical step.
+    // dual time stepping.  With DT given, num_cycles is the number of cycles per physical step.
     bool dual_given = false;          // a DT was given: mgcfd_set_dual_time before the first cycle, mgcfd_advance for the cycles
     bool dual_extras_given = false;   // one of the three companions was given (they need DT)
     double dual_dt = 0.0, dual_clamp = MGCFD_DUAL_TIME_CLAMP;
     int time_steps = 1, bdf_order = 2;
-    // flow statistics (mgcfd_set_statistics): --output-statistics writes statistics.* (and, with --output-surface,
-    // surface_statistics.*) from the samples mgcfd_advance takes; --statistics-start K: the first K physical steps are not sampled.
-    // Dual-time runs on one GPU only.
+    // flow statistics (mgcfd_set_statistics): statistics.* (and, with output_surface, surface_statistics.*) from the samples
+    // mgcfd_advance takes; the first statistics_start physical steps are not sampled
     bool output_statistics = false, statistics_start_given = false;
     int statistics_start = 0;
     int steps() const { return dual_given ? time_steps : 1; }
     int total_cycles() const { return (num_cycles > 0 ? num_cycles : 0) * steps(); }      // RMS lines of the run
     int loads_rows() const { return dual_given ? time_steps : (num_cycles > 0 ? num_cycles : 0); }   // one row per physical step
-    // the k-th angle of the run (one angle without --polar)
+    // the k-th angle of the run (one angle without a polar)
     int num_angles() const { return polar ? polar_n : 1; }
     double angle(int k) const { return !polar ? angle_of_attack : (polar_n == 1 ? polar_a0 : polar_a0 + (polar_a1 - polar_a0) * double(k) / double(polar_n - 1)); }
 };
@@ -151,19 +141,7 @@ bool parse_number(const char *text, double *out)
     *out = v;
     return true;
 }
-
-// reference | global | local | local-legacy (or local_legacy)
-bool parse_time_step_mode(const char *text, int *out)
-{
-    const std::string t(text ? text : "");
-    if (t == "reference") *out = MGCFD_DT_REFERENCE;
-    else if (t == "global") *out = MGCFD_DT_GLOBAL;
-    else if (t == "local") *out = MGCFD_DT_LOCAL;
-    else if (t == "local-legacy" || t == "local_legacy") *out = MGCFD_DT_LOCAL_LEGACY;
-    else return false;
-    return true;
-}
-// a finite number above zero (the CFL number, the residual smoothing's coefficient)
+// a finite number above zero
 bool parse_positive(const char *text, double *out)
 {
     double v = 0.0;
@@ -171,59 +149,7 @@ bool parse_positive(const char *text, double *out)
     *out = v;
     return true;
 }
-
-// --limiter / limiter: "none", "barth-jespersen" or "venkatakrishnan"
-bool set_limiter(Config &c, const char *text)
-{
-    const std::string v(text);
-    if (v == "none") c.limiter = MGCFD_LIMITER_NONE;
-    else if (v == "barth-jespersen") c.limiter = MGCFD_LIMITER_BARTH_JESPERSEN;
-    else if (v == "venkatakrishnan") c.limiter = MGCFD_LIMITER_VENKATAKRISHNAN;
-    else return false;
-    c.upwind_given = true;
-    return true;
-}
-// --face-gradient / face_gradient: "averaged" or "corrected"
-bool set_face_gradient(Config &c, const char *text)
-{
-    const std::string v(text ? text : "");
-    if (v != "averaged" && v != "corrected") return false;
-    c.face_gradient = v == "corrected" ? MGCFD_FACE_GRADIENT_CORRECTED : MGCFD_FACE_GRADIENT_AVERAGED;
-    c.face_gradient_given = true;
-    return true;
-}
-// --sa-length / sa_length: the model length of the Spalart-Allmaras model by name
-bool set_sa_length(Config &c, const char *text)
-{
-    const std::string v(text ? text : "");
-    if (v != "wall" && v != "des" && v != "ddes") return false;
-    c.sa_length = v == "ddes" ? MGCFD_SA_LENGTH_DDES : (v == "des" ? MGCFD_SA_LENGTH_DES : MGCFD_SA_LENGTH_WALL);
-    return true;
-}
-
-// one of the three wall thermal settings: which = 0 --wall-temperature T, 1 --wall-temperature-ratio R (both above zero),
-// 2 --wall-heat-flux Q (any finite number); counts how many were given
-bool set_wall_thermal(Config &c, int which, const char *text)
-{
-    double v = 0.0;
-    if (which == 2 ? !parse_number(text, &v) : !parse_positive(text, &v)) return false;
-    c.wall_thermal_flags++;
-    c.wall_mode = which == 2 ? MGCFD_WALL_HEAT_FLUX : MGCFD_WALL_ISOTHERMAL;
-    c.wall_value = v;
-    c.wall_ratio = which == 1;
-    return true;
-}
-
-// the smoothing's Jacobi iterations: a whole number 0 ... MGCFD_MAX_SMOOTHING_ITERATIONS
-bool parse_smoothing_iterations(const char *text, int *out)
-{
-    double v = 0.0;
-    if (!parse_number(text, &v) || v < 0.0 || v > double(MGCFD_MAX_SMOOTHING_ITERATIONS) || v != double(int(v))) return false;
-    *out = int(v);
-    return true;
-}
-
-// a finite number not below zero (the JST coefficients)
+// a finite number not below zero
 bool parse_not_negative(const char *text, double *out)
 {
     double v = 0.0;
@@ -231,8 +157,7 @@ bool parse_not_negative(const char *text, double *out)
     *out = v;
     return true;
 }
-
-// a whole number lo ... hi (the physical time steps, the BDF order, the JST levels)
+// a whole number lo ... hi
 bool parse_whole(const char *text, int lo, int hi, int *out)
 {
     double v = 0.0;
@@ -257,8 +182,10 @@ bool parse_whole_list(const char *text, int lo, int hi, std::vector<int> *out)
 constexpr int kMaxTimeSteps = 1000000;
 constexpr int kMaxJstLevels = 64;
 
-// "A0:A1:N": two finite angles and a count of at least 1
-bool parse_polar(const char *text, Config &c)
+// ---- the options that need more than a kind of value: each a function of its own, named by its entry in kOptions
+
+// --polar "A0:A1:N": two finite angles and a count of at least 1
+bool set_polar(Config &c, const char *text)
 {
     const std::string t(text ? text : "");
     const size_t p1 = t.find(':'), p2 = p1 == std::string::npos ? p1 : t.find(':', p1 + 1);
@@ -273,8 +200,8 @@ bool parse_polar(const char *text, Config &c)
     return true;
 }
 
-// "S,c,x,y,z": five finite numbers, S and c positive; false on anything else
-bool parse_loads_reference(const char *text, double out[5])
+// --loads-reference "S,c,x,y,z": five finite numbers, S and c positive; false on anything else
+bool set_loads_reference(Config &c, const char *text)
 {
     const char *p = text;
     for (int k = 0; k < 5; k++) {
@@ -286,10 +213,275 @@ bool parse_loads_reference(const char *text, double out[5])
         char *end = nullptr;
         const double v = std::strtod(p, &end);
         if (end == p || !std::isfinite(v)) return false;
-        out[k] = v;
+        c.loads_ref[k] = v;
         p = end;
     }
-    return *p == '\0' && out[0] > 0.0 && out[1] > 0.0;
+    return *p == '\0' && c.loads_ref[0] > 0.0 && c.loads_ref[1] > 0.0;
+}
+
+// one of the three wall thermal settings: which = 0 --wall-temperature T, 1 --wall-temperature-ratio R (both above zero),
+// 2 --wall-heat-flux Q (any finite number); counts how many were given
+bool set_wall_thermal(Config &c, int which, const char *text)
+{
+    double v = 0.0;
+    if (which == 2 ? !parse_number(text, &v) : !parse_positive(text, &v)) return false;
+    c.wall_thermal_flags++;
+    c.wall_mode = which == 2 ? MGCFD_WALL_HEAT_FLUX : MGCFD_WALL_ISOTHERMAL;
+    c.wall_value = v;
+    c.wall_ratio = which == 1;
+    return true;
+}
+bool set_wall_temperature(Config &c, const char *text) { return set_wall_thermal(c, 0, text); }
+bool set_wall_temperature_ratio(Config &c, const char *text) { return set_wall_thermal(c, 1, text); }
+bool set_wall_heat_flux(Config &c, const char *text) { return set_wall_thermal(c, 2, text); }
+
+bool set_no_slip(Config &c, const char *) { return c.no_slip = c.viscous_extras_given = true; }
+bool set_sa_time_accurate(Config &c, const char *) { return c.sa_time_accurate = c.sa_unsteady_given = true; }
+bool set_viscous_cfl(Config &c, const char *text)
+{
+    if (!parse_positive(text, &c.viscous_cfl)) return false;
+    return c.viscous_extras_given = c.viscous_cfl_given = true;
+}
+// --entropy-fix: Harten's fraction, 0 ... 1
+bool set_entropy_fix(Config &c, const char *text)
+{
+    if (!parse_not_negative(text, &c.entropy_fix) || c.entropy_fix > 1.0) return false;
+    return c.upwind_given = true;
+}
+void read_config(Config &c);
+// -c: the file is read where it stands among the arguments, so an argument behind it overrides the file's value
+bool set_config_filepath(Config &c, const char *text)
+{
+    c.config_filepath = text;
+    read_config(c);
+    return true;
+}
+void print_help();
+// -h: refuses without a phrase, which ends the parsing without an error message
+bool help_and_stop(Config &, const char *)
+{
+    print_help();
+    return false;
+}
+
+// ---- the option table: every flag of the command line and every key of a config file, once
+
+enum class Read {
+    Flag,          // sets its bool (a config file: by the value Y only)
+    FlagOff,       // clears its bool
+    String,
+    Int,           // atoi, as the reference reads its numbers: never refused
+    Ignored,       // accepted and dropped
+    Number,        // parse_number
+    Positive,      // parse_positive
+    NotNegative,   // parse_not_negative
+    Whole,         // parse_whole(lo, hi)
+    WholeList,     // parse_whole_list(lo, hi)
+    Name,          // one of `names`
+    Custom,        // the function `custom`
+};
+
+struct Name { const char *name; int value; };
+const Name kTimeStepModes[] = {{"reference", MGCFD_DT_REFERENCE}, {"global", MGCFD_DT_GLOBAL}, {"local", MGCFD_DT_LOCAL},
+                               {"local-legacy", MGCFD_DT_LOCAL_LEGACY}, {"local_legacy", MGCFD_DT_LOCAL_LEGACY}, {nullptr, 0}};
+const Name kCycleShapes[] = {{"V", MGCFD_CYCLE_V}, {"v", MGCFD_CYCLE_V}, {"W", MGCFD_CYCLE_W}, {"w", MGCFD_CYCLE_W}, {"F", MGCFD_CYCLE_F}, {"f", MGCFD_CYCLE_F}, {nullptr, 0}};
+const Name kLimiters[] = {{"none", MGCFD_LIMITER_NONE}, {"barth-jespersen", MGCFD_LIMITER_BARTH_JESPERSEN}, {"venkatakrishnan", MGCFD_LIMITER_VENKATAKRISHNAN}, {nullptr, 0}};
+const Name kFaceGradients[] = {{"averaged", MGCFD_FACE_GRADIENT_AVERAGED}, {"corrected", MGCFD_FACE_GRADIENT_CORRECTED}, {nullptr, 0}};
+const Name kSaLengths[] = {{"wall", MGCFD_SA_LENGTH_WALL}, {"des", MGCFD_SA_LENGTH_DES}, {"ddes", MGCFD_SA_LENGTH_DDES}, {nullptr, 0}};
+
+// the field of Config a value goes to, whatever its type
+struct Dest {
+    bool Config::*b = nullptr;
+    int Config::*i = nullptr;
+    double Config::*d = nullptr;
+    std::string Config::*s = nullptr;
+    std::vector<int> Config::*v = nullptr;
+    Dest() {}
+    Dest(bool Config::*p) : b(p) {}
+    Dest(int Config::*p) : i(p) {}
+    Dest(double Config::*p) : d(p) {}
+    Dest(std::string Config::*p) : s(p) {}
+    Dest(std::vector<int> Config::*p) : v(p) {}
+};
+
+// how an option's value is read: a kind, and what that kind needs
+struct Reader {
+    Read kind;
+    int lo, hi;                                  // Whole, WholeList
+    const Name *names;                           // Name
+    bool (*custom)(Config &, const char *);      // Custom
+    Reader(Read k, int l = 0, int h = 0, const Name *n = nullptr, bool (*f)(Config &, const char *) = nullptr) : kind(k), lo(l), hi(h), names(n), custom(f) {}
+};
+Reader whole(int lo, int hi) { return {Read::Whole, lo, hi}; }
+Reader whole_list(int lo, int hi) { return {Read::WholeList, lo, hi}; }
+Reader one_of(const Name *names) { return {Read::Name, 0, 0, names}; }
+Reader by(bool (*custom)(Config &, const char *)) { return {Read::Custom, 0, 0, nullptr, custom}; }
+
+struct Option {
+    const char *cli;                  // --cli on the command line, or none
+    char letter;                      // -l, or 0
+    const char *key;                  // the key of a config file, or none
+    int has_arg;                      // kNoArg; kArg; kOptArg: --cli, --cli=X or --cli X on the command line, Y, X or N in a config file
+    Reader read;
+    Dest dest = {};
+    bool Config::*given = nullptr;    // raised by every accepted value (of a kOptArg option: the option's own switch)
+    const char *expected = nullptr;   // "ERROR: ...: expected <this>"; none: the phrase of the kind (expected_phrase)
+    bool config_warns = false;        // a config file's bad value is a warning on stdout and the run goes on
+};
+
+constexpr int kNoArg = no_argument, kArg = required_argument, kOptArg = optional_argument;
+const Option kOptions[] = {
+    // the reference's (src/Base/config.cpp:32-47, 81-157)
+    {"help", 'h', nullptr, kNoArg, by(help_and_stop)},
+    {"config-filepath", 'c', nullptr, kArg, by(set_config_filepath)},
+    {"input-file", 'i', "input_file", kArg, Read::String, &Config::input_file},
+    {"input-directory", 'd', "input_file_directory", kArg, Read::String, &Config::input_file_directory},
+    {"papi_config_file", 'p', "papi_config_file", kArg, Read::String, &Config::papi_config_file},
+    {"output-file-prefix", 'o', "output_file_prefix", kArg, Read::String, &Config::output_file_prefix},
+    {"mesh-duplicate-count", 'm', "mesh_duplicate_count", kArg, Read::Int, &Config::mesh_duplicate_count},
+    {"num-cycles", 'g', "cycles", kArg, Read::Int, &Config::num_cycles},
+    {"validate-result", 'v', nullptr, kNoArg, Read::Flag, &Config::validate_result},
+    {"output-variables", 0, "output_variables", kNoArg, Read::Flag, &Config::output_variables},
+    {"output-fluxes", 0, "output_fluxes", kNoArg, Read::Flag, &Config::output_fluxes},
+    {"output-step-factors", 0, "output_step_factors", kNoArg, Read::Flag, &Config::output_step_factors},
+    // extensions
+    {"device", 0, nullptr, kArg, Read::Int, &Config::device},
+    {"no-timers", 0, nullptr, kNoArg, Read::FlagOff, &Config::timers},
+    {"no-indirect-rw", 0, nullptr, kNoArg, Read::FlagOff, &Config::indirect_rw},
+    {"fast", 0, nullptr, kNoArg, Read::Flag, &Config::fast_math},
+    {"legacy-ordering", 0, nullptr, kNoArg, Read::Flag, &Config::legacy_ordering},
+    {"gpus", 0, nullptr, kArg, Read::Int, &Config::gpus},
+    {"gpus-share-device", 0, nullptr, kNoArg, Read::Flag, &Config::gpus_share_device},
+    {"loop-timers", 0, nullptr, kNoArg, Read::Flag, &Config::loop_timers},
+    {"gpus-partition", 0, nullptr, kNoArg, Read::Flag, &Config::gpus_partition},
+    {"output-loads", 0, nullptr, kNoArg, Read::Flag, &Config::output_loads},
+    {"loads-reference", 0, nullptr, kArg, by(set_loads_reference), {}, nullptr, "S,c,x,y,z (five numbers, S and c positive)"},
+    {"mach", 0, "ff_mach", kArg, Read::Number, &Config::ff_mach, &Config::free_stream_given, nullptr, true},
+    {"alpha", 0, "angle_of_attack", kArg, Read::Number, &Config::angle_of_attack, &Config::free_stream_given, nullptr, true},
+    {"polar", 0, nullptr, kArg, by(set_polar), {}, nullptr, "A0:A1:N (two angles in degrees and a count of at least 1)"},
+    {"time-step", 0, "time_step", kArg, one_of(kTimeStepModes), &Config::time_step_mode, &Config::time_step_given, "reference, global, local or local-legacy"},
+    {"cfl", 0, "cfl", kArg, Read::Positive, &Config::cfl, &Config::time_step_given},
+    {"residual-smoothing", 0, "residual_smoothing", kArg, Read::Positive, &Config::smoothing_eps, &Config::smoothing_given},
+    {"smoothing-iterations", 0, "smoothing_iterations", kArg, whole(0, MGCFD_MAX_SMOOTHING_ITERATIONS), &Config::smoothing_iterations, &Config::smoothing_iterations_given},
+    {"physical-time-step", 0, "physical_time_step", kArg, Read::Positive, &Config::dual_dt, &Config::dual_given},
+    {"time-steps", 0, "time_steps", kArg, whole(1, kMaxTimeSteps), &Config::time_steps, &Config::dual_extras_given},
+    {"dual-time-clamp", 0, "dual_time_clamp", kArg, Read::Positive, &Config::dual_clamp, &Config::dual_extras_given},
+    {"bdf-order", 0, "bdf_order", kArg, whole(1, 2), &Config::bdf_order, &Config::dual_extras_given, "1 or 2"},
+    {"jst", 0, "jst", kNoArg, Read::Flag, &Config::jst_given},
+    {"fas", 0, "fas", kNoArg, Read::Flag, &Config::fas},
+    {"cycle", 0, nullptr, kArg, one_of(kCycleShapes), &Config::cycle_shape, nullptr, "V, W or F"},
+    {"pre-sweeps", 0, nullptr, kArg, whole_list(1, MGCFD_MAX_CYCLE_SWEEPS), &Config::pre_sweeps},
+    {"post-sweeps", 0, nullptr, kArg, whole_list(0, MGCFD_MAX_CYCLE_SWEEPS), &Config::post_sweeps},
+    {"fmg-cycles", 0, nullptr, kArg, whole_list(0, MGCFD_MAX_ADVANCE_CYCLES), &Config::fmg_cycles},
+    {"jst-kappa2", 0, "jst_kappa2", kArg, Read::NotNegative, &Config::jst_kappa2, &Config::jst_given},
+    {"jst-kappa4", 0, "jst_kappa4", kArg, Read::NotNegative, &Config::jst_kappa4, &Config::jst_given},
+    {"jst-levels", 0, "jst_levels", kArg, whole(0, kMaxJstLevels), &Config::jst_levels, &Config::jst_given},
+    {"viscosity", 0, "viscosity", kArg, Read::Positive, &Config::viscosity, &Config::viscosity_given},
+    {"reynolds", 0, "reynolds", kArg, Read::Positive, &Config::reynolds, &Config::reynolds_given},
+    {"ref-length", 0, "ref_length", kArg, Read::Positive, &Config::ref_length, &Config::viscous_extras_given},
+    {"prandtl", 0, "prandtl", kArg, Read::Positive, &Config::prandtl, &Config::viscous_extras_given},
+    {"viscous-cfl", 0, "viscous_cfl", kArg, by(set_viscous_cfl), {}, nullptr, "a finite number above zero"},
+    {"no-slip", 0, "no_slip", kNoArg, by(set_no_slip)},
+    {"viscous-levels", 0, "viscous_levels", kArg, whole(0, kMaxJstLevels), &Config::viscous_levels, &Config::viscous_extras_given},
+    {"sutherland", 0, "sutherland", kNoArg, Read::Flag, &Config::sutherland},
+    {"sutherland-tref", 0, "sutherland_tref", kArg, Read::Positive, &Config::sutherland_tref, &Config::model_extras_given},
+    {"sutherland-s", 0, "sutherland_s", kArg, Read::Positive, &Config::sutherland_s, &Config::model_extras_given},
+    {"prandtl-turbulent", 0, "prandtl_turbulent", kArg, Read::Positive, &Config::prandtl_turbulent, &Config::model_extras_given},
+    {"smagorinsky", 0, "smagorinsky", kOptArg, Read::Positive, &Config::smagorinsky_cs, &Config::smagorinsky, "a finite constant above zero"},
+    {"wall-damping", 0, "wall_damping", kOptArg, Read::Positive, &Config::wall_kappa, &Config::wall_damping, "a finite constant above zero"},
+    {"spalart-allmaras", 0, "spalart_allmaras", kOptArg, Read::Positive, &Config::sa_ratio, &Config::spalart_allmaras, "a finite ratio above zero"},
+    {"loads-friction", 0, nullptr, kNoArg, Read::Flag, &Config::loads_friction},
+    {"output-surface", 0, nullptr, kNoArg, Read::Flag, &Config::output_surface},
+    {"wall-temperature", 0, "wall_temperature", kArg, by(set_wall_temperature), {}, nullptr, "a finite number above zero"},
+    {"wall-temperature-ratio", 0, "wall_temperature_ratio", kArg, by(set_wall_temperature_ratio), {}, nullptr, "a finite number above zero"},
+    {"wall-heat-flux", 0, "wall_heat_flux", kArg, by(set_wall_heat_flux), {}, nullptr, "a finite number"},
+    {"loads-heat", 0, "loads_heat", kNoArg, Read::Flag, &Config::loads_heat},
+    {"face-gradient", 0, "face_gradient", kArg, one_of(kFaceGradients), &Config::face_gradient, &Config::face_gradient_given, "averaged or corrected"},
+    {"sa-time-accurate", 0, "sa_time_accurate", kNoArg, by(set_sa_time_accurate)},
+    {"sa-length", 0, "sa_length", kArg, one_of(kSaLengths), &Config::sa_length, &Config::sa_unsteady_given, "wall, des or ddes"},
+    {"sa-cdes", 0, "sa_cdes", kArg, Read::Positive, &Config::sa_cdes, &Config::sa_unsteady_given},
+    {"output-statistics", 0, nullptr, kNoArg, Read::Flag, &Config::output_statistics},
+    {"statistics-start", 0, nullptr, kArg, whole(0, kMaxTimeSteps), &Config::statistics_start, &Config::statistics_start_given},
+    {"upwind", 0, "upwind", kNoArg, Read::Flag, &Config::upwind_given},
+    {"upwind-levels", 0, "upwind_levels", kArg, whole(0, kMaxJstLevels), &Config::upwind_levels, &Config::upwind_given},
+    {"muscl-levels", 0, "muscl_levels", kArg, whole(0, kMaxJstLevels), &Config::muscl_levels_said, &Config::upwind_given},
+    {"limiter", 0, "limiter", kArg, one_of(kLimiters), &Config::limiter, &Config::upwind_given, "none, barth-jespersen or venkatakrishnan"},
+    {"venkat-k", 0, "venkat_k", kArg, Read::Positive, &Config::venkat_k, &Config::upwind_given},
+    {"entropy-fix", 0, "entropy_fix", kArg, by(set_entropy_fix), {}, nullptr, "a number 0 ... 1"},
+    // keys of a config file alone (src/Base/config.cpp:81-157)
+    {nullptr, 0, "config_filepath", kArg, Read::String, &Config::config_filepath},
+    {nullptr, 0, "omp_num_threads", kArg, Read::Ignored},      // (no OpenMP here)
+    {nullptr, 0, "output_old_variables", kNoArg, Read::Flag, &Config::output_old_variables},
+    {nullptr, 0, "output_edge_fluxes", kNoArg, Read::Flag, &Config::output_edge_fluxes},
+    {nullptr, 0, "output_volumes", kNoArg, Read::Flag, &Config::output_volumes},
+};
+constexpr int kFirstOptionCode = 1000;   // getopt_long's code of kOptions[k] is kFirstOptionCode + k: above every short letter
+
+std::string expected_phrase(const Option &o)
+{
+    if (o.expected) return o.expected;
+    switch (o.read.kind) {
+        case Read::Number: return "a number";
+        case Read::Positive: return "a finite number above zero";
+        case Read::NotNegative: return "a finite number, zero or above";
+        case Read::Whole: return "a whole number " + std::to_string(o.read.lo) + " ... " + std::to_string(o.read.hi);
+        case Read::WholeList: return "whole numbers " + std::to_string(o.read.lo) + " ... " + std::to_string(o.read.hi) + ", comma separated";
+        default: return "";
+    }
+}
+
+// the value of one option into its field; false: refused
+bool read_value(const Option &o, Config &c, const char *text)
+{
+    switch (o.read.kind) {
+        case Read::Flag: c.*o.dest.b = true; return true;
+        case Read::FlagOff: c.*o.dest.b = false; return true;
+        case Read::String: c.*o.dest.s = text; return true;
+        case Read::Int: c.*o.dest.i = std::atoi(text); return true;
+        case Read::Ignored: return true;
+        case Read::Number: return parse_number(text, &(c.*o.dest.d));
+        case Read::Positive: return parse_positive(text, &(c.*o.dest.d));
+        case Read::NotNegative: return parse_not_negative(text, &(c.*o.dest.d));
+        case Read::Whole: return parse_whole(text, o.read.lo, o.read.hi, &(c.*o.dest.i));
+        case Read::WholeList: return parse_whole_list(text, o.read.lo, o.read.hi, &(c.*o.dest.v));
+        case Read::Name:
+            for (const Name *n = o.read.names; n->name; n++)
+                if (std::strcmp(text, n->name) == 0) {
+                    c.*o.dest.i = n->value;
+                    return true;
+                }
+            return false;
+        case Read::Custom: return o.read.custom(c, text);
+    }
+    return false;
+}
+
+// One option with its value (none: a flag, or an optional value left out), from the command line or from a config file.
+// A refused value is reported as its source has it: the command line ends the parsing (false); a config file marks the run
+// (config_bad) and is read on.
+bool apply_option(const Option &o, Config &c, const char *text, bool from_config_file)
+{
+    if (from_config_file && o.has_arg == no_argument && std::strcmp(text, "Y") != 0) return true;   // (a flag is set by Y alone)
+    if (from_config_file && o.has_arg == optional_argument) {
+        if (std::strcmp(text, "N") == 0) return true;
+        if (std::strcmp(text, "Y") == 0) text = nullptr;
+    }
+    if ((text || o.has_arg != optional_argument) && !read_value(o, c, text)) {
+        const std::string expected = expected_phrase(o);
+        if (expected.empty()) return false;
+        if (!from_config_file) {
+            std::fprintf(stderr, "ERROR: --%s=%s: expected %s\n", o.cli, text, expected.c_str());
+            return false;
+        }
+        if (o.config_warns) std::printf("WARNING: %s = '%s' is not a number.\n", o.key, text);
+        else {
+            std::fprintf(stderr, "ERROR: %s = '%s': expected %s%s\n", o.key, text, o.has_arg == optional_argument ? "Y or " : "", expected.c_str());
+            c.config_bad = true;
+        }
+        return true;
+    }
+    if (o.given) c.*o.given = true;
+    return true;
 }
 
 std::string trim(const std::string &s)
@@ -301,135 +493,12 @@ std::string trim(const std::string &s)
 
 void set_param(Config &c, const std::string &key, const std::string &value)
 {
-    // src/Base/config.cpp:81-157
-    if (key == "config_filepath") c.config_filepath = value;
-    else if (key == "input_file") c.input_file = value;
-    else if (key == "input_file_directory") c.input_file_directory = value;
-    else if (key == "papi_config_file") c.papi_config_file = value;
-    else if (key == "output_file_prefix") c.output_file_prefix = value;
-    else if (key == "mesh_duplicate_count") c.mesh_duplicate_count = std::atoi(value.c_str());
-    else if (key == "cycles") c.num_cycles = std::atoi(value.c_str());
-    else if (key == "omp_num_threads") { /* no OpenMP here */ }
-    else if (key == "output_variables") { if (value == "Y") c.output_variables = true; }
-    else if (key == "output_old_variables") { if (value == "Y") c.output_old_variables = true; }
-    else if (key == "output_step_factors") { if (value == "Y") c.output_step_factors = true; }
-    else if (key == "output_edge_fluxes") { if (value == "Y") c.output_edge_fluxes = true; }
-    else if (key == "output_fluxes") { if (value == "Y") c.output_fluxes = true; }
-    else if (key == "output_volumes") { if (value == "Y") c.output_volumes = true; }
-    else if (key == "ff_mach") { if (parse_number(value.c_str(), &c.ff_mach)) c.free_stream_given = true; else std::printf("WARNING: ff_mach = '%s' is not a number.\n", value.c_str()); }
-    else if (key == "angle_of_attack") { if (parse_number(value.c_str(), &c.angle_of_attack)) c.free_stream_given = true; else std::printf("WARNING: angle_of_attack = '%s' is not a number.\n", value.c_str()); }
-    else if (key == "time_step") {
-        if (parse_time_step_mode(value.c_str(), &c.time_step_mode)) c.time_step_given = true;
-        else { std::fprintf(stderr, "ERROR: time_step = '%s': expected reference, global, local or local-legacy\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "cfl") {
-        if (parse_positive(value.c_str(), &c.cfl)) c.time_step_given = true;
-        else { std::fprintf(stderr, "ERROR: cfl = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "residual_smoothing") {
-        if (parse_positive(value.c_str(), &c.smoothing_eps)) c.smoothing_given = true;
-        else { std::fprintf(stderr, "ERROR: residual_smoothing = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "smoothing_iterations") {
-        if (parse_smoothing_iterations(value.c_str(), &c.smoothing_iterations)) c.smoothing_iterations_given = true;
-        else { std::fprintf(stderr, "ERROR: smoothing_iterations = '%s': expected a whole number 0 ... %d\n", value.c_str(), MGCFD_MAX_SMOOTHING_ITERATIONS); c.config_bad = true; }
-    }
-    else if (key == "jst") { if (value == "Y") c.jst_given = true; }
-    else if (key == "fas") { if (value == "Y") c.fas = true; }
-    else if (key == "jst_kappa2" || key == "jst_kappa4") {
-        if (parse_not_negative(value.c_str(), key == "jst_kappa2" ? &c.jst_kappa2 : &c.jst_kappa4)) c.jst_given = true;
-        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number, zero or above\n", key.c_str(), value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "jst_levels") {
-        if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.jst_levels)) c.jst_given = true;
-        else { std::fprintf(stderr, "ERROR: jst_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
-    }
-    else if (key == "upwind") { if (value == "Y") c.upwind_given = true; }
-    else if (key == "upwind_levels" || key == "muscl_levels") {
-        if (parse_whole(value.c_str(), 0, kMaxJstLevels, key == "upwind_levels" ? &c.upwind_levels : &c.muscl_levels_said)) c.upwind_given = true;
-        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a whole number 0 ... %d\n", key.c_str(), value.c_str(), kMaxJstLevels); c.config_bad = true; }
-    }
-    else if (key == "limiter") {
-        if (!set_limiter(c, value.c_str())) { std::fprintf(stderr, "ERROR: limiter = '%s': expected none, barth-jespersen or venkatakrishnan\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "venkat_k") {
-        if (parse_positive(value.c_str(), &c.venkat_k)) c.upwind_given = true;
-        else { std::fprintf(stderr, "ERROR: venkat_k = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "entropy_fix") {
-        if (parse_not_negative(value.c_str(), &c.entropy_fix) && c.entropy_fix <= 1.0) c.upwind_given = true;
-        else { std::fprintf(stderr, "ERROR: entropy_fix = '%s': expected a number 0 ... 1\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "viscosity" || key == "reynolds" || key == "ref_length" || key == "prandtl" || key == "viscous_cfl") {
-        double *dst = key == "viscosity" ? &c.viscosity : key == "reynolds" ? &c.reynolds : key == "ref_length" ? &c.ref_length : key == "prandtl" ? &c.prandtl : &c.viscous_cfl;
-        if (parse_positive(value.c_str(), dst)) {
-            if (key == "viscosity") c.viscosity_given = true; else if (key == "reynolds") c.reynolds_given = true; else c.viscous_extras_given = true;
-            if (key == "viscous_cfl") c.viscous_cfl_given = true;
+    for (const Option &o : kOptions)
+        if (o.key && key == o.key) {
+            apply_option(o, c, value.c_str(), true);
+            return;
         }
-        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "sutherland") { if (value == "Y") c.sutherland = true; }
-    else if (key == "smagorinsky") {
-        if (value == "Y") c.smagorinsky = true;
-        else if (parse_positive(value.c_str(), &c.smagorinsky_cs)) c.smagorinsky = true;
-        else if (value != "N") { std::fprintf(stderr, "ERROR: smagorinsky = '%s': expected Y or a finite constant above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "spalart_allmaras") {
-        if (value == "Y") c.spalart_allmaras = true;
-        else if (parse_positive(value.c_str(), &c.sa_ratio)) c.spalart_allmaras = true;
-        else if (value != "N") { std::fprintf(stderr, "ERROR: spalart_allmaras = '%s': expected Y or a finite ratio above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "sa_time_accurate") { if (value == "Y") { c.sa_time_accurate = true; c.sa_unsteady_given = true; } }
-    else if (key == "sa_length") {
-        if (set_sa_length(c, value.c_str())) c.sa_unsteady_given = true;
-        else { std::fprintf(stderr, "ERROR: sa_length = '%s': expected wall, des or ddes\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "sa_cdes") {
-        if (parse_positive(value.c_str(), &c.sa_cdes)) c.sa_unsteady_given = true;
-        else { std::fprintf(stderr, "ERROR: sa_cdes = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "wall_damping") {
-        if (value == "Y") c.wall_damping = true;
-        else if (parse_positive(value.c_str(), &c.wall_kappa)) c.wall_damping = true;
-        else if (value != "N") { std::fprintf(stderr, "ERROR: wall_damping = '%s': expected Y or a finite constant above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "sutherland_tref" || key == "sutherland_s" || key == "prandtl_turbulent") {
-        double *dst = key == "sutherland_tref" ? &c.sutherland_tref : key == "sutherland_s" ? &c.sutherland_s : &c.prandtl_turbulent;
-        if (parse_positive(value.c_str(), dst)) c.model_extras_given = true;
-        else { std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number above zero\n", key.c_str(), value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "no_slip") { if (value == "Y") { c.no_slip = true; c.viscous_extras_given = true; } }
-    else if (key == "wall_temperature" || key == "wall_temperature_ratio" || key == "wall_heat_flux") {
-        if (!set_wall_thermal(c, key == "wall_heat_flux" ? 2 : (key == "wall_temperature_ratio" ? 1 : 0), value.c_str())) {
-            std::fprintf(stderr, "ERROR: %s = '%s': expected a finite number%s\n", key.c_str(), value.c_str(), key == "wall_heat_flux" ? "" : " above zero");
-            c.config_bad = true;
-        }
-    }
-    else if (key == "loads_heat") { if (value == "Y") c.loads_heat = true; }
-    else if (key == "face_gradient") {
-        if (!set_face_gradient(c, value.c_str())) { std::fprintf(stderr, "ERROR: face_gradient = '%s': expected averaged or corrected\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "viscous_levels") {
-        if (parse_whole(value.c_str(), 0, kMaxJstLevels, &c.viscous_levels)) c.viscous_extras_given = true;
-        else { std::fprintf(stderr, "ERROR: viscous_levels = '%s': expected a whole number 0 ... %d\n", value.c_str(), kMaxJstLevels); c.config_bad = true; }
-    }
-    else if (key == "physical_time_step") {
-        if (parse_positive(value.c_str(), &c.dual_dt)) c.dual_given = true;
-        else { std::fprintf(stderr, "ERROR: physical_time_step = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "time_steps") {
-        if (parse_whole(value.c_str(), 1, kMaxTimeSteps, &c.time_steps)) c.dual_extras_given = true;
-        else { std::fprintf(stderr, "ERROR: time_steps = '%s': expected a whole number 1 ... %d\n", value.c_str(), kMaxTimeSteps); c.config_bad = true; }
-    }
-    else if (key == "dual_time_clamp") {
-        if (parse_positive(value.c_str(), &c.dual_clamp)) c.dual_extras_given = true;
-        else { std::fprintf(stderr, "ERROR: dual_time_clamp = '%s': expected a finite number above zero\n", value.c_str()); c.config_bad = true; }
-    }
-    else if (key == "bdf_order") {
-        if (parse_whole(value.c_str(), 1, 2, &c.bdf_order)) c.dual_extras_given = true;
-        else { std::fprintf(stderr, "ERROR: bdf_order = '%s': expected 1 or 2\n", value.c_str()); c.config_bad = true; }
-    }
-    else std::printf("WARNING: Unknown key '%s' encountered during parsing of config file.\n", key.c_str());
+    std::printf("WARNING: Unknown key '%s' encountered during parsing of config file.\n", key.c_str());
 }
 
 void read_config(Config &c)
@@ -613,362 +682,28 @@ bool parse_arguments(int argc, char **argv, Config &c)
 {
     // src/Base/config.cpp:32-47,219-259.  (The reference stores the three --output-* flags
     // through bool-to-int* casts, so each one also clobbers the bools after it; here every
-    // flag sets exactly its own field.)
-    static const option long_opts[] = {
-        {"help", no_argument, nullptr, 'h'},
-        {"config-filepath", required_argument, nullptr, 'c'},
-        {"input-file", required_argument, nullptr, 'i'},
-        {"input-directory", required_argument, nullptr, 'd'},
-        {"papi_config_file", required_argument, nullptr, 'p'},
-        {"output-file-prefix", required_argument, nullptr, 'o'},
-        {"mesh-duplicate-count", required_argument, nullptr, 'm'},
-        {"num-cycles", required_argument, nullptr, 'g'},
-        {"validate-result", no_argument, nullptr, 'v'},
-        {"output-variables", no_argument, nullptr, 1001},
-        {"output-fluxes", no_argument, nullptr, 1002},
-        {"output-step-factors", no_argument, nullptr, 1003},
-        {"device", required_argument, nullptr, 1004},
-        {"no-timers", no_argument, nullptr, 1005},
-        {"no-indirect-rw", no_argument, nullptr, 1006},
-        {"fast", no_argument, nullptr, 1007},
-        {"legacy-ordering", no_argument, nullptr, 1008},
-        {"gpus", required_argument, nullptr, 1009},
-        {"gpus-share-device", no_argument, nullptr, 1010},
-        {"loop-timers", no_argument, nullptr, 1011},
-        {"gpus-partition", no_argument, nullptr, 1012},
-        {"output-loads", no_argument, nullptr, 1013},
-        {"loads-reference", required_argument, nullptr, 1014},
-        {"mach", required_argument, nullptr, 1015},
-        {"alpha", required_argument, nullptr, 1016},
-        {"polar", required_argument, nullptr, 1017},
-        {"time-step", required_argument, nullptr, 1018},
-        {"cfl", required_argument, nullptr, 1019},
-        {"residual-smoothing", required_argument, nullptr, 1020},
-        {"smoothing-iterations", required_argument, nullptr, 1021},
-        {"physical-time-step", required_argument, nullptr, 1022},
-        {"time-steps", required_argument, nullptr, 1023},
-        {"dual-time-clamp", required_argument, nullptr, 1024},
-        {"bdf-order", required_argument, nullptr, 1025},
-        {"jst", no_argument, nullptr, 1026},
-        {"fas", no_argument, nullptr, 1030},
-        {"cycle", required_argument, nullptr, 1050},
-        {"pre-sweeps", required_argument, nullptr, 1051},
-        {"post-sweeps", required_argument, nullptr, 1052},
-        {"fmg-cycles", required_argument, nullptr, 1053},
-        {"jst-kappa2", required_argument, nullptr, 1027},
-        {"jst-kappa4", required_argument, nullptr, 1028},
-        {"jst-levels", required_argument, nullptr, 1029},
-        {"viscosity", required_argument, nullptr, 1031},
-        {"reynolds", required_argument, nullptr, 1032},
-        {"ref-length", required_argument, nullptr, 1033},
-        {"prandtl", required_argument, nullptr, 1034},
-        {"viscous-cfl", required_argument, nullptr, 1035},
-        {"no-slip", no_argument, nullptr, 1036},
-        {"viscous-levels", required_argument, nullptr, 1037},
-        {"sutherland", no_argument, nullptr, 1040},
-        {"sutherland-tref", required_argument, nullptr, 1041},
-        {"sutherland-s", required_argument, nullptr, 1042},
-        {"prandtl-turbulent", required_argument, nullptr, 1043},
-        {"smagorinsky", optional_argument, nullptr, 1044},
-        {"wall-damping", optional_argument, nullptr, 1045},
-        {"spalart-allmaras", optional_argument, nullptr, 1046},
-        {"loads-friction", no_argument, nullptr, 1038},
-        {"output-surface", no_argument, nullptr, 1039},
-        {"wall-temperature", required_argument, nullptr, 1047},
-        {"wall-temperature-ratio", required_argument, nullptr, 1048},
-        {"wall-heat-flux", required_argument, nullptr, 1049},
-        {"loads-heat", no_argument, nullptr, 1054},
-        {"face-gradient", required_argument, nullptr, 1055},
-        {"sa-time-accurate", no_argument, nullptr, 1056},
-        {"sa-length", required_argument, nullptr, 1057},
-        {"sa-cdes", required_argument, nullptr, 1058},
-        {"output-statistics", no_argument, nullptr, 1059},
-        {"statistics-start", required_argument, nullptr, 1060},
-        {"upwind", no_argument, nullptr, 1061},
-        {"upwind-levels", required_argument, nullptr, 1062},
-        {"muscl-levels", required_argument, nullptr, 1063},
-        {"limiter", required_argument, nullptr, 1064},
-        {"venkat-k", required_argument, nullptr, 1065},
-        {"entropy-fix", required_argument, nullptr, 1066},
-        {nullptr, 0, nullptr, 0}};
+    // flag sets exactly its own field.)  getopt_long's tables are made from kOptions.
+    std::vector<option> long_opts;
+    std::string letters;
+    for (const Option &o : kOptions) {
+        if (!o.cli) continue;
+        long_opts.push_back({o.cli, o.has_arg, nullptr, kFirstOptionCode + int(&o - kOptions)});
+        if (o.letter) letters += o.has_arg == required_argument ? std::string{o.letter, ':'} : std::string{o.letter};
+    }
+    long_opts.push_back({nullptr, 0, nullptr, 0});
     int optc;
-    while ((optc = getopt_long(argc, argv, "hc:i:d:p:o:m:g:v", long_opts, nullptr)) != -1) {
-        switch (optc) {
-            case 'h': print_help(); return false;
-            case 'i': c.input_file = optarg; break;
-            case 'c': c.config_filepath = optarg; read_config(c); break;
-            case 'd': c.input_file_directory = optarg; break;
-            case 'p': c.papi_config_file = optarg; break;
-            case 'o': c.output_file_prefix = optarg; break;
-            case 'm': c.mesh_duplicate_count = std::atoi(optarg); break;
-            case 'g': c.num_cycles = std::atoi(optarg); break;
-            case 'v': c.validate_result = true; break;
-            case 1001: c.output_variables = true; break;
-            case 1002: c.output_fluxes = true; break;
-            case 1003: c.output_step_factors = true; break;
-            case 1004: c.device = std::atoi(optarg); break;
-            case 1005: c.timers = false; break;
-            case 1006: c.indirect_rw = false; break;
-            case 1007: c.fast_math = true; break;
-            case 1008: c.legacy_ordering = true; break;
-            case 1009: c.gpus = std::atoi(optarg); break;
-            case 1010: c.gpus_share_device = true; break;
-            case 1011: c.loop_timers = true; break;
-            case 1012: c.gpus_partition = true; break;
-            case 1013: c.output_loads = true; break;
-            case 1014:
-                if (!parse_loads_reference(optarg, c.loads_ref)) {
-                    std::fprintf(stderr, "ERROR: --loads-reference=%s: expected S,c,x,y,z (five numbers, S and c positive)\n", optarg);
-                    return false;
-                }
-                break;
-            case 1015:
-            case 1016:
-                if (!parse_number(optarg, optc == 1015 ? &c.ff_mach : &c.angle_of_attack)) {
-                    std::fprintf(stderr, "ERROR: --%s=%s: expected a number\n", optc == 1015 ? "mach" : "alpha", optarg);
-                    return false;
-                }
-                c.free_stream_given = true;
-                break;
-            case 1017:
-                if (!parse_polar(optarg, c)) {
-                    std::fprintf(stderr, "ERROR: --polar=%s: expected A0:A1:N (two angles in degrees and a count of at least 1)\n", optarg);
-                    return false;
-                }
-                break;
-            case 1018:
-                if (!parse_time_step_mode(optarg, &c.time_step_mode)) {
-                    std::fprintf(stderr, "ERROR: --time-step=%s: expected reference, global, local or local-legacy\n", optarg);
-                    return false;
-                }
-                c.time_step_given = true;
-                break;
-            case 1019:
-                if (!parse_positive(optarg, &c.cfl)) {
-                    std::fprintf(stderr, "ERROR: --cfl=%s: expected a finite number above zero\n", optarg);
-                    return false;
-                }
-                c.time_step_given = true;
-                break;
-            case 1020:
-                if (!parse_positive(optarg, &c.smoothing_eps)) {
-                    std::fprintf(stderr, "ERROR: --residual-smoothing=%s: expected a finite number above zero\n", optarg);
-                    return false;
-                }
-                c.smoothing_given = true;
-                break;
-            case 1021:
-                if (!parse_smoothing_iterations(optarg, &c.smoothing_iterations)) {
-                    std::fprintf(stderr, "ERROR: --smoothing-iterations=%s: expected a whole number 0 ... %d\n", optarg, MGCFD_MAX_SMOOTHING_ITERATIONS);
-                    return false;
-                }
-                c.smoothing_iterations_given = true;
-                break;
-            case 1022:
-                if (!parse_positive(optarg, &c.dual_dt)) {
-                    std::fprintf(stderr, "ERROR: --physical-time-step=%s: expected a finite number above zero\n", optarg);
-                    return false;
-                }
-                c.dual_given = true;
-                break;
-            case 1023:
-                if (!parse_whole(optarg, 1, kMaxTimeSteps, &c.time_steps)) {
-                    std::fprintf(stderr, "ERROR: --time-steps=%s: expected a whole number 1 ... %d\n", optarg, kMaxTimeSteps);
-                    return false;
-                }
-                c.dual_extras_given = true;
-                break;
-            case 1024:
-                if (!parse_positive(optarg, &c.dual_clamp)) {
-                    std::fprintf(stderr, "ERROR: --dual-time-clamp=%s: expected a finite number above zero\n", optarg);
-                    return false;
-                }
-                c.dual_extras_given = true;
-                break;
-            case 1025:
-                if (!parse_whole(optarg, 1, 2, &c.bdf_order)) {
-                    std::fprintf(stderr, "ERROR: --bdf-order=%s: expected 1 or 2\n", optarg);
-                    return false;
-                }
-                c.dual_extras_given = true;
-                break;
-            case 1026: c.jst_given = true; break;
-            case 1030: c.fas = true; break;
-            case 1061: c.upwind_given = true; break;
-            case 1062:
-            case 1063:
-                if (!parse_whole(optarg, 0, kMaxJstLevels, optc == 1062 ? &c.upwind_levels : &c.muscl_levels_said)) {
-                    std::fprintf(stderr, "ERROR: --%s-levels=%s: expected a whole number 0 ... %d\n", optc == 1062 ? "upwind" : "muscl", optarg, kMaxJstLevels);
-                    return false;
-                }
-                c.upwind_given = true;
-                break;
-            case 1064:
-                if (!set_limiter(c, optarg)) {
-                    std::fprintf(stderr, "ERROR: --limiter=%s: expected none, barth-jespersen or venkatakrishnan\n", optarg);
-                    return false;
-                }
-                break;
-            case 1065:
-                if (!parse_positive(optarg, &c.venkat_k)) {
-                    std::fprintf(stderr, "ERROR: --venkat-k=%s: expected a finite number above zero\n", optarg);
-                    return false;
-                }
-                c.upwind_given = true;
-                break;
-            case 1066:
-                if (!parse_not_negative(optarg, &c.entropy_fix) || c.entropy_fix > 1.0) {
-                    std::fprintf(stderr, "ERROR: --entropy-fix=%s: expected a number 0 ... 1\n", optarg);
-                    return false;
-                }
-                c.upwind_given = true;
-                break;
-            case 1050: {
-                const std::string v(optarg);
-                if (v == "V" || v == "v") c.cycle_shape = MGCFD_CYCLE_V;
-                else if (v == "W" || v == "w") c.cycle_shape = MGCFD_CYCLE_W;
-                else if (v == "F" || v == "f") c.cycle_shape = MGCFD_CYCLE_F;
-                else { std::fprintf(stderr, "ERROR: --cycle=%s: expected V, W or F\n", optarg); return false; }
-                break;
-            }
-            case 1051:
-                if (!parse_whole_list(optarg, 1, MGCFD_MAX_CYCLE_SWEEPS, &c.pre_sweeps)) {
-                    std::fprintf(stderr, "ERROR: --pre-sweeps=%s: expected whole numbers 1 ... %d, comma separated\n", optarg, MGCFD_MAX_CYCLE_SWEEPS);
-                    return false;
-                }
-                break;
-            case 1052:
-                if (!parse_whole_list(optarg, 0, MGCFD_MAX_CYCLE_SWEEPS, &c.post_sweeps)) {
-                    std::fprintf(stderr, "ERROR: --post-sweeps=%s: expected whole numbers 0 ... %d, comma separated\n", optarg, MGCFD_MAX_CYCLE_SWEEPS);
-                    return false;
-                }
-                break;
-            case 1053:
-                if (!parse_whole_list(optarg, 0, MGCFD_MAX_ADVANCE_CYCLES, &c.fmg_cycles)) {
-                    std::fprintf(stderr, "ERROR: --fmg-cycles=%s: expected whole numbers 0 ... %d, comma separated\n", optarg, MGCFD_MAX_ADVANCE_CYCLES);
-                    return false;
-                }
-                break;
-            case 1027:
-            case 1028:
-                if (!parse_not_negative(optarg, optc == 1027 ? &c.jst_kappa2 : &c.jst_kappa4)) {
-                    std::fprintf(stderr, "ERROR: --jst-kappa%d=%s: expected a finite number, zero or above\n", optc == 1027 ? 2 : 4, optarg);
-                    return false;
-                }
-                c.jst_given = true;
-                break;
-            case 1029:
-                if (!parse_whole(optarg, 0, kMaxJstLevels, &c.jst_levels)) {
-                    std::fprintf(stderr, "ERROR: --jst-levels=%s: expected a whole number 0 ... %d\n", optarg, kMaxJstLevels);
-                    return false;
-                }
-                c.jst_given = true;
-                break;
-            case 1031: case 1032: case 1033: case 1034: case 1035: {
-                static const char *const names[] = {"viscosity", "reynolds", "ref-length", "prandtl", "viscous-cfl"};
-                double *const dst[] = {&c.viscosity, &c.reynolds, &c.ref_length, &c.prandtl, &c.viscous_cfl};
-                if (!parse_positive(optarg, dst[optc - 1031])) {
-                    std::fprintf(stderr, "ERROR: --%s=%s: expected a finite number above zero\n", names[optc - 1031], optarg);
-                    return false;
-                }
-                if (optc == 1031) c.viscosity_given = true; else if (optc == 1032) c.reynolds_given = true; else c.viscous_extras_given = true;
-                if (optc == 1035) c.viscous_cfl_given = true;
-                break;
-            }
-            case 1036: c.no_slip = true; c.viscous_extras_given = true; break;
-            case 1037:
-                if (!parse_whole(optarg, 0, kMaxJstLevels, &c.viscous_levels)) {
-                    std::fprintf(stderr, "ERROR: --viscous-levels=%s: expected a whole number 0 ... %d\n", optarg, kMaxJstLevels);
-                    return false;
-                }
-                c.viscous_extras_given = true;
-                break;
-            case 1038: c.loads_friction = true; break;
-            case 1040: c.sutherland = true; break;
-            case 1041: case 1042: case 1043: {
-                static const char *const names[] = {"sutherland-tref", "sutherland-s", "prandtl-turbulent"};
-                double *const dst[] = {&c.sutherland_tref, &c.sutherland_s, &c.prandtl_turbulent};
-                if (!parse_positive(optarg, dst[optc - 1041])) {
-                    std::fprintf(stderr, "ERROR: --%s=%s: expected a finite number above zero\n", names[optc - 1041], optarg);
-                    return false;
-                }
-                c.model_extras_given = true;
-                break;
-            }
-            case 1044: {
-                // --smagorinsky, --smagorinsky=CS or --smagorinsky CS (the next word, where it does not start another option)
-                const char *arg = optarg;
-                if (!arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
-                if (arg && !parse_positive(arg, &c.smagorinsky_cs)) {
-                    std::fprintf(stderr, "ERROR: --smagorinsky=%s: expected a finite constant above zero\n", arg);
-                    return false;
-                }
-                c.smagorinsky = true;
-                break;
-            }
-            case 1045: {
-                // --wall-damping, --wall-damping=KAPPA or --wall-damping KAPPA, as --smagorinsky takes its constant
-                const char *arg = optarg;
-                if (!arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
-                if (arg && !parse_positive(arg, &c.wall_kappa)) {
-                    std::fprintf(stderr, "ERROR: --wall-damping=%s: expected a finite constant above zero\n", arg);
-                    return false;
-                }
-                c.wall_damping = true;
-                break;
-            }
-            case 1046: {
-                // --spalart-allmaras, --spalart-allmaras=RATIO or --spalart-allmaras RATIO, as --smagorinsky takes its constant
-                const char *arg = optarg;
-                if (!arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
-                if (arg && !parse_positive(arg, &c.sa_ratio)) {
-                    std::fprintf(stderr, "ERROR: --spalart-allmaras=%s: expected a finite ratio above zero\n", arg);
-                    return false;
-                }
-                c.spalart_allmaras = true;
-                break;
-            }
-            case 1039: c.output_surface = true; break;
-            case 1047: case 1048: case 1049: {
-                static const char *const names[] = {"wall-temperature", "wall-temperature-ratio", "wall-heat-flux"};
-                if (!set_wall_thermal(c, optc - 1047, optarg)) {
-                    std::fprintf(stderr, "ERROR: --%s=%s: expected a finite number%s\n", names[optc - 1047], optarg, optc == 1049 ? "" : " above zero");
-                    return false;
-                }
-                break;
-            }
-            case 1054: c.loads_heat = true; break;
-            case 1055:
-                if (!set_face_gradient(c, optarg)) {
-                    std::fprintf(stderr, "ERROR: --face-gradient=%s: expected averaged or corrected\n", optarg);
-                    return false;
-                }
-                break;
-            case 1056: c.sa_time_accurate = true; c.sa_unsteady_given = true; break;
-            case 1057:
-                if (!set_sa_length(c, optarg)) {
-                    std::fprintf(stderr, "ERROR: --sa-length=%s: expected wall, des or ddes\n", optarg);
-                    return false;
-                }
-                c.sa_unsteady_given = true;
-                break;
-            case 1058:
-                if (!parse_positive(optarg, &c.sa_cdes)) {
-                    std::fprintf(stderr, "ERROR: --sa-cdes=%s: expected a finite number above zero\n", optarg);
-                    return false;
-                }
-                c.sa_unsteady_given = true;
-                break;
-            case 1059: c.output_statistics = true; break;
-            case 1060:
-                if (!parse_whole(optarg, 0, kMaxTimeSteps, &c.statistics_start)) {
-                    std::fprintf(stderr, "ERROR: --statistics-start=%s: expected a whole number 0 ... %d\n", optarg, kMaxTimeSteps);
-                    return false;
-                }
-                c.statistics_start_given = true;
-                break;
-            default: std::printf("Unknown command line parameter '%c'\n", optc);
+    while ((optc = getopt_long(argc, argv, letters.c_str(), long_opts.data(), nullptr)) != -1) {
+        const Option *o = nullptr;      // (a long option comes back as its code, a short one as its letter, anything else as '?')
+        for (const Option &s : kOptions)
+            if (s.cli && (optc == s.letter || optc == kFirstOptionCode + int(&s - kOptions))) o = &s;
+        if (!o) {
+            std::printf("Unknown command line parameter '%c'\n", optc);
+            continue;
         }
+        // --smagorinsky, --smagorinsky=CS or --smagorinsky CS (the next word, where it does not start another option)
+        const char *arg = optarg;
+        if (o->has_arg == optional_argument && !arg && optind < argc && argv[optind][0] != '-') arg = argv[optind++];
+        if (!apply_option(*o, c, arg, false)) return false;
     }
     if (c.smoothing_iterations_given && !c.smoothing_given && c.smoothing_iterations > 0) {
         std::fprintf(stderr, "ERROR: --smoothing-iterations needs --residual-smoothing EPS (the residual smoothing's coefficient)\n");
@@ -1076,6 +811,52 @@ bool parse_arguments(int argc, char **argv, Config &c)
         return false;
     }
     return !c.config_bad;
+}
+
+// the rules between options that main() applies once parse_arguments has let the run pass (so behind a config file's refused value)
+bool check_combinations(const Config &c)
+{
+    if (c.output_loads && c.gpus > 1 && !c.gpus_partition) {
+        std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
+        return false;
+    }
+    if (c.smoothing_given && c.smoothing_iterations > 0 && c.gpus > 1 && c.gpus_partition) {
+        std::fprintf(stderr, "ERROR: residual smoothing (--residual-smoothing) does not run with --gpus-partition: a level split over GPUs would need a halo exchange per Jacobi iteration\n");
+        return false;
+    }
+    if (c.jst_given && c.jst_levels > 0 && c.gpus > 1 && c.gpus_partition) {
+        std::fprintf(stderr, "ERROR: the JST dissipation (--jst) does not run with --gpus-partition: a level split over GPUs would need its sensor and Laplacian exchanged per stage\n");
+        return false;
+    }
+    if (c.viscous() && c.viscous_levels > 0 && c.gpus > 1 && c.gpus_partition) {
+        std::fprintf(stderr, "ERROR: the viscous terms (--viscosity, --reynolds) do not run with --gpus-partition: a level split over GPUs would need its node stresses exchanged per stage\n");
+        return false;
+    }
+    if (c.dual_given && c.gpus > 1 && c.gpus_partition) {
+        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --gpus-partition: levels split over GPUs are out of scope\n");
+        return false;
+    }
+    if (c.fas && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: FAS multigrid (--fas) runs on one GPU only: levels split over GPUs, or one level per GPU, would need the residuals, the forcing and the corrections exchanged\n");
+        return false;
+    }
+    if ((c.cycle_given() || !c.fmg_cycles.empty()) && c.gpus > 1) {
+        std::fprintf(stderr, "ERROR: --cycle, --pre-sweeps, --post-sweeps and --fmg-cycles run on one GPU only: levels split over GPUs, or one level per GPU, run the default cycle\n");
+        return false;
+    }
+    if (!c.fmg_cycles.empty() && (c.dual_given || c.polar)) {
+        std::fprintf(stderr, "ERROR: a full-multigrid start (--fmg-cycles) does not run with --physical-time-step or --polar\n");
+        return false;
+    }
+    if (c.dual_given && c.polar) {
+        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --polar\n");
+        return false;
+    }
+    if (c.polar && c.gpus > 1 && !c.gpus_partition) {
+        std::fprintf(stderr, "ERROR: --polar runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
+        return false;
+    }
+    return true;
 }
 
 // src/Base/io_enhanced.cpp:26-74
@@ -1574,46 +1355,7 @@ int main(int argc, char **argv)
     const double epoch_at_main = std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count();
     Config conf;
     if (!parse_arguments(argc, argv, conf)) return 1;
-    if (conf.output_loads && conf.gpus > 1 && !conf.gpus_partition) {
-        std::fprintf(stderr, "ERROR: --output-loads runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
-        return 1;
-    }
-    if (conf.smoothing_given && conf.smoothing_iterations > 0 && conf.gpus > 1 && conf.gpus_partition) {
-        std::fprintf(stderr, "ERROR: residual smoothing (--residual-smoothing) does not run with --gpus-partition: a level split over GPUs would need a halo exchange per Jacobi iteration\n");
-        return 1;
-    }
-    if (conf.jst_given && conf.jst_levels > 0 && conf.gpus > 1 && conf.gpus_partition) {
-        std::fprintf(stderr, "ERROR: the JST dissipation (--jst) does not run with --gpus-partition: a level split over GPUs would need its sensor and Laplacian exchanged per stage\n");
-        return 1;
-    }
-    if (conf.viscous() && conf.viscous_levels > 0 && conf.gpus > 1 && conf.gpus_partition) {
-        std::fprintf(stderr, "ERROR: the viscous terms (--viscosity, --reynolds) do not run with --gpus-partition: a level split over GPUs would need its node stresses exchanged per stage\n");
-        return 1;
-    }
-    if (conf.dual_given && conf.gpus > 1 && conf.gpus_partition) {
-        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --gpus-partition: levels split over GPUs are out of scope\n");
-        return 1;
-    }
-    if (conf.fas && conf.gpus > 1) {
-        std::fprintf(stderr, "ERROR: FAS multigrid (--fas) runs on one GPU only: levels split over GPUs, or one level per GPU, would need the residuals, the forcing and the corrections exchanged\n");
-        return 1;
-    }
-    if ((conf.cycle_given() || !conf.fmg_cycles.empty()) && conf.gpus > 1) {
-        std::fprintf(stderr, "ERROR: --cycle, --pre-sweeps, --post-sweeps and --fmg-cycles run on one GPU only: levels split over GPUs, or one level per GPU, run the default cycle\n");
-        return 1;
-    }
-    if (!conf.fmg_cycles.empty() && (conf.dual_given || conf.polar)) {
-        std::fprintf(stderr, "ERROR: a full-multigrid start (--fmg-cycles) does not run with --physical-time-step or --polar\n");
-        return 1;
-    }
-    if (conf.dual_given && conf.polar) {
-        std::fprintf(stderr, "ERROR: dual time stepping (--physical-time-step) does not run with --polar\n");
-        return 1;
-    }
-    if (conf.polar && conf.gpus > 1 && !conf.gpus_partition) {
-        std::fprintf(stderr, "ERROR: --polar runs on one GPU only, or on --gpus N with --gpus-partition (every level split over the ranks)\n");
-        return 1;
-    }
+    if (!check_combinations(conf)) return 1;
     if (conf.free_stream_given || conf.polar) {
         // (the arguments are checked before any file is read: the same rule as mgcfd_set_free_stream's)
         double ff17[17];
