@@ -131,6 +131,21 @@ struct HaloExchange {
     int64_t total_recv() const { return recv_off.empty() ? 0 : recv_off.back(); }
 };
 
+// The column families of the surface loads (DESIGN.md "Adding a loads column family"): the pressure six, the friction six
+// beside them, the heat rate Q and the wall area A behind the twelve.  The public calls name a kind (the partitioned form
+// sums the pressure six only); everything below them takes it.
+enum class LoadsKind { Pressure, Friction, Heat };
+constexpr int kLoadsKinds = 3, kLoadsMaxWidth = 14;
+constexpr size_t loads_width(LoadsKind kind) { constexpr size_t w[kLoadsKinds] = {6, 12, kLoadsMaxWidth}; return w[static_cast<int>(kind)]; }
+
+// Where a loads launch stores its row: a device address, or the kind's history at the row of the cycle whose RMS was
+// appended last.
+struct LoadsDest {
+    double *out = nullptr;               // nullptr: the history row
+    static LoadsDest at(double *p) { return LoadsDest{p}; }
+    static LoadsDest history() { return LoadsDest{}; }
+};
+
 // Surface loads of a level split over ranks (mgcfd_rank_set_wall_slots; INTEGRATION.md "Surface loads", the partitioned form)
 struct RankLoads {
     std::vector<int64_t> slot_host;      // position of this rank's k-th solid-wall edge in the whole level's solid-wall slice
@@ -160,11 +175,10 @@ struct WallPlan {
     WallNodes wn;
     int32_t *wall_of_rec = nullptr;      // [n_wall_rec] the wall node of every solid-wall record
     double *sw = nullptr;                // [12][wn.n] the wall nodes' stresses of the last k_wall_stress launch
-    double *partial = nullptr;           // [12][ceil(n_wall_rec / 256)]
+    double *partial = nullptr;           // [14][ceil(n_wall_rec / 256)]: the widest kind's sums, a narrower kind uses the front
     unsigned *ticket = nullptr;
     double *dist = nullptr;              // [wn.n][MGCFD_WALL_COLUMNS] the distribution's result
-    // the heat loads (mgcfd_surface_loads_heat, mgcfd_wall_heat), made by the first such call for the level
-    double *partial14 = nullptr;         // [14][ceil(n_wall_rec / 256)]
+    // the heat table (mgcfd_wall_heat), made by the first such call for the level
     double *heat = nullptr;              // [wn.n][MGCFD_WALL_HEAT_COLUMNS] the heat table's result
 };
 
@@ -351,15 +365,15 @@ struct mgcfd_solver {
     static constexpr int kRmsRing = 4096;
     double *rms_ring = nullptr;                    // level-0 sum of squares of the cycles run since the last read-back
     int *rms_count = nullptr;
-    // surface loads: a [kRmsRing][6] history filled beside rms_ring (row = the cycle's RMS slot), the reference point and
-    // a synchronous call's result on the device; the cycle appends to the history while loads_in_cycle is set
-    double *loads_ring = nullptr, *loads_dev = nullptr;                       // loads_dev: ref [3] | out [12]
-    double *loads_ring12 = nullptr;                                           // [kRmsRing][12]: pressure and friction (mgcfd_run_cycles_loads_viscous)
+    // surface loads: per kind a [kRmsRing][loads_width(kind)] history filled beside rms_ring (row = the cycle's RMS slot;
+    // made by ensure_loads_ring, so a call of one kind never reads rows another kind wrote), the reference point and a
+    // synchronous call's result on the device; the cycle appends rows of loads_kind to that kind's history while
+    // loads_in_cycle is set
+    double *loads_ring[kLoadsKinds] = {nullptr, nullptr, nullptr};
+    double *loads_dev = nullptr;                                              // ref [3] | out [kLoadsMaxWidth]
     double loads_ref_host[3] = {0.0, 0.0, 0.0};
     bool loads_in_cycle = false;
-    bool loads_friction = false;                   // ... as twelve-wide rows, the friction six beside the pressure six
-    bool loads_heat = false;                       // ... as fourteen-wide rows, Q and A behind them (mgcfd_run_cycles_loads_heat)
-    double *loads_ring14 = nullptr, *loads_dev14 = nullptr;                   // [kRmsRing][14]; a synchronous call's out [14]
+    LoadsKind loads_kind = LoadsKind::Pressure;
     bool partitioned = false;                      // made by mgcfd_create_partitioned* (loads: the group and rank forms, over all ranks)
     double p_inf = 0.0;                            // far-field pressure, derive()'s expression on ff_variable
     double fs_mach = kDefaultMach, fs_alpha_deg = kDefaultAlphaDeg;      // what ff17 was computed from (mgcfd_set_free_stream)
@@ -2914,16 +2928,11 @@ int mgcfd_smooth(mgcfd_solver *s, int level, int sweeps)
 }
 
 // ---- surface loads (no reference counterpart: the sum of compute_boundary_flux_edge's momentum term) ----
-// Level `lv`'s loads of its current `variables`, into the synchronous result (loads_dev + 3) or into the history row of
-// the cycle whose RMS was appended last.  Always the non-contracting kernel, whatever MGCFD_OPT_EXACT says.
-static void launch_loads(mgcfd_solver *s, DeviceLevel &lv, bool to_ring)
+// The destination's fields of a task that sums rows of `kind` on solver s.
+static void loads_store_to(mgcfd_solver *s, LoadsKind kind, LoadsDest to, LoadsTask &t)
 {
-    LoadsTask t;
-    t.rec = lv.wall_rec; t.n = lv.n_wall_rec; t.p_inf = s->p_inf; t.ref = s->loads_dev;
-    t.partial = lv.loads_partial; t.ticket = lv.loads_ticket;
-    if (to_ring) { t.ring = s->loads_ring; t.count = s->rms_count; t.cap = mgcfd_solver::kRmsRing; }
-    else t.out = s->loads_dev + 3;
-    launch_surface_loads(s->stream, lv.dp.stride, lv.q, t);
+    if (to.out) { t.out = to.out; return; }
+    t.ring = s->loads_ring[static_cast<int>(kind)]; t.count = s->rms_count; t.cap = mgcfd_solver::kRmsRing;
 }
 
 // The wall plan of a level (allocations and uploads: never inside a capture or a cycle).
@@ -2942,7 +2951,7 @@ static WallPlan &wall_plan(mgcfd_solver *s, DeviceLevel &lv)
     wp->wn.wall_edge = wp->mem.upload(R.wall_edge);
     wp->wall_of_rec = wp->mem.upload(R.wall_of_rec);
     wp->sw = wp->mem.alloc<double>(12 * R.node.size());
-    wp->partial = wp->mem.alloc<double>(12 * static_cast<size_t>((lv.n_wall_rec + 255) / 256));
+    wp->partial = wp->mem.alloc<double>(kLoadsMaxWidth * static_cast<size_t>((lv.n_wall_rec + 255) / 256));
     wp->ticket = wp->mem.upload(std::vector<unsigned>(1, 0u));
     wp->dist = wp->mem.alloc<double>(MGCFD_WALL_COLUMNS * R.node.size());
     lv.wp = std::move(wp);
@@ -2960,32 +2969,36 @@ static void launch_wall_stress(mgcfd_solver *s, int l)
     launch_wall_stress(s->stream, lv.dp.stride, lv.q, a);
 }
 
-// Level l's pressure and friction loads of its current `variables` (the level has a plan), as launch_loads: twelve sums
-// into `out` (device) or, out == nullptr, into the twelve-wide history's row of the cycle whose RMS was appended last.  The
-// stress launch runs where the viscous terms are on for the level.
-// heat (mgcfd_surface_loads_heat): fourteen sums, Q and A behind the twelve, into `out` or the fourteen-wide history
-static void launch_loads_twelve(mgcfd_solver *s, int l, double *out, bool heat = false)
+// Level l's loads of `kind` of its current `variables`, stored at `to`.  Always the non-contracting kernels, whatever
+// MGCFD_OPT_EXACT says.  The pressure six sum over the level's own partial sums; the wider kinds need the level's wall plan
+// (loads_plan) and run the stress launch first where the viscous terms are on for the level (stress = false: the loads
+// launch alone, for the diagnostics that time it).
+static void launch_loads(mgcfd_solver *s, int l, LoadsKind kind, LoadsDest to, bool stress = true)
 {
     DeviceLevel &lv = s->level(l);
-    const bool viscous = s->viscous_on(l);
     LoadsTaskViscous t;
     t.base.rec = lv.wall_rec; t.base.n = lv.n_wall_rec; t.base.p_inf = s->p_inf; t.base.ref = s->loads_dev;
-    t.base.partial = heat ? lv.wp->partial14 : lv.wp->partial; t.base.ticket = lv.wp->ticket;
-    if (!out) { t.base.ring = heat ? s->loads_ring14 : s->loads_ring12; t.base.count = s->rms_count; t.base.cap = mgcfd_solver::kRmsRing; }
-    else t.base.out = out;
+    loads_store_to(s, kind, to, t.base);
+    if (kind == LoadsKind::Pressure) {
+        t.base.partial = lv.loads_partial; t.base.ticket = lv.loads_ticket;
+        launch_surface_loads(s->stream, lv.dp.stride, lv.q, t.base);
+        return;
+    }
+    const bool viscous = s->viscous_on(l);
+    if (viscous && stress) launch_wall_stress(s, l);
+    t.base.partial = lv.wp->partial; t.base.ticket = lv.wp->ticket;
     t.wall_of_rec = lv.wp->wall_of_rec; t.sw = viscous ? lv.wp->sw : nullptr; t.nw = lv.wp->wn.n;
-    launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t, heat ? 14 : 12);
+    launch_surface_loads_viscous(s->stream, lv.dp.stride, lv.q, t, static_cast<int>(loads_width(kind)));
 }
-static void launch_loads_viscous(mgcfd_solver *s, int l, double *out, bool heat = false)
+// What a level keeps for the launches of `kind` (allocations and uploads: never inside a capture or a cycle).
+static void loads_plan(mgcfd_solver *s, DeviceLevel &lv, LoadsKind kind)
 {
-    if (s->viscous_on(l)) launch_wall_stress(s, l);
-    launch_loads_twelve(s, l, out, heat);
+    if (kind != LoadsKind::Pressure) wall_plan(s, lv);
 }
-// The wall plan with what the heat loads add to it (allocations: never inside a capture or a cycle).
+// The wall plan with the heat table (allocations: never inside a capture or a cycle).
 static WallPlan &wall_plan_heat(mgcfd_solver *s, DeviceLevel &lv)
 {
     WallPlan &wp = wall_plan(s, lv);
-    if (!wp.partial14) wp.partial14 = wp.mem.alloc<double>(14 * static_cast<size_t>((lv.n_wall_rec + 255) / 256));
     if (!wp.heat) wp.heat = wp.mem.alloc<double>(MGCFD_WALL_HEAT_COLUMNS * static_cast<size_t>(wp.wn.n));
     return wp;
 }
@@ -3004,17 +3017,10 @@ static void ensure_rms_ring(mgcfd_solver *s)
     s->rms_ring = s->mem.alloc<double>(mgcfd_solver::kRmsRing);
     s->rms_count = s->mem.alloc<int>(1);
 }
-static void ensure_loads_ring(mgcfd_solver *s)
+static void ensure_loads_ring(mgcfd_solver *s, LoadsKind kind)
 {
-    if (!s->loads_ring) s->loads_ring = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 6);
-}
-static void ensure_loads_ring12(mgcfd_solver *s)
-{
-    if (!s->loads_ring12) s->loads_ring12 = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 12);
-}
-static void ensure_loads_ring14(mgcfd_solver *s)
-{
-    if (!s->loads_ring14) s->loads_ring14 = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * 14);
+    double *&ring = s->loads_ring[static_cast<int>(kind)];
+    if (!ring) ring = s->mem.alloc<double>(static_cast<size_t>(mgcfd_solver::kRmsRing) * loads_width(kind));
 }
 
 static void loads_prepare(mgcfd_solver *s, const double *ref_point)
@@ -3025,9 +3031,37 @@ static void loads_prepare(mgcfd_solver *s, const double *ref_point)
 
 static void loads_upload_ref(mgcfd_solver *s, const double *ref_point)
 {
-    if (!s->loads_dev) s->loads_dev = s->mem.alloc<double>(15);
+    if (!s->loads_dev) s->loads_dev = s->mem.alloc<double>(3 + kLoadsMaxWidth);
     for (int k = 0; k < 3; k++) s->loads_ref_host[k] = ref_point ? ref_point[k] : 0.0;
     HIP_CHECK(hipMemcpyAsync(s->loads_dev, s->loads_ref_host, sizeof(double) * 3, hipMemcpyHostToDevice, s->stream));
+}
+
+// The tail of every synchronous loads call: `launch(to)` stores the row of `kind` at `to` on s's stream (whatever it takes:
+// the single solver launches, a group waits for its ranks' terms and reduces, a rank reduces and shares), then the row to
+// the caller.  wall = false, the level has no solid wall: exact zeros, nothing launched.
+static void loads_now(mgcfd_solver *s, LoadsKind kind, bool wall, double *out, const std::function<void(LoadsDest)> &launch)
+{
+    double got[kLoadsMaxWidth] = {};
+    const size_t bytes = sizeof(double) * loads_width(kind);
+    if (wall) {
+        launch(LoadsDest::at(s->loads_dev + 3));
+        HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, bytes, hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        HIP_CHECK(hipGetLastError());
+    }
+    std::memcpy(out, got, bytes);
+}
+
+// The read-back of every loads history, [..][loads_width(kind)] at `out`: rows [first, first + n) from the first n rows of
+// s's history of `kind` on s's stream (the caller synchronises before it reads them; wall = false: exact zeros, nothing
+// was launched), rows [first + n, end) NaN: what did not complete.
+static void loads_rows(mgcfd_solver *s, LoadsKind kind, bool wall, double *out, size_t first, size_t n, size_t end)
+{
+    const size_t width = loads_width(kind);
+    if (n > 0 && wall)
+        HIP_CHECK(hipMemcpyAsync(out + first * width, s->loads_ring[static_cast<int>(kind)], sizeof(double) * width * n, hipMemcpyDeviceToHost, s->stream));
+    else std::fill(out + first * width, out + (first + n) * width, 0.0);
+    if (end > first + n) std::fill(out + (first + n) * width, out + end * width, std::numeric_limits<double>::quiet_NaN());
 }
 
 // ---- cycle driver: src/euler3d_cpu_double.cpp:371-694 ----
@@ -3103,30 +3137,26 @@ static void cycle_once(mgcfd_solver *s, bool capturing)
     };
     visit(top, s->cycle_shape);
     // (the state the cycle leaves: after the last prolongation and level 0's post-sweeps)
-    if (s->loads_in_cycle) { if (s->loads_friction) launch_loads_viscous(s, 0, nullptr, s->loads_heat); else launch_loads(s, s->L[0], true); }
+    if (s->loads_in_cycle) launch_loads(s, 0, s->loads_kind, LoadsDest::history());
 }
 
-// loads_out != nullptr (mgcfd_run_cycles_loads): also the level-0 surface loads at the end of every cycle, [cycles][6];
-// friction (mgcfd_run_cycles_loads_viscous): rows of twelve, the friction six beside the pressure six, launched directly;
-// heat (with friction: mgcfd_run_cycles_loads_heat): rows of fourteen, Q and A behind the twelve
-static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out, bool friction = false, bool heat = false)
+// loads_out != nullptr (mgcfd_run_cycles_loads*): also the level-0 surface loads of `kind` at the end of every cycle,
+// [cycles][loads_width(kind)]; the kinds wider than the pressure six are launched directly (no cycle graph)
+static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const double *ref_point, double *loads_out, LoadsKind kind = LoadsKind::Pressure)
 {
-    const size_t width = heat ? 14 : (friction ? 12 : 6);
     REQUIRE(s);
     int code = MGCFD_OK, failed_cycle = -1, seq_before = 0, seq_per_cycle = 0;
-    std::vector<double> loads;
+    const bool friction = loads_out && kind != LoadsKind::Pressure;
     int rc = guarded([&] {
         s->use_device();
         ensure_rms_ring(s);
-        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = s->loads_friction = s->loads_heat = false; } } loads_off{s};
+        struct LoadsOff { mgcfd_solver *s; ~LoadsOff() { s->loads_in_cycle = false; s->loads_kind = LoadsKind::Pressure; } } loads_off{s};
         if (loads_out) {
             loads_prepare(s, ref_point);
-            if (heat) ensure_loads_ring14(s); else if (friction) ensure_loads_ring12(s); else ensure_loads_ring(s);
+            ensure_loads_ring(s, kind);
             s->loads_in_cycle = s->L[0].n_wall_rec > 0;        // (no solid wall: zeros, nothing launched)
-            s->loads_friction = friction;
-            s->loads_heat = heat;
-            if (friction && s->loads_in_cycle) { if (heat) wall_plan_heat(s, s->L[0]); else wall_plan(s, s->L[0]); }
-            loads.reserve(static_cast<size_t>(cycles > 0 ? cycles : 0) * width);
+            s->loads_kind = kind;
+            if (s->loads_in_cycle) loads_plan(s, s->L[0], kind);
         }
         const size_t nl = s->L.size();
         std::vector<double> sums;
@@ -3212,12 +3242,7 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
             const size_t at = sums.size();
             sums.resize(at + static_cast<size_t>(chunk));
             HIP_CHECK(hipMemcpyAsync(sums.data() + at, s->rms_ring, sizeof(double) * chunk, hipMemcpyDeviceToHost, s->stream));
-            if (loads_out) {
-                loads.resize((at + static_cast<size_t>(chunk)) * width, 0.0);
-                if (s->loads_in_cycle)
-                    HIP_CHECK(hipMemcpyAsync(loads.data() + at * width, heat ? s->loads_ring14 : (friction ? s->loads_ring12 : s->loads_ring), sizeof(double) * width * chunk,
-                                             hipMemcpyDeviceToHost, s->stream));
-            }
+            if (loads_out) loads_rows(s, kind, s->loads_in_cycle, loads_out, at, static_cast<size_t>(chunk), at + static_cast<size_t>(chunk));
             int seq = 0;
             code = s->read_error(nullptr, &seq);                           // synchronises
             if (att1) {
@@ -3243,12 +3268,10 @@ static int run_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const d
                 rms_out[c] = (c < static_cast<int>(sums.size()) && (failed_cycle < 0 || c < failed_cycle))
                                  ? std::sqrt(sums[static_cast<size_t>(c)] / double(s->L[static_cast<size_t>(s->cycle_top)].n_owned)) : nan;
         }
-        if (loads_out) {
-            const double nan = std::numeric_limits<double>::quiet_NaN();
-            for (int c = 0; c < cycles; c++) {
-                const bool ok = c < static_cast<int>(sums.size()) && (failed_cycle < 0 || c < failed_cycle);
-                for (size_t k = 0; k < width; k++) loads_out[static_cast<size_t>(c) * width + k] = ok ? loads[static_cast<size_t>(c) * width + k] : nan;
-            }
+        if (loads_out && cycles > 0) {
+            // NaN from the failing cycle on (the rows read back before it stay)
+            const size_t valid = failed_cycle < 0 ? sums.size() : std::min(sums.size(), static_cast<size_t>(failed_cycle));
+            loads_rows(s, kind, s->loads_in_cycle, loads_out, valid, 0, static_cast<size_t>(cycles));
         }
         HIP_CHECK(hipGetLastError());
     });
@@ -5291,13 +5314,12 @@ static LoadsTerms loads_terms_of(mgcfd_solver *s, DeviceLevel &lv, const int32_t
     return t;
 }
 
-// rank 0's reduce of its table on its stream: into the synchronous result (loads_dev + 3) or the history row of the cycle
-static void loads_reduce(mgcfd_solver *s0, RankLoads &r0, bool to_ring)
+// rank 0's reduce of its table on its stream, stored at `to` (the terms tables hold the pressure six)
+static void loads_reduce(mgcfd_solver *s0, RankLoads &r0, LoadsDest to)
 {
     LoadsTask t;
     t.n = r0.total; t.partial = r0.partial; t.ticket = r0.ticket;
-    if (to_ring) { t.ring = s0->loads_ring; t.count = s0->rms_count; t.cap = mgcfd_solver::kRmsRing; }
-    else t.out = s0->loads_dev + 3;
+    loads_store_to(s0, LoadsKind::Pressure, to, t);
     launch_loads_reduce(s0->stream, r0.table, r0.row, t);
 }
 
@@ -5355,21 +5377,21 @@ static void group_loads_terms(mgcfd_group *g, mgcfd_solver *s, int level)
 }
 
 // ... and rank 0's (on its device, every rank's terms event of this evaluation recorded): the reduce behind all of them
-static void group_loads_reduce(mgcfd_group *g, int level, bool to_ring)
+static void group_loads_reduce(mgcfd_group *g, int level, LoadsDest to)
 {
     mgcfd_solver *s0 = g->ranks[0];
     RankLoads &r0 = *s0->level(level).rl;
     if (r0.total == 0) return;
     for (mgcfd_solver *s : g->ranks) if (s != s0) HIP_CHECK(hipStreamWaitEvent(s0->stream, s->level(level).rl->terms.get(), 0));
-    loads_reduce(s0, r0, to_ring);
+    loads_reduce(s0, r0, to);
     HIP_CHECK(hipEventRecord(r0.read.get(), s0->stream));
 }
 
-static void group_loads_once(mgcfd_group *g, int level, bool to_ring)
+static void group_loads_once(mgcfd_group *g, int level, LoadsDest to)
 {
     for (mgcfd_solver *s : g->ranks) { s->use_device(); group_loads_terms(g, s, level); }
     g->ranks[0]->use_device();
-    group_loads_reduce(g, level, to_ring);
+    group_loads_reduce(g, level, to);
 }
 
 static void append_level0_sumsq(mgcfd_solver *s)
@@ -5402,7 +5424,7 @@ static void group_cycle_once(mgcfd_group *g, bool with_rms, bool with_loads)
         group_exchange_array(g, l, MGCFD_ARR_VARIABLES);
         if (l > 0) group_sweep_once(g, l);
     }
-    if (with_loads) group_loads_once(g, 0, true);
+    if (with_loads) group_loads_once(g, 0, LoadsDest::history());
 }
 
 // The same cycle with a host thread per rank (direct mode; what mgcfd_group_cycles runs for groups of several ranks:
@@ -5492,7 +5514,7 @@ static void group_cycles_threaded(mgcfd_group *g, int cycles, bool with_rms, boo
                 step([&] { group_loads_terms(g, s, 0); });
                 bar.wait();                             // every rank's terms event is recorded
                 // (rank 0's record of `read` lies ahead of the barriers of the next cycle's first sweep, the other ranks' waits for it behind them)
-                if (r == 0) step([&] { group_loads_reduce(g, 0, true); });
+                if (r == 0) step([&] { group_loads_reduce(g, 0, LoadsDest::history()); });
             }
         }
         step([&] { for (int l = 0; l < nl; l++) wait_for_peers(g, s, l, 2); HIP_CHECK(hipGetLastError()); });
@@ -5521,7 +5543,8 @@ static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const 
 {
     REQUIRE(g);
     int code = MGCFD_OK;
-    if (loads_out) std::fill(loads_out, loads_out + static_cast<size_t>(std::max(cycles, 0)) * 6, std::numeric_limits<double>::quiet_NaN());
+    const LoadsKind kind = LoadsKind::Pressure;                 // (what the terms tables hold)
+    if (loads_out) loads_rows(nullptr, kind, false, loads_out, 0, 0, static_cast<size_t>(std::max(cycles, 0)));    // NaN until the run is through
     const bool with_rms = rms_out || loads_out;                 // (a cycle's loads go into the row of its RMS)
     const int rc = guarded([&] {
         if (cycles > mgcfd_solver::kRmsRing) throw std::invalid_argument("at most 4096 cycles per call");
@@ -5534,7 +5557,7 @@ static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const 
             group_loads_prepare(g, 0, ref_point);
             mgcfd_solver *s0 = g->ranks[0];
             s0->use_device();
-            ensure_loads_ring(s0);
+            ensure_loads_ring(s0, kind);
         }
         const bool with_loads = loads_out != nullptr;
         for (mgcfd_solver *s : g->ranks) {
@@ -5573,13 +5596,9 @@ static int group_cycles_impl(mgcfd_group *g, int cycles, double *rms_out, const 
         }
         if (loads_out && cycles > 0) {
             mgcfd_solver *s0 = g->ranks[0];
-            std::vector<double> rows(static_cast<size_t>(cycles) * 6, 0.0);     // (no solid wall: zeros, nothing was launched)
-            if (s0->level(0).rl->total > 0) {
-                s0->use_device();
-                HIP_CHECK(hipMemcpyAsync(rows.data(), s0->loads_ring, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, s0->stream));
-                HIP_CHECK(hipStreamSynchronize(s0->stream));
-            }
-            std::copy(rows.begin(), rows.end(), loads_out);
+            s0->use_device();
+            loads_rows(s0, kind, s0->level(0).rl->total > 0, loads_out, 0, static_cast<size_t>(cycles), static_cast<size_t>(cycles));
+            HIP_CHECK(hipStreamSynchronize(s0->stream));
         }
         code = group_read_errors(g);
         for (mgcfd_solver *s : g->ranks) { s->use_device(); HIP_CHECK(hipGetLastError()); }
@@ -5604,14 +5623,7 @@ int mgcfd_group_surface_loads(mgcfd_group *g, int level, const double ref_point[
         group_require_same_time_step(g);
         group_loads_prepare(g, level, ref_point);
         mgcfd_solver *s0 = g->ranks[0];
-        double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (s0->level(level).rl->total > 0) {                 // (no solid wall: exact zeros, nothing launched)
-            group_loads_once(g, level, false);
-            HIP_CHECK(hipMemcpyAsync(got, s0->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s0->stream));
-            HIP_CHECK(hipStreamSynchronize(s0->stream));
-            HIP_CHECK(hipGetLastError());
-        }
-        std::memcpy(out6, got, sizeof(got));
+        loads_now(s0, LoadsKind::Pressure, s0->level(level).rl->total > 0, out6, [&](LoadsDest to) { group_loads_once(g, level, to); });
     });
 }
 
@@ -5704,7 +5716,7 @@ static void rank_loads_prepare(mgcfd_solver *s, int level, const double *ref_poi
 }
 
 // one evaluation on this rank's stream: the other ranks send their compact terms, rank 0 places them by slot and reduces
-static void rank_loads_once(mgcfd_solver *s, int level, bool to_ring)
+static void rank_loads_once(mgcfd_solver *s, int level, LoadsDest to)
 {
     mgcfd_comm &c = comm_of(s);
     DeviceLevel &lv = s->level(level);
@@ -5734,7 +5746,7 @@ static void rank_loads_once(mgcfd_solver *s, int level, bool to_ring)
             off += rl.counts[r];
         }
     }
-    loads_reduce(s, rl, to_ring);
+    loads_reduce(s, rl, to);
 }
 
 // rank 0's `n` results at `buf` to the same place on every other rank
@@ -5762,7 +5774,7 @@ static void rank_cycle_once(mgcfd_solver *s, bool with_rms, bool with_loads)
         rank_exchange_array(s, l, MGCFD_ARR_VARIABLES);
         if (l > 0) rank_sweep_once(s, l);
     }
-    if (with_loads) rank_loads_once(s, 0, true);
+    if (with_loads) rank_loads_once(s, 0, LoadsDest::history());
 }
 
 // loads_out != nullptr (mgcfd_rank_cycles_loads): also the level-0 surface loads of the state every cycle leaves, [cycles][6]
@@ -5770,7 +5782,8 @@ static int rank_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const 
 {
     REQUIRE(s);
     int code = MGCFD_OK;
-    if (loads_out) std::fill(loads_out, loads_out + static_cast<size_t>(std::max(cycles, 0)) * 6, std::numeric_limits<double>::quiet_NaN());
+    const LoadsKind kind = LoadsKind::Pressure;                 // (what the terms tables hold)
+    if (loads_out) loads_rows(nullptr, kind, false, loads_out, 0, 0, static_cast<size_t>(std::max(cycles, 0)));    // NaN until the run is through
     const bool with_rms = rms_out || loads_out;                 // (a cycle's loads go into the row of its RMS)
     const int rc = guarded([&] {
         s->use_device();
@@ -5786,17 +5799,14 @@ static int rank_cycles_impl(mgcfd_solver *s, int cycles, double *rms_out, const 
         HIP_CHECK(hipMemsetAsync(s->rms_count, 0, sizeof(int), s->stream));
         if (loads_out) {
             rank_loads_prepare(s, 0, ref_point);
-            ensure_loads_ring(s);
+            ensure_loads_ring(s, kind);
         }
         for (int k = 0; k < cycles; k++) rank_cycle_once(s, with_rms, loads_out != nullptr);
         if (loads_out && cycles > 0) {
-            std::vector<double> rows(static_cast<size_t>(cycles) * 6, 0.0);     // (no solid wall: zeros, nothing was launched)
-            if (s->level(0).rl->total > 0) {
-                rank_loads_share(s, s->loads_ring, rows.size());
-                HIP_CHECK(hipMemcpyAsync(rows.data(), s->loads_ring, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, s->stream));
-                HIP_CHECK(hipStreamSynchronize(s->stream));
-            }
-            std::copy(rows.begin(), rows.end(), loads_out);
+            const bool wall = s->level(0).rl->total > 0;
+            if (wall) rank_loads_share(s, s->loads_ring[static_cast<int>(kind)], static_cast<size_t>(cycles) * loads_width(kind));
+            loads_rows(s, kind, wall, loads_out, 0, static_cast<size_t>(cycles), static_cast<size_t>(cycles));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
         }
         if (rms_out && cycles > 0) {
             // calc_rms of the whole level (validation.cpp:91-105): the ranks' sums of every cycle added by ONE all-reduce
@@ -5833,15 +5843,10 @@ int mgcfd_rank_surface_loads(mgcfd_solver *s, int level, const double ref_point[
     return guarded([&] {
         s->use_device();
         rank_loads_prepare(s, level, ref_point);
-        double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (s->level(level).rl->total > 0) {                  // (no solid wall: exact zeros, nothing launched or sent)
-            rank_loads_once(s, level, false);
-            rank_loads_share(s, s->loads_dev + 3, 6);
-            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s->stream));
-            HIP_CHECK(hipStreamSynchronize(s->stream));
-            HIP_CHECK(hipGetLastError());
-        }
-        std::memcpy(out6, got, sizeof(got));
+        loads_now(s, LoadsKind::Pressure, s->level(level).rl->total > 0, out6, [&](LoadsDest to) {      // (no solid wall: nothing sent either)
+            rank_loads_once(s, level, to);
+            rank_loads_share(s, to.out, loads_width(LoadsKind::Pressure));
+        });
     });
 }
 
@@ -5940,24 +5945,23 @@ static void wall_table(mgcfd_solver *s, int level, int64_t *node_ids, double *ou
     HIP_CHECK(hipGetLastError());
 }
 
+// mgcfd_surface_loads*: level `level`'s loads of `kind` in its current state, synchronously
+static int surface_loads_impl(mgcfd_solver *s, int level, const double *ref_point, double *out, LoadsKind kind)
+{
+    return guarded([&] {
+        s->use_device();
+        DeviceLevel &lv = s->level(level);
+        loads_prepare(s, ref_point);
+        loads_now(s, kind, lv.n_wall_rec > 0, out, [&](LoadsDest to) { loads_plan(s, lv, kind); launch_loads(s, level, kind, to); });
+    });
+}
+
 extern "C" {
 
 int mgcfd_surface_loads(mgcfd_solver *s, int level, const double ref_point[3], double out6[6])
 {
     REQUIRE(s); REQUIRE(out6);
-    return guarded([&] {
-        s->use_device();
-        DeviceLevel &lv = s->level(level);
-        loads_prepare(s, ref_point);
-        double got[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (lv.n_wall_rec > 0) {                          // (no solid wall: exact zeros, nothing launched)
-            launch_loads(s, lv, false);
-            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s->stream));
-            HIP_CHECK(hipStreamSynchronize(s->stream));
-            HIP_CHECK(hipGetLastError());
-        }
-        std::memcpy(out6, got, sizeof(got));
-    });
+    return surface_loads_impl(s, level, ref_point, out6, LoadsKind::Pressure);
 }
 
 int mgcfd_run_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
@@ -5970,26 +5974,13 @@ int mgcfd_run_cycles_loads(mgcfd_solver *s, int cycles, const double ref_point[3
 int mgcfd_surface_loads_viscous(mgcfd_solver *s, int level, const double ref_point[3], double out12[12])
 {
     REQUIRE(s); REQUIRE(out12);
-    return guarded([&] {
-        s->use_device();
-        DeviceLevel &lv = s->level(level);
-        loads_prepare(s, ref_point);
-        double got[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (lv.n_wall_rec > 0) {                          // (no solid wall: exact zeros, nothing launched)
-            wall_plan(s, lv);
-            launch_loads_viscous(s, level, s->loads_dev + 3);
-            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev + 3, sizeof(got), hipMemcpyDeviceToHost, s->stream));
-            HIP_CHECK(hipStreamSynchronize(s->stream));
-            HIP_CHECK(hipGetLastError());
-        }
-        std::memcpy(out12, got, sizeof(got));
-    });
+    return surface_loads_impl(s, level, ref_point, out12, LoadsKind::Friction);
 }
 
 int mgcfd_run_cycles_loads_viscous(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
 {
     REQUIRE(s); REQUIRE(loads_out);
-    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out, true);
+    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out, LoadsKind::Friction);
 }
 
 int mgcfd_wall_node_count(mgcfd_solver *s, int level, int64_t *n)
@@ -6044,12 +6035,13 @@ int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launche
         if (kind < 0 || kind > 2) throw std::invalid_argument("friction loads launch kind: 0 wall stress, 1 pressure and friction loads, 2 pressure loads");
         if (lv.n_wall_rec == 0) throw std::invalid_argument("the level has no solid-wall edge");
         loads_prepare(s, nullptr);
-        wall_plan(s, lv);
-        launch_loads_viscous(s, level, s->loads_dev + 3);
+        loads_plan(s, lv, LoadsKind::Friction);
+        const LoadsDest to = LoadsDest::at(s->loads_dev + 3);
+        launch_loads(s, level, LoadsKind::Friction, to);
         *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) launch_wall_stress(s, level);
-            else if (kind == 1) launch_loads_twelve(s, level, s->loads_dev + 3);
-            else launch_loads(s, lv, false);
+            else if (kind == 1) launch_loads(s, level, LoadsKind::Friction, to, false);
+            else launch_loads(s, level, LoadsKind::Pressure, to);
         });
     });
 }
@@ -6058,27 +6050,13 @@ int mgcfd_bench_friction_loads(mgcfd_solver *s, int level, int kind, int launche
 int mgcfd_surface_loads_heat(mgcfd_solver *s, int level, const double ref_point[3], double out14[14])
 {
     REQUIRE(s); REQUIRE(out14);
-    return guarded([&] {
-        s->use_device();
-        DeviceLevel &lv = s->level(level);
-        loads_prepare(s, ref_point);
-        double got[14] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (lv.n_wall_rec > 0) {                          // (no solid wall: exact zeros, nothing launched)
-            wall_plan_heat(s, lv);
-            if (!s->loads_dev14) s->loads_dev14 = s->mem.alloc<double>(14);
-            launch_loads_viscous(s, level, s->loads_dev14, true);
-            HIP_CHECK(hipMemcpyAsync(got, s->loads_dev14, sizeof(got), hipMemcpyDeviceToHost, s->stream));
-            HIP_CHECK(hipStreamSynchronize(s->stream));
-            HIP_CHECK(hipGetLastError());
-        }
-        std::memcpy(out14, got, sizeof(got));
-    });
+    return surface_loads_impl(s, level, ref_point, out14, LoadsKind::Heat);
 }
 
 int mgcfd_run_cycles_loads_heat(mgcfd_solver *s, int cycles, const double ref_point[3], double *rms_out, double *loads_out)
 {
     REQUIRE(s); REQUIRE(loads_out);
-    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out, true, true);
+    return run_cycles_impl(s, cycles, rms_out, ref_point, loads_out, LoadsKind::Heat);
 }
 
 int mgcfd_wall_heat(mgcfd_solver *s, int level, int64_t *node_ids, double *out)
@@ -6113,7 +6091,7 @@ int mgcfd_bench_wall_heat(mgcfd_solver *s, int level, int kind, int launches, do
         require_no_sweep_under_way(s, "wall heat");
         loads_upload_ref(s, nullptr);
         WallPlan &wp = wall_plan_heat(s, lv);
-        if (!s->loads_dev14) s->loads_dev14 = s->mem.alloc<double>(14);
+        const LoadsDest to = LoadsDest::at(s->loads_dev + 3);
         const double ew = s->wt_mode == MGCFD_WALL_ISOTHERMAL ? s->wt_ew : 1.0 / (1.4 - 1.0);
         const double qw = s->wt_mode == MGCFD_WALL_HEAT_FLUX ? s->wt_value : 1.0;
         DeviceOwner local;
@@ -6124,14 +6102,14 @@ int mgcfd_bench_wall_heat(mgcfd_solver *s, int level, int kind, int launches, do
             area = local.upload(wall_areas(lv.info, lv.edges, lv.plan.new_of_old, nodes));
         }
         if (kind == 2) s->settle_fluxes(lv);
-        launch_loads_viscous(s, level, s->loads_dev14, true);
+        launch_loads(s, level, LoadsKind::Heat, to);
         WallDistribution a;
         a.wn = wp.wn; a.rec = lv.wall_rec; a.p_inf = s->p_inf; a.sw = wp.sw; a.out = wp.heat;
         *avg_seconds = s->timed_launches(launches, [&] {
             if (kind == 0) launch_viscous_wall_isothermal(s->stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, ew, lv.q_alt, nullptr, nullptr, nullptr);
             else if (kind == 1) launch_viscous_wall(s->stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, lv.q_alt, nullptr, nullptr, nullptr);
             else if (kind == 2) launch_wall_heat_flux(s->stream, lv.n_visc_wall, lv.dp.stride, lv.visc_wall, area, qw, lv.fluxes);
-            else if (kind == 3) launch_loads_twelve(s, level, s->loads_dev14, true);
+            else if (kind == 3) launch_loads(s, level, LoadsKind::Heat, to, false);
             else launch_wall_heat(s->stream, lv.dp.stride, lv.q, a);
         });
         if (kind == 2) { lv.fluxes_zero = false; lv.fluxes_stale = false; }
@@ -6634,20 +6612,19 @@ int mgcfd_bench_statistics(mgcfd_solver *s, int kind, int launches, double *avg_
         });
     });
 }
-// friction (mgcfd_advance_loads_viscous): rows of twelve, every step's launches store into a row of the twelve-wide history on
-// the device and the rows are read back when it is full and at the end
-// heat (with friction: mgcfd_advance_loads_heat): rows of fourteen in the fourteen-wide history
-static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double *ref_point, bool friction,
-                        bool heat = false)
+// loads_out != nullptr: also the level-0 loads of `kind` of the state every physical step leaves, [steps][loads_width(kind)].
+// Every step's launches store into the next row of the kind's history on the device; the rows held there are read back when it
+// is full and at the end.
+static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double *ref_point, LoadsKind kind)
 {
     REQUIRE(s);
-    const size_t width = heat ? 14 : (friction ? 12 : 6);
+    const size_t width = loads_width(kind);
+    bool wall = false;                          // the loads are asked for and level 0 has a solid wall
     int held = 0;                               // history rows not yet read back, the last of them row `step`
     auto read_rows = [&](int step) {
         if (held == 0) return int(MGCFD_OK);
         return guarded([&] {
-            HIP_CHECK(hipMemcpyAsync(loads_out + size_t(step + 1 - held) * width, heat ? s->loads_ring14 : s->loads_ring12, sizeof(double) * width * size_t(held),
-                                     hipMemcpyDeviceToHost, s->stream));
+            loads_rows(s, kind, true, loads_out, size_t(step + 1 - held), size_t(held), size_t(step + 1));
             HIP_CHECK(hipStreamSynchronize(s->stream));
             held = 0;
         });
@@ -6657,13 +6634,14 @@ static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double 
         if (steps < 0 || cycles_per_step < 1) throw std::invalid_argument("mgcfd_advance (dual time): steps >= 0 and cycles_per_step >= 1");
         if (int64_t(steps) * cycles_per_step > MGCFD_MAX_ADVANCE_CYCLES)
             throw std::invalid_argument("mgcfd_advance (dual time): at most " + std::to_string(MGCFD_MAX_ADVANCE_CYCLES) + " cycles per call (steps * cycles_per_step)");
-        if (loads_out) loads_require_whole(s);
-        if (loads_out && friction) {
+        if (loads_out) {
+            loads_require_whole(s);
             s->use_device();
             loads_upload_ref(s, ref_point);
-            if (heat) ensure_loads_ring14(s); else ensure_loads_ring12(s);
-            if (s->L[0].n_wall_rec > 0) { if (heat) wall_plan_heat(s, s->L[0]); else wall_plan(s, s->L[0]); }
-            else std::fill(loads_out, loads_out + size_t(steps) * width, 0.0);      // (no solid wall: zeros, nothing launched)
+            ensure_loads_ring(s, kind);
+            wall = s->L[0].n_wall_rec > 0;
+            if (wall) loads_plan(s, s->L[0], kind);
+            else loads_rows(s, kind, false, loads_out, 0, size_t(steps), size_t(steps));     // (no solid wall: zeros, nothing launched)
         }
         s->dual_invalid_step = -1;
     });
@@ -6673,13 +6651,12 @@ static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double 
         double *rms = rms_out ? rms_out + size_t(step) * size_t(cycles_per_step) : nullptr;
         rc = mgcfd_dual_time_begin_step(s);
         if (rc == MGCFD_OK) rc = run_cycles_impl(s, cycles_per_step, rms, nullptr, nullptr);
-        if (rc == MGCFD_OK && loads_out && !friction) rc = mgcfd_surface_loads(s, 0, ref_point, loads_out + size_t(step) * 6);
         // the flow statistics: one sample of the completed step with weight dt, behind the loads launch
         const auto sample = [&] { if (s->stat_mode != MGCFD_STATISTICS_OFF) statistics_sample(s, s->dual_dt); };
-        if (rc == MGCFD_OK && loads_out && friction && s->L[0].n_wall_rec > 0) {
+        if (rc == MGCFD_OK && wall) {
             rc = guarded([&] {
                 s->use_device();
-                launch_loads_viscous(s, 0, (heat ? s->loads_ring14 : s->loads_ring12) + size_t(held) * width, heat);
+                launch_loads(s, 0, kind, LoadsDest::at(s->loads_ring[static_cast<int>(kind)] + size_t(held) * width));
                 sample();
             });
             if (rc == MGCFD_OK) held++;
@@ -6687,30 +6664,29 @@ static int advance_impl(mgcfd_solver *s, int steps, int cycles_per_step, double 
         }
         else if (rc == MGCFD_OK) rc = guarded(sample);
         if (rc == MGCFD_OK) continue;
-        if (friction && loads_out) (void)read_rows(step - 1);      // (the steps that completed keep their rows)
+        (void)read_rows(step - 1);                                 // (the steps that completed keep their rows)
         // as mgcfd_run_cycles: what did not complete is NaN (the failing step's RMS entries are already), later steps do not run
         if (rc >= MGCFD_ERR_NAN && rc <= MGCFD_ERR_NEG_ENERGY) s->dual_invalid_step = step;
         for (int k = step + 1; rms_out && k < steps; k++)
             for (int c = 0; c < cycles_per_step; c++) rms_out[size_t(k) * size_t(cycles_per_step) + size_t(c)] = nan;
-        for (int k = step; loads_out && k < steps; k++)
-            for (size_t c = 0; c < width; c++) loads_out[size_t(k) * width + c] = nan;
+        if (loads_out) loads_rows(s, kind, wall, loads_out, size_t(step), 0, size_t(steps));
         return rc;
     }
     return MGCFD_OK;
 }
 int mgcfd_advance(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
 {
-    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, false);
+    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, LoadsKind::Pressure);
 }
 int mgcfd_advance_loads_viscous(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
 {
     REQUIRE(loads_out);
-    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, true);
+    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, LoadsKind::Friction);
 }
 int mgcfd_advance_loads_heat(mgcfd_solver *s, int steps, int cycles_per_step, double *rms_out, double *loads_out, const double ref_point[3])
 {
     REQUIRE(loads_out);
-    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, true, true);
+    return advance_impl(s, steps, cycles_per_step, rms_out, loads_out, ref_point, LoadsKind::Heat);
 }
 
 } // extern "C"
